@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: trajectories/s for a batch of 10-segment min-snap paths.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's coefficients, segment times, status, cost and, for the
+nonlinear workload, samples) as DIR/<name>.npy in float64, so that two builds can be compared output for output.
 
 N = 1 runs in this process.  N > 1 without a torch.distributed environment starts N ranks itself:
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same arguments>`
@@ -108,7 +111,48 @@ def parse_args(argv=None):
     ap.add_argument("--shared-inputs", dest="distinct_slots", action="store_false",
                     help="every batch in flight reads slot 0's input arrays (the round-3 set-up; default: each slot has its own batch)")
     ap.add_argument("--config3-paths", type=int, default=CONFIG3_PATHS, help="size of the fixed batch of extras.config3")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (rank 0's batch) as "
+                         "DIR/<name>.npy, float64, at most DUMP_LIMIT_BYTES in all (a fixed, seeded sample of paths beyond that)")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240611
+
+
+def dump_outputs(directory, seg_offsets, per_segment, per_path, limit_bytes=DUMP_LIMIT_BYTES, seed=DUMP_SAMPLE_SEED):
+    """Write the arrays of one step as directory/<name>.npy in float64.  per_segment: {name: array with one leading row per
+    segment}, per_path: {name: array with one leading row per path}.  When all of them together exceed limit_bytes, the same
+    rows of every array are kept for a fixed, seeded sample of paths (all segments of a sampled path).  path_index.npy names
+    the paths written.  Returns {name: shape}."""
+    import numpy as np
+    seg_offsets = np.asarray(seg_offsets, dtype=np.int64)
+    n_paths = len(seg_offsets) - 1
+    per_segment = {k: np.asarray(v) for k, v in per_segment.items()}
+    per_path = {k: np.asarray(v) for k, v in per_path.items()}
+    for k, v in per_segment.items():
+        assert v.shape[0] == seg_offsets[-1], (k, v.shape)
+    for k, v in per_path.items():
+        assert v.shape[0] == n_paths, (k, v.shape)
+    seg_bytes = np.diff(seg_offsets) * sum(8 * int(np.prod(v.shape[1:])) for v in per_segment.values())
+    path_bytes = seg_bytes + 8 + sum(8 * int(np.prod(v.shape[1:])) for v in per_path.values())   # (+ path_index)
+    paths = np.arange(n_paths)
+    if path_bytes.sum() > limit_bytes:
+        order = np.random.default_rng(seed).permutation(n_paths)
+        keep = int(np.searchsorted(np.cumsum(path_bytes[order]), limit_bytes, side="right"))
+        paths = np.sort(order[:keep])
+    rows = np.concatenate([np.arange(seg_offsets[p], seg_offsets[p + 1]) for p in paths]) if len(paths) else np.zeros(0, np.int64)
+    arrays = {"path_index": paths}
+    arrays.update({k: v[rows] for k, v in per_segment.items()})
+    arrays.update({k: v[paths] for k, v in per_path.items()})
+    os.makedirs(directory, exist_ok=True)
+    shapes = {}
+    for k, v in arrays.items():
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        np.save(os.path.join(directory, k + ".npy"), v)
+        shapes[k] = list(v.shape)
+    return shapes
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -687,6 +731,26 @@ def main():
     value = total_paths / elapsed
     own_regions_main = list(LAST_OWN_REGIONS[0])   # this rank's own regions (later measurements overwrite the global)
     own_elapsed_main = median_of(own_regions_main)
+    # --dump-outputs: the arrays the last timed step handed back (its slot's outputs), copied before any later measurement
+    # writes that slot again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        torch.cuda.synchronize()
+        slot = last_slot[0][0]
+        if args.workload == "linear":
+            per_segment = dict(coeffs=out_coeffs[slot], seg_times=slot_inputs(slot)[2])
+            per_path = dict(status=status_i32[slot], cost=slot_cost[slot])
+        else:
+            n_samp = slot_nsamp[slot].cpu().numpy()
+            samples = slot_samples[slot].cpu().numpy().copy()
+            # (rows beyond a path's sample count are not part of its result)
+            samples[np.arange(samples.shape[1])[None, :] >= np.minimum(n_samp, samples.shape[1])[:, None]] = 0.0
+            per_segment = dict(coeffs=out_coeffs[slot], seg_times=out_times[slot])
+            per_path = dict(status=status_i32[slot], cost=slot_cost[slot], n_samples=n_samp, samples=samples)
+        per_segment = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in per_segment.items()}
+        per_path = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in per_path.items()}
+        dumped = dict(directory=os.path.abspath(args.dump_outputs), slot=slot,
+                      arrays=dump_outputs(args.dump_outputs, batch.seg_offsets, per_segment, per_path))
     # what every rank saw, so that a first multi-GPU curve can be read from the line alone: its own K-step time, the device it
     # ran on, and whether the dmabuf IPC mode the pool's driver needs was set in its environment
     props = torch.cuda.get_device_properties(dev)
@@ -1429,7 +1493,7 @@ def main():
                     in_flight_slots_vs_cpu_ref=(slots_checked if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None),
                     rccl_version=rccl_version,
                     roofline=roofline, roofline_headline=roofline_headline, roofline_solve=roofline_solve,
-                    roofline_outer_loop=roofline_outer, cpu_baseline=cpu, extras=extras)
+                    roofline_outer_loop=roofline_outer, cpu_baseline=cpu, extras=extras, dump_outputs=dumped)
         import ctypes
         ctypes.CDLL(None).fflush(None)   # RCCL's banner sits in C stdio: keep the JSON line the last thing printed
         print(json.dumps(line), flush=True)
