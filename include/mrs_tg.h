@@ -164,7 +164,9 @@ enum {
 
 /* mrs_tg_capabilities(): what this build of the library contains beyond the mandatory surface */
 enum {
-  MRS_TG_CAP_CAREFUL_COST = 1 /* MRS_TG_FLAG_CAREFUL_COST is honoured (optimize_careful_kernel is built in) */
+  MRS_TG_CAP_CAREFUL_COST = 1, /* MRS_TG_FLAG_CAREFUL_COST is honoured (optimize_careful_kernel is built in) */
+  MRS_TG_CAP_FUTURE_PATHS = 2  /* the initial condition of paths stamped in the future: mrs_tg_prepare_initial_condition and
+                                  mrs_tg_splice_prediction are exported */
 };
 
 typedef struct mrs_tg_options {
@@ -477,7 +479,8 @@ void mrs_tg_default_policy_options(mrs_tg_policy_options* opt);
 /* MrsTrajectoryGeneration::optimize() (src/mrs_trajectory_generation.cpp:620-851) for n_paths independent
  * paths: preprocessPath, solve (all still-active paths of a round in ONE batched GPU call), Baca length
  * sanity check, validateTrajectorySpatial, mid-point insertion into unsafe segments, re-solve -- up to
- * max_deviation_iterations rounds.  ROS-only branches (tf, stamps, prediction splicing, overtime) are absent.
+ * max_deviation_iterations rounds.  Tf is absent; the initial condition of stamped paths and the prediction splice are
+ * mrs_tg_prepare_initial_condition / mrs_tg_splice_prediction below, around this call.
  *   wp_offsets [n_paths+1] CSR over `waypoints`; the first waypoint of a path is its initial condition when
  *   has_initial_state[p] != 0 (then initial_states[p] supplies the derivatives, :946-957).
  *   limits [n_paths][9]; relax_heading [n_paths] or NULL.
@@ -495,6 +498,46 @@ int mrs_tg_optimize_paths(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* wp_of
 /* getWaypointInTrajectoryIdxs (src/...cpp:1461-1499) for one path; returns the number of indices written. */
 int32_t mrs_tg_waypoint_trajectory_idxs(const double* samples, int32_t n_samples, const mrs_tg_waypoint* waypoints,
                                         int32_t n_waypoints, int32_t* idxs_out);
+
+/* ---- initial condition: paths stamped in the future, before takeoff ------------------------ */
+
+/* mrs_msgs::MpcPredictionFullState of the tracker command, already transformed into the path's frame.  Row i of each array is
+ * sample i of the MPC horizon (a first step of 0.01 s, then 0.2 s steps); n_samples = 0 (arrays may be NULL): no prediction. */
+typedef struct mrs_tg_prediction {
+  int32_t n_samples;
+  const double* position;     /* [n_samples][4] x, y, z, heading */
+  const double* velocity;     /* [n_samples][4] xyz + heading_rate */
+  const double* acceleration; /* [n_samples][4] xyz + heading_acceleration */
+  const double* jerk;         /* [n_samples][4] xyz + heading_jerk */
+} mrs_tg_prediction;
+
+/* prepareInitialCondition (src/mrs_trajectory_generation.cpp:506-614) with the first-waypoint rule of optimize() (:650-655) for
+ * one request.  Host arithmetic, no device, no context.  All times in seconds, differences the caller took from ONE clock read:
+ *   tracker_pose + tracker_state: the tracker command (both NULL: none); tracker_age_s = now - its stamp (> 1.0: stale, :518);
+ *   prediction: its full_state_prediction (NULL: none); uav_pose4: x, y, z, heading of the UAV state (NULL: none);
+ *   path_time_offset_s = path stamp - now (0 for an unstamped path); n_path_waypoints: the request's waypoints (loop point
+ *   included); dont_prepend: dont_prepend_current_state.
+ * The first case that holds decides:
+ *   dont_prepend                         -> no initial condition;
+ *   no tracker command, or a stale one   -> the UAV state with z + takeoff_height, derivatives 0 (no UAV state: none);
+ *   offset > 0.2 and k <= n_samples - 1  -> prediction row k, from the future; k = int(ceil((offset * 0.5 - 0.01) / 0.2)) + 1;
+ *   otherwise                            -> the tracker command (k is still reported when offset > 0.2).
+ * *drop_first_waypoint_out = offset > 0.2 and n_path_waypoints >= 2, whatever the case.  A path from the future is sampled at
+ * 0.2 s and gets mrs_tg_splice_prediction after its solve.  Returns MRS_TG_OK or MRS_TG_ERR_INVALID_ARG. */
+int mrs_tg_prepare_initial_condition(const mrs_tg_waypoint* tracker_pose, const mrs_tg_initial_state* tracker_state,
+                                     double tracker_age_s, const mrs_tg_prediction* prediction, const double* uav_pose4,
+                                     double takeoff_height, double path_time_offset_s, int32_t n_path_waypoints,
+                                     int32_t dont_prepend, mrs_tg_waypoint* initial_waypoint_out,
+                                     mrs_tg_initial_state* initial_state_out, int32_t* has_initial_condition_out,
+                                     int32_t* from_future_out, int32_t* sample_offset_out, int32_t* drop_first_waypoint_out);
+
+/* The pre-trajectory of a path from the future (:801-838): with k = sample_offset and k2 = int(floor((prediction_age_s - 0.01)
+ * / 0.2)) + 1, where prediction_age_s = now - the stamp of the prediction held after the solve, prediction rows 0 .. k-1
+ * (position + heading) are inserted in front of samples [n_samples][4] when k > k2.  Returns the spliced sample count
+ * (n_samples when nothing is inserted); writes only when that fits sample_capacity.  MRS_TG_ERR_INVALID_ARG when the
+ * prediction has fewer than k rows. */
+int32_t mrs_tg_splice_prediction(const mrs_tg_prediction* prediction, int32_t sample_offset, double prediction_age_s,
+                                 double* samples, int32_t n_samples, int32_t sample_capacity);
 
 #ifdef __cplusplus
 }

@@ -79,6 +79,11 @@ class InitialState(C.Structure):
                 ("jerk", C.c_double * 4)]
 
 
+class Prediction(C.Structure):
+    _fields_ = [("n_samples", C.c_int32), ("position", C.c_void_p), ("velocity", C.c_void_p),
+                ("acceleration", C.c_void_p), ("jerk", C.c_void_p)]
+
+
 EXPORTED_SYMBOLS = [
     "mrs_tg_create", "mrs_tg_destroy", "mrs_tg_last_error", "mrs_tg_abi_version", "mrs_tg_capabilities", "mrs_tg_default_options",
     "mrs_tg_kernel_trace_reset", "mrs_tg_kernel_trace", "mrs_tg_plan_explain",
@@ -93,6 +98,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_default_policy_options", "mrs_tg_optimize_paths", "mrs_tg_waypoint_trajectory_idxs",
     "mrs_tg_create_multi", "mrs_tg_destroy_multi", "mrs_tg_multi_n_devices", "mrs_tg_multi_context", "mrs_tg_multi_shard",
     "mrs_tg_multi_solve_batch", "mrs_tg_multi_last_error",
+    "mrs_tg_prepare_initial_condition", "mrs_tg_splice_prediction",
 ]
 
 _lib = None
@@ -216,11 +222,18 @@ def load_library():
     L.mrs_tg_multi_solve_batch.argtypes = [vp, C.c_int32, ip, dp, bp, dp, dp, C.POINTER(Options), dp, dp, ip, dp, ip, dp]
     L.mrs_tg_multi_last_error.restype = C.c_char_p
     L.mrs_tg_multi_last_error.argtypes = [vp]
+    L.mrs_tg_prepare_initial_condition.restype = C.c_int
+    L.mrs_tg_prepare_initial_condition.argtypes = [C.POINTER(Waypoint), C.POINTER(InitialState), C.c_double, C.POINTER(Prediction),
+                                                   dp, C.c_double, C.c_double, C.c_int32, C.c_int32, C.POINTER(Waypoint),
+                                                   C.POINTER(InitialState), ip, ip, ip, ip]
+    L.mrs_tg_splice_prediction.restype = C.c_int32
+    L.mrs_tg_splice_prediction.argtypes = [C.POINTER(Prediction), C.c_int32, C.c_double, dp, C.c_int32, C.c_int32]
     _lib = L
     return L
 
 
 CAP_CAREFUL_COST = 1   # MRS_TG_CAP_CAREFUL_COST
+CAP_FUTURE_PATHS = 2   # MRS_TG_CAP_FUTURE_PATHS: prepare_initial_condition / splice_prediction
 
 
 def capabilities():
@@ -261,6 +274,77 @@ def estimate_times_baca(waypoints, limits9):
     if rc != 0:
         raise MrsTgError("mrs_tg_estimate_times_baca failed (%d)" % rc)
     return out
+
+
+def _prediction(prediction):
+    """(Prediction, arrays kept alive) from a dict of [n][4] arrays position / velocity / acceleration / jerk, or None"""
+    if prediction is None:
+        return None, ()
+    arrs = [np.ascontiguousarray(prediction[k], dtype=np.float64).reshape(-1, 4)
+            for k in ("position", "velocity", "acceleration", "jerk")]
+    n = arrs[0].shape[0]
+    if any(a.shape[0] != n for a in arrs):
+        raise ValueError("the prediction's four arrays need the same number of samples")
+    return Prediction(n, *(a.ctypes.data for a in arrs)), arrs
+
+
+def prepare_initial_condition(tracker=None, tracker_age=0.0, prediction=None, uav_pose=None, takeoff_height=0.0,
+                              path_time_offset=0.0, n_path_waypoints=1, dont_prepend=False):
+    """prepareInitialCondition (mrs_trajectory_generation.cpp:506-614) + the first-waypoint rule (:650-655) for one request
+    (mrs_tg_prepare_initial_condition; host arithmetic, no device).
+    tracker: None or a dict with "position" (x, y, z, heading) and "velocity" / "acceleration" / "jerk" (4 each, the 4th the
+    heading's); prediction: None or a dict of [n][4] arrays "position" / "velocity" / "acceleration" / "jerk";
+    uav_pose: None or (x, y, z, heading).  Returns a dict: has_initial_condition, from_future, sample_offset,
+    drop_first_waypoint, waypoint (4,) and initial_state (dict in optimize_paths' form) -- the latter two None without one."""
+    L = load_library()
+    pose = st = None
+    if tracker is not None:
+        pose = Waypoint()
+        st = InitialState()
+        for i in range(4):
+            pose.coords[i] = float(tracker["position"][i])
+            st.velocity[i] = float(tracker["velocity"][i])
+            st.acceleration[i] = float(tracker["acceleration"][i])
+            st.jerk[i] = float(tracker["jerk"][i])
+        st.heading = float(tracker["position"][3])
+    pred, _keep = _prediction(prediction)
+    uav = None if uav_pose is None else np.ascontiguousarray(uav_pose, dtype=np.float64).reshape(4)
+    wp_out, st_out = Waypoint(), InitialState()
+    flags = np.zeros(4, dtype=np.int32)
+    rc = L.mrs_tg_prepare_initial_condition(C.byref(pose) if pose is not None else None, C.byref(st) if st is not None else None,
+                                            float(tracker_age), C.byref(pred) if pred is not None else None, _np_ptr(uav),
+                                            float(takeoff_height), float(path_time_offset), int(n_path_waypoints), int(bool(dont_prepend)),
+                                            C.byref(wp_out), C.byref(st_out), flags[0:].ctypes.data, flags[1:].ctypes.data,
+                                            flags[2:].ctypes.data, flags[3:].ctypes.data)
+    if rc != 0:
+        raise MrsTgError("mrs_tg_prepare_initial_condition failed (%d): %s" % (rc, L.mrs_tg_last_error(None).decode()))
+    has = bool(flags[0])
+    return dict(has_initial_condition=has, from_future=bool(flags[1]), sample_offset=int(flags[2]),
+                drop_first_waypoint=bool(flags[3]),
+                waypoint=np.array(wp_out.coords[:]) if has else None,
+                initial_state=dict(heading=st_out.heading, velocity=np.array(st_out.velocity[:]),
+                                   acceleration=np.array(st_out.acceleration[:]), jerk=np.array(st_out.jerk[:])) if has else None)
+
+
+def splice_prediction(prediction, sample_offset, prediction_age, samples, sample_capacity=None):
+    """The pre-trajectory of a path from the future (mrs_trajectory_generation.cpp:801-838, mrs_tg_splice_prediction): returns
+    a new [m][4] array -- prediction rows 0 .. sample_offset-1 in front of samples [n][4] when sample_offset exceeds the
+    prediction's current index, else samples unchanged.  sample_capacity (default: room for the whole prediction) is the
+    buffer handed to the library; when the result does not fit, MrsTgError names the count needed."""
+    L = load_library()
+    pred, _keep = _prediction(prediction)
+    smp = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1, 4)
+    n = smp.shape[0]
+    cap = n + (pred.n_samples if pred is not None else 0) if sample_capacity is None else int(sample_capacity)
+    buf = np.zeros((max(cap, n, 1), 4))
+    buf[:n] = smp
+    m = L.mrs_tg_splice_prediction(C.byref(pred) if pred is not None else None, int(sample_offset), float(prediction_age),
+                                   _np_ptr(buf), n, cap)
+    if m < 0:
+        raise MrsTgError("mrs_tg_splice_prediction failed (%d): %s" % (m, L.mrs_tg_last_error(None).decode()))
+    if m > cap:
+        raise MrsTgError("mrs_tg_splice_prediction: %d samples need a capacity of %d, not %d" % (m, m, cap))
+    return buf[:m].copy()
 
 
 def default_options(**overrides):

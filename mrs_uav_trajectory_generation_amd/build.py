@@ -16,7 +16,8 @@ LIB = os.path.join(HERE, "libmrs_tg.so")
 SOURCES = ["mrs_tg_kernels.hip", "mrs_tg_tile.hip", "mrs_tg_rows.hip", "mrs_tg_quad.hip", "mrs_tg_general.hip", "mrs_tg_nonlinear.hip", "mrs_tg_wave.hip", "mrs_tg_dfo.hip", "mrs_tg_abi.hip", "mrs_tg_multi.hip", "mrs_tg_policy.hip", "mrs_tg_policy_dev.hip",
            "mrs_tg_pool.hip"]
 # every header under csrc/ (a header that is split or added is picked up without editing this file) + the public ABI
-HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [os.path.join("..", "..", "include", "mrs_tg.h")]
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + \
+    [os.path.join("..", "..", "include", h) for h in ("mrs_tg.h", "mrs_tg_initial_condition.hpp")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # the careful re-run of MRS_TG_FLAG_CAREFUL_COST (optimize_careful_kernel) is built in unless MRS_TG_WITH_CAREFUL=0 is set in the
 # environment of the build (mrs_tg_capabilities() reports which library is loaded)

@@ -26,6 +26,7 @@
 #include "mrs_tg_launch.h"
 #include "mrs_tg_nonlinear.h"
 #include "mrs_tg_policy_host.hpp"
+#include "../../include/mrs_tg_initial_condition.hpp"
 
 namespace {
 
@@ -212,7 +213,43 @@ extern "C" {
 
 int mrs_tg_abi_version(void) { return MRS_TG_ABI_VERSION; }
 
-int mrs_tg_capabilities(void) { return mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0; }
+int mrs_tg_capabilities(void) {
+  return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS;
+}
+
+// prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
+int mrs_tg_prepare_initial_condition(const mrs_tg_waypoint* tracker_pose, const mrs_tg_initial_state* tracker_state,
+                                     double tracker_age_s, const mrs_tg_prediction* prediction, const double* uav_pose4,
+                                     double takeoff_height, double path_time_offset_s, int32_t n_path_waypoints,
+                                     int32_t dont_prepend, mrs_tg_waypoint* initial_waypoint_out,
+                                     mrs_tg_initial_state* initial_state_out, int32_t* has_initial_condition_out,
+                                     int32_t* from_future_out, int32_t* sample_offset_out, int32_t* drop_first_waypoint_out) {
+  if (!initial_waypoint_out || !initial_state_out || !has_initial_condition_out || !from_future_out || !sample_offset_out ||
+      !drop_first_waypoint_out)
+    return mrs_tg::report_error(nullptr, MRS_TG_ERR_INVALID_ARG, "mrs_tg_prepare_initial_condition: every output is required");
+  mrs_tg::initial_condition::Decision d;
+  const char* why = "";
+  const int rc = mrs_tg::initial_condition::prepare(tracker_pose, tracker_state, tracker_age_s, prediction, uav_pose4, takeoff_height,
+                                                    path_time_offset_s, n_path_waypoints, dont_prepend != 0, &d, &why);
+  if (rc != MRS_TG_OK) return mrs_tg::report_error(nullptr, rc, "mrs_tg_prepare_initial_condition: %s", why);
+  *initial_waypoint_out = d.waypoint;
+  *initial_state_out = d.state;
+  *has_initial_condition_out = d.has_initial_condition ? 1 : 0;
+  *from_future_out = d.from_future ? 1 : 0;
+  *sample_offset_out = d.sample_offset;
+  *drop_first_waypoint_out = d.drop_first_waypoint ? 1 : 0;
+  return MRS_TG_OK;
+}
+
+// the pre-trajectory of a path from the future (:801-838)
+int32_t mrs_tg_splice_prediction(const mrs_tg_prediction* prediction, int32_t sample_offset, double prediction_age_s,
+                                 double* samples, int32_t n_samples, int32_t sample_capacity) {
+  const char* why = "";
+  const int32_t n = mrs_tg::initial_condition::splice(prediction, sample_offset, prediction_age_s, samples, n_samples,
+                                                      sample_capacity, &why);
+  if (n < 0) return mrs_tg::report_error(nullptr, n, "mrs_tg_splice_prediction: %s", why);
+  return n;
+}
 
 void mrs_tg_kernel_trace_reset(void) { mrs_tg::kernel_trace_reset(); }
 

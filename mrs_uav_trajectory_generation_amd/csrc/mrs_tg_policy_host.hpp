@@ -8,8 +8,8 @@
 // No HIP type or call appears here: mrs_tg_policy.hip instantiates optimize_paths() with the batched GPU solve and
 // mrs_tg_abi.hip's mrs_tg_find_trajectory uses the vertex builder, the Baca total and the two gates; the same header compiles
 // with g++ and is driven by tests/host/policy_host_harness.cpp with the CPU oracle as the solver on 16 threads under
-// ASan / UBSan / TSan (tests/test_host_sanitizers.py).  ROS-only branches (tf, stamps, "path from the future", MPC
-// prediction splicing) have no counterpart.
+// ASan / UBSan / TSan (tests/test_host_sanitizers.py).  Tf has no counterpart; the initial condition of stamped paths ("path
+// from the future", before takeoff) and the MPC prediction splice happen around this layer, in include/mrs_tg_initial_condition.hpp.
 #pragma once
 
 #include <algorithm>
