@@ -160,13 +160,30 @@ enum {
                                          stretched 25-fold by a perfectly healthy scaling, and the reference never checks a
                                          trajectory shorter than one second.  Coefficients, times and samples are the same bits
                                          with and without the flag */
+  ,
+  MRS_TG_FLAG_REFINE = 256            /* every mode: after the final linear solve, each path with status > 0 is refined at its
+                                         returned segment times (mrs_tg_refine.hip): vertex derivatives held in double-double,
+                                         the residual of the free slots formed in double-double from exact unit-time constants,
+                                         corrections solved in double (one factorisation, at most 3 steps, a step kept only if
+                                         it lowered the residual), coefficients formed in double-double and rounded once, the
+                                         cost recomputed.  R_pp's condition number grows like (T_max / T_min)^7 between
+                                         neighbouring segments; without the flag such a path (a 0.18 s segment between 4 s ones)
+                                         is 1e-8 off, with it 1e-11 or better.  What is refined: coeffs and cost.  What is not:
+                                         segment times, status, and the time-allocation search's own evaluations -- times and
+                                         status are bit-identical to the same call without the flag and without sampling;
+                                         samples are taken from the refined coefficients.  Cost: one more kernel per call,
+                                         12-31 times the solve it follows (10240 x 10: 446 us after a 31 us solve), and a
+                                         workspace of 2080 bytes per path per vertex of the plan's longest path, kept by the plan
+                                         (65536 x 10: 1.5 GB).  Refused with MRS_TG_ERR_UNSUPPORTED by
+                                         mrs_tg_bound_solve_launch_group */
 };
 
 /* mrs_tg_capabilities(): what this build of the library contains beyond the mandatory surface */
 enum {
   MRS_TG_CAP_CAREFUL_COST = 1, /* MRS_TG_FLAG_CAREFUL_COST is honoured (optimize_careful_kernel is built in) */
-  MRS_TG_CAP_FUTURE_PATHS = 2  /* the initial condition of paths stamped in the future: mrs_tg_prepare_initial_condition and
+  MRS_TG_CAP_FUTURE_PATHS = 2, /* the initial condition of paths stamped in the future: mrs_tg_prepare_initial_condition and
                                   mrs_tg_splice_prediction are exported */
+  MRS_TG_CAP_REFINE = 4        /* MRS_TG_FLAG_REFINE is honoured (refine_kernel is built in) */
 };
 
 typedef struct mrs_tg_options {

@@ -60,6 +60,7 @@ public:
   TrajectoryGenerator(const TrajectoryGenerator&) = delete;
   TrajectoryGenerator& operator=(const TrajectoryGenerator&) = delete;
 
+  // (options().flags reaches every call as it is: options().flags |= MRS_TG_FLAG_REFINE refines the final solve)
   mrs_tg_options& options() { return opt_; }
 
   // nullopt = failure, exactly where the reference returns {}: a rejected optimiser code (:1146-1149) and a sampled

@@ -106,7 +106,8 @@ struct ServiceParams {  // config/{public,private}/trajectory_generation.yaml
   int sample_capacity = 8192;            // capacity of one trajectory in samples (host buffer size, not a reference parameter)
   double takeoff_height = 0;             // mrs_uav_managers/uav_manager/takeoff/takeoff_height [m]: the start before takeoff
   bool require_uav_state = false;        // answer "missing UAV state" without one, as the nodelet does (:1996, :2224)
-  mrs_tg_policy_options policy{};        // everything optimize() / findTrajectory() read
+  mrs_tg_policy_options policy{};        // everything optimize() / findTrajectory() read (policy.solver.flags reaches the
+                                         // library as it is: policy.solver.flags |= MRS_TG_FLAG_REFINE refines the final solve)
   ServiceParams() {
     mrs_tg_default_policy_options(&policy);
     policy.solver.time_alloc_method = MRS_TG_TIME_ALLOC_MELLINGER;  // time_allocation: 2

@@ -33,6 +33,7 @@ FLAG_SHARED_DEVICE = 4         # hint: several batches are in flight on this dev
 FLAG_POSITIONS_ARE_WAYPOINTS = 32   # every vertex's position constraint is its waypoint (checked at bind time): read the compact array
 FLAG_REFERENCE_STATUS = 128         # Mellinger: the outer loop's own code, no runaway rule (MRS_TG_FLAG_REFERENCE_STATUS)
 FLAG_CONSTRAINED_SLOTS = 64         # hint: interior vertices may hold constrained derivative slots (stop_at) under min-snap
+FLAG_REFINE = 256                   # refine the final solve's coefficients and cost (double-double residual; MRS_TG_FLAG_REFINE)
 
 STATUS_ROUNDOFF_LIMITED = -4   # MRS_TG_STATUS_ROUNDOFF_LIMITED: the feasibility scaling ran away (include/mrs_tg.h)
 RUNAWAY_TIME_FACTOR = 25.0     # MRS_TG_RUNAWAY_TIME_FACTOR
@@ -234,6 +235,7 @@ def load_library():
 
 CAP_CAREFUL_COST = 1   # MRS_TG_CAP_CAREFUL_COST
 CAP_FUTURE_PATHS = 2   # MRS_TG_CAP_FUTURE_PATHS: prepare_initial_condition / splice_prediction
+CAP_REFINE = 4         # MRS_TG_CAP_REFINE: FLAG_REFINE is honoured
 
 
 def capabilities():

@@ -214,7 +214,7 @@ extern "C" {
 int mrs_tg_abi_version(void) { return MRS_TG_ABI_VERSION; }
 
 int mrs_tg_capabilities(void) {
-  return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS;
+  return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -529,6 +529,10 @@ int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
     ~ConstrainedSlotsScope() { mrs_tg::set_constrained_slots_hint(false); }
   } slots_scope((opt->flags & MRS_TG_FLAG_CONSTRAINED_SLOTS) != 0);
   bool sampled = false;  // the sampling rode on the final solve's launch
+  // MRS_TG_FLAG_REFINE: the refinement pass follows the final solve, so no sampling rides on a solve launch -- the solves go
+  // out exactly as in the same call without sampling, and the sampler reads the refined coefficients
+  const bool refine = (opt->flags & MRS_TG_FLAG_REFINE) != 0;
+  const double solve_sampling_dt = refine ? 0.0 : opt->sampling_dt;
   // (the Mellinger pipeline takes the estimate as its start point itself: mrs_tg::NonlinearParams::estimate_wp)
   if (opt->estimate_times && opt->time_alloc_method != MRS_TG_TIME_ALLOC_MELLINGER)
     HIP_TRY(ctx, mrs_tg::launch_estimate_times(b, wp, limits, seg_times, ctx->stream));
@@ -571,7 +575,7 @@ int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
     prm.reference_status = (opt->flags & MRS_TG_FLAG_REFERENCE_STATUS) != 0;
     ProfileScope ps(ctx, 2);
     HIP_TRY(ctx, mrs_tg::launch_nonlinear(plan->nl, b, prm, mask, vals, limits, seg_times, coeffs, status, cost, ctx->stream,
-                                          opt->sampling_dt, opt->sample_capacity, n_samples, samples, &sampled,
+                                          solve_sampling_dt, opt->sample_capacity, n_samples, samples, &sampled,
                                           (opt->flags & MRS_TG_FLAG_GENERAL_PATTERNS) != 0));
   } else {
     const bool fused = (opt->flags & MRS_TG_FLAG_MATERIALIZED_BLOCKS) == 0;  // the default since ABI 2
@@ -585,7 +589,7 @@ int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
       HIP_TRY(ctx, mrs_tg::launch_assemble(b, d, seg_times, plan->d_H, plan->d_Ainv, ctx->stream));
     }
     ProfileScope ps(ctx, 1);
-    if (fused && !general && opt->sampling_dt > 0 && mrs_tg::rows_tail_sampling_pays(b)) {  // solve and sample in one launch
+    if (fused && !general && solve_sampling_dt > 0 && mrs_tg::rows_tail_sampling_pays(b)) {  // solve and sample in one launch
       mrs_tg::RowsTail tail;
       tail.sampling_dt = opt->sampling_dt;
       tail.sample_capacity = opt->sample_capacity;
@@ -600,6 +604,10 @@ int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
     // the paths the fast kernels sent back with status -2 (a vertex without a position constraint): 5 x 5 vertex blocks
     if (general)
       HIP_TRY(ctx, mrs_tg::launch_solve_general(b, d, mask, vals, seg_times, plan->d_ws, coeffs, status, cost, ctx->stream));
+  }
+  if (refine) {  // every mode's final solve: the paths with status > 0 at the returned times (the dry run allocates nothing)
+    if (!mrs_tg::dry_run() && (rc = ensure_ws(plan, mrs_tg::refine_workspace_doubles(b))) != MRS_TG_OK) return rc;
+    HIP_TRY(ctx, mrs_tg::launch_refine(b, d, mask, vals, seg_times, plan->d_ws, coeffs, status, cost, ctx->stream));
   }
   if (opt->sampling_dt > 0 && !sampled)
     HIP_TRY(ctx, mrs_tg::launch_sample(b, coeffs, seg_times, opt->sampling_dt, opt->sample_capacity, n_samples, samples,
@@ -836,6 +844,8 @@ int mrs_tg_bound_solve_launch_group(mrs_tg_bound_solve* const* bound, int32_t n_
     const mrs_tg_bound_solve* b = bound[i];
     mrs_tg_ctx* ctx = b->plan->ctx;
     const mrs_tg_options& o = b->opt;
+    if (o.flags & MRS_TG_FLAG_REFINE)
+      return fail(ctx, MRS_TG_ERR_UNSUPPORTED, "grouped launches do not take MRS_TG_FLAG_REFINE (solve %d sets it)", i);
     if (o.time_alloc_method != MRS_TG_TIME_ALLOC_NONE || o.estimate_times || o.sampling_dt > 0 ||
         (o.flags & (MRS_TG_FLAG_MATERIALIZED_BLOCKS | MRS_TG_FLAG_GENERAL_PATTERNS)))
       return fail(ctx, MRS_TG_ERR_UNSUPPORTED, "grouped launches are for the fixed-times default solve without sampling (solve %d differs)", i);

@@ -167,6 +167,11 @@ size_t general_workspace_doubles(const BatchView& b);
 hipError_t launch_solve_general(const BatchView& b, int d, const uint8_t* mask, const double* vals, const double* seg_times,
                                 double* ws, double* coeffs, int32_t* status, double* cost, hipStream_t stream,
                                 const int32_t* only = nullptr, const int32_t* opt_status = nullptr);
+// MRS_TG_FLAG_REFINE (mrs_tg_refine.hip): every path with status > 0 refined at its segment times -- coeffs and cost (may be
+// NULL) rewritten, seg_times and status read only; per-lane factors and iterates in `ws` (refine_workspace_doubles)
+size_t refine_workspace_doubles(const BatchView& b);
+hipError_t launch_refine(const BatchView& b, int d, const uint8_t* mask, const double* vals, const double* seg_times, double* ws,
+                         double* coeffs, const int32_t* status, double* cost, hipStream_t stream);
 // phase-split tile kernel (mrs_tg_tile.hip): small and medium batches whose per-path state fits in LDS
 bool tile_kernel_applies(const BatchView& b, bool fused);
 hipError_t launch_solve_tile(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,
