@@ -183,7 +183,8 @@ enum {
   MRS_TG_CAP_CAREFUL_COST = 1, /* MRS_TG_FLAG_CAREFUL_COST is honoured (optimize_careful_kernel is built in) */
   MRS_TG_CAP_FUTURE_PATHS = 2, /* the initial condition of paths stamped in the future: mrs_tg_prepare_initial_condition and
                                   mrs_tg_splice_prediction are exported */
-  MRS_TG_CAP_REFINE = 4        /* MRS_TG_FLAG_REFINE is honoured (refine_kernel is built in) */
+  MRS_TG_CAP_REFINE = 4,       /* MRS_TG_FLAG_REFINE is honoured (refine_kernel is built in) */
+  MRS_TG_CAP_GRADIENT = 8      /* mrs_tg_plan_solve_vjp is exported: the backward pass of the fixed-times solve */
 };
 
 typedef struct mrs_tg_options {
@@ -379,6 +380,22 @@ int mrs_tg_plan_cost_gradient(mrs_tg_plan* plan, int32_t derivative_to_optimize,
  * [segment][k-1][group]. */
 int mrs_tg_plan_segment_maxima(mrs_tg_plan* plan, const double* coeffs_dev, const double* seg_times_dev,
                                double* maxima_out_dev);
+/* Backward pass of the fixed-times solve (MRS_TG_CAP_GRADIENT; vjp_kernel): given what a
+ * mrs_tg_plan_solve with time_alloc_method = MRS_TG_TIME_ALLOC_NONE returned for (fixed_mask, fixed_values, seg_times) --
+ * coeffs_dev [sum S][4][10] and status_dev [n_paths] -- and the gradient of a loss L with respect to the coefficients
+ * (grad_coeffs_dev [sum S][4][10]) and the cost (grad_cost_dev [n_paths]), writes dL/dfixed_values
+ * (grad_fixed_values_out_dev [sum V][5][4]; 0 on the free slots) and dL/dseg_times (grad_seg_times_out_dev [sum S]).  The
+ * exact chain rule of the linear QP at the returned solution: the free slots of the vertices are those the coefficients hold,
+ * one adjoint solve with the same masked R_pp per path and dimension (a vanishing pivot leaves its multiplier at 0).  Any
+ * fixed / free pattern; derivative_to_optimize 0 .. 4 as for the solve.  At least one upstream array and one output must be
+ * given; a NULL upstream counts as zero, a NULL output is not written.  A path with status <= 0 gets zeros in all of its
+ * output rows.  Not differentiated: time allocation, feasibility scaling, limits, sampling.  Deterministic (no atomics).
+ * Device pointers in the caller's CSR order, asynchronous on the context's stream; per-lane factors in the plan's workspace
+ * (1440 bytes per path per vertex of the plan's longest path). */
+int mrs_tg_plan_solve_vjp(mrs_tg_plan* plan, int32_t derivative_to_optimize, const uint8_t* fixed_mask_dev,
+                          const double* fixed_values_dev, const double* seg_times_dev, const double* coeffs_dev,
+                          const int32_t* status_dev, const double* grad_coeffs_dev, const double* grad_cost_dev,
+                          double* grad_fixed_values_out_dev, double* grad_seg_times_out_dev);
 /* sampleWholeTrajectory with every field of the sampled state (sampleTrajectoryInRange, trajectory_sampling.cpp:49-104:
  * five evaluateRange passes over the same accumulate-and-carry walk, trajectory.cpp:93-151): for the trajectories given by
  * coeffs_dev [sum S][4][10] and seg_times_dev [sum S], states_out_dev [n_paths][sample_capacity][MRS_TG_STATE_ORDERS][4]
@@ -397,7 +414,8 @@ int mrs_tg_plan_sample_states(mrs_tg_plan* plan, const double* coeffs_dev, const
 
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
- * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop.
+ * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
+ * 3 backward pass (mrs_tg_plan_solve_vjp).
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

@@ -42,7 +42,7 @@ RUNAWAY_TIME_FACTOR = 25.0     # MRS_TG_RUNAWAY_TIME_FACTOR
 FIND_ACCEPTED, FIND_REJECTED_CODE, FIND_REJECTED_TOO_LONG, FIND_REJECTED_TOO_SHORT = 0, 1, 2, 3
 
 STATE_ORDERS = 5   # derivative orders 0..4 per sample of Plan.sample_states (MRS_TG_STATE_ORDERS)
-KERNEL_ASSEMBLE, KERNEL_SOLVE_LINEAR, KERNEL_NONLINEAR = 0, 1, 2
+KERNEL_ASSEMBLE, KERNEL_SOLVE_LINEAR, KERNEL_NONLINEAR, KERNEL_VJP = 0, 1, 2, 3
 
 
 class MrsTgError(RuntimeError):
@@ -99,7 +99,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_default_policy_options", "mrs_tg_optimize_paths", "mrs_tg_waypoint_trajectory_idxs",
     "mrs_tg_create_multi", "mrs_tg_destroy_multi", "mrs_tg_multi_n_devices", "mrs_tg_multi_context", "mrs_tg_multi_shard",
     "mrs_tg_multi_solve_batch", "mrs_tg_multi_last_error",
-    "mrs_tg_prepare_initial_condition", "mrs_tg_splice_prediction",
+    "mrs_tg_prepare_initial_condition", "mrs_tg_splice_prediction", "mrs_tg_plan_solve_vjp",
 ]
 
 _lib = None
@@ -185,6 +185,8 @@ def load_library():
     L.mrs_tg_plan_cost_gradient.argtypes = [vp, C.c_int32, bp, dp, dp, dp, dp]
     L.mrs_tg_plan_segment_maxima.restype = C.c_int
     L.mrs_tg_plan_segment_maxima.argtypes = [vp, dp, dp, dp]
+    L.mrs_tg_plan_solve_vjp.restype = C.c_int
+    L.mrs_tg_plan_solve_vjp.argtypes = [vp, C.c_int32, bp, dp, dp, dp, ip, dp, dp, dp, dp]
     L.mrs_tg_plan_careful_count.restype = C.c_int
     L.mrs_tg_plan_careful_count.argtypes = [vp, ip]
     L.mrs_tg_plan_sample_states.restype = C.c_int
@@ -236,6 +238,7 @@ def load_library():
 CAP_CAREFUL_COST = 1   # MRS_TG_CAP_CAREFUL_COST
 CAP_FUTURE_PATHS = 2   # MRS_TG_CAP_FUTURE_PATHS: prepare_initial_condition / splice_prediction
 CAP_REFINE = 4         # MRS_TG_CAP_REFINE: FLAG_REFINE is honoured
+CAP_GRADIENT = 8       # MRS_TG_CAP_GRADIENT: Plan.solve_vjp (the backward pass of the fixed-times solve)
 
 
 def capabilities():
@@ -779,6 +782,15 @@ class Plan:
     def segment_maxima(self, coeffs, seg_times, maxima):
         self.ctx._check(self._L.mrs_tg_plan_segment_maxima(self._h, _t_ptr(coeffs), _t_ptr(seg_times), _t_ptr(maxima)),
                         "mrs_tg_plan_segment_maxima")
+
+    def solve_vjp(self, derivative, fixed_mask, fixed_values, seg_times, coeffs, status, grad_coeffs=None, grad_cost=None,
+                  grad_fixed_values=None, grad_seg_times=None):
+        """mrs_tg_plan_solve_vjp: dL/dfixed_values and dL/dseg_times (device tensors, written) from dL/dcoeffs and dL/dcost
+        (NULL = zero) at what a fixed-times solve returned (coeffs, status); asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_solve_vjp(self._h, int(derivative), _t_ptr(fixed_mask), _t_ptr(fixed_values),
+                                                      _t_ptr(seg_times), _t_ptr(coeffs), _t_ptr(status), _t_ptr(grad_coeffs),
+                                                      _t_ptr(grad_cost), _t_ptr(grad_fixed_values), _t_ptr(grad_seg_times)),
+                        "mrs_tg_plan_solve_vjp")
 
     def careful_count(self):
         n = C.c_int32(0)

@@ -51,8 +51,9 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  std::vector<hipEvent_t> ev_start[3], ev_stop[3];
-  long long ev_count[3] = {0, 0, 0};   // timed launches since profiling was switched on
+  static constexpr int kTimedKernels = 4;  // kernel_id 0 .. 3 (mrs_tg_last_kernel_ms)
+  std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
+  long long ev_count[kTimedKernels] = {0, 0, 0, 0};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
   double wall_clock_hz = 1.0e8;  // rate of s_memrealtime (hipDeviceAttributeWallClockRate)
   // plan of the most recent mrs_tg_solve_batch: a caller that sends the same batch shape again (the nodelet's
@@ -214,7 +215,8 @@ extern "C" {
 int mrs_tg_abi_version(void) { return MRS_TG_ABI_VERSION; }
 
 int mrs_tg_capabilities(void) {
-  return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE;
+  return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE |
+         MRS_TG_CAP_GRADIENT;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -309,7 +311,7 @@ void mrs_tg_destroy(mrs_tg_ctx* ctx) {
     ctx->cached_plan = nullptr;
     mrs_tg_plan_destroy(p);
   }
-  for (int i = 0; i < 3; ++i) {
+  for (int i = 0; i < mrs_tg_ctx::kTimedKernels; ++i) {
     for (hipEvent_t e : ctx->ev_start[i])
       if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_stop[i])
@@ -349,13 +351,14 @@ int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled) {
   if (!ctx) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "ctx is NULL");
   ctx->profiling = enabled != 0;
   if (ctx->profiling)
-    for (int i = 0; i < 3; ++i) ctx->ev_count[i] = 0;  // a new series
+    for (int i = 0; i < mrs_tg_ctx::kTimedKernels; ++i) ctx->ev_count[i] = 0;  // a new series
   return MRS_TG_OK;
 }
 
 int mrs_tg_kernel_ms_history(mrs_tg_ctx* ctx, int kernel_id, float* ms_out, int capacity) {
   if (!ctx || (capacity > 0 && !ms_out)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "NULL argument");
-  if (kernel_id < 0 || kernel_id > 2) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "kernel id %d outside [0, 2]", kernel_id);
+  if (kernel_id < 0 || kernel_id >= mrs_tg_ctx::kTimedKernels)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "kernel id %d outside [0, %d]", kernel_id, mrs_tg_ctx::kTimedKernels - 1);
   const long long total = ctx->ev_count[kernel_id];
   long long n = total < mrs_tg_ctx::kTimerRing ? total : mrs_tg_ctx::kTimerRing;
   if (n > capacity) n = capacity;
@@ -370,7 +373,7 @@ int mrs_tg_kernel_ms_history(mrs_tg_ctx* ctx, int kernel_id, float* ms_out, int 
 
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out) {
   if (!ctx || !ms_out) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "NULL argument");
-  if (kernel_id < 0 || kernel_id > 2 || ctx->ev_count[kernel_id] == 0)
+  if (kernel_id < 0 || kernel_id >= mrs_tg_ctx::kTimedKernels || ctx->ev_count[kernel_id] == 0)
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "no timed launch recorded for kernel id %d (mrs_tg_set_profiling, then a call that runs that kernel)", kernel_id);
   const int n = mrs_tg_kernel_ms_history(ctx, kernel_id, ms_out, 1);
   return n == 1 ? MRS_TG_OK : n;
@@ -955,6 +958,27 @@ int mrs_tg_plan_segment_maxima(mrs_tg_plan* plan, const double* coeffs, const do
   mrs_tg_ctx* ctx = plan->ctx;
   HIP_TRY(ctx, use_device(ctx->device));
   HIP_TRY(ctx, mrs_tg::launch_segment_maxima(plan->view, coeffs, seg_times, maxima, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_solve_vjp(mrs_tg_plan* plan, int32_t d, const uint8_t* mask, const double* vals, const double* seg_times,
+                          const double* coeffs, const int32_t* status, const double* grad_coeffs, const double* grad_cost,
+                          double* grad_vals, double* grad_times) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!mask || !vals || !seg_times || !coeffs || !status)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "fixed_mask, fixed_values, seg_times, coeffs and status are required");
+  if (!grad_coeffs && !grad_cost) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_coeffs and grad_cost are both NULL");
+  if (!grad_vals && !grad_times)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_fixed_values_out and grad_seg_times_out are both NULL");
+  if (d < 0 || d > 4) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "derivative_to_optimize %d outside [0, 4]", d);
+  HIP_TRY(ctx, use_device(ctx->device));
+  const mrs_tg::BatchView& b = plan->view;
+  int rc = ensure_ws(plan, mrs_tg::vjp_workspace_doubles(b));
+  if (rc != MRS_TG_OK) return rc;
+  ProfileScope ps(ctx, 3);
+  HIP_TRY(ctx, mrs_tg::launch_vjp(b, d, mask, vals, seg_times, coeffs, status, grad_coeffs, grad_cost, plan->d_ws, grad_vals,
+                                  grad_times, ctx->stream));
   return MRS_TG_OK;
 }
 

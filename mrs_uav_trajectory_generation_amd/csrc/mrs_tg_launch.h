@@ -172,6 +172,13 @@ hipError_t launch_solve_general(const BatchView& b, int d, const uint8_t* mask, 
 size_t refine_workspace_doubles(const BatchView& b);
 hipError_t launch_refine(const BatchView& b, int d, const uint8_t* mask, const double* vals, const double* seg_times, double* ws,
                          double* coeffs, const int32_t* status, double* cost, hipStream_t stream);
+// mrs_tg_plan_solve_vjp (mrs_tg_vjp.hip): the backward pass of the fixed-times solve -- dL/dfixed_values and dL/dseg_times
+// (either may be NULL) from dL/dcoeffs and dL/dcost (either may be NULL = zero); reads only; per-lane factors in `ws`
+// (vjp_workspace_doubles); timed as the kernel family of the pending ProfileScope
+size_t vjp_workspace_doubles(const BatchView& b);
+hipError_t launch_vjp(const BatchView& b, int d, const uint8_t* mask, const double* vals, const double* seg_times,
+                      const double* coeffs, const int32_t* status, const double* grad_coeffs, const double* grad_cost, double* ws,
+                      double* grad_vals, double* grad_times, hipStream_t stream);
 // phase-split tile kernel (mrs_tg_tile.hip): small and medium batches whose per-path state fits in LDS
 bool tile_kernel_applies(const BatchView& b, bool fused);
 hipError_t launch_solve_tile(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,

@@ -1,0 +1,195 @@
+#!/usr/bin/env python3
+"""Generate tests/golden/vjp_cases.json: 60-digit gradients of the fixed-times solve for mrs_tg_plan_solve_vjp.
+
+The ground truth is NOT the adjoint formulas of DESIGN.md section 4c: it is central differences (step 1e-20) of the loss
+L = sum G . coeffs + g * cost through a dense KKT restatement of the linear QP in 60-digit mpmath, built from
+oracle/gen_golden.py's mapping / cost_matrix (nothing of that module is changed).  exact_solve itself rounds its fixed values
+through float, so it cannot be perturbed by 1e-20; the restatement takes mpf inputs and is checked against exact_solve at the
+unperturbed point to 1e-50.  G and g are dyadic (exact in double).  Every case stores the coefficients of the exact solution
+rounded to double (what a perfect forward returns: the input of the backward pass), G, g, the gradient for every segment time
+and for every fixed slot (0 on free slots).  Cases:
+
+  * d = 2, 3, 4 on 3- to 6-segment paths;
+  * free end derivatives (the end vertex constrains its position only) with an interior stop_at vertex;
+  * a vertex whose position is free;
+  * a 30-segment path: directional derivatives along three random directions in (times, fixed values) only;
+  * an ill-conditioned path: one segment 50 times shorter than its neighbours.
+
+Run from the repo root:  python3 tests/golden/gen_vjp_cases.py   (a few minutes: the 30-segment case dominates)
+"""
+import json
+import os
+import sys
+
+import mpmath as mp
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
+sys.path.insert(0, ROOT)
+from mrs_uav_trajectory_generation_amd import problem as pr  # noqa: E402
+from oracle.gen_golden import cost_matrix, euclid_times, exact_solve, mapping  # noqa: E402
+
+mp.mp.dps = 60
+N, D, B = 10, 4, 5
+STEP = mp.mpf("1e-20")
+OUT = os.path.join(ROOT, "tests", "golden", "vjp_cases.json")
+
+
+def kkt_solver(mask, times, d):
+    """The linear QP at the given (mpf) times: a function of the fixed values [V*5][4] (mpf) -> (coeffs [S][4][10], J)."""
+    S = len(times)
+    n_all = B * (S + 1)
+    flat = [int(x) for x in np.asarray(mask).reshape(-1)]
+    fixed = [i for i in range(n_all) if flat[i]]
+    free = [i for i in range(n_all) if not flat[i]]
+    R = mp.zeros(n_all, n_all)
+    Ainv, Hs = [], []
+    for i in range(S):
+        Ai = mp.inverse(mapping(times[i]))
+        H = Ai.T * cost_matrix(d, times[i]) * Ai
+        Ainv.append(Ai)
+        Hs.append(H)
+        for r in range(N):
+            for c in range(N):
+                R[B * i + r, B * i + c] += H[r, c]
+    if free:
+        Rpp = mp.matrix([[R[a, b] for b in free] for a in free])
+        Rpf = mp.matrix([[R[a, b] for b in fixed] for a in free]) if fixed else None
+        Rpp_inv = mp.inverse(Rpp)
+
+    def solve(vals):
+        dall = [[mp.mpf(0)] * D for _ in range(n_all)]
+        for i in fixed:
+            for k in range(D):
+                dall[i][k] = vals[i][k]
+        if free:
+            for k in range(D):
+                rhs = -(Rpf * mp.matrix([dall[i][k] for i in fixed])) if fixed else mp.zeros(len(free), 1)
+                sol = Rpp_inv * rhs
+                for r, i in enumerate(free):
+                    dall[i][k] = sol[r]
+        coeffs, J = [], mp.mpf(0)
+        for i in range(S):
+            seg = []
+            for k in range(D):
+                u = mp.matrix([dall[B * i + r][k] for r in range(N)])
+                seg.append(list(Ainv[i] * u))
+                J += (u.T * Hs[i] * u)[0, 0] / 2
+            coeffs.append(seg)
+        return coeffs, J
+    return solve
+
+
+def loss(coeffs, J, G, g):
+    s = mp.mpf(0)
+    for i, seg in enumerate(coeffs):
+        for k in range(D):
+            for j in range(N):
+                s += mp.mpf(G[i][k][j]) * seg[k][j]
+    return s + mp.mpf(g) * J
+
+
+def dyadic(rng, shape, denom):
+    return (rng.integers(-64, 65, size=shape) / denom).astype(np.float64)
+
+
+def record(name, mask, vals, times, d, seed, directional=0):
+    S = len(times)
+    n_all = B * (S + 1)
+    rng = np.random.default_rng(seed)
+    G = dyadic(rng, (S, D, N), 64.0)
+    g = float(rng.integers(1, 17)) / 8.0
+    tm = [mp.mpf(float(t)) for t in times]
+    vflat = np.asarray(vals, dtype=np.float64).reshape(n_all, D)
+    vm = [[mp.mpf(float(vflat[i, k])) for k in range(D)] for i in range(n_all)]
+    flat = np.asarray(mask).reshape(-1)
+    solve0 = kkt_solver(mask, tm, d)
+    c0, J0 = solve0(vm)
+    ce, Je, _, _ = exact_solve(mask, vals, [float(t) for t in times], d)   # (vals are doubles: exact_solve's rounding is exact)
+    scale = max(abs(x) for seg in ce for dim in seg for x in dim)
+    worst = max(abs(c0[i][k][j] - ce[i][k][j]) for i in range(S) for k in range(D) for j in range(N)) / scale
+    assert worst < mp.mpf("1e-50") and abs(J0 - Je) < mp.mpf("1e-50") * abs(Je), (name, worst)
+    rec = dict(name=name, derivative_to_optimize=d, fixed_mask=np.asarray(mask).astype(int).tolist(),
+               fixed_values=np.asarray(vals, dtype=np.float64).tolist(), seg_times=[float(t) for t in times],
+               coeffs=[[[float(x) for x in dim] for dim in seg] for seg in c0], cost=float(J0), grad_coeffs=G.tolist(),
+               grad_cost=g, step=float(STEP))
+
+    def L_at(t, v):
+        c, J = (solve0 if t is tm else kkt_solver(mask, t, d))(v)
+        return loss(c, J, G, g)
+
+    if directional:
+        dirs = []
+        for _ in range(directional):
+            dt = [float(x) for x in (rng.integers(-8, 9, size=S) / 16.0) * np.asarray(times)]
+            dv = np.where(np.repeat(flat[:, None], D, axis=1) != 0, rng.integers(-16, 17, size=(n_all, D)) / 16.0, 0.0)
+            lp, lm = [], []
+            for sgn, out in ((1, lp), (-1, lm)):
+                t = [tm[i] + sgn * STEP * mp.mpf(dt[i]) for i in range(S)]
+                v = [[vm[i][k] + sgn * STEP * mp.mpf(float(dv[i, k])) for k in range(D)] for i in range(n_all)]
+                out.append(L_at(t, v))
+            dirs.append(dict(d_seg_times=dt, d_fixed_values=dv.reshape(S + 1, B, D).tolist(),
+                             derivative=float((lp[0] - lm[0]) / (2 * STEP))))
+        rec["directions"] = dirs
+        return rec
+    gt = []
+    for i in range(S):
+        tp = list(tm)
+        tq = list(tm)
+        tp[i] += STEP
+        tq[i] -= STEP
+        gt.append(float((L_at(tp, vm) - L_at(tq, vm)) / (2 * STEP)))
+    gv = np.zeros((n_all, D))
+    for i in range(n_all):
+        if not flat[i]:
+            continue
+        for k in range(D):
+            vp = [row[:] for row in vm]
+            vq = [row[:] for row in vm]
+            vp[i][k] += STEP
+            vq[i][k] -= STEP
+            gv[i, k] = float((L_at(tm, vp) - L_at(tm, vq)) / (2 * STEP))
+    rec["grad_seg_times"] = gt
+    rec["grad_fixed_values"] = gv.reshape(S + 1, B, D).tolist()
+    return rec
+
+
+def path(n_seg, seed, d, stop_at=None):
+    wp0 = pr.random_box_waypoints(n_seg, seed)
+    wp, m, v = pr.build_vertices(wp0, d, stop_at=stop_at)
+    t = [float(x) for x in euclid_times(wp, pr.DEFAULT_LIMITS)]
+    return m.copy(), v.copy(), t
+
+
+def cases():
+    out = []
+    for name, S, d, seed in (("d2_s3", 3, 2, 700), ("d3_s5", 5, 3, 701), ("d4_s4", 4, 4, 702), ("d4_s6", 6, 4, 703)):
+        m, v, t = path(S, seed, d)
+        out.append(record(name, m, v, t, d, seed))
+    stop = [False] * 6
+    stop[2] = True
+    m, v, t = path(5, 710, 4, stop_at=stop)
+    m[-1, 1:] = 0      # the end vertex constrains its position only
+    v[-1, 1:, :] = 0.0
+    out.append(record("free_end_stop_at", m, v, t, 4, 710))
+    m, v, t = path(5, 720, 4)
+    m[2, 0] = 0        # vertex 2 leaves its position free
+    v[2, 0, :] = 0.0
+    out.append(record("position_free_vertex", m, v, t, 4, 720))
+    m, v, t = path(6, 730, 4)
+    t[3] = 0.5 * (t[2] + t[4]) / 50.0
+    out.append(record("ratio50", m, v, t, 4, 730))
+    m, v, t = path(30, 740, 4)
+    out.append(record("seg30_directional", m, v, t, 4, 740, directional=3))
+    return out
+
+
+def main():
+    cs = cases()
+    with open(OUT, "w") as f:
+        json.dump(dict(generator="tests/golden/gen_vjp_cases.py", mp_dps=60, cases=cs), f)
+    print("wrote", len(cs), "cases to", OUT)
+
+
+if __name__ == "__main__":
+    main()
