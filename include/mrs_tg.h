@@ -184,7 +184,8 @@ enum {
   MRS_TG_CAP_FUTURE_PATHS = 2, /* the initial condition of paths stamped in the future: mrs_tg_prepare_initial_condition and
                                   mrs_tg_splice_prediction are exported */
   MRS_TG_CAP_REFINE = 4,       /* MRS_TG_FLAG_REFINE is honoured (refine_kernel is built in) */
-  MRS_TG_CAP_GRADIENT = 8      /* mrs_tg_plan_solve_vjp is exported: the backward pass of the fixed-times solve */
+  MRS_TG_CAP_GRADIENT = 8,     /* mrs_tg_plan_solve_vjp is exported: the backward pass of the fixed-times solve */
+  MRS_TG_CAP_MAXIMA_GRADIENT = 16 /* mrs_tg_plan_segment_maxima_vjp is exported: the backward pass of the segment maxima */
 };
 
 typedef struct mrs_tg_options {
@@ -389,13 +390,34 @@ int mrs_tg_plan_segment_maxima(mrs_tg_plan* plan, const double* coeffs_dev, cons
  * one adjoint solve with the same masked R_pp per path and dimension (a vanishing pivot leaves its multiplier at 0).  Any
  * fixed / free pattern; derivative_to_optimize 0 .. 4 as for the solve.  At least one upstream array and one output must be
  * given; a NULL upstream counts as zero, a NULL output is not written.  A path with status <= 0 gets zeros in all of its
- * output rows.  Not differentiated: time allocation, feasibility scaling, limits, sampling.  Deterministic (no atomics).
+ * output rows.  Not differentiated here: time allocation, sampling, and the maxima that the feasibility scaling and the
+ * limits rest on (those: mrs_tg_plan_segment_maxima_vjp).  Deterministic (no atomics).
  * Device pointers in the caller's CSR order, asynchronous on the context's stream; per-lane factors in the plan's workspace
  * (1440 bytes per path per vertex of the plan's longest path). */
 int mrs_tg_plan_solve_vjp(mrs_tg_plan* plan, int32_t derivative_to_optimize, const uint8_t* fixed_mask_dev,
                           const double* fixed_values_dev, const double* seg_times_dev, const double* coeffs_dev,
                           const int32_t* status_dev, const double* grad_coeffs_dev, const double* grad_cost_dev,
                           double* grad_fixed_values_out_dev, double* grad_seg_times_out_dev);
+/* Backward pass of the segment maxima (MRS_TG_CAP_MAXIMA_GRADIENT; segment_maxima_vjp_kernel): given
+ * the gradient of a loss L with respect to what mrs_tg_plan_segment_maxima returns for (coeffs_dev, seg_times_dev) --
+ * grad_maxima_dev [sum S][3][3], required -- writes dL/dcoeffs (grad_coeffs_out_dev [sum S][4][10]), dL/dseg_times
+ * (grad_seg_times_out_dev [sum S]) and the maximiser t* in seconds of every entry (argmax_out_dev [sum S][3][3]); a NULL
+ * output is not written, at least one must be given.  By the envelope theorem, for the entry (k, group) with maximiser t*
+ * and u = p^(k)(t*) / |p^(k)(t*)|: dM/dc[dim][j] = u_dim j!/(j-k)! t*^(j-k) (j >= k, dim in the group) and dM/dT =
+ * u . p^(k+1)(T) if t* = T, else 0.  Non-smooth cases:
+ *   winner -- t* is the candidate of the forward's own search that produced its value: the first, in the search's
+ *     evaluation order, whose magnitude equals the maximum; on a tie (two equal peaks) the result is that winner's one-sided
+ *     gradient (an element of the Clarke subdifferential), the same bits on every call;
+ *   refinement -- an interior winner is polished by at most 4 Newton steps on d|p^(k)|^2/dt, kept only if it stays in the
+ *     winner's grid cell and within 2^-20 of the segment's length from the winner, is a maximum there and the magnitude did
+ *     not fall beyond rounding (else the winner itself); end points are not refined; the forward's values are never changed;
+ *   degenerate -- a zero maximum contributes 0; an entry whose upstream is exactly 0 contributes exactly 0; a segment with
+ *     T <= 0 or a non-finite T or coefficient gets zero rows (and t* = 0).
+ * The 9 entries of a segment are summed in a fixed order: deterministic (no atomics, no workspace).  Device pointers in CSR
+ * order, asynchronous on the context's stream. */
+int mrs_tg_plan_segment_maxima_vjp(mrs_tg_plan* plan, const double* coeffs_dev, const double* seg_times_dev,
+                                   const double* grad_maxima_dev, double* grad_coeffs_out_dev, double* grad_seg_times_out_dev,
+                                   double* argmax_out_dev);
 /* sampleWholeTrajectory with every field of the sampled state (sampleTrajectoryInRange, trajectory_sampling.cpp:49-104:
  * five evaluateRange passes over the same accumulate-and-carry walk, trajectory.cpp:93-151): for the trajectories given by
  * coeffs_dev [sum S][4][10] and seg_times_dev [sum S], states_out_dev [n_paths][sample_capacity][MRS_TG_STATE_ORDERS][4]
@@ -415,7 +437,7 @@ int mrs_tg_plan_sample_states(mrs_tg_plan* plan, const double* coeffs_dev, const
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
- * 3 backward pass (mrs_tg_plan_solve_vjp).
+ * 3 backward pass of the solve (mrs_tg_plan_solve_vjp), 4 backward pass of the maxima (mrs_tg_plan_segment_maxima_vjp).
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

@@ -42,7 +42,7 @@ RUNAWAY_TIME_FACTOR = 25.0     # MRS_TG_RUNAWAY_TIME_FACTOR
 FIND_ACCEPTED, FIND_REJECTED_CODE, FIND_REJECTED_TOO_LONG, FIND_REJECTED_TOO_SHORT = 0, 1, 2, 3
 
 STATE_ORDERS = 5   # derivative orders 0..4 per sample of Plan.sample_states (MRS_TG_STATE_ORDERS)
-KERNEL_ASSEMBLE, KERNEL_SOLVE_LINEAR, KERNEL_NONLINEAR, KERNEL_VJP = 0, 1, 2, 3
+KERNEL_ASSEMBLE, KERNEL_SOLVE_LINEAR, KERNEL_NONLINEAR, KERNEL_VJP, KERNEL_MAXIMA_VJP = 0, 1, 2, 3, 4
 
 
 class MrsTgError(RuntimeError):
@@ -100,6 +100,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_create_multi", "mrs_tg_destroy_multi", "mrs_tg_multi_n_devices", "mrs_tg_multi_context", "mrs_tg_multi_shard",
     "mrs_tg_multi_solve_batch", "mrs_tg_multi_last_error",
     "mrs_tg_prepare_initial_condition", "mrs_tg_splice_prediction", "mrs_tg_plan_solve_vjp",
+    "mrs_tg_plan_segment_maxima_vjp",
 ]
 
 _lib = None
@@ -187,6 +188,8 @@ def load_library():
     L.mrs_tg_plan_segment_maxima.argtypes = [vp, dp, dp, dp]
     L.mrs_tg_plan_solve_vjp.restype = C.c_int
     L.mrs_tg_plan_solve_vjp.argtypes = [vp, C.c_int32, bp, dp, dp, dp, ip, dp, dp, dp, dp]
+    L.mrs_tg_plan_segment_maxima_vjp.restype = C.c_int
+    L.mrs_tg_plan_segment_maxima_vjp.argtypes = [vp, dp, dp, dp, dp, dp, dp]
     L.mrs_tg_plan_careful_count.restype = C.c_int
     L.mrs_tg_plan_careful_count.argtypes = [vp, ip]
     L.mrs_tg_plan_sample_states.restype = C.c_int
@@ -239,6 +242,7 @@ CAP_CAREFUL_COST = 1   # MRS_TG_CAP_CAREFUL_COST
 CAP_FUTURE_PATHS = 2   # MRS_TG_CAP_FUTURE_PATHS: prepare_initial_condition / splice_prediction
 CAP_REFINE = 4         # MRS_TG_CAP_REFINE: FLAG_REFINE is honoured
 CAP_GRADIENT = 8       # MRS_TG_CAP_GRADIENT: Plan.solve_vjp (the backward pass of the fixed-times solve)
+CAP_MAXIMA_GRADIENT = 16   # MRS_TG_CAP_MAXIMA_GRADIENT: Plan.segment_maxima_vjp (the backward pass of the segment maxima)
 
 
 def capabilities():
@@ -791,6 +795,14 @@ class Plan:
                                                       _t_ptr(seg_times), _t_ptr(coeffs), _t_ptr(status), _t_ptr(grad_coeffs),
                                                       _t_ptr(grad_cost), _t_ptr(grad_fixed_values), _t_ptr(grad_seg_times)),
                         "mrs_tg_plan_solve_vjp")
+
+    def segment_maxima_vjp(self, coeffs, seg_times, grad_maxima, grad_coeffs=None, grad_seg_times=None, argmax=None):
+        """mrs_tg_plan_segment_maxima_vjp: dL/dcoeffs [sum S][4][10], dL/dseg_times [sum S] and the maximisers t* [sum S][3][3]
+        in seconds (device tensors, written; None = not wanted, at least one given) from dL/dmaxima [sum S][3][3] at
+        (coeffs, seg_times); asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_segment_maxima_vjp(self._h, _t_ptr(coeffs), _t_ptr(seg_times), _t_ptr(grad_maxima),
+                                                               _t_ptr(grad_coeffs), _t_ptr(grad_seg_times), _t_ptr(argmax)),
+                        "mrs_tg_plan_segment_maxima_vjp")
 
     def careful_count(self):
         n = C.c_int32(0)

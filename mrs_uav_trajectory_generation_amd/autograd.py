@@ -1,13 +1,23 @@
-"""The fixed-times solve as a torch.autograd.Function: gradients of a loss on the coefficients and the cost reach the fixed
-values (waypoints, initial state) and the segment times.
+"""The fixed-times solve and the segment maxima as torch.autograd.Functions: gradients of a loss on the coefficients, the cost
+and the derivative maxima reach the fixed values (waypoints, initial state), the segment times and the limits.
 
 Forward: Plan.solve with time_alloc_method = NONE, no sampling, no waypoints, no limits (the existing kernels, unchanged).
 Backward: Plan.solve_vjp (mrs_tg_plan_solve_vjp, vjp_kernel), the exact chain rule of the linear QP at the returned solution
-(DESIGN.md section 4c).  Differentiated: fixed_values and seg_times.  Not differentiated: time allocation, feasibility scaling,
-limits, sampling, second derivatives.  Both passes run on torch's current stream of the thread that runs them: the call binds
+(DESIGN.md section 4c).  Differentiated: fixed_values and seg_times.  Not differentiated by solve itself: time allocation,
+sampling, second derivatives; the feasibility scaling and the limits are segment_maxima and scale_times_to_limits below
+(DESIGN.md section 4d).  Both passes run on torch's current stream of the thread that runs them: the call binds
 the plan's context to it (Context.use_torch_stream), and the context stays bound afterwards.
 
     >>> fv = fixed_values.clone(); fv[:, 0, :] = waypoints; coeffs, cost, status = solve(plan, fixed_mask, fv, seg_times)
+
+segment_maxima (Plan.segment_maxima forward, Plan.segment_maxima_vjp backward: mrs_tg_plan_segment_maxima_vjp, DESIGN.md
+section 4d) differentiates the per-segment maxima of |p^(k)| in the coefficients and the segment times; scale_times_to_limits
+puts the product's feasibility step T <- T max(1, v, sqrt a, cbrt j) on top of it.  The intended chain
+differentiates everything after the time allocation -- solve, maxima, scaling, re-solve:
+
+    >>> coeffs, _, status = solve(plan, fixed_mask, fv, seg_times)
+    >>> times = scale_times_to_limits(plan, coeffs, seg_times, limits, status)
+    >>> coeffs, cost, status = solve(plan, fixed_mask, fv, times)
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -57,3 +67,76 @@ def solve(plan, fixed_mask, fixed_values, seg_times, derivative=4, flags=api.FLA
     fixed_values [sum V][5][4] and seg_times [sum S] (float64 device tensors; fixed_mask uint8 [sum V][5]).  A path with
     status <= 0 gets zero gradients."""
     return _FixedTimesSolve.apply(plan, fixed_mask, fixed_values, seg_times, derivative, flags)
+
+
+class _SegmentMaxima(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, coeffs, seg_times):
+        c = coeffs.detach().to(torch.float64).contiguous()
+        t = seg_times.detach().to(torch.float64).contiguous()
+        maxima = torch.empty((plan.n_segments, 3, 3), dtype=torch.float64, device=c.device)
+        plan.ctx.use_torch_stream()
+        plan.segment_maxima(c, t, maxima)
+        ctx.plan = plan
+        ctx.save_for_backward(c, t)
+        ctx.set_materialize_grads(False)
+        return maxima
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_maxima):
+        c, t = ctx.saved_tensors
+        want_c, want_t = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        gc = torch.empty_like(c) if want_c else None
+        gt = torch.empty_like(t) if want_t else None
+        if grad_maxima is None:
+            return None, None if gc is None else gc.zero_(), None if gt is None else gt.zero_()
+        if gc is None and gt is None:
+            return None, None, None
+        plan = ctx.plan
+        plan.ctx.use_torch_stream()
+        plan.segment_maxima_vjp(c, t, grad_maxima.to(torch.float64).contiguous(), grad_coeffs=gc, grad_seg_times=gt)
+        return None, gc, gt
+
+
+def segment_maxima(plan, coeffs, seg_times):
+    """maxima [sum S][3][3] = max over [0, T] of |p^(k)|, indexed [segment][k-1][group] (groups {x,y}, {z}, {heading}), of
+    the trajectories (coeffs [sum S][4][10], seg_times [sum S]; float64 device tensors), differentiable in both.  The gradient
+    is the envelope theorem's at the forward search's own maximiser (a tie gives that winner's one-sided gradient); a zero
+    maximum and a segment with T <= 0 or non-finite inputs give zero gradients."""
+    return _SegmentMaxima.apply(plan, coeffs, seg_times)
+
+
+def _root(x, p):
+    """x^(1/p) for x >= 0 with a finite gradient everywhere: 0 at x = 0 (where the root is never the active term of the
+    scaling unless every term is 0, and the max(1, ...) then holds)"""
+    pos = x > 0
+    safe = torch.where(pos, x, torch.ones_like(x))
+    r = torch.sqrt(safe) if p == 2 else torch.pow(safe, 1.0 / 3.0)
+    return torch.where(pos, r, torch.zeros_like(x))
+
+
+def scale_times_to_limits(plan, coeffs, seg_times, limits, status=None):
+    """The product's one-sweep feasibility step (violation_scaling in mrs_tg_device.hpp) in torch on top
+    of segment_maxima: T_i max(1, max_g v_g / v_lim_g, sqrt(max_g a_g / a_lim_g), cbrt(max_g j_g / j_lim_g)) per segment,
+    limits [n_paths][9] indexed 3 (k-1) + group in the plan's (caller's) path order.  Segments of paths with status <= 0
+    (status [n_paths], optional) keep their times; their maxima are set aside before the division, so that what the solve
+    left in their coefficients (NaN included) reaches neither the scaling nor any gradient.  The maxima are combined with
+    fmax, as violation_scaling combines them (a NaN term is ignored).  Differentiable in coeffs, seg_times and limits."""
+    dev = seg_times.device
+    so = torch.as_tensor(plan.seg_offsets, dtype=torch.int64, device=dev)
+    counts = so[1:] - so[:-1]
+    path_of_seg = torch.repeat_interleave(torch.arange(plan.n_paths, device=dev), counts, output_size=plan.n_segments)
+    mx = segment_maxima(plan, coeffs, seg_times)
+    keep = None
+    if status is not None:
+        keep = status.to(dev)[path_of_seg] > 0
+        mx = torch.where(keep[:, None, None], mx, torch.zeros_like(mx))
+    lim = limits.to(torch.float64).reshape(plan.n_paths, 3, 3)[path_of_seg]
+    ratio = mx / lim
+    viol = torch.fmax(torch.fmax(ratio[:, :, 0], ratio[:, :, 1]), ratio[:, :, 2])   # [sum S][3]: over the groups, per k
+    one = torch.ones_like(viol[:, 0])
+    s = torch.fmax(one, torch.fmax(torch.fmax(viol[:, 0], _root(viol[:, 1], 2)), _root(viol[:, 2], 3)))
+    if keep is not None:
+        s = torch.where(keep, s, one)
+    return seg_times * s

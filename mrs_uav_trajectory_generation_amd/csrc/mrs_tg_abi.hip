@@ -51,9 +51,9 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 4;  // kernel_id 0 .. 3 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 5;  // kernel_id 0 .. 4 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
-  long long ev_count[kTimedKernels] = {0, 0, 0, 0};   // timed launches since profiling was switched on
+  long long ev_count[kTimedKernels] = {0, 0, 0, 0, 0};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
   double wall_clock_hz = 1.0e8;  // rate of s_memrealtime (hipDeviceAttributeWallClockRate)
   // plan of the most recent mrs_tg_solve_batch: a caller that sends the same batch shape again (the nodelet's
@@ -216,7 +216,7 @@ int mrs_tg_abi_version(void) { return MRS_TG_ABI_VERSION; }
 
 int mrs_tg_capabilities(void) {
   return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE |
-         MRS_TG_CAP_GRADIENT;
+         MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -958,6 +958,21 @@ int mrs_tg_plan_segment_maxima(mrs_tg_plan* plan, const double* coeffs, const do
   mrs_tg_ctx* ctx = plan->ctx;
   HIP_TRY(ctx, use_device(ctx->device));
   HIP_TRY(ctx, mrs_tg::launch_segment_maxima(plan->view, coeffs, seg_times, maxima, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_segment_maxima_vjp(mrs_tg_plan* plan, const double* coeffs, const double* seg_times, const double* grad_maxima,
+                                   double* grad_coeffs, double* grad_times, double* argmax) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!coeffs || !seg_times || !grad_maxima)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "coeffs, seg_times and grad_maxima are required");
+  if (!grad_coeffs && !grad_times && !argmax)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_coeffs_out, grad_seg_times_out and argmax_out are all NULL");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 4);
+  HIP_TRY(ctx, mrs_tg::launch_segment_maxima_vjp(plan->view.n_segments, coeffs, seg_times, grad_maxima, grad_coeffs, grad_times,
+                                                 argmax, ctx->stream));
   return MRS_TG_OK;
 }
 

@@ -179,6 +179,11 @@ size_t vjp_workspace_doubles(const BatchView& b);
 hipError_t launch_vjp(const BatchView& b, int d, const uint8_t* mask, const double* vals, const double* seg_times,
                       const double* coeffs, const int32_t* status, const double* grad_coeffs, const double* grad_cost, double* ws,
                       double* grad_vals, double* grad_times, hipStream_t stream);
+// mrs_tg_plan_segment_maxima_vjp (mrs_tg_maxima_vjp.hip): the backward pass of the segment maxima -- dL/dcoeffs, dL/dseg_times
+// and the maximisers t* (each may be NULL) from dL/dmaxima; reads only, no workspace; timed as the kernel family of the
+// pending ProfileScope
+hipError_t launch_segment_maxima_vjp(int n_segments, const double* coeffs, const double* seg_times, const double* grad_maxima,
+                                     double* grad_coeffs, double* grad_times, double* argmax, hipStream_t stream);
 // phase-split tile kernel (mrs_tg_tile.hip): small and medium batches whose per-path state fits in LDS
 bool tile_kernel_applies(const BatchView& b, bool fused);
 hipError_t launch_solve_tile(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,

@@ -1,5 +1,6 @@
 // mrs_tg_maxima.hpp -- per-segment maxima of the derivative magnitudes (device functions; the kernels that call them are
-// segment_maxima9_kernel in mrs_tg_nonlinear.hip and segment_maxima4_kernel in mrs_tg_dfo.hip).
+// segment_maxima9_kernel in mrs_tg_nonlinear.hip, segment_maxima4_kernel in mrs_tg_dfo.hip and, with the winner tracked,
+// segment_maxima_vjp_kernel in mrs_tg_maxima_vjp.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -110,6 +111,14 @@ struct MagPolyAny : MagPolyBase<NDIM, kN - 1> {
   }
 };
 
+// Where the search's value came from (max_mag2_search<PARTS, true>, the backward pass segment_maxima_vjp_kernel): the abscissa
+// of the FIRST candidate, in evaluation order, whose m2 equals the returned maximum (strict > against the running maximum, the
+// candidate the fmax chain keeps), and the grid cell it belongs to: [lo, hi] = the polished cell, or the two cells around a
+// grid point (one at an end point).
+struct ArgmaxOut {
+  double tau, lo, hi;
+};
+
 // max over tau in [0,1] of sum_dim q^(K)(tau)^2.
 // Pass 1 walks the grid and records, as a bit mask, the cells where g changes sign + -> - (a local
 // maximum inside).  Pass 2 polishes the recorded cells.  Keeping the two apart matters on a 64-wide
@@ -119,20 +128,26 @@ struct MagPolyAny : MagPolyBase<NDIM, kN - 1> {
 // grid points and the same polished cells as one lane walking all 32, so the maximum over the PARTS lanes (taken by the
 // caller) is the same number; the dependent work of a lane, and with it the time a wavefront waits for its slowest lane's
 // Newton loops, is PARTS times shorter.
-template <int PARTS, class Poly>
-__device__ __forceinline__ double max_mag2_search(const Poly& mp, int part) {
+// ARGMAX: also report the winner in *am (PARTS = 1 only); the value and every decision of the search are unchanged, and with
+// ARGMAX = false (every forward kernel) the tracking is not compiled at all.
+template <int PARTS, bool ARGMAX = false, class Poly>
+__device__ __forceinline__ double max_mag2_search(const Poly& mp, int part, ArgmaxOut* am = nullptr) {
   static_assert(kGridCells <= 32 && kGridCells % PARTS == 0, "cell mask is 32 bits");
+  static_assert(!ARGMAX || PARTS == 1, "the winner is tracked by a lane that walks the whole grid");
   constexpr int kCells = kGridCells / PARTS;
   const double h = 1.0 / kGridCells;
   const int i0 = part * kCells;
   double m2, g;
   mp.eval(i0 * h, m2, g);  // (i0 = 0: tau = 0 exactly)
   double best = m2;
+  if constexpr (ARGMAX) *am = ArgmaxOut{0.0, 0.0, h};
   double g_prev = g;
   unsigned cells = 0u;
   for (int i = i0 + 1; i <= i0 + kCells; ++i) {
     const double tau = (i == kGridCells) ? 1.0 : i * h;
     mp.eval(tau, m2, g);
+    if constexpr (ARGMAX)
+      if (m2 > best) *am = ArgmaxOut{tau, (i - 1) * h, (i + 1 >= kGridCells) ? 1.0 : (i + 1) * h};
     best = fmax(best, m2);
     if (g_prev > 0.0 && g <= 0.0) cells |= 1u << (i - 1);
     g_prev = g;
@@ -146,9 +161,12 @@ __device__ __forceinline__ double max_mag2_search(const Poly& mp, int part) {
     // m2 is flat at its maximum: an abscissa error e costs ~ m2'' e^2 / 2, so |e| ~ 1e-8 already gives
     // the value to ~1e-16; the iteration cap bounds the slowest lane of the wavefront (pure bisection
     // from a 1/32 cell reaches 2e-7 after 17 halvings, i.e. a value error below 1e-12).
+    const double lo0 = lo, hi0 = hi;
     for (int it = 0; it < kPolishIters; ++it) {
       double mm, gg, dd;
       mp.eval2(t, mm, gg, dd);
+      if constexpr (ARGMAX)
+        if (mm > best) *am = ArgmaxOut{t, lo0, hi0};
       best = fmax(best, mm);
       if (gg > 0.0) lo = t;
       else hi = t;
@@ -165,16 +183,18 @@ __device__ __forceinline__ double max_mag2_search(const Poly& mp, int part) {
   return best;
 }
 
-template <int K, int NDIM, int PARTS = 1>
-__device__ __forceinline__ double max_mag2(const double (&cb)[NDIM][kN], int part = 0) {
+template <int K, int NDIM, int PARTS = 1, bool ARGMAX = false>
+__device__ __forceinline__ double max_mag2(const double (&cb)[NDIM][kN], int part = 0, ArgmaxOut* am = nullptr) {
   MagPoly<K, NDIM> mp;
   mp.init(cb);
-  return max_mag2_search<PARTS>(mp, part);
+  return max_mag2_search<PARTS, ARGMAX>(mp, part, am);
 }
 
-// which = 3*(k-1) + group: maximum of |p^(k)| over [0, T] for one (k, group) of one segment
-template <int PARTS = 1>
-__device__ __forceinline__ double segment_maximum(const double* __restrict__ c, double T, int which, int part = 0) {
+// which = 3*(k-1) + group: maximum of |p^(k)| over [0, T] for one (k, group) of one segment (ARGMAX: and its winner in *am,
+// tau = t / T)
+template <int PARTS = 1, bool ARGMAX = false>
+__device__ __forceinline__ double segment_maximum(const double* __restrict__ c, double T, int which, int part = 0,
+                                                  ArgmaxOut* am = nullptr) {
   const int k = which / 3 + 1, grp = which % 3;
   double tp = 1.0;
   const double ti = 1.0 / T;
@@ -190,7 +210,9 @@ __device__ __forceinline__ double segment_maximum(const double* __restrict__ c, 
       cb[1][j] = c[1 * kN + j] * tp;
       tp *= T;
     }
-    m2 = (k == 1) ? max_mag2<1, 2, PARTS>(cb, part) : (k == 2) ? max_mag2<2, 2, PARTS>(cb, part) : max_mag2<3, 2, PARTS>(cb, part);
+    m2 = (k == 1)   ? max_mag2<1, 2, PARTS, ARGMAX>(cb, part, am)
+         : (k == 2) ? max_mag2<2, 2, PARTS, ARGMAX>(cb, part, am)
+                    : max_mag2<3, 2, PARTS, ARGMAX>(cb, part, am);
   } else {
     double cb[1][kN];
     const int dim = (grp == 1) ? 2 : 3;
@@ -199,7 +221,9 @@ __device__ __forceinline__ double segment_maximum(const double* __restrict__ c, 
       cb[0][j] = c[dim * kN + j] * tp;
       tp *= T;
     }
-    m2 = (k == 1) ? max_mag2<1, 1, PARTS>(cb, part) : (k == 2) ? max_mag2<2, 1, PARTS>(cb, part) : max_mag2<3, 1, PARTS>(cb, part);
+    m2 = (k == 1)   ? max_mag2<1, 1, PARTS, ARGMAX>(cb, part, am)
+         : (k == 2) ? max_mag2<2, 1, PARTS, ARGMAX>(cb, part, am)
+                    : max_mag2<3, 1, PARTS, ARGMAX>(cb, part, am);
   }
   if (PARTS == 4) {  // the four lanes of a quad share the polynomial
     m2 = fmax(m2, dpp_move<0xB1>(m2));
