@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: trajectories/s for a batch of 10-segment min-snap paths.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up, clock ramp and stream calibration, W warm-up steps,
+the timed regions of K steps, the --dump-outputs arrays, the JSON line.  Every other measurement and check -- the rooflines
+(per-dispatch timings that take runs of their own), value_200_steps, `extras` (other workloads, sizes and issue methods,
+configs[3], host interface, policy layer), the comparison of the results with the oracle and the CPU baseline -- runs only
+with `--full`; without it their keys of the line are null (`extras` is empty).  --no-extras and --no-cpu-baseline take
+parts out of a --full run and mean nothing without it.
 
 --dump-outputs DIR writes what the last timed step computed (rank 0's coefficients, segment times, status, cost and, for the
 nonlinear workload, samples) as DIR/<name>.npy in float64, so that two builds can be compared output for output.
@@ -41,7 +48,8 @@ two-dispatch round picks the pair (config.issue_policy.stream_pair holds the tab
 reported as extras.streams_in_flight; extras.one_batch_in_flight is one stream, every step waiting for the previous.  The
 nonlinear workload keeps one batch in flight per stream.
 
-Prints ONE JSON line (rank 0): `roofline` (assembly kernel, HBM-write bound; `achieved` uses the PER-DISPATCH duration --
+Prints ONE JSON line (rank 0).  With --full it carries `roofline` (assembly kernel, HBM-write bound; `achieved` uses the
+PER-DISPATCH duration --
 events attached to the kernel launch itself, what rocprofv3 --kernel-trace reports for the dispatch; the back-to-back
 launch interval is given beside it and labelled), `roofline_solve` / `roofline_outer_loop` (FP64, flop model of SURVEY.md 8d
 over the per-dispatch duration), and `cpu_baseline` (rank 0 of an N = 1 run only; the C oracle on this box's host cores: one core, and all cores through
@@ -80,9 +88,12 @@ def parse_args(argv=None):
     ap.add_argument("--workload", choices=["linear", "nonlinear"], default="linear")
     ap.add_argument("--paths", type=int, default=1024, help="paths per GPU")
     ap.add_argument("--segments", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every other measurement and check as well: rooflines, value_200_steps, extras, "
+                         "parity against the oracle, CPU baseline (off by default: a plain run is the headline figure alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the oracle comparison and the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="single-core work of the cpu_baseline sample")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the secondary measurements (extras)")
     ap.add_argument("--gather", choices=["final", "every"], default="final",
                     help="N > 1: gather the results to rank 0 once at the end of the timed steps (default) or after every step")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed even for one rank (tests the RCCL path)")
@@ -408,6 +419,9 @@ def main():
     args = parse_args(argv)
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(self_launch(args, argv))   # nothing below has run: no torch import, no GPU call in this process
+    # what a plain run leaves out (--full): the secondary measurements, and the oracle comparison + CPU baseline
+    do_extras = args.full and not args.no_extras
+    do_cpu = args.full and not args.no_cpu_baseline
 
     import numpy as np
     rank = int(os.environ.get("RANK", "0"))
@@ -465,7 +479,7 @@ def main():
     # placements are measured and reported.
     BIG_P = 65536
     early_big = None
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and do_extras:
         early_big = (torch.empty(BIG_P * args.segments * 100, dtype=torch.float64, device=dev),
                      torch.empty(BIG_P * args.segments * 100, dtype=torch.float64, device=dev))
     plan = api.Plan(ctx, batch.seg_offsets)
@@ -766,14 +780,14 @@ def main():
 
     # ---- the same issue path over 200 steps (the driver's run is 20): kept as a top-level key so that rounds stay comparable
     value_200 = None
-    if args.steps != 200 and args.workload == "linear" and not args.no_extras:
+    if args.steps != 200 and args.workload == "linear" and do_extras:
         el200, _ = time_steps(steps_fn[args.workload], 200, 0, dist, torch, None, block_fn=block_for(args.workload))
         value_200 = P * world * 200 / el200
 
     # ---- roofline of the kernel the timed region RUNS (rank 0's device): the dispatches of the headline's own issue path,
     # each with its own pair of events (the library times the launches of kernel family 1 on the lane's context) ----
     roofline_headline = None
-    if args.workload == "linear" and block_for("linear") is not None:
+    if args.full and args.workload == "linear" and block_for("linear") is not None:
         group_n = max(1, min(args.group_size, n_group_slots)) if (grouped_mode[0] and n_lanes > 1 and n_group_slots > 1) else 1
         api.kernel_trace_reset()
         block_for("linear")(n_group_slots if group_n > 1 else n_lanes)          # one round: what kernels does a dispatch run?
@@ -839,140 +853,143 @@ def main():
                     valu_active_share_of_wave_cycles=(c["SQ_ACTIVE_INST_VALU"] / c["SQ_WAVE_CYCLES"] if c.get("SQ_WAVE_CYCLES") else None),
                     counters_source=d["source"] + " (separate rocprofv3 --pmc passes; from profiles/, not this run)")
 
-    # ---- roofline of the assembly kernel (rank 0's device) ----
-    Hbuf = torch.empty(plan.block_doubles, dtype=torch.float64, device=dev)
-    Abuf = torch.empty(plan.block_doubles, dtype=torch.float64, device=dev)
+    # ---- --full: rooflines of the assembly, solve and outer-loop kernels (rank 0's device), each from launches of its own ----
+    roofline = roofline_solve = roofline_outer = None
+    if args.full:
+        # ---- roofline of the assembly kernel (rank 0's device) ----
+        Hbuf = torch.empty(plan.block_doubles, dtype=torch.float64, device=dev)
+        Abuf = torch.empty(plan.block_doubles, dtype=torch.float64, device=dev)
 
-    def launch_assemble():
-        plan.assemble(4, t_init, Hbuf, Abuf)
+        def launch_assemble():
+            plan.assemble(4, t_init, Hbuf, Abuf)
 
-    for _ in range(20):
-        launch_assemble()
-    torch.cuda.synchronize()
-    q_mean, q_med, q_min = dispatch_stats(ctx, api.KERNEL_ASSEMBLE, launch_assemble, 300, torch)     # queued: neighbours overlap
-    asm_mean, asm_med, asm_min = isolated_dispatch_stats(ctx, api.KERNEL_ASSEMBLE, launch_assemble, 300, torch)
-    asm_b2b = back_to_back_ms(launch_assemble, 200, torch)
-    alg_bytes = ASSEMBLY_BYTES_PER_SEGMENT * nS
-    achieved = alg_bytes / (asm_mean * 1e-3) / 1e9
-    traffic, traffic_source = None, "no PMC summary for this batch shape under profiles/"
-    tm = measured_traffic(P, args.segments)
-    if tm is not None:
-        traffic = tm[0]["hbm_bytes_per_launch"]
-        traffic_source = "%s (separate rocprofv3 --pmc passes; from profiles/, not this run)" % tm[1]
-    roofline = dict(kernel="assemble_blocks_uniform_kernel", in_timed_region=False,
-                    scope="SURVEY.md 8d's contract kernel (the HBM-bound Hessian / mapping-block assembly behind mrs_tg_plan_assemble and "
-                          "MRS_TG_FLAG_MATERIALIZED_BLOCKS), measured on its own AFTER the timed region: the headline's default solve "
-                          "forms the blocks in registers and never launches it -- the kernel the timed steps run is roofline_headline",
-                    bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s",
-                    frac=achieved / HBM_PEAK_GBS, traffic=traffic, traffic_source=traffic_source, bytes_per_launch=alg_bytes,
-                    avg_launch_us=asm_mean * 1e3, median_launch_us=asm_med * 1e3, min_launch_us=asm_min * 1e3,
-                    timing="per dispatch: a pair of events attached to each of 300 launches, every launch issued when the previous "
-                           "one has finished (round 6; the dispatch's own duration, which is also what rocprofv3 --kernel-trace "
-                           "reports in its run of the command: the tool's work per launch keeps the dispatches apart).  Until round 5 "
-                           "the 300 launches were QUEUED: the next dispatch's ramp then runs into this one's tail and each pair of "
-                           "events spans more than its own dispatch -- 5.2 to 6.3 us from run to run where isolated dispatches take "
-                           "5.0 to 5.2; those figures are queued_*",
-                    queued_avg_launch_us=q_mean * 1e3, queued_median_launch_us=q_med * 1e3,
-                    queued_frac=alg_bytes / (q_mean * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                    back_to_back_interval_us=asm_b2b * 1e3,
-                    back_to_back_note="launch-to-launch interval of 200 queued launches; one dispatch's tail overlaps the "
-                                      "next one's ramp, so this is NOT a kernel duration (%.3f of peak if it were)"
-                                      % (alg_bytes / (asm_b2b * 1e-3) / 1e9 / HBM_PEAK_GBS),
-                    note="16 MB per launch: launch-ramp bound, see extras.roofline_large for the same kernel at 1 GB")
-    ceil = fill_ceiling(P, args.segments)
-    if ceil is not None:
-        ceil["frac"] = alg_bytes / (ceil["avg_launch_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS
-        ceil["note"] = ("fastest pure fill of the same bytes, per dispatch, from profiles/ (not this run): the ceiling of this "
-                        "launch size")
-        roofline["fill_ceiling"] = ceil
+        for _ in range(20):
+            launch_assemble()
+        torch.cuda.synchronize()
+        q_mean, q_med, q_min = dispatch_stats(ctx, api.KERNEL_ASSEMBLE, launch_assemble, 300, torch)     # queued: neighbours overlap
+        asm_mean, asm_med, asm_min = isolated_dispatch_stats(ctx, api.KERNEL_ASSEMBLE, launch_assemble, 300, torch)
+        asm_b2b = back_to_back_ms(launch_assemble, 200, torch)
+        alg_bytes = ASSEMBLY_BYTES_PER_SEGMENT * nS
+        achieved = alg_bytes / (asm_mean * 1e-3) / 1e9
+        traffic, traffic_source = None, "no PMC summary for this batch shape under profiles/"
+        tm = measured_traffic(P, args.segments)
+        if tm is not None:
+            traffic = tm[0]["hbm_bytes_per_launch"]
+            traffic_source = "%s (separate rocprofv3 --pmc passes; from profiles/, not this run)" % tm[1]
+        roofline = dict(kernel="assemble_blocks_uniform_kernel", in_timed_region=False,
+                        scope="SURVEY.md 8d's contract kernel (the HBM-bound Hessian / mapping-block assembly behind mrs_tg_plan_assemble and "
+                              "MRS_TG_FLAG_MATERIALIZED_BLOCKS), measured on its own AFTER the timed region: the headline's default solve "
+                              "forms the blocks in registers and never launches it -- the kernel the timed steps run is roofline_headline",
+                        bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s",
+                        frac=achieved / HBM_PEAK_GBS, traffic=traffic, traffic_source=traffic_source, bytes_per_launch=alg_bytes,
+                        avg_launch_us=asm_mean * 1e3, median_launch_us=asm_med * 1e3, min_launch_us=asm_min * 1e3,
+                        timing="per dispatch: a pair of events attached to each of 300 launches, every launch issued when the previous "
+                               "one has finished (round 6; the dispatch's own duration, which is also what rocprofv3 --kernel-trace "
+                               "reports in its run of the command: the tool's work per launch keeps the dispatches apart).  Until round 5 "
+                               "the 300 launches were QUEUED: the next dispatch's ramp then runs into this one's tail and each pair of "
+                               "events spans more than its own dispatch -- 5.2 to 6.3 us from run to run where isolated dispatches take "
+                               "5.0 to 5.2; those figures are queued_*",
+                        queued_avg_launch_us=q_mean * 1e3, queued_median_launch_us=q_med * 1e3,
+                        queued_frac=alg_bytes / (q_mean * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                        back_to_back_interval_us=asm_b2b * 1e3,
+                        back_to_back_note="launch-to-launch interval of 200 queued launches; one dispatch's tail overlaps the "
+                                          "next one's ramp, so this is NOT a kernel duration (%.3f of peak if it were)"
+                                          % (alg_bytes / (asm_b2b * 1e-3) / 1e9 / HBM_PEAK_GBS),
+                        note="16 MB per launch: launch-ramp bound, see extras.roofline_large for the same kernel at 1 GB")
+        ceil = fill_ceiling(P, args.segments)
+        if ceil is not None:
+            ceil["frac"] = alg_bytes / (ceil["avg_launch_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS
+            ceil["note"] = ("fastest pure fill of the same bytes, per dispatch, from profiles/ (not this run): the ceiling of this "
+                            "launch size")
+            roofline["fill_ceiling"] = ceil
 
-    # ---- FP64 rooflines of the solve kernel and of the outer-loop kernel (per dispatch, flop model of SURVEY.md 8d) ----
-    db.coeffs, db.seg_times, db.status = out_coeffs[0], out_times[0], status_i32[0]
+        # ---- FP64 rooflines of the solve kernel and of the outer-loop kernel (per dispatch, flop model of SURVEY.md 8d) ----
+        db.coeffs, db.seg_times, db.status = out_coeffs[0], out_times[0], status_i32[0]
 
-    def launch_solve():
-        plan.solve(opt_lin[0], db.fixed_mask, db.fixed_values, t_fixed, out_coeffs[0], status_i32[0], slot_cost[0], waypoints=db.waypoints)
+        def launch_solve():
+            plan.solve(opt_lin[0], db.fixed_mask, db.fixed_values, t_fixed, out_coeffs[0], status_i32[0], slot_cost[0], waypoints=db.waypoints)
 
-    def launch_nl():
-        plan.solve(opt_nl[0], db.fixed_mask, db.fixed_values, out_times[0], out_coeffs[0], status_i32[0], slot_cost[0],
-                   waypoints=db.waypoints, limits=db.limits, n_samples=slot_nsamp[0], samples=slot_samples[0])
+        def launch_nl():
+            plan.solve(opt_nl[0], db.fixed_mask, db.fixed_values, out_times[0], out_coeffs[0], status_i32[0], slot_cost[0],
+                       waypoints=db.waypoints, limits=db.limits, n_samples=slot_nsamp[0], samples=slot_samples[0])
 
-    for _ in range(10):
-        launch_solve()
-    torch.cuda.synchronize()
-    sol_mean, sol_med, sol_min = dispatch_stats(ctx, api.KERNEL_SOLVE_LINEAR, launch_solve, 200, torch)
-    solve_flop = SOLVE_FLOP_PER_SEGMENT * nS
-    def newest_sq(pattern):
-        """SQ counters of a kernel at this batch shape from the newest committed PMC passes (scripts/pmc_sq.sh, pmc_sq_json.py)"""
-        for f in sorted(glob.glob(os.path.join(ROOT, "profiles", pattern)), reverse=True):
-            try:
-                with open(f) as fh:
-                    d = json.load(fh)
-            except (OSError, ValueError):
-                continue
-            if d.get("paths") == P and d.get("segments") == args.segments:
-                return d
-        return None
+        for _ in range(10):
+            launch_solve()
+        torch.cuda.synchronize()
+        sol_mean, sol_med, sol_min = dispatch_stats(ctx, api.KERNEL_SOLVE_LINEAR, launch_solve, 200, torch)
+        solve_flop = SOLVE_FLOP_PER_SEGMENT * nS
+        def newest_sq(pattern):
+            """SQ counters of a kernel at this batch shape from the newest committed PMC passes (scripts/pmc_sq.sh, pmc_sq_json.py)"""
+            for f in sorted(glob.glob(os.path.join(ROOT, "profiles", pattern)), reverse=True):
+                try:
+                    with open(f) as fh:
+                        d = json.load(fh)
+                except (OSError, ValueError):
+                    continue
+                if d.get("paths") == P and d.get("segments") == args.segments:
+                    return d
+            return None
 
-    sq = newest_sq("round*_pmc_sq_solve_rows.json")
-    issue_peak = 256 * 4 * 2.4e9 / 4.0   # wavefront VALU instructions per second: one per 4 cycles per SIMD
-    counted = None
-    if sq is not None:
-        c = sq["counters"]
-        counted = dict(source=sq["source"] + " (separate rocprofv3 --pmc passes; from profiles/, not this run)",
-                       valu_instructions_per_launch=c["SQ_INSTS_VALU"], lds_instructions_per_launch=c["SQ_INSTS_LDS"],
-                       valu_issue_rate_ginst_s=c["SQ_INSTS_VALU"] / (sol_mean * 1e-3) / 1e9,
-                       valu_issue_peak_ginst_s=issue_peak / 1e9,
-                       valu_issue_frac=c["SQ_INSTS_VALU"] / (sol_mean * 1e-3) / issue_peak,
-                       executed_fp64_tflops_upper_bound=2.0 * 64 * c["SQ_INSTS_VALU"] / (sol_mean * 1e-3) / 1e12,
-                       wait_share_of_wave_cycles=c["SQ_WAIT_ANY"] / c["SQ_WAVE_CYCLES"],
-                       valu_active_share_of_wave_cycles=c["SQ_ACTIVE_INST_VALU"] / c["SQ_WAVE_CYCLES"])
-    roofline_solve = dict(kernel="solve_rows_kernel", bound="fp64 vector", unit="TFLOP/s", peak=FP64_VECTOR_PEAK_TFLOPS,
-                          counted=counted,
-                          flop_per_launch=solve_flop, avg_launch_us=sol_mean * 1e3, median_launch_us=sol_med * 1e3,
-                          achieved=solve_flop / (sol_mean * 1e-3) / 1e12,
-                          frac=solve_flop / (sol_mean * 1e-3) / 1e12 / FP64_VECTOR_PEAK_TFLOPS,
-                          note="flop model of SURVEY.md 8d (6e3 flop per segment, which counts the reference's two dense "
-                               "10^3 products per segment; the kernel forms the blocks from exact constants and executes "
-                               "roughly a quarter of that); the kernel is bound by one dependent chain per path, not by "
-                               "FP64 issue: see DESIGN.md")
-    for _ in range(3):
-        launch_nl()
-    torch.cuda.synchronize()
-    nl_mean, nl_med, nl_min = dispatch_stats(ctx, api.KERNEL_NONLINEAR, launch_nl, 50, torch)
-    nl_flop = NONLINEAR_FLOP_PER_PATH_S10 * (args.segments / 10.0) ** 2 * P
-    sq_nl = newest_sq("round*_pmc_sq_outer_loop.json")
-    if sq_nl is not None:
-        # executed work: every VALU instruction counted as a 64-lane FP64 FMA -- an upper bound of the flops the kernel ran
-        c = sq_nl["counters"]
-        nl_exec = 2.0 * 64 * c["SQ_INSTS_VALU"]
-        roofline_outer = dict(kernel=sq_nl["kernel"], bound="fp64 vector issue", unit="wavefront VALU instructions/s",
-                              peak=issue_peak, avg_launch_us=nl_mean * 1e3, median_launch_us=nl_med * 1e3,
-                              achieved=c["SQ_INSTS_VALU"] / (nl_mean * 1e-3),
-                              valu_issue_frac=c["SQ_INSTS_VALU"] / (nl_mean * 1e-3) / issue_peak,
-                              valu_lane_flop_upper_bound_per_launch=nl_exec,
-                              counted=dict(source=sq_nl["source"] + " (separate rocprofv3 --pmc passes; from profiles/, not this run)",
-                                           valu_instructions_per_launch=c["SQ_INSTS_VALU"],
-                                           lds_instructions_per_launch=c["SQ_INSTS_LDS"],
-                                           valu_issue_frac=c["SQ_INSTS_VALU"] / (nl_mean * 1e-3) / issue_peak,
-                                           wait_share_of_wave_cycles=c["SQ_WAIT_ANY"] / c["SQ_WAVE_CYCLES"],
-                                           valu_active_share_of_wave_cycles=c["SQ_ACTIVE_INST_VALU"] / c["SQ_WAVE_CYCLES"],
-                                           lds_bank_conflict_share=(c["SQ_LDS_BANK_CONFLICT"] / c["SQ_LDS_IDX_ACTIVE"]
-                                                                    if c.get("SQ_LDS_IDX_ACTIVE") else None)),
-                              reference_work_flop=nl_flop,
-                              note="an ISSUE rate, not a flop rate: counted VALU instructions per second against one per 4 cycles per SIMD "
-                                   "(valu_lane_flop_upper_bound_per_launch = 2 x 64 x that count, if every instruction were a full FP64 FMA); "
-                                   "reference_work_flop is SURVEY.md 8d's model of what the reference would execute for the same "
-                                   "batch (7e6 flop per 10-segment path = 121 linear solves), which the kernel undercuts by running "
-                                   "forward-only cost sweeps on exact constants and stopping on ftol / xtol -- not a rate")
-    else:
-        roofline_outer = dict(kernel="optimize_wave_kernel / optimize_split_kernel / optimize_lean_kernel", bound="fp64 vector issue",
-                              unit="wavefront VALU instructions/s", peak=issue_peak, avg_launch_us=nl_mean * 1e3,
-                              median_launch_us=nl_med * 1e3, achieved=None, valu_issue_frac=None, reference_work_flop=nl_flop,
-                              note="no committed SQ counters for this batch shape (scripts/pmc_sq.sh); reference_work_flop is "
-                                   "SURVEY.md 8d's model of the reference's work, not what the kernel executes")
+        sq = newest_sq("round*_pmc_sq_solve_rows.json")
+        issue_peak = 256 * 4 * 2.4e9 / 4.0   # wavefront VALU instructions per second: one per 4 cycles per SIMD
+        counted = None
+        if sq is not None:
+            c = sq["counters"]
+            counted = dict(source=sq["source"] + " (separate rocprofv3 --pmc passes; from profiles/, not this run)",
+                           valu_instructions_per_launch=c["SQ_INSTS_VALU"], lds_instructions_per_launch=c["SQ_INSTS_LDS"],
+                           valu_issue_rate_ginst_s=c["SQ_INSTS_VALU"] / (sol_mean * 1e-3) / 1e9,
+                           valu_issue_peak_ginst_s=issue_peak / 1e9,
+                           valu_issue_frac=c["SQ_INSTS_VALU"] / (sol_mean * 1e-3) / issue_peak,
+                           executed_fp64_tflops_upper_bound=2.0 * 64 * c["SQ_INSTS_VALU"] / (sol_mean * 1e-3) / 1e12,
+                           wait_share_of_wave_cycles=c["SQ_WAIT_ANY"] / c["SQ_WAVE_CYCLES"],
+                           valu_active_share_of_wave_cycles=c["SQ_ACTIVE_INST_VALU"] / c["SQ_WAVE_CYCLES"])
+        roofline_solve = dict(kernel="solve_rows_kernel", bound="fp64 vector", unit="TFLOP/s", peak=FP64_VECTOR_PEAK_TFLOPS,
+                              counted=counted,
+                              flop_per_launch=solve_flop, avg_launch_us=sol_mean * 1e3, median_launch_us=sol_med * 1e3,
+                              achieved=solve_flop / (sol_mean * 1e-3) / 1e12,
+                              frac=solve_flop / (sol_mean * 1e-3) / 1e12 / FP64_VECTOR_PEAK_TFLOPS,
+                              note="flop model of SURVEY.md 8d (6e3 flop per segment, which counts the reference's two dense "
+                                   "10^3 products per segment; the kernel forms the blocks from exact constants and executes "
+                                   "roughly a quarter of that); the kernel is bound by one dependent chain per path, not by "
+                                   "FP64 issue: see DESIGN.md")
+        for _ in range(3):
+            launch_nl()
+        torch.cuda.synchronize()
+        nl_mean, nl_med, nl_min = dispatch_stats(ctx, api.KERNEL_NONLINEAR, launch_nl, 50, torch)
+        nl_flop = NONLINEAR_FLOP_PER_PATH_S10 * (args.segments / 10.0) ** 2 * P
+        sq_nl = newest_sq("round*_pmc_sq_outer_loop.json")
+        if sq_nl is not None:
+            # executed work: every VALU instruction counted as a 64-lane FP64 FMA -- an upper bound of the flops the kernel ran
+            c = sq_nl["counters"]
+            nl_exec = 2.0 * 64 * c["SQ_INSTS_VALU"]
+            roofline_outer = dict(kernel=sq_nl["kernel"], bound="fp64 vector issue", unit="wavefront VALU instructions/s",
+                                  peak=issue_peak, avg_launch_us=nl_mean * 1e3, median_launch_us=nl_med * 1e3,
+                                  achieved=c["SQ_INSTS_VALU"] / (nl_mean * 1e-3),
+                                  valu_issue_frac=c["SQ_INSTS_VALU"] / (nl_mean * 1e-3) / issue_peak,
+                                  valu_lane_flop_upper_bound_per_launch=nl_exec,
+                                  counted=dict(source=sq_nl["source"] + " (separate rocprofv3 --pmc passes; from profiles/, not this run)",
+                                               valu_instructions_per_launch=c["SQ_INSTS_VALU"],
+                                               lds_instructions_per_launch=c["SQ_INSTS_LDS"],
+                                               valu_issue_frac=c["SQ_INSTS_VALU"] / (nl_mean * 1e-3) / issue_peak,
+                                               wait_share_of_wave_cycles=c["SQ_WAIT_ANY"] / c["SQ_WAVE_CYCLES"],
+                                               valu_active_share_of_wave_cycles=c["SQ_ACTIVE_INST_VALU"] / c["SQ_WAVE_CYCLES"],
+                                               lds_bank_conflict_share=(c["SQ_LDS_BANK_CONFLICT"] / c["SQ_LDS_IDX_ACTIVE"]
+                                                                        if c.get("SQ_LDS_IDX_ACTIVE") else None)),
+                                  reference_work_flop=nl_flop,
+                                  note="an ISSUE rate, not a flop rate: counted VALU instructions per second against one per 4 cycles per SIMD "
+                                       "(valu_lane_flop_upper_bound_per_launch = 2 x 64 x that count, if every instruction were a full FP64 FMA); "
+                                       "reference_work_flop is SURVEY.md 8d's model of what the reference would execute for the same "
+                                       "batch (7e6 flop per 10-segment path = 121 linear solves), which the kernel undercuts by running "
+                                       "forward-only cost sweeps on exact constants and stopping on ftol / xtol -- not a rate")
+        else:
+            roofline_outer = dict(kernel="optimize_wave_kernel / optimize_split_kernel / optimize_lean_kernel", bound="fp64 vector issue",
+                                  unit="wavefront VALU instructions/s", peak=issue_peak, avg_launch_us=nl_mean * 1e3,
+                                  median_launch_us=nl_med * 1e3, achieved=None, valu_issue_frac=None, reference_work_flop=nl_flop,
+                                  note="no committed SQ counters for this batch shape (scripts/pmc_sq.sh); reference_work_flop is "
+                                       "SURVEY.md 8d's model of the reference's work, not what the kernel executes")
 
     extras = {}
-    if not args.no_extras and rank == 0:
+    if do_extras and rank == 0:
         # the same kernel on a batch that is not launch-ramp dominated (65536 x 10 segments = 1.05 GB per launch)
         big_P = 65536
         so_big = (np.arange(big_P + 1, dtype=np.int64) * args.segments).astype(np.int32)
@@ -1072,7 +1089,7 @@ def main():
                                                      "examples/request_latency_host.cpp); python_wrapper_median_us: "
                                                      "Context.find_trajectory, which builds the ctypes structures and output arrays "
                                                      "per call (the figure of rounds 1-3)" % args.segments)
-    if not args.no_extras and args.workload == "linear":
+    if do_extras and args.workload == "linear":
         # the step that materialises the blocks: assembly kernel + solve from the blocks in HBM
         elb, _ = time_steps(steps_fn["blocks"], args.steps, 3, dist, torch, final_gather, block_fn=block_for("blocks"))
         if rank == 0:
@@ -1080,7 +1097,7 @@ def main():
                                                       ms_per_step=elb / args.steps * 1e3,
                                                       note="MRS_TG_FLAG_MATERIALIZED_BLOCKS: assemble_blocks kernel (16.5 MB to "
                                                            "HBM) + solve_tile_kernel reading the blocks back; %d in flight" % n_lanes)
-    if n_lanes > 1 and not args.no_extras and args.workload == "linear" and grouped_mode[0]:
+    if n_lanes > 1 and do_extras and args.workload == "linear" and grouped_mode[0]:
         # the same K steps issued one dispatch per step, round-robin over the streams (the headline's method up to round 2)
         grouped_mode[0] = False
         els, _ = time_steps(steps_fn["linear"], args.steps, 3, dist, torch, final_gather, block_fn=block_for("linear"))
@@ -1089,7 +1106,7 @@ def main():
             extras["streams_in_flight"] = dict(value=P * world * args.steps / els, unit="trajectories/s", ms_per_step=els / args.steps * 1e3,
                                                note="one dispatch per step on %d HIP streams (mrs_tg_bound_solve_launch_many), "
                                                     "MRS_TG_FLAG_SHARED_DEVICE" % n_lanes)
-    if n_lanes > 1 and not args.no_extras:
+    if n_lanes > 1 and do_extras:
         # the same steps with one batch in flight: every step waits for the previous one (single stream)
         torch.cuda.synchronize()
         active_lanes[0] = 1
@@ -1104,7 +1121,7 @@ def main():
                                                  ms_per_step=el1 / args.steps * 1e3)
             if el1b is not None:
                 extras["one_batch_in_flight"]["materialized_blocks_ms_per_step"] = el1b / args.steps * 1e3
-    if not args.no_extras:
+    if do_extras:
         other = "nonlinear" if args.workload == "linear" else "linear"
         k2 = max(5, args.steps // 10) if other == "nonlinear" else args.steps
         el2, _ = time_steps(steps_fn[other], k2, 3, dist, torch, final_gather, block_fn=block_for(other))
@@ -1121,7 +1138,7 @@ def main():
                                                    bytes_per_rank_per_step=int(packed[0].numel() * 8))
 
     # ---- BASELINE configs[3]: ONE batch of 65536 nonlinear-time paths, contiguous shards over the ranks, gather to rank 0
-    if not args.no_extras:
+    if do_extras:
         total3 = args.config3_paths
         a3, b3 = shard.contiguous_shard(total3, rank, world)
         n3 = b3 - a3
@@ -1210,7 +1227,7 @@ def main():
         del db3, pk3, pad3, recv3
 
     # ---- two figures beside the BASELINE configs (rank 0, after every other measurement so that they disturb none)
-    if not args.no_extras and rank == 0 and world == 1:
+    if do_extras and rank == 0 and world == 1:
         # the policy layer around the solver (mrs_tg_optimize_paths = the reference's optimize(): preprocessing, solve, length
         # check, spatial validation, mid-point subdivision rounds) for a batch of requests, host arrays in and out
         try:
@@ -1270,7 +1287,7 @@ def main():
     cpu = None
     err = None
     err_exact = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # (the contract: rank 0, at N = 1 only)
+    if rank == 0 and world == 1 and do_cpu:   # (the contract: rank 0, at N = 1 only)
         from oracle import pyoracle as po
         active_lanes[0] = n_lanes
         step_no[0] = 0
@@ -1380,7 +1397,7 @@ def main():
                    cpu_quota_cpus=quota,
                    sample_all_cores="%d x a batch of %d paths (the same %d paths tiled), %d threads of the oracle's "
                                     "persistent pool, dynamic chunks" % (reps_all, big.n_paths, n_cpu, cores))
-        if args.workload == "nonlinear" or not args.no_extras:
+        if args.workload == "nonlinear" or do_extras:
             n_nl = min(P, 256)
             subn = batch.select(range(n_nl))
 
@@ -1490,7 +1507,7 @@ def main():
                                                 "steps; value_including_gather has it inside"))
                                 if world > 1 else "single GPU"),
                     max_coeff_err_vs_cpu_ref=err, max_coeff_err_vs_113bit_ref=err_exact,
-                    in_flight_slots_vs_cpu_ref=(slots_checked if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None),
+                    in_flight_slots_vs_cpu_ref=(slots_checked if (rank == 0 and world == 1 and do_cpu) else None),
                     rccl_version=rccl_version,
                     roofline=roofline, roofline_headline=roofline_headline, roofline_solve=roofline_solve,
                     roofline_outer_loop=roofline_outer, cpu_baseline=cpu, extras=extras, dump_outputs=dumped)

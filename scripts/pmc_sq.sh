@@ -4,7 +4,7 @@
 tag=${1:-round}
 cd "$(dirname "$0")/.." && export TMPDIR=/tmp
 mkdir -p gpurun_out
-B="--no-cpu-baseline --no-extras --in-flight 1 --steps 20 --warmup 3"
+B="--full --no-cpu-baseline --no-extras --in-flight 1 --steps 20 --warmup 3"
 groups=("SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU" "SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE")
 for wl in linear nonlinear; do
   dirs=""

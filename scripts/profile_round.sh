@@ -12,7 +12,7 @@ run() {  # name, program, arguments...   (the program itself follows `--`: no wr
   f=$(find gpurun_out/prof_$name -name '*kernel_stats.csv' | head -1)
   [ -n "$f" ] && cp "$f" gpurun_out/${tag}_${name}_kernel_stats.csv
 }
-B="--no-cpu-baseline --no-extras"
+B="--full --no-cpu-baseline --no-extras"   # (--full: the assembly, solve and outer-loop kernels of the rooflines are in the statistics)
 run bench_linear python3 bench.py --steps 200 --warmup 20 $B                       # the bench command (four batches in flight: kernels of the streams overlap)
 run bench_linear_one_in_flight python3 bench.py --in-flight 1 --steps 200 --warmup 20 $B   # per-kernel durations without overlap
 run bench_nonlinear_1024 python3 bench.py --workload nonlinear --in-flight 1 --steps 50 --warmup 5 $B

@@ -8,8 +8,8 @@ O=gpurun_out
 # the micro-benchmark binaries are not tracked: build what is missing (hipcc is on the GPU box as well)
 [ -x scripts/tile_phases.bin ] || /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -I mrs_uav_trajectory_generation_amd/csrc -I include scripts/tile_phases.hip -o scripts/tile_phases.bin
 [ -x scripts/k1_variants.bin ] || /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -I mrs_uav_trajectory_generation_amd/csrc -I include scripts/k1_variants.hip -o scripts/k1_variants.bin
-python3 bench.py --steps 20 --warmup 5 2>/dev/null | grep '^{"metric' > $O/${tag}_bench_line_20_steps.json
-python3 bench.py --steps 200 --warmup 20 2>/dev/null | grep '^{"metric' > $O/${tag}_bench_line.json
+python3 bench.py --full --steps 20 --warmup 5 2>/dev/null | grep '^{"metric' > $O/${tag}_bench_line_20_steps.json
+python3 bench.py --full --steps 200 --warmup 20 2>/dev/null | grep '^{"metric' > $O/${tag}_bench_line.json
 scripts/profile_round.sh $tag > $O/${tag}_profile_round.log 2>&1
 scripts/pmc_sq.sh $tag > $O/${tag}_pmc_sq.log 2>&1
 python3 scripts/pmc_sq_json.py $O/${tag}_pmc_sq_linear.csv solve_rows_kernel 65536 1024 10 $O/${tag}_pmc_sq_solve_rows.json

@@ -69,7 +69,7 @@ def test_two_ranks_started_by_bench_itself_on_one_gpu():
     gloo), configs[3]'s fixed batch cut in two, one JSON line that says so."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "5",
-                          "--warmup", "2", "--paths", "256", "--config3-paths", "2048", "--no-cpu-baseline"],
+                          "--warmup", "2", "--paths", "256", "--config3-paths", "2048", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -92,7 +92,7 @@ def test_single_rank_rccl_path_runs_and_the_gather_delivers_the_local_results():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--dist-backend", "nccl",
-                          "--steps", "5", "--warmup", "2", "--config3-paths", "4096", "--no-cpu-baseline"],
+                          "--steps", "5", "--warmup", "2", "--config3-paths", "4096", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
