@@ -185,7 +185,9 @@ enum {
                                   mrs_tg_splice_prediction are exported */
   MRS_TG_CAP_REFINE = 4,       /* MRS_TG_FLAG_REFINE is honoured (refine_kernel is built in) */
   MRS_TG_CAP_GRADIENT = 8,     /* mrs_tg_plan_solve_vjp is exported: the backward pass of the fixed-times solve */
-  MRS_TG_CAP_MAXIMA_GRADIENT = 16 /* mrs_tg_plan_segment_maxima_vjp is exported: the backward pass of the segment maxima */
+  MRS_TG_CAP_MAXIMA_GRADIENT = 16, /* mrs_tg_plan_segment_maxima_vjp is exported: the backward pass of the segment maxima */
+  MRS_TG_CAP_SAMPLE_GRADIENT = 32  /* mrs_tg_plan_sample_states_vjp and mrs_tg_plan_sample are exported: the backward pass of
+                                      the sampler */
 };
 
 typedef struct mrs_tg_options {
@@ -434,10 +436,47 @@ int mrs_tg_plan_careful_count(mrs_tg_plan* plan, int32_t* count_out);
 int mrs_tg_plan_sample_states(mrs_tg_plan* plan, const double* coeffs_dev, const double* seg_times_dev, double sampling_dt,
                               int32_t sample_capacity, int32_t* n_samples_out_dev, double* states_out_dev);
 
+/* The positions + heading sampler on its own (what the solve calls write to samples_out when sampling_dt > 0): the same
+ * arguments as mrs_tg_plan_sample_states with samples_out_dev [n_paths][sample_capacity][4], order 0 of the states bit for
+ * bit at a fifth of the stores. */
+int mrs_tg_plan_sample(mrs_tg_plan* plan, const double* coeffs_dev, const double* seg_times_dev, double sampling_dt,
+                       int32_t sample_capacity, int32_t* n_samples_out_dev, double* samples_out_dev);
+/* Backward pass of the sampler (MRS_TG_CAP_SAMPLE_GRADIENT; sample_vjp_kernel): given the gradient of
+ * a loss L with respect to the samples -- grad_states_dev [n_paths][sample_capacity][n_orders][4], n_orders = 1 (the
+ * upstream of mrs_tg_plan_sample / the solve calls' samples_out) or MRS_TG_STATE_ORDERS (of mrs_tg_plan_sample_states) --
+ * writes dL/dcoeffs (grad_coeffs_out_dev [sum S][4][10]) and dL/dseg_times (grad_seg_times_out_dev [sum S]), and, with or
+ * without an upstream, what the gradient is taken at: per sample the segment (index within its path) and the time in that
+ * segment in seconds of the forward's own walk (sample_segment_out_dev / sample_time_out_dev [n_paths][sample_capacity];
+ * entries at or beyond a path's sample count are not written) and the counts (n_samples_out_dev [n_paths], as the forward
+ * reports them).  Sample k of segment i_k at the time t_k = k dt - sum_{i < i_k} T_i contributes
+ *   dL/dc[i_k][dim][j] += sum_{o <= min(j, n_orders-1)} G[k][o][dim] j!/(j-o)! t_k^(j-o)
+ *   dL/dT_i            -= sum_{o, dim} G[k][o][dim] p_dim^(o+1)(t_k)      for every segment i < i_k.
+ * What is not smooth, and what the call does there:
+ *   sample count and segment membership -- piecewise constant in the times: the gradient is that of the walk the forward
+ *     took, n and i_k held fixed (positions are continuous across a segment boundary; the one true discontinuity of a loss on
+ *     positions is the appearance of a new last sample when the total time crosses a multiple of dt);
+ *   the floating-point walk -- t_k is a chain of rounded additions and carries; it is differentiated as its exact
+ *     counterpart, dt_k/dT_i = -1 for the segments in front of the sample's own and 0 otherwise;
+ *   heading wrap -- derivative 1, at the seam the one-sided value;
+ *   overflow -- when the forward reports sample_capacity + 1, the first sample_capacity samples exist and contribute;
+ *   rows of the upstream at or beyond a path's sample count are never read;
+ *   degenerate -- a path whose total time is not a number has no samples and gets zero rows; with status_dev, a path with
+ *     status <= 0 gets zero rows whatever its coefficients hold; a segment without a sample gets zero coefficient rows and
+ *     still its time gradient from the samples behind it.
+ * At least one output must be given, the two gradients need grad_states_dev; every output element that belongs to the plan
+ * is written exactly once (zeros included).  Every sum runs in a fixed order (a segment's samples in increasing index, the
+ * 4 n_orders time partials in index order, the segments from the last downwards): deterministic, no atomics, no workspace.
+ * Device pointers in CSR order, asynchronous on the context's stream. */
+int mrs_tg_plan_sample_states_vjp(mrs_tg_plan* plan, const double* coeffs_dev, const double* seg_times_dev, double sampling_dt,
+                                  int32_t sample_capacity, int32_t n_orders, const double* grad_states_dev,
+                                  const int32_t* status_dev, double* grad_coeffs_out_dev, double* grad_seg_times_out_dev,
+                                  int32_t* sample_segment_out_dev, double* sample_time_out_dev, int32_t* n_samples_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
- * 3 backward pass of the solve (mrs_tg_plan_solve_vjp), 4 backward pass of the maxima (mrs_tg_plan_segment_maxima_vjp).
+ * 3 backward pass of the solve (mrs_tg_plan_solve_vjp), 4 backward pass of the maxima (mrs_tg_plan_segment_maxima_vjp),
+ * 5 backward pass of the sampler (mrs_tg_plan_sample_states_vjp).
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

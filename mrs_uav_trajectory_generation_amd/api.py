@@ -43,6 +43,7 @@ FIND_ACCEPTED, FIND_REJECTED_CODE, FIND_REJECTED_TOO_LONG, FIND_REJECTED_TOO_SHO
 
 STATE_ORDERS = 5   # derivative orders 0..4 per sample of Plan.sample_states (MRS_TG_STATE_ORDERS)
 KERNEL_ASSEMBLE, KERNEL_SOLVE_LINEAR, KERNEL_NONLINEAR, KERNEL_VJP, KERNEL_MAXIMA_VJP = 0, 1, 2, 3, 4
+KERNEL_SAMPLE_VJP = 5
 
 
 class MrsTgError(RuntimeError):
@@ -100,7 +101,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_create_multi", "mrs_tg_destroy_multi", "mrs_tg_multi_n_devices", "mrs_tg_multi_context", "mrs_tg_multi_shard",
     "mrs_tg_multi_solve_batch", "mrs_tg_multi_last_error",
     "mrs_tg_prepare_initial_condition", "mrs_tg_splice_prediction", "mrs_tg_plan_solve_vjp",
-    "mrs_tg_plan_segment_maxima_vjp",
+    "mrs_tg_plan_segment_maxima_vjp", "mrs_tg_plan_sample", "mrs_tg_plan_sample_states_vjp",
 ]
 
 _lib = None
@@ -194,6 +195,10 @@ def load_library():
     L.mrs_tg_plan_careful_count.argtypes = [vp, ip]
     L.mrs_tg_plan_sample_states.restype = C.c_int
     L.mrs_tg_plan_sample_states.argtypes = [vp, dp, dp, C.c_double, C.c_int32, ip, dp]
+    L.mrs_tg_plan_sample.restype = C.c_int
+    L.mrs_tg_plan_sample.argtypes = [vp, dp, dp, C.c_double, C.c_int32, ip, dp]
+    L.mrs_tg_plan_sample_states_vjp.restype = C.c_int
+    L.mrs_tg_plan_sample_states_vjp.argtypes = [vp, dp, dp, C.c_double, C.c_int32, C.c_int32, dp, ip, dp, dp, ip, dp, ip]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -243,6 +248,7 @@ CAP_FUTURE_PATHS = 2   # MRS_TG_CAP_FUTURE_PATHS: prepare_initial_condition / sp
 CAP_REFINE = 4         # MRS_TG_CAP_REFINE: FLAG_REFINE is honoured
 CAP_GRADIENT = 8       # MRS_TG_CAP_GRADIENT: Plan.solve_vjp (the backward pass of the fixed-times solve)
 CAP_MAXIMA_GRADIENT = 16   # MRS_TG_CAP_MAXIMA_GRADIENT: Plan.segment_maxima_vjp (the backward pass of the segment maxima)
+CAP_SAMPLE_GRADIENT = 32   # MRS_TG_CAP_SAMPLE_GRADIENT: Plan.sample_states_vjp (the backward pass of the sampler), Plan.sample
 
 
 def capabilities():
@@ -814,6 +820,25 @@ class Plan:
         self.ctx._check(self._L.mrs_tg_plan_sample_states(self._h, _t_ptr(coeffs), _t_ptr(seg_times), float(sampling_dt),
                                                           int(sample_capacity), _t_ptr(n_samples), _t_ptr(states)),
                         "mrs_tg_plan_sample_states")
+
+    def sample(self, coeffs, seg_times, sampling_dt, sample_capacity, n_samples, samples):
+        """mrs_tg_plan_sample: positions + wrapped heading, samples [n_paths][capacity][4] (order 0 of sample_states)."""
+        self.ctx._check(self._L.mrs_tg_plan_sample(self._h, _t_ptr(coeffs), _t_ptr(seg_times), float(sampling_dt),
+                                                   int(sample_capacity), _t_ptr(n_samples), _t_ptr(samples)),
+                        "mrs_tg_plan_sample")
+
+    def sample_states_vjp(self, coeffs, seg_times, sampling_dt, sample_capacity, grad_states, status=None, grad_coeffs=None,
+                          grad_seg_times=None, sample_segment=None, sample_time=None, n_samples=None):
+        """mrs_tg_plan_sample_states_vjp: dL/dcoeffs [sum S][4][10] and dL/dseg_times [sum S] from dL/dsamples (grad_states
+        [n_paths][capacity][n_orders][4], n_orders 1 or STATE_ORDERS; a 3-D tensor [n_paths][capacity][4] means 1; None when
+        no gradient is wanted), and the walk's own sample_segment (int32) / sample_time [n_paths][capacity] and n_samples
+        [n_paths] (device tensors, written; None = not wanted, at least one given); asynchronous on the context's stream."""
+        n_orders = 1 if grad_states is None or grad_states.dim() == 3 else int(grad_states.shape[2])
+        self.ctx._check(self._L.mrs_tg_plan_sample_states_vjp(self._h, _t_ptr(coeffs), _t_ptr(seg_times), float(sampling_dt),
+                                                              int(sample_capacity), n_orders, _t_ptr(grad_states),
+                                                              _t_ptr(status), _t_ptr(grad_coeffs), _t_ptr(grad_seg_times),
+                                                              _t_ptr(sample_segment), _t_ptr(sample_time), _t_ptr(n_samples)),
+                        "mrs_tg_plan_sample_states_vjp")
 
 
 class RoundRobin:

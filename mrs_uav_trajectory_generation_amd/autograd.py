@@ -1,11 +1,12 @@
-"""The fixed-times solve and the segment maxima as torch.autograd.Functions: gradients of a loss on the coefficients, the cost
-and the derivative maxima reach the fixed values (waypoints, initial state), the segment times and the limits.
+"""The fixed-times solve, the segment maxima and the sampler as torch.autograd.Functions: gradients of a loss on the
+coefficients, the cost, the derivative maxima and the samples reach the fixed values (waypoints, initial state), the segment
+times and the limits.
 
 Forward: Plan.solve with time_alloc_method = NONE, no sampling, no waypoints, no limits (the existing kernels, unchanged).
 Backward: Plan.solve_vjp (mrs_tg_plan_solve_vjp, vjp_kernel), the exact chain rule of the linear QP at the returned solution
-(DESIGN.md section 4c).  Differentiated: fixed_values and seg_times.  Not differentiated by solve itself: time allocation,
-sampling, second derivatives; the feasibility scaling and the limits are segment_maxima and scale_times_to_limits below
-(DESIGN.md section 4d).  Both passes run on torch's current stream of the thread that runs them: the call binds
+(DESIGN.md section 4c).  Differentiated: fixed_values and seg_times.  Not differentiated by solve itself: time allocation and
+second derivatives; the feasibility scaling and the limits are segment_maxima and scale_times_to_limits below (DESIGN.md
+section 4d), the sampling is sample / sample_states.  Both passes run on torch's current stream of the thread that runs them: the call binds
 the plan's context to it (Context.use_torch_stream), and the context stays bound afterwards.
 
     >>> fv = fixed_values.clone(); fv[:, 0, :] = waypoints; coeffs, cost, status = solve(plan, fixed_mask, fv, seg_times)
@@ -17,7 +18,19 @@ differentiates everything after the time allocation -- solve, maxima, scaling, r
 
     >>> coeffs, _, status = solve(plan, fixed_mask, fv, seg_times)
     >>> times = scale_times_to_limits(plan, coeffs, seg_times, limits, status)
-    >>> coeffs, cost, status = solve(plan, fixed_mask, fv, times)
+    >>> coeffs, cost, status = solve(plan, fixed_mask, fv, times); samples, n = sample(plan, coeffs, times, dt, cap, status)
+
+sample / sample_states (Plan.sample / Plan.sample_states forward, Plan.sample_states_vjp backward:
+mrs_tg_plan_sample_states_vjp) put the losses people write on a trajectory -- clearance, tracking --
+within reach: the gradient is that of the walk the forward took (sample count and segment membership held fixed).  From
+waypoints to a loss on samples:
+
+    >>> fv = fixed_values.clone().requires_grad_(); times = seg_times.clone().requires_grad_()
+    >>> coeffs, _, status = solve(plan, fixed_mask, fv, times)
+    >>> samples, n = sample(plan, coeffs, times, 0.2, 512, status)      # [n_paths][512][4], rows >= n are zero
+    >>> valid = torch.arange(512, device=n.device)[None, :] < n[:, None]
+    >>> loss = (torch.relu(1.0 - (samples[..., :3] - obstacle).norm(dim=-1)) * valid).sum()
+    >>> loss.backward()                                                 # fv.grad, times.grad
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -105,6 +118,57 @@ def segment_maxima(plan, coeffs, seg_times):
     is the envelope theorem's at the forward search's own maximiser (a tie gives that winner's one-sided gradient); a zero
     maximum and a segment with T <= 0 or non-finite inputs give zero gradients."""
     return _SegmentMaxima.apply(plan, coeffs, seg_times)
+
+
+class _Sample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, coeffs, seg_times, sampling_dt, sample_capacity, status, all_orders):
+        c = coeffs.detach().to(torch.float64).contiguous()
+        t = seg_times.detach().to(torch.float64).contiguous()
+        cap = int(sample_capacity)
+        n = torch.empty(plan.n_paths, dtype=torch.int32, device=c.device)
+        # (the kernels write the rows a path has; the rows at or beyond its count stay zero)
+        shape = (plan.n_paths, cap, api.STATE_ORDERS, api.N_DIM) if all_orders else (plan.n_paths, cap, api.N_DIM)
+        out = torch.zeros(shape, dtype=torch.float64, device=c.device)
+        plan.ctx.use_torch_stream()
+        (plan.sample_states if all_orders else plan.sample)(c, t, float(sampling_dt), cap, n, out if cap > 0 else None)
+        ctx.plan, ctx.dt, ctx.cap = plan, float(sampling_dt), cap
+        ctx.status = None if status is None else status.detach().to(torch.int32).contiguous()
+        ctx.save_for_backward(c, t)
+        ctx.mark_non_differentiable(n)
+        ctx.set_materialize_grads(False)
+        return out, n
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, _grad_n):
+        c, t = ctx.saved_tensors
+        want_c, want_t = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if grad_out is None or not (want_c or want_t):
+            return None, None, None, None, None, None, None
+        gc = torch.empty_like(c) if want_c else None
+        gt = torch.empty_like(t) if want_t else None
+        plan = ctx.plan
+        plan.ctx.use_torch_stream()   # (the autograd engine runs this on its own thread, on the forward's stream)
+        plan.sample_states_vjp(c, t, ctx.dt, ctx.cap, grad_out.to(torch.float64).contiguous(), status=ctx.status,
+                               grad_coeffs=gc, grad_seg_times=gt)
+        return None, gc, gt, None, None, None, None
+
+
+def sample_states(plan, coeffs, seg_times, sampling_dt, sample_capacity, status=None):
+    """(states [n_paths][capacity][5][4], n_samples [n_paths] int32) of Plan.sample_states -- derivative orders 0..4 of
+    (x, y, z, heading) every sampling_dt seconds -- differentiable in coeffs [sum S][4][10] and seg_times [sum S] (float64
+    device tensors).  Rows at or beyond a path's n_samples are zero (n_samples = capacity + 1: more samples than fit, the first
+    capacity are there).  The gradient is that of the walk the forward took: the sample count and the segment of every sample
+    are held fixed, d(time in segment)/dT_i = -1 for the segments in front of the sample's own.  A path with status <= 0
+    (status [n_paths], optional) gets zero gradients."""
+    return _Sample.apply(plan, coeffs, seg_times, sampling_dt, sample_capacity, status, True)
+
+
+def sample(plan, coeffs, seg_times, sampling_dt, sample_capacity, status=None):
+    """(samples [n_paths][capacity][4], n_samples [n_paths] int32) of Plan.sample: positions and wrapped heading, order 0 of
+    sample_states (same walk, same bits, a fifth of the stores); differentiable as sample_states is."""
+    return _Sample.apply(plan, coeffs, seg_times, sampling_dt, sample_capacity, status, False)
 
 
 def _root(x, p):

@@ -51,9 +51,9 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 5;  // kernel_id 0 .. 4 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 6;  // kernel_id 0 .. 5 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
-  long long ev_count[kTimedKernels] = {0, 0, 0, 0, 0};   // timed launches since profiling was switched on
+  long long ev_count[kTimedKernels] = {0, 0, 0, 0, 0, 0};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
   double wall_clock_hz = 1.0e8;  // rate of s_memrealtime (hipDeviceAttributeWallClockRate)
   // plan of the most recent mrs_tg_solve_batch: a caller that sends the same batch shape again (the nodelet's
@@ -216,7 +216,7 @@ int mrs_tg_abi_version(void) { return MRS_TG_ABI_VERSION; }
 
 int mrs_tg_capabilities(void) {
   return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE |
-         MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT;
+         MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1018,6 +1018,43 @@ int mrs_tg_plan_sample_states(mrs_tg_plan* plan, const double* coeffs, const dou
   HIP_TRY(ctx, use_device(ctx->device));
   HIP_TRY(ctx, mrs_tg::launch_sample_states(plan->view, coeffs, seg_times, sampling_dt, sample_capacity, n_samples,
                                             sample_capacity > 0 ? states : nullptr, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_sample(mrs_tg_plan* plan, const double* coeffs, const double* seg_times, double sampling_dt,
+                       int32_t sample_capacity, int32_t* n_samples, double* samples) {
+  if (!plan || !coeffs || !seg_times || !n_samples)
+    return fail(plan ? plan->ctx : nullptr, MRS_TG_ERR_INVALID_ARG, "NULL argument");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!(sampling_dt > 0.0) || sample_capacity < 0 || (sample_capacity > 0 && !samples))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sampling_dt must be positive and samples_out_dev given for a positive capacity");
+  HIP_TRY(ctx, use_device(ctx->device));
+  HIP_TRY(ctx, mrs_tg::launch_sample(plan->view, coeffs, seg_times, sampling_dt, sample_capacity, n_samples,
+                                     sample_capacity > 0 ? samples : nullptr, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_sample_states_vjp(mrs_tg_plan* plan, const double* coeffs, const double* seg_times, double sampling_dt,
+                                  int32_t sample_capacity, int32_t n_orders, const double* grad_states, const int32_t* status,
+                                  double* grad_coeffs, double* grad_times, int32_t* sample_segment, double* sample_time,
+                                  int32_t* n_samples) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!coeffs || !seg_times) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "coeffs and seg_times are required");
+  if (!(sampling_dt > 0.0) || sample_capacity < 0)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sampling_dt must be positive and sample_capacity non-negative");
+  if (n_orders != 1 && n_orders != MRS_TG_STATE_ORDERS)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_orders %d is neither 1 (positions and heading) nor %d (all orders)", n_orders,
+                MRS_TG_STATE_ORDERS);
+  if (!grad_coeffs && !grad_times && !sample_segment && !sample_time && !n_samples)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
+                "grad_coeffs_out, grad_seg_times_out, sample_segment_out, sample_time_out and n_samples_out are all NULL");
+  if ((grad_coeffs || grad_times) && !grad_states)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_coeffs_out and grad_seg_times_out need the upstream grad_states");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 5);
+  HIP_TRY(ctx, mrs_tg::launch_sample_vjp(plan->view, coeffs, seg_times, sampling_dt, sample_capacity, n_orders, grad_states, status,
+                                         grad_coeffs, grad_times, sample_segment, sample_time, n_samples, ctx->stream));
   return MRS_TG_OK;
 }
 

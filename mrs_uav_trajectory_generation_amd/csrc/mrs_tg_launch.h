@@ -184,6 +184,14 @@ hipError_t launch_vjp(const BatchView& b, int d, const uint8_t* mask, const doub
 // pending ProfileScope
 hipError_t launch_segment_maxima_vjp(int n_segments, const double* coeffs, const double* seg_times, const double* grad_maxima,
                                      double* grad_coeffs, double* grad_times, double* argmax, hipStream_t stream);
+// mrs_tg_plan_sample_states_vjp (mrs_tg_sample_vjp.hip): the backward pass of the sampler -- dL/dcoeffs and dL/dseg_times from
+// dL/dsamples (grad_states [n_paths][capacity][n_orders][4], n_orders 1 or kSampleStateOrders), the (segment, time) of every
+// sample and the counts (each output may be NULL); status NULL or per path (<= 0: zero rows); reads only, no workspace; timed as
+// the kernel family of the pending ProfileScope
+hipError_t launch_sample_vjp(const BatchView& b, const double* coeffs, const double* seg_times, double dt, int capacity,
+                             int n_orders, const double* grad_states, const int32_t* status, double* grad_coeffs,
+                             double* grad_times, int32_t* sample_segment, double* sample_time, int32_t* n_samples,
+                             hipStream_t stream);
 // phase-split tile kernel (mrs_tg_tile.hip): small and medium batches whose per-path state fits in LDS
 bool tile_kernel_applies(const BatchView& b, bool fused);
 hipError_t launch_solve_tile(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,

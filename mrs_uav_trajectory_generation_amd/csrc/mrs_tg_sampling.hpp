@@ -54,10 +54,20 @@ constexpr int kSampleBuffer = 192;  // samples parked per flush.  1024 made the 
 // dt with the same IEEE additions, sample_acc_table), the walk finds N = #{k : A[k] < t_end} with one look at the table around
 // t_end / dt, and "accumulated < t_end" for sample k is "k < N": the second of the two dependent additions per sample that the
 // walk used to carry is gone, bit for bit the same samples.
-template <int NDER = 0>
+//
+// SINK: who consumes the parked (t, segment) buffer at a flush.  WalkEvaluates (the default) is the Horner evaluation into
+// `out` described above.  Any other type (the backward pass, mrs_tg_sample_vjp.hip) gets, between the flush's fences,
+// sink->flush(s_t, s_seg, first, count): the parked samples [first, first + count), already cut at `capacity`, entry e of the
+// path at s_t / s_seg[e - first]; `out` is then unused, and sink->active == false means "count only" as a null `out` does.
+struct WalkEvaluates {};
+__device__ __forceinline__ bool walk_parks(const WalkEvaluates*, const double* out) { return out != nullptr; }
+template <class SINK>
+__device__ __forceinline__ bool walk_parks(const SINK* sink, const double*) { return sink->active; }
+template <int NDER = 0, class SINK = WalkEvaluates>
 __device__ __forceinline__ int sample_path_walk(const double* s_T, const double* s_c, double* s_t, unsigned short* s_seg, int S,
                                                 double dt, int capacity, double* out, const double* __restrict__ acc_table,
-                                                int acc_n) {
+                                                int acc_n, SINK* sink = nullptr) {
+  constexpr bool kEvaluates = __is_same(SINK, WalkEvaluates);
   const int lane = threadIdx.x & 63;
   // every lane carries the same walk state (i, Ti, tin, n): t_end and the start segment as the reference
   // computes them (trajectory.cpp:100-120, t_start = 0)
@@ -98,6 +108,18 @@ __device__ __forceinline__ int sample_path_walk(const double* s_T, const double*
   int n = 0;
   int n_flushed = 0;  // samples [n_flushed, n) are parked in the buffer
   auto flush = [&](int upto) {
+    if constexpr (!kEvaluates) {
+      if (!sink->active) return;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+      const int end = upto < capacity ? upto : capacity;
+      if (end > n_flushed) sink->flush(s_t, s_seg, n_flushed, end - n_flushed);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+      return;
+    }
     if (!out) return;
     // (the fences order LDS only: over every address space they wait for the samples stored by the previous flush as well)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
@@ -202,7 +224,7 @@ __device__ __forceinline__ int sample_path_walk(const double* s_T, const double*
       const bool ok = (lane <= last) && (n + lane < n_total) && !(tj > Ti) && (n + lane <= capacity);
       const unsigned long long okmask = __ballot(ok);
       const int m = (~okmask == 0ull) ? 64 : __builtin_ctzll(~okmask);  // lanes [0, m) emit a sample
-      if (out) {
+      if (walk_parks(sink, out)) {
         if (n + m - n_flushed > kSampleBuffer) {  // the chunk does not fit: evaluate what is parked first
           flush(n);
           n_flushed = n;
