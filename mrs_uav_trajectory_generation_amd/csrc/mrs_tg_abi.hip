@@ -509,11 +509,7 @@ int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
   // MRS_TG_VERIFY_FLAGS=1 (debug / test knob, read once): the statement of MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS is checked on
   // every solve, not only at bind time -- a blocking check; a false statement fails the call instead of solving the
   // waypoints' problem on launches that take the saturated-device kernel and the caller's on the others
-  static const bool verify_flags = [] {
-    const char* e = std::getenv("MRS_TG_VERIFY_FLAGS");
-    return e != nullptr && std::atoi(e) != 0;
-  }();
-  if (verify_flags && !mrs_tg::dry_run() && (opt->flags & MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS)) {
+  if (mrs_tg::knob::verify_flags() && !mrs_tg::dry_run() && (opt->flags & MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS)) {
     long long bad = 0;
     HIP_TRY(ctx, mrs_tg::count_position_mismatches(b, wp, mask, vals, ctx->stream, &bad));
     if (bad != 0)
@@ -523,14 +519,8 @@ int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
   }
   const double* pos_wp = (opt->flags & MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS) ? wp : nullptr;
   const int d = opt->derivative_to_optimize;
-  struct SharedDeviceScope {
-    explicit SharedDeviceScope(bool on) { mrs_tg::set_shared_device_hint(on); }
-    ~SharedDeviceScope() { mrs_tg::set_shared_device_hint(false); }
-  } shared_scope((opt->flags & MRS_TG_FLAG_SHARED_DEVICE) != 0);
-  struct ConstrainedSlotsScope {
-    explicit ConstrainedSlotsScope(bool on) { mrs_tg::set_constrained_slots_hint(on); }
-    ~ConstrainedSlotsScope() { mrs_tg::set_constrained_slots_hint(false); }
-  } slots_scope((opt->flags & MRS_TG_FLAG_CONSTRAINED_SLOTS) != 0);
+  mrs_tg::HintScope shared_scope(mrs_tg::set_shared_device_hint, (opt->flags & MRS_TG_FLAG_SHARED_DEVICE) != 0);
+  mrs_tg::HintScope slots_scope(mrs_tg::set_constrained_slots_hint, (opt->flags & MRS_TG_FLAG_CONSTRAINED_SLOTS) != 0);
   bool sampled = false;  // the sampling rode on the final solve's launch
   // MRS_TG_FLAG_REFINE: the refinement pass follows the final solve, so no sampling rides on a solve launch -- the solves go
   // out exactly as in the same call without sampling, and the sampler reads the refined coefficients
@@ -881,10 +871,7 @@ int mrs_tg_bound_solve_launch_group(mrs_tg_bound_solve* const* bound, int32_t n_
     ProfileScope ps(ctx, 1);
     // MRS_TG_FLAG_CONSTRAINED_SLOTS of any batch of the group: the dispatch runs the instantiations that take stop_at vertices
     // inside the specialised sweeps (the hint was only set by mrs_tg_plan_solve)
-    struct HintScope {
-      explicit HintScope(bool on) { mrs_tg::set_constrained_slots_hint(on); }
-      ~HintScope() { mrs_tg::set_constrained_slots_hint(false); }
-    } hint_scope(group_constrained_slots);
+    mrs_tg::HintScope hint_scope(mrs_tg::set_constrained_slots_hint, group_constrained_slots);
     if (mrs_tg::quad_kernel_applies(plan->view, (long long)plan->view.n_paths * g.n, false)) {
       // the dispatch carries more paths than the rows kernel has wavefront slots for: four lanes per path, factors in LDS
       // (one factor store per batch of THIS group; grows when a larger group comes, never shrinks)
@@ -1282,14 +1269,8 @@ static int solve_batch_impl(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* so,
   //   * pageable memory, large: hipMemcpyAsync on the caller's buffer (the runtime pins the pages in place; staging 3 MB
   //     of coefficients through another host copy costs more than that).
   // Waypoints are only read by the time estimator: not uploaded when estimate_times is off.
-  static const size_t stage_max = [] {
-    const char* e = std::getenv("MRS_TG_STAGE_MAX_BYTES");
-    return e ? (size_t)std::atoll(e) : (size_t)256 * 1024;
-  }();
-  static const bool zero_copy_allowed = [] {
-    const char* e = std::getenv("MRS_TG_ZERO_COPY");
-    return e == nullptr || std::atoi(e) != 0;
-  }();
+  const size_t stage_max = mrs_tg::knob::stage_max_bytes();
+  const bool zero_copy_allowed = mrs_tg::knob::zero_copy();
   struct Arr {
     const void* src;  // host source (inputs)
     void* dst;        // host destination (outputs)
@@ -1417,10 +1398,7 @@ static int solve_batch_impl(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* so,
           for (int q = 0; q < 4; ++q) moving_starts = moving_starts || vals[(v * 5 + k) * 4 + q] != 0.0;
     }
   }
-  struct MovingScope {
-    explicit MovingScope(bool on) { mrs_tg::set_moving_starts_hint(on); }
-    ~MovingScope() { mrs_tg::set_moving_starts_hint(false); }
-  } moving_scope(moving_starts);
+  mrs_tg::HintScope moving_scope(mrs_tg::set_moving_starts_hint, moving_starts);
   // zero copy: one pass over every array (fixed times, default solve) and every array the caller passed is pinned
   bool zero_copy = zero_copy_allowed && local.time_alloc_method == MRS_TG_TIME_ALLOC_NONE && !local.estimate_times &&
                    (local.flags & (MRS_TG_FLAG_GENERAL_PATTERNS | MRS_TG_FLAG_MATERIALIZED_BLOCKS)) == 0 &&

@@ -65,27 +65,16 @@ __device__ __forceinline__ void mapping_inverse_row(double T, int a, double (&ar
 // The blocks leave as STREAMING stores (round 6): 1 600 bytes per segment that the kernel itself never reads again.  Marked
 // non-temporal, a 16.5 MB launch takes 5.3 instead of 5.9 us (0.385 instead of 0.35 of the HBM peak), a 1.05 GB launch 154-157
 // instead of 161-165 us (0.84-0.85); the step that solves from the blocks right behind it finds fewer of them in the L2 and is
-// 0.5 us slower (12.7-13.5 -> 13.1-14.0 us per 1024 x 10 step).  -DMRS_TG_ASSEMBLE_NT=0: ordinary stores, as until round 5.
-#ifndef MRS_TG_ASSEMBLE_NT
-#define MRS_TG_ASSEMBLE_NT 1
-#endif
+// 0.5 us slower (12.7-13.5 -> 13.1-14.0 us per 1024 x 10 step).  (Ordinary stores until round 5.)
 __device__ __forceinline__ void store_block_rows(double T, int d, int a, size_t base, size_t P, double* __restrict__ Hout,
                                                  double* __restrict__ Aout) {
   double row[kN];
   hessian_row(T, d, a, row);
-#if MRS_TG_ASSEMBLE_NT
 #pragma unroll
   for (int c = 0; c < kN; ++c) __builtin_nontemporal_store(row[c], &Hout[base + (size_t)c * P]);
   mapping_inverse_row(T, a, row);
 #pragma unroll
   for (int c = 0; c < kN; ++c) __builtin_nontemporal_store(row[c], &Aout[base + (size_t)c * P]);
-#else
-#pragma unroll
-  for (int c = 0; c < kN; ++c) Hout[base + (size_t)c * P] = row[c];
-  mapping_inverse_row(T, a, row);
-#pragma unroll
-  for (int c = 0; c < kN; ++c) Aout[base + (size_t)c * P] = row[c];
-#endif
 }
 
 // general (ragged) batches: slot j holds the first slot_start[j+1] - slot_start[j] positions of the
@@ -108,9 +97,6 @@ __global__ __launch_bounds__(256) void assemble_blocks_kernel(BatchView b, int d
 // contiguous range (xcd_contiguous_index): the XCD that writes the blocks of paths [128 c, 128 c + 128) is then the XCD
 // whose tiles of the solve kernel read them (same partition of the paths over the XCDs), and finds them in its own L2.
 constexpr int kAssembleChunk = 128;
-#ifndef MRS_TG_ASSEMBLE_ORDER
-#define MRS_TG_ASSEMBLE_ORDER 2   // by size
-#endif
 __global__ __launch_bounds__(kAssembleChunk) void assemble_blocks_uniform_kernel(int n_paths, int S, int d,
                                                                                  const double* __restrict__ seg_times,
                                                                                  double* __restrict__ Hout,
@@ -120,9 +106,9 @@ __global__ __launch_bounds__(kAssembleChunk) void assemble_blocks_uniform_kernel
   // them.  Large launches: the CHUNK varies fastest -- the workgroups in flight then write neighbouring 1 KB runs of the same few
   // rows instead of runs scattered over the whole gigabyte (twenty arrays 512 KB apart per workgroup): 65536 x 10 on buffers the
   // driver placed badly 0.63-0.66 -> 0.73-0.75 of the HBM peak, on well-placed ones 0.78 -> 0.80 (round 6,
-  // profiles/round6_assembly_placement.txt); MRS_TG_ASSEMBLE_ORDER=0 / 1: the first / second order at every size (A / B builds)
+  // profiles/round6_assembly_placement.txt, whose A / B builds ran the first / second order at every size)
   const int n_chunks = (n_paths + kAssembleChunk - 1) / kAssembleChunk;
-  const bool chunk_fastest = MRS_TG_ASSEMBLE_ORDER == 1 || (MRS_TG_ASSEMBLE_ORDER == 2 && n_chunks >= 64);
+  const bool chunk_fastest = n_chunks >= 64;
   int chunk, rem;
   if (chunk_fastest) {
     const int logical = (int)blockIdx.x;
@@ -255,196 +241,6 @@ __global__ __launch_bounds__(64) void sample_kernel(BatchView b, const double* _
 }
 
 // ---------------------------------------------------------------------------------------------
-// The sampler of large launches (round 6): a GROUP of G = 8 or 16 lanes per path, 64 / G paths per wavefront, walk and
-// evaluation fused.  sample_kernel spends a whole wavefront on a walk that is a scalar, sequential algorithm: per path ~13
-// chunks, each with ~150 instructions of bookkeeping on all 64 lanes in front of the next (8 % of its wave cycles had a VALU
-// instruction in flight: profiles/round5_pmc_sq_nonlinear_65536.csv).  Here the same bookkeeping serves 64 / G paths at once:
-// per step lane j of a group adds dt to the group's time in segment j times (the reference's running sum, bit for bit), one
-// ballot finds in every group the first lane at which the walk stops (segment end, trajectory end, capacity), the lanes before
-// it evaluate the four polynomials of their path's segment (coefficients in LDS) and store their sample, and the stopping
-// lane's value seeds the group's next step; groups whose time has run over their segment carry it into the next one in a
-// predicated loop.  Same samples and counts as sample_kernel to the last bit
-// (tests/test_gpu_large_batches.py::test_separate_sampler_equals_the_sampler_in_the_solve_kernels_tail, test_gpu_round6.py).
-// (The round-5 verdict's proposal -- a lane-per-path walk that emits chunk descriptors + a sample-per-lane evaluation -- was
-// built first and measured 2.4 x SLOWER than sample_kernel at 65536 x 10: profiles/round6_sampler_two_kernel_ab.txt.)
-// LDS of a group: its path's segment times [Smax] and a RING of three segments' coefficients (the segment being walked, the
-// next one, and the slot the one after next is written to when the walk moves on).  With all S segments of every path staged
-// (26 KB per wavefront of eight 10-segment paths) a CU held six wavefronts and the SIMDs waited 62 % of their cycles
-// (profiles/round6_pmc_sampler.txt); the ring is 1 KB per path whatever its length.
-#ifndef MRS_TG_SAMPLE_EXP
-#define MRS_TG_SAMPLE_EXP 0   // experiment builds of the group sampler (python -m ...build --variant NAME -DMRS_TG_SAMPLE_EXP=n)
-#endif
-constexpr int kRingSlots = 3;
-__host__ __device__ constexpr int sample_group_ring_stride() { return kRingSlots * kD * kN + 10; }  // 130 doubles: 2 (mod 32), bank spread
-
-template <int G>
-__device__ __forceinline__ double group_lane_value(double v, int base, int idx) {  // lane base + idx of this wavefront
-  return __shfl(v, base + idx, 64);
-}
-
-template <int G, int NDER>
-__global__ __launch_bounds__(64, 4) void sample_group_kernel(BatchView b, const double* __restrict__ coeffs,
-                                                             const double* __restrict__ seg_times, double dt, int capacity,
-                                                             int32_t* __restrict__ n_samples, double* __restrict__ samples,
-                                                             const double* __restrict__ acc_table, int acc_n) {
-  constexpr int P = 64 / G;                       // paths per wavefront
-  constexpr int kPer = (kD * kN + G - 1) / G;     // coefficients a lane moves when its group's ring advances
-  extern __shared__ double lds[];                 // [P][Smax] segment times | [P] rings
-  const int lane = threadIdx.x, g = lane / G, j = lane % G, base = g * G;
-  const int Smax = b.max_segments;
-  const int q = blockIdx.x * P + g;
-  const bool active = q < b.n_paths;
-  const PathRef pr = path_at(b, active ? q : b.n_paths - 1);
-  const int S = pr.S;
-  double* s_T = lds + (size_t)g * Smax;
-  double* s_ring = lds + (size_t)P * Smax + (size_t)g * sample_group_ring_stride();
-  const double* __restrict__ cg = coeffs + (size_t)pr.s0 * (kD * kN);
-  if (b.uniform_S > 0) {  // the wavefront's paths are one contiguous run of segments: coalesced over all 64 lanes
-    const int q0 = blockIdx.x * P;
-    const int np = min(P, b.n_paths - q0);
-    const double* __restrict__ tg = seg_times + (size_t)q0 * S;
-    for (int e = lane; e < np * S; e += 64) lds[e] = tg[e];
-  } else if (active) {
-    for (int e = j; e < S; e += G) s_T[e] = seg_times[pr.s0 + e];
-  }
-  __syncthreads();
-  // every lane of a group carries the group's walk state (i, Ti, tin, n): t_end and the start segment as the reference
-  // computes them (trajectory.cpp:100-120, t_start = 0); N = #{k : A[k] < t_end} from the accumulated-time table
-  // (mrs_tg_sampling.hpp: "accumulated < t_end" for sample k is "k < N")
-  double t_end = 0.0;
-  for (int i = 0; i < S; ++i) t_end += s_T[i];
-  const double inv_dt = 1.0 / dt;
-  int n_total = 0;
-  if (t_end == t_end) {  // (a t_end that is not a number ends the reference's loop at once: no sample)
-    int k = (int)fmin(fmax(t_end * inv_dt - 1.0, 0.0), (double)(acc_n - 1));
-    while (k > 0 && acc_table[k - 1] >= t_end) --k;
-    while (k < acc_n && acc_table[k] < t_end) ++k;   // the first k with A[k] >= t_end
-    n_total = (k >= acc_n) ? 0x3fffffff : k;         // (none in the table: more samples than any buffer it was built for holds)
-  }
-  int i = 0;
-  {
-    double cum = 0.0;
-    for (i = 0; i < S; ++i) {
-      cum += s_T[i];
-      if (cum > 0.0) break;
-    }
-  }
-  bool done = !active || i >= S;
-  const bool eval = samples != nullptr;
-  // the ring: segments i and i + 1 into their slots (slot = segment mod 3), segment i + 2 requested into registers
-  double pre[kPer];
-  auto request = [&](int seg) {  // this lane's share of a segment's coefficients, global -> registers (no wait here)
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-      const int e = j * kPer + u;
-      pre[u] = (eval && !done && seg < S && e < kD * kN) ? cg[(size_t)seg * (kD * kN) + e] : 0.0;
-    }
-  };
-  auto deposit = [&](int seg) {  // ... registers -> the segment's slot
-    double* slot = s_ring + (seg % kRingSlots) * (kD * kN);
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-      const int e = j * kPer + u;
-      if (e < kD * kN) slot[e] = pre[u];
-    }
-  };
-  request(i);
-  deposit(i);
-  request(i + 1);
-  deposit(i + 1);
-  request(i + 2);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-  double dt_r[G];
-#pragma unroll
-  for (int r = 1; r < G; ++r) dt_r[r] = (j >= r) ? dt : 0.0;
-  double tin = 0.0;  // (t_start = 0: the walk enters the first segment of positive length at its start)
-  double Ti = done ? 0.0 : s_T[i];
-  int n = 0;
-  double* out = (eval && active) ? samples + (size_t)pr.p * capacity * (NDER + 1) * kD : nullptr;
-  for (;;) {
-    done = done || n >= n_total;  // trajectory.cpp:131
-    // carry the remainder into the next segment(s) (:132-139), group by group; a group that moves on deposits the segment
-    // after next (requested one segment ago) into the slot the segment it leaves behind no longer needs, and requests another
-    while (__ballot(!done && tin > Ti) != 0ull) {
-      if (!done && tin > Ti) {
-        tin = tin - Ti;
-        ++i;
-        if (i >= S) {
-          done = true;
-        } else {
-          Ti = s_T[i];
-          deposit(i + 1);
-          request(i + 2);
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");   // (LDS only: over every address space the fence
-      __builtin_amdgcn_wave_barrier();                                    //  waits for the previous step's sample stores as well)
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    }
-    if (__ballot(!done) == 0ull) break;
-    // lane j adds dt j times (the addends dt_r = j >= r ? dt : +0.0 are set up once: x + 0.0 is x, bit for bit, for x >= 0)
-    double tj = tin;
-#pragma unroll
-    for (int r = 1; r < G; ++r) tj += dt_r[r];
-    const bool ok = !done && (n + j < n_total) && !(tj > Ti) && (n + j <= capacity);
-    const unsigned long long ball = __ballot(ok);
-    const unsigned bits = (unsigned)(ball >> base) & ((1u << G) - 1u);
-    const int m = (bits == (1u << G) - 1u) ? G : __builtin_ctz(~bits);  // lanes [0, m) of the group emit a sample
-    if (out && j < m && n + j < capacity) {
-      const double* c = s_ring + (i % kRingSlots) * (kD * kN);
-      double* o = out + (size_t)(n + j) * (NDER + 1) * kD;
-#pragma unroll
-      for (int k = 0; k <= NDER; ++k) {
-        double v[kD];
-#pragma unroll
-        for (int dd = 0; dd < kD; ++dd) {
-#if MRS_TG_SAMPLE_EXP == 2   // experiment: no evaluation (no LDS coefficient reads, no Horner): the walk and the stores only
-          v[dd] = tj + (double)dd;
-          (void)c;
-#else
-          double accv = falling_factorial(kN - 1, k) * c[dd * kN + kN - 1];
-#pragma unroll
-          for (int jj = kN - 2; jj >= k; --jj) accv = accv * tj + falling_factorial(jj, k) * c[dd * kN + jj];
-          v[dd] = accv;
-#endif
-        }
-        if (k == 0) v[3] = wrap_heading(v[3]);
-#if MRS_TG_SAMPLE_EXP == 1   // experiment: the samples are computed and not stored
-#pragma unroll
-        for (int dd = 0; dd < kD; ++dd) asm volatile("" ::"v"(v[dd]));
-        (void)o;
-#else
-        {  // (streaming stores, as sample_kernel's: mrs_tg_sampling.hpp)
-          typedef double sample_pair __attribute__((ext_vector_type(2)));
-          sample_pair* o2 = reinterpret_cast<sample_pair*>(o + k * kD);
-          sample_pair lo, hi;
-          lo.x = v[0], lo.y = v[1], hi.x = v[2], hi.y = v[3];
-          __builtin_nontemporal_store(lo, o2);
-          __builtin_nontemporal_store(hi, o2 + 1);
-        }
-#endif
-      }
-    }
-    if (!done) {
-#if MRS_TG_SAMPLE_EXP == 3   // experiment: no cross-lane exchange (a wrong walk: every step advances by G samples' worth of time)
-      tin = tin + (double)(m > 0 ? m : 1) * dt;
-#else
-      if (m == G) {  // every lane emitted: the step ran out before the walk stopped
-        tin = group_lane_value<G>(tj, base, G - 1) + dt;
-      } else {       // lane m is the first that did not emit: its value is the walk's state at the stop
-        tin = group_lane_value<G>(tj, base, m);
-      }
-#endif
-      n += m;
-      if (n > capacity) done = true;  // overflow: reported as capacity + 1
-    }
-  }
-  if (active && j == 0 && n_samples) n_samples[pr.p] = n;
-}
-
-// ---------------------------------------------------------------------------------------------
 // launchers
 
 static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
@@ -483,19 +279,12 @@ hipError_t launch_solve_linear(const BatchView& b, int d, bool fused, const uint
     return launch_solve_tile(b, d, fused, mask, vals, seg_times, H, Ainv, coeffs, status, cost, status_in, stream);
   // (the one-lane-per-path solve from materialised blocks -- 512 registers and 264 bytes of scratch per lane -- is gone: a
   // blocks solve of a batch the tile kernel does not take runs four lanes per path whatever its size)
-  if (use_split_dims(b.n_paths) || !fused) {
-    dim3 grid(cdiv((long long)b.n_paths * 4, 64));
-    if (fused)
-      MRS_TG_LAUNCH_TIMED((solve_linear_kernel<1, true>), grid, dim3(64), 0, stream, b, d, mask, vals, seg_times, H, Ainv,
-                         ws, coeffs, status, cost, status_in);
-    else
-      MRS_TG_LAUNCH_TIMED((solve_linear_kernel<1, false>), grid, dim3(64), 0, stream, b, d, mask, vals, seg_times, H,
-                         Ainv, ws, coeffs, status, cost, status_in);
-  } else {
-    dim3 grid(cdiv(b.n_paths, 64));
-    MRS_TG_LAUNCH_TIMED((solve_linear_kernel<4, true>), grid, dim3(64), 0, stream, b, d, mask, vals, seg_times, H, Ainv,
-                        ws, coeffs, status, cost, status_in);
-  }
+  // (the parentheses are part of the names these launches have always noted)
+  const bool split = use_split_dims(b.n_paths) || !fused;
+  const auto linear = !split ? MRS_TG_KERNEL((solve_linear_kernel<4, true>))
+                      : fused ? MRS_TG_KERNEL((solve_linear_kernel<1, true>)) : MRS_TG_KERNEL((solve_linear_kernel<1, false>));
+  const dim3 grid(split ? cdiv((long long)b.n_paths * 4, 64) : cdiv(b.n_paths, 64));
+  MRS_TG_LAUNCH_TIMED(linear, grid, dim3(64), 0, stream, b, d, mask, vals, seg_times, H, Ainv, ws, coeffs, status, cost, status_in);
   return hipGetLastError();
 }
 
@@ -731,23 +520,8 @@ hipError_t sample_acc_table(double dt, int capacity, hipStream_t stream, const d
   return hipSuccess;
 }
 
-static size_t sample_group_lds_bytes(int Smax, int G) {
-  return (size_t)(64 / G) * ((size_t)Smax + sample_group_ring_stride()) * sizeof(double);
-}
-
-// Which sampler a launch takes: 0 = one wavefront per path (sample_kernel), 8 / 16 = sample_group_kernel with that many lanes
-// per path.  The group kernels need 64 / G paths' coefficients in LDS (40 KB at most: four wavefronts per CU and more) and
-// enough paths to fill the SIMDs with 64 / G of them per wavefront.  MRS_TG_SAMPLE_GROUP=0 | 8 | 16 forces.
-int sample_group_lanes(const BatchView& b) {
-  const char* env = std::getenv("MRS_TG_SAMPLE_GROUP");  // (read at every call: the tests run all three kernels)
-  const int forced = env ? std::atoi(env) : -1;
-  auto fits = [&](int G) { return sample_group_lds_bytes(b.max_segments, G) <= 40 * 1024; };
-  if (forced == 0) return 0;
-  if (forced == 8 || forced == 16) return fits(forced) ? forced : 0;
-  (void)fits;
-  return 0;  // measured slower than sample_kernel at every size so far (profiles/round6_sampler_group_ab.txt): on request only
-}
-
+// One wavefront per path at every size.  (A sampler of 8 or 16 lanes per path, walk and evaluation fused, was built in round 6 and
+// measured slower everywhere; it is gone, the record is profiles/round6_sampler_group_ab.txt.)
 template <int NDER>
 static hipError_t launch_sample_n(const BatchView& b, const double* coeffs, const double* seg_times, double dt, int capacity,
                                   int32_t* n_samples, double* samples, hipStream_t stream) {
@@ -758,31 +532,16 @@ static hipError_t launch_sample_n(const BatchView& b, const double* coeffs, cons
     hipError_t et = sample_acc_table(dt, capacity, stream, &acc_table, &acc_n, &pin);
     if (et != hipSuccess) return et;
   }
-  const int G = sample_group_lanes(b);
-  if (G != 0) {
-    const int P = 64 / G;
-    const size_t lds_g = sample_group_lds_bytes(b.max_segments, G);
-    const unsigned grid = (unsigned)((b.n_paths + P - 1) / P);
-    if (G == 8) {
-      note_kernel(NDER == 0 ? "sample_group_kernel<8, 0>" : "sample_group_kernel<8, NDER>");
-      if (!dry_run()) hipLaunchKernelGGL((sample_group_kernel<8, NDER>), dim3(grid), dim3(64), lds_g, stream, b, coeffs, seg_times, dt, capacity,
-                         n_samples, samples, acc_table, acc_n);
-    } else {
-      note_kernel(NDER == 0 ? "sample_group_kernel<16, 0>" : "sample_group_kernel<16, NDER>");
-      if (!dry_run()) hipLaunchKernelGGL((sample_group_kernel<16, NDER>), dim3(grid), dim3(64), lds_g, stream, b, coeffs, seg_times, dt, capacity,
-                         n_samples, samples, acc_table, acc_n);
-    }
-    return hipGetLastError();
-  }
   const size_t lds = sizeof(double) * ((size_t)b.max_segments * (1 + kD * kN) + kSampleBuffer) + sizeof(unsigned short) * kSampleBuffer;
   if (lds > 160 * 1024) return hipErrorInvalidValue;
+  const auto sampler = MRS_TG_KERNEL(sample_kernel<NDER>);
   if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)sample_kernel<NDER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = set_max_dynamic_lds(sampler, lds);
     if (e != hipSuccess) return e;
   }
   // one workgroup per path.  (Fewer, persistent workgroups that walk several paths each -- the kernel's loop allows it --
   // were measured in round 5: 65536 x 10 pipeline 1328 -> 1347 / 1385 / 1384 us with 15360 / 7680 / 3840 workgroups.)
-  MRS_TG_LAUNCH(sample_kernel<NDER>, dim3((unsigned)b.n_paths), dim3(64), lds, stream, b, coeffs, seg_times, dt, capacity,
+  MRS_TG_LAUNCH(sampler, dim3((unsigned)b.n_paths), dim3(64), lds, stream, b, coeffs, seg_times, dt, capacity,
                      n_samples, samples, acc_table, acc_n);
   return hipGetLastError();
 }

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "../../include/mrs_tg.h"
+#include "mrs_tg_knobs.hpp"
 
 struct mrs_tg_ctx;
 
@@ -30,6 +31,17 @@ bool constrained_slots_hint();
 // flag for it); read by launch_nonlinear's choice between the plan's dimension split and lane groups
 void set_moving_starts_hint(bool on);
 bool moving_starts_hint();
+// a hint set for the scope of one ABI call of the calling thread and cleared behind it
+struct HintScope {
+  void (*set)(bool);
+  HintScope(void (*setter)(bool), bool on) : set(setter) { set(on); }
+  ~HintScope() { set(false); }
+  HintScope(const HintScope&) = delete;
+  HintScope& operator=(const HintScope&) = delete;
+};
+// compute units of the calling thread's current device, looked up once per device ordinal (a process may drive devices of
+// different sizes or partitions); 256 while the runtime cannot say
+int device_compute_units();
 KernelTimer take_kernel_timer();  // the pending pair (null events when nothing is pending); consumed by the call
 void set_kernel_timer(hipEvent_t start, hipEvent_t stop);  // arms the next timed launch of this thread
 // Kernel trace (mrs_tg_kernel_trace): every launch of the library notes its kernel's name in a small per-thread ring, so
@@ -41,33 +53,53 @@ int kernel_trace(const char** names_out, int capacity);  // oldest first; at mos
 // hint exactly as in a real call -- and NOTE the kernels they would launch, but enqueue nothing
 bool dry_run();
 void set_dry_run(bool on);
+// One kernel of a launcher's choice: the host function with the name that note_kernel records.  The instantiations a launcher
+// chooses between share one signature, so the choice is an ordinary ?: over these values, made once and handed to both
+// hipFuncSetAttribute (set_max_dynamic_lds) and the launch.  MRS_TG_KERNEL(solve_quad_kernel<false, true>) notes exactly that
+// text, and MRS_TG_KERNEL((solve_linear_kernel<1, true>)) its parentheses too: the names are interface (mrs_tg_kernel_trace,
+// mrs_tg_plan_explain) and stay as they always were; a name no expression spells goes to kernel_as directly.
+template <class... Args>
+struct Kernel {
+  void (*fn)(Args...);
+  const char* name;
+};
+template <class... Args>
+constexpr Kernel<Args...> kernel_as(void (*fn)(Args...), const char* name) { return {fn, name}; }
+#define MRS_TG_KERNEL(...) ::mrs_tg::kernel_as(__VA_ARGS__, #__VA_ARGS__)
+// (the launch macros take a Kernel or a kernel written in place, which is noted as written)
+template <class... Args>
+constexpr auto kernel_fn(const Kernel<Args...>& k) { return k.fn; }
+template <class... Args>
+constexpr auto kernel_fn(void (*fn)(Args...)) { return fn; }
+template <class... Args>
+constexpr const char* kernel_name(const Kernel<Args...>& k, const char*) { return k.name; }
+template <class... Args>
+constexpr const char* kernel_name(void (*)(Args...), const char* written) { return written; }
+template <class... Args>
+inline hipError_t set_max_dynamic_lds(const Kernel<Args...>& k, size_t bytes) {
+  return hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
 // launch with the pending timer, if any
 #define MRS_TG_LAUNCH_TIMED(kernel, grid, block, lds, stream, ...)                                           \
   do {                                                                                                       \
     const ::mrs_tg::KernelTimer kt__ = ::mrs_tg::take_kernel_timer();                                        \
-    ::mrs_tg::note_kernel(#kernel);                                                                          \
+    ::mrs_tg::note_kernel(::mrs_tg::kernel_name(kernel, #kernel));                                           \
     if (!::mrs_tg::dry_run())                                                                                \
-      hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, kt__.start, kt__.stop, 0, __VA_ARGS__);        \
-  } while (0)
-// the same for a kernel template of two arguments (a comma inside a macro argument needs parentheses, which would end up in the
-// noted name): MRS_TG_LAUNCH_TIMED_T2(kernel, A, B, grid, ...) launches kernel<A, B> and notes "kernel<A, B>"
-#define MRS_TG_LAUNCH_TIMED_T2(kernel, A, B, grid, block, lds, stream, ...)                                        \
-  do {                                                                                                             \
-    const ::mrs_tg::KernelTimer kt__ = ::mrs_tg::take_kernel_timer();                                              \
-    ::mrs_tg::note_kernel(#kernel "<" #A ", " #B ">");                                                             \
-    if (!::mrs_tg::dry_run())                                                                                      \
-      hipExtLaunchKernelGGL((kernel<A, B>), grid, block, lds, stream, kt__.start, kt__.stop, 0, __VA_ARGS__);      \
+      hipExtLaunchKernelGGL(::mrs_tg::kernel_fn(kernel), grid, block, lds, stream, kt__.start, kt__.stop, 0, __VA_ARGS__); \
   } while (0)
 // plain launches, and launches that carry the events of a multi-kernel timing themselves
-#define MRS_TG_LAUNCH(kernel, ...)                \
-  do {                                            \
-    ::mrs_tg::note_kernel(#kernel);               \
-    if (!::mrs_tg::dry_run()) hipLaunchKernelGGL(kernel, __VA_ARGS__);      \
+#define MRS_TG_LAUNCH(kernel, ...)                                                    \
+  do {                                                                                \
+    ::mrs_tg::note_kernel(::mrs_tg::kernel_name(kernel, #kernel));                    \
+    if (!::mrs_tg::dry_run()) {                                                       \
+      const auto fn__ = ::mrs_tg::kernel_fn(kernel);                                  \
+      hipLaunchKernelGGL(fn__, __VA_ARGS__);                                          \
+    }                                                                                 \
   } while (0)
-#define MRS_TG_LAUNCH_EXT(kernel, ...)            \
-  do {                                            \
-    ::mrs_tg::note_kernel(#kernel);               \
-    if (!::mrs_tg::dry_run()) hipExtLaunchKernelGGL(kernel, __VA_ARGS__);   \
+#define MRS_TG_LAUNCH_EXT(kernel, ...)                                                \
+  do {                                                                                \
+    ::mrs_tg::note_kernel(::mrs_tg::kernel_name(kernel, #kernel));                    \
+    if (!::mrs_tg::dry_run()) hipExtLaunchKernelGGL(::mrs_tg::kernel_fn(kernel), __VA_ARGS__);   \
   } while (0)
 
 // records `message` as the context's (and the global) last error and returns `code`
@@ -122,10 +154,9 @@ hipError_t launch_copy_samples(const double* src, double* dst, const int32_t* n_
 
 hipError_t launch_estimate_times(const BatchView& b, const double* wp, const double* limits, double* seg_times,
                                  hipStream_t stream);
-// (large launches: 8 or 16 lanes per path, 64 / G paths per wavefront -- sample_group_kernel; else one wavefront per path)
+// (one wavefront per path: sample_kernel)
 hipError_t launch_sample(const BatchView& b, const double* coeffs, const double* seg_times, double dt, int capacity,
                          int32_t* n_samples, double* samples, hipStream_t stream);
-int sample_group_lanes(const BatchView& b);  // 0 | 8 | 16: which sampler a launch of this batch takes
 // the same walk, every sample with its derivative orders 0..4: states [n_paths][capacity][kSampleStateOrders][4]
 constexpr int kSampleStateOrders = 5;
 hipError_t launch_sample_states(const BatchView& b, const double* coeffs, const double* seg_times, double dt, int capacity,

@@ -33,8 +33,6 @@
 // oracle/mto_nonlinear.c.
 #include <hip/hip_runtime.h>
 
-#include <map>
-#include <mutex>
 
 #include <algorithm>
 #include <cfloat>
@@ -380,18 +378,15 @@ constexpr int kLeanPub = 3 * 28;  // evaluate_lean_shared's hand-over area: thre
 constexpr int kLeanMoving = 18;
 __host__ __device__ constexpr int lean_eval_doubles(int Sb) { return 4 * Sb + 4 * (Sb + 1) + kLeanPub + kLeanMoving; }  // dp, staging area, hand-over, moving start
 
-// MRS_TG_LEAN_CONST_TABLE=1 (an A / B build, NOT the default): the 45 table constants as compile-time operands -- SGPR pairs the
-// scalar unit sets up -- instead of 90 VGPRs per lane, and ONE table for both sweep directions (mrs_tg_sweep.hpp, PsTab).
-// Bit-identical results; measured in round 5 (same box, scripts/lean_ab.py): optimize_lean_shared_kernel 256 VGPRs + 80 B of
+// The 45 table constants live in 90 VGPRs per lane, one table per sweep direction.  As compile-time operands -- SGPR pairs the
+// scalar unit sets up -- and ONE table for both sweep directions (an A / B build of round 5, profiles/round5_lean_table_ab.txt):
+// bit-identical results; measured in round 5 (same box, scripts/lean_ab.py): optimize_lean_shared_kernel 256 VGPRs + 80 B of
 // scratch -> 202 VGPRs without scratch and 3 % SLOWER (8192 x 10: 126.4 -> 130.9 us, 65536 x 10: 569 -> 575 us), the mixed
 // kernel of ragged batches 9 % slower (334 -> 365 us); compiled for three wavefronts per SIMD (168 VGPRs + 80 B) slower again
 // (149 us).  The kernels issue one FP64 instruction per 6.2 SIMD cycles with two wavefronts resident against 4.9-5.1 at best
 // (scripts/dpp_probe.hip): bound by their instruction count, not by registers or occupancy -- and the two s_mov_b32 per
 // constant use are instructions too.
-#ifndef MRS_TG_LEAN_CONST_TABLE
-#define MRS_TG_LEAN_CONST_TABLE 0
-#endif
-#define LEAN1_TAB(e) (MRS_TG_LEAN_CONST_TABLE ? PsTab<4>::at(e) : tab[e])
+#define LEAN1_TAB(e) tab[e]
 template <bool MASKED>
 __device__ __forceinline__ double evaluate_lean(const double* tabs, const double* ev, int S, int Sb, int d, const double* pt,
                                                 double* grad, int g, int G, bool active, int* tripped) {
@@ -407,7 +402,7 @@ __device__ __forceinline__ double evaluate_lean(const double* tabs, const double
     const int k = g + (r << g_shift);
     double Jk = 0.0, qfk = 0.0;
     if (!MASKED && active && k <= S && (k == 0 || S > 1)) {
-      // (the table: compile-time constants of order 4 -- the plain-path kernels never run another order; mrs_tg_sweep.hpp, PsTab)
+      // (the powers: a compile-time objective order of 4 -- the plain-path kernels never run another order)
       // The plain sweep (start | interior ... | end), written out for four dimensions per lane with the smallest live set
       // the step allows.  The right-hand-side brackets are not materialised per (dimension, row) (FastStep::w: 36 doubles
       // that lived across the whole step and pushed the kernel to 256 VGPRs + 116 bytes of scratch): row r of every
@@ -554,11 +549,7 @@ __device__ __forceinline__ double evaluate_lean(const double* tabs, const double
 // their partner's state to their own and factor the middle vertex.  For plain paths with 4 <= S and S + 4 <= G.
 //   lanes of the group: 0: x left | 1 .. m: vector k = lane, left | m + 1: B' left |
 //                       m + 2: x right | m + 2 + r: vector m + r, right (r = 1 .. S - m) | S + 3: B' right
-#if MRS_TG_LEAN_CONST_TABLE
-#define LEAN_TAB(e) PsTab<4>::at(e)
-#else
 #define LEAN_TAB(e) Tab_regs.at(e)
-#endif
 // ENDS: the two end vertices may leave derivative slots free (rest-to-rest paths under an objective order below snap: jerk
 // and / or snap stay free there; stage_ps leaves the two free masks in front of qs).  The first step of a half sweep then
 // eliminates the end vertex like any other vertex -- the block of the segment's near part with the rows and columns of the
@@ -575,7 +566,6 @@ template <bool ENDS, bool MOVING>
 __device__ __forceinline__ double evaluate_lean_shared_pass(const double* tabs, const double* ev, double* pub, int S, int Sb, int d,
                                                             const double* pt, double* grad, int gv, bool active, int* tripped,
                                                             int j0_lane, bool have_j0, double j0_in) {
-  static_assert(!(ENDS && MRS_TG_LEAN_CONST_TABLE), "the compile-time table is the order-4 one");
   const double* mv = pub + kLeanPub;
   const bool moving = MOVING && mv[0] != 0.0;
   const double* dp = ev;
@@ -588,14 +578,7 @@ __device__ __forceinline__ double evaluate_lean_shared_pass(const double* tabs, 
   const bool pure = r == nhalf + 1, base = r == 0;
   const int k = base ? 0 : pure ? (left ? S : 1) : (left ? r : m + r);
   const double corr = kGradStep / ((double)S - 1.0);
-  // the table: compile-time constants of order 4, the same for both directions (mrs_tg_sweep.hpp, PsTab): a right-to-left
-  // lane sweeps in sign-transformed variables and `flip` = -1 puts its state into the common frame where it meets a left one
-#if MRS_TG_LEAN_CONST_TABLE
-  using Tab = PsTab<4>;
-  const double flip = left ? 1.0 : -1.0;
-  (void)tabs;
-  (void)d;
-#else  // (A / B build: the per-lane table of its direction in 90 registers, as until round 4)
+  // the table of this lane's direction, in 90 registers
   struct {
     double t[kPsTable];
     __device__ __forceinline__ double at(int e) const { return t[e]; }
@@ -605,8 +588,6 @@ __device__ __forceinline__ double evaluate_lean_shared_pass(const double* tabs, 
 #pragma unroll
     for (int e = 0; e < kPsTable; ++e) Tab_regs.t[e] = tsrc[e];
   }
-  const double flip = 1.0;
-#endif
   double Sm[10], y[kNB][4], qf = 0.0, red = 0.0;
 #pragma unroll
   for (int e = 0; e < 10; ++e) Sm[e] = 0.0;
@@ -764,7 +745,6 @@ __device__ __forceinline__ double evaluate_lean_shared_pass(const double* tabs, 
   const bool base_right = !left && base;
   if (valid && (pure || base_right)) {
     double* ps = pub + (base_right ? 0 : (left ? 2 : 1)) * 28;
-    lean_flip_state(Sm, y, flip);  // a right lane's state leaves in the common (left-to-right) frame
 #pragma unroll
     for (int e = 0; e < 10; ++e) ps[e] = Sm[e];
 #pragma unroll
@@ -779,7 +759,6 @@ __device__ __forceinline__ double evaluate_lean_shared_pass(const double* tabs, 
   double Jk = 0.0, qfk = 0.0;
   if (join) {
     const double* ps = pub + (left ? (base ? 0 : 1) : 2) * 28;
-    lean_flip_state(Sm, y, flip);  // a right lane joins in the common frame as well (the factorisation's |z|^2 is frame-independent)
 #pragma unroll
     for (int e = 0; e < 10; ++e) Sm[e] += ps[e];
 #pragma unroll
@@ -1929,7 +1908,7 @@ __global__ __launch_bounds__(64) void cost_gradient_kernel(BatchView b, int d, i
 
 // split the four dimensions over lanes while the batch is too small to fill the machine otherwise
 static int dim_split_for(int n_paths, int max_S) {
-  if (const char* e = std::getenv("MRS_TG_DIM_SPLIT_MAX_PATHS")) return n_paths <= std::atoi(e) ? 4 : 1;  // tuning knob
+  if (const int forced = knob::dim_split_max_paths(); forced != knob::kUnset) return n_paths <= forced ? 4 : 1;  // tuning knob
   // One lane per dimension pays while a path's (S + 1) x 4 lanes fit ONE wavefront: from 16 segments on the split kernel
   // walks a path in several passes and the lean kernel's lane groups are 2-3x faster at every batch size (whole pipeline,
   // scripts/measure_configs.py uniform<P>x<S>, profiles/round5_dim_split_crossover.txt: 256 x 16 0.378 vs 0.168 ms,
@@ -1962,11 +1941,8 @@ constexpr int kLeanTwoPassMaxS = 121;  // evaluate_lean_shared: 3 publishers + 6
 // lanes per path when EVERY path of kEndsMinSegments or more segments gets its S + 4 lanes (0: no group is wide enough).
 // Two segments are enough for the shared half sweeps (one step per half); handing the 2- and 3-segment paths of a ragged
 // batch to the sweeping kernel BEHIND the launch instead cost 8192 ragged paths 0.67 instead of 0.58 ms (d = 2).
-// MRS_TG_ENDS_MIN_SEGMENTS: tuning / test knob, read once per process
-static const int kEndsMinSegments = [] {
-  const char* e = std::getenv("MRS_TG_ENDS_MIN_SEGMENTS");
-  return e ? std::max(2, std::atoi(e)) : 2;
-}();
+// MRS_TG_ENDS_MIN_SEGMENTS: tuning / test knob, read when the library is loaded
+static const int kEndsMinSegments = knob::ends_min_segments();
 static int group_for_ends(int S) {
   if (S < kEndsMinSegments) return group_for(S, 1);
   if (S + 4 > 64) return S <= kLeanTwoPassMaxS ? 64 : 0;  // a wavefront per path, two passes of the shared evaluation
@@ -2022,49 +1998,35 @@ int nonlinear_plan_build(NonlinearPlan& nl, const std::vector<int32_t>& so, cons
   return 0;
 }
 
-void nonlinear_plan_free(NonlinearPlan& nl) {
-  if (nl.d_ws) (void)mrs_tg::pool_free(nl.d_ws);
-  if (nl.d_opt_status) (void)mrs_tg::pool_free(nl.d_opt_status);
-  if (nl.d_maxima) (void)mrs_tg::pool_free(nl.d_maxima);
-  if (nl.d_sum_t0) (void)mrs_tg::pool_free(nl.d_sum_t0);
-  nl.d_sum_t0 = nullptr;
-  if (nl.d_queue) (void)mrs_tg::pool_free(nl.d_queue);
-  nl.d_queue = nullptr;
-  if (nl.d_general) (void)mrs_tg::pool_free(nl.d_general);
-  nl.d_general = nullptr;
-  if (nl.d_general_ws) (void)mrs_tg::pool_free(nl.d_general_ws);
-  nl.d_general_ws = nullptr;
-  if (nl.d_general_solve_ws) (void)mrs_tg::pool_free(nl.d_general_solve_ws);
-  nl.d_general_solve_ws = nullptr;
-  if (nl.d_general_t0) (void)mrs_tg::pool_free(nl.d_general_t0);
-  nl.d_general_t0 = nullptr;
-  if (nl.d_careful) (void)mrs_tg::pool_free(nl.d_careful);
-  nl.d_careful = nullptr;
-  if (nl.d_fallback) (void)mrs_tg::pool_free(nl.d_fallback);
-  nl.d_fallback = nullptr;
-  if (nl.d_careful_ws) (void)mrs_tg::pool_free(nl.d_careful_ws);
-  nl.d_careful_ws = nullptr;
-  nl.careful_ws_doubles = 0;
-  if (nl.d_dfo_vec) (void)mrs_tg::pool_free(nl.d_dfo_vec);
-  if (nl.d_dfo_f) (void)mrs_tg::pool_free(nl.d_dfo_f);
-  if (nl.d_dfo_state) (void)mrs_tg::pool_free(nl.d_dfo_state);
-  if (nl.d_dfo_fidx) (void)mrs_tg::pool_free(nl.d_dfo_fidx);
-  if (nl.d_dfo_segcost) (void)mrs_tg::pool_free(nl.d_dfo_segcost);
-  if (nl.d_dfo_seg_path) (void)mrs_tg::pool_free(nl.d_dfo_seg_path);
-  if (nl.d_dfo_deadline) (void)mrs_tg::pool_free(nl.d_dfo_deadline);
-  nl.d_dfo_deadline = nullptr;
-  nl.d_dfo_fidx = nullptr;
-  nl.d_dfo_segcost = nullptr;
-  nl.d_dfo_seg_path = nullptr;
-  nl.d_dfo_vec = nullptr;
-  nl.d_dfo_f = nullptr;
-  nl.d_dfo_state = nullptr;
-  nl.d_ws = nullptr;
-  nl.d_opt_status = nullptr;
-  nl.d_maxima = nullptr;
-  nl.ws_doubles = 0;
+template <class T>
+static void release(T*& p) {
+  if (p) (void)mrs_tg::pool_free(p);
+  p = nullptr;
 }
 
+void nonlinear_plan_free(NonlinearPlan& nl) {
+  release(nl.d_ws);
+  release(nl.d_opt_status);
+  release(nl.d_maxima);
+  release(nl.d_sum_t0);
+  release(nl.d_queue);
+  release(nl.d_general);
+  release(nl.d_general_ws);
+  release(nl.d_general_solve_ws);
+  release(nl.d_general_t0);
+  release(nl.d_careful);
+  release(nl.d_fallback);
+  release(nl.d_careful_ws);
+  release(nl.d_dfo_vec);
+  release(nl.d_dfo_f);
+  release(nl.d_dfo_state);
+  release(nl.d_dfo_fidx);
+  release(nl.d_dfo_segcost);
+  release(nl.d_dfo_seg_path);
+  release(nl.d_dfo_deadline);
+  nl.ws_doubles = 0;
+  nl.careful_ws_doubles = 0;
+}
 
 constexpr int kCarefulCap = 1024;  // paths per call that can be re-run with primal costs; further ones keep the fast result
 
@@ -2074,8 +2036,7 @@ hipError_t nonlinear_ensure_buffers(NonlinearPlan& nl, const BatchView& b) {
   hipError_t e;
   const size_t need = linear_workspace_doubles(b);
   if (nl.ws_doubles < need) {
-    if (nl.d_ws) (void)mrs_tg::pool_free(nl.d_ws);
-    nl.d_ws = nullptr;
+    release(nl.d_ws);
     nl.ws_doubles = 0;
     if ((e = mrs_tg::pool_alloc(&nl.d_ws, need * sizeof(double))) != hipSuccess) return e;
     nl.ws_doubles = need;
@@ -2098,7 +2059,7 @@ hipError_t nonlinear_ensure_buffers(NonlinearPlan& nl, const BatchView& b) {
 // those (masked step at the two ends of the sweep), at one wavefront per SIMD -- 256 + 74 registers; forced to two it spills
 // 96 and loses to the general kernel (8192 x 10 random-walk paths at d = 2: 429 vs 365 us; at one wavefront 332 us).
 static bool lean_applies(int dim_split) {
-  if (const char* e = std::getenv("MRS_TG_LEAN")) return std::atoi(e) != 0;
+  if (const int forced = knob::lean_forced(); forced >= 0) return forced != 0;
   return dim_split == 1;
 }
 
@@ -2137,6 +2098,197 @@ hipError_t nonlinear_prepare_general(NonlinearPlan& nl, const BatchView& b, cons
   return hipGetLastError();
 }
 
+// ---- the route of a call: WHICH kernels launch_nonlinear enqueues, with which bins, grid and LDS -- decided here, from the plan,
+// the batch, the call's options and hints, the knobs (mrs_tg_knobs.hpp) and the device's compute units; nothing is allocated or
+// launched, and no HIP call is made
+using LeanKernel = Kernel<BatchView, NonlinearParams, BinTable, const uint8_t*, const double*, double*, int32_t*, int32_t*>;
+using SweepKernel = Kernel<BatchView, NonlinearParams, BinTable, const uint8_t*, const double*, double*, int32_t*>;
+
+struct OuterLaunch {
+  BinTable bins{};
+  int blocks = 0;
+  unsigned threads = 64;
+  size_t lds_bytes = 0;
+};
+
+// what follows the outer loop
+enum class Closing {
+  kRowsPipeline,  // solve -> maxima -> scaling -> solve (-> sampling) in one launch of the rows kernel
+  kQuadTail,      // solve, maxima, then the scaling on the quad kernel's final solve (the caller's sampler follows)
+  kRowsTail,      // solve, maxima, then scaling (and sampling) on the rows kernel's final solve
+  kSeparate,      // solve, maxima, scaling, runaway test and final solve as launches of their own
+};
+
+struct NonlinearRoute {
+  bool estimate_in_kernel = false;  // the outer-loop kernels compute the start point themselves (else: a launch in front of them)
+  int dim_split = 1;                // of THIS call: 1 where it goes back from the plan's dimension split to lane groups
+  // 1a. the lean kernel takes every plain path and flags the others for the sweeping kernel behind it
+  bool lean = false;
+  LeanKernel lean_kernel{};
+  OuterLaunch lean_launch;
+  bool queued = false;              // the launch holds what is resident; lane groups claim further paths from the plan's queue
+  // 1b. the sweeping kernel: alone, or behind the lean kernel for the paths that one flagged
+  bool wave = false;                // one wavefront per path (mrs_tg_wave.hip) instead of the kernel below
+  bool sweep_fits = true;           // false: more than five bins or more LDS than a workgroup can have -- the call fails there
+  SweepKernel sweep_kernel{};
+  OuterLaunch sweep_launch;
+  bool careful = false;             // 1c. the careful re-run follows
+  bool general = false;             // 1d. the outer loop of the paths with a position-free vertex follows (and their solves below)
+  bool certified_maxima = true;     // segment_maxima_scaling_kernel, else every entry searched (segment_maxima9_kernel)
+  Closing closing = Closing::kSeparate;
+  bool tail_samples = false;        // the sampling rides on the closing launch
+};
+
+// the kernel's table of `bins`; returns the largest lds_of(bin) and leaves the workgroup count in *blocks
+template <class LdsOf>
+static size_t fill_bin_table(BinTable& bt, const std::vector<NonlinearBin>& bins, LdsOf lds_of, int* blocks) {
+  bt.n = (int)bins.size();
+  size_t lds = 0;
+  *blocks = 0;
+  for (int i = 0; i < bt.n; ++i) {
+    const NonlinearBin& bin = bins[i];
+    bt.group[i] = bin.group;
+    bt.q_begin[i] = bin.q_begin;
+    bt.q_count[i] = bin.q_count;
+    bt.max_S[i] = bin.max_S;
+    bt.block_begin[i] = *blocks;
+    *blocks += (int)cdiv_u(bin.q_count, 64 / bin.group);
+    lds = std::max(lds, lds_of(bin));
+  }
+  return lds;
+}
+
+// hints: those of the calling thread's ABI call (constrained_slots_hint, moving_starts_hint); compute_units: of the current device
+// (device_compute_units); estimate: the search starts from the estimate; samples_wanted: the caller asked for samples
+static NonlinearRoute route_nonlinear(const NonlinearPlan& nl, const BatchView& b, int derivative, bool constrained_slots,
+                                      bool moving_starts, int compute_units, bool estimate, bool general, bool careful,
+                                      bool samples_wanted) {
+  NonlinearRoute r;
+  r.general = general;
+  r.careful = careful;
+  // the start point is the estimate: computed by the outer-loop kernels themselves (start_time), by a launch of its own in
+  // front of the kernels that read their start from a copy
+  // (every outer-loop kernel but the one for position-free paths and the careful re-run, which start from a copy of the times)
+  r.estimate_in_kernel = estimate && !general && !careful;
+  // The split of the four dimensions over lanes is the PLAN's choice (batch size and longest path); this CALL goes back to
+  // lane groups where the split kernel would hand its paths to the general step anyway and the groups are 10-25 % faster:
+  // 13-15 segments (<= 1536 paths) under an objective order below snap, or when the caller says that vertices hold
+  // constrained slots (stop_at waypoints: MRS_TG_FLAG_CONSTRAINED_SLOTS) or mrs_tg_solve_batch has seen a moving start in
+  // its host copy of the values.  MRS_TG_REGROUP=0 switches it off.
+  const bool regroup = knob::regroup() && nl.regroup_possible && (derivative < 4 || constrained_slots || moving_starts);
+  r.dim_split = regroup ? 1 : nl.dim_split;
+  const std::vector<NonlinearBin>& plan_bins = regroup ? nl.bins1 : nl.bins;
+  r.lean = lean_applies(r.dim_split) && (int)plan_bins.size() <= 5;
+  auto plain_lds = [](const NonlinearBin& bin) {
+    return ((size_t)(64 / bin.group) * lean_group_doubles(bin.max_S) + 2 * kPsTable) * sizeof(double);
+  };
+  auto all_fit = [&](const std::vector<NonlinearBin>& bins) {
+    for (const NonlinearBin& bin : bins)
+      if (plain_lds(bin) > 160 * 1024) return false;
+    return true;
+  };
+  // Which lane groups.  The shared half sweeps halve the steps of an evaluation but need S + 4 lanes, the next group width
+  // for 13-15 and 29-30 segments: half the paths per wavefront for (S/2 + 1)/S of the steps -- more instructions per path,
+  // so a launch of many residency rounds (a saturated device: the kernel is bound by its instruction count) keeps the
+  // narrow groups and their one-sided sweeps.  A launch of a few residency rounds lasts about as long as its slowest
+  // wavefronts -- ten evaluations of the longest paths -- and there the wide groups win: whole pipeline, wide vs narrow,
+  // 8192 ragged 0.57 vs 0.65 ms, 8192 x 14 0.395 vs 0.425, 16384 x 14 0.644 vs 0.674, 32768 x 30 3.33 vs 3.51,
+  // 32768 ragged 1.87 vs 1.89; past that narrow: 65536 x 14 2.03 vs 1.97 ms (profiles/round5_wide_groups_ab.txt).
+  // (MRS_TG_LEAN_WIDE=0 / 1 forces.)
+  // (per device: a process may drive devices of different sizes or partitions, and the first call's figure is not theirs)
+  const int resident_waves = compute_units * 4 * MRS_TG_LEAN_WAVES;
+  const int lean_shared = knob::lean_shared();
+  const int wide_forced = knob::lean_wide_forced();
+  const bool lean_masked = derivative < 4;  // rest-to-rest paths end on vertices with free slots
+  const bool wide = !nl.wide_bins.empty() && (int)nl.wide_bins.size() <= 5 && !lean_masked && lean_shared != 0 &&
+                    (wide_forced >= 0 ? wide_forced == 1 : nl.wide_blocks <= 8 * resident_waves) && all_fit(nl.wide_bins);
+  // objective orders below snap: the shared half sweeps with free end slots, every path in a group of S + 4 lanes at least
+  // (MRS_TG_LEAN_SHARED=0: the one-sided masked sweeps of optimize_lean_masked_kernel, as until round 5)
+  // (a min-snap launch whose caller says that interior vertices may hold constrained slots -- stop_at waypoints -- as well:
+  // MRS_TG_FLAG_CONSTRAINED_SLOTS)
+  const bool ends_shared = (lean_masked || constrained_slots) && lean_shared != 0 && !nl.ends_bins.empty() &&
+                           (int)nl.ends_bins.size() <= 5 && all_fit(nl.ends_bins);
+  // min-snap launches of a few residency rounds: EVERY path of two or more segments in a group of S + 4 lanes (the bins of the
+  // free-end kernel), so that the kernel with only the shared half sweeps runs -- the one that takes moving starts; 5-7
+  // segments then pay 3-4 % for their wider groups when they start at rest (MRS_TG_LEAN_WIDE_ALL=0: only 13-15 and 29-30
+  // segments move up and a ragged batch runs the mixed kernel, whose one-sided sweeps leave moving starts to the sweeping kernel)
+  const bool wide_shared_all = wide && knob::lean_wide_all() && !nl.ends_bins.empty() && (int)nl.ends_bins.size() <= 5;
+  const std::vector<NonlinearBin>& lean_bins = (ends_shared || wide_shared_all) ? nl.ends_bins : wide ? nl.wide_bins : plan_bins;
+  r.lean = r.lean && all_fit(lean_bins);
+  if (r.lean) {
+    OuterLaunch& L = r.lean_launch;
+    L.lds_bytes = fill_bin_table(L.bins, lean_bins, plain_lds, &L.blocks);
+    // A uniform batch of more wavefronts than the device holds at once (two per SIMD): launch what is resident and let a
+    // lane group whose path has stopped claim the next one (optimize_body, `queued`), instead of eight rounds of wavefronts
+    // that each last as long as the slowest of their four paths.  65536 x 10: 780 -> us.
+    // (what the FIRST device to run a lean launch holds, for the whole process -- a process that drives devices of different
+    // sizes queues as it always has; changing that is for another day.  MRS_TG_LEAN_RESIDENT_BLOCKS: tuning knob; 0 = no queue)
+    static const int resident_blocks =
+        knob::lean_resident_blocks() != knob::kUnset ? knob::lean_resident_blocks() : compute_units * 4 * MRS_TG_LEAN_WAVES;
+    if (L.bins.n == 1 && resident_blocks > 0 && L.blocks > resident_blocks) {
+      L.blocks = resident_blocks;
+      r.queued = true;
+    }
+    // shared half sweeps (evaluate_lean_shared) where every path of every bin has its S + 4 lanes
+    // (with a bin of paths shorter than four segments beside them the kernel that has both evaluations compiled in runs, the
+    // short paths in wavefronts of their own next to the others: handing them to the compact kernel BEHIND the launch cost
+    // 66 us on 8192 ragged paths, profiles/round5_wide_groups_ab.txt)
+    bool lean_shared_only = lean_shared != 0 && !lean_masked;
+    bool long_paths = false;  // a bin whose paths have more half sweeps than a wavefront has lanes: the two-pass instantiations
+    for (const NonlinearBin& bin : lean_bins) {  // (a bin of one-segment paths: the kernel leaves them to the sweeping kernel behind it)
+      if (bin.max_S >= 2 && (bin.min_S < 2 || (bin.max_S + 4 > bin.group && !(bin.group == 64 && bin.max_S <= kLeanTwoPassMaxS))))
+        lean_shared_only = false;
+      if (bin.max_S + 4 > bin.group && bin.group == 64) long_paths = true;
+    }
+    const bool ends_long = long_paths && (ends_shared || lean_shared_only);
+    r.lean_kernel = ends_long          ? MRS_TG_KERNEL(optimize_lean_shared_ends_long_kernel)
+                    : ends_shared      ? MRS_TG_KERNEL(optimize_lean_shared_ends_kernel)
+                    : lean_masked      ? MRS_TG_KERNEL(optimize_lean_masked_kernel)
+                    : lean_shared_only ? MRS_TG_KERNEL(optimize_lean_shared_kernel)
+                                       : MRS_TG_KERNEL(optimize_lean_kernel);
+  }
+  // one wavefront per path, both directions of the two-sided evaluation in it (mrs_tg_wave.hip)
+  r.wave = !r.lean && wave_kernel_applies(b, r.dim_split);
+  if (!r.wave) {
+    OuterLaunch& L = r.sweep_launch;
+    r.sweep_fits = (int)plan_bins.size() <= 5;
+    if (r.sweep_fits) {
+      const bool split = r.dim_split == 4;
+      L.lds_bytes = fill_bin_table(L.bins, plan_bins, [split](const NonlinearBin& bin) {
+        return ((size_t)(64 / bin.group) * group_lds_doubles(bin.max_S, split) + kBlockConsts) * sizeof(double);
+      }, &L.blocks);
+      bool all_single = true;
+      for (const NonlinearBin& bin : plan_bins)
+        if (bin.group != 64) all_single = false;
+      // one path per block and one dimension per lane: a partner wavefront runs the other half of every sweep
+      L.threads = (split && all_single) ? 128u : 64u;
+      if (L.threads == 128u) L.lds_bytes += (64 * kPairState + 2) * sizeof(double);  // hand-over area + flags
+      r.sweep_fits = L.lds_bytes <= 160 * 1024;
+      // objective order below snap: the end vertices of rest-to-rest paths keep free slots, so the large-batch kernel is
+      // launched with the masked step compiled in (the min-snap instantiation stays free of it)
+      r.sweep_kernel = split            ? MRS_TG_KERNEL(optimize_split_kernel)
+                       : derivative < 4 ? MRS_TG_KERNEL(optimize_compact_kernel<true>)
+                                        : MRS_TG_KERNEL(optimize_compact_kernel<false>);
+    }
+  }
+  r.certified_maxima = knob::maxima_bounds();  // MRS_TG_MAXIMA_BOUNDS=0: every entry searched
+  // 2-4 in one launch for the small batches whose wavefronts hold one path (solve_rows_pipeline_kernel, mrs_tg_rows.hip); else
+  // 3b + 4 in one launch where the quad kernel (saturated device; the caller's sampler follows) or the rows kernel applies:
+  // its staging pass scales the times of its own path, the rows kernel's tail samples
+  const bool quad = quad_kernel_applies(b, b.n_paths, false);
+  const bool rows_samples = samples_wanted && rows_tail_sampling_pays(b);
+  if (!general && !quad && rows_pipeline_applies(b)) {
+    r.closing = Closing::kRowsPipeline;
+    r.tail_samples = samples_wanted;
+  } else if (!general && quad) {
+    r.closing = Closing::kQuadTail;
+  } else if (!general && rows_kernel_applies(b, rows_samples)) {
+    r.closing = Closing::kRowsTail;
+    r.tail_samples = rows_samples;
+  }
+  return r;
+}
+
 hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const NonlinearParams& prm_in, const uint8_t* mask,
                             const double* vals, const double* limits, double* seg_times, double* coeffs,
                             int32_t* status, double* cost, hipStream_t stream, double sampling_dt, int sample_capacity,
@@ -2145,11 +2297,11 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
   if (b.n_paths == 0) return hipSuccess;
   hipError_t e = nonlinear_ensure_buffers(nl, b);
   if (e != hipSuccess) return e;
-  // the start point is the estimate (prm_in.estimate_wp): computed by the outer-loop kernels themselves (start_time), by a
-  // launch of its own in front of the kernels that read their start from a copy
-  // (every outer-loop kernel but the one for position-free paths and the careful re-run, which start from a copy of the times)
-  const bool estimate_in_kernel = prm_in.estimate_wp != nullptr && !general && prm_in.careful_cap == 0;
-  if (prm_in.estimate_wp && !estimate_in_kernel &&
+  const bool careful = prm_in.careful_cap != 0;  // the caller asked for the careful re-run (MRS_TG_FLAG_CAREFUL_COST)
+  const NonlinearRoute route =
+      route_nonlinear(nl, b, prm_in.derivative, constrained_slots_hint(), moving_starts_hint(), device_compute_units(),
+                      prm_in.estimate_wp != nullptr, general, careful, sampling_dt > 0.0 && n_samples != nullptr);
+  if (prm_in.estimate_wp && !route.estimate_in_kernel &&
       (e = launch_estimate_times(b, prm_in.estimate_wp, prm_in.estimate_limits, seg_times, stream)) != hipSuccess)
     return e;
   // paths with a position-free vertex (the caller says there may be some): flagged and listed, their start times kept aside
@@ -2158,15 +2310,9 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
   const int32_t* general_flag = general ? nl.d_general + 4 : nullptr;
   // 1. outer loop: every bin in one launch
   NonlinearParams prm = prm_in;
-  static const int lean_shared = [] {
-    // tuning / test knob, read once per process; 0: one-sided lean sweeps only, 1: shared half sweeps where a whole batch
-    // takes them (optimize_lean_shared_kernel), 2 (default): also wave by wave inside the mixed kernel (ragged batches)
-    const char* e = std::getenv("MRS_TG_LEAN_SHARED");
-    return e == nullptr ? 2 : std::atoi(e);
-  }();
-  prm.lean_shared = lean_shared;
+  prm.lean_shared = knob::lean_shared();
   prm.ends_min_segments = kEndsMinSegments;
-  if (!estimate_in_kernel) prm.estimate_wp = prm.estimate_limits = nullptr;
+  if (!route.estimate_in_kernel) prm.estimate_wp = prm.estimate_limits = nullptr;
   prm.sum_t0 = nl.d_sum_t0;
   prm.deadline = nullptr;
   if (prm_in.time_budget_ticks > 0) {
@@ -2175,7 +2321,6 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
     if ((e = hipGetLastError()) != hipSuccess) return e;
     prm.deadline = nl.d_dfo_deadline;
   }
-  const bool careful = prm_in.careful_cap != 0;  // the caller asked for the careful re-run (MRS_TG_FLAG_CAREFUL_COST)
   int careful_cap = 0;
   if (careful) {
     // as many paths per call as a 2 GB factor store holds (64 lanes x S vertices x 30 doubles each), at most kCarefulCap
@@ -2184,8 +2329,7 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
     careful_cap = std::min(careful_cap, b.n_paths);
     const size_t need = per_path * (size_t)careful_cap;
     if (nl.careful_ws_doubles < need) {
-      if (nl.d_careful_ws) (void)mrs_tg::pool_free(nl.d_careful_ws);
-      nl.d_careful_ws = nullptr;
+      release(nl.d_careful_ws);
       nl.careful_ws_doubles = 0;
       if ((e = mrs_tg::pool_alloc(&nl.d_careful_ws, need * sizeof(double))) != hipSuccess) return e;
       nl.careful_ws_doubles = need;
@@ -2202,201 +2346,35 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
   // rides on the first, the stop event on the last (the lean kernel, the general kernel for the paths it flagged, the
   // careful re-run)
   const KernelTimer kt = take_kernel_timer();
-  // 1a. the lean kernel takes every plain path and flags the others for the sweeping kernel below
-  // The split of the four dimensions over lanes is the PLAN's choice (batch size and longest path); this CALL goes back to
-  // lane groups where the split kernel would hand its paths to the general step anyway and the groups are 10-25 % faster:
-  // 13-15 segments (<= 1536 paths) under an objective order below snap, or when the caller says that vertices hold
-  // constrained slots (stop_at waypoints: MRS_TG_FLAG_CONSTRAINED_SLOTS) or mrs_tg_solve_batch has seen a moving start in
-  // its host copy of the values.  MRS_TG_REGROUP=0 switches it off.
-  static const bool regroup_allowed = [] {
-    const char* e = std::getenv("MRS_TG_REGROUP");
-    return e == nullptr || std::atoi(e) != 0;
-  }();
-  const bool regroup = regroup_allowed && nl.regroup_possible &&
-                       (prm_in.derivative < 4 || constrained_slots_hint() || moving_starts_hint());
-  const int dim_split = regroup ? 1 : nl.dim_split;
-  const std::vector<NonlinearBin>& plan_bins = regroup ? nl.bins1 : nl.bins;
-  bool lean = lean_applies(dim_split) && (int)plan_bins.size() <= 5;
-  auto plain_lds = [&](const NonlinearBin& bin) {
-    return ((size_t)(64 / bin.group) * lean_group_doubles(bin.max_S) + 2 * kPsTable) * sizeof(double);
-  };
-  // Which lane groups.  The shared half sweeps halve the steps of an evaluation but need S + 4 lanes, the next group width
-  // for 13-15 and 29-30 segments: half the paths per wavefront for (S/2 + 1)/S of the steps -- more instructions per path,
-  // so a launch of many residency rounds (a saturated device: the kernel is bound by its instruction count) keeps the
-  // narrow groups and their one-sided sweeps.  A launch of a few residency rounds lasts about as long as its slowest
-  // wavefronts -- ten evaluations of the longest paths -- and there the wide groups win: whole pipeline, wide vs narrow,
-  // 8192 ragged 0.57 vs 0.65 ms, 8192 x 14 0.395 vs 0.425, 16384 x 14 0.644 vs 0.674, 32768 x 30 3.33 vs 3.51,
-  // 32768 ragged 1.87 vs 1.89; past that narrow: 65536 x 14 2.03 vs 1.97 ms (profiles/round5_wide_groups_ab.txt).
-  // (MRS_TG_LEAN_WIDE=0 / 1 forces.)
-  // (per device: a process may drive devices of different sizes or partitions, and the first call's figure is not theirs)
-  int resident_waves = 256 * 4 * MRS_TG_LEAN_WAVES;
-  {
-    static std::mutex mu;
-    static std::map<int, int> cus_of;  // device ordinal -> compute units
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-      std::lock_guard<std::mutex> lock(mu);
-      auto it = cus_of.find(dev);
-      if (it == cus_of.end()) {
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        it = cus_of.emplace(dev, cus).first;
-      }
-      resident_waves = it->second * 4 * MRS_TG_LEAN_WAVES;
-    }
-  }
-  static const int wide_forced = [] {
-    const char* e = std::getenv("MRS_TG_LEAN_WIDE");
-    return e ? (std::atoi(e) != 0 ? 1 : 0) : -1;
-  }();
-  const bool lean_masked_order = prm_in.derivative < 4;
-  bool wide = !nl.wide_bins.empty() && (int)nl.wide_bins.size() <= 5 && !lean_masked_order && prm.lean_shared != 0 &&
-              (wide_forced >= 0 ? wide_forced == 1 : nl.wide_blocks <= 8 * resident_waves);
-  if (wide)
-    for (const NonlinearBin& bin : nl.wide_bins)
-      if (plain_lds(bin) > 160 * 1024) wide = false;
-  // objective orders below snap: the shared half sweeps with free end slots, every path in a group of S + 4 lanes at least
-  // (MRS_TG_LEAN_SHARED=0: the one-sided masked sweeps of optimize_lean_masked_kernel, as until round 5)
-  // (a min-snap launch whose caller says that interior vertices may hold constrained slots -- stop_at waypoints -- as well:
-  // MRS_TG_FLAG_CONSTRAINED_SLOTS)
-  bool ends_shared = (lean_masked_order || constrained_slots_hint()) && prm.lean_shared != 0 && !nl.ends_bins.empty() &&
-                     (int)nl.ends_bins.size() <= 5;
-  if (ends_shared)
-    for (const NonlinearBin& bin : nl.ends_bins)
-      if (plain_lds(bin) > 160 * 1024) ends_shared = false;
-  // min-snap launches of a few residency rounds: EVERY path of two or more segments in a group of S + 4 lanes (the bins of the
-  // free-end kernel), so that the kernel with only the shared half sweeps runs -- the one that takes moving starts; 5-7
-  // segments then pay 3-4 % for their wider groups when they start at rest (MRS_TG_LEAN_WIDE_ALL=0: only 13-15 and 29-30
-  // segments move up and a ragged batch runs the mixed kernel, whose one-sided sweeps leave moving starts to the sweeping kernel)
-  static const bool wide_all = [] {
-    const char* e = std::getenv("MRS_TG_LEAN_WIDE_ALL");
-    return e == nullptr || std::atoi(e) != 0;
-  }();
-  const bool wide_shared_all = wide && wide_all && !nl.ends_bins.empty() && (int)nl.ends_bins.size() <= 5;
-  const std::vector<NonlinearBin>& lean_bins = (ends_shared || wide_shared_all) ? nl.ends_bins : wide ? nl.wide_bins : plan_bins;
-  if (lean)
-    for (const NonlinearBin& bin : lean_bins)
-      if (plain_lds(bin) > 160 * 1024) lean = false;
-  if (lean) {
+  // 1a. the lean kernel
+  if (route.lean) {
+    const OuterLaunch& L = route.lean_launch;
     if ((e = ensure_fallback(nl, b)) != hipSuccess) return e;
-    BinTable bt{};
-    bt.n = (int)lean_bins.size();
-    size_t plds = 0;
-    int blocks = 0;
-    for (int i = 0; i < bt.n; ++i) {
-      const NonlinearBin& bin = lean_bins[i];
-      bt.group[i] = bin.group;
-      bt.q_begin[i] = bin.q_begin;
-      bt.q_count[i] = bin.q_count;
-      bt.max_S[i] = bin.max_S;
-      bt.block_begin[i] = blocks;
-      blocks += (int)cdiv_u(bin.q_count, 64 / bin.group);
-      plds = std::max(plds, plain_lds(bin));
-    }
-    // A uniform batch of more wavefronts than the device holds at once (two per SIMD): launch what is resident and let a
-    // lane group whose path has stopped claim the next one (optimize_body, `queued`), instead of eight rounds of wavefronts
-    // that each last as long as the slowest of their four paths.  65536 x 10: 780 -> us.
     prm.queue_next = nullptr;
-    static const int resident_blocks = [] {
-      if (const char* e = std::getenv("MRS_TG_LEAN_RESIDENT_BLOCKS")) return std::atoi(e);  // tuning knob; 0 = no queue
-      int dev = 0, cus = 256;
-      if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      return cus * 4 * MRS_TG_LEAN_WAVES;
-    }();
-    if (bt.n == 1 && resident_blocks > 0 && blocks > resident_blocks) {
+    if (route.queued) {
       if (!nl.d_queue && (e = mrs_tg::pool_alloc(&nl.d_queue, sizeof(int32_t) * 4)) != hipSuccess) return e;
-      blocks = resident_blocks;
-      MRS_TG_LAUNCH(set_queue_kernel, dim3(1), dim3(1), 0, stream, nl.d_queue, blocks * (64 / bt.group[0]));
+      MRS_TG_LAUNCH(set_queue_kernel, dim3(1), dim3(1), 0, stream, nl.d_queue, L.blocks * (64 / L.bins.group[0]));
       if ((e = hipGetLastError()) != hipSuccess) return e;
       prm.queue_next = nl.d_queue;
     }
-    const bool lean_masked = prm.derivative < 4;  // rest-to-rest paths end on vertices with free slots
-    // shared half sweeps (evaluate_lean_shared) where every path of every bin has its S + 4 lanes
-    // (with a bin of paths shorter than four segments beside them the kernel that has both evaluations compiled in runs, the
-    // short paths in wavefronts of their own next to the others: handing them to the compact kernel BEHIND the launch cost
-    // 66 us on 8192 ragged paths, profiles/round5_wide_groups_ab.txt)
-    bool lean_shared_only = prm.lean_shared != 0 && !lean_masked;
-    for (const NonlinearBin& bin : lean_bins)  // (a bin of one-segment paths: the kernel leaves them to the sweeping kernel behind it)
-      if (bin.max_S >= 2 && (bin.min_S < 2 || (bin.max_S + 4 > bin.group && !(bin.group == 64 && bin.max_S <= kLeanTwoPassMaxS))))
-        lean_shared_only = false;
-    bool long_paths = false;  // a bin whose paths have more half sweeps than a wavefront has lanes: the two-pass instantiations
-    for (const NonlinearBin& bin : lean_bins)
-      if (bin.max_S + 4 > bin.group && bin.group == 64) long_paths = true;
-    const bool ends_long = long_paths && (ends_shared || lean_shared_only);
-    if (plds > 64 * 1024 &&
-        (e = hipFuncSetAttribute(ends_long ? (const void*)optimize_lean_shared_ends_long_kernel
-                                 : ends_shared ? (const void*)optimize_lean_shared_ends_kernel
-                                 : lean_masked ? (const void*)optimize_lean_masked_kernel
-                                 : lean_shared_only ? (const void*)optimize_lean_shared_kernel : (const void*)optimize_lean_kernel,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds)) != hipSuccess)
-      return e;
-    if (ends_long)
-      MRS_TG_LAUNCH_EXT(optimize_lean_shared_ends_long_kernel, dim3(blocks), dim3(64), plds, stream, kt.start, nullptr, 0, b, prm, bt,
-                            mask, vals, seg_times, nl.d_opt_status, nl.d_fallback);
-    else if (ends_shared)
-      MRS_TG_LAUNCH_EXT(optimize_lean_shared_ends_kernel, dim3(blocks), dim3(64), plds, stream, kt.start, nullptr, 0, b, prm, bt,
-                            mask, vals, seg_times, nl.d_opt_status, nl.d_fallback);
-    else if (lean_masked)
-      MRS_TG_LAUNCH_EXT(optimize_lean_masked_kernel, dim3(blocks), dim3(64), plds, stream, kt.start, nullptr, 0, b, prm, bt, mask,
-                            vals, seg_times, nl.d_opt_status, nl.d_fallback);
-    else if (lean_shared_only)
-      MRS_TG_LAUNCH_EXT(optimize_lean_shared_kernel, dim3(blocks), dim3(64), plds, stream, kt.start, nullptr, 0, b, prm, bt, mask,
-                            vals, seg_times, nl.d_opt_status, nl.d_fallback);
-    else
-      MRS_TG_LAUNCH_EXT(optimize_lean_kernel, dim3(blocks), dim3(64), plds, stream, kt.start, nullptr, 0, b, prm, bt, mask, vals,
-                            seg_times, nl.d_opt_status, nl.d_fallback);
+    if (L.lds_bytes > 64 * 1024 && (e = set_max_dynamic_lds(route.lean_kernel, L.lds_bytes)) != hipSuccess) return e;
+    MRS_TG_LAUNCH_EXT(route.lean_kernel, dim3(L.blocks), dim3(64), L.lds_bytes, stream, kt.start, nullptr, 0, b, prm, L.bins, mask,
+                      vals, seg_times, nl.d_opt_status, nl.d_fallback);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     prm.only_flagged = nl.d_fallback;
     prm.queue_next = nullptr;
   }
+  // 1b. the sweeping kernel
   {
-    const hipEvent_t ev_start = lean ? nullptr : kt.start, ev_stop = (careful || general) ? nullptr : kt.stop;
-    if (!lean && wave_kernel_applies(b, dim_split)) {
-      // one wavefront per path, both directions of the two-sided evaluation in it (mrs_tg_wave.hip)
+    const hipEvent_t ev_start = route.lean ? nullptr : kt.start, ev_stop = (careful || general) ? nullptr : kt.stop;
+    if (route.wave) {
       if ((e = launch_optimize_wave(b, prm, mask, vals, seg_times, nl.d_opt_status, stream, ev_start, ev_stop)) != hipSuccess) return e;
     } else {
-    BinTable bt{};
-    bt.n = (int)plan_bins.size();
-    if (bt.n > 5) return hipErrorInvalidValue;
-    size_t lds_bytes = 0;
-    int blocks = 0;
-    bool all_single = true;
-    for (int i = 0; i < bt.n; ++i) {
-      const NonlinearBin& bin = plan_bins[i];
-      const int per_block = 64 / bin.group;
-      bt.group[i] = bin.group;
-      bt.q_begin[i] = bin.q_begin;
-      bt.q_count[i] = bin.q_count;
-      bt.max_S[i] = bin.max_S;
-      bt.block_begin[i] = blocks;
-      blocks += (int)cdiv_u(bin.q_count, per_block);
-      const size_t need = ((size_t)per_block * group_lds_doubles(bin.max_S, dim_split == 4) + kBlockConsts) * sizeof(double);
-      if (need > lds_bytes) lds_bytes = need;
-      if (bin.group != 64) all_single = false;
-    }
-    // one path per block and one dimension per lane: a partner wavefront runs the other half of every sweep
-    const unsigned threads = (dim_split == 4 && all_single) ? 128u : 64u;
-    if (threads == 128u) lds_bytes += (64 * kPairState + 2) * sizeof(double);  // hand-over area + flags
-    if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-    // objective order below snap: the end vertices of rest-to-rest paths keep free slots, so the large-batch kernel is
-    // launched with the masked step compiled in (the min-snap instantiation stays free of it)
-    const bool masked4 = prm.derivative < 4;
-    if (lds_bytes > 64 * 1024) {
-      const void* fn = dim_split == 4 ? (const void*)optimize_split_kernel
-                       : masked4         ? (const void*)optimize_compact_kernel<true>
-                                         : (const void*)optimize_compact_kernel<false>;
-      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-      if (e != hipSuccess) return e;
-    }
-    if (dim_split == 4)
-      MRS_TG_LAUNCH_EXT(optimize_split_kernel, dim3(blocks), dim3(threads), lds_bytes, stream, ev_start, ev_stop, 0, b, prm, bt,
-                            mask, vals, seg_times, nl.d_opt_status);
-    else if (masked4)
-      MRS_TG_LAUNCH_EXT(optimize_compact_kernel<true>, dim3(blocks), dim3(64), lds_bytes, stream, ev_start, ev_stop, 0, b, prm,
-                            bt, mask, vals, seg_times, nl.d_opt_status);
-    else
-      MRS_TG_LAUNCH_EXT(optimize_compact_kernel<false>, dim3(blocks), dim3(64), lds_bytes, stream, ev_start, ev_stop, 0, b, prm,
-                            bt, mask, vals, seg_times, nl.d_opt_status);
+      const OuterLaunch& L = route.sweep_launch;
+      if (!route.sweep_fits) return hipErrorInvalidValue;
+      if (L.lds_bytes > 64 * 1024 && (e = set_max_dynamic_lds(route.sweep_kernel, L.lds_bytes)) != hipSuccess) return e;
+      MRS_TG_LAUNCH_EXT(route.sweep_kernel, dim3(L.blocks), dim3(L.threads), L.lds_bytes, stream, ev_start, ev_stop, 0, b, prm, L.bins,
+                        mask, vals, seg_times, nl.d_opt_status);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
 #if MRS_TG_WITH_CAREFUL
@@ -2441,21 +2419,25 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
       }
     }
   }
-  // 2-4 in one launch for the small batches whose wavefronts hold one path (solve_rows_pipeline_kernel, mrs_tg_rows.hip)
-  if (!general && !quad_kernel_applies(b, b.n_paths, false) && rows_pipeline_applies(b)) {
+  // the RowsTail of the closing launch: the feasibility scaling in front of its solve, the sampling behind it
+  auto closing_tail = [&]() {
     RowsTail tail;
-    tail.maxima_in_launch = true;
     tail.limits = limits;
     tail.opt_status = nl.d_opt_status;
     tail.sum_t0 = prm.reference_status ? nullptr : nl.d_sum_t0;  // (no runaway test: MRS_TG_FLAG_REFERENCE_STATUS)
     tail.seg_times_out = seg_times;
-    if (sampling_dt > 0.0 && n_samples != nullptr) {
+    if (route.tail_samples) {
       tail.sampling_dt = sampling_dt;
       tail.sample_capacity = sample_capacity;
       tail.n_samples = n_samples;
       tail.samples = samples;
       if (sampled_out) *sampled_out = true;
     }
+    return tail;
+  };
+  if (route.closing == Closing::kRowsPipeline) {
+    RowsTail tail = closing_tail();
+    tail.maxima_in_launch = true;
     return launch_solve_rows(b, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status, stream, tail);
   }
   // 2. trajectory of the last evaluated point (scaleSegmentTimesWithViolation works on poly_opt_'s state)
@@ -2466,43 +2448,23 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
                                            stream, general_flag, nullptr)) != hipSuccess)
     return e;
   // 3. per-segment maxima and time scaling
-  static const bool certified_maxima = [] {  // MRS_TG_MAXIMA_BOUNDS=0: every entry searched (tuning / test knob, read once)
-    const char* e = std::getenv("MRS_TG_MAXIMA_BOUNDS");
-    return e == nullptr || std::atoi(e) != 0;
-  }();
-  if (certified_maxima)
+  if (route.certified_maxima)
     MRS_TG_LAUNCH(segment_maxima_scaling_kernel, dim3(cdiv_u(b.n_segments, kMsSegs)), dim3(kMsThreads), 0, stream, b, coeffs,
                        seg_times, limits, nl.d_maxima);
   else
     MRS_TG_LAUNCH(segment_maxima9_kernel, dim3(cdiv_u(b.n_segments, 64), 9), dim3(64), 0, stream, b.n_segments,
                        coeffs, seg_times, nl.d_maxima);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  // 3b + 4 in one launch where the rows kernel applies: its staging pass scales the times of its own path, its tail samples
-  const bool want_samples = sampling_dt > 0.0 && n_samples != nullptr && rows_tail_sampling_pays(b);
-  if (!general && quad_kernel_applies(b, b.n_paths, false)) {  // saturated device; the caller's sampler follows
-    RowsTail tail;
+  // 3b + 4 in one launch
+  if (route.closing == Closing::kQuadTail) {
+    RowsTail tail = closing_tail();
     tail.maxima = nl.d_maxima;
-    tail.limits = limits;
-    tail.opt_status = nl.d_opt_status;
-    tail.sum_t0 = prm.reference_status ? nullptr : nl.d_sum_t0;  // (no runaway test: MRS_TG_FLAG_REFERENCE_STATUS)
-    tail.seg_times_out = seg_times;
     tail.pos_wp = prm.pos_wp;
     return launch_solve_quad(b, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status, nl.d_ws, stream, tail);
   }
-  if (!general && rows_kernel_applies(b, want_samples)) {
-    RowsTail tail;
+  if (route.closing == Closing::kRowsTail) {
+    RowsTail tail = closing_tail();
     tail.maxima = nl.d_maxima;
-    tail.limits = limits;
-    tail.opt_status = nl.d_opt_status;
-    tail.sum_t0 = prm.reference_status ? nullptr : nl.d_sum_t0;  // (no runaway test: MRS_TG_FLAG_REFERENCE_STATUS)
-    tail.seg_times_out = seg_times;
-    if (want_samples) {
-      tail.sampling_dt = sampling_dt;
-      tail.sample_capacity = sample_capacity;
-      tail.n_samples = n_samples;
-      tail.samples = samples;
-      if (sampled_out) *sampled_out = true;
-    }
     return launch_solve_rows(b, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status, stream, tail);
   }
   MRS_TG_LAUNCH(apply_scaling_kernel, dim3(cdiv_u(b.n_segments, 256)), dim3(256), 0, stream, b, nl.d_maxima, limits,
@@ -2531,12 +2493,9 @@ hipError_t launch_cost_gradient(NonlinearPlan& nl, const BatchView& b, int d, co
     const size_t lds_bytes = ((size_t)per_block * gradient_lds_doubles(bin.max_S, nl.dim_split == 4) + kBlockConsts) * sizeof(double);
     if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
     const dim3 grid(cdiv_u(bin.q_count, per_block));
-    if (nl.dim_split == 4)
-      MRS_TG_LAUNCH(cost_gradient_kernel<4>, grid, dim3(64), lds_bytes, stream, b, d, bin.group, bin.q_begin,
-                         bin.q_count, bin.max_S, mask, vals, seg_times, cost, grad, only);
-    else
-      MRS_TG_LAUNCH(cost_gradient_kernel<1>, grid, dim3(64), lds_bytes, stream, b, d, bin.group, bin.q_begin,
-                         bin.q_count, bin.max_S, mask, vals, seg_times, cost, grad, only);
+    const auto gradient = nl.dim_split == 4 ? MRS_TG_KERNEL(cost_gradient_kernel<4>) : MRS_TG_KERNEL(cost_gradient_kernel<1>);
+    MRS_TG_LAUNCH(gradient, grid, dim3(64), lds_bytes, stream, b, d, bin.group, bin.q_begin, bin.q_count, bin.max_S, mask, vals,
+                  seg_times, cost, grad, only);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   return hipSuccess;

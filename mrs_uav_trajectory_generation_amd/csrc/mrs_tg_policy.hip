@@ -22,10 +22,7 @@ struct GpuHost {  // the Host of mrs_tg::policy::optimize_paths
   // From 64 active requests on: below, a round's two extra launches and the second copy kernel cost a lone request more than
   // its 36 KB of values and samples on the wire (one 5-round request: 1.15 ms on the host route, 1.97 on the device route).
   bool device_round_enabled(size_t active_paths) const {
-    static const int min_paths = [] {
-      const char* e = std::getenv("MRS_TG_POLICY_DEVICE");   // 0: never; n >= 1: from n active requests on
-      return e == nullptr ? 64 : std::atoi(e);
-    }();
+    const int min_paths = mrs_tg::knob::policy_device();
     return min_paths > 0 && active_paths >= (size_t)min_paths;
   }
   int round(const mrs_tg::PolicyRoundIn& in) { return mrs_tg::policy_round_device(ctx, in); }

@@ -30,6 +30,7 @@
 #include <sched.h>
 
 #include "../../include/mrs_tg.h"
+#include "mrs_tg_knobs.hpp"
 
 struct mrs_tg_ctx;
 
@@ -209,7 +210,7 @@ inline void estimate_times_baca(int S, const double* wp, const double* lim, std:
 // (a nodelet's single request) stay on the calling thread.  MRS_TG_POLICY_THREADS=1 switches the threads off.
 inline int policy_threads() {
   static const int n = [] {
-    if (const char* e = std::getenv("MRS_TG_POLICY_THREADS")) return std::max(1, std::atoi(e));
+    if (knob::policy_threads()) return knob::policy_threads();
     int cpus = (int)std::thread::hardware_concurrency();
     cpu_set_t set;
     if (sched_getaffinity(0, sizeof(set), &set) == 0) cpus = std::min(cpus > 0 ? cpus : 1 << 20, CPU_COUNT(&set));
@@ -225,11 +226,7 @@ template <class F>
 void parallel_ranges(size_t n, size_t min_per_thread, F&& body) {
   // MRS_TG_POLICY_GRAIN=k (test knob, read once): k items are enough for a thread, whatever the call site asks for -- lets a
   // test put a few dozen requests on 16 threads (tests/host/policy_host_harness.cpp)
-  static const size_t grain_override = [] {
-    const char* e = std::getenv("MRS_TG_POLICY_GRAIN");
-    return e ? (size_t)std::max(1, std::atoi(e)) : (size_t)0;
-  }();
-  if (grain_override) min_per_thread = grain_override;
+  if (knob::policy_grain()) min_per_thread = knob::policy_grain();
   const size_t threads = std::min<size_t>((size_t)policy_threads(), n / std::max<size_t>(min_per_thread, 1));
   if (threads <= 1) {
     body((size_t)0, n);
@@ -521,10 +518,7 @@ int optimize_paths(Host& host, int32_t n_paths, const int32_t* wp_offsets, const
   });
   std::vector<int> active;
   // MRS_TG_POLICY_TRACE=1: where the call's time went (host phases and the batched GPU call), on stderr
-  static const bool trace = [] {
-    const char* e = std::getenv("MRS_TG_POLICY_TRACE");
-    return e != nullptr && std::atoi(e) != 0;
-  }();
+  const bool trace = knob::policy_trace();
   double t_build = 0, t_solve = 0, t_post = 0, t_validate = 0;
   auto now = [&]() { return trace ? elapsed() : 0.0; };
   for (int round = 0; round <= o.max_deviation_iterations; ++round) {
@@ -572,11 +566,7 @@ int optimize_paths(Host& host, int32_t n_paths, const int32_t* wp_offsets, const
         for (size_t a = 0; a < A; ++a) so[a + 1] = so[a] + st[active[a]].n_wp - 1;
         const size_t nS = (size_t)so.back(), nV = nS + A;
         const PolicyRoundLayout L = policy_round_layout(A, nS, sample_capacity);
-        static const bool pinned_allowed = [] {  // MRS_TG_POLICY_PINNED=0: ordinary memory (test knob, read once per process)
-          const char* e = std::getenv("MRS_TG_POLICY_PINNED");
-          return e == nullptr || std::atoi(e) != 0;
-        }();
-        char* block = pinned_allowed ? static_cast<char*>(host.scratch(L.total_bytes)) : nullptr;
+        char* block = knob::policy_pinned() ? static_cast<char*>(host.scratch(L.total_bytes)) : nullptr;
         std::vector<char> pageable;
         if (!block) {
           pageable.resize(L.total_bytes);
@@ -704,11 +694,7 @@ int optimize_paths(Host& host, int32_t n_paths, const int32_t* wp_offsets, const
                    b_times = up(nS * sizeof(double)), b_smp = up(A * (size_t)sample_capacity * 4 * sizeof(double)),
                    b_status = up(A * sizeof(int32_t)), b_ns = up(A * sizeof(int32_t)), b_mask = up(nV * 5);
       const size_t need = b_wp + b_vals + b_lim + b_times + b_smp + b_status + b_ns + b_mask;
-      static const bool pinned_allowed = [] {  // MRS_TG_POLICY_PINNED=0: ordinary memory (test knob, read once per process)
-        const char* e = std::getenv("MRS_TG_POLICY_PINNED");
-        return e == nullptr || std::atoi(e) != 0;
-      }();
-      char* block = pinned_allowed ? static_cast<char*>(host.scratch(need)) : nullptr;
+      char* block = knob::policy_pinned() ? static_cast<char*>(host.scratch(need)) : nullptr;
       std::vector<char> pageable;  // (the runtime refused that much pinned memory: ordinary memory, copied by the runtime)
       if (!block) {
         pageable.resize(need);

@@ -39,8 +39,7 @@ size_t round_size(size_t bytes) {
 // MRS_TG_POOL_POISON=1 fills every block handed out with 0xFF bytes (NaN as a double, -1 as an int): a test-suite run
 // under it shows any read of memory that this library did not write first.
 static hipError_t poison(void* p, size_t bytes) {
-  static const bool on = std::getenv("MRS_TG_POOL_POISON") != nullptr;
-  if (!on) return hipSuccess;
+  if (!mrs_tg::knob::pool_poison()) return hipSuccess;
   hipError_t e = hipMemset(p, 0xFF, bytes);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   return e;
@@ -127,6 +126,20 @@ bool constrained_slots_hint() { return t_constrained_slots; }
 static thread_local bool t_moving_starts = false;
 bool moving_starts_hint() { return t_moving_starts; }
 void set_moving_starts_hint(bool on) { t_moving_starts = on; }
+int device_compute_units() {
+  static std::mutex mu;
+  static std::map<int, int> cus_of;  // device ordinal -> compute units
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 256;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cus_of.find(dev);
+  if (it == cus_of.end()) {
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    it = cus_of.emplace(dev, cus).first;
+  }
+  return it->second;
+}
 static thread_local bool t_dry_run = false;
 bool dry_run() { return t_dry_run; }
 void set_dry_run(bool on) { t_dry_run = on; }

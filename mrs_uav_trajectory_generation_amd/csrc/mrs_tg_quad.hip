@@ -43,9 +43,6 @@
 #ifndef MRS_TG_QUAD_WAVES
 #define MRS_TG_QUAD_WAVES 1
 #endif
-#ifndef MRS_TG_QUAD_EXP
-#define MRS_TG_QUAD_EXP 0
-#endif
 #ifndef MRS_TG_QUAD_GROUP_WAVES
 #define MRS_TG_QUAD_GROUP_WAVES 2
 #endif
@@ -70,9 +67,6 @@ constexpr int kQdL = 0, kQdLinv = 6, kQdZ = 10, kQdRec = 26;
 __host__ __device__ constexpr size_t quad_lds_doubles(int Smax, bool ends = false) {
   return (size_t)(ends ? Smax + 1 : (Smax > 1 ? Smax - 1 : 1)) * kQdRec * kQdPaths + (size_t)Smax * kQdPaths  // records | times
          + (ends ? (size_t)(Smax + 1) * 2 : 0)  // ends: the free mask of every (vertex, path), one byte each
-#if MRS_TG_QUAD_EXP == 5
-         + kQdPaths  // per path: first segment and segment count (ints)
-#endif
       ;
 }
 
@@ -92,22 +86,12 @@ __device__ __forceinline__ void quad_powers(double T, bool d1, bool d2, bool d4,
   p2[8] = p2[4] * t4;
 }
 
-// a pair of coefficients (16 bytes).  MRS_TG_COEFF_NT=1 (experiment build): as a streaming store -- measured in round 6 after
+// a pair of coefficients (16 bytes), an ordinary store.  As a streaming store (an experiment build) -- measured in round 6 after
 // the samples and the assembled blocks had gained from it: here it is 2.5-3 x SLOWER (headline dispatch 26 -> 73-81 us, 65536 x 10
 // 131 -> 335-339 us): a lane owns 80 consecutive bytes, so a store instruction writes 64 separate 16-byte pieces, and without the
 // L2 to combine them every piece is a partial-line write to HBM.  Streaming pays where an instruction writes whole lines.
-#ifndef MRS_TG_COEFF_NT
-#define MRS_TG_COEFF_NT 0
-#endif
 __device__ __forceinline__ void store_coeff_pair(double2* dst, double a, double b) {
-#if MRS_TG_COEFF_NT
-  typedef double coeff_pair __attribute__((ext_vector_type(2)));
-  coeff_pair v;
-  v.x = a, v.y = b;
-  __builtin_nontemporal_store(v, reinterpret_cast<coeff_pair*>(dst));
-#else
   *dst = make_double2(a, b);
-#endif
 }
 
 __device__ __forceinline__ void quad_wave_sync() {
@@ -148,14 +132,6 @@ __device__ __forceinline__ void solve_quad_body(const BatchView& b, int d, const
   double* rec0 = lds;
   double* tbuf = lds + (size_t)(ENDS ? Smax + 1 : (Smax > 1 ? Smax - 1 : 1)) * kQdRec * kQdPaths;  // [segment][path]
   unsigned char* vmask = reinterpret_cast<unsigned char*>(tbuf + (size_t)Smax * kQdPaths);        // ENDS: [vertex][path] free masks
-#if MRS_TG_QUAD_EXP == 5
-  const int n_rec = Smax > 1 ? Smax - 1 : 1;
-  int* pinfo = reinterpret_cast<int*>(tbuf + (size_t)Smax * kQdPaths);
-  if (dim == 0) {
-    pinfo[pl] = pr.s0;
-    pinfo[kQdPaths + pl] = active ? S : 0;
-  }
-#endif
   // ---- prologue: times (scaled, for the last solve of a Mellinger pipeline), plainness of the path
   const bool scaling = tail.maxima != nullptr;
   double t_sum = 0.0;
@@ -560,61 +536,9 @@ __device__ __forceinline__ void solve_quad_body(const BatchView& b, int d, const
         // measured in round 5: 65536 x 10 129 -> 156 us -- the LDS round trip and its two wavefront syncs per step cost a
         // lone wavefront more than the 4x fewer write requests return (HISTORY.md)
         double2* out = reinterpret_cast<double2*>(coeffs + ((size_t)(pr.s0 + v) * kD + dim) * kN);
-#if MRS_TG_QUAD_EXP == 5   // experiment: staged through the LDS of the consumed vertex records (256 B of one path per 16 lanes)
-        (void)out;
-        if ((v > 0 ? v - 1 : 0) + 2 <= n_rec) {
-          double2* st = reinterpret_cast<double2*>(rec0 + (size_t)(v > 0 ? v - 1 : 0) * kQdRec * kQdPaths + pl * (kN * kD) + dim * kN);
-#pragma unroll
-          for (int k = 0; k < kN; k += 2) st[k / 2] = make_double2(c[k], c[k + 1]);
-        } else {
-          double2* o5 = reinterpret_cast<double2*>(coeffs + ((size_t)(pr.s0 + v) * kD + dim) * kN);
-#pragma unroll
-          for (int k = 0; k < kN; k += 2) o5[k / 2] = make_double2(c[k], c[k + 1]);
-        }
-#elif MRS_TG_QUAD_EXP == 1   // experiment: the coefficients are computed and not stored
-#pragma unroll
-        for (int k = 0; k < kN; ++k) asm volatile("" ::"v"(c[k]));
-        (void)out;
-#elif MRS_TG_QUAD_EXP == 3  // experiment: the same pieces into a 5 KB window per wavefront (L2 hits, no HBM write traffic)
-        double2* o3 = reinterpret_cast<double2*>(coeffs + (size_t)block * 640 + lane * 10);
-#pragma unroll
-        for (int k = 0; k < kN; k += 2) o3[k / 2] = make_double2(c[k], c[k + 1]);
-        (void)out;
-#elif MRS_TG_QUAD_EXP == 4  // experiment: perfectly coalesced (wrong) layout: instruction k writes 64 consecutive 16-byte pieces
-        double2* o4 = reinterpret_cast<double2*>(coeffs + ((size_t)block * Smax + v) * 640);
-#pragma unroll
-        for (int k = 0; k < kN; k += 2) o4[(k / 2) * 64 + lane] = make_double2(c[k], c[k + 1]);
-        (void)out;
-#elif MRS_TG_QUAD_EXP == 2  // experiment: streaming stores
-#pragma unroll
-        for (int k = 0; k < kN; k += 2) {
-          __builtin_nontemporal_store(c[k], reinterpret_cast<double*>(out) + k);
-          __builtin_nontemporal_store(c[k + 1], reinterpret_cast<double*>(out) + k + 1);
-        }
-#else
 #pragma unroll
         for (int k = 0; k < kN; k += 2) store_coeff_pair(out + k / 2, c[k], c[k + 1]);
-#endif
       }
-#if MRS_TG_QUAD_EXP == 5
-      if ((v > 0 ? v - 1 : 0) + 2 <= n_rec) {  // (uniform)
-        const double* stage = rec0 + (size_t)(v > 0 ? v - 1 : 0) * kQdRec * kQdPaths;
-        quad_wave_sync();
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int P = 4 * g + (lane >> 4), piece = lane & 15;
-          const int s0P = pinfo[P], SP = pinfo[kQdPaths + P];
-          if (v < SP) {
-            const double2 val = *reinterpret_cast<const double2*>(stage + P * (kN * kD) + piece * 2);
-            *reinterpret_cast<double2*>(coeffs + ((size_t)(s0P + v) * (kN * kD) + piece * 2)) = val;
-          }
-        }
-        if (on) {
-          const double2 val = *reinterpret_cast<const double2*>(stage + pl * (kN * kD) + 32 + dim * 2);
-          *reinterpret_cast<double2*>(coeffs + ((size_t)(pr.s0 + v) * (kN * kD) + 32 + dim * 2)) = val;
-        }
-      }
-#endif
 #pragma unroll
       for (int r = 0; r < kNB; ++r) xn[r] = x[r];
       if (on) p_end = p_start;
@@ -1223,39 +1147,19 @@ __global__ __launch_bounds__(64, MRS_TG_QUAD_GROUP_WAVES) void solve_quad_group_
 
 static constexpr size_t kQuadLdsBudget = 80 * 1024;  // at least two wavefronts per CU
 
-// MRS_TG_QUAD_MIN_PATHS: paths per launch from which the quad kernel takes over (tuning / test knob, read once per process)
-static long long quad_min_paths() {
-  static const long long v = [] {
-    const char* e = std::getenv("MRS_TG_QUAD_MIN_PATHS");
-    return e ? std::atoll(e) : 6144ll;
-  }();
-  return v;
-}
-
-// MRS_TG_QUAD_ENDS=0: the general step for paths whose end vertices leave slots free, as until round 5 (read once per process)
-static bool quad_ends_allowed() {
-  static const bool v = [] {
-    const char* e = std::getenv("MRS_TG_QUAD_ENDS");
-    return e == nullptr || std::atoi(e) != 0;
-  }();
-  return v;
-}
-
 // The two-sided kernel takes a launch whose quad wavefronts (16 paths each) would leave SIMDs idle or barely covered: fewer than
 // 1.25 per SIMD.  MRS_TG_DUO=0: never, =1: whenever the pattern allows (tuning / test knob).
 static bool duo_pays(long long paths_in_launch) {
-  if (const char* e = std::getenv("MRS_TG_DUO")) return std::atoi(e) != 0;  // (read at every call: tests run both kernels)
-  static const int cus = [] {  // (of the first device used: the threshold is a tuning figure, results do not depend on it)
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n;
-  }();
+  if (const int forced = knob::duo_forced(); forced >= 0) return forced != 0;  // (read at every call: tests run both kernels)
+  // (of the FIRST device used, for the whole process: the threshold is a tuning figure, results do not depend on it; a
+  // process that drives devices of different sizes routes as it always has -- changing that is for another day)
+  static const int cus = device_compute_units();
   return (paths_in_launch + kQdPaths - 1) / kQdPaths < (long long)cus * 4 * 5 / 4;
 }
 
 bool quad_kernel_applies(const BatchView& b, long long paths_in_launch, bool with_sampling) {
   if (b.n_paths == 0 || with_sampling) return false;
-  if (paths_in_launch < quad_min_paths()) return false;
+  if (paths_in_launch < knob::quad_min_paths()) return false;
   return quad_lds_doubles(b.max_segments) * sizeof(double) <= kQuadLdsBudget;
 }
 
@@ -1265,88 +1169,64 @@ hipError_t launch_solve_quad(const BatchView& b, int d, const uint8_t* mask, con
   // objective orders below snap leave jerk and / or snap free at the end vertices of a rest-to-rest path: the instantiation
   // that eliminates such end vertices (two more records per path in LDS), while its LDS fits; MRS_TG_QUAD_ENDS=0: the general
   // step for those paths, as until round 5
-  const bool ends = quad_ends_allowed() && (d < 4 || constrained_slots_hint()) &&
+  const bool ends = knob::quad_ends() && (d < 4 || constrained_slots_hint()) &&
                     quad_lds_doubles(b.max_segments, true) * sizeof(double) <= kQuadLdsBudget;
   const bool wp = tail.pos_wp != nullptr;
   if (!ends && !(d < 4) && duo_pays(b.n_paths)) {  // few wavefronts: eight lanes per path, the chain cut in the middle
     const size_t lds_duo = duo_lds_doubles(b.max_segments) * sizeof(double);
+    const auto duo = wp ? MRS_TG_KERNEL(solve_duo_kernel<true>) : MRS_TG_KERNEL(solve_duo_kernel<false>);
     if (lds_duo > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(wp ? (const void*)solve_duo_kernel<true> : (const void*)solve_duo_kernel<false>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQuadLdsBudget);
+      hipError_t e = set_max_dynamic_lds(duo, kQuadLdsBudget);
       if (e != hipSuccess) return e;
     }
     const unsigned grid_duo = (unsigned)((b.n_paths + kDuoPaths - 1) / kDuoPaths);
-    if (wp)
-      MRS_TG_LAUNCH_TIMED(solve_duo_kernel<true>, dim3(grid_duo), dim3(64), lds_duo, stream, b, d, mask, vals, seg_times, coeffs, status,
-                          cost, status_in, ws, tail);
-    else
-      MRS_TG_LAUNCH_TIMED(solve_duo_kernel<false>, dim3(grid_duo), dim3(64), lds_duo, stream, b, d, mask, vals, seg_times, coeffs, status,
-                          cost, status_in, ws, tail);
+    MRS_TG_LAUNCH_TIMED(duo, dim3(grid_duo), dim3(64), lds_duo, stream, b, d, mask, vals, seg_times, coeffs, status, cost, status_in,
+                        ws, tail);
     return hipGetLastError();
   }
   const size_t lds_bytes = quad_lds_doubles(b.max_segments, ends) * sizeof(double);
-  const void* fn = ends ? (wp ? (const void*)solve_quad_kernel<true, true> : (const void*)solve_quad_kernel<false, true>)
-                        : (wp ? (const void*)solve_quad_kernel<true> : (const void*)solve_quad_kernel<false>);
+  const auto quad = ends ? (wp ? MRS_TG_KERNEL(solve_quad_kernel<true, true>) : MRS_TG_KERNEL(solve_quad_kernel<false, true>))
+                         : (wp ? MRS_TG_KERNEL(solve_quad_kernel<true>) : MRS_TG_KERNEL(solve_quad_kernel<false>));
   if (lds_bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQuadLdsBudget);
+    hipError_t e = set_max_dynamic_lds(quad, kQuadLdsBudget);
     if (e != hipSuccess) return e;
   }
   const unsigned grid = (unsigned)((b.n_paths + kQdPaths - 1) / kQdPaths);
-  if (ends && wp)
-    MRS_TG_LAUNCH_TIMED_T2(solve_quad_kernel, true, true, dim3(grid), dim3(64), lds_bytes, stream, b, d, mask, vals, seg_times, coeffs,
-                        status, cost, status_in, ws, tail);
-  else if (ends)
-    MRS_TG_LAUNCH_TIMED_T2(solve_quad_kernel, false, true, dim3(grid), dim3(64), lds_bytes, stream, b, d, mask, vals, seg_times, coeffs,
-                        status, cost, status_in, ws, tail);
-  else if (wp)
-    MRS_TG_LAUNCH_TIMED(solve_quad_kernel<true>, dim3(grid), dim3(64), lds_bytes, stream, b, d, mask, vals, seg_times, coeffs, status,
-                        cost, status_in, ws, tail);
-  else
-    MRS_TG_LAUNCH_TIMED(solve_quad_kernel<false>, dim3(grid), dim3(64), lds_bytes, stream, b, d, mask, vals, seg_times, coeffs, status,
-                        cost, status_in, ws, tail);
+  MRS_TG_LAUNCH_TIMED(quad, dim3(grid), dim3(64), lds_bytes, stream, b, d, mask, vals, seg_times, coeffs, status, cost, status_in, ws,
+                      tail);
   return hipGetLastError();
 }
 
 hipError_t launch_solve_quad_group(const BatchView& b, int d, const RowsGroup& g, double* ws, hipStream_t stream) {
   if (g.n < 1 || g.n > kRowsGroupMax) return hipErrorInvalidValue;
-  const bool ends = quad_ends_allowed() && (d < 4 || constrained_slots_hint()) &&
+  const bool ends = knob::quad_ends() && (d < 4 || constrained_slots_hint()) &&
                     quad_lds_doubles(b.max_segments, true) * sizeof(double) <= kQuadLdsBudget;
   const size_t lds_bytes = quad_lds_doubles(b.max_segments, ends) * sizeof(double);
   bool wp = true;
   for (int j = 0; j < g.n; ++j) wp = wp && g.pos_wp[j] != nullptr;
   if (!ends && !(d < 4) && duo_pays((long long)b.n_paths * g.n)) {
     const size_t lds_duo = duo_lds_doubles(b.max_segments) * sizeof(double);
+    const auto duo = wp ? MRS_TG_KERNEL(solve_duo_group_kernel<true>) : MRS_TG_KERNEL(solve_duo_group_kernel<false>);
     if (lds_duo > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(wp ? (const void*)solve_duo_group_kernel<true> : (const void*)solve_duo_group_kernel<false>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQuadLdsBudget);
+      hipError_t e = set_max_dynamic_lds(duo, kQuadLdsBudget);
       if (e != hipSuccess) return e;
     }
     const int per_batch_duo = (b.n_paths + kDuoPaths - 1) / kDuoPaths;
     const dim3 grid_duo((unsigned)(per_batch_duo * g.n));
     const size_t wsd_duo = linear_workspace_doubles(b);
-    if (wp)
-      MRS_TG_LAUNCH_TIMED(solve_duo_group_kernel<true>, grid_duo, dim3(64), lds_duo, stream, b, d, g, ws, wsd_duo, per_batch_duo);
-    else
-      MRS_TG_LAUNCH_TIMED(solve_duo_group_kernel<false>, grid_duo, dim3(64), lds_duo, stream, b, d, g, ws, wsd_duo, per_batch_duo);
+    MRS_TG_LAUNCH_TIMED(duo, grid_duo, dim3(64), lds_duo, stream, b, d, g, ws, wsd_duo, per_batch_duo);
     return hipGetLastError();
   }
+  const auto quad = ends ? (wp ? MRS_TG_KERNEL(solve_quad_group_kernel<true, true>) : MRS_TG_KERNEL(solve_quad_group_kernel<false, true>))
+                         : (wp ? MRS_TG_KERNEL(solve_quad_group_kernel<true>) : MRS_TG_KERNEL(solve_quad_group_kernel<false>));
   if (lds_bytes > 64 * 1024) {
-    const void* fn = ends ? (wp ? (const void*)solve_quad_group_kernel<true, true> : (const void*)solve_quad_group_kernel<false, true>)
-                          : (wp ? (const void*)solve_quad_group_kernel<true> : (const void*)solve_quad_group_kernel<false>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQuadLdsBudget);
+    hipError_t e = set_max_dynamic_lds(quad, kQuadLdsBudget);
     if (e != hipSuccess) return e;
   }
   const int per_batch = (b.n_paths + kQdPaths - 1) / kQdPaths;
   const dim3 grid((unsigned)(per_batch * g.n));
   const size_t wsd = linear_workspace_doubles(b);
-  if (ends && wp)
-    MRS_TG_LAUNCH_TIMED_T2(solve_quad_group_kernel, true, true, grid, dim3(64), lds_bytes, stream, b, d, g, ws, wsd, per_batch);
-  else if (ends)
-    MRS_TG_LAUNCH_TIMED_T2(solve_quad_group_kernel, false, true, grid, dim3(64), lds_bytes, stream, b, d, g, ws, wsd, per_batch);
-  else if (wp)
-    MRS_TG_LAUNCH_TIMED(solve_quad_group_kernel<true>, grid, dim3(64), lds_bytes, stream, b, d, g, ws, wsd, per_batch);
-  else
-    MRS_TG_LAUNCH_TIMED(solve_quad_group_kernel<false>, grid, dim3(64), lds_bytes, stream, b, d, g, ws, wsd, per_batch);
+  MRS_TG_LAUNCH_TIMED(quad, grid, dim3(64), lds_bytes, stream, b, d, g, ws, wsd, per_batch);
   return hipGetLastError();
 }
 

@@ -701,29 +701,19 @@ static size_t rows_lds_bytes(int Smax, int ppw, bool sampling, bool maxima = fal
 
 bool rows_kernel_applies(const BatchView& b, bool with_sampling) {
   if (b.n_paths == 0) return false;
-  // tuning / test knob, read once per process (a getenv per launch is a measurable share of a 3 us launch):
-  // MRS_TG_ROWS_KERNEL=0 falls back to the tile and lane kernels
-  static const bool disabled = [] {
-    const char* e = std::getenv("MRS_TG_ROWS_KERNEL");
-    return e != nullptr && std::atoi(e) == 0;
-  }();
-  if (disabled) return false;
+  if (!knob::rows_kernel()) return false;  // MRS_TG_ROWS_KERNEL=0 falls back to the tile and lane kernels
   return rows_lds_bytes(b.max_segments, 1, with_sampling) <= kRowsLdsBudget;
 }
 
 bool rows_tail_sampling_pays(const BatchView& b) { return b.n_paths <= 2048 && rows_kernel_applies(b, true); }
 
 bool rows_pipeline_applies(const BatchView& b) {
-  static const bool on = [] {  // MRS_TG_ROWS_PIPELINE=0: the separate launches (tuning / test knob, read once per process)
-    const char* e = std::getenv("MRS_TG_ROWS_PIPELINE");
-    return e == nullptr || std::atoi(e) != 0;
-  }();
   // up to one solving wavefront per SIMD (its helper shares the SIMD of another path's solver): 1024 x 10 pipeline 106.6 ->
   // 101.0 us; at 2048 paths two solvers share every SIMD and the separate launches win (153 vs 169 us)
   // (long paths: the separate launches again -- one 80-segment request 0.399 -> 0.379 ms, 64 x 80 0.706 -> 0.682, 48 / 49 segments
   // on either side of a first threshold 0.182 / 0.176, equal at 30
   // segments; the results are the same bits either way, tests/test_gpu_pipeline_shortcuts.py)
-  return on && b.n_paths > 0 && b.n_paths <= 1024 && b.max_segments <= 32 &&
+  return knob::rows_pipeline() && b.n_paths > 0 && b.n_paths <= 1024 && b.max_segments <= 32 &&
          rows_lds_bytes(b.max_segments, 1, true, true) <= kRowsLdsBudget;
 }
 
@@ -754,26 +744,19 @@ hipError_t launch_solve_rows(const BatchView& b, int d, const uint8_t* mask, con
   // wavefronts per launch let two launches run side by side, 512 two-path wavefronts four (1024 x 10, four streams:
   // 4.9 -> 4.1 us per step; alone on the device the two-path launch is 0.9 us slower)
   int ppw = (b.n_paths <= 2048 && !(shared_device_hint() && !sampling)) ? 1 : 2;
-  static const int forced_ppw = [] {  // MRS_TG_ROWS_PPW=1|2, read once per process
-    const char* e = std::getenv("MRS_TG_ROWS_PPW");
-    return e ? (std::atoi(e) == 1 ? 1 : 2) : 0;
-  }();
-  if (forced_ppw) ppw = forced_ppw;
+  if (knob::rows_ppw()) ppw = knob::rows_ppw();  // MRS_TG_ROWS_PPW=1|2
   if (rows_lds_bytes(b.max_segments, 2, sampling) > kRowsLdsBudget) ppw = 1;
   const size_t lds_bytes = rows_lds_bytes(b.max_segments, ppw, sampling);
   const bool with_tail = sampling || tail.maxima != nullptr;
+  const auto rows = with_tail ? MRS_TG_KERNEL(solve_rows_kernel<1>) : MRS_TG_KERNEL(solve_rows_kernel<0>);
   if (lds_bytes > 64 * 1024) {  // beyond the default limit of a launch: raise it (a driver call, so only when needed)
-    hipError_t e = hipFuncSetAttribute(with_tail ? (const void*)solve_rows_kernel<1> : (const void*)solve_rows_kernel<0>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRowsLdsBudget);
+    hipError_t e = set_max_dynamic_lds(rows, kRowsLdsBudget);
     if (e != hipSuccess) return e;
   }
   const unsigned grid = (unsigned)((b.n_paths + ppw - 1) / ppw);
-  if (with_tail)
-    MRS_TG_LAUNCH_TIMED(solve_rows_kernel<1>, dim3(grid), dim3(64), lds_bytes, stream, b, d, ppw, b.max_segments, mask, vals,
-                        seg_times, coeffs, status, cost, status_in, tail_k);
-  else
-    MRS_TG_LAUNCH_TIMED(solve_rows_kernel<0>, dim3(grid), dim3(64), lds_bytes, stream, b, d, ppw, b.max_segments, mask, vals,
-                        seg_times, coeffs, status, cost, status_in, tail);
+  // (tail_k is the caller's tail unless the launch samples)
+  MRS_TG_LAUNCH_TIMED(rows, dim3(grid), dim3(64), lds_bytes, stream, b, d, ppw, b.max_segments, mask, vals, seg_times, coeffs, status,
+                      cost, status_in, tail_k);
   return hipGetLastError();
 }
 
@@ -782,11 +765,7 @@ hipError_t launch_solve_rows_group(const BatchView& b, int d, const RowsGroup& g
   // two paths per wavefront as soon as the launch carries more than one small batch: a host that groups launches keeps
   // several of them in flight (on alternating streams), and at 255 VGPRs a SIMD holds two wavefronts (launch_solve_rows)
   int ppw = ((long long)b.n_paths * g.n <= 1024) ? 1 : 2;
-  static const int forced_ppw = [] {  // MRS_TG_ROWS_PPW=1|2, read once per process
-    const char* e = std::getenv("MRS_TG_ROWS_PPW");
-    return e ? (std::atoi(e) == 1 ? 1 : 2) : 0;
-  }();
-  if (forced_ppw) ppw = forced_ppw;
+  if (knob::rows_ppw()) ppw = knob::rows_ppw();  // MRS_TG_ROWS_PPW=1|2
   if (rows_lds_bytes(b.max_segments, 2, false) > kRowsLdsBudget) ppw = 1;
   const size_t lds_bytes = rows_lds_bytes(b.max_segments, ppw, false);
   if (lds_bytes > 64 * 1024) {

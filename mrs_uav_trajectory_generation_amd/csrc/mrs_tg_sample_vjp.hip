@@ -184,18 +184,13 @@ hipError_t launch_sample_vjp(const BatchView& b, const double* coeffs, const dou
   }
   const size_t lds = sizeof(double) * ((size_t)b.max_segments * (2 + kD * kN) + kSampleBuffer) + sizeof(unsigned short) * kSampleBuffer;
   if (lds > 160 * 1024) return hipErrorInvalidValue;
-  const void* fn = n_orders == 1 ? (const void*)sample_vjp_kernel<1> : (const void*)sample_vjp_kernel<kSampleStateOrders>;
+  const auto vjp = n_orders == 1 ? MRS_TG_KERNEL(sample_vjp_kernel<1>) : MRS_TG_KERNEL(sample_vjp_kernel<kSampleStateOrders>);
   if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = set_max_dynamic_lds(vjp, lds);
     if (e != hipSuccess) return e;
   }
-  if (n_orders == 1)
-    MRS_TG_LAUNCH_TIMED(sample_vjp_kernel<1>, dim3((unsigned)b.n_paths), dim3(64), lds, stream, b, coeffs, seg_times, dt, capacity,
-                        grad_states, status, grad_coeffs, grad_times, sample_segment, sample_time, n_samples, acc_table, acc_n);
-  else
-    MRS_TG_LAUNCH_TIMED(sample_vjp_kernel<kSampleStateOrders>, dim3((unsigned)b.n_paths), dim3(64), lds, stream, b, coeffs,
-                        seg_times, dt, capacity, grad_states, status, grad_coeffs, grad_times, sample_segment, sample_time,
-                        n_samples, acc_table, acc_n);
+  MRS_TG_LAUNCH_TIMED(vjp, dim3((unsigned)b.n_paths), dim3(64), lds, stream, b, coeffs, seg_times, dt, capacity, grad_states, status,
+                      grad_coeffs, grad_times, sample_segment, sample_time, n_samples, acc_table, acc_n);
   return hipGetLastError();
 }
 

@@ -573,8 +573,7 @@ bool tile_kernel_applies(const BatchView& b, bool fused) {
   // every size tried on uniform batches.  Ragged batches (3..30 segments: every tile is sized and looped for the
   // longest path of the batch) cross over earlier: blocks 4096 paths 130 vs 163, 8192 225 vs 234, 16384 478 vs 349;
   // fused 2048 779 vs 857, 4096 744 vs 736, 8192 1070 vs 960 (scripts/ragged_tile_sweep.py).
-  long long max_paths = (b.uniform_S > 0) ? (1ll << 40) : (fused ? 4096 : 8192);
-  if (const char* e = std::getenv("MRS_TG_TILE_MAX_PATHS")) max_paths = std::atoll(e);  // tuning knob (scripts/sweep_tile.sh)
+  const long long max_paths = knob::tile_max_paths((b.uniform_S > 0) ? (1ll << 40) : (fused ? 4096 : 8192));
   if (b.n_paths == 0 || b.n_paths > max_paths) return false;
   // 32-bit byte offsets into the block buffers (load_H_blocks32)
   if (!fused && (unsigned long long)b.max_segments * 800ull * (unsigned long long)b.n_paths > 0xFFFFFFFFull) return false;
@@ -591,19 +590,11 @@ hipError_t launch_solve_tile(const BatchView& b, int d, bool fused, const uint8_
   while (TP > 4 && (b.n_paths + TP - 1) / TP < 512) TP >>= 1;
   const size_t lds_bytes = per_path * (size_t)TP;
   const unsigned grid = (unsigned)((b.n_paths + TP - 1) / TP);
-  if (fused) {
-    hipError_t e = hipFuncSetAttribute((const void*)solve_tile_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)kTileLdsBudget);
-    if (e != hipSuccess) return e;
-    MRS_TG_LAUNCH_TIMED(solve_tile_kernel<true>, dim3(grid), dim3(kTileThreads), lds_bytes, stream, b, d, TP, b.max_segments, mask,
-                       vals, seg_times, H, Ainv, coeffs, status, cost, status_in);
-  } else {
-    hipError_t e = hipFuncSetAttribute((const void*)solve_tile_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)kTileLdsBudget);
-    if (e != hipSuccess) return e;
-    MRS_TG_LAUNCH_TIMED(solve_tile_kernel<false>, dim3(grid), dim3(kTileThreads), lds_bytes, stream, b, d, TP, b.max_segments, mask,
-                       vals, seg_times, H, Ainv, coeffs, status, cost, status_in);
-  }
+  const auto tile = fused ? MRS_TG_KERNEL(solve_tile_kernel<true>) : MRS_TG_KERNEL(solve_tile_kernel<false>);
+  hipError_t e = set_max_dynamic_lds(tile, kTileLdsBudget);
+  if (e != hipSuccess) return e;
+  MRS_TG_LAUNCH_TIMED(tile, dim3(grid), dim3(kTileThreads), lds_bytes, stream, b, d, TP, b.max_segments, mask, vals, seg_times, H, Ainv,
+                      coeffs, status, cost, status_in);
   return hipGetLastError();
 }
 

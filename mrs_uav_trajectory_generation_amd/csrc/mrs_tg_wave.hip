@@ -596,11 +596,7 @@ __global__ __launch_bounds__(64, MRS_TG_WAVE_WAVES) void optimize_wave_kernel(Ba
 }
 
 bool wave_kernel_applies(const BatchView& b, int dim_split) {
-  static const bool on = [] {
-    const char* e = std::getenv("MRS_TG_WAVE_KERNEL");  // tuning / test knob, read once per process
-    return e == nullptr || std::atoi(e) != 0;
-  }();
-  return on && dim_split == 4 && b.n_paths > 0 && b.max_segments <= kWaveMaxS;
+  return knob::wave_kernel() && dim_split == 4 && b.n_paths > 0 && b.max_segments <= kWaveMaxS;
 }
 
 hipError_t launch_optimize_wave(const BatchView& b, const NonlinearParams& prm, const uint8_t* mask, const double* vals,

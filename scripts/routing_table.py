@@ -3,7 +3,7 @@
 note the kernels they would launch).  Prints a markdown table of batch shape x options -> kernels; DESIGN.md section 4 holds its
 output for an MI355X, tests/test_gpu_routing.py pins the rows of the BASELINE configs and of the nodelet's defaults.
 
-    python scripts/routing_table.py > profiles/round6_routing_table.md      (needs the GPU: a plan lives on a device)
+    python scripts/routing_table.py > profiles/launch_layer_routing_table.md      (needs the GPU: a plan lives on a device)
 """
 import os
 import sys
@@ -32,6 +32,20 @@ SHAPES = [("1 x 3 (configs[0])", lambda: uniform(1, 3)), ("1 x 10 (one request)"
           ("8192 x 10 (a shard of configs[3])", lambda: uniform(8192, 10)), ("8192 ragged 3..30 (configs[4])", lambda: ragged(8192)),
           ("65536 x 10 (configs[3])", lambda: uniform(65536, 10)), ("300 x 80", lambda: uniform(300, 80)),
           ("4 x 200", lambda: uniform(4, 200))]
+# one batch on each side of every size the routers compare against (mrs_tg_nonlinear.hip: route_nonlinear, dim_split_for;
+# mrs_tg_quad.hip: quad_kernel_applies; mrs_tg_rows.hip: rows_pipeline_applies, launch_solve_rows)
+BOUNDS = [(2560, 10), (2561, 10), (1536, 14), (1537, 14),   # dimension split
+          (6143, 10), (6144, 10),                            # MRS_TG_QUAD_MIN_PATHS
+          (1024, 10), (1025, 10), (1, 32), (1, 33),          # rows pipeline
+          (2048, 10), (2049, 10),                            # one or two paths per wavefront of the rows kernel
+          (1, 121), (1, 122)]                                # two-pass lean
+SHAPES += [("%d x %d" % (n, S), lambda n=n, S=S: uniform(n, S)) for n, S in BOUNDS]
+
+
+def duo_bound_shapes(compute_units):
+    """the two sizes on either side of duo_pays' bound: 16 paths per quad wavefront, fewer than 1.25 wavefronts per SIMD"""
+    last = (compute_units * 4 * 5 // 4 - 1) * 16
+    return [("%d x 10 (two-sided solve, %d compute units)" % (n, compute_units), lambda n=n: uniform(n, 10)) for n in (last, last + 1)]
 
 MEL = dict(time_alloc_method=api.TIME_ALLOC_MELLINGER, estimate_times=1, sampling_dt=0.2, sample_capacity=512)
 OPTIONS = [("fixed times, min-snap", dict(derivative_to_optimize=4)),
@@ -44,14 +58,21 @@ OPTIONS = [("fixed times, min-snap", dict(derivative_to_optimize=4)),
 
 
 def routes(ctx):
+    import torch
     out = []
-    for sname, make in SHAPES:
+    for sname, make in SHAPES + duo_bound_shapes(torch.cuda.get_device_properties(ctx.device).multi_processor_count):
         plan = api.Plan(ctx, make())
+        def explain(opt, **kw):   # a call the library refuses (under a knob that takes its kernel away) is a row too
+            try:
+                return plan.explain(opt, **kw)
+            except api.MrsTgError as ex:
+                return ["refused: %s" % ex]
+
         for oname, kw in OPTIONS:
-            out.append((sname, oname, plan.explain(api.default_options(**kw))))
+            out.append((sname, oname, explain(api.default_options(**kw))))
         if plan.max_segments <= 15:
             opt = api.default_options(derivative_to_optimize=4)
-            out.append((sname, "fixed times, min-snap, grouped dispatch of 10 batches", plan.explain(opt, group_size=10)))
+            out.append((sname, "fixed times, min-snap, grouped dispatch of 10 batches", explain(opt, group_size=10)))
         plan.close()
     return out
 

@@ -113,8 +113,8 @@ def test_unit_time_tables_equal_the_products_constants():
 def test_unit_time_hessian_is_exactly_time_reversal_symmetric():
     """Reversing a segment's time maps end-point derivative r to (-1)^r times the other end's, and the cost does not change:
     HBAR = P^T HBAR P with P = [[0, D], [D, 0]], D = diag((-1)^r).  The rounded constants keep that symmetry to the last
-    bit, which is what lets the lean outer-loop kernels run their right-to-left half sweeps on the LEFT-to-right table in
-    sign-transformed variables (mrs_tg_sweep.hpp: PsTab, lean_flip_state) and still produce the bits of the mirrored
+    bit, which is what would let the lean outer-loop kernels run their right-to-left half sweeps on the LEFT-to-right table in
+    sign-transformed variables (the one-table build of profiles/round5_lean_table_ab.txt) and still produce the bits of the mirrored
     table: every entry the right-to-left table of stage_ps_tables holds is the left-to-right entry times sigma_r sigma_c."""
     _, h = po.unit_tables()
     sig = np.array([(-1.0) ** r for r in range(5)])
