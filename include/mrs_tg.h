@@ -186,8 +186,10 @@ enum {
   MRS_TG_CAP_REFINE = 4,       /* MRS_TG_FLAG_REFINE is honoured (refine_kernel is built in) */
   MRS_TG_CAP_GRADIENT = 8,     /* mrs_tg_plan_solve_vjp is exported: the backward pass of the fixed-times solve */
   MRS_TG_CAP_MAXIMA_GRADIENT = 16, /* mrs_tg_plan_segment_maxima_vjp is exported: the backward pass of the segment maxima */
-  MRS_TG_CAP_SAMPLE_GRADIENT = 32  /* mrs_tg_plan_sample_states_vjp and mrs_tg_plan_sample are exported: the backward pass of
+  MRS_TG_CAP_SAMPLE_GRADIENT = 32, /* mrs_tg_plan_sample_states_vjp and mrs_tg_plan_sample are exported: the backward pass of
                                       the sampler */
+  MRS_TG_CAP_EVALUATE = 64         /* mrs_tg_plan_evaluate and mrs_tg_plan_evaluate_vjp are exported: the state at caller-given
+                                      times and its backward pass */
 };
 
 typedef struct mrs_tg_options {
@@ -472,11 +474,56 @@ int mrs_tg_plan_sample_states_vjp(mrs_tg_plan* plan, const double* coeffs_dev, c
                                   const int32_t* status_dev, double* grad_coeffs_out_dev, double* grad_seg_times_out_dev,
                                   int32_t* sample_segment_out_dev, double* sample_time_out_dev, int32_t* n_samples_out_dev);
 
+/* The state of every path at caller-given times (MRS_TG_CAP_EVALUATE; evaluate_kernel):
+ * Trajectory::evaluate (trajectory.cpp:55-87) and what sampleTrajectoryAtTime / sampleFlatStateAtTime build on it.
+ * query_times_dev [n_paths][n_queries], seconds from the start of that path's trajectory, in the caller's path order; any
+ * order, duplicates allowed; a caller who wants fewer queries on some path pads with NaN.  The query t is located as the
+ * reference does: acc = 0; for i = 0 .. S-1: acc += T_i, stop at the first i with acc > t (a query on a vertex belongs to
+ * the segment on its right, zero-length segments are skipped); when no i stops the loop, i = S-1 (t equals the total);
+ * start = acc - T_i, computed like that, and tau = t - start.  states_out_dev [n_paths][n_queries][n_orders][4] holds the
+ * derivative orders 0 .. n_orders-1 (n_orders = 1 or MRS_TG_STATE_ORDERS) of (x, y, z, heading) at tau, evaluated as the
+ * sampler evaluates (Horner over j!/(j-o)! c_j, the heading of order 0 wrapped to (-pi, pi]).  OUT OF RANGE -- t < 0,
+ * t above the total, t not a number, or a total that is not a number -- gives a zero state row, segment -1 and local time 0
+ * (the reference logs and returns a zero vector; here the segment index reports it).  query_segment_out_dev (index within
+ * the path) and query_local_time_out_dev (tau), both [n_paths][n_queries], may be NULL.  n_queries == 0 succeeds and
+ * touches nothing; n_queries is not bounded by the device's LDS, the segment count is (a plan whose longest path needs
+ * more than 160 KB is refused).  Device pointers (16-byte aligned, as every allocator gives them) in CSR order,
+ * asynchronous on the context's stream. */
+int mrs_tg_plan_evaluate(mrs_tg_plan* plan, const double* coeffs_dev, const double* seg_times_dev, const double* query_times_dev,
+                         int32_t n_queries, int32_t n_orders, double* states_out_dev, int32_t* query_segment_out_dev,
+                         double* query_local_time_out_dev);
+/* Backward pass of mrs_tg_plan_evaluate (evaluate_vjp_kernel): given the gradient of a loss L with
+ * respect to the states, grad_states_dev [n_paths][n_queries][n_orders][4], writes dL/dcoeffs (grad_coeffs_out_dev
+ * [sum S][4][10]), dL/dseg_times (grad_seg_times_out_dev [sum S]) and dL/dquery_times (grad_query_times_out_dev
+ * [n_paths][n_queries]); at least one must be given.  An in-range query q in segment i at tau contributes
+ *   dL/dc[i][dim][j] += sum_{o <= min(j, n_orders-1)} G[q][o][dim] j!/(j-o)! tau^(j-o)
+ *   g_q               = sum_{o, dim} G[q][o][dim] p_dim^(o+1)(tau)       (order 4 takes the fifth derivative)
+ *   dL/dt_q           = g_q,        dL/dT_m -= g_q for every segment m < i.
+ * What is not smooth, and what the call does there:
+ *   segment membership -- held fixed; a query on a vertex gets the right-hand segment's one-sided gradient, a query at
+ *     the total time the last segment's;
+ *   the floating-point start -- differentiated as the exact prefix: dtau/dT_m = -1 for m < i, 0 otherwise, dtau/dt = 1;
+ *   heading wrap -- derivative 1;
+ *   an out-of-range query -- contributes nothing and gets dL/dt = 0; its upstream row is never read (NaN there is harmless);
+ *   with status_dev, a path with status <= 0 gets zero rows in all three outputs, whatever its coefficients hold;
+ *   a segment without a query gets zero coefficient rows and still its time gradient from the queries behind it;
+ *   a zero upstream entry contributes exactly 0.
+ * Every output element that belongs to the plan is written exactly once (zeros included; with n_queries == 0 the
+ * coefficient and time gradients are zeros).  Every sum runs in a fixed order -- a segment's queries in increasing query
+ * index from 0.0, the 4 n_orders partials of g_q in the order o * 4 + dim, the segments from the last downwards --
+ * whatever the order of the queries: deterministic, no atomics, no workspace, the same bits for a path wherever it sits in a
+ * batch.  Device pointers in CSR order, asynchronous on the context's stream. */
+int mrs_tg_plan_evaluate_vjp(mrs_tg_plan* plan, const double* coeffs_dev, const double* seg_times_dev,
+                             const double* query_times_dev, int32_t n_queries, int32_t n_orders, const double* grad_states_dev,
+                             const int32_t* status_dev, double* grad_coeffs_out_dev, double* grad_seg_times_out_dev,
+                             double* grad_query_times_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
  * 3 backward pass of the solve (mrs_tg_plan_solve_vjp), 4 backward pass of the maxima (mrs_tg_plan_segment_maxima_vjp),
- * 5 backward pass of the sampler (mrs_tg_plan_sample_states_vjp).
+ * 5 backward pass of the sampler (mrs_tg_plan_sample_states_vjp), 6 evaluation at given times (mrs_tg_plan_evaluate),
+ * 7 its backward pass (mrs_tg_plan_evaluate_vjp): eight ids, 0 .. 7.
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

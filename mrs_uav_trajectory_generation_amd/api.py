@@ -44,6 +44,7 @@ FIND_ACCEPTED, FIND_REJECTED_CODE, FIND_REJECTED_TOO_LONG, FIND_REJECTED_TOO_SHO
 STATE_ORDERS = 5   # derivative orders 0..4 per sample of Plan.sample_states (MRS_TG_STATE_ORDERS)
 KERNEL_ASSEMBLE, KERNEL_SOLVE_LINEAR, KERNEL_NONLINEAR, KERNEL_VJP, KERNEL_MAXIMA_VJP = 0, 1, 2, 3, 4
 KERNEL_SAMPLE_VJP = 5
+KERNEL_EVALUATE, KERNEL_EVALUATE_VJP = 6, 7
 
 
 class MrsTgError(RuntimeError):
@@ -102,6 +103,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_multi_solve_batch", "mrs_tg_multi_last_error",
     "mrs_tg_prepare_initial_condition", "mrs_tg_splice_prediction", "mrs_tg_plan_solve_vjp",
     "mrs_tg_plan_segment_maxima_vjp", "mrs_tg_plan_sample", "mrs_tg_plan_sample_states_vjp",
+    "mrs_tg_plan_evaluate", "mrs_tg_plan_evaluate_vjp",
 ]
 
 _lib = None
@@ -199,6 +201,10 @@ def load_library():
     L.mrs_tg_plan_sample.argtypes = [vp, dp, dp, C.c_double, C.c_int32, ip, dp]
     L.mrs_tg_plan_sample_states_vjp.restype = C.c_int
     L.mrs_tg_plan_sample_states_vjp.argtypes = [vp, dp, dp, C.c_double, C.c_int32, C.c_int32, dp, ip, dp, dp, ip, dp, ip]
+    L.mrs_tg_plan_evaluate.restype = C.c_int
+    L.mrs_tg_plan_evaluate.argtypes = [vp, dp, dp, dp, C.c_int32, C.c_int32, dp, ip, dp]
+    L.mrs_tg_plan_evaluate_vjp.restype = C.c_int
+    L.mrs_tg_plan_evaluate_vjp.argtypes = [vp, dp, dp, dp, C.c_int32, C.c_int32, dp, ip, dp, dp, dp]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -249,6 +255,7 @@ CAP_REFINE = 4         # MRS_TG_CAP_REFINE: FLAG_REFINE is honoured
 CAP_GRADIENT = 8       # MRS_TG_CAP_GRADIENT: Plan.solve_vjp (the backward pass of the fixed-times solve)
 CAP_MAXIMA_GRADIENT = 16   # MRS_TG_CAP_MAXIMA_GRADIENT: Plan.segment_maxima_vjp (the backward pass of the segment maxima)
 CAP_SAMPLE_GRADIENT = 32   # MRS_TG_CAP_SAMPLE_GRADIENT: Plan.sample_states_vjp (the backward pass of the sampler), Plan.sample
+CAP_EVALUATE = 64          # MRS_TG_CAP_EVALUATE: Plan.evaluate (the state at caller-given times), Plan.evaluate_vjp
 
 
 def capabilities():
@@ -839,6 +846,28 @@ class Plan:
                                                               _t_ptr(status), _t_ptr(grad_coeffs), _t_ptr(grad_seg_times),
                                                               _t_ptr(sample_segment), _t_ptr(sample_time), _t_ptr(n_samples)),
                         "mrs_tg_plan_sample_states_vjp")
+
+    def evaluate(self, coeffs, seg_times, query_times, states, query_segment=None, query_local_time=None):
+        """mrs_tg_plan_evaluate: the state of every path at query_times [n_paths][n_queries] (seconds from the path's start; NaN
+        = padding) into states [n_paths][n_queries][n_orders][4] (n_orders 1 or STATE_ORDERS; a 3-D tensor
+        [n_paths][n_queries][4] means 1), with the segment (int32, -1 = out of range: a zero row) and the time in it
+        [n_paths][n_queries] (device tensors, written; None = not wanted); asynchronous on the context's stream."""
+        n_orders = 1 if states.dim() == 3 else int(states.shape[2])
+        self.ctx._check(self._L.mrs_tg_plan_evaluate(self._h, _t_ptr(coeffs), _t_ptr(seg_times), _t_ptr(query_times),
+                                                     int(query_times.shape[1]), n_orders, _t_ptr(states), _t_ptr(query_segment),
+                                                     _t_ptr(query_local_time)), "mrs_tg_plan_evaluate")
+
+    def evaluate_vjp(self, coeffs, seg_times, query_times, grad_states, status=None, grad_coeffs=None, grad_seg_times=None,
+                     grad_query_times=None):
+        """mrs_tg_plan_evaluate_vjp: dL/dcoeffs [sum S][4][10], dL/dseg_times [sum S] and dL/dquery_times [n_paths][n_queries]
+        (device tensors, written; None = not wanted, at least one given) from dL/dstates (grad_states
+        [n_paths][n_queries][n_orders][4]; a 3-D tensor means n_orders 1) at (coeffs, seg_times, query_times); asynchronous on the
+        context's stream."""
+        n_orders = 1 if grad_states.dim() == 3 else int(grad_states.shape[2])
+        self.ctx._check(self._L.mrs_tg_plan_evaluate_vjp(self._h, _t_ptr(coeffs), _t_ptr(seg_times), _t_ptr(query_times),
+                                                         int(query_times.shape[1]), n_orders, _t_ptr(grad_states), _t_ptr(status),
+                                                         _t_ptr(grad_coeffs), _t_ptr(grad_seg_times), _t_ptr(grad_query_times)),
+                        "mrs_tg_plan_evaluate_vjp")
 
 
 class RoundRobin:

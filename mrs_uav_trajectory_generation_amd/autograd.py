@@ -1,6 +1,6 @@
-"""The fixed-times solve, the segment maxima and the sampler as torch.autograd.Functions: gradients of a loss on the
-coefficients, the cost, the derivative maxima and the samples reach the fixed values (waypoints, initial state), the segment
-times and the limits.
+"""The fixed-times solve, the segment maxima, the sampler and the evaluation at given times as torch.autograd.Functions:
+gradients of a loss on the coefficients, the cost, the derivative maxima, the samples and the states at chosen times reach the
+fixed values (waypoints, initial state), the segment times, the limits and the query times.
 
 Forward: Plan.solve with time_alloc_method = NONE, no sampling, no waypoints, no limits (the existing kernels, unchanged).
 Backward: Plan.solve_vjp (mrs_tg_plan_solve_vjp, vjp_kernel), the exact chain rule of the linear QP at the returned solution
@@ -31,6 +31,19 @@ waypoints to a loss on samples:
     >>> valid = torch.arange(512, device=n.device)[None, :] < n[:, None]
     >>> loss = (torch.relu(1.0 - (samples[..., :3] - obstacle).norm(dim=-1)) * valid).sum()
     >>> loss.backward()                                                 # fv.grad, times.grad
+
+evaluate (Plan.evaluate forward, Plan.evaluate_vjp backward: mrs_tg_plan_evaluate / mrs_tg_plan_evaluate_vjp, DESIGN.md section
+7c) is the other access path: the state of every path at times the caller chooses, differentiable in the coefficients, the
+segment times AND the query times, with nothing that appears or disappears as the total time moves.  The clearance between two
+UAVs at common absolute time stamps -- two plans, trajectories of different durations, one time grid:
+
+    >>> ca, _, sa = solve(plan_a, mask_a, fv_a, times_a); cb, _, sb = solve(plan_b, mask_b, fv_b, times_b)
+    >>> grid = torch.arange(0.0, 12.0, 0.1, dtype=torch.float64, device="cuda").expand(plan_a.n_paths, -1)   # seconds from the start
+    >>> pa, seg_a = evaluate(plan_a, ca, times_a, grid, n_orders=1, status=sa)   # [n_paths][120][1][4]; seg -1: behind the end
+    >>> pb, seg_b = evaluate(plan_b, cb, times_b, grid, n_orders=1, status=sb)
+    >>> both = (seg_a >= 0) & (seg_b >= 0)
+    >>> loss = (torch.relu(2.0 - (pa[..., 0, :3] - pb[..., 0, :3]).norm(dim=-1)) * both).sum()
+    >>> loss.backward()                                   # fv_a.grad, times_a.grad, fv_b.grad, times_b.grad
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -169,6 +182,56 @@ def sample(plan, coeffs, seg_times, sampling_dt, sample_capacity, status=None):
     """(samples [n_paths][capacity][4], n_samples [n_paths] int32) of Plan.sample: positions and wrapped heading, order 0 of
     sample_states (same walk, same bits, a fifth of the stores); differentiable as sample_states is."""
     return _Sample.apply(plan, coeffs, seg_times, sampling_dt, sample_capacity, status, False)
+
+
+class _Evaluate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, coeffs, seg_times, query_times, n_orders, status):
+        c = coeffs.detach().to(torch.float64).contiguous()
+        t = seg_times.detach().to(torch.float64).contiguous()
+        q = query_times.detach().to(torch.float64).contiguous()
+        if q.dim() != 2 or q.shape[0] != plan.n_paths:
+            raise ValueError("query_times must be [n_paths][n_queries]")
+        no = int(n_orders)
+        states = torch.empty((plan.n_paths, q.shape[1], no, api.N_DIM), dtype=torch.float64, device=c.device)
+        segment = torch.empty((plan.n_paths, q.shape[1]), dtype=torch.int32, device=c.device)
+        plan.ctx.use_torch_stream()
+        plan.evaluate(c, t, q, states, query_segment=segment)
+        ctx.plan = plan
+        ctx.status = None if status is None else status.detach().to(torch.int32).contiguous()
+        ctx.save_for_backward(c, t, q)
+        ctx.mark_non_differentiable(segment)
+        ctx.set_materialize_grads(False)
+        return states, segment
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_states, _grad_segment):
+        c, t, q = ctx.saved_tensors
+        want_c, want_t, want_q = ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        if grad_states is None or not (want_c or want_t or want_q):
+            return None, None, None, None, None, None
+        gc = torch.empty_like(c) if want_c else None
+        gt = torch.empty_like(t) if want_t else None
+        gq = torch.empty_like(q) if want_q else None
+        plan = ctx.plan
+        plan.ctx.use_torch_stream()   # (the autograd engine runs this on its own thread, on the forward's stream)
+        plan.evaluate_vjp(c, t, q, grad_states.to(torch.float64).contiguous(), status=ctx.status, grad_coeffs=gc,
+                          grad_seg_times=gt, grad_query_times=gq)
+        return None, gc, gt, gq, None, None
+
+
+def evaluate(plan, coeffs, seg_times, query_times, n_orders=5, status=None):
+    """(states [n_paths][n_queries][n_orders][4], segment [n_paths][n_queries] int32) of Plan.evaluate: the derivative orders
+    0 .. n_orders-1 (n_orders 1 or 5) of (x, y, z, heading) of every path at query_times [n_paths][n_queries], seconds from
+    the path's start, in any order -- differentiable in coeffs [sum S][4][10], seg_times [sum S] and query_times (float64
+    device tensors).  segment is the index within the path of the segment a query fell into, or -1 for a query that is
+    negative, behind the path's end or NaN (the padding for a path with fewer queries): its state row is zero and it gets and
+    gives no gradient.  The gradient holds the segment of every query fixed; d(time in segment)/dT_m = -1 for the segments in
+    front of the query's own, d/dquery = 1.  A path with status <= 0 (status [n_paths], optional) gets zero gradients."""
+    if int(n_orders) not in (1, api.STATE_ORDERS):
+        raise ValueError("n_orders must be 1 or %d" % api.STATE_ORDERS)
+    return _Evaluate.apply(plan, coeffs, seg_times, query_times, int(n_orders), status)
 
 
 def _root(x, p):

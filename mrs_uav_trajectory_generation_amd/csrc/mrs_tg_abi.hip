@@ -51,9 +51,9 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 6;  // kernel_id 0 .. 5 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 8;  // kernel_id 0 .. 7 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
-  long long ev_count[kTimedKernels] = {0, 0, 0, 0, 0, 0};   // timed launches since profiling was switched on
+  long long ev_count[kTimedKernels] = {0, 0, 0, 0, 0, 0, 0, 0};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
   double wall_clock_hz = 1.0e8;  // rate of s_memrealtime (hipDeviceAttributeWallClockRate)
   // plan of the most recent mrs_tg_solve_batch: a caller that sends the same batch shape again (the nodelet's
@@ -216,7 +216,7 @@ int mrs_tg_abi_version(void) { return MRS_TG_ABI_VERSION; }
 
 int mrs_tg_capabilities(void) {
   return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE |
-         MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT;
+         MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1042,6 +1042,51 @@ int mrs_tg_plan_sample_states_vjp(mrs_tg_plan* plan, const double* coeffs, const
   ProfileScope ps(ctx, 5);
   HIP_TRY(ctx, mrs_tg::launch_sample_vjp(plan->view, coeffs, seg_times, sampling_dt, sample_capacity, n_orders, grad_states, status,
                                          grad_coeffs, grad_times, sample_segment, sample_time, n_samples, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_evaluate(mrs_tg_plan* plan, const double* coeffs, const double* seg_times, const double* query_times,
+                         int32_t n_queries, int32_t n_orders, double* states, int32_t* query_segment, double* query_local_time) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (n_queries < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_queries %d is negative", n_queries);
+  if (n_orders != 1 && n_orders != MRS_TG_STATE_ORDERS)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_orders %d is neither 1 (positions and heading) nor %d (all orders)", n_orders,
+                MRS_TG_STATE_ORDERS);
+  if (!coeffs || !seg_times) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "coeffs and seg_times are required");
+  if (n_queries > 0 && (!query_times || !states))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "query_times_dev and states_out_dev are required");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 6);
+  hipError_t e = mrs_tg::launch_evaluate(plan->view, coeffs, seg_times, query_times, n_queries, n_orders, states, query_segment,
+                                         query_local_time, ctx->stream);
+  if (e == hipErrorInvalidValue)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "a path of %d segments needs more than 160 KB of LDS", plan->view.max_segments);
+  HIP_TRY(ctx, e);
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_evaluate_vjp(mrs_tg_plan* plan, const double* coeffs, const double* seg_times, const double* query_times,
+                             int32_t n_queries, int32_t n_orders, const double* grad_states, const int32_t* status,
+                             double* grad_coeffs, double* grad_times, double* grad_query_times) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (n_queries < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_queries %d is negative", n_queries);
+  if (n_orders != 1 && n_orders != MRS_TG_STATE_ORDERS)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_orders %d is neither 1 (positions and heading) nor %d (all orders)", n_orders,
+                MRS_TG_STATE_ORDERS);
+  if (!coeffs || !seg_times) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "coeffs and seg_times are required");
+  if (n_queries > 0 && (!query_times || !grad_states))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "query_times_dev and grad_states_dev are required");
+  if (!grad_coeffs && !grad_times && !grad_query_times)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_coeffs_out, grad_seg_times_out and grad_query_times_out are all NULL");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 7);
+  hipError_t e = mrs_tg::launch_evaluate_vjp(plan->view, coeffs, seg_times, query_times, n_queries, n_orders, grad_states, status,
+                                             grad_coeffs, grad_times, grad_query_times, ctx->stream);
+  if (e == hipErrorInvalidValue)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "a path of %d segments needs more than 160 KB of LDS", plan->view.max_segments);
+  HIP_TRY(ctx, e);
   return MRS_TG_OK;
 }
 

@@ -223,6 +223,17 @@ hipError_t launch_sample_vjp(const BatchView& b, const double* coeffs, const dou
                              int n_orders, const double* grad_states, const int32_t* status, double* grad_coeffs,
                              double* grad_times, int32_t* sample_segment, double* sample_time, int32_t* n_samples,
                              hipStream_t stream);
+// mrs_tg_plan_evaluate / mrs_tg_plan_evaluate_vjp (mrs_tg_evaluate.hip): the state of every path at caller-given times
+// (query_times [n_paths][n_queries] in the caller's path order, states [n_paths][n_queries][n_orders][4], n_orders 1 or
+// kSampleStateOrders; query_segment / query_tau [n_paths][n_queries] may be NULL) and its backward pass -- dL/dcoeffs,
+// dL/dseg_times and dL/dquery_times (each may be NULL) from dL/dstates; status NULL or per path (<= 0: zero rows); reads only,
+// no workspace; each timed as the kernel family of the pending ProfileScope
+hipError_t launch_evaluate(const BatchView& b, const double* coeffs, const double* seg_times, const double* query_times,
+                           int n_queries, int n_orders, double* states, int32_t* query_segment, double* query_tau,
+                           hipStream_t stream);
+hipError_t launch_evaluate_vjp(const BatchView& b, const double* coeffs, const double* seg_times, const double* query_times,
+                               int n_queries, int n_orders, const double* grad_states, const int32_t* status,
+                               double* grad_coeffs, double* grad_times, double* grad_query, hipStream_t stream);
 // phase-split tile kernel (mrs_tg_tile.hip): small and medium batches whose per-path state fits in LDS
 bool tile_kernel_applies(const BatchView& b, bool fused);
 hipError_t launch_solve_tile(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,
