@@ -50,6 +50,11 @@ inline long long quad_min_paths() { static const long long v = env_ll("MRS_TG_QU
 inline bool quad_ends() { static const bool v = env_flag("MRS_TG_QUAD_ENDS", true); return v; }
 // MRS_TG_DUO=0: never the two-sided kernel, =1: whenever the pattern allows; not set: by wavefronts per SIMD.  Every call.
 inline int duo_forced() { return env_forced("MRS_TG_DUO"); }
+// MRS_TG_DUO_UNIFORM=0: no wavefront of the two-sided kernel is treated as uniform (default 1: a wavefront whose eight paths are
+// present and of one length takes the forward loop without predicate and exchanges its coefficients through LDS before it
+// stores them; same bits either way).  A TEST knob, not a tuning one and not an interface: it exists so that
+// tests/test_gpu_duo_bits.py can hold the two roads to the same bits.  Every call.
+inline bool duo_uniform() { return env_flag("MRS_TG_DUO_UNIFORM", true); }
 // MRS_TG_TILE_MAX_PATHS=n: largest batch the tile kernel takes (scripts/sweep_tile.sh); not set: `by_shape`.  Every call.
 inline long long tile_max_paths(long long by_shape) { return env_ll("MRS_TG_TILE_MAX_PATHS", by_shape); }
 

@@ -651,7 +651,8 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
                                                const double* __restrict__ vals, const double* seg_times,
                                                double* __restrict__ coeffs, int32_t* __restrict__ status,
                                                double* __restrict__ cost, const int32_t* __restrict__ status_in, double* ws,
-                                               const RowsTail& tail, int block, const double* __restrict__ pos_wp) {
+                                               const RowsTail& tail, int block, const double* __restrict__ pos_wp,
+                                               bool uniform_loops) {
   extern __shared__ double lds[];
   const int lane = threadIdx.x, pl = lane >> 3, side = (lane >> 2) & 1, dim = lane & 3, l8 = lane & 7;
   const int q = block * kDuoPaths + pl;
@@ -771,6 +772,8 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
   if (any_moving) moving_path = __shfl((int)moving_path, lane & ~7, 64) != 0 && side == 0;  // (vertex 0 was read by lane 0 of the eight)
   const bool plain_wave = __ballot(active && !ok) == 0ull;
   const unsigned long long pos_bad = __ballot(active && !pos_ok);
+  // all eight paths present and of one length (MRS_TG_DUO_UNIFORM=0: no wavefront is treated as such)
+  const bool uni_wave = uniform_loops && __ballot(active && S == __builtin_amdgcn_readfirstlane(S)) == ~0ull;
   quad_wave_sync();
   DUO_STAMP(3);
 
@@ -820,9 +823,152 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
     for (int e = 0; e < 10; ++e) Sm[e] = 0.0;
 #pragma unroll
     for (int r = 0; r < kNB; ++r) y[r] = 0.0;
-    double p_cur = pos(ids_now(), 0);
-    DUO_STAMP(4);
-    for (int i = 0; i < Mmx; ++i) {
+    // The arithmetic of a forward step is written ONCE, in the two lambdas below, and used by two loops: the predicated one
+    // (any mix of lengths in the wavefront, a partly filled wavefront) and the one for UNIFORM wavefronts (all eight paths
+    // present, one length: every wavefront but the last of a batch of equal lengths, the runs of equal lengths of a sorted
+    // ragged one).  Same operations in the same order on the same numbers: the same bits (tests/test_gpu_duo_bits.py).
+    // (The backward loop has no uniform twin: its step as one straight block, or a second copy of it, makes the compiler park
+    // some fifty of the step's constants in lanes of a VGPR and fetch them with v_readlane -- 410-450 instructions instead of
+    // 366; and that loop is bound by its stores, not its instructions: DESIGN.md section 4.)
+    // local segment 0: the end vertex is fully constrained, the state moves to local vertex 1
+    auto fwd_first = [&](const double (&p2)[9], double dp, const double (&f0)[kNB]) {
+#pragma unroll
+      for (int r = 0; r < kNB; ++r) {
+#pragma unroll
+        for (int c = 0; c <= r; ++c) Sm[tri(r, c)] = cFar[tri(r, c)] * p2[r + c + 2];
+        y[r] = -((cF[r] * p2[r + 1]) * dp);
+      }
+      if (any_moving) {  // local vertex 1's right-hand side: - sum_c E[c][r] T^(r+c+2-2d) f_c
+#pragma unroll
+        for (int r = 0; r < kNB; ++r)
+#pragma unroll
+          for (int c = 0; c < kNB; ++c) y[r] = fma(-(cCpl[c][r] * p2[r + c + 2]), f0[c], y[r]);
+      }
+    };
+    // local vertex i >= 1: its block and right-hand side are complete with this segment's near part; rec: its record, at the
+    // path's column
+    auto fwd_interior = [&](const double (&p2)[9], double dp, double* rec, int dim_now) {
+#pragma unroll
+      for (int r = 0; r < kNB; ++r) {
+#pragma unroll
+        for (int c = 0; c <= r; ++c) Sm[tri(r, c)] = fma(cNear[tri(r, c)], p2[r + c + 2], Sm[tri(r, c)]);
+        y[r] = fma(-(cN[r] * p2[r + 1]), dp, y[r]);
+      }
+      double L[10], Linv[kNB], z[kNB];
+#pragma unroll
+      for (int c = 0; c < kNB; ++c) {
+        double dsum = Sm[tri(c, c)];
+#pragma unroll
+        for (int mm = 0; mm < c; ++mm) dsum = fma(-L[tri(c, mm)], L[tri(c, mm)], dsum);
+        const double inv = rsqrt_refined(dsum);
+        Linv[c] = inv;
+#pragma unroll
+        for (int r = c + 1; r < kNB; ++r) {
+          double t = Sm[tri(r, c)];
+#pragma unroll
+          for (int mm = 0; mm < c; ++mm) t = fma(-L[tri(r, mm)], L[tri(c, mm)], t);
+          L[tri(r, c)] = t * inv;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < kNB; ++r) {
+        double t = y[r];
+#pragma unroll
+        for (int mm = 0; mm < r; ++mm) t = fma(-L[tri(r, mm)], z[mm], t);
+        z[r] = t * Linv[r];
+      }
+      if (dim_now == 0) {
+        rec[(kQdL + 0) * kDuoPaths] = L[tri(1, 0)];
+        rec[(kQdL + 1) * kDuoPaths] = L[tri(2, 0)];
+        rec[(kQdL + 2) * kDuoPaths] = L[tri(2, 1)];
+        rec[(kQdL + 3) * kDuoPaths] = L[tri(3, 0)];
+        rec[(kQdL + 4) * kDuoPaths] = L[tri(3, 1)];
+        rec[(kQdL + 5) * kDuoPaths] = L[tri(3, 2)];
+#pragma unroll
+        for (int r = 0; r < kNB; ++r) rec[(kQdLinv + r) * kDuoPaths] = Linv[r];
+      }
+#pragma unroll
+      for (int r = 0; r < kNB; ++r) rec[(kQdZ + r * kD + dim_now) * kDuoPaths] = z[r];
+      // W = L^-1 E, then the Schur complement and right-hand side of local vertex i + 1 (always an unknown: the next one
+      // of this side, or the middle vertex)
+      double W[kNB][kNB];
+#pragma unroll
+      for (int c = 0; c < kNB; ++c)
+#pragma unroll
+        for (int r = 0; r < kNB; ++r) {
+          double t = cCpl[r][c] * p2[r + c + 2];
+#pragma unroll
+          for (int mm = 0; mm < r; ++mm) t = fma(-L[tri(r, mm)], W[mm][c], t);
+          W[r][c] = t * Linv[r];
+        }
+#pragma unroll
+      for (int r = 0; r < kNB; ++r) {
+#pragma unroll
+        for (int c = 0; c <= r; ++c) {
+          double t = cFar[tri(r, c)] * p2[r + c + 2];
+#pragma unroll
+          for (int mm = 0; mm < kNB; ++mm) t = fma(-W[mm][r], W[mm][c], t);
+          Sm[tri(r, c)] = t;
+        }
+        double t = -((cF[r] * p2[r + 1]) * dp);
+#pragma unroll
+        for (int mm = 0; mm < kNB; ++mm) t = fma(-W[mm][r], z[mm], t);
+        y[r] = t;
+      }
+    };
+    // the start vertex's constrained derivative values (MOVING, side 0 of a path that starts in motion)
+    auto moving_values = [&](int dim_now, double (&f)[kNB]) {
+      const double* vrow0 = vals + (size_t)pr.v0 * kHalf * kD + dim_now;
+#pragma unroll
+      for (int r = 0; r < kNB; ++r) f[r] = vrow0[(r + 1) * kD];
+    };
+    // uniform wavefronts: S_u segments on every path, side 0 eliminates M0 vertices, side 1 M1 (M0 - M1 is 0 or 1); the uniform
+    // loop takes the M1 steps that both sides have, the predicated loop the step in between (and every step of other wavefronts)
+    const int S_u = __builtin_amdgcn_readfirstlane(S);
+    const int M0 = (S_u + 1) >> 1, M1 = S_u - M0;
+    int i_lo = 0, i_hi = Mmx;
+    double p_cur;
+    if (uni_wave) {
+      // no predicate, no clamp; the LDS addresses of times, positions and records walk by a per-lane stride: + on side 0,
+      // - on side 1 (original index of local segment i: i | S - 1 - i, of local vertex v: v | S - v)
+      const LaneIds id = ids_now();
+      const int v1 = id.side ? S_u - 1 : 1;  // local vertex 1; on side 1 also local segment 0
+      const int st = id.side ? -kDuoPaths : kDuoPaths, sp = st * kD, sr = st * kQdRec;
+      const double* tp = tbuf + (id.side ? v1 : 0) * kDuoPaths + id.pl;
+      const double* pp = pbuf + (v1 * kD + id.dim) * kDuoPaths + id.pl;
+      double* rp = rec0 + (v1 - 1) * kQdRec * kDuoPaths + id.pl;
+      p_cur = pbuf[((id.side ? S_u : 0) * kD + id.dim) * kDuoPaths + id.pl];
+      DUO_STAMP(4);
+      {
+        const double T = *tp, p_nxt = *pp;
+        double p2[9];
+        quad_powers(T, d1, d2, d4, p2);
+        double f0[kNB] = {0.0, 0.0, 0.0, 0.0};
+        if (any_moving && moving_path) moving_values(id.dim, f0);  // (side 0 only: moving_path is false on side 1)
+        fwd_first(p2, p_cur - p_nxt, f0);
+        p_cur = p_nxt;
+      }
+      DUO_STAMP(5);
+      for (int i = 1; i < M1; ++i) {
+        tp += st;
+        pp += sp;
+        const double T = *tp, p_nxt = *pp;
+        double p2[9];
+        quad_powers(T, d1, d2, d4, p2);
+        fwd_interior(p2, p_cur - p_nxt, rp, lane_now() & 3);
+        rp += sr;
+        p_cur = p_nxt;
+#ifdef MRS_TG_DUO_STAMPS
+        if (i == 1) DUO_STAMP(6);
+#endif
+      }
+      i_lo = M1;
+      i_hi = M0;
+    } else {
+      p_cur = pos(ids_now(), 0);
+      DUO_STAMP(4);
+    }
+    for (int i = i_lo; i < i_hi; ++i) {
       const LaneIds id = ids_now();
       const bool on = active && i < side_len(id.side);
       const double T = on ? tbuf[oseg(id.side, i) * kDuoPaths + id.pl] : 1.0;
@@ -831,95 +977,12 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
       quad_powers(T, d1, d2, d4, p2);
       const double dp = p_cur - p_nxt;
       double f0[kNB] = {0.0, 0.0, 0.0, 0.0};
-      if (any_moving && i == 0 && active && moving_path) {  // (side 0 only: moving_path is false on side 1)
-        const double* vrow0 = vals + (size_t)pr.v0 * kHalf * kD + id.dim;
-#pragma unroll
-        for (int r = 0; r < kNB; ++r) f0[r] = vrow0[(r + 1) * kD];
-      }
+      if (any_moving && i == 0 && active && moving_path) moving_values(id.dim, f0);  // (side 0 only, as above)
       if (on) {
-        if (i == 0) {  // the end vertex is fully constrained: the state moves to local vertex 1
-#pragma unroll
-          for (int r = 0; r < kNB; ++r) {
-#pragma unroll
-            for (int c = 0; c <= r; ++c) Sm[tri(r, c)] = cFar[tri(r, c)] * p2[r + c + 2];
-            y[r] = -((cF[r] * p2[r + 1]) * dp);
-          }
-          if (any_moving) {  // local vertex 1's right-hand side: - sum_c E[c][r] T^(r+c+2-2d) f_c
-#pragma unroll
-            for (int r = 0; r < kNB; ++r)
-#pragma unroll
-              for (int c = 0; c < kNB; ++c) y[r] = fma(-(cCpl[c][r] * p2[r + c + 2]), f0[c], y[r]);
-          }
+        if (i == 0) {
+          fwd_first(p2, dp, f0);
         } else {
-          // local vertex i: its block and right-hand side are complete with this segment's near part
-#pragma unroll
-          for (int r = 0; r < kNB; ++r) {
-#pragma unroll
-            for (int c = 0; c <= r; ++c) Sm[tri(r, c)] = fma(cNear[tri(r, c)], p2[r + c + 2], Sm[tri(r, c)]);
-            y[r] = fma(-(cN[r] * p2[r + 1]), dp, y[r]);
-          }
-          double L[10], Linv[kNB], z[kNB];
-#pragma unroll
-          for (int c = 0; c < kNB; ++c) {
-            double dsum = Sm[tri(c, c)];
-#pragma unroll
-            for (int mm = 0; mm < c; ++mm) dsum = fma(-L[tri(c, mm)], L[tri(c, mm)], dsum);
-            const double inv = rsqrt_refined(dsum);
-            Linv[c] = inv;
-#pragma unroll
-            for (int r = c + 1; r < kNB; ++r) {
-              double t = Sm[tri(r, c)];
-#pragma unroll
-              for (int mm = 0; mm < c; ++mm) t = fma(-L[tri(r, mm)], L[tri(c, mm)], t);
-              L[tri(r, c)] = t * inv;
-            }
-          }
-#pragma unroll
-          for (int r = 0; r < kNB; ++r) {
-            double t = y[r];
-#pragma unroll
-            for (int mm = 0; mm < r; ++mm) t = fma(-L[tri(r, mm)], z[mm], t);
-            z[r] = t * Linv[r];
-          }
-          double* rec = rec0 + (size_t)(overt(id.side, i) - 1) * kQdRec * kDuoPaths + id.pl;
-          if (id.dim == 0) {
-            rec[(kQdL + 0) * kDuoPaths] = L[tri(1, 0)];
-            rec[(kQdL + 1) * kDuoPaths] = L[tri(2, 0)];
-            rec[(kQdL + 2) * kDuoPaths] = L[tri(2, 1)];
-            rec[(kQdL + 3) * kDuoPaths] = L[tri(3, 0)];
-            rec[(kQdL + 4) * kDuoPaths] = L[tri(3, 1)];
-            rec[(kQdL + 5) * kDuoPaths] = L[tri(3, 2)];
-#pragma unroll
-            for (int r = 0; r < kNB; ++r) rec[(kQdLinv + r) * kDuoPaths] = Linv[r];
-          }
-#pragma unroll
-          for (int r = 0; r < kNB; ++r) rec[(kQdZ + r * kD + id.dim) * kDuoPaths] = z[r];
-          // W = L^-1 E, then the Schur complement and right-hand side of local vertex i + 1 (always an unknown: the next one
-          // of this side, or the middle vertex)
-          double W[kNB][kNB];
-#pragma unroll
-          for (int c = 0; c < kNB; ++c)
-#pragma unroll
-            for (int r = 0; r < kNB; ++r) {
-              double t = cCpl[r][c] * p2[r + c + 2];
-#pragma unroll
-              for (int mm = 0; mm < r; ++mm) t = fma(-L[tri(r, mm)], W[mm][c], t);
-              W[r][c] = t * Linv[r];
-            }
-#pragma unroll
-          for (int r = 0; r < kNB; ++r) {
-#pragma unroll
-            for (int c = 0; c <= r; ++c) {
-              double t = cFar[tri(r, c)] * p2[r + c + 2];
-#pragma unroll
-              for (int mm = 0; mm < kNB; ++mm) t = fma(-W[mm][r], W[mm][c], t);
-              Sm[tri(r, c)] = t;
-            }
-            double t = -((cF[r] * p2[r + 1]) * dp);
-#pragma unroll
-            for (int mm = 0; mm < kNB; ++mm) t = fma(-W[mm][r], z[mm], t);
-            y[r] = t;
-          }
+          fwd_interior(p2, dp, rec0 + (size_t)(overt(id.side, i) - 1) * kQdRec * kDuoPaths + id.pl, id.dim);
         }
       }
       p_cur = p_nxt;
@@ -972,7 +1035,7 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
       xn[1] = fma(-L[tri(3, 1)], xn[3], fma(-L[tri(2, 1)], xn[2], z[1])) * Linv[1];
       xn[0] = fma(-L[tri(3, 0)], xn[3], fma(-L[tri(2, 0)], xn[2], fma(-L[tri(1, 0)], xn[1], z[0]))) * Linv[0];
     }
-    quad_wave_sync();  // (lane 0 of a side wrote L for the other three)
+    quad_wave_sync();  // (the forward loop's records -- L written by the lane of dimension 0 for the other three -- are read below)
     DUO_STAMP(8);
     // ---- backward through this side's half: x_v = L^-T (z - W x_{v+1}); coefficients and cost of local segment v
     double p_end;
@@ -1064,8 +1127,46 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
         quad_powers(T, d1, d2, d4, p2);  // p2[0] = T^(1 - 2d)
         my_cost = fma(cost_quadratic_form<kOrder>(cb), p2[0], my_cost);
         double2* out = reinterpret_cast<double2*>(coeffs + ((size_t)(pr.s0 + oseg(side, v)) * kD + dim) * kN);
+        // A lane owns 80 consecutive bytes of its segment's 320, so a store instruction of 16 bytes per lane writes 64 separate
+        // pieces over 50-odd cache lines, and the kernel is bound by that: with the stores left out a wavefront lives 30.7 k
+        // clocks instead of 45.1 k (profiles/round6_duo_phase_clocks.txt, "stores").  In a uniform wavefront the four lanes of a
+        // segment exchange their pairs through LDS first, so that an instruction writes 64 consecutive bytes per segment: 16
+        // half lines.  The exchange buffer (16 segments x 320 bytes) lies in the records this step and the steps before it
+        // have read: rows v .. S - v of the record store, at least kXchgRows of them (the first step of a side has three and
+        // stores as before).  One wavefront, LDS in program order: the reads of this step's records precede the writes below.
+        // (rows the buffer needs: 2 sides x 8 paths x 40 doubles over rows of kQdRec x 8 -- four today)
+        constexpr int kXchgDoubles = 2 * kDuoPaths * kD * kN, kRowDoubles = kQdRec * kDuoPaths;
+        constexpr int kXchgRows = (kXchgDoubles + kRowDoubles - 1) / kRowDoubles;
+        static_assert(kD == 4 && kN % 2 == 0, "a row of four lanes writes 64 consecutive bytes: one pair per dimension");
+#if defined(MRS_TG_DUO_STORE_EXPERIMENT) && MRS_TG_DUO_STORE_EXPERIMENT == 1
+        // experiment build (WRONG results; profiles/round6_duo_phase_clocks.txt, "stores"): no coefficient store at all
 #pragma unroll
-        for (int k = 0; k < kN; k += 2) store_coeff_pair(out + k / 2, c[k], c[k + 1]);
+        for (int k = 0; k < kN; k += 2) asm volatile("; keep %0 %1" ::"v"(c[k]), "v"(c[k + 1]));
+        if (false)
+#elif defined(MRS_TG_DUO_STORE_EXPERIMENT) && MRS_TG_DUO_STORE_EXPERIMENT == 2
+        // experiment build (WRONG results; same place): the step's 5120 bytes as whole lines inside the wavefront's own output
+        if (uni_wave) {
+          double2* wbase = reinterpret_cast<double2*>(coeffs + (size_t)(pr.s0 - pl * S) * kD * kN) + (v * 5 * 64 + (pl * 8 + side * 4 + dim));
+#pragma unroll
+          for (int k = 0; k < kN; k += 2) store_coeff_pair(wbase + (k / 2) * 64, c[k], c[k + 1]);
+        } else
+#endif
+        if (uni_wave && v < M1 && S_u - 2 * max(v, 1) + 1 >= kXchgRows) {
+          double2* xbuf = reinterpret_cast<double2*>(rec0 + (size_t)max(v - 1, 0) * kQdRec * kDuoPaths) + (pl * 2 + side) * (kD * kN / 2);
+#pragma unroll
+          for (int k = 0; k < kN; k += 2) xbuf[dim * (kN / 2) + k / 2] = make_double2(c[k], c[k + 1]);
+          quad_wave_sync();
+          double2* out4 = out - 4 * dim;  // (the segment's first pair + this lane's place in a row of four)
+#pragma unroll
+          for (int t = 0; t < kN / 2; ++t) {
+            const double2 piece = xbuf[4 * t + dim];
+            store_coeff_pair(out4 + 4 * t, piece.x, piece.y);
+          }
+          quad_wave_sync();  // (the next step's records are other rows; the buffer of the next step overlaps this one)
+        } else {
+#pragma unroll
+          for (int k = 0; k < kN; k += 2) store_coeff_pair(out + k / 2, c[k], c[k + 1]);
+        }
       }
       if (on) {  // (a side shorter than the wavefront's longest joins late: until then xn is the middle vertex's solution)
 #pragma unroll
@@ -1110,16 +1211,19 @@ __global__ __launch_bounds__(64, MRS_TG_QUAD_WAVES) void solve_duo_kernel(BatchV
                                                        const double* __restrict__ vals, const double* seg_times,
                                                        double* __restrict__ coeffs, int32_t* __restrict__ status,
                                                        double* __restrict__ cost, const int32_t* __restrict__ status_in,
-                                                       double* ws, RowsTail tail) {
-  solve_duo_body<WP, true>(b, d, mask, vals, seg_times, coeffs, status, cost, status_in, ws, tail, (int)blockIdx.x, tail.pos_wp);
+                                                       double* ws, RowsTail tail, int uniform_loops) {
+  solve_duo_body<WP, true>(b, d, mask, vals, seg_times, coeffs, status, cost, status_in, ws, tail, (int)blockIdx.x, tail.pos_wp,
+                           uniform_loops != 0);
 }
 
 template <bool WP>
 __global__ __launch_bounds__(64, MRS_TG_DUO_GROUP_WAVES) void solve_duo_group_kernel(BatchView b, int d, RowsGroup g, double* ws,
-                                                                                    size_t ws_batch_doubles, int blocks_per_batch) {
+                                                                                    size_t ws_batch_doubles, int blocks_per_batch,
+                                                                                    int uniform_loops) {
   const int j = __builtin_amdgcn_readfirstlane((int)blockIdx.x / blocks_per_batch);
   solve_duo_body<WP>(b, d, g.mask[j], g.vals[j], g.seg_times[j], g.coeffs[j], g.status[j], g.cost[j], nullptr,
-                     ws + (size_t)j * ws_batch_doubles, RowsTail(), (int)blockIdx.x - j * blocks_per_batch, g.pos_wp[j]);
+                     ws + (size_t)j * ws_batch_doubles, RowsTail(), (int)blockIdx.x - j * blocks_per_batch, g.pos_wp[j],
+                     uniform_loops != 0);
 }
 
 template <bool WP, bool ENDS = false>
@@ -1181,7 +1285,7 @@ hipError_t launch_solve_quad(const BatchView& b, int d, const uint8_t* mask, con
     }
     const unsigned grid_duo = (unsigned)((b.n_paths + kDuoPaths - 1) / kDuoPaths);
     MRS_TG_LAUNCH_TIMED(duo, dim3(grid_duo), dim3(64), lds_duo, stream, b, d, mask, vals, seg_times, coeffs, status, cost, status_in,
-                        ws, tail);
+                        ws, tail, (int)knob::duo_uniform());
     return hipGetLastError();
   }
   const size_t lds_bytes = quad_lds_doubles(b.max_segments, ends) * sizeof(double);
@@ -1214,7 +1318,7 @@ hipError_t launch_solve_quad_group(const BatchView& b, int d, const RowsGroup& g
     const int per_batch_duo = (b.n_paths + kDuoPaths - 1) / kDuoPaths;
     const dim3 grid_duo((unsigned)(per_batch_duo * g.n));
     const size_t wsd_duo = linear_workspace_doubles(b);
-    MRS_TG_LAUNCH_TIMED(duo, grid_duo, dim3(64), lds_duo, stream, b, d, g, ws, wsd_duo, per_batch_duo);
+    MRS_TG_LAUNCH_TIMED(duo, grid_duo, dim3(64), lds_duo, stream, b, d, g, ws, wsd_duo, per_batch_duo, (int)knob::duo_uniform());
     return hipGetLastError();
   }
   const auto quad = ends ? (wp ? MRS_TG_KERNEL(solve_quad_group_kernel<true, true>) : MRS_TG_KERNEL(solve_quad_group_kernel<false, true>))
