@@ -586,7 +586,8 @@ __device__ __forceinline__ void solve_quad_body(const BatchView& b, int d, const
 // Memory: every global load in the prologue, in one round; the position constraints, the times and the paths' indices wait in
 // LDS; no register is carried across the loops that the compiler would spill ("What bounds the two-sided
 // kernel": loads and stores share one in-order counter on gfx950, so a load or a scratch reload in the loops waits for the
-// coefficient stores in flight).  Min-snap only (the launchers send nothing else; the ABI sends paths of up to 15 segments).
+// coefficient stores in flight).  Min-snap only (the launchers send nothing else).  Paths of up to 24 segments:
+// the routing's only length rule is quad_kernel_applies, the four-lane record store within kQuadLdsBudget.
 constexpr int kDuoPaths = 8;  // paths per wavefront
 
 __host__ __device__ constexpr size_t duo_lds_doubles(int Smax) {
@@ -748,7 +749,7 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
       }
     }
   };
-  // (the first trip is straight-line code -- all there is for paths of up to 15 segments: inside a loop the compiler has to
+  // (the first trip is straight-line code -- all there is for batches of up to 15 segments: inside a loop the compiler has to
   // assume loads of the previous trip in flight and waits for the end vertices' values before it issues the positions' loads)
   trip(0);
   for (int base = 16; base <= Smax; base += 16) trip(base);

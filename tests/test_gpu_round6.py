@@ -120,7 +120,8 @@ def test_two_sided_solve_against_the_oracle(gpu_ctx, shape, n_paths, moving):
     vertex -- the launch shape of dispatches that would leave SIMDs idle as quad wavefronts (6144 .. 20479 paths).  Against the
     oracle in the reference's arithmetic (1e-7; 1e-6 on paths with a segment below 0.5 s, where that route itself is off) and in
     113 bits (the HIP path's own error: median below 1e-13, worst 1e-8), costs included; continuity and constraints on every path."""
-    if shape == "short":   # ragged, 3 .. 15 segments (the LDS record of the four- and eight-lane kernels holds 15)
+    if shape == "short":   # ragged, 3 .. 15 segments (the LDS record of the four- and eight-lane kernels holds 24: 16 .. 24 are
+        # tests/test_gpu_solve_16_to_24_segments.py's)
         rag = pr.random_batch(3 * n_paths, "ragged", seed0=777)
         keep = [p for p in range(rag.n_paths) if rag.seg_offsets[p + 1] - rag.seg_offsets[p] <= 15][:n_paths]
         assert len(keep) == n_paths
