@@ -55,6 +55,11 @@ inline int duo_forced() { return env_forced("MRS_TG_DUO"); }
 // stores them; same bits either way).  A TEST knob, not a tuning one and not an interface: it exists so that
 // tests/test_gpu_duo_bits.py can hold the two roads to the same bits.  Every call.
 inline bool duo_uniform() { return env_flag("MRS_TG_DUO_UNIFORM", true); }
+// MRS_TG_DUO_STORE_THROUGH=0: every coefficient store of the two-sided kernels is an ordinary one (default 1: in the grouped
+// dispatch, the stores of a uniform wavefront's exchange road -- 64 consecutive bytes per segment and instruction -- are
+// write-through stores, which leave no dirty lines in L2 for the end of the dispatch to write back; same bytes either way).  A
+// TEST knob like the one above, not an interface: tests/test_gpu_duo_store_through.py holds the two to the same bits.  Every call.
+inline bool duo_store_through() { return env_flag("MRS_TG_DUO_STORE_THROUGH", true); }
 // MRS_TG_TILE_MAX_PATHS=n: largest batch the tile kernel takes (scripts/sweep_tile.sh); not set: `by_shape`.  Every call.
 inline long long tile_max_paths(long long by_shape) { return env_ll("MRS_TG_TILE_MAX_PATHS", by_shape); }
 

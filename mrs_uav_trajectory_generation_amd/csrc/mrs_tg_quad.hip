@@ -88,10 +88,40 @@ __device__ __forceinline__ void quad_powers(double T, bool d1, bool d2, bool d4,
 
 // a pair of coefficients (16 bytes), an ordinary store.  As a streaming store (an experiment build) -- measured in round 6 after
 // the samples and the assembled blocks had gained from it: here it is 2.5-3 x SLOWER (headline dispatch 26 -> 73-81 us, 65536 x 10
-// 131 -> 335-339 us): a lane owns 80 consecutive bytes, so a store instruction writes 64 separate 16-byte pieces, and without the
-// L2 to combine them every piece is a partial-line write to HBM.  Streaming pays where an instruction writes whole lines.
+// 131 -> 335-339 us).  That trial is about SEPARATE 16-BYTE PIECES: a lane owned 80 consecutive bytes then, so a store instruction
+// wrote 64 of them, and without the L2 to combine them every piece is a partial-line write to HBM.  It says nothing about a store
+// instruction that writes 64 consecutive bytes per segment (store_coeff_pair_through below); it does say that a store of separate
+// pieces must stay an ordinary one.
 __device__ __forceinline__ void store_coeff_pair(double2* dst, double a, double b) {
   *dst = make_double2(a, b);
+}
+
+// The same 16 bytes as a store that leaves the XCD's L2 at once instead of staying there as a dirty line until the release at the
+// end of the dispatch writes all of them back.  Only where the lanes of a store instruction write
+// 64 consecutive bytes per segment (the exchange road of solve_duo_body), and only in a dispatch whose coefficients no kernel
+// reads next: the line does not stay in L2.  MRS_TG_DUO_THROUGH_FORM (experiment builds: the A/B of profiles/duo_store_through_ab.txt):
+// 1 = write-through at agent scope (sc1; the default), 2 = at system scope (sc0 sc1), 3 = the compiler's non-temporal store (nt).
+// (inline assembly: the compiler has no 16-byte store with these cache bits to lower to.  It reads registers only -- no memory
+// clobber, the LDS reads around it keep their schedule; the closing s_nop keeps the compiler's next instruction off the data
+// registers until the store has read them.  The compiler does not count it in vmcnt: its own waits are then stricter than
+// needed, never weaker, and there is no load behind these stores.)
+#ifndef MRS_TG_DUO_THROUGH_FORM
+#define MRS_TG_DUO_THROUGH_FORM 1
+#endif
+// (BYTES: the instruction's offset field, so that the five stores of a step share one address register pair)
+template <int BYTES>
+__device__ __forceinline__ void store_coeff_pair_through(double2* dst, double2 v) {
+  typedef int int4v __attribute__((ext_vector_type(4)));
+  const int4v bits = __builtin_bit_cast(int4v, v);
+#if MRS_TG_DUO_THROUGH_FORM == 3
+  __builtin_nontemporal_store(bits, reinterpret_cast<int4v*>(dst + BYTES / 16));
+#else
+#if MRS_TG_DUO_THROUGH_FORM == 2
+  asm volatile("global_store_dwordx4 %0, %1, off offset:%2 sc0 sc1\n\ts_nop 1" ::"v"(dst), "v"(bits), "i"(BYTES));
+#else
+  asm volatile("global_store_dwordx4 %0, %1, off offset:%2 sc1\n\ts_nop 1" ::"v"(dst), "v"(bits), "i"(BYTES));
+#endif
+#endif
 }
 
 __device__ __forceinline__ void quad_wave_sync() {
@@ -590,13 +620,30 @@ __device__ __forceinline__ void solve_quad_body(const BatchView& b, int d, const
 // the routing's only length rule is quad_kernel_applies, the four-lane record store within kQuadLdsBudget.
 constexpr int kDuoPaths = 8;  // paths per wavefront
 
+// the coefficient exchange of a uniform wavefront (solve_duo_body's backward loop): one chunk of 4 dimensions x 10 coefficients
+// per (path, side); the last of the sixteen chunks has a place of its own behind the path indices, the others lie in record rows
+constexpr int kDuoXchgChunk = kD * kN;  // doubles
+
 __host__ __device__ constexpr size_t duo_lds_doubles(int Smax) {
   return (size_t)(Smax > 1 ? Smax - 1 : 1) * kQdRec * kDuoPaths + (size_t)Smax * kDuoPaths +  // records | times
-         (size_t)(Smax + 1) * kD * kDuoPaths + kDuoPaths / 2;                                   // | position constraints | path indices
+         (size_t)(Smax + 1) * kD * kDuoPaths + kDuoPaths / 2 +                                  // | position constraints | path indices
+         kDuoXchgChunk;                                                                         // | the sixteenth exchange chunk
 }
+// The chunk's 320 bytes change neither residency nor routing: the headline's 10 segments stay at eight wavefronts per CU (two per
+// SIMD) within the CU's 160 KB, and at every length the four-lane kernel's record store -- the routing's only length rule,
+// quad_kernel_applies -- is the larger of the two, so whatever that rule admits (24 segments today) fits kQuadLdsBudget here too.
+static_assert(8 * duo_lds_doubles(10) * sizeof(double) <= 160 * 1024, "two-sided kernel at 10 segments: two wavefronts per SIMD");
+static_assert(duo_lds_doubles(2) <= quad_lds_doubles(2) && duo_lds_doubles(24) <= quad_lds_doubles(24) &&
+                  duo_lds_doubles(64) <= quad_lds_doubles(64),
+              "(both grow linearly, the four-lane store faster: 432 against 248 doubles per segment)");
 
 #ifdef MRS_TG_DUO_STAMPS  // experiment builds (build.py --variant): the shader clock at the phase boundaries of each wavefront
-__device__ unsigned long long g_duo_stamps[2048 * 16];
+// slots 0 .. 13: the shader clock (s_memtime: one counter per XCD, not comparable across wavefronts of different XCDs); 14 and 15:
+// the device-wide 100 MHz clock (s_memrealtime) at entry and behind the final wait -- first entry -> last exit of a dispatch
+// in microseconds, and shader clocks per microsecond; 16: which dispatch wrote the row (the grouped kernel: its first batch's
+// coefficient array), since the headline's two dispatches run side by side and share the rows
+constexpr int kDuoStampSlots = 20;
+__device__ unsigned long long g_duo_stamps[2048 * kDuoStampSlots];
 #define DUO_STAMP(k) (duo_stamp[k] = __builtin_readcyclecounter())
 #else
 #define DUO_STAMP(k)
@@ -647,13 +694,17 @@ __device__ __forceinline__ void duo_finish(double my_cost, bool active, unsigned
   }
 }
 
-template <bool WP, bool MOVING = false>
+// THROUGH: the coefficient stores of the exchange road may be write-through stores (store_coeff_pair_through), `through` says
+// whether this call's are (MRS_TG_DUO_STORE_THROUGH).  On for the grouped dispatch, whose coefficients nothing on the device
+// reads next; off for the single launch: the sampling, the maxima or a second solve read its coefficients right behind it, and a
+// written-through line does not stay in L2.
+template <bool WP, bool MOVING = false, bool THROUGH = false>
 __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const uint8_t* __restrict__ mask,
                                                const double* __restrict__ vals, const double* seg_times,
                                                double* __restrict__ coeffs, int32_t* __restrict__ status,
                                                double* __restrict__ cost, const int32_t* __restrict__ status_in, double* ws,
                                                const RowsTail& tail, int block, const double* __restrict__ pos_wp,
-                                               bool uniform_loops) {
+                                               bool uniform_loops, bool through = false) {
   extern __shared__ double lds[];
   const int lane = threadIdx.x, pl = lane >> 3, side = (lane >> 2) & 1, dim = lane & 3, l8 = lane & 7;
   const int q = block * kDuoPaths + pl;
@@ -665,6 +716,7 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
   double* tbuf = lds + (size_t)(Smax > 1 ? Smax - 1 : 1) * kQdRec * kDuoPaths;  // [segment][path]
 #ifdef MRS_TG_DUO_STAMPS
   unsigned long long duo_stamp[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  duo_stamp[14] = __builtin_amdgcn_s_memrealtime();
 #endif
   DUO_STAMP(0);
   // ---- prologue: times (scaled, for the last solve of a Mellinger pipeline), plainness of the path, the position constraints
@@ -1132,12 +1184,23 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
         // pieces over 50-odd cache lines, and the kernel is bound by that: with the stores left out a wavefront lives 30.7 k
         // clocks instead of 45.1 k (profiles/round6_duo_phase_clocks.txt, "stores").  In a uniform wavefront the four lanes of a
         // segment exchange their pairs through LDS first, so that an instruction writes 64 consecutive bytes per segment: 16
-        // half lines.  The exchange buffer (16 segments x 320 bytes) lies in the records this step and the steps before it
-        // have read: rows v .. S - v of the record store, at least kXchgRows of them (the first step of a side has three and
-        // stores as before).  One wavefront, LDS in program order: the reads of this step's records precede the writes below.
-        // (rows the buffer needs: 2 sides x 8 paths x 40 doubles over rows of kQdRec x 8 -- four today)
-        constexpr int kXchgDoubles = 2 * kDuoPaths * kD * kN, kRowDoubles = kQdRec * kDuoPaths;
-        constexpr int kXchgRows = (kXchgDoubles + kRowDoubles - 1) / kRowDoubles;
+        // half lines.  The exchange buffer is one chunk of 320 bytes per segment; a quad of lanes writes and reads its own chunk
+        // only.  The chunks lie in the records this step and the steps before it have read -- the rows of vertices v .. S - v,
+        // S - 2 max(v, 1) + 1 of them (the middle vertex's row, which nobody writes, among them) -- and the sixteenth has a place of
+        // its own (duo_lds_doubles):
+        //   * a step of both sides (v < M1) has sixteen segments; fifteen chunks need three rows, which every such step has from
+        //     S = 4 on -- the first step of a side, which has exactly three, included;
+        //   * the step in between of an odd length (v = M1, side 0 alone: the lanes of side 1 are masked off here) has eight
+        //     segments, chunk = path, and exactly two dead rows, the row of vertex v and the middle vertex's: eight chunks fit.
+        //     The rows side 1 still has to read (vertices S - M1 + 1 .. S - 1) lie behind the middle vertex's;
+        //   * what is left stores separate 16-byte pieces as before, at two lengths only: the one step of S = 2 (one row) and
+        //     step 0 of S = 3 (two rows for sixteen segments).
+        // One wavefront, LDS in program order: this step's reads of its records (the rows of vertices v and S - v, above) precede
+        // the writes below, the rows of later steps (vertices < v and > S - v) are not touched, and the sync that closes a step
+        // stands between its reads of the buffer and the next step's writes, the sixteenth chunk's included.
+        constexpr int kRowDoubles = kQdRec * kDuoPaths;
+        constexpr int kXchgRowsBoth = ((2 * kDuoPaths - 1) * kDuoXchgChunk + kRowDoubles - 1) / kRowDoubles;  // three today
+        static_assert(kDuoPaths * kDuoXchgChunk <= 2 * kRowDoubles, "the step of side 0 alone: eight chunks in two rows");
         static_assert(kD == 4 && kN % 2 == 0, "a row of four lanes writes 64 consecutive bytes: one pair per dimension");
 #if defined(MRS_TG_DUO_STORE_EXPERIMENT) && MRS_TG_DUO_STORE_EXPERIMENT == 1
         // experiment build (WRONG results; profiles/round6_duo_phase_clocks.txt, "stores"): no coefficient store at all
@@ -1152,16 +1215,30 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
           for (int k = 0; k < kN; k += 2) store_coeff_pair(wbase + (k / 2) * 64, c[k], c[k + 1]);
         } else
 #endif
-        if (uni_wave && v < M1 && S_u - 2 * max(v, 1) + 1 >= kXchgRows) {
-          double2* xbuf = reinterpret_cast<double2*>(rec0 + (size_t)max(v - 1, 0) * kQdRec * kDuoPaths) + (pl * 2 + side) * (kD * kN / 2);
+        if (uni_wave && (v >= M1 || S_u - 2 * max(v, 1) + 1 >= kXchgRowsBoth)) {
+          const int chunk = v < M1 ? pl * 2 + side : pl;
+          double* xrows = rec0 + (size_t)max(v - 1, 0) * kRowDoubles + chunk * kDuoXchgChunk;
+          double* xlast = lds + (duo_lds_doubles(Smax) - kDuoXchgChunk);
+          double2* xbuf = reinterpret_cast<double2*>(chunk == 2 * kDuoPaths - 1 ? xlast : xrows);
 #pragma unroll
           for (int k = 0; k < kN; k += 2) xbuf[dim * (kN / 2) + k / 2] = make_double2(c[k], c[k + 1]);
           quad_wave_sync();
           double2* out4 = out - 4 * dim;  // (the segment's first pair + this lane's place in a row of four)
+          // (all five reads ahead of the stores and of the branch: the assembly statements keep their order, and an LDS read
+          // placed between two of them would be waited for there)
+          double2 piece[kN / 2];
 #pragma unroll
-          for (int t = 0; t < kN / 2; ++t) {
-            const double2 piece = xbuf[4 * t + dim];
-            store_coeff_pair(out4 + 4 * t, piece.x, piece.y);
+          for (int t = 0; t < kN / 2; ++t) piece[t] = xbuf[4 * t + dim];
+          if (THROUGH && through) {
+            static_assert(kN / 2 == 5, "one statement per pair");
+            store_coeff_pair_through<0>(out4, piece[0]);
+            store_coeff_pair_through<64>(out4, piece[1]);
+            store_coeff_pair_through<128>(out4, piece[2]);
+            store_coeff_pair_through<192>(out4, piece[3]);
+            store_coeff_pair_through<256>(out4, piece[4]);
+          } else {
+#pragma unroll
+            for (int t = 0; t < kN / 2; ++t) store_coeff_pair(out4 + 4 * t, piece[t].x, piece[t].y);
           }
           quad_wave_sync();  // (the next step's records are other rows; the buffer of the next step overlaps this one)
         } else {
@@ -1196,14 +1273,15 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
   DUO_STAMP(11);
   __builtin_amdgcn_s_waitcnt(0);  // (every store acknowledged)
   DUO_STAMP(12);
+  duo_stamp[15] = __builtin_amdgcn_s_memrealtime();
   if (lane == 0 && blockIdx.x < 2048)
-    for (int k = 0; k < 16; ++k) g_duo_stamps[blockIdx.x * 16 + k] = duo_stamp[k];
+    for (int k = 0; k < 16; ++k) g_duo_stamps[blockIdx.x * kDuoStampSlots + k] = duo_stamp[k];
 #endif
 }
 
 #ifdef MRS_TG_DUO_STAMPS
 extern "C" int mrs_tg_debug_duo_stamps(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_duo_stamps), sizeof(unsigned long long) * 2048 * 16);
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_duo_stamps), sizeof(unsigned long long) * 2048 * kDuoStampSlots);
 }
 #endif
 
@@ -1214,7 +1292,7 @@ __global__ __launch_bounds__(64, MRS_TG_QUAD_WAVES) void solve_duo_kernel(BatchV
                                                        double* __restrict__ cost, const int32_t* __restrict__ status_in,
                                                        double* ws, RowsTail tail, int uniform_loops) {
   solve_duo_body<WP, true>(b, d, mask, vals, seg_times, coeffs, status, cost, status_in, ws, tail, (int)blockIdx.x, tail.pos_wp,
-                           uniform_loops != 0);
+                           (uniform_loops & 1) != 0);
 }
 
 template <bool WP>
@@ -1222,9 +1300,12 @@ __global__ __launch_bounds__(64, MRS_TG_DUO_GROUP_WAVES) void solve_duo_group_ke
                                                                                     size_t ws_batch_doubles, int blocks_per_batch,
                                                                                     int uniform_loops) {
   const int j = __builtin_amdgcn_readfirstlane((int)blockIdx.x / blocks_per_batch);
-  solve_duo_body<WP>(b, d, g.mask[j], g.vals[j], g.seg_times[j], g.coeffs[j], g.status[j], g.cost[j], nullptr,
-                     ws + (size_t)j * ws_batch_doubles, RowsTail(), (int)blockIdx.x - j * blocks_per_batch, g.pos_wp[j],
-                     uniform_loops != 0);
+  solve_duo_body<WP, false, true>(b, d, g.mask[j], g.vals[j], g.seg_times[j], g.coeffs[j], g.status[j], g.cost[j], nullptr,
+                                  ws + (size_t)j * ws_batch_doubles, RowsTail(), (int)blockIdx.x - j * blocks_per_batch, g.pos_wp[j],
+                                  (uniform_loops & 1) != 0, (uniform_loops & 2) != 0);
+#ifdef MRS_TG_DUO_STAMPS
+  if (threadIdx.x == 0 && blockIdx.x < 2048) g_duo_stamps[blockIdx.x * kDuoStampSlots + 16] = (unsigned long long)g.coeffs[0];
+#endif
 }
 
 template <bool WP, bool ENDS = false>
@@ -1251,6 +1332,7 @@ __global__ __launch_bounds__(64, MRS_TG_QUAD_GROUP_WAVES) void solve_quad_group_
 // launcher
 
 static constexpr size_t kQuadLdsBudget = 80 * 1024;  // at least two wavefronts per CU
+static_assert(duo_lds_doubles(24) * sizeof(double) <= kQuadLdsBudget, "the two-sided kernel at the longest routed length");
 
 // The two-sided kernel takes a launch whose quad wavefronts (16 paths each) would leave SIMDs idle or barely covered: fewer than
 // 1.25 per SIMD.  MRS_TG_DUO=0: never, =1: whenever the pattern allows (tuning / test knob).
@@ -1261,6 +1343,10 @@ static bool duo_pays(long long paths_in_launch) {
   static const int cus = device_compute_units();
   return (paths_in_launch + kQdPaths - 1) / kQdPaths < (long long)cus * 4 * 5 / 4;
 }
+
+// the two-sided kernels' `uniform_loops` argument: bit 0 MRS_TG_DUO_UNIFORM, bit 1 MRS_TG_DUO_STORE_THROUGH (the grouped kernel
+// alone looks at it); both read at every call
+static int duo_loop_bits() { return (knob::duo_uniform() ? 1 : 0) | (knob::duo_store_through() ? 2 : 0); }
 
 bool quad_kernel_applies(const BatchView& b, long long paths_in_launch, bool with_sampling) {
   if (b.n_paths == 0 || with_sampling) return false;
@@ -1286,7 +1372,7 @@ hipError_t launch_solve_quad(const BatchView& b, int d, const uint8_t* mask, con
     }
     const unsigned grid_duo = (unsigned)((b.n_paths + kDuoPaths - 1) / kDuoPaths);
     MRS_TG_LAUNCH_TIMED(duo, dim3(grid_duo), dim3(64), lds_duo, stream, b, d, mask, vals, seg_times, coeffs, status, cost, status_in,
-                        ws, tail, (int)knob::duo_uniform());
+                        ws, tail, duo_loop_bits());
     return hipGetLastError();
   }
   const size_t lds_bytes = quad_lds_doubles(b.max_segments, ends) * sizeof(double);
@@ -1319,7 +1405,7 @@ hipError_t launch_solve_quad_group(const BatchView& b, int d, const RowsGroup& g
     const int per_batch_duo = (b.n_paths + kDuoPaths - 1) / kDuoPaths;
     const dim3 grid_duo((unsigned)(per_batch_duo * g.n));
     const size_t wsd_duo = linear_workspace_doubles(b);
-    MRS_TG_LAUNCH_TIMED(duo, grid_duo, dim3(64), lds_duo, stream, b, d, g, ws, wsd_duo, per_batch_duo, (int)knob::duo_uniform());
+    MRS_TG_LAUNCH_TIMED(duo, grid_duo, dim3(64), lds_duo, stream, b, d, g, ws, wsd_duo, per_batch_duo, duo_loop_bits());
     return hipGetLastError();
   }
   const auto quad = ends ? (wp ? MRS_TG_KERNEL(solve_quad_group_kernel<true, true>) : MRS_TG_KERNEL(solve_quad_group_kernel<false, true>))
