@@ -188,8 +188,10 @@ enum {
   MRS_TG_CAP_MAXIMA_GRADIENT = 16, /* mrs_tg_plan_segment_maxima_vjp is exported: the backward pass of the segment maxima */
   MRS_TG_CAP_SAMPLE_GRADIENT = 32, /* mrs_tg_plan_sample_states_vjp and mrs_tg_plan_sample are exported: the backward pass of
                                       the sampler */
-  MRS_TG_CAP_EVALUATE = 64         /* mrs_tg_plan_evaluate and mrs_tg_plan_evaluate_vjp are exported: the state at caller-given
+  MRS_TG_CAP_EVALUATE = 64,        /* mrs_tg_plan_evaluate and mrs_tg_plan_evaluate_vjp are exported: the state at caller-given
                                       times and its backward pass */
+  MRS_TG_CAP_DEVIATION = 128       /* mrs_tg_plan_path_deviation and mrs_tg_plan_path_deviation_vjp are exported: the deviation
+                                      of the samples from the waypoint polyline and its backward pass */
 };
 
 typedef struct mrs_tg_options {
@@ -518,12 +520,63 @@ int mrs_tg_plan_evaluate_vjp(mrs_tg_plan* plan, const double* coeffs_dev, const 
                              const int32_t* status_dev, double* grad_coeffs_out_dev, double* grad_seg_times_out_dev,
                              double* grad_query_times_out_dev);
 
+/* How far the sampled trajectory strays from the waypoint polyline (MRS_TG_CAP_DEVIATION; path_deviation_kernel, DESIGN.md
+ * section 11b): validateTrajectorySpatial (mrs_trajectory_generation.cpp:1401-1455), the figure
+ * check_trajectory_deviation/max_deviation acts on, as a plan step on samples where they are.
+ * samples_dev [n_paths][sample_capacity][4] and n_samples_dev [n_paths] are what a solve or mrs_tg_plan_sample left
+ * (n = min(n_samples, sample_capacity) rows are read, x, y, z of each); waypoints_dev [sum V][4] are the plan's S + 1
+ * vertices per path (x, y, z read), both in the caller's path order.  With D = distFromSegment (:1533-1554) and the
+ * cursor c_0 = 0, for the samples i = 0 .. n-2 of a path:
+ *   d_i = D(s_i, w_c, w_{c+1}),  e_i = D(w_{c+1}, s_i, s_{i+1}),  c_{i+1} = c_i + 1 if e_i < 0.05 and c_i < S - 1, else c_i.
+ * Sample i is COUNTED if c_i > 0, or first_segment != 0 (max_deviation_first_segment), or S + 1 <= 2.
+ * Outputs, each may be NULL, at least one given:
+ *   deviation_out_dev [n_paths][sample_capacity]  d_i of every scanned sample, counted or not; 0 in the rows >= n - 1
+ *   cursor_out_dev [n_paths][sample_capacity]     c_i; -1 in the rows >= n - 1
+ *   max_deviation_out_dev [n_paths]               the maximum over the counted samples (0 without any): the reference's
+ *   argmax_out_dev [n_paths]                      the first counted sample whose d exceeded, strictly, every one in front
+ *                                                 of it -- the reference's running maximum, which starts at 0: -1 when no
+ *                                                 counted sample has d > 0
+ *   segment_max_out_dev [sum S]                   the maximum over the counted samples whose cursor is that segment (0
+ *                                                 without any): the reference's segment_safe is segment_max <= max_deviation
+ * With status_dev, a path with status <= 0 gets zeros and cursor -1; a path with n <= 1 scans nothing.  A deviation that is
+ * not a number never becomes a maximum (the reference's `>`).  The arithmetic is the host's, operation by operation with
+ * no fused multiply-add: the bits of mrs_tg_optimize_paths' own scan.  Every output element that belongs to the plan is
+ * written exactly once.  Device pointers (16-byte aligned), asynchronous on the context's stream. */
+int mrs_tg_plan_path_deviation(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev,
+                               int32_t sample_capacity, const double* waypoints_dev, int32_t first_segment,
+                               const int32_t* status_dev, double* deviation_out_dev, int32_t* cursor_out_dev,
+                               double* max_deviation_out_dev, int32_t* argmax_out_dev, double* segment_max_out_dev);
+/* Backward pass of mrs_tg_plan_path_deviation (path_deviation_vjp_kernel): given
+ * grad_deviation_dev [n_paths][sample_capacity] = dL/dd_i (the rows >= n - 1 are never read), writes dL/dsamples
+ * (grad_samples_out_dev [n_paths][sample_capacity][4]) and dL/dwaypoints (grad_waypoints_out_dev [sum V][4]); column 3 of
+ * both is zero; at least one must be given.  The cursors are recomputed as the forward computes them.  With p = s_i,
+ * a = w_c, b = w_{c+1}, d = d_i, and coord, len, the perpendicular component e as distFromSegment forms them:
+ *   coord < 0     dd/dp = (p - a)/d,  dd/da = -dd/dp,        dd/db = 0
+ *   coord > len   dd/dp = (p - b)/d,  dd/da = 0,             dd/db = -dd/dp
+ *   otherwise     dd/dp = u = e/d,    dd/da = -(1 - tau) u,  dd/db = -tau u,   tau = coord/len
+ * What is not smooth, and what the call does there:
+ *   the cursor -- held fixed: the advance test e_i < 0.05 is piecewise constant, nothing flows through s_{i+1};
+ *   the branch -- the forward's; coord == 0 and coord == len take the interior row (its one-sided gradient);
+ *   coincident waypoints (len == 0) -- the interior row with tau = 0: everything goes to a;
+ *   a sample on its segment (d == 0) -- contributes exactly 0;
+ *   a zero upstream entry contributes exactly 0;
+ *   with status_dev, a path with status <= 0 gets zero rows in both outputs.
+ * Every sum runs in a fixed order: a waypoint's accumulator starts at 0.0 and takes, in increasing sample index, the
+ * b-parts of the samples whose cursor is the segment in front of it, then the a-parts of the samples whose cursor is its
+ * own segment.  Deterministic, no atomics, no workspace, the same bits for a path wherever it sits in a batch; every output
+ * element that belongs to the plan is written exactly once.  Device pointers, asynchronous on the context's stream. */
+int mrs_tg_plan_path_deviation_vjp(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev,
+                                   int32_t sample_capacity, const double* waypoints_dev, const int32_t* status_dev,
+                                   const double* grad_deviation_dev, double* grad_samples_out_dev,
+                                   double* grad_waypoints_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
  * 3 backward pass of the solve (mrs_tg_plan_solve_vjp), 4 backward pass of the maxima (mrs_tg_plan_segment_maxima_vjp),
  * 5 backward pass of the sampler (mrs_tg_plan_sample_states_vjp), 6 evaluation at given times (mrs_tg_plan_evaluate),
- * 7 its backward pass (mrs_tg_plan_evaluate_vjp): eight ids, 0 .. 7.
+ * 7 its backward pass (mrs_tg_plan_evaluate_vjp), 8 deviation from the waypoint path (mrs_tg_plan_path_deviation),
+ * 9 its backward pass (mrs_tg_plan_path_deviation_vjp): ten ids, 0 .. 9.
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

@@ -45,6 +45,7 @@ STATE_ORDERS = 5   # derivative orders 0..4 per sample of Plan.sample_states (MR
 KERNEL_ASSEMBLE, KERNEL_SOLVE_LINEAR, KERNEL_NONLINEAR, KERNEL_VJP, KERNEL_MAXIMA_VJP = 0, 1, 2, 3, 4
 KERNEL_SAMPLE_VJP = 5
 KERNEL_EVALUATE, KERNEL_EVALUATE_VJP = 6, 7
+KERNEL_DEVIATION, KERNEL_DEVIATION_VJP = 8, 9
 
 
 class MrsTgError(RuntimeError):
@@ -104,6 +105,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_prepare_initial_condition", "mrs_tg_splice_prediction", "mrs_tg_plan_solve_vjp",
     "mrs_tg_plan_segment_maxima_vjp", "mrs_tg_plan_sample", "mrs_tg_plan_sample_states_vjp",
     "mrs_tg_plan_evaluate", "mrs_tg_plan_evaluate_vjp",
+    "mrs_tg_plan_path_deviation", "mrs_tg_plan_path_deviation_vjp",
 ]
 
 _lib = None
@@ -205,6 +207,10 @@ def load_library():
     L.mrs_tg_plan_evaluate.argtypes = [vp, dp, dp, dp, C.c_int32, C.c_int32, dp, ip, dp]
     L.mrs_tg_plan_evaluate_vjp.restype = C.c_int
     L.mrs_tg_plan_evaluate_vjp.argtypes = [vp, dp, dp, dp, C.c_int32, C.c_int32, dp, ip, dp, dp, dp]
+    L.mrs_tg_plan_path_deviation.restype = C.c_int
+    L.mrs_tg_plan_path_deviation.argtypes = [vp, dp, ip, C.c_int32, dp, C.c_int32, ip, dp, ip, dp, ip, dp]
+    L.mrs_tg_plan_path_deviation_vjp.restype = C.c_int
+    L.mrs_tg_plan_path_deviation_vjp.argtypes = [vp, dp, ip, C.c_int32, dp, ip, dp, dp, dp]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -256,6 +262,7 @@ CAP_GRADIENT = 8       # MRS_TG_CAP_GRADIENT: Plan.solve_vjp (the backward pass 
 CAP_MAXIMA_GRADIENT = 16   # MRS_TG_CAP_MAXIMA_GRADIENT: Plan.segment_maxima_vjp (the backward pass of the segment maxima)
 CAP_SAMPLE_GRADIENT = 32   # MRS_TG_CAP_SAMPLE_GRADIENT: Plan.sample_states_vjp (the backward pass of the sampler), Plan.sample
 CAP_EVALUATE = 64          # MRS_TG_CAP_EVALUATE: Plan.evaluate (the state at caller-given times), Plan.evaluate_vjp
+CAP_DEVIATION = 128        # MRS_TG_CAP_DEVIATION: Plan.path_deviation (samples against the waypoint polyline), Plan.path_deviation_vjp
 
 
 def capabilities():
@@ -868,6 +875,27 @@ class Plan:
                                                          int(query_times.shape[1]), n_orders, _t_ptr(grad_states), _t_ptr(status),
                                                          _t_ptr(grad_coeffs), _t_ptr(grad_seg_times), _t_ptr(grad_query_times)),
                         "mrs_tg_plan_evaluate_vjp")
+
+    def path_deviation(self, samples, n_samples, waypoints, first_segment=True, status=None, deviation=None, cursor=None,
+                       max_deviation=None, argmax=None, segment_max=None):
+        """mrs_tg_plan_path_deviation: validateTrajectorySpatial's scan of samples [n_paths][capacity][4] (n_samples [n_paths]
+        int32) against waypoints [sum V][4] into deviation [n_paths][capacity], cursor [n_paths][capacity] (int32, -1 behind the
+        scanned rows), max_deviation [n_paths], argmax [n_paths] (int32) and segment_max [sum S] (device tensors, written; None =
+        not wanted, at least one given); asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_path_deviation(self._h, _t_ptr(samples), _t_ptr(n_samples), int(samples.shape[1]),
+                                                           _t_ptr(waypoints), 1 if first_segment else 0, _t_ptr(status),
+                                                           _t_ptr(deviation), _t_ptr(cursor), _t_ptr(max_deviation),
+                                                           _t_ptr(argmax), _t_ptr(segment_max)), "mrs_tg_plan_path_deviation")
+
+    def path_deviation_vjp(self, samples, n_samples, waypoints, grad_deviation, status=None, grad_samples=None,
+                           grad_waypoints=None):
+        """mrs_tg_plan_path_deviation_vjp: dL/dsamples [n_paths][capacity][4] and dL/dwaypoints [sum V][4] (device tensors,
+        written; None = not wanted, at least one given) from dL/ddeviation (grad_deviation [n_paths][capacity]), the cursors
+        held fixed; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_path_deviation_vjp(self._h, _t_ptr(samples), _t_ptr(n_samples),
+                                                               int(samples.shape[1]), _t_ptr(waypoints), _t_ptr(status),
+                                                               _t_ptr(grad_deviation), _t_ptr(grad_samples),
+                                                               _t_ptr(grad_waypoints)), "mrs_tg_plan_path_deviation_vjp")
 
 
 class RoundRobin:

@@ -1,6 +1,7 @@
-"""The fixed-times solve, the segment maxima, the sampler and the evaluation at given times as torch.autograd.Functions:
-gradients of a loss on the coefficients, the cost, the derivative maxima, the samples and the states at chosen times reach the
-fixed values (waypoints, initial state), the segment times, the limits and the query times.
+"""The fixed-times solve, the segment maxima, the sampler, the evaluation at given times and the deviation from the waypoint
+path as torch.autograd.Functions: gradients of a loss on the coefficients, the cost, the derivative maxima, the samples, the
+states at chosen times and the deviations reach the fixed values (waypoints, initial state), the segment times, the limits and
+the query times.
 
 Forward: Plan.solve with time_alloc_method = NONE, no sampling, no waypoints, no limits (the existing kernels, unchanged).
 Backward: Plan.solve_vjp (mrs_tg_plan_solve_vjp, vjp_kernel), the exact chain rule of the linear QP at the returned solution
@@ -44,6 +45,20 @@ UAVs at common absolute time stamps -- two plans, trajectories of different dura
     >>> both = (seg_a >= 0) & (seg_b >= 0)
     >>> loss = (torch.relu(2.0 - (pa[..., 0, :3] - pb[..., 0, :3]).norm(dim=-1)) * both).sum()
     >>> loss.backward()                                   # fv_a.grad, times_a.grad, fv_b.grad, times_b.grad
+
+path_deviation (Plan.path_deviation forward, Plan.path_deviation_vjp backward: mrs_tg_plan_path_deviation /
+mrs_tg_plan_path_deviation_vjp) is the figure the reference's own policy acts on: how far every sample
+strays from the waypoint polyline, by validateTrajectorySpatial's scan with its waypoint cursor.  The cursor of every sample is
+held fixed in the backward pass.  From waypoints to "stay within 5 cm of the path" -- the term the reference enforces by
+subdividing segments -- through the solve and the sampler:
+
+    >>> fv = fixed_values.clone().requires_grad_(); times = seg_times.clone().requires_grad_()
+    >>> coeffs, _, status = solve(plan, fixed_mask, fv, times)
+    >>> samples, n = sample(plan, coeffs, times, 0.2, 512, status)
+    >>> deviation, cursor = path_deviation(plan, samples, n, fv[:, 0, :], first_segment=True, status=status)
+    >>> corridor = torch.relu(deviation - 0.05).sum()             # rows behind a path's scan are zero: no mask needed
+    >>> worst = deviation.amax(dim=1)                             # the reference's max_deviation per path (first_segment=True)
+    >>> corridor.backward()                                       # fv.grad (through the samples AND the polyline), times.grad
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -232,6 +247,55 @@ def evaluate(plan, coeffs, seg_times, query_times, n_orders=5, status=None):
     if int(n_orders) not in (1, api.STATE_ORDERS):
         raise ValueError("n_orders must be 1 or %d" % api.STATE_ORDERS)
     return _Evaluate.apply(plan, coeffs, seg_times, query_times, int(n_orders), status)
+
+
+class _PathDeviation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, samples, n_samples, waypoints, first_segment, status):
+        s = samples.detach().to(torch.float64).contiguous()
+        w = waypoints.detach().to(torch.float64).contiguous()
+        n = n_samples.detach().to(torch.int32).contiguous()
+        if s.dim() != 3 or s.shape[0] != plan.n_paths or s.shape[2] != api.N_DIM:
+            raise ValueError("samples must be [n_paths][capacity][4]")
+        if w.dim() != 2 or w.shape[0] != plan.n_segments + plan.n_paths or w.shape[1] != api.N_DIM:
+            raise ValueError("waypoints must be [sum V][4]")
+        st = None if status is None else status.detach().to(torch.int32).contiguous()
+        deviation = torch.empty(s.shape[:2], dtype=torch.float64, device=s.device)
+        cursor = torch.empty(s.shape[:2], dtype=torch.int32, device=s.device)
+        plan.ctx.use_torch_stream()
+        plan.path_deviation(s, n, w, first_segment=bool(first_segment), status=st, deviation=deviation, cursor=cursor)
+        ctx.plan, ctx.status = plan, st
+        ctx.save_for_backward(s, n, w)
+        ctx.mark_non_differentiable(cursor)
+        ctx.set_materialize_grads(False)
+        return deviation, cursor
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_deviation, _grad_cursor):
+        s, n, w = ctx.saved_tensors
+        want_s, want_w = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        if grad_deviation is None or not (want_s or want_w):
+            return None, None, None, None, None, None
+        gs = torch.empty_like(s) if want_s else None
+        gw = torch.empty_like(w) if want_w else None
+        plan = ctx.plan
+        plan.ctx.use_torch_stream()   # (the autograd engine runs this on its own thread, on the forward's stream)
+        plan.path_deviation_vjp(s, n, w, grad_deviation.to(torch.float64).contiguous(), status=ctx.status, grad_samples=gs,
+                                grad_waypoints=gw)
+        return None, gs, None, gw, None, None
+
+
+def path_deviation(plan, samples, n_samples, waypoints, first_segment=True, status=None):
+    """(deviation [n_paths][capacity], cursor [n_paths][capacity] int32) of Plan.path_deviation: the distance of every sample
+    i = 0 .. n-2 of a path from the segment w_c -> w_{c+1} of its waypoint polyline that validateTrajectorySpatial's cursor c
+    points at -- differentiable in samples [n_paths][capacity][4] and waypoints [sum V][4] (float64 device tensors; x, y, z
+    are read, column 3 gets a zero gradient); n_samples [n_paths] int32 as the sampler returned it.  Rows from n - 1 on hold
+    deviation 0 and cursor -1.  The deviation does not depend on first_segment; with first_segment=False the reference leaves
+    the samples whose cursor is 0 out of its maximum (paths of more than one segment): mask with cursor > 0.  The gradient
+    holds every cursor and the branch of every distance fixed; a sample on its segment (deviation 0) and a path with
+    status <= 0 (status [n_paths], optional) get and give zero."""
+    return _PathDeviation.apply(plan, samples, n_samples, waypoints, first_segment, status)
 
 
 def _root(x, p):

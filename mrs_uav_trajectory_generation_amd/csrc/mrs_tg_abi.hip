@@ -51,9 +51,9 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 8;  // kernel_id 0 .. 7 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 10;  // kernel_id 0 .. 9 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
-  long long ev_count[kTimedKernels] = {0, 0, 0, 0, 0, 0, 0, 0};   // timed launches since profiling was switched on
+  long long ev_count[kTimedKernels] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
   double wall_clock_hz = 1.0e8;  // rate of s_memrealtime (hipDeviceAttributeWallClockRate)
   // plan of the most recent mrs_tg_solve_batch: a caller that sends the same batch shape again (the nodelet's
@@ -216,7 +216,7 @@ int mrs_tg_abi_version(void) { return MRS_TG_ABI_VERSION; }
 
 int mrs_tg_capabilities(void) {
   return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE |
-         MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE;
+         MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE | MRS_TG_CAP_DEVIATION;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1084,6 +1084,46 @@ int mrs_tg_plan_evaluate_vjp(mrs_tg_plan* plan, const double* coeffs, const doub
   ProfileScope ps(ctx, 7);
   hipError_t e = mrs_tg::launch_evaluate_vjp(plan->view, coeffs, seg_times, query_times, n_queries, n_orders, grad_states, status,
                                              grad_coeffs, grad_times, grad_query_times, ctx->stream);
+  if (e == hipErrorInvalidValue)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "a path of %d segments needs more than 160 KB of LDS", plan->view.max_segments);
+  HIP_TRY(ctx, e);
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_path_deviation(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                               const double* waypoints, int32_t first_segment, const int32_t* status, double* deviation,
+                               int32_t* cursor, double* max_deviation, int32_t* argmax, double* segment_max) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
+  if (!n_samples || !waypoints || (sample_capacity > 0 && !samples))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev and waypoints_dev are required");
+  if (!deviation && !cursor && !max_deviation && !argmax && !segment_max)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "every output of mrs_tg_plan_path_deviation is NULL");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 8);
+  hipError_t e = mrs_tg::launch_path_deviation(plan->view, samples, n_samples, waypoints, sample_capacity, first_segment, status,
+                                               deviation, cursor, max_deviation, argmax, segment_max, ctx->stream);
+  if (e == hipErrorInvalidValue)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "a path of %d segments needs more than 160 KB of LDS", plan->view.max_segments);
+  HIP_TRY(ctx, e);
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_path_deviation_vjp(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                   const double* waypoints, const int32_t* status, const double* grad_deviation,
+                                   double* grad_samples, double* grad_waypoints) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
+  if (!n_samples || !waypoints || (sample_capacity > 0 && (!samples || !grad_deviation)))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev, waypoints_dev and grad_deviation_dev are required");
+  if (!grad_samples && !grad_waypoints)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_samples_out and grad_waypoints_out are both NULL");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 9);
+  hipError_t e = mrs_tg::launch_path_deviation_vjp(plan->view, samples, n_samples, waypoints, sample_capacity, status,
+                                                   grad_deviation, grad_samples, grad_waypoints, ctx->stream);
   if (e == hipErrorInvalidValue)
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "a path of %d segments needs more than 160 KB of LDS", plan->view.max_segments);
   HIP_TRY(ctx, e);

@@ -234,6 +234,16 @@ hipError_t launch_evaluate(const BatchView& b, const double* coeffs, const doubl
 hipError_t launch_evaluate_vjp(const BatchView& b, const double* coeffs, const double* seg_times, const double* query_times,
                                int n_queries, int n_orders, const double* grad_states, const int32_t* status,
                                double* grad_coeffs, double* grad_times, double* grad_query, hipStream_t stream);
+// mrs_tg_plan_path_deviation / mrs_tg_plan_path_deviation_vjp (mrs_tg_deviation.hip): the deviation of the samples
+// [n_paths][capacity][4] from the waypoint polyline [sum V][4] by validateTrajectorySpatial's scan (every output may be NULL)
+// and its backward pass -- dL/dsamples and dL/dwaypoints (each may be NULL) from dL/ddeviation; status NULL or per path
+// (<= 0: zero rows); reads only, no workspace; each timed as the kernel family of the pending ProfileScope
+hipError_t launch_path_deviation(const BatchView& b, const double* samples, const int32_t* n_samples, const double* waypoints,
+                                 int capacity, int first_segment, const int32_t* status, double* deviation, int32_t* cursor,
+                                 double* max_deviation, int32_t* argmax, double* segment_max, hipStream_t stream);
+hipError_t launch_path_deviation_vjp(const BatchView& b, const double* samples, const int32_t* n_samples,
+                                     const double* waypoints, int capacity, const int32_t* status, const double* grad_deviation,
+                                     double* grad_samples, double* grad_waypoints, hipStream_t stream);
 // phase-split tile kernel (mrs_tg_tile.hip): small and medium batches whose per-path state fits in LDS
 bool tile_kernel_applies(const BatchView& b, bool fused);
 hipError_t launch_solve_tile(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,
