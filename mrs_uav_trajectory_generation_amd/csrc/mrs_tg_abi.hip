@@ -114,6 +114,22 @@ long long budget_ticks(const mrs_tg_ctx* ctx, double seconds_left) {
     if (e__ != hipSuccess) return fail((ctx), MRS_TG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e__)); \
   } while (0)
 
+// the two shapes of a state row: the refusal of any other n_orders, or MRS_TG_OK
+int check_n_orders(mrs_tg_ctx* ctx, int32_t n_orders) {
+  if (n_orders == 1 || n_orders == MRS_TG_STATE_ORDERS) return MRS_TG_OK;
+  return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_orders %d is neither 1 (positions and heading) nor %d (all orders)", n_orders,
+              MRS_TG_STATE_ORDERS);
+}
+
+// What a launcher that stages a whole path in LDS returned, for the caller: hipErrorInvalidValue is its refusal of a path
+// that does not fit (mrs_tg::prepare_dynamic_lds)
+int staged_launch_result(mrs_tg_ctx* ctx, const mrs_tg_plan* plan, hipError_t e) {
+  if (e == hipErrorInvalidValue)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "a path of %d segments needs more than 160 KB of LDS", plan->view.max_segments);
+  HIP_TRY(ctx, e);
+  return MRS_TG_OK;
+}
+
 // Arms the per-dispatch timer for the next timed launch of this thread (the main kernel of the family `kernel_id`):
 // the events ride on the kernel launch itself, so their difference is that dispatch's own duration.
 struct ProfileScope {
@@ -1030,9 +1046,7 @@ int mrs_tg_plan_sample_states_vjp(mrs_tg_plan* plan, const double* coeffs, const
   if (!coeffs || !seg_times) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "coeffs and seg_times are required");
   if (!(sampling_dt > 0.0) || sample_capacity < 0)
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sampling_dt must be positive and sample_capacity non-negative");
-  if (n_orders != 1 && n_orders != MRS_TG_STATE_ORDERS)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_orders %d is neither 1 (positions and heading) nor %d (all orders)", n_orders,
-                MRS_TG_STATE_ORDERS);
+  if (int rc = check_n_orders(ctx, n_orders)) return rc;
   if (!grad_coeffs && !grad_times && !sample_segment && !sample_time && !n_samples)
     return fail(ctx, MRS_TG_ERR_INVALID_ARG,
                 "grad_coeffs_out, grad_seg_times_out, sample_segment_out, sample_time_out and n_samples_out are all NULL");
@@ -1050,20 +1064,15 @@ int mrs_tg_plan_evaluate(mrs_tg_plan* plan, const double* coeffs, const double* 
   if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
   mrs_tg_ctx* ctx = plan->ctx;
   if (n_queries < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_queries %d is negative", n_queries);
-  if (n_orders != 1 && n_orders != MRS_TG_STATE_ORDERS)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_orders %d is neither 1 (positions and heading) nor %d (all orders)", n_orders,
-                MRS_TG_STATE_ORDERS);
+  if (int rc = check_n_orders(ctx, n_orders)) return rc;
   if (!coeffs || !seg_times) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "coeffs and seg_times are required");
   if (n_queries > 0 && (!query_times || !states))
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "query_times_dev and states_out_dev are required");
   HIP_TRY(ctx, use_device(ctx->device));
   ProfileScope ps(ctx, 6);
-  hipError_t e = mrs_tg::launch_evaluate(plan->view, coeffs, seg_times, query_times, n_queries, n_orders, states, query_segment,
-                                         query_local_time, ctx->stream);
-  if (e == hipErrorInvalidValue)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "a path of %d segments needs more than 160 KB of LDS", plan->view.max_segments);
-  HIP_TRY(ctx, e);
-  return MRS_TG_OK;
+  return staged_launch_result(ctx, plan,
+                              mrs_tg::launch_evaluate(plan->view, coeffs, seg_times, query_times, n_queries, n_orders, states,
+                                                      query_segment, query_local_time, ctx->stream));
 }
 
 int mrs_tg_plan_evaluate_vjp(mrs_tg_plan* plan, const double* coeffs, const double* seg_times, const double* query_times,
@@ -1072,9 +1081,7 @@ int mrs_tg_plan_evaluate_vjp(mrs_tg_plan* plan, const double* coeffs, const doub
   if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
   mrs_tg_ctx* ctx = plan->ctx;
   if (n_queries < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_queries %d is negative", n_queries);
-  if (n_orders != 1 && n_orders != MRS_TG_STATE_ORDERS)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_orders %d is neither 1 (positions and heading) nor %d (all orders)", n_orders,
-                MRS_TG_STATE_ORDERS);
+  if (int rc = check_n_orders(ctx, n_orders)) return rc;
   if (!coeffs || !seg_times) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "coeffs and seg_times are required");
   if (n_queries > 0 && (!query_times || !grad_states))
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "query_times_dev and grad_states_dev are required");
@@ -1082,12 +1089,9 @@ int mrs_tg_plan_evaluate_vjp(mrs_tg_plan* plan, const double* coeffs, const doub
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_coeffs_out, grad_seg_times_out and grad_query_times_out are all NULL");
   HIP_TRY(ctx, use_device(ctx->device));
   ProfileScope ps(ctx, 7);
-  hipError_t e = mrs_tg::launch_evaluate_vjp(plan->view, coeffs, seg_times, query_times, n_queries, n_orders, grad_states, status,
-                                             grad_coeffs, grad_times, grad_query_times, ctx->stream);
-  if (e == hipErrorInvalidValue)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "a path of %d segments needs more than 160 KB of LDS", plan->view.max_segments);
-  HIP_TRY(ctx, e);
-  return MRS_TG_OK;
+  return staged_launch_result(ctx, plan,
+                              mrs_tg::launch_evaluate_vjp(plan->view, coeffs, seg_times, query_times, n_queries, n_orders, grad_states,
+                                                          status, grad_coeffs, grad_times, grad_query_times, ctx->stream));
 }
 
 int mrs_tg_plan_path_deviation(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
@@ -1102,12 +1106,10 @@ int mrs_tg_plan_path_deviation(mrs_tg_plan* plan, const double* samples, const i
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "every output of mrs_tg_plan_path_deviation is NULL");
   HIP_TRY(ctx, use_device(ctx->device));
   ProfileScope ps(ctx, 8);
-  hipError_t e = mrs_tg::launch_path_deviation(plan->view, samples, n_samples, waypoints, sample_capacity, first_segment, status,
-                                               deviation, cursor, max_deviation, argmax, segment_max, ctx->stream);
-  if (e == hipErrorInvalidValue)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "a path of %d segments needs more than 160 KB of LDS", plan->view.max_segments);
-  HIP_TRY(ctx, e);
-  return MRS_TG_OK;
+  return staged_launch_result(ctx, plan,
+                              mrs_tg::launch_path_deviation(plan->view, samples, n_samples, waypoints, sample_capacity, first_segment,
+                                                            status, deviation, cursor, max_deviation, argmax, segment_max,
+                                                            ctx->stream));
 }
 
 int mrs_tg_plan_path_deviation_vjp(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
@@ -1122,12 +1124,9 @@ int mrs_tg_plan_path_deviation_vjp(mrs_tg_plan* plan, const double* samples, con
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_samples_out and grad_waypoints_out are both NULL");
   HIP_TRY(ctx, use_device(ctx->device));
   ProfileScope ps(ctx, 9);
-  hipError_t e = mrs_tg::launch_path_deviation_vjp(plan->view, samples, n_samples, waypoints, sample_capacity, status,
-                                                   grad_deviation, grad_samples, grad_waypoints, ctx->stream);
-  if (e == hipErrorInvalidValue)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "a path of %d segments needs more than 160 KB of LDS", plan->view.max_segments);
-  HIP_TRY(ctx, e);
-  return MRS_TG_OK;
+  return staged_launch_result(ctx, plan,
+                              mrs_tg::launch_path_deviation_vjp(plan->view, samples, n_samples, waypoints, sample_capacity, status,
+                                                                grad_deviation, grad_samples, grad_waypoints, ctx->stream));
 }
 
 // ---- one-call host interface ------------------------------------------------------------------

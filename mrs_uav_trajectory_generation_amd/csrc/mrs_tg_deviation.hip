@@ -26,12 +26,6 @@ typedef double dev_pair __attribute__((ext_vector_type(2)));
 
 constexpr int kDevTileStride = 7;  // doubles between the parked rows [6] of two samples (odd: no bank is hit twice by a row)
 
-__device__ __forceinline__ void lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
@@ -108,7 +102,7 @@ __global__ __launch_bounds__(64) void path_deviation_kernel(BatchView b, const d
   const double* __restrict__ rows = samples + row0 * 4;
   double cur[3];
   load_sample(rows, lane, n, cur);
-  lds_sync();
+  wave_lds_barrier();
   int c = 0, run_arg = -1;
   double run_max = 0.0;
   for (int k0 = 0; k0 < n - 1; k0 += 64) {
@@ -151,7 +145,7 @@ __global__ __launch_bounds__(64) void path_deviation_kernel(BatchView b, const d
     if (argmax) argmax[pr.p] = run_arg;
   }
   if (segment_max) {
-    lds_sync();
+    wave_lds_barrier();
     for (int i = lane; i < S; i += 64) segment_max[pr.s0 + i] = s_m[i];
   }
 }
@@ -182,7 +176,7 @@ __global__ __launch_bounds__(64) void path_deviation_vjp_kernel(BatchView b, con
   const double* __restrict__ rows = samples + row0 * 4;
   double cur[3];
   load_sample(rows, lane, n, cur);
-  lds_sync();
+  wave_lds_barrier();
   const int slot = min(lane, 5);  // lanes 0..2: the waypoint at the cursor, 3..5: the one behind it (the others follow lane 5 and store nothing)
   const bool owns = lane < 6;
   int c = 0, acc_c = 0;  // acc_c: the cursor the accumulators belong to
@@ -209,7 +203,7 @@ __global__ __launch_bounds__(64) void path_deviation_vjp_kernel(BatchView b, con
 #pragma unroll
       for (int k = 0; k < 3; ++k) row[k] = ga[k], row[3 + k] = gb[k];
       s_cur[lane] = mine;
-      lds_sync();
+      wave_lds_barrier();
       const int count = min(64, n - 1 - k0);
       for (int r = 0; r < count; ++r) {
         const int cr = __builtin_amdgcn_readfirstlane(s_cur[r]);
@@ -221,7 +215,7 @@ __global__ __launch_bounds__(64) void path_deviation_vjp_kernel(BatchView b, con
         }
         acc = devq::accumulate(acc, s_tile[r * kDevTileStride + slot]);
       }
-      lds_sync();  // (the next chunk overwrites the tile)
+      wave_lds_barrier();  // (the next chunk overwrites the tile)
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) cur[k] = nxt[k];
@@ -234,7 +228,7 @@ __global__ __launch_bounds__(64) void path_deviation_vjp_kernel(BatchView b, con
   }
   if (grad_waypoints) {
     if (owns) s_gw[3 * acc_c + lane] = acc;
-    lds_sync();
+    wave_lds_barrier();
     for (int e = lane; e < 4 * (S + 1); e += 64)
       grad_waypoints[(size_t)pr.v0 * 4 + e] = e % 4 < 3 ? s_gw[3 * (e / 4) + e % 4] : 0.0;
   }
@@ -244,13 +238,9 @@ hipError_t launch_path_deviation(const BatchView& b, const double* samples, cons
                                  int capacity, int first_segment, const int32_t* status, double* deviation, int32_t* cursor,
                                  double* max_deviation, int32_t* argmax, double* segment_max, hipStream_t stream) {
   const size_t lds = sizeof(double) * (3 * ((size_t)b.max_segments + 1) + (size_t)b.max_segments);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (b.n_paths == 0) return hipSuccess;
+  if (b.n_paths == 0) return lds > kLdsPerWorkgroup ? hipErrorInvalidValue : hipSuccess;
   const auto fwd = MRS_TG_KERNEL(path_deviation_kernel);
-  if (lds > 64 * 1024) {
-    hipError_t e = set_max_dynamic_lds(fwd, lds);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = prepare_dynamic_lds(fwd, lds); e != hipSuccess) return e;
   MRS_TG_LAUNCH_TIMED(fwd, dim3((unsigned)b.n_paths), dim3(64), lds, stream, b, samples, n_samples, waypoints, capacity,
                       first_segment, status, deviation, cursor, max_deviation, argmax, segment_max);
   return hipGetLastError();
@@ -260,13 +250,9 @@ hipError_t launch_path_deviation_vjp(const BatchView& b, const double* samples, 
                                      const double* waypoints, int capacity, const int32_t* status, const double* grad_deviation,
                                      double* grad_samples, double* grad_waypoints, hipStream_t stream) {
   const size_t lds = sizeof(double) * (6 * ((size_t)b.max_segments + 1) + 64 * kDevTileStride) + sizeof(int) * 64;
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (b.n_paths == 0) return hipSuccess;
+  if (b.n_paths == 0) return lds > kLdsPerWorkgroup ? hipErrorInvalidValue : hipSuccess;
   const auto vjp = MRS_TG_KERNEL(path_deviation_vjp_kernel);
-  if (lds > 64 * 1024) {
-    hipError_t e = set_max_dynamic_lds(vjp, lds);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = prepare_dynamic_lds(vjp, lds); e != hipSuccess) return e;
   MRS_TG_LAUNCH_TIMED(vjp, dim3((unsigned)b.n_paths), dim3(64), lds, stream, b, samples, n_samples, waypoints, capacity, status,
                       grad_deviation, grad_samples, grad_waypoints);
   return hipGetLastError();

@@ -19,30 +19,18 @@
 // of the samples whose cursor is w (cursors never decrease, so that is increasing sample index throughout).
 #pragma once
 
-#include <cmath>
-#include <cstddef>
-
-#ifndef MRS_TG_HD
-#if defined(__HIPCC__)
-#define MRS_TG_HD __host__ __device__
-#else
-#define MRS_TG_HD
-#endif
-#endif
-#if defined(__clang__)
-#define MRS_TG_DEV_NO_CONTRACT _Pragma("clang fp contract(off)")
-#else
-#define MRS_TG_DEV_NO_CONTRACT
-#endif
+#include "mrs_tg_hd.hpp"
 
 namespace mrs_tg {
 namespace devq {
+
+using mrs_tg::accumulate;
 
 constexpr double kAdvanceDistance = 0.05;  // :1448, a constant of the reference
 
 // distFromSegment (:1533-1554): the distance of p from the segment s1 -> s2 (x, y, z; whatever follows is not read)
 MRS_TG_HD inline double dist(const double* p, const double* s1, const double* s2) {
-  MRS_TG_DEV_NO_CONTRACT
+  MRS_TG_NO_CONTRACT
   const double sv0 = s2[0] - s1[0], sv1 = s2[1] - s1[1], sv2 = s2[2] - s1[2];
   const double len = sqrt(sv0 * sv0 + sv1 * sv1 + sv2 * sv2);
   double n0 = sv0, n1 = sv1, n2 = sv2;
@@ -73,7 +61,7 @@ MRS_TG_HD inline bool counted(int c, int first_segment, int S) { return c > 0 ||
 // g * dd/dp, g * dd/da, g * dd/db of d = dist(p, a, b), the branch being the forward's
 MRS_TG_HD inline void dist_vjp(const double* p, const double* a, const double* b, double g, double (&gp)[3], double (&ga)[3],
                                double (&gb)[3]) {
-  MRS_TG_DEV_NO_CONTRACT
+  MRS_TG_NO_CONTRACT
   for (int k = 0; k < 3; ++k) gp[k] = ga[k] = gb[k] = 0.0;
   if (g == 0.0) return;
   const double sv0 = b[0] - a[0], sv1 = b[1] - a[1], sv2 = b[2] - a[2];
@@ -111,12 +99,6 @@ MRS_TG_HD inline void dist_vjp(const double* p, const double* a, const double* b
     ga[k] = 0.0 - rest * gp[k];
     gb[k] = 0.0 - tau * gp[k];
   }
-}
-
-// every accumulator: acc <- acc + term, from 0.0
-MRS_TG_HD inline double accumulate(double acc, double term) {
-  MRS_TG_DEV_NO_CONTRACT
-  return acc + term;
 }
 
 }  // namespace devq

@@ -15,13 +15,13 @@
 #include <hip/hip_runtime.h>
 
 #include "mrs_tg_constants.h"
+#include "mrs_tg_hd.hpp"
 #include "mrs_tg_launch.h"
 
 namespace mrs_tg {
 
-constexpr int kN = 10;     // coefficients per polynomial
-constexpr int kHalf = 5;   // derivative slots per vertex
-constexpr int kD = 4;      // dimensions
+// (kN coefficients per polynomial, kD dimensions: mrs_tg_hd.hpp)
+constexpr int kHalf = kB;  // derivative slots per vertex
 constexpr int kNB = 4;     // free-candidate slots per vertex (velocity..snap)
 constexpr int kSlot0 = 1;  // first free-candidate slot
 constexpr double kTimeLowerBound = 0.01;  // kOptimizationTimeLowerBound (polynomial_optimization_nonlinear.h:304)
@@ -45,6 +45,18 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+// The same within one wavefront: what its lanes wrote to LDS before the call is what they read behind it
+__device__ __forceinline__ void wave_lds_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// lane src's value of v in every lane (src wavefront-uniform)
+__device__ __forceinline__ double lane_value(double v, int src) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), src), hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
+  return __hiloint2double(hi, lo);
 }
 
 // blockIdx -> work index such that the workgroups of one XCD (blockIdx % 8: round-robin dispatch over the eight XCDs of

@@ -29,12 +29,6 @@ constexpr int kEvTileStride = evalq::kCoeffElems + 1;    // 40 coefficient terms
 constexpr int kEvRowStride = 21;                         // doubles between the rows [5][4] of a pass in LDS (odd: no bank is hit 8 times)
 constexpr int kEvTargetBlocks = 8192;                    // the forward cuts the queries of few paths into slices up to here
 
-__device__ __forceinline__ void lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 }  // namespace
 
 template <int NO>
@@ -55,9 +49,9 @@ __global__ __launch_bounds__(64) void evaluate_kernel(BatchView b, const double*
     const double* __restrict__ cg = coeffs + (size_t)pr.s0 * kD * kN;
     for (int e = lane; e < S * kD * kN; e += 64) s_c[e] = cg[e];
   }
-  lds_sync();
+  wave_lds_barrier();
   const bool sorted = evalq::running_sums(s_T, S, s_A, lane == 0);
-  lds_sync();
+  wave_lds_barrier();
   const int k_begin = blockIdx.y * slice;
   const int k_end = min(k_begin + slice, n_queries);
   const size_t row0 = (size_t)pr.p * (size_t)n_queries;
@@ -95,7 +89,7 @@ __global__ __launch_bounds__(64) void evaluate_kernel(BatchView b, const double*
       for (int o = 0; o < NO; ++o)
 #pragma unroll
         for (int dd = 0; dd < kD; ++dd) mine[o * kD + dd] = row[o][dd];
-      lds_sync();
+      wave_lds_barrier();
       const int pairs = min(64, k_end - k0) * (kRow / 2);
       eval_pair* out = reinterpret_cast<eval_pair*>(states + (row0 + k0) * (size_t)kRow);
 #pragma unroll
@@ -108,7 +102,7 @@ __global__ __launch_bounds__(64) void evaluate_kernel(BatchView b, const double*
           __builtin_nontemporal_store(v, out + ch);
         }
       }
-      lds_sync();  // (the next pass overwrites the rows)
+      wave_lds_barrier();  // (the next pass overwrites the rows)
     }
     if (valid) {
       if (query_segment) __builtin_nontemporal_store((int32_t)at.seg, query_segment + row0 + k);
@@ -148,9 +142,9 @@ __global__ __launch_bounds__(64) void evaluate_vjp_kernel(BatchView b, const dou
       for (int e = lane; e < S * kD * kN; e += 64) s_c[e] = cg[e];
     }
     for (int e = lane; e < S * kEvTileStride; e += 64) s_acc[e] = 0.0;
-    lds_sync();
+    wave_lds_barrier();
     const bool sorted = evalq::running_sums(s_T, S, s_A, lane == 0);
-    lds_sync();
+    wave_lds_barrier();
     int cur = -1;  // the segment the register accumulator belongs to
     double acc = 0.0;
     for (int k0 = 0; k0 < n_queries; k0 += 64) {
@@ -191,7 +185,7 @@ __global__ __launch_bounds__(64) void evaluate_vjp_kernel(BatchView b, const dou
           mine[evalq::kCoeffElems] = g;
           s_seg[lane % kEvTileQueries] = at.seg;
         }
-        lds_sync();
+        wave_lds_barrier();
         for (int r = 0; r < count; ++r) {
           const int seg = __builtin_amdgcn_readfirstlane(s_seg[r]);
           if (seg < 0) continue;
@@ -202,11 +196,11 @@ __global__ __launch_bounds__(64) void evaluate_vjp_kernel(BatchView b, const dou
           }
           acc = sampvjp::accumulate(acc, s_tile[r * kEvTileStride + slot]);
         }
-        lds_sync();
+        wave_lds_barrier();
       }
     }
     if (cur >= 0 && owns) s_acc[cur * kEvTileStride + slot] = acc;
-    lds_sync();
+    wave_lds_barrier();
     if (grad_coeffs) {
       double* __restrict__ gc = grad_coeffs + (size_t)pr.s0 * kD * kN;
       for (int e = lane; e < S * kD * kN; e += 64) gc[e] = s_acc[(e / evalq::kCoeffElems) * kEvTileStride + e % evalq::kCoeffElems];
@@ -219,7 +213,7 @@ __global__ __launch_bounds__(64) void evaluate_vjp_kernel(BatchView b, const dou
         r = sampvjp::accumulate(s_acc[i * kEvTileStride + evalq::kCoeffElems], r);
       }
     }
-    lds_sync();  // (the next path's staging overwrites what this one read)
+    wave_lds_barrier();  // (the next path's staging overwrites what this one read)
   }
 }
 
@@ -228,13 +222,9 @@ hipError_t launch_evaluate(const BatchView& b, const double* coeffs, const doubl
                            hipStream_t stream) {
   if (n_orders != 1 && n_orders != kSampleStateOrders) return hipErrorInvalidValue;
   const size_t lds = sizeof(double) * ((size_t)b.max_segments * (2 + kD * kN) + (n_orders == 1 ? 0 : 64 * kEvRowStride));
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (b.n_paths == 0 || n_queries == 0) return hipSuccess;
+  if (b.n_paths == 0 || n_queries == 0) return lds > kLdsPerWorkgroup ? hipErrorInvalidValue : hipSuccess;
   const auto fwd = n_orders == 1 ? MRS_TG_KERNEL(evaluate_kernel<1>) : MRS_TG_KERNEL(evaluate_kernel<kSampleStateOrders>);
-  if (lds > 64 * 1024) {
-    hipError_t e = set_max_dynamic_lds(fwd, lds);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = prepare_dynamic_lds(fwd, lds); e != hipSuccess) return e;
   // one wavefront per path; the queries of few paths are cut into slices (multiples of 64) so that the device has work
   const int passes = (n_queries + 63) / 64;
   int slices = (kEvTargetBlocks + b.n_paths - 1) / b.n_paths;
@@ -252,13 +242,9 @@ hipError_t launch_evaluate_vjp(const BatchView& b, const double* coeffs, const d
   if (n_orders != 1 && n_orders != kSampleStateOrders) return hipErrorInvalidValue;
   const size_t lds = sizeof(double) * ((size_t)b.max_segments * (2 + kD * kN + kEvTileStride) + kEvTileQueries * kEvTileStride) +
                      sizeof(int) * kEvTileQueries;
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (b.n_paths == 0) return hipSuccess;
+  if (b.n_paths == 0) return lds > kLdsPerWorkgroup ? hipErrorInvalidValue : hipSuccess;
   const auto vjp = n_orders == 1 ? MRS_TG_KERNEL(evaluate_vjp_kernel<1>) : MRS_TG_KERNEL(evaluate_vjp_kernel<kSampleStateOrders>);
-  if (lds > 64 * 1024) {
-    hipError_t e = set_max_dynamic_lds(vjp, lds);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = prepare_dynamic_lds(vjp, lds); e != hipSuccess) return e;
   MRS_TG_LAUNCH_TIMED(vjp, dim3((unsigned)b.n_paths), dim3(64), lds, stream, b, coeffs, seg_times, query_times, n_queries,
                       grad_states, status, grad_coeffs, grad_times, grad_query);
   return hipGetLastError();

@@ -21,21 +21,16 @@
 namespace mrs_tg {
 namespace evalq {
 
-constexpr int kN = sampvjp::kN, kD = sampvjp::kD, kMaxOrders = sampvjp::kMaxOrders;
+using mrs_tg::kD;
+using mrs_tg::kMaxOrders;
+using mrs_tg::kN;
 constexpr int kCoeffElems = sampvjp::kCoeffElems;
-
-// j!/(j-k)!, a compile-time constant wherever j and k are
-MRS_TG_HD constexpr double falling(int j, int k) {
-  double v = 1.0;
-  for (int n = 0; n < k; ++n) v *= (double)(j - n);
-  return v;
-}
 
 // A[i] = ((0 + T_0) + T_1) + ... + T_i, the additions of the reference's loop.  Returns whether the sums never decrease (no
 // negative time, nothing that is not a number): then the first sum above a query may be found by bisection.
 // (store: false in the lanes of a wavefront that only need the answer)
 MRS_TG_HD inline bool running_sums(const double* T, int S, double* A, bool store = true) {
-  MRS_TG_SVJP_NO_CONTRACT
+  MRS_TG_NO_CONTRACT
   double acc = 0.0;
   bool sorted = true;
   for (int i = 0; i < S; ++i) {
@@ -55,7 +50,7 @@ struct Located {
 // The first i with A[i] > t: the loop as written when the sums may decrease, a bisection over them when they do not (the
 // same index: "A[i] > t" is then false up to it and true from it on).
 MRS_TG_HD inline Located locate(const double* T, const double* A, int S, bool sorted, double t) {
-  MRS_TG_SVJP_NO_CONTRACT
+  MRS_TG_NO_CONTRACT
   Located r;
   r.seg = -1;
   r.tau = 0.0;
@@ -87,27 +82,20 @@ MRS_TG_HD inline Located locate(const double* T, const double* A, int S, bool so
   return r;
 }
 
-// the sampler's wrap_heading (mrs_tg_sampling.hpp), operation for operation
-MRS_TG_HD inline double wrap_heading(double y) {
-  const double two_pi_hi = 6.283185307179586232e+00, two_pi_lo = 2.449293598294706414e-16;
-  const double kf = rint(y * 1.591549430918953456e-01);
-  return fma(-kf, two_pi_lo, fma(-kf, two_pi_hi, y));
-}
-
 // p^(O)(tau) of the polynomial c[0 .. 10): Horner over j!/(j-O)! c_j, as sample_path_walk evaluates
 template <int O>
 MRS_TG_HD inline double derivative(const double* c, double tau) {
-  MRS_TG_SVJP_NO_CONTRACT
-  double acc = falling(kN - 1, O) * c[kN - 1];
-  MRS_TG_SVJP_UNROLL
-  for (int j = kN - 2; j >= O; --j) acc = fma(acc, tau, falling(j, O) * c[j]);
+  MRS_TG_NO_CONTRACT
+  double acc = falling_factorial(kN - 1, O) * c[kN - 1];
+  MRS_TG_UNROLL
+  for (int j = kN - 2; j >= O; --j) acc = fma(acc, tau, falling_factorial(j, O) * c[j]);
   return acc;
 }
 
 // one state row [NO][4] from the segment's coefficients c[4][10]
 template <int NO>
 MRS_TG_HD inline void state_row(const double* c, double tau, double (&out)[NO][kD]) {
-  MRS_TG_SVJP_UNROLL
+  MRS_TG_UNROLL
   for (int dd = 0; dd < kD; ++dd) {
     const double* cd = c + dd * kN;
     out[0][dd] = derivative<0>(cd, tau);
@@ -124,12 +112,12 @@ MRS_TG_HD inline void state_row(const double* c, double tau, double (&out)[NO][k
 // One query's terms of dL/dc of its segment: terms[dim * 10 + j] from its upstream row G[NO][4]
 template <int NO>
 MRS_TG_HD inline void coeff_terms(const double* G, double tau, double (&terms)[kCoeffElems]) {
-  MRS_TG_SVJP_UNROLL
+  MRS_TG_UNROLL
   for (int dd = 0; dd < kD; ++dd) {
     double g[NO];
-    MRS_TG_SVJP_UNROLL
+    MRS_TG_UNROLL
     for (int o = 0; o < NO; ++o) g[o] = G[o * kD + dd];
-    MRS_TG_SVJP_UNROLL
+    MRS_TG_UNROLL
     for (int j = 0; j < kN; ++j) {
       double w[kN];
       sampvjp::coeff_weights(j, w);
@@ -142,11 +130,11 @@ MRS_TG_HD inline void coeff_terms(const double* G, double tau, double (&terms)[k
 template <int NO>
 MRS_TG_HD inline double time_gradient(const double* c, const double* G, double tau) {
   double s = 0.0;
-  MRS_TG_SVJP_UNROLL
+  MRS_TG_UNROLL
   for (int o = 0; o < NO; ++o) {
     double w[kN];
     sampvjp::time_weights(o, w);
-    MRS_TG_SVJP_UNROLL
+    MRS_TG_UNROLL
     for (int dd = 0; dd < kD; ++dd) {
       const double term = sampvjp::time_term(o, w, c + dd * kN, G[o * kD + dd], tau);
       s = (o == 0 && dd == 0) ? term : sampvjp::accumulate(s, term);

@@ -533,12 +533,8 @@ static hipError_t launch_sample_n(const BatchView& b, const double* coeffs, cons
     if (et != hipSuccess) return et;
   }
   const size_t lds = sizeof(double) * ((size_t)b.max_segments * (1 + kD * kN) + kSampleBuffer) + sizeof(unsigned short) * kSampleBuffer;
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
   const auto sampler = MRS_TG_KERNEL(sample_kernel<NDER>);
-  if (lds > 64 * 1024) {
-    hipError_t e = set_max_dynamic_lds(sampler, lds);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = prepare_dynamic_lds(sampler, lds); e != hipSuccess) return e;
   // one workgroup per path.  (Fewer, persistent workgroups that walk several paths each -- the kernel's loop allows it --
   // were measured in round 5: 65536 x 10 pipeline 1328 -> 1347 / 1385 / 1384 us with 15360 / 7680 / 3840 workgroups.)
   MRS_TG_LAUNCH(sampler, dim3((unsigned)b.n_paths), dim3(64), lds, stream, b, coeffs, seg_times, dt, capacity,

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "../../include/mrs_tg.h"
+#include "mrs_tg_hd.hpp"
 #include "mrs_tg_knobs.hpp"
 
 struct mrs_tg_ctx;
@@ -78,6 +79,15 @@ constexpr const char* kernel_name(void (*)(Args...), const char* written) { retu
 template <class... Args>
 inline hipError_t set_max_dynamic_lds(const Kernel<Args...>& k, size_t bytes) {
   return hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+// The dynamic LDS of a launch: a workgroup cannot have more than a compute unit's 160 KB (hipErrorInvalidValue, which the ABI
+// words for its caller), and more than the 64 KB a launch may ask for by default needs the kernel's limit raised first (a
+// driver call, so only then).  A launcher that returns early for an empty batch refuses an oversize need before it does.
+constexpr size_t kLdsPerWorkgroup = 160 * 1024, kLdsDefaultLimit = 64 * 1024;
+template <class... Args>
+inline hipError_t prepare_dynamic_lds(const Kernel<Args...>& k, size_t bytes) {
+  if (bytes > kLdsPerWorkgroup) return hipErrorInvalidValue;
+  return bytes > kLdsDefaultLimit ? set_max_dynamic_lds(k, bytes) : hipSuccess;
 }
 // launch with the pending timer, if any
 #define MRS_TG_LAUNCH_TIMED(kernel, grid, block, lds, stream, ...)                                           \
@@ -158,7 +168,7 @@ hipError_t launch_estimate_times(const BatchView& b, const double* wp, const dou
 hipError_t launch_sample(const BatchView& b, const double* coeffs, const double* seg_times, double dt, int capacity,
                          int32_t* n_samples, double* samples, hipStream_t stream);
 // the same walk, every sample with its derivative orders 0..4: states [n_paths][capacity][kSampleStateOrders][4]
-constexpr int kSampleStateOrders = 5;
+constexpr int kSampleStateOrders = kMaxOrders;
 hipError_t launch_sample_states(const BatchView& b, const double* coeffs, const double* seg_times, double dt, int capacity,
                                 int32_t* n_samples, double* states, hipStream_t stream);
 // ---- the policy layer's per-round device work (mrs_tg_policy_dev.hip) ----

@@ -24,13 +24,6 @@ namespace mrs_tg {
 constexpr int kGridCells = 32;
 constexpr int kPolishIters = 17;
 
-// falling factorial j!/(j-k)! as a compile-time constant
-__host__ __device__ constexpr double falling(int j, int k) {
-  double v = 1.0;
-  for (int n = 0; n < k; ++n) v *= (double)(j - n);
-  return v;
-}
-
 // Coefficients of q^(K) (derivative K in normalised time) of NDIM dimensions, kept in registers; every loop below has
 // compile-time bounds so nothing is indexed dynamically.  q^(K+1) and q^(K+2) come out of the same Horner pass (the nested
 // recurrence p'' <- p'' t + p', p' <- p' t + p, p <- p t + c): one coefficient array per dimension instead of three -- 18
@@ -86,7 +79,7 @@ struct MagPoly : MagPolyBase<NDIM, kN - K> {
 #pragma unroll
     for (int q = 0; q < NDIM; ++q)
 #pragma unroll
-      for (int j = 0; j < N0; ++j) this->d0[q][j] = cb[q][j + K] * falling(j + K, K);
+      for (int j = 0; j < N0; ++j) this->d0[q][j] = cb[q][j + K] * falling_factorial(j + K, K);
   }
 };
 
@@ -103,9 +96,9 @@ struct MagPolyAny : MagPolyBase<NDIM, kN - 1> {
     for (int q = 0; q < NDIM; ++q)
 #pragma unroll
       for (int j = 0; j < N0; ++j) {
-        const double a1 = cb[q][j + 1] * falling(j + 1, 1);
-        const double a2 = (j + 2 < kN) ? cb[q][j + 2 < kN ? j + 2 : 0] * falling(j + 2, 2) : 0.0;
-        const double a3 = (j + 3 < kN) ? cb[q][j + 3 < kN ? j + 3 : 0] * falling(j + 3, 3) : 0.0;
+        const double a1 = cb[q][j + 1] * falling_factorial(j + 1, 1);
+        const double a2 = (j + 2 < kN) ? cb[q][j + 2 < kN ? j + 2 : 0] * falling_factorial(j + 2, 2) : 0.0;
+        const double a3 = (j + 3 < kN) ? cb[q][j + 3 < kN ? j + 3 : 0] * falling_factorial(j + 3, 3) : 0.0;
         this->d0[q][j] = (K == 1) ? a1 : (K == 2) ? a2 : a3;
       }
   }
@@ -278,7 +271,7 @@ __device__ __forceinline__ double bernstein_bound(const double (&cb)[kN]) {
   double a[n + 1], mag = 0.0;
 #pragma unroll
   for (int j = 0; j <= n; ++j) {
-    a[j] = cb[j + K] * falling(j + K, K);
+    a[j] = cb[j + K] * falling_factorial(j + K, K);
     mag += fabs(a[j]);
   }
   double best = 0.0;

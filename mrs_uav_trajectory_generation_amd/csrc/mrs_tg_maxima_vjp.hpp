@@ -14,28 +14,14 @@
 // explicit fma or kept apart by contraction being off, so the CPU and the GPU execute the same operations.
 #pragma once
 
-#include <cmath>
-#include <cstddef>
-
-#ifndef MRS_TG_HD
-#if defined(__HIPCC__)
-#define MRS_TG_HD __host__ __device__
-#else
-#define MRS_TG_HD
-#endif
-#endif
-#if defined(__clang__)
-#define MRS_TG_MVJP_NO_CONTRACT _Pragma("clang fp contract(off)")
-#define MRS_TG_MVJP_UNROLL _Pragma("unroll")
-#else
-#define MRS_TG_MVJP_NO_CONTRACT
-#define MRS_TG_MVJP_UNROLL
-#endif
+#include "mrs_tg_hd.hpp"
 
 namespace mrs_tg {
 namespace maxvjp {
 
-constexpr int kN = 10, kD = 4, kEntries = 9;
+using mrs_tg::kD;
+using mrs_tg::kN;
+constexpr int kEntries = 9;
 constexpr int kRefineSteps = 4;
 constexpr double kRefineStop = 0x1p-50;
 // the refinement polishes the forward's own maximiser, it does not look for another: a seed the polish left at its stopping
@@ -46,13 +32,6 @@ constexpr double kRefineReach = 0x1p-20;
 // of its own evaluation (Horner with cancelling terms), so the refined m2 may come out lower although the abscissa improved.
 // A fall counts only beyond that rounding: 2 (2 N0 + 2) eps sum_q A_q^2, A_q = sum_j |d0_qj| tau^j (the evaluation's bound).
 constexpr double kEps = 0x1p-53;
-
-// j!/(j-k)!, an exact integer
-MRS_TG_HD constexpr double falling_factorial(int j, int k) {
-  double v = 1.0;
-  for (int n = 0; n < k; ++n) v *= (double)(j - n);
-  return v;
-}
 
 // group 0 = {x, y} (dimensions 0, 1), 1 = {z} (2), 2 = {heading} (3)
 MRS_TG_HD constexpr int group_of_dim(int dim) { return dim < 2 ? 0 : dim - 1; }
@@ -71,29 +50,29 @@ struct QPoly {
   double d0[NDIM][N0];
 
   MRS_TG_HD void init(const double* c, int dim0, double T) {
-    MRS_TG_MVJP_NO_CONTRACT
+    MRS_TG_NO_CONTRACT
     double cb[NDIM][kN];
     double tp = 1.0;
-    MRS_TG_MVJP_UNROLL
+    MRS_TG_UNROLL
     for (int j = 0; j < kN; ++j) {
-      MRS_TG_MVJP_UNROLL
+      MRS_TG_UNROLL
       for (int q = 0; q < NDIM; ++q) cb[q][j] = c[(dim0 + q) * kN + j] * tp;
       tp *= T;
     }
-    MRS_TG_MVJP_UNROLL
+    MRS_TG_UNROLL
     for (int q = 0; q < NDIM; ++q)
-      MRS_TG_MVJP_UNROLL
+      MRS_TG_UNROLL
       for (int j = 0; j < N0; ++j) d0[q][j] = cb[q][j + K] * falling_factorial(j + K, K);
   }
 
   // the rounding bound of m2 at tau (see kEps)
   MRS_TG_HD double m2_rounding(double tau) const {
-    MRS_TG_MVJP_NO_CONTRACT
+    MRS_TG_NO_CONTRACT
     double s = 0.0;
-    MRS_TG_MVJP_UNROLL
+    MRS_TG_UNROLL
     for (int q = 0; q < NDIM; ++q) {
       double a = fabs(d0[q][N0 - 1]);
-      MRS_TG_MVJP_UNROLL
+      MRS_TG_UNROLL
       for (int j = N0 - 2; j >= 0; --j) a = fma(a, tau, fabs(d0[q][j]));
       s = fma(a, a, s);
     }
@@ -103,14 +82,14 @@ struct QPoly {
   // v0 = q^(K)(tau), v1 = q^(K+1)(tau), h2 = q^(K+2)(tau) / 2 per dimension (one nested Horner pass);
   // m2 = sum v0^2, g = sum v0 v1 = dm2/dtau / 2, dg = dg/dtau
   MRS_TG_HD void eval(double tau, double (&v0)[NDIM], double (&v1)[NDIM], double& m2, double& g, double& dg) const {
-    MRS_TG_MVJP_NO_CONTRACT
+    MRS_TG_NO_CONTRACT
     m2 = 0.0;
     g = 0.0;
     dg = 0.0;
-    MRS_TG_MVJP_UNROLL
+    MRS_TG_UNROLL
     for (int q = 0; q < NDIM; ++q) {
       double a0 = d0[q][N0 - 1], a1 = 0.0, h2 = 0.0;
-      MRS_TG_MVJP_UNROLL
+      MRS_TG_UNROLL
       for (int j = N0 - 2; j >= 0; --j) {
         h2 = fma(h2, tau, a1);
         a1 = fma(a1, tau, a0);
@@ -128,7 +107,7 @@ struct QPoly {
 // The refined abscissa of a seed (see the file comment); [lo, hi] is the seed's grid cell
 template <int K, int NDIM>
 MRS_TG_HD double refine_tau(const QPoly<K, NDIM>& qp, double tau, double lo, double hi) {
-  MRS_TG_MVJP_NO_CONTRACT
+  MRS_TG_NO_CONTRACT
   if (!(tau > 0.0 && tau < 1.0)) return tau;
   double v0[NDIM], v1[NDIM], m2_seed, g, dg;
   qp.eval(tau, v0, v1, m2_seed, g, dg);
@@ -144,7 +123,7 @@ MRS_TG_HD double refine_tau(const QPoly<K, NDIM>& qp, double tau, double lo, dou
 
 template <int K, int NDIM>
 MRS_TG_HD EntryTerms entry_terms_k(const double* c, double T, int dim0, double tau_seed, double lo, double hi, double G) {
-  MRS_TG_MVJP_NO_CONTRACT
+  MRS_TG_NO_CONTRACT
   QPoly<K, NDIM> qp;
   qp.init(c, dim0, T);
   const double tau = refine_tau(qp, tau_seed, lo, hi);
@@ -155,17 +134,17 @@ MRS_TG_HD EntryTerms entry_terms_k(const double* c, double T, int dim0, double t
   if (!(m2 > 0.0)) return e;  // a zero maximum: the entry contributes 0 (no direction to take)
   const double inv = 1.0 / sqrt(m2);
   double u[NDIM];
-  MRS_TG_MVJP_UNROLL
+  MRS_TG_UNROLL
   for (int q = 0; q < NDIM; ++q) u[q] = v0[q] * inv;
   e.s0 = G * u[0];
   e.s1 = (NDIM == 2) ? G * u[NDIM - 1] : 0.0;
   if (tau == 1.0) {  // the maximum sits at the segment's end: dM/dT = u . p^(k+1)(T) = u . q^(k+1)(1) / T^(k+1)
     const double ti = 1.0 / T;
     double sc = ti;
-    MRS_TG_MVJP_UNROLL
+    MRS_TG_UNROLL
     for (int n = 0; n < K; ++n) sc = sc * ti;
     double d = 0.0;
-    MRS_TG_MVJP_UNROLL
+    MRS_TG_UNROLL
     for (int q = 0; q < NDIM; ++q) d = fma(u[q], v1[q], d);
     e.dT = G * (d * sc);
   }
@@ -199,7 +178,7 @@ MRS_TG_HD inline EntryTerms entry_terms(const double* c, double T, int which, do
 // The segment's sums, entry w of the segment at e[w * stride]: dL/dc[dim][j] = sum over k = 1, 2, 3 (in that order) of
 // s_dim j!/(j-k)! t*_k^(j-k) of the entry (k, group of dim)
 MRS_TG_HD inline double coeff_gradient(const EntryTerms* e, int stride, int dim, int j) {
-  MRS_TG_MVJP_NO_CONTRACT
+  MRS_TG_NO_CONTRACT
   const int grp = group_of_dim(dim);
   double acc = 0.0;
   for (int k = 1; k <= 3; ++k) {
@@ -216,7 +195,7 @@ MRS_TG_HD inline double coeff_gradient(const EntryTerms* e, int stride, int dim,
 
 // dL/dT = the nine entries' time terms, summed in entry order
 MRS_TG_HD inline double time_gradient(const EntryTerms* e, int stride) {
-  MRS_TG_MVJP_NO_CONTRACT
+  MRS_TG_NO_CONTRACT
   double acc = 0.0;
   for (int w = 0; w < kEntries; ++w) acc = acc + e[w * stride].dT;
   return acc;

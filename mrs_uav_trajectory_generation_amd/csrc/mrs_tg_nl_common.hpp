@@ -6,20 +6,17 @@
 
 #include <cmath>
 
+#include "mrs_tg_device.hpp"
+
 namespace mrs_tg {
 
-// cross-lane moves (DPP within a row of 16, v_readlane across rows)
+// cross-lane moves (DPP within a row of 16; across rows: lane_value of mrs_tg_device.hpp, v_readlane)
 // (bound_ctrl set: with all rows and banks enabled and a permutation that stays inside the row every lane is written, so
 // the "old" operand is dead -- without the flag the compiler materialises it, two more v_mov_b32 per moved double)
 template <int CTRL>
 __device__ __forceinline__ double dpp_move(double v) {
   const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
   const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double row_value(double v, int src_lane) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
   return __hiloint2double(hi, lo);
 }
 

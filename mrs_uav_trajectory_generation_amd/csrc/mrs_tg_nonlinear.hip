@@ -121,7 +121,7 @@ __device__ __forceinline__ double group_sum(double v, int G) {
     v += dpp_move<0x4E>(v);
     v += dpp_move<0x141>(v);
     v += dpp_move<0x140>(v);
-    return row_value(v, 0);
+    return lane_value(v, 0);
   }
   v += dpp_move<0xB1>(v);                 // quad_perm [1,0,3,2]: lane ^ 1
   if (G >= 4) v += dpp_move<0x4E>(v);     // quad_perm [2,3,0,1]: lane ^ 2
@@ -130,7 +130,7 @@ __device__ __forceinline__ double group_sum(double v, int G) {
   if (G >= 32) {
     // every lane of a row now holds its row's sum.  Rows of a group that is masked off at this point deliver stale
     // values, which only that group's (inactive) lanes would consume.
-    const double a = row_value(v, 0) + row_value(v, 16), b = row_value(v, 32) + row_value(v, 48);
+    const double a = lane_value(v, 0) + lane_value(v, 16), b = lane_value(v, 32) + lane_value(v, 48);
     v = (G == 64) ? a + b : ((threadIdx.x & 32) ? b : a);
   }
   return v;
@@ -150,7 +150,7 @@ __device__ __forceinline__ void group_sum_n(double (&v)[N], int G) {
 #pragma unroll
     for (int n = 0; n < N; ++n) v[n] += dpp_move<0x140>(v[n]);
 #pragma unroll
-    for (int n = 0; n < N; ++n) v[n] = row_value(v[n], 0);
+    for (int n = 0; n < N; ++n) v[n] = lane_value(v[n], 0);
     return;
   }
 #pragma unroll
@@ -170,7 +170,7 @@ __device__ __forceinline__ void group_sum_n(double (&v)[N], int G) {
   if (G >= 32) {
 #pragma unroll
     for (int n = 0; n < N; ++n) {
-      const double a = row_value(v[n], 0) + row_value(v[n], 16), b = row_value(v[n], 32) + row_value(v[n], 48);
+      const double a = lane_value(v[n], 0) + lane_value(v[n], 16), b = lane_value(v[n], 32) + lane_value(v[n], 48);
       v[n] = (G == 64) ? a + b : ((threadIdx.x & 32) ? b : a);
     }
   }
@@ -244,7 +244,7 @@ __device__ __forceinline__ double evaluate_pair(const double* seg, const double*
   qfk += dpp_move<0x4E>(qfk);
   Jk = guarded_cost(Jk, qfk, k == 0);
   if (work && Jk == kUnreliableCost) *tripped = 1;
-  const double J0 = row_value(Jk, 0);
+  const double J0 = lane_value(Jk, 0);
   if (work && dim0 == 0 && k >= 1) grad[k - 1] = (Jk - J0) / kGradStep;
   return J0;
 }
@@ -336,7 +336,7 @@ __device__ __forceinline__ double evaluate_careful(const uint8_t* __restrict__ m
     if (active && k <= S && (k == 0 || S > 1)) Jk = primal_cost_lane(mask, vals, v0, S, d, pt, k, dim0, ws, wstride, wlane);
     Jk += dpp_move<0xB1>(Jk);
     Jk += dpp_move<0x4E>(Jk);
-    if (r == 0) J0 = row_value(Jk, 0);
+    if (r == 0) J0 = lane_value(Jk, 0);
     if (active && dim0 == 0 && k >= 1 && k <= S) grad[k - 1] = (S > 1) ? (Jk - J0) / kGradStep : 0.0;
   }
   return J0;
@@ -359,7 +359,7 @@ __device__ __forceinline__ double evaluate_general(const uint8_t* __restrict__ m
                                      wstride, wlane, nullptr);
     Jk += dpp_move<0xB1>(Jk);
     Jk += dpp_move<0x4E>(Jk);
-    if (r == 0) J0 = row_value(Jk, 0);
+    if (r == 0) J0 = lane_value(Jk, 0);
     if (active && dim0 == 0 && k >= 1 && k <= S) grad[k - 1] = (S > 1) ? (Jk - J0) / kGradStep : 0.0;
   }
   return J0;
@@ -2380,10 +2380,7 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
 #if MRS_TG_WITH_CAREFUL
     if (careful) {
       const size_t clds = ((size_t)group_lds_doubles(b.max_segments, true) + kBlockConsts) * sizeof(double);
-      if (clds > 160 * 1024) return hipErrorInvalidValue;
-      if (clds > 64 * 1024 &&
-          (e = hipFuncSetAttribute((const void*)optimize_careful_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds)) != hipSuccess)
-        return e;
+      if ((e = prepare_dynamic_lds(MRS_TG_KERNEL(optimize_careful_kernel), clds)) != hipSuccess) return e;
       MRS_TG_LAUNCH_EXT(optimize_careful_kernel, dim3(careful_cap), dim3(64), clds, stream, nullptr,
                             general ? nullptr : kt.stop, 0, b, prm, mask, vals, seg_times, nl.d_opt_status, nl.d_careful_ws);
       if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -2397,10 +2394,7 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
     // 5 x 5-block evaluation, from the start times kept aside, `general_cap` listed paths per launch
     if (general) {
       const size_t glds = ((size_t)group_lds_doubles(b.max_segments, true) + kBlockConsts) * sizeof(double);
-      if (glds > 160 * 1024) return hipErrorInvalidValue;
-      if (glds > 64 * 1024 &&
-          (e = hipFuncSetAttribute((const void*)optimize_general_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds)) != hipSuccess)
-        return e;
+      if ((e = prepare_dynamic_lds(MRS_TG_KERNEL(optimize_general_kernel), glds)) != hipSuccess) return e;
       NonlinearParams gp = prm;
       gp.only_flagged = nullptr;
       gp.queue_next = nullptr;

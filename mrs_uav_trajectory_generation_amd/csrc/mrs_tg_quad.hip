@@ -124,12 +124,6 @@ __device__ __forceinline__ void store_coeff_pair_through(double2* dst, double2 v
 #endif
 }
 
-__device__ __forceinline__ void quad_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 __device__ __forceinline__ double quad_sum(double v) {  // over the four lanes of a quad, to all of them
   v += dpp_move<0xB1>(v);
   v += dpp_move<0x4E>(v);
@@ -245,7 +239,7 @@ __device__ __forceinline__ void solve_quad_body(const BatchView& b, int d, const
   const bool plain_wave = __ballot(active && !ok) == 0ull;
   const unsigned long long pos_bad = __ballot(active && !pos_ok);
   const bool path_pos_ok = ((pos_bad >> (lane & ~3)) & 0xFull) == 0ull;
-  quad_wave_sync();
+  wave_lds_barrier();
 
   double my_cost = 0.0;
   if (plain_wave) {
@@ -460,7 +454,7 @@ __device__ __forceinline__ void solve_quad_body(const BatchView& b, int d, const
       p_a2 = p_a3;
       p_a3 = p_a4;
     }
-    quad_wave_sync();  // (lane 0 of a quad wrote L and W for the other three)
+    wave_lds_barrier();  // (lane 0 of a quad wrote L and W for the other three)
     // ---- backward: x_v = L^-T (z - W x_{v+1}); coefficients and cost of segment v from x_v, x_{v+1}
     double xn[kNB] = {0.0, 0.0, 0.0, 0.0};  // the last vertex is fully constrained (ENDS: or solved below, when it has unknowns)
     // (positions again, requested three vertices ahead of their use; a path shorter than the wavefront's longest joins late.
@@ -827,7 +821,7 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
   const unsigned long long pos_bad = __ballot(active && !pos_ok);
   // all eight paths present and of one length (MRS_TG_DUO_UNIFORM=0: no wavefront is treated as such)
   const bool uni_wave = uniform_loops && __ballot(active && S == __builtin_amdgcn_readfirstlane(S)) == ~0ull;
-  quad_wave_sync();
+  wave_lds_barrier();
   DUO_STAMP(3);
 
   double my_cost = 0.0;
@@ -1088,7 +1082,7 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
       xn[1] = fma(-L[tri(3, 1)], xn[3], fma(-L[tri(2, 1)], xn[2], z[1])) * Linv[1];
       xn[0] = fma(-L[tri(3, 0)], xn[3], fma(-L[tri(2, 0)], xn[2], fma(-L[tri(1, 0)], xn[1], z[0]))) * Linv[0];
     }
-    quad_wave_sync();  // (the forward loop's records -- L written by the lane of dimension 0 for the other three -- are read below)
+    wave_lds_barrier();  // (the forward loop's records -- L written by the lane of dimension 0 for the other three -- are read below)
     DUO_STAMP(8);
     // ---- backward through this side's half: x_v = L^-T (z - W x_{v+1}); coefficients and cost of local segment v
     double p_end;
@@ -1222,7 +1216,7 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
           double2* xbuf = reinterpret_cast<double2*>(chunk == 2 * kDuoPaths - 1 ? xlast : xrows);
 #pragma unroll
           for (int k = 0; k < kN; k += 2) xbuf[dim * (kN / 2) + k / 2] = make_double2(c[k], c[k + 1]);
-          quad_wave_sync();
+          wave_lds_barrier();
           double2* out4 = out - 4 * dim;  // (the segment's first pair + this lane's place in a row of four)
           // (all five reads ahead of the stores and of the branch: the assembly statements keep their order, and an LDS read
           // placed between two of them would be waited for there)
@@ -1240,7 +1234,7 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
 #pragma unroll
             for (int t = 0; t < kN / 2; ++t) store_coeff_pair(out4 + 4 * t, piece[t].x, piece[t].y);
           }
-          quad_wave_sync();  // (the next step's records are other rows; the buffer of the next step overlaps this one)
+          wave_lds_barrier();  // (the next step's records are other rows; the buffer of the next step overlaps this one)
         } else {
 #pragma unroll
           for (int k = 0; k < kN; k += 2) store_coeff_pair(out + k / 2, c[k], c[k + 1]);

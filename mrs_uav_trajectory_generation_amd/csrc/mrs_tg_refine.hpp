@@ -18,30 +18,13 @@
 // fused steps are explicit fma.
 #pragma once
 
-#include <cmath>
-#include <cstddef>
-#include <cstdint>
-
 #include "mrs_tg_constants.h"
 #include "mrs_tg_constants_dd.h"
-
-#if defined(__HIPCC__)
-#define MRS_TG_HD __host__ __device__
-#else
-#define MRS_TG_HD
-#endif
-#if defined(__clang__)
-#define MRS_TG_NO_CONTRACT _Pragma("clang fp contract(off)")
-#define MRS_TG_UNROLL _Pragma("unroll")
-#else
-#define MRS_TG_NO_CONTRACT
-#define MRS_TG_UNROLL
-#endif
+#include "mrs_tg_hd.hpp"
 
 namespace mrs_tg {
 namespace refine {
 
-constexpr int kN = 10, kB = 5, kD = 4;
 constexpr int kTri = kB * (kB + 1) / 2;
 constexpr int kRefineSteps = 3;
 // per vertex and lane: L (diagonal entries hold 1 / L_cc), W, z, two double-double iterates (hi[5], lo[5] each)
@@ -122,7 +105,9 @@ MRS_TG_HD inline void dd_fma_acc(dd& acc, const double (&a)[2], dd x) {
 }
 MRS_TG_HD inline dd dd_norm(dd x) { return quick_two_sum(x.hi, x.lo); }
 
-MRS_TG_HD inline double inv_sqrt_pivot(double x) {
+// 1 / sqrt of a Cholesky pivot, the device's way: NOT the correctly rounded one of the solve's backward pass
+// (vjp::inv_sqrt_pivot_exact) -- the correction solve only has to contract, the residual is what is exact
+MRS_TG_HD inline double inv_sqrt_pivot_rsq(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
   // v_rsq_f64 + one third-order step (rsqrt_refined of mrs_tg_device.hpp); a pivot <= 0 is rejected (variable left at 0)
   const double y = __builtin_amdgcn_rsq(x);
@@ -134,15 +119,7 @@ MRS_TG_HD inline double inv_sqrt_pivot(double x) {
 #endif
 }
 
-MRS_TG_HD constexpr int tri5(int r, int c) { return r * (r + 1) / 2 + c; }
-
-// Where the lane's per-vertex state lives: element e of vertex v at ws[(v * kWsPerVertex + e) * stride] (the kernel strides
-// by the number of lanes so that a wavefront's accesses coalesce; the host harness passes stride 1)
-struct LaneWs {
-  double* ws;
-  size_t stride;
-  MRS_TG_HD double& at(int v, int e) const { return ws[((size_t)v * kWsPerVertex + e) * stride]; }
-};
+using LaneWs = LaneWsT<kWsPerVertex>;
 
 // T^0..T^4 and T^(1-2d) * T^0..4 in double-double
 struct SegPowers {
@@ -161,7 +138,6 @@ MRS_TG_HD inline void seg_powers(double T, int d, SegPowers& P) {
   for (int k = 0; k < kB; ++k) P.sp[k] = dd_mul(s, P.tp[k]);
 }
 
-MRS_TG_HD inline bool slot_free(const uint8_t* mask, int v, int k) { return mask[(size_t)v * kB + k] == 0; }
 MRS_TG_HD inline double slot_value(const double* vals, int v, int k, int dim) { return vals[((size_t)v * kB + k) * kD + dim]; }
 
 MRS_TG_HD inline void load_iterate(const LaneWs& w, int v, int buf, dd (&x)[kB]) {
@@ -237,7 +213,7 @@ MRS_TG_HD inline void factor_lane(const uint8_t* mask, int v0, int S, int d, con
       double dsum = Sm[tri5(c, c)];
       MRS_TG_UNROLL
       for (int m = 0; m < c; ++m) dsum = fma(-L[tri5(c, m)], L[tri5(c, m)], dsum);
-      const double inv = inv_sqrt_pivot(dsum);
+      const double inv = inv_sqrt_pivot_rsq(dsum);
       L[tri5(c, c)] = fmax(dsum * inv, 1.0e-300);
       Linv[c] = inv;
       MRS_TG_UNROLL
@@ -294,12 +270,6 @@ MRS_TG_HD inline void load_factors(const LaneWs& w, int v, double (&L)[kTri], do
   for (int e = 0; e < kTri; ++e) L[e] = w.at(v, kWsL + e);
   MRS_TG_UNROLL
   for (int e = 0; e < kB * kB; ++e) W[e] = w.at(v, kWsW + e);
-}
-MRS_TG_HD inline unsigned free_bits(const uint8_t* mask, int v) {
-  unsigned f = 0u;
-  MRS_TG_UNROLL
-  for (int k = 0; k < kB; ++k) f |= slot_free(mask, v, k) ? (1u << k) : 0u;
-  return f;
 }
 
 MRS_TG_HD inline double residual_forward(const uint8_t* mask, int v0, int S, int d, const double* times, const LaneWs& w, int buf) {

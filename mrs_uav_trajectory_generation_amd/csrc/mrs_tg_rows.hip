@@ -51,12 +51,6 @@ __host__ __device__ constexpr int rows_path_doubles(int S) {
 
 // (LDS only: a fence over every address space also drains the global-memory counter -- s_waitcnt vmcnt(0) -- and the
 // wavefront then sits out the write latency of the coefficients it has just stored before it may add up its cost or sample)
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 #ifdef MRS_TG_ROWS_DEBUG
 __device__ double g_rows_debug[64 * 24 * 2];
 #endif
@@ -473,7 +467,7 @@ __device__ __forceinline__ void solve_rows_body(const BatchView& b, int d, int p
     pos_bad[tt] = __ballot(!pos_ok_lane);
     gen_any[tt] = __ballot(nonzero_lane);
   }
-  wave_lds_sync();
+  wave_lds_barrier();
   MRS_TG_PHASE_MARK(1);
 
   // TAIL = 2: mx_lds = [Smax][9] maxima of the first solve's trajectory, behind the sampler's areas
@@ -500,7 +494,7 @@ __device__ __forceinline__ void solve_rows_body(const BatchView& b, int d, int p
                        max(__builtin_amdgcn_readlane(rs.nact, 32), __builtin_amdgcn_readlane(rs.nact, 48)));
         rs.run(wmax);
       }
-      wave_lds_sync();
+      wave_lds_barrier();
       MRS_TG_PHASE_MARK(4);
 
       // ---- recover: coefficients c = A^-1 [d_i; d_{i+1}] and the cost share 0.5 c^T Q c per (segment, dimension)
@@ -564,7 +558,7 @@ __device__ __forceinline__ void solve_rows_body(const BatchView& b, int d, int p
         // T^(1 - 2d) = q[0] / T
         pcb[r] = quad_form * (sb[(size_t)i * kRSegRec + kRSegPow] * ti);
       }
-      wave_lds_sync();
+      wave_lds_barrier();
     }
     if (TAIL == 2 && pass == 0) {
       // ---- maxima of the trajectory just solved: which = 3 (k - 1) + group
@@ -603,7 +597,7 @@ __device__ __forceinline__ void solve_rows_body(const BatchView& b, int d, int p
       MRS_TG_PHASE_MARK(14);
       if (__ballot(moved) == 0ull) break;
       rs.load_constants();  // (again: held across the searches above they cost the registers the searches need)
-      wave_lds_sync();
+      wave_lds_barrier();
     }
   }
 
@@ -646,12 +640,12 @@ __device__ __forceinline__ void solve_rows_body(const BatchView& b, int d, int p
       double* sT = samp + (size_t)tt * ((size_t)Smax * (kD * kN + 1));
       const double* sb = lds + (size_t)tt * PS + (size_t)(Smax + 1) * kRVtxRec;
       for (int i = lane; i < S_t; i += 64) sT[i] = sb[(size_t)i * kRSegRec + kRSegT];
-      wave_lds_sync();
+      wave_lds_barrier();
       double* out = tail.samples ? tail.samples + (size_t)p_t * tail.sample_capacity * kD : nullptr;
       const int n = sample_path_walk(sT, sT + Smax, s_t, s_seg, S_t, tail.sampling_dt, tail.sample_capacity, out, tail.sample_acc,
                                      tail.sample_acc_n);
       if (lane == 0 && tail.n_samples) tail.n_samples[p_t] = n;
-      wave_lds_sync();
+      wave_lds_barrier();
     }
   }
   MRS_TG_PHASE_MARK(8);

@@ -154,9 +154,7 @@ __global__ __launch_bounds__(64) void sample_vjp_kernel(BatchView b, const doubl
     if (want_grad) {
       sink.close_segments(S);  // the last segment with samples, and zero rows for every segment behind it
       if (grad_times) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+        wave_lds_barrier();
         // dL/dT_i = -(s_{i+1} + (s_{i+2} + ...)): sampvjp::time_gradients, lane 0 writing
         double r = 0.0;
         for (int i = S - 1; i >= 0; --i) {
@@ -183,12 +181,8 @@ hipError_t launch_sample_vjp(const BatchView& b, const double* coeffs, const dou
     if (et != hipSuccess) return et;
   }
   const size_t lds = sizeof(double) * ((size_t)b.max_segments * (2 + kD * kN) + kSampleBuffer) + sizeof(unsigned short) * kSampleBuffer;
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
   const auto vjp = n_orders == 1 ? MRS_TG_KERNEL(sample_vjp_kernel<1>) : MRS_TG_KERNEL(sample_vjp_kernel<kSampleStateOrders>);
-  if (lds > 64 * 1024) {
-    hipError_t e = set_max_dynamic_lds(vjp, lds);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = prepare_dynamic_lds(vjp, lds); e != hipSuccess) return e;
   MRS_TG_LAUNCH_TIMED(vjp, dim3((unsigned)b.n_paths), dim3(64), lds, stream, b, coeffs, seg_times, dt, capacity, grad_states, status,
                       grad_coeffs, grad_times, sample_segment, sample_time, n_samples, acc_table, acc_n);
   return hipGetLastError();

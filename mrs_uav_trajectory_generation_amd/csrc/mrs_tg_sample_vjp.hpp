@@ -13,48 +13,26 @@
 // written with constant bounds and a predicate, so that the device keeps g[] and w[] in registers.
 #pragma once
 
-#include <cmath>
-#include <cstddef>
-
-#ifndef MRS_TG_HD
-#if defined(__HIPCC__)
-#define MRS_TG_HD __host__ __device__
-#else
-#define MRS_TG_HD
-#endif
-#endif
-#if defined(__clang__)
-#define MRS_TG_SVJP_NO_CONTRACT _Pragma("clang fp contract(off)")
-#define MRS_TG_SVJP_UNROLL _Pragma("unroll")
-#else
-#define MRS_TG_SVJP_NO_CONTRACT
-#define MRS_TG_SVJP_UNROLL
-#endif
+#include "mrs_tg_hd.hpp"
 
 namespace mrs_tg {
 namespace sampvjp {
 
-constexpr int kN = 10, kD = 4, kMaxOrders = 5;
+using mrs_tg::accumulate;
+using mrs_tg::kD;
+using mrs_tg::kMaxOrders;
+using mrs_tg::kN;
 constexpr int kCoeffElems = kD * kN;  // (dim, j) = (e / kN, e % kN)
-
-// j!/(j-k)! (an exact integer; 0 for k > j)
-MRS_TG_HD inline double falling_factorial(int j, int k) {
-  double v = 1.0;
-  MRS_TG_SVJP_UNROLL
-  for (int n = 0; n < kN; ++n)
-    if (n < k) v *= (double)(j - n);
-  return v;
-}
 
 // the weights an output element multiplies with, formed once: w[o] = j!/(j-o)! for the coefficient element j (o <= 4 used),
 // w[j] = j!/(j-o-1)! for the time element of order o
 MRS_TG_HD inline void coeff_weights(int j, double (&w)[kN]) {
-  MRS_TG_SVJP_UNROLL
-  for (int o = 0; o < kN; ++o) w[o] = falling_factorial(j, o);
+  MRS_TG_UNROLL
+  for (int o = 0; o < kN; ++o) w[o] = falling_factorial_predicated(j, o);
 }
 MRS_TG_HD inline void time_weights(int o, double (&w)[kN]) {
-  MRS_TG_SVJP_UNROLL
-  for (int j = 0; j < kN; ++j) w[j] = falling_factorial(j, o + 1);
+  MRS_TG_UNROLL
+  for (int j = 0; j < kN; ++j) w[j] = falling_factorial_predicated(j, o + 1);
 }
 
 // One sample's term of dL/dc[dim][j]: g[o] = G[k][o][dim], w = coeff_weights(j).  With omax = min(j, NO-1):
@@ -62,13 +40,13 @@ MRS_TG_HD inline void time_weights(int o, double (&w)[kN]) {
 // multiplication.
 template <int NO>
 MRS_TG_HD inline double coeff_term(int j, const double (&w)[kN], const double (&g)[NO], double t) {
-  MRS_TG_SVJP_NO_CONTRACT
+  MRS_TG_NO_CONTRACT
   const int omax = j < NO - 1 ? j : NO - 1;
   double acc = g[0] * w[0];
-  MRS_TG_SVJP_UNROLL
+  MRS_TG_UNROLL
   for (int o = 1; o < NO; ++o)
     if (o <= omax) acc = fma(acc, t, g[o] * w[o]);
-  MRS_TG_SVJP_UNROLL
+  MRS_TG_UNROLL
   for (int n = 0; n < kN - 1; ++n)
     if (n < j - omax) acc = acc * t;
   return acc;
@@ -77,23 +55,17 @@ MRS_TG_HD inline double coeff_term(int j, const double (&w)[kN], const double (&
 // One sample's term of the (o, dim) time partial: g = G[k][o][dim], c = the kN coefficients of dim in the sample's segment,
 // w = time_weights(o): g p_dim^(o+1)(t), Horner from j = 9 down to o + 1
 MRS_TG_HD inline double time_term(int o, const double (&w)[kN], const double* c, double g, double t) {
-  MRS_TG_SVJP_NO_CONTRACT
+  MRS_TG_NO_CONTRACT
   double acc = w[kN - 1] * c[kN - 1];
-  MRS_TG_SVJP_UNROLL
+  MRS_TG_UNROLL
   for (int j = kN - 2; j >= 1; --j)
     if (j >= o + 1) acc = fma(acc, t, w[j] * c[j]);
   return g * acc;
 }
 
-// every accumulator: acc <- acc + term, from 0.0 at the segment's first sample
-MRS_TG_HD inline double accumulate(double acc, double term) {
-  MRS_TG_SVJP_NO_CONTRACT
-  return acc + term;
-}
-
 // dL/dT from the segments' sums s[0 .. S): out[i] = -(s[i+1] + (s[i+2] + ...)), from the last segment downwards
 MRS_TG_HD inline void time_gradients(const double* s, int S, double* out) {
-  MRS_TG_SVJP_NO_CONTRACT
+  MRS_TG_NO_CONTRACT
   double r = 0.0;
   for (int i = S - 1; i >= 0; --i) {
     out[i] = 0.0 - r;

@@ -9,24 +9,6 @@
 
 namespace mrs_tg {
 
-__device__ __forceinline__ double wrap_heading(double y) {
-  const double two_pi_hi = 6.283185307179586232e+00, two_pi_lo = 2.449293598294706414e-16;
-  const double kf = rint(y * 1.591549430918953456e-01);
-  return fma(-kf, two_pi_lo, fma(-kf, two_pi_hi, y));
-}
-
-// j!/(j-k)!, a compile-time constant wherever j and k are
-__host__ __device__ constexpr double falling_factorial(int j, int k) {
-  double v = 1.0;
-  for (int n = 0; n < k; ++n) v *= (double)(j - n);
-  return v;
-}
-
-__device__ __forceinline__ double lane_value(double v, int src) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), src), hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-  return __hiloint2double(hi, lo);
-}
-
 // The walk and the evaluation are separate passes.  The walk produces, chunk by chunk, the time in its segment of every
 // sample (lane j of a chunk holds the j-th one) and parks it with its segment index in an LDS buffer; nothing else sits
 // on the walk's dependent chain.  When the buffer is full (or the walk has ended) all buffered samples are evaluated at
@@ -106,21 +88,15 @@ __device__ __forceinline__ int sample_path_walk(const double* s_T, const double*
   auto flush = [&](int upto) {
     if constexpr (!kEvaluates) {
       if (!sink->active) return;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+      wave_lds_barrier();
       const int end = upto < capacity ? upto : capacity;
       if (end > n_flushed) sink->flush(s_t, s_seg, n_flushed, end - n_flushed);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+      wave_lds_barrier();
       return;
     }
     if (!out) return;
     // (the fences order LDS only: over every address space they wait for the samples stored by the previous flush as well)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    wave_lds_barrier();
     for (int e = n_flushed + lane; e < upto; e += 64) {
       if (e >= capacity) break;
       const double tj = s_t[e - n_flushed];
@@ -149,9 +125,7 @@ __device__ __forceinline__ int sample_path_walk(const double* s_T, const double*
         }
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    wave_lds_barrier();
   };
   if (i < S) {
     double tin = 0.0;  // (t_start = 0: the walk enters the first segment of positive length at its start)

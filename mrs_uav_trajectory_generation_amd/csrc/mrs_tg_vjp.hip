@@ -47,7 +47,7 @@ __global__ __launch_bounds__(64) void vjp_kernel(BatchView b, int d, const uint8
   if (!(status[pr.p] > 0)) {  // (the four lanes of a path agree) zero rows for a path the forward did not solve
     if (grad_vals)
       for (int v = 0; v <= pr.S; ++v)
-        for (int k = 0; k < vjp::kB; ++k) grad_vals[((size_t)(pr.v0 + v) * vjp::kB + k) * kD + dim] = 0.0;
+        for (int k = 0; k < kB; ++k) grad_vals[((size_t)(pr.v0 + v) * kB + k) * kD + dim] = 0.0;
     if (grad_times && dim == 0)
       for (int i = 0; i < pr.S; ++i) grad_times[pr.s0 + i] = 0.0;
     return;

@@ -74,7 +74,7 @@ __device__ __forceinline__ void row0_sum(double (&v)[N]) {
 #pragma unroll
   for (int n = 0; n < N; ++n) v[n] += dpp_move<0x140>(v[n]);
 #pragma unroll
-  for (int n = 0; n < N; ++n) v[n] = row_value(v[n], 0);
+  for (int n = 0; n < N; ++n) v[n] = lane_value(v[n], 0);
 }
 
 // a condition that is the same in every lane, as a scalar (v_cmp into an SGPR pair + s_cmp: no round trip through a VGPR)
@@ -262,7 +262,7 @@ __device__ __forceinline__ double wave_evaluate(const double* lds, const WaveRol
   qfk += dpp_move<0x4E>(qfk);
   Jk = guarded_cost(Jk, qfk, w.k == 0);
   if (w.src >= 0 && Jk == kUnreliableCost) reinterpret_cast<int*>(const_cast<double*>(lds) + kWvFlags)[0] = 1;
-  const double J0 = row_value(Jk, 0);  // lanes 0..3: the left half of x, joined with its right half
+  const double J0 = lane_value(Jk, 0);  // lanes 0..3: the left half of x, joined with its right half
   if (w.src >= 0 && dim == 0 && w.k >= 1) grad[w.k - 1] = (Jk - J0) / kGradStep;
   return J0;
 }

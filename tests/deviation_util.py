@@ -2,39 +2,18 @@
 fixtures, the CPU harness of csrc/mrs_tg_deviation.hpp, a Python restatement of the scan over the oracle's
 mto_dist_from_segment, the small shapes built to break the kernel, and a float64 torch restatement with given cursors."""
 import ctypes as C
-import json
+import functools
 import os
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURES = os.path.join(ROOT, "tests", "golden", "deviation_cases.json")
-HARNESS = os.path.join(ROOT, "tests", "host", "deviation_harness.cpp")
+from tests import host_harness as hh
+
+FIXTURES = os.path.join(hh.GOLDEN, "deviation_cases.json")
+load_cases = functools.partial(hh.load_cases, "deviation_cases.json")
+build_harness = functools.partial(hh.build, "deviation_harness.cpp")   # (tmp_path, sanitize=False)
 EPS = 2.0 ** -52
 ADVANCE = 0.05
-
-
-def load_cases():
-    with open(FIXTURES) as f:
-        return json.load(f)["cases"]
-
-
-def build_harness(tmp_path, sanitize=False):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no C++ compiler for tests/host/deviation_harness.cpp")
-    exe = str(tmp_path / ("deviation_harness_san" if sanitize else "deviation_harness"))
-    flags = ["-std=c++17", "-ffp-contract=off"]
-    flags += ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-    subprocess.run([cxx] + flags + [HARNESS, "-o", exe], check=True, capture_output=True, text=True)
-    return exe
-
-
-def _fmt(a):
-    return " ".join(repr(float(x)) for x in np.asarray(a, dtype=np.float64).reshape(-1))
 
 
 def problem(waypoints, samples, n_samples=None, capacity=None, first_segment=1, status=1, upstream=None):
@@ -64,12 +43,9 @@ def run_harness(exe, problems, env=None):
         S, m = p["waypoints"].shape[0] - 1, min(p["n_samples"], p["capacity"])
         k = scanned_rows(p)
         lines.append("%d %d %d %d %d %s %s %s\n" % (S, p["n_samples"], p["capacity"], p["first_segment"], p["status"],
-                                                    _fmt(p["waypoints"]), _fmt(p["samples"][:max(m, 0)]), _fmt(p["upstream"][:k])))
-    r = subprocess.run([exe], input="".join(lines), capture_output=True, text=True, timeout=900,
-                       env=dict(os.environ, **(env or {})))
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-    out = r.stdout.strip("\n").split("\n") if problems else []
-    assert len(out) == len(problems), (len(out), r.stderr[-2000:])
+                                                    hh.fmt(p["waypoints"]), hh.fmt(p["samples"][:max(m, 0)]),
+                                                    hh.fmt(p["upstream"][:k])))
+    out = hh.run(exe, lines, len(problems), timeout=900, env=env)
     res = []
     for p, line in zip(problems, out):
         S, k = p["waypoints"].shape[0] - 1, scanned_rows(p)

@@ -1,24 +1,17 @@
 """Shared helpers of the tests of the evaluation at caller-given times (test_evaluate_host.py, test_gpu_evaluate.py): the
 fixtures, the CPU harness of csrc/mrs_tg_evaluate.hpp, and a plain-Python restatement of the locate rule."""
-import json
+import functools
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURES = os.path.join(ROOT, "tests", "golden", "evaluate_cases.json")
-COMPOSITE = os.path.join(ROOT, "tests", "golden", "evaluate_composite_cases.json")
-HARNESS = os.path.join(ROOT, "tests", "host", "evaluate_harness.cpp")
+from tests import host_harness as hh
+
+ROOT = hh.ROOT
+load_cases = functools.partial(hh.load_cases, "evaluate_cases.json")
+load_composite_cases = functools.partial(hh.load_cases, "evaluate_composite_cases.json")
+build_harness = functools.partial(hh.build, "evaluate_harness.cpp")   # (tmp_path, sanitize=False)
 N, D, ORDERS = 10, 4, 5
-
-
-def load_cases():
-    with open(FIXTURES) as f:
-        return json.load(f)["cases"]
 
 
 def gradient_cases():
@@ -27,11 +20,6 @@ def gradient_cases():
 
 def forward_cases():
     return [c for c in load_cases() if c.get("forward")]
-
-
-def load_composite_cases():
-    with open(COMPOSITE) as f:
-        return json.load(f)["cases"]
 
 
 def query_array(case):
@@ -62,21 +50,6 @@ def locate(seg_times, t):
     return stop, t - start
 
 
-def build_harness(tmp_path, sanitize=False):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no C++ compiler for tests/host/evaluate_harness.cpp")
-    exe = str(tmp_path / ("evaluate_harness_san" if sanitize else "evaluate_harness"))
-    flags = ["-std=c++17", "-ffp-contract=off"]
-    flags += ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-    subprocess.run([cxx] + flags + [HARNESS, "-o", exe], check=True, capture_output=True, text=True)
-    return exe
-
-
-def _fmt(a):
-    return " ".join(repr(float(x)) for x in np.asarray(a, dtype=np.float64).reshape(-1))
-
-
 def run_harness(exe, problems, env=None):
     """problems: dicts with seg_times [S], coeffs [S][4][10], query_times [Q], n_orders, grad_states [Q][n_orders][4] (default
     zeros), optional status (default 1).
@@ -87,13 +60,9 @@ def run_harness(exe, problems, env=None):
         S, Q, no = len(p["seg_times"]), len(p["query_times"]), p["n_orders"]
         G = p.get("grad_states")
         G = np.zeros((Q, no, D)) if G is None else np.asarray(G, dtype=np.float64).reshape(Q, no, D)
-        lines.append("%d %d %d %d %s %s %s %s\n" % (S, no, Q, p.get("status", 1), _fmt(p["seg_times"]), _fmt(p["coeffs"]),
-                                                     _fmt(p["query_times"]), _fmt(G)))
-    r = subprocess.run([exe], input="".join(lines), capture_output=True, text=True, timeout=900,
-                       env=dict(os.environ, **(env or {})))
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-    out = r.stdout.strip("\n").split("\n") if problems else []
-    assert len(out) == len(problems), (len(out), r.stderr[-2000:])
+        lines.append("%d %d %d %d %s %s %s %s\n" % (S, no, Q, p.get("status", 1), hh.fmt(p["seg_times"]), hh.fmt(p["coeffs"]),
+                                                     hh.fmt(p["query_times"]), hh.fmt(G)))
+    out = hh.run(exe, lines, len(problems), timeout=900, env=env)
     res = []
     for p, line in zip(problems, out):
         S, Q, no = len(p["seg_times"]), len(p["query_times"]), p["n_orders"]

@@ -1,41 +1,17 @@
 """Shared helpers of the segment-maxima backward-pass tests (test_maxima_vjp_host.py, test_gpu_maxima_vjp.py): the fixtures,
 the CPU harness of csrc/mrs_tg_maxima_vjp.hpp, and torch restatements of |p^(k)(t*)| and of the feasibility scaling."""
-import json
-import os
-import shutil
-import subprocess
+import functools
 
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURES = os.path.join(ROOT, "tests", "golden", "maxima_vjp_cases.json")
-COMPOSITE = os.path.join(ROOT, "tests", "golden", "maxima_vjp_composite_cases.json")
-HARNESS = os.path.join(ROOT, "tests", "host", "maxima_vjp_harness.cpp")
+from tests import host_harness as hh
+
+load_cases = functools.partial(hh.load_cases, "maxima_vjp_cases.json")
+load_composite_cases = functools.partial(hh.load_cases, "maxima_vjp_composite_cases.json")
+build_harness = functools.partial(hh.build, "maxima_vjp_harness.cpp")   # (tmp_path, sanitize=False)
 N, D = 10, 4
 GROUPS = ((0, 1), (2,), (3,))
 GRID = 32   # the forward search's grid cells (kGridCells, mrs_tg_maxima.hpp)
-
-
-def load_cases():
-    with open(FIXTURES) as f:
-        return json.load(f)["cases"]
-
-
-def load_composite_cases():
-    with open(COMPOSITE) as f:
-        return json.load(f)["cases"]
-
-
-def build_harness(tmp_path, sanitize=False):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no C++ compiler for tests/host/maxima_vjp_harness.cpp")
-    exe = str(tmp_path / ("maxima_vjp_harness_san" if sanitize else "maxima_vjp_harness"))
-    flags = ["-std=c++17", "-ffp-contract=off"]
-    flags += ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-    subprocess.run([cxx] + flags + [HARNESS, "-o", exe], check=True, capture_output=True, text=True)
-    return exe
 
 
 def cell_of(tau):
@@ -56,12 +32,8 @@ def run_harness(exe, problems, env=None):
     for p in problems:
         vals = list(np.asarray(p["coeffs"], dtype=np.float64).reshape(-1)) + [float(p["T"])] + \
             list(np.asarray(p["seeds"], dtype=np.float64).reshape(-1))
-        lines.append(" ".join(repr(float(x)) for x in vals) + "\n")
-    r = subprocess.run([exe], input="".join(lines), capture_output=True, text=True, timeout=600,
-                       env=dict(os.environ, **(env or {})))
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-    out = r.stdout.strip().split("\n")
-    assert len(out) == len(problems), (len(out), r.stderr[-2000:])
+        lines.append(hh.fmt(vals) + "\n")
+    out = hh.run(exe, lines, len(problems), env=env)
     res = []
     for line in out:
         x = np.array([float(v) for v in line.split()])

@@ -1,43 +1,15 @@
 """Shared helpers of the sampler's backward-pass tests (test_sample_vjp_host.py, test_gpu_sample_vjp.py): the fixtures, the
 CPU harness of csrc/mrs_tg_sample_vjp.hpp, and a torch restatement of the sampled states at given (segment, time) pairs."""
-import json
-import os
-import shutil
-import subprocess
+import functools
 
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURES = os.path.join(ROOT, "tests", "golden", "sample_vjp_cases.json")
-COMPOSITE = os.path.join(ROOT, "tests", "golden", "sample_vjp_composite_cases.json")
-HARNESS = os.path.join(ROOT, "tests", "host", "sample_vjp_harness.cpp")
+from tests import host_harness as hh
+
+load_cases = functools.partial(hh.load_cases, "sample_vjp_cases.json")
+load_composite_cases = functools.partial(hh.load_cases, "sample_vjp_composite_cases.json")
+build_harness = functools.partial(hh.build, "sample_vjp_harness.cpp")   # (tmp_path, sanitize=False)
 N, D, ORDERS = 10, 4, 5
-
-
-def load_cases():
-    with open(FIXTURES) as f:
-        return json.load(f)["cases"]
-
-
-def load_composite_cases():
-    with open(COMPOSITE) as f:
-        return json.load(f)["cases"]
-
-
-def build_harness(tmp_path, sanitize=False):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no C++ compiler for tests/host/sample_vjp_harness.cpp")
-    exe = str(tmp_path / ("sample_vjp_harness_san" if sanitize else "sample_vjp_harness"))
-    flags = ["-std=c++17", "-ffp-contract=off"]
-    flags += ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-    subprocess.run([cxx] + flags + [HARNESS, "-o", exe], check=True, capture_output=True, text=True)
-    return exe
-
-
-def _fmt(a):
-    return " ".join(repr(float(x)) for x in np.asarray(a, dtype=np.float64).reshape(-1))
 
 
 def run_harness(exe, problems, env=None):
@@ -49,12 +21,8 @@ def run_harness(exe, problems, env=None):
         S = len(p["seg_times"])
         G = np.asarray(p["grad_states"], dtype=np.float64).reshape(-1, p["n_orders"], D)
         lines.append("%d %d %d %d %r %s %s %d %s\n" % (S, p["n_orders"], p["capacity"], p.get("status", 1), float(p["dt"]),
-                                                        _fmt(p["seg_times"]), _fmt(p["coeffs"]), G.shape[0], _fmt(G)))
-    r = subprocess.run([exe], input="".join(lines), capture_output=True, text=True, timeout=600,
-                       env=dict(os.environ, **(env or {})))
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-    out = r.stdout.strip().split("\n")
-    assert len(out) == len(problems), (len(out), r.stderr[-2000:])
+                                                        hh.fmt(p["seg_times"]), hh.fmt(p["coeffs"]), G.shape[0], hh.fmt(G)))
+    out = hh.run(exe, lines, len(problems), env=env)
     res = []
     for p, line in zip(problems, out):
         S = len(p["seg_times"])

@@ -11,9 +11,7 @@ and the per-lane refinement routine (csrc/mrs_tg_refine.hpp) compiled for the CP
     refuses such a step, the lane keeps its previous iterate, and the result is no worse than the start.
 """
 import importlib.util
-import json
 import os
-import shutil
 import subprocess
 from fractions import Fraction
 
@@ -21,11 +19,10 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle as po
-from tests import util
+from tests import host_harness, util
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mrs_uav_trajectory_generation_amd", "csrc")
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 GUARD_CASE = "guard_1em4_between_10s"
 TOL_REFINED = 1e-11
 
@@ -38,9 +35,7 @@ def _gen():
     return mod
 
 
-def _cases(name):
-    with open(os.path.join(GOLDEN, name)) as f:
-        return json.load(f)["cases"]
+_cases = host_harness.load_cases
 
 
 def test_generator_reproduces_both_headers(tmp_path):
@@ -96,16 +91,6 @@ def test_refine_fixtures_agree_with_the_113_bit_route():
         assert e < 1e-12, (case["name"], e)
 
 
-def _harness(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no C++ compiler for tests/host/refine_harness.cpp")
-    exe = str(tmp_path / "refine_harness")
-    subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", os.path.join(ROOT, "tests", "host", "refine_harness.cpp"),
-                    "-o", exe], check=True, cwd=ROOT, timeout=300)
-    return exe
-
-
 def _refine_on_cpu(exe, d, m, v, t, coeffs):
     text = "%d %d\n" % (d, len(t))
     text += " ".join(repr(float(x)) for x in t) + "\n"
@@ -119,7 +104,7 @@ def _refine_on_cpu(exe, d, m, v, t, coeffs):
 
 
 def test_refinement_routine_on_the_cpu_reaches_the_60_digit_solutions(tmp_path):
-    exe = _harness(tmp_path)
+    exe = host_harness.build("refine_harness.cpp", tmp_path)
     worst = 0.0
     for case in _cases("linear_qp_cases.json") + _cases("refine_cases.json"):
         d, m, v, t, _ = util.case_arrays(case)

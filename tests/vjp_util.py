@@ -4,39 +4,16 @@ csrc/mrs_tg_vjp.hpp, and a dense float64 torch-autograd restatement of the fixed
 The restatement solves the whole masked KKT system of a path at once (fixed rows replaced by identity rows, A(T) and Q(T)
 formed from their definitions, torch.linalg.solve) and lets torch's autograd differentiate L = sum G . coeffs + g * cost: an
 independent route to the same gradients, without the block elimination or the adjoint formulas of the kernel."""
-import json
+import functools
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURES = os.path.join(ROOT, "tests", "golden", "vjp_cases.json")
-HARNESS = os.path.join(ROOT, "tests", "host", "vjp_harness.cpp")
+from tests import host_harness as hh
+
+load_cases = functools.partial(hh.load_cases, "vjp_cases.json")
+build_harness = functools.partial(hh.build, "vjp_harness.cpp")   # (tmp_path, sanitize=False)
 N, D, B = 10, 4, 5
-
-
-def load_cases():
-    with open(FIXTURES) as f:
-        return json.load(f)["cases"]
-
-
-def build_harness(tmp_path, sanitize=False):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no C++ compiler for tests/host/vjp_harness.cpp")
-    exe = str(tmp_path / ("vjp_harness_san" if sanitize else "vjp_harness"))
-    flags = ["-std=c++17", "-ffp-contract=off"]
-    flags += ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-    subprocess.run([cxx] + flags + [HARNESS, "-o", exe], check=True, capture_output=True, text=True)
-    return exe
-
-
-def _fmt(a):
-    return " ".join(repr(float(x)) for x in np.asarray(a, dtype=np.float64).reshape(-1))
 
 
 def run_harness(exe, problems, env=None):
@@ -47,13 +24,9 @@ def run_harness(exe, problems, env=None):
         S = len(p["times"])
         G = p["G"]
         lines.append("%d %d\n%s\n%s\n%s\n%s\n%d\n%s\n%r\n" % (
-            p["d"], S, _fmt(p["times"]), " ".join(str(int(x)) for x in np.asarray(p["mask"]).reshape(-1)), _fmt(p["vals"]),
-            _fmt(p["coeffs"]), 0 if G is None else 1, _fmt(np.zeros((S, D, N)) if G is None else G), float(p["g"])))
-    r = subprocess.run([exe], input="".join(lines), capture_output=True, text=True, timeout=600,
-                       env=dict(os.environ, **(env or {})))
-    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
-    out = r.stdout.strip().split("\n")
-    assert len(out) == 2 * len(problems), (len(out), r.stderr[-2000:])
+            p["d"], S, hh.fmt(p["times"]), " ".join(str(int(x)) for x in np.asarray(p["mask"]).reshape(-1)), hh.fmt(p["vals"]),
+            hh.fmt(p["coeffs"]), 0 if G is None else 1, hh.fmt(np.zeros((S, D, N)) if G is None else G), float(p["g"])))
+    out = hh.run(exe, lines, 2 * len(problems), env=env)
     res = []
     for i, p in enumerate(problems):
         S = len(p["times"])
