@@ -130,7 +130,7 @@ __device__ __forceinline__ int sample_path_walk(const double* s_T, const double*
   if (i < S) {
     double tin = 0.0;  // (t_start = 0: the walk enters the first segment of positive length at its start)
     double Ti = s_T[i];
-    while (true) {  // trajectory.cpp:131-150, one chunk per iteration
+    while (true) {  // trajectory.cpp:131-150, one chunk per iteration (chunk_model, tests/sampler_walk_util.py, restates this loop: edit both)
       if (n >= n_total) break;
       bool past_end = false;
       while (tin > Ti) {  // carry the remainder into the next segment(s)
