@@ -60,6 +60,15 @@ inline bool duo_uniform() { return env_flag("MRS_TG_DUO_UNIFORM", true); }
 // write-through stores, which leave no dirty lines in L2 for the end of the dispatch to write back; same bytes either way).  A
 // TEST knob like the one above, not an interface: tests/test_gpu_duo_store_through.py holds the two to the same bits.  Every call.
 inline bool duo_store_through() { return env_flag("MRS_TG_DUO_STORE_THROUGH", true); }
+// MRS_TG_DUO_LEAN=0: the grouped two-sided dispatch never takes its lean instantiation (default 1: a batch whose paths all have
+// one even length of at least 4 segments and fill every wavefront -- uniform_S, n_paths % 8 == 0 -- with both knobs above on runs
+// solve_duo_group_kernel<WP, true>, the same arithmetic without the bookkeeping of partly filled or mixed wavefronts; same bits
+// either way).  A TEST knob like the two above: tests/test_gpu_duo_lean.py holds the two to the same bits.  Every call.
+inline bool duo_lean() { return env_flag("MRS_TG_DUO_LEAN", true); }
+// MRS_TG_TRACE_INSTANTIATIONS=1: the kernel trace and mrs_tg_plan_explain spell an instantiation that otherwise goes by its
+// family's name -- the lean one above reads solve_duo_group_kernel<true, true> instead of solve_duo_group_kernel<true> (default
+// 0: the names are interface and stay).  A TEST knob: it lets a test tell which instantiation ran.  Every call.
+inline bool trace_instantiations() { return env_flag("MRS_TG_TRACE_INSTANTIATIONS", false); }
 // MRS_TG_TILE_MAX_PATHS=n: largest batch the tile kernel takes (scripts/sweep_tile.sh); not set: `by_shape`.  Every call.
 inline long long tile_max_paths(long long by_shape) { return env_ll("MRS_TG_TILE_MAX_PATHS", by_shape); }
 

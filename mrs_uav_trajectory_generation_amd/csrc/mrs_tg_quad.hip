@@ -124,6 +124,23 @@ __device__ __forceinline__ void store_coeff_pair_through(double2* dst, double2 v
 #endif
 }
 
+// The same store with its address as a wave-uniform base and a 32-bit byte offset per lane (the lean instantiation of the grouped
+// kernel: the base is the wavefront's first segment, so no 64-bit address is formed per lane and step).  Same bytes, same place.
+template <int BYTES>
+__device__ __forceinline__ void store_coeff_pair_through(const double* base, unsigned lane_bytes, double2 v) {
+  typedef int int4v __attribute__((ext_vector_type(4)));
+  const int4v bits = __builtin_bit_cast(int4v, v);
+#if MRS_TG_DUO_THROUGH_FORM == 3
+  __builtin_nontemporal_store(bits, reinterpret_cast<int4v*>(reinterpret_cast<char*>(const_cast<double*>(base)) + lane_bytes + BYTES));
+#else
+#if MRS_TG_DUO_THROUGH_FORM == 2
+  asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 sc0 sc1\n\ts_nop 1" ::"v"(lane_bytes), "v"(bits), "s"(base), "i"(BYTES));
+#else
+  asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 sc1\n\ts_nop 1" ::"v"(lane_bytes), "v"(bits), "s"(base), "i"(BYTES));
+#endif
+#endif
+}
+
 __device__ __forceinline__ double quad_sum(double v) {  // over the four lanes of a quad, to all of them
   v += dpp_move<0xB1>(v);
   v += dpp_move<0x4E>(v);
@@ -692,7 +709,14 @@ __device__ __forceinline__ void duo_finish(double my_cost, bool active, unsigned
 // whether this call's are (MRS_TG_DUO_STORE_THROUGH).  On for the grouped dispatch, whose coefficients nothing on the device
 // reads next; off for the single launch: the sampling, the maxima or a second solve read its coefficients right behind it, and a
 // written-through line does not stay in L2.
-template <bool WP, bool MOVING = false, bool THROUGH = false>
+// LEAN: the batch is WHOLE-UNIFORM -- every path has the same even number of segments, at least 4, and the paths fill every
+// wavefront (the launcher's rule: launch_solve_quad_group) -- with the uniform loops and the write-through stores on.  The same
+// arithmetic in the same order (the lambdas and step bodies below are written once), without what serves partly filled or mixed
+// wavefronts: no activity predicate, the path's place is arithmetic, the forward pass is the uniform loop alone, and the backward
+// loop walks its LDS addresses by the per-lane stride, reads its positions unclamped and has the one store flavour -- exchange,
+// then write-through -- that every step of an even length from 4 on takes.  The plainness test, the general step, cost and status
+// are as in the other instantiation.
+template <bool WP, bool MOVING = false, bool THROUGH = false, bool LEAN = false>
 __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const uint8_t* __restrict__ mask,
                                                const double* __restrict__ vals, const double* seg_times,
                                                double* __restrict__ coeffs, int32_t* __restrict__ status,
@@ -702,8 +726,9 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
   extern __shared__ double lds[];
   const int lane = threadIdx.x, pl = lane >> 3, side = (lane >> 2) & 1, dim = lane & 3, l8 = lane & 7;
   const int q = block * kDuoPaths + pl;
-  const bool active = q < b.n_paths;
-  const PathRef pr = path_at(b, active ? q : b.n_paths - 1);
+  static_assert(!LEAN || THROUGH, "the lean instantiation has the write-through flavour only");
+  const bool active = LEAN || q < b.n_paths;
+  const PathRef pr = LEAN ? PathRef{q, q * b.uniform_S, b.uniform_S, q * b.uniform_S + q} : path_at(b, active ? q : b.n_paths - 1);
   const int S = pr.S;
   const int Smax = b.max_segments;
   double* rec0 = lds;
@@ -742,10 +767,18 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
   const int v_end = (l8 & 1) ? S : 0;
   const unsigned f_end = mask_bits(v_end);
   double av[kHalf * kD];
+  // LEAN: the sixteen values of a path's end vertex spread over the four lanes of the eight that read it -- lane l8 has
+  // derivative slot 1 + l8 / 2 -- and reduced below (nz is a sum of absolute values compared with zero: its order is free)
+  const int k_end = 1 + (l8 >> 1);
   {
     const double* vrow = vals + (size_t)(pr.v0 + v_end) * kHalf * kD;
+    if constexpr (LEAN) {
 #pragma unroll
-    for (int e = kD; e < kHalf * kD; ++e) av[e] = fabs(vrow[e]);
+      for (int e = 0; e < kD; ++e) av[e] = fabs(vrow[k_end * kD + e]);
+    } else {
+#pragma unroll
+      for (int e = kD; e < kHalf * kD; ++e) av[e] = fabs(vrow[e]);
+    }
   }
   const int opt_st = (scaling && active) ? tail.opt_status[pr.p] : 0;
   auto trip = [&](int base) {               // sixteen segments and vertices of every path: two of each per lane
@@ -799,12 +832,20 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
   // assume loads of the previous trip in flight and waits for the end vertices' values before it issues the positions' loads)
   trip(0);
   for (int base = 16; base <= Smax; base += 16) trip(base);
+  double nz_end = 0.0;
+  if constexpr (LEAN) {
+    nz_end = ((f_end >> k_end) & 1u) ? (av[0] + av[1]) + (av[2] + av[3]) : 0.0;
+    nz_end += dpp_move<0x4E>(nz_end);  // (lane ^ 2, then lane ^ 4: the four lanes of the eight with this lane's end vertex)
+    nz_end += xor4(nz_end);
+  }
   if (active && l8 < 2) {  // the end vertices: fully constrained, at rest (MOVING: the start vertex may be in motion)
-    double nz = 0.0;
+    double nz = nz_end;
+    if constexpr (!LEAN) {
 #pragma unroll
-    for (int k = 1; k < kHalf; ++k)
+      for (int k = 1; k < kHalf; ++k)
 #pragma unroll
-      for (int e = 0; e < kD; ++e) nz += ((f_end >> k) & 1u) ? av[k * kD + e] : 0.0;
+        for (int e = 0; e < kD; ++e) nz += ((f_end >> k) & 1u) ? av[k * kD + e] : 0.0;
+    }
     if (MOVING && l8 == 0) {
       moving_path = nz != 0.0;
       nz = 0.0;
@@ -820,7 +861,7 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
   const bool plain_wave = __ballot(active && !ok) == 0ull;
   const unsigned long long pos_bad = __ballot(active && !pos_ok);
   // all eight paths present and of one length (MRS_TG_DUO_UNIFORM=0: no wavefront is treated as such)
-  const bool uni_wave = uniform_loops && __ballot(active && S == __builtin_amdgcn_readfirstlane(S)) == ~0ull;
+  const bool uni_wave = LEAN || (uniform_loops && __ballot(active && S == __builtin_amdgcn_readfirstlane(S)) == ~0ull);
   wave_lds_barrier();
   DUO_STAMP(3);
 
@@ -876,7 +917,8 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
     // ragged one).  Same operations in the same order on the same numbers: the same bits (tests/test_gpu_duo_bits.py).
     // (The backward loop has no uniform twin: its step as one straight block, or a second copy of it, makes the compiler park
     // some fifty of the step's constants in lanes of a VGPR and fetch them with v_readlane -- 410-450 instructions instead of
-    // 366; and that loop is bound by its stores, not its instructions: DESIGN.md section 4.)
+    // 366; and that loop was bound by its stores, not its instructions: DESIGN.md section 4.  That is about two copies in ONE
+    // kernel: the LEAN instantiation holds the uniform form of the step alone -- 340 instructions, no v_readlane: item 6 there.)
     // local segment 0: the end vertex is fully constrained, the state moves to local vertex 1
     auto fwd_first = [&](const double (&p2)[9], double dp, const double (&f0)[kNB]) {
 #pragma unroll
@@ -1015,6 +1057,7 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
       p_cur = pos(ids_now(), 0);
       DUO_STAMP(4);
     }
+    if constexpr (!LEAN)  // (an even uniform length: both sides have every step, the uniform loop has taken them all)
     for (int i = i_lo; i < i_hi; ++i) {
       const LaneIds id = ids_now();
       const bool on = active && i < side_len(id.side);
@@ -1086,18 +1129,37 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
     DUO_STAMP(8);
     // ---- backward through this side's half: x_v = L^-T (z - W x_{v+1}); coefficients and cost of local segment v
     double p_end;
-    {
+    // LEAN: the places of local vertex v's record and position, of local segment v's time (doubles from the start of LDS) and
+    // of its coefficients (bytes from the wavefront's first segment) walk by the per-lane stride, as the forward loop's do
+    int at_rec = 0, at_pos = 0, at_time = 0;
+    unsigned at_out = 0;
+    const int v_top = LEAN ? M1 - 1 : Mmx - 1;
+    if constexpr (LEAN) {
+      const LaneIds id = ids_now();
+      p_end = pbuf[(M0 * kD + id.dim) * kDuoPaths + id.pl];  // (the middle vertex: S / 2 from either end)
+      const int ov = id.side ? S_u - v_top : v_top, os = id.side ? ov - 1 : ov;  // original vertex and segment of local v_top
+      at_rec = (ov - 1) * kQdRec * kDuoPaths + id.pl;
+      at_pos = (int)(pbuf - lds) + (ov * kD + id.dim) * kDuoPaths + id.pl;
+      at_time = (int)(tbuf - lds) + os * kDuoPaths + id.pl;
+      at_out = (unsigned)(((id.pl * S_u + os) * kD * kN + 2 * id.dim) * (int)sizeof(double));
+    } else {
       const LaneIds id = ids_now();
       p_end = pos(id, side_len(id.side));
     }
-    for (int v = Mmx - 1; v >= 0; --v) {
+    for (int v = v_top; v >= 0; --v) {
       const LaneIds id = ids_now();
       const int side = id.side, dim = id.dim, pl = id.pl;  // (this iteration's: see lane_now)
-      const bool on = active && v < side_len(side);
+      const bool on = LEAN || (active && v < side_len(side));
       double x[kNB] = {0.0, 0.0, 0.0, 0.0};
-      const double p_start = pos(id, v);
+      double p_start, T_now = 0.0;
+      if constexpr (LEAN) {
+        p_start = lds[at_pos];
+        T_now = lds[at_time];
+      } else {
+        p_start = pos(id, v);
+      }
       if (on && v >= 1) {
-        const double* rec = rec0 + (size_t)(overt(side, v) - 1) * kQdRec * kDuoPaths + pl;
+        const double* rec = LEAN ? lds + at_rec : rec0 + (size_t)(overt(side, v) - 1) * kQdRec * kDuoPaths + pl;
         double t[kNB];
 #pragma unroll
         for (int r = 0; r < kNB; ++r) t[r] = rec[(kQdZ + r * kD + dim) * kDuoPaths];
@@ -1107,7 +1169,7 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
                      i3 = rec[(kQdLinv + 3) * kDuoPaths];
         {  // t = z - W x_{v+1},  W x = L^-1 (E x)  (local vertex v + 1 is an unknown for every v <= M - 1)
           double pw[9];
-          quad_powers(tbuf[oseg(side, v) * kDuoPaths + pl], d1, d2, d4, pw);
+          quad_powers(LEAN ? T_now : tbuf[oseg(side, v) * kDuoPaths + pl], d1, d2, d4, pw);
           double u[kNB];
 #pragma unroll
           for (int r = 0; r < kNB; ++r) {
@@ -1135,7 +1197,7 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
         for (int r = 0; r < kNB; ++r) x[r] += vrow0[(r + 1) * kD];
       }
       if (on) {
-        const double T = tbuf[oseg(side, v) * kDuoPaths + pl];
+        const double T = LEAN ? T_now : tbuf[oseg(side, v) * kDuoPaths + pl];
         // the segment's end-point derivatives in FORWARD orientation: side 0 as they are, side 1 with start and end swapped
         // and the odd derivatives negated back
         const double s1 = side ? -1.0 : 1.0;
@@ -1173,7 +1235,7 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
         double p2[9];
         quad_powers(T, d1, d2, d4, p2);  // p2[0] = T^(1 - 2d)
         my_cost = fma(cost_quadratic_form<kOrder>(cb), p2[0], my_cost);
-        double2* out = reinterpret_cast<double2*>(coeffs + ((size_t)(pr.s0 + oseg(side, v)) * kD + dim) * kN);
+        double2* out = LEAN ? nullptr : reinterpret_cast<double2*>(coeffs + ((size_t)(pr.s0 + oseg(side, v)) * kD + dim) * kN);
         // A lane owns 80 consecutive bytes of its segment's 320, so a store instruction of 16 bytes per lane writes 64 separate
         // pieces over 50-odd cache lines, and the kernel is bound by that: with the stores left out a wavefront lives 30.7 k
         // clocks instead of 45.1 k (profiles/round6_duo_phase_clocks.txt, "stores").  In a uniform wavefront the four lanes of a
@@ -1209,21 +1271,28 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
           for (int k = 0; k < kN; k += 2) store_coeff_pair(wbase + (k / 2) * 64, c[k], c[k + 1]);
         } else
 #endif
-        if (uni_wave && (v >= M1 || S_u - 2 * max(v, 1) + 1 >= kXchgRowsBoth)) {
-          const int chunk = v < M1 ? pl * 2 + side : pl;
+        if (LEAN || (uni_wave && (v >= M1 || S_u - 2 * max(v, 1) + 1 >= kXchgRowsBoth))) {
+          const int chunk = (LEAN || v < M1) ? pl * 2 + side : pl;
           double* xrows = rec0 + (size_t)max(v - 1, 0) * kRowDoubles + chunk * kDuoXchgChunk;
           double* xlast = lds + (duo_lds_doubles(Smax) - kDuoXchgChunk);
           double2* xbuf = reinterpret_cast<double2*>(chunk == 2 * kDuoPaths - 1 ? xlast : xrows);
 #pragma unroll
           for (int k = 0; k < kN; k += 2) xbuf[dim * (kN / 2) + k / 2] = make_double2(c[k], c[k + 1]);
           wave_lds_barrier();
-          double2* out4 = out - 4 * dim;  // (the segment's first pair + this lane's place in a row of four)
+          double2* out4 = out - 4 * dim;  // (the segment's first pair + this lane's place in a row of four; LEAN: at_out)
           // (all five reads ahead of the stores and of the branch: the assembly statements keep their order, and an LDS read
           // placed between two of them would be waited for there)
           double2 piece[kN / 2];
 #pragma unroll
           for (int t = 0; t < kN / 2; ++t) piece[t] = xbuf[4 * t + dim];
-          if (THROUGH && through) {
+          if constexpr (LEAN) {
+            const double* wave_out = coeffs + (size_t)block * (kDuoPaths * kD * kN) * S_u;  // (the wavefront's first segment)
+            store_coeff_pair_through<0>(wave_out, at_out, piece[0]);
+            store_coeff_pair_through<64>(wave_out, at_out, piece[1]);
+            store_coeff_pair_through<128>(wave_out, at_out, piece[2]);
+            store_coeff_pair_through<192>(wave_out, at_out, piece[3]);
+            store_coeff_pair_through<256>(wave_out, at_out, piece[4]);
+          } else if (THROUGH && through) {
             static_assert(kN / 2 == 5, "one statement per pair");
             store_coeff_pair_through<0>(out4, piece[0]);
             store_coeff_pair_through<64>(out4, piece[1]);
@@ -1245,8 +1314,15 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
         for (int r = 0; r < kNB; ++r) xn[r] = x[r];
         p_end = p_start;
       }
+      if constexpr (LEAN) {  // local vertex and segment v - 1: one back on side 0, one on on side 1
+        const int st = side ? kDuoPaths : -kDuoPaths;
+        at_rec += st * kQdRec;
+        at_pos += st * kD;
+        at_time += st;
+        at_out += (unsigned)(st * (kD * kN * (int)sizeof(double) / kDuoPaths));
+      }
 #ifdef MRS_TG_DUO_STAMPS
-      if (v == Mmx - 1) DUO_STAMP(9);
+      if (v == v_top) DUO_STAMP(9);
 #endif
     }
     DUO_STAMP(10);
@@ -1268,8 +1344,8 @@ __device__ __forceinline__ void solve_duo_body(const BatchView& b, int d, const 
   __builtin_amdgcn_s_waitcnt(0);  // (every store acknowledged)
   DUO_STAMP(12);
   duo_stamp[15] = __builtin_amdgcn_s_memrealtime();
-  if (lane == 0 && blockIdx.x < 2048)
-    for (int k = 0; k < 16; ++k) g_duo_stamps[blockIdx.x * kDuoStampSlots + k] = duo_stamp[k];
+  if (const unsigned wg = blockIdx.y * gridDim.x + blockIdx.x; lane == 0 && wg < 2048)
+    for (int k = 0; k < 16; ++k) g_duo_stamps[wg * kDuoStampSlots + k] = duo_stamp[k];
 #endif
 }
 
@@ -1289,16 +1365,19 @@ __global__ __launch_bounds__(64, MRS_TG_QUAD_WAVES) void solve_duo_kernel(BatchV
                            (uniform_loops & 1) != 0);
 }
 
-template <bool WP>
+// several batches of ONE plan in one launch: the grid is (workgroups of a batch, batches) -- the batch's index is there at entry,
+// so its pointers load beside the other kernel arguments (a division of a linear index by a loaded count was two dependent
+// scalar trips before any input address was known); workgroups are dispatched x first: the linear order is batch by batch
+template <bool WP, bool LEAN = false>
 __global__ __launch_bounds__(64, MRS_TG_DUO_GROUP_WAVES) void solve_duo_group_kernel(BatchView b, int d, RowsGroup g, double* ws,
-                                                                                    size_t ws_batch_doubles, int blocks_per_batch,
-                                                                                    int uniform_loops) {
-  const int j = __builtin_amdgcn_readfirstlane((int)blockIdx.x / blocks_per_batch);
-  solve_duo_body<WP, false, true>(b, d, g.mask[j], g.vals[j], g.seg_times[j], g.coeffs[j], g.status[j], g.cost[j], nullptr,
-                                  ws + (size_t)j * ws_batch_doubles, RowsTail(), (int)blockIdx.x - j * blocks_per_batch, g.pos_wp[j],
-                                  (uniform_loops & 1) != 0, (uniform_loops & 2) != 0);
+                                                                                    size_t ws_batch_doubles, int uniform_loops) {
+  const int j = (int)blockIdx.y;
+  solve_duo_body<WP, false, true, LEAN>(b, d, g.mask[j], g.vals[j], g.seg_times[j], g.coeffs[j], g.status[j], g.cost[j], nullptr,
+                                        ws + (size_t)j * ws_batch_doubles, RowsTail(), (int)blockIdx.x, g.pos_wp[j],
+                                        (uniform_loops & 1) != 0, (uniform_loops & 2) != 0);
 #ifdef MRS_TG_DUO_STAMPS
-  if (threadIdx.x == 0 && blockIdx.x < 2048) g_duo_stamps[blockIdx.x * kDuoStampSlots + 16] = (unsigned long long)g.coeffs[0];
+  if (const unsigned wg = blockIdx.y * gridDim.x + blockIdx.x; threadIdx.x == 0 && wg < 2048)
+    g_duo_stamps[wg * kDuoStampSlots + 16] = (unsigned long long)g.coeffs[0];
 #endif
 }
 
@@ -1391,15 +1470,22 @@ hipError_t launch_solve_quad_group(const BatchView& b, int d, const RowsGroup& g
   for (int j = 0; j < g.n; ++j) wp = wp && g.pos_wp[j] != nullptr;
   if (!ends && !(d < 4) && duo_pays((long long)b.n_paths * g.n)) {
     const size_t lds_duo = duo_lds_doubles(b.max_segments) * sizeof(double);
-    const auto duo = wp ? MRS_TG_KERNEL(solve_duo_group_kernel<true>) : MRS_TG_KERNEL(solve_duo_group_kernel<false>);
+    // the lean instantiation (solve_duo_body, LEAN): whole-uniform batches of an even length from 4 on, every wavefront full,
+    // both loop knobs on.  Its name in the trace is the family's -- an interface -- unless MRS_TG_TRACE_INSTANTIATIONS asks
+    const int loop_bits = duo_loop_bits();
+    const bool lean = b.uniform_S >= 4 && b.uniform_S % 2 == 0 && b.n_paths % kDuoPaths == 0 && loop_bits == 3 && knob::duo_lean();
+    const bool spell = lean && knob::trace_instantiations();
+    const auto duo = lean ? (wp ? kernel_as(solve_duo_group_kernel<true, true>, spell ? "solve_duo_group_kernel<true, true>" : "solve_duo_group_kernel<true>")
+                                : kernel_as(solve_duo_group_kernel<false, true>, spell ? "solve_duo_group_kernel<false, true>" : "solve_duo_group_kernel<false>"))
+                          : (wp ? MRS_TG_KERNEL(solve_duo_group_kernel<true>) : MRS_TG_KERNEL(solve_duo_group_kernel<false>));
     if (lds_duo > 64 * 1024) {
       hipError_t e = set_max_dynamic_lds(duo, kQuadLdsBudget);
       if (e != hipSuccess) return e;
     }
     const int per_batch_duo = (b.n_paths + kDuoPaths - 1) / kDuoPaths;
-    const dim3 grid_duo((unsigned)(per_batch_duo * g.n));
+    const dim3 grid_duo((unsigned)per_batch_duo, (unsigned)g.n);  // (x: the batch's workgroups, y: the batch)
     const size_t wsd_duo = linear_workspace_doubles(b);
-    MRS_TG_LAUNCH_TIMED(duo, grid_duo, dim3(64), lds_duo, stream, b, d, g, ws, wsd_duo, per_batch_duo, duo_loop_bits());
+    MRS_TG_LAUNCH_TIMED(duo, grid_duo, dim3(64), lds_duo, stream, b, d, g, ws, wsd_duo, loop_bits);
     return hipGetLastError();
   }
   const auto quad = ends ? (wp ? MRS_TG_KERNEL(solve_quad_group_kernel<true, true>) : MRS_TG_KERNEL(solve_quad_group_kernel<false, true>))

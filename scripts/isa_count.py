@@ -1,9 +1,10 @@
 """Instruction mix of one kernel's loops, from the gfx950 assembly the build's flags give.  Runs without a GPU.
 
-    python scripts/isa_count.py mrs_uav_trajectory_generation_amd/csrc/mrs_tg_quad.hip 'solve_duo_group_kernel<true>'
+    python scripts/isa_count.py mrs_uav_trajectory_generation_amd/csrc/mrs_tg_quad.hip 'solve_duo_group_kernel<true, true>'
     python scripts/isa_count.py FILE.hip KERNEL [KERNEL ...] [--min-loop N] [-DX=1 ...]
 
-KERNEL is matched against the demangled name without its argument list (`mrs_tg::` may be left out); every match is printed.
+KERNEL is matched against the demangled name without its argument list (`mrs_tg::` may be left out; defaulted template
+arguments are spelled: the general grouped two-sided kernel is 'solve_duo_group_kernel<true, false>'); every match is printed.
 For each: VGPRs, SGPRs, scratch (private_segment_fixed_size) and LDS as the kernel descriptor states them, the size of the
 whole body, and one line per LOOP -- a label with a later branch back to it -- with its instructions split into FP64 arithmetic
 (v_*_f64 except compares and moves), other VALU, scalar, LDS, vector memory (global / flat / buffer / scratch) and waits
