@@ -190,8 +190,18 @@ enum {
                                       the sampler */
   MRS_TG_CAP_EVALUATE = 64,        /* mrs_tg_plan_evaluate and mrs_tg_plan_evaluate_vjp are exported: the state at caller-given
                                       times and its backward pass */
-  MRS_TG_CAP_DEVIATION = 128       /* mrs_tg_plan_path_deviation and mrs_tg_plan_path_deviation_vjp are exported: the deviation
+  MRS_TG_CAP_DEVIATION = 128,      /* mrs_tg_plan_path_deviation and mrs_tg_plan_path_deviation_vjp are exported: the deviation
                                       of the samples from the waypoint polyline and its backward pass */
+  MRS_TG_CAP_ESTIMATE_GRADIENT = 256 /* mrs_tg_plan_estimate_times and mrs_tg_plan_estimate_times_vjp are exported: the Euclidean
+                                        segment-time estimate as a plan step and its backward pass */
+};
+
+/* mrs_tg_plan_estimate_times_vjp's term_out_dev: the term of the estimate a segment's time came from */
+enum {
+  MRS_TG_ESTIMATE_TERM_HORIZONTAL = 0, /* h / v_h: |inclination| <= atan2(v_v, v_h) */
+  MRS_TG_ESTIMATE_TERM_VERTICAL = 1,   /* |dz| / v_v: steeper than that */
+  MRS_TG_ESTIMATE_TERM_FLOOR = 2,      /* the forward took 0.01 */
+  MRS_TG_ESTIMATE_TERM_HEADING = 3     /* 1.5 (t_vel + t_acc) exceeded the distance term, strictly */
 };
 
 typedef struct mrs_tg_options {
@@ -570,13 +580,53 @@ int mrs_tg_plan_path_deviation_vjp(mrs_tg_plan* plan, const double* samples_dev,
                                    const double* grad_deviation_dev, double* grad_samples_out_dev,
                                    double* grad_waypoints_out_dev);
 
+/* The Euclidean segment-time estimate as a plan step (MRS_TG_CAP_ESTIMATE_GRADIENT; estimate_times_kernel, DESIGN.md section
+ * 4e): estimateSegmentTimesEuclidean (vertex.cpp:491-565), the times a solve with options.estimate_times = 1 starts from,
+ * without a solve.  waypoints_dev [sum V][4] are the plan's S + 1 vertices per path (x, y, z, unwrapped heading), limits_dev
+ * [n_paths][9] (index 3 (k - 1) + group; entries 0, 1, 2 and 5 are read), both in the caller's path order;
+ * seg_times_out_dev [sum S].  The kernel is the solve's own: the result is, bit for bit, what mrs_tg_plan_solve with
+ * estimate_times = 1 and MRS_TG_TIME_ALLOC_NONE leaves in seg_times_inout.  Device pointers, asynchronous on the context's
+ * stream. */
+int mrs_tg_plan_estimate_times(mrs_tg_plan* plan, const double* waypoints_dev, const double* limits_dev,
+                               double* seg_times_out_dev);
+/* Backward pass of mrs_tg_plan_estimate_times (estimate_times_vjp_kernel): given grad_seg_times_dev
+ * [sum S] = dL/dt_i, writes dL/dwaypoints (grad_waypoints_out_dev [sum V][4]), dL/dlimits (grad_limits_out_dev [n_paths][9])
+ * and the term every segment's time came from (term_out_dev [sum S], MRS_TG_ESTIMATE_TERM_*).  At least one of the three
+ * must be given; the two gradients need grad_seg_times_dev, term_out_dev alone does not.  The term is decided by the
+ * forward's own expressions in the forward's order.  With G = dL/dt_i, start s, end e, d = e - s, h = sqrt(dx^2 + dy^2),
+ * delta the forward's signed wrapped heading difference (start minus end), ang = |delta|, w = limits[2], a = limits[5]:
+ *   HORIZONTAL  dt/de = (dx/h, dy/h, 0, 0)/v_h          dt/dv_h = -(h/v_h)/v_h
+ *   VERTICAL    dt/de = (0, 0, sign(dz), 0)/v_v         dt/dv_v = -(|dz|/v_v)/v_v
+ *   FLOOR       0                                       0
+ *   HEADING     dt/de = (0, 0, 0, -1.5 sign(delta)/w)   dt/dw = 1.5 (-ang/w^2 - [cruise] 1/a + [acc] 2/a)
+ *                                                       dt/da = 1.5 ([cruise] w/a^2 - [acc] 2 w/a^2)
+ * and dt/ds = -dt/de; cruise is the forward's `reduced >= 0` branch, acc is ang > pi/4.  No transcendental enters a
+ * gradient's value.  What is not smooth, and what the call does there:
+ *   every branch -- the regime, the floor, heading-wins, cruise / acc -- is the forward's and is held fixed;
+ *   a tie between the heading term and the distance term stays with the distance term;
+ *   equal headings (delta == 0) have sign 0; at the +-pi seam the gradient is the one-sided value;
+ *   a relaxed heading (a heading limit >= FLT_MAX) never takes HEADING;
+ *   coincident waypoints land on FLOOR, so h = 0 is never divided by; a purely vertical segment is VERTICAL;
+ *   a zero upstream entry contributes exactly 0;
+ *   a segment with a non-finite waypoint or time, or a limit that is not a number, contributes zeros and reports FLOOR.
+ * Every sum runs in a fixed order: a vertex's accumulator starts at 0.0 and takes the end-part of the segment in front of
+ * it, then the start-part of its own segment; a path's nine limit gradients start at 0.0 and take its segments in increasing
+ * index; entries 3, 4, 6, 7 and 8 are always 0.  Deterministic, no atomics, no workspace, the same bits for a path wherever
+ * it sits in a batch; every output element that belongs to the plan is written exactly once, zeros included.  Device
+ * pointers, asynchronous on the context's stream. */
+int mrs_tg_plan_estimate_times_vjp(mrs_tg_plan* plan, const double* waypoints_dev, const double* limits_dev,
+                                   const double* grad_seg_times_dev, double* grad_waypoints_out_dev,
+                                   double* grad_limits_out_dev, int32_t* term_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
  * 3 backward pass of the solve (mrs_tg_plan_solve_vjp), 4 backward pass of the maxima (mrs_tg_plan_segment_maxima_vjp),
  * 5 backward pass of the sampler (mrs_tg_plan_sample_states_vjp), 6 evaluation at given times (mrs_tg_plan_evaluate),
  * 7 its backward pass (mrs_tg_plan_evaluate_vjp), 8 deviation from the waypoint path (mrs_tg_plan_path_deviation),
- * 9 its backward pass (mrs_tg_plan_path_deviation_vjp): ten ids, 0 .. 9.
+ * 9 its backward pass (mrs_tg_plan_path_deviation_vjp), 10 the segment-time estimate as a plan step
+ * (mrs_tg_plan_estimate_times; inside a solve the estimate is not timed), 11 its backward pass
+ * (mrs_tg_plan_estimate_times_vjp): twelve ids, 0 .. 11.
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

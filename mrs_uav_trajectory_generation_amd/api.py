@@ -46,6 +46,7 @@ KERNEL_ASSEMBLE, KERNEL_SOLVE_LINEAR, KERNEL_NONLINEAR, KERNEL_VJP, KERNEL_MAXIM
 KERNEL_SAMPLE_VJP = 5
 KERNEL_EVALUATE, KERNEL_EVALUATE_VJP = 6, 7
 KERNEL_DEVIATION, KERNEL_DEVIATION_VJP = 8, 9
+KERNEL_ESTIMATE, KERNEL_ESTIMATE_VJP = 10, 11
 
 
 class MrsTgError(RuntimeError):
@@ -106,6 +107,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_plan_segment_maxima_vjp", "mrs_tg_plan_sample", "mrs_tg_plan_sample_states_vjp",
     "mrs_tg_plan_evaluate", "mrs_tg_plan_evaluate_vjp",
     "mrs_tg_plan_path_deviation", "mrs_tg_plan_path_deviation_vjp",
+    "mrs_tg_plan_estimate_times", "mrs_tg_plan_estimate_times_vjp",
 ]
 
 _lib = None
@@ -211,6 +213,10 @@ def load_library():
     L.mrs_tg_plan_path_deviation.argtypes = [vp, dp, ip, C.c_int32, dp, C.c_int32, ip, dp, ip, dp, ip, dp]
     L.mrs_tg_plan_path_deviation_vjp.restype = C.c_int
     L.mrs_tg_plan_path_deviation_vjp.argtypes = [vp, dp, ip, C.c_int32, dp, ip, dp, dp, dp]
+    L.mrs_tg_plan_estimate_times.restype = C.c_int
+    L.mrs_tg_plan_estimate_times.argtypes = [vp, dp, dp, dp]
+    L.mrs_tg_plan_estimate_times_vjp.restype = C.c_int
+    L.mrs_tg_plan_estimate_times_vjp.argtypes = [vp, dp, dp, dp, dp, dp, ip]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -263,6 +269,9 @@ CAP_MAXIMA_GRADIENT = 16   # MRS_TG_CAP_MAXIMA_GRADIENT: Plan.segment_maxima_vjp
 CAP_SAMPLE_GRADIENT = 32   # MRS_TG_CAP_SAMPLE_GRADIENT: Plan.sample_states_vjp (the backward pass of the sampler), Plan.sample
 CAP_EVALUATE = 64          # MRS_TG_CAP_EVALUATE: Plan.evaluate (the state at caller-given times), Plan.evaluate_vjp
 CAP_DEVIATION = 128        # MRS_TG_CAP_DEVIATION: Plan.path_deviation (samples against the waypoint polyline), Plan.path_deviation_vjp
+CAP_ESTIMATE_GRADIENT = 256   # MRS_TG_CAP_ESTIMATE_GRADIENT: Plan.estimate_times (the Euclidean estimate as a plan step), Plan.estimate_times_vjp
+# Plan.estimate_times_vjp's term: the term of the estimate a segment's time came from (MRS_TG_ESTIMATE_TERM_*)
+ESTIMATE_TERM_HORIZONTAL, ESTIMATE_TERM_VERTICAL, ESTIMATE_TERM_FLOOR, ESTIMATE_TERM_HEADING = 0, 1, 2, 3
 
 
 def capabilities():
@@ -896,6 +905,23 @@ class Plan:
                                                                int(samples.shape[1]), _t_ptr(waypoints), _t_ptr(status),
                                                                _t_ptr(grad_deviation), _t_ptr(grad_samples),
                                                                _t_ptr(grad_waypoints)), "mrs_tg_plan_path_deviation_vjp")
+
+    def estimate_times(self, waypoints, limits, seg_times):
+        """mrs_tg_plan_estimate_times: the Euclidean segment-time estimate of waypoints [sum V][4] under limits [n_paths][9] into
+        seg_times [sum S] (device tensors; seg_times written) -- the times a solve with estimate_times = 1 starts from, in the
+        same bits; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_estimate_times(self._h, _t_ptr(waypoints), _t_ptr(limits), _t_ptr(seg_times)),
+                        "mrs_tg_plan_estimate_times")
+
+    def estimate_times_vjp(self, waypoints, limits, grad_seg_times=None, grad_waypoints=None, grad_limits=None, term=None):
+        """mrs_tg_plan_estimate_times_vjp: dL/dwaypoints [sum V][4], dL/dlimits [n_paths][9] and the term of every segment
+        [sum S] (int32, ESTIMATE_TERM_*) (device tensors, written; None = not wanted, at least one given) from dL/dseg_times
+        (grad_seg_times [sum S]; the gradients need it, term alone does not), every branch of the forward held fixed;
+        asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_estimate_times_vjp(self._h, _t_ptr(waypoints), _t_ptr(limits),
+                                                               _t_ptr(grad_seg_times), _t_ptr(grad_waypoints),
+                                                               _t_ptr(grad_limits), _t_ptr(term)),
+                        "mrs_tg_plan_estimate_times_vjp")
 
 
 class RoundRobin:

@@ -1,7 +1,7 @@
-"""The fixed-times solve, the segment maxima, the sampler, the evaluation at given times and the deviation from the waypoint
-path as torch.autograd.Functions: gradients of a loss on the coefficients, the cost, the derivative maxima, the samples, the
-states at chosen times and the deviations reach the fixed values (waypoints, initial state), the segment times, the limits and
-the query times.
+"""The segment-time estimate, the fixed-times solve, the segment maxima, the sampler, the evaluation at given times and the
+deviation from the waypoint path as torch.autograd.Functions: gradients of a loss on the coefficients, the cost, the derivative
+maxima, the samples, the states at chosen times and the deviations reach the waypoints (through the fixed values AND through
+the estimated times), the initial state, the segment times, the limits and the query times.
 
 Forward: Plan.solve with time_alloc_method = NONE, no sampling, no waypoints, no limits (the existing kernels, unchanged).
 Backward: Plan.solve_vjp (mrs_tg_plan_solve_vjp, vjp_kernel), the exact chain rule of the linear QP at the returned solution
@@ -59,6 +59,22 @@ subdividing segments -- through the solve and the sampler:
     >>> corridor = torch.relu(deviation - 0.05).sum()             # rows behind a path's scan are zero: no mask needed
     >>> worst = deviation.amax(dim=1)                             # the reference's max_deviation per path (first_segment=True)
     >>> corridor.backward()                                       # fv.grad (through the samples AND the polyline), times.grad
+
+estimate_times (Plan.estimate_times forward, Plan.estimate_times_vjp backward: mrs_tg_plan_estimate_times /
+mrs_tg_plan_estimate_times_vjp) is where the times come from: the Euclidean estimate a solve with
+estimate_times = 1 starts from, in the same bits, differentiable in the waypoints and the limits with every branch of the
+forward held fixed.  With it the chain starts at the waypoints and the limits, and the corridor term sees a waypoint through its
+two segment times as well -- estimate, solve, feasibility scaling, re-solve, sampler, deviation:
+
+    >>> wp = waypoints.clone().requires_grad_(); lim = limits.clone().requires_grad_()
+    >>> fv = fixed_values.clone(); fv[:, 0, :] = wp
+    >>> times = estimate_times(plan, wp, lim)
+    >>> coeffs, _, status = solve(plan, fixed_mask, fv, times)
+    >>> times = scale_times_to_limits(plan, coeffs, times, lim, status)
+    >>> coeffs, _, status = solve(plan, fixed_mask, fv, times)
+    >>> samples, n = sample(plan, coeffs, times, 0.2, 512, status)
+    >>> deviation, cursor = path_deviation(plan, samples, n, wp, first_segment=True, status=status)
+    >>> torch.relu(deviation - 0.05).sum().backward()             # wp.grad (values, polyline AND times), lim.grad
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -296,6 +312,48 @@ def path_deviation(plan, samples, n_samples, waypoints, first_segment=True, stat
     holds every cursor and the branch of every distance fixed; a sample on its segment (deviation 0) and a path with
     status <= 0 (status [n_paths], optional) get and give zero."""
     return _PathDeviation.apply(plan, samples, n_samples, waypoints, first_segment, status)
+
+
+class _EstimateTimes(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, waypoints, limits):
+        w = waypoints.detach().to(torch.float64).contiguous()
+        lim = limits.detach().to(torch.float64).contiguous()
+        if w.dim() != 2 or w.shape[0] != plan.n_segments + plan.n_paths or w.shape[1] != api.N_DIM:
+            raise ValueError("waypoints must be [sum V][4]")
+        if lim.dim() != 2 or lim.shape[0] != plan.n_paths or lim.shape[1] != 9:
+            raise ValueError("limits must be [n_paths][9]")
+        times = torch.empty(plan.n_segments, dtype=torch.float64, device=w.device)
+        plan.ctx.use_torch_stream()
+        plan.estimate_times(w, lim, times)
+        ctx.plan = plan
+        ctx.save_for_backward(w, lim)
+        ctx.set_materialize_grads(False)
+        return times
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_times):
+        w, lim = ctx.saved_tensors
+        want_w, want_l = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if grad_times is None or not (want_w or want_l):
+            return None, None, None
+        gw = torch.empty_like(w) if want_w else None
+        gl = torch.empty_like(lim) if want_l else None
+        plan = ctx.plan
+        plan.ctx.use_torch_stream()   # (the autograd engine runs this on its own thread, on the forward's stream)
+        plan.estimate_times_vjp(w, lim, grad_seg_times=grad_times.to(torch.float64).contiguous(), grad_waypoints=gw,
+                                grad_limits=gl)
+        return None, gw, gl
+
+
+def estimate_times(plan, waypoints, limits):
+    """seg_times [sum S] of Plan.estimate_times: the Euclidean segment-time estimate (the times a solve with
+    estimate_times = 1 starts from, in the same bits) -- differentiable in waypoints [sum V][4] (x, y, z, unwrapped heading)
+    and limits [n_paths][9] (float64 device tensors; entries 0, 1, 2 and 5 are read, the others get a zero gradient).  The
+    gradient holds every branch of the forward fixed: the regime (horizontal / vertical), the 0.01 s floor (zero gradient),
+    whether the heading term wins and its own two branches; Plan.estimate_times_vjp(term=...) reports the term per segment."""
+    return _EstimateTimes.apply(plan, waypoints, limits)
 
 
 def _root(x, p):

@@ -51,9 +51,9 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 10;  // kernel_id 0 .. 9 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 12;  // kernel_id 0 .. 11 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
-  long long ev_count[kTimedKernels] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // timed launches since profiling was switched on
+  long long ev_count[kTimedKernels] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
   double wall_clock_hz = 1.0e8;  // rate of s_memrealtime (hipDeviceAttributeWallClockRate)
   // plan of the most recent mrs_tg_solve_batch: a caller that sends the same batch shape again (the nodelet's
@@ -232,7 +232,8 @@ int mrs_tg_abi_version(void) { return MRS_TG_ABI_VERSION; }
 
 int mrs_tg_capabilities(void) {
   return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE |
-         MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE | MRS_TG_CAP_DEVIATION;
+         MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE | MRS_TG_CAP_DEVIATION |
+         MRS_TG_CAP_ESTIMATE_GRADIENT;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1127,6 +1128,33 @@ int mrs_tg_plan_path_deviation_vjp(mrs_tg_plan* plan, const double* samples, con
   return staged_launch_result(ctx, plan,
                               mrs_tg::launch_path_deviation_vjp(plan->view, samples, n_samples, waypoints, sample_capacity, status,
                                                                 grad_deviation, grad_samples, grad_waypoints, ctx->stream));
+}
+
+int mrs_tg_plan_estimate_times(mrs_tg_plan* plan, const double* waypoints, const double* limits, double* seg_times_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!waypoints || !limits || !seg_times_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "waypoints_dev, limits_dev and seg_times_out_dev are required");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 10);
+  HIP_TRY(ctx, mrs_tg::launch_estimate_times(plan->view, waypoints, limits, seg_times_out, ctx->stream, /*timed=*/true));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_estimate_times_vjp(mrs_tg_plan* plan, const double* waypoints, const double* limits,
+                                   const double* grad_seg_times, double* grad_waypoints, double* grad_limits, int32_t* term) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!waypoints || !limits) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "waypoints_dev and limits_dev are required");
+  if (!grad_waypoints && !grad_limits && !term)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "every output of mrs_tg_plan_estimate_times_vjp is NULL");
+  if ((grad_waypoints || grad_limits) && !grad_seg_times)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_waypoints_out_dev and grad_limits_out_dev need grad_seg_times_dev");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 11);
+  HIP_TRY(ctx, mrs_tg::launch_estimate_times_vjp(plan->view, waypoints, limits, grad_seg_times, grad_waypoints, grad_limits,
+                                                 term, ctx->stream));
+  return MRS_TG_OK;
 }
 
 // ---- one-call host interface ------------------------------------------------------------------

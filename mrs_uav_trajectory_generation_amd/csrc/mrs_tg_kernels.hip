@@ -352,9 +352,12 @@ hipError_t launch_copy_many(const CopyList& cl, hipStream_t stream) {
 }
 
 hipError_t launch_estimate_times(const BatchView& b, const double* wp, const double* limits, double* seg_times,
-                                 hipStream_t stream) {
+                                 hipStream_t stream, bool timed) {
   if (b.n_segments == 0) return hipSuccess;
-  MRS_TG_LAUNCH(estimate_times_kernel, dim3(cdiv(b.n_segments, 256)), dim3(256), 0, stream, b, wp, limits,
+  if (timed)
+    MRS_TG_LAUNCH_TIMED(estimate_times_kernel, dim3(cdiv(b.n_segments, 256)), dim3(256), 0, stream, b, wp, limits, seg_times);
+  else
+    MRS_TG_LAUNCH(estimate_times_kernel, dim3(cdiv(b.n_segments, 256)), dim3(256), 0, stream, b, wp, limits,
                      seg_times);
   return hipGetLastError();
 }

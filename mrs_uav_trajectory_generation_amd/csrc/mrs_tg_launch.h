@@ -162,8 +162,10 @@ hipError_t launch_copy_many(const CopyList& cl, hipStream_t stream);
 hipError_t launch_copy_samples(const double* src, double* dst, const int32_t* n_samples, int n_paths, int capacity,
                                hipStream_t stream);
 
+// (timed: the launch carries the pending ProfileScope's events -- mrs_tg_plan_estimate_times, where the estimate is the call's
+// own kernel; inside a solve it is a prelude and leaves the timer to the solve)
 hipError_t launch_estimate_times(const BatchView& b, const double* wp, const double* limits, double* seg_times,
-                                 hipStream_t stream);
+                                 hipStream_t stream, bool timed = false);
 // (one wavefront per path: sample_kernel)
 hipError_t launch_sample(const BatchView& b, const double* coeffs, const double* seg_times, double dt, int capacity,
                          int32_t* n_samples, double* samples, hipStream_t stream);
@@ -254,6 +256,11 @@ hipError_t launch_path_deviation(const BatchView& b, const double* samples, cons
 hipError_t launch_path_deviation_vjp(const BatchView& b, const double* samples, const int32_t* n_samples,
                                      const double* waypoints, int capacity, const int32_t* status, const double* grad_deviation,
                                      double* grad_samples, double* grad_waypoints, hipStream_t stream);
+// mrs_tg_plan_estimate_times_vjp (mrs_tg_estimate_vjp.hip): the backward pass of the Euclidean segment-time estimate --
+// dL/dwaypoints [sum V][4], dL/dlimits [n_paths][9] and the term of every segment [sum S] (each may be NULL) from dL/dseg_times
+// (may be NULL when only the terms are wanted); reads only, no workspace; timed as the kernel family of the pending ProfileScope
+hipError_t launch_estimate_times_vjp(const BatchView& b, const double* wp, const double* limits, const double* grad_times,
+                                     double* grad_wp, double* grad_limits, int32_t* term, hipStream_t stream);
 // phase-split tile kernel (mrs_tg_tile.hip): small and medium batches whose per-path state fits in LDS
 bool tile_kernel_applies(const BatchView& b, bool fused);
 hipError_t launch_solve_tile(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,
