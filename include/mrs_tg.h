@@ -192,8 +192,11 @@ enum {
                                       times and its backward pass */
   MRS_TG_CAP_DEVIATION = 128,      /* mrs_tg_plan_path_deviation and mrs_tg_plan_path_deviation_vjp are exported: the deviation
                                       of the samples from the waypoint polyline and its backward pass */
-  MRS_TG_CAP_ESTIMATE_GRADIENT = 256 /* mrs_tg_plan_estimate_times and mrs_tg_plan_estimate_times_vjp are exported: the Euclidean
-                                        segment-time estimate as a plan step and its backward pass */
+  MRS_TG_CAP_ESTIMATE_GRADIENT = 256, /* mrs_tg_plan_estimate_times and mrs_tg_plan_estimate_times_vjp are exported: the Euclidean
+                                         segment-time estimate as a plan step and its backward pass */
+  MRS_TG_CAP_WAYPOINT_PASSAGE = 512   /* mrs_tg_plan_waypoint_passage and mrs_tg_plan_waypoint_passage_vjp are exported: where the
+                                         samples pass the requested waypoints (index, miss distance, foot point) and its
+                                         backward pass */
 };
 
 /* mrs_tg_plan_estimate_times_vjp's term_out_dev: the term of the estimate a segment's time came from */
@@ -618,6 +621,58 @@ int mrs_tg_plan_estimate_times_vjp(mrs_tg_plan* plan, const double* waypoints_de
                                    const double* grad_seg_times_dev, double* grad_waypoints_out_dev,
                                    double* grad_limits_out_dev, int32_t* term_out_dev);
 
+/* Where the sampled trajectory passes the requested waypoints (MRS_TG_CAP_WAYPOINT_PASSAGE; waypoint_passage_kernel, DESIGN.md
+ * section 11c): getWaypointInTrajectoryIdxs (mrs_trajectory_generation.cpp:1461-1499), the waypoint_trajectory_idxs of the
+ * service's response, as a plan step on samples where they are -- with the miss distance and the place of the foot point on
+ * the step, which say how closely and WHEN a waypoint is passed.
+ * samples_dev [n_paths][sample_capacity][4] and n_samples_dev [n_paths] are what a solve or mrs_tg_plan_sample left
+ * (n = min(n_samples, sample_capacity) rows are read, x, y, z of each).  The waypoints are the ones the caller asks about,
+ * which need not be the plan's vertices: wp_offsets_dev [n_paths + 1] (int32, device memory, the caller's path order) is a
+ * CSR over waypoints_dev [sum W][4] (x, y, z read), path p owning the rows wp_offsets[p] .. wp_offsets[p + 1] - 1 (W = 0 is
+ * allowed; W has no upper bound).  wp_offsets_dev == NULL means the plan's own vertices: path p's rows start at
+ * seg_offsets[p] + p and W = S + 1.  With D = distFromSegment (:1533-1554) and the cursor c = 0, for i = 0 .. n-2 of a path:
+ *   m = D(w_c, s_i, s_{i+1});   if m < 0.1:  index[c] = i, miss[c] = m, fraction[c] = tau, c = c + 1;   stop when c == W
+ * tau is the place of the foot point on the step s_i -> s_{i+1}, from the very coord and len that D forms: 0 when coord < 0
+ * or len * len == 0, 1 when coord > len, otherwise coord / len.  The passing time of waypoint k is
+ * (index[k] + fraction[k]) * sampling_dt.  A step takes at most one waypoint: the indices increase strictly.  A distance that
+ * is not a number is no hit.  Outputs, each may be NULL, at least one given:
+ *   index_out_dev [sum W] (int32)  the step at which waypoint k is passed; -1 for every waypoint from the first one not
+ *                                  reached on, even if a later one lies near the trajectory (the reference never tests it)
+ *   count_out_dev [n_paths]        how many were reached: the reference's idxs.size()
+ *   miss_out_dev [sum W]           m of the hit; 0.0 where not reached
+ *   fraction_out_dev [sum W]       tau of the hit; 0.0 where not reached
+ * With status_dev, a path with status <= 0 gets count 0, indices -1 and zeros; n <= 1 or W = 0 scans nothing.  The arithmetic
+ * is the host's, operation by operation with no fused multiply-add: index and count are mrs_tg_waypoint_trajectory_idxs' on
+ * the same samples.  Every output element that belongs to the plan is written exactly once, in the caller's path order.
+ * Device pointers (16-byte aligned), asynchronous on the context's stream. */
+int mrs_tg_plan_waypoint_passage(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev,
+                                 int32_t sample_capacity, const int32_t* wp_offsets_dev, const double* waypoints_dev,
+                                 const int32_t* status_dev, int32_t* index_out_dev, int32_t* count_out_dev,
+                                 double* miss_out_dev, double* fraction_out_dev);
+/* Backward pass of mrs_tg_plan_waypoint_passage (waypoint_passage_vjp_kernel): given grad_miss_dev
+ * [sum W] = dL/dmiss and grad_fraction_dev [sum W] = dL/dfraction (either may be NULL, which counts as zero; entries of
+ * waypoints that are not reached are never read), writes dL/dsamples (grad_samples_out_dev [n_paths][sample_capacity][4])
+ * and dL/dwaypoints (grad_waypoints_out_dev [sum W][4]); column 3 of both is zero; at least one must be given.  The scan is
+ * recomputed as the forward computes it.  For a hit of p = w_k on the step a = s_i, b = s_{i+1}: the miss part is the row of
+ * mrs_tg_plan_path_deviation_vjp's table for D(p, a, b); the fraction part is zero in the two clamped branches and for
+ * len * len == 0, and in the interior, with v = b - a, q = p - a, L2 = len * len:
+ *   dtau/dp = v / L2,   dtau/db = (q - 2 tau v) / L2,   dtau/da = -dtau/dp - dtau/db
+ * What is not smooth, and what the call does there:
+ *   the index -- held fixed: the test m < 0.1 is piecewise constant;
+ *   the branch -- the forward's; coord == 0 and coord == len take the interior row;
+ *   a waypoint on its step (m == 0) -- contributes exactly 0 through the miss;
+ *   a zero upstream contributes exactly 0;
+ *   waypoints that are not reached, and with status_dev the paths with status <= 0, get zero rows.
+ * Every sum runs in a fixed order: a hit's contribution to a row is, per coordinate, the miss part plus the fraction part;
+ * a waypoint's row is that one term; sample row j starts at 0.0 and takes the b-contribution of the hit on step j - 1, if
+ * there is one, then the a-contribution of the hit on step j, if there is one.  The rows from n on are zero.  Deterministic,
+ * no atomics, no workspace, the same bits for a path wherever it sits in a batch; every output element that belongs to the
+ * plan is written exactly once.  Device pointers (16-byte aligned), asynchronous on the context's stream. */
+int mrs_tg_plan_waypoint_passage_vjp(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev,
+                                     int32_t sample_capacity, const int32_t* wp_offsets_dev, const double* waypoints_dev,
+                                     const int32_t* status_dev, const double* grad_miss_dev, const double* grad_fraction_dev,
+                                     double* grad_samples_out_dev, double* grad_waypoints_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
@@ -626,7 +681,8 @@ int mrs_tg_plan_estimate_times_vjp(mrs_tg_plan* plan, const double* waypoints_de
  * 7 its backward pass (mrs_tg_plan_evaluate_vjp), 8 deviation from the waypoint path (mrs_tg_plan_path_deviation),
  * 9 its backward pass (mrs_tg_plan_path_deviation_vjp), 10 the segment-time estimate as a plan step
  * (mrs_tg_plan_estimate_times; inside a solve the estimate is not timed), 11 its backward pass
- * (mrs_tg_plan_estimate_times_vjp): twelve ids, 0 .. 11.
+ * (mrs_tg_plan_estimate_times_vjp), 12 waypoint passage (mrs_tg_plan_waypoint_passage), 13 its backward pass
+ * (mrs_tg_plan_waypoint_passage_vjp): fourteen ids, 0 .. 13.
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

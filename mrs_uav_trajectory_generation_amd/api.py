@@ -47,6 +47,7 @@ KERNEL_SAMPLE_VJP = 5
 KERNEL_EVALUATE, KERNEL_EVALUATE_VJP = 6, 7
 KERNEL_DEVIATION, KERNEL_DEVIATION_VJP = 8, 9
 KERNEL_ESTIMATE, KERNEL_ESTIMATE_VJP = 10, 11
+KERNEL_PASSAGE, KERNEL_PASSAGE_VJP = 12, 13
 
 
 class MrsTgError(RuntimeError):
@@ -108,6 +109,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_plan_evaluate", "mrs_tg_plan_evaluate_vjp",
     "mrs_tg_plan_path_deviation", "mrs_tg_plan_path_deviation_vjp",
     "mrs_tg_plan_estimate_times", "mrs_tg_plan_estimate_times_vjp",
+    "mrs_tg_plan_waypoint_passage", "mrs_tg_plan_waypoint_passage_vjp",
 ]
 
 _lib = None
@@ -217,6 +219,10 @@ def load_library():
     L.mrs_tg_plan_estimate_times.argtypes = [vp, dp, dp, dp]
     L.mrs_tg_plan_estimate_times_vjp.restype = C.c_int
     L.mrs_tg_plan_estimate_times_vjp.argtypes = [vp, dp, dp, dp, dp, dp, ip]
+    L.mrs_tg_plan_waypoint_passage.restype = C.c_int
+    L.mrs_tg_plan_waypoint_passage.argtypes = [vp, dp, ip, C.c_int32, ip, dp, ip, ip, ip, dp, dp]
+    L.mrs_tg_plan_waypoint_passage_vjp.restype = C.c_int
+    L.mrs_tg_plan_waypoint_passage_vjp.argtypes = [vp, dp, ip, C.c_int32, ip, dp, ip, dp, dp, dp, dp]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -270,6 +276,7 @@ CAP_SAMPLE_GRADIENT = 32   # MRS_TG_CAP_SAMPLE_GRADIENT: Plan.sample_states_vjp 
 CAP_EVALUATE = 64          # MRS_TG_CAP_EVALUATE: Plan.evaluate (the state at caller-given times), Plan.evaluate_vjp
 CAP_DEVIATION = 128        # MRS_TG_CAP_DEVIATION: Plan.path_deviation (samples against the waypoint polyline), Plan.path_deviation_vjp
 CAP_ESTIMATE_GRADIENT = 256   # MRS_TG_CAP_ESTIMATE_GRADIENT: Plan.estimate_times (the Euclidean estimate as a plan step), Plan.estimate_times_vjp
+CAP_WAYPOINT_PASSAGE = 512    # MRS_TG_CAP_WAYPOINT_PASSAGE: Plan.waypoint_passage (where the samples pass the requested waypoints), Plan.waypoint_passage_vjp
 # Plan.estimate_times_vjp's term: the term of the estimate a segment's time came from (MRS_TG_ESTIMATE_TERM_*)
 ESTIMATE_TERM_HORIZONTAL, ESTIMATE_TERM_VERTICAL, ESTIMATE_TERM_FLOOR, ESTIMATE_TERM_HEADING = 0, 1, 2, 3
 
@@ -922,6 +929,29 @@ class Plan:
                                                                _t_ptr(grad_seg_times), _t_ptr(grad_waypoints),
                                                                _t_ptr(grad_limits), _t_ptr(term)),
                         "mrs_tg_plan_estimate_times_vjp")
+
+    def waypoint_passage(self, samples, n_samples, waypoints, wp_offsets=None, status=None, index=None, count=None, miss=None,
+                         fraction=None):
+        """mrs_tg_plan_waypoint_passage: getWaypointInTrajectoryIdxs' scan of samples [n_paths][capacity][4] (n_samples
+        [n_paths] int32) for the waypoints [sum W][4] that wp_offsets [n_paths + 1] (int32 device tensor; None = the plan's own
+        vertices) gives every path, into index [sum W] (int32, -1 from the first waypoint not reached on), count [n_paths]
+        (int32), miss [sum W] and fraction [sum W] (device tensors, written; None = not wanted, at least one given): waypoint k
+        is passed at (index[k] + fraction[k]) * sampling_dt; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_waypoint_passage(self._h, _t_ptr(samples), _t_ptr(n_samples), int(samples.shape[1]),
+                                                             _t_ptr(wp_offsets), _t_ptr(waypoints), _t_ptr(status),
+                                                             _t_ptr(index), _t_ptr(count), _t_ptr(miss), _t_ptr(fraction)),
+                        "mrs_tg_plan_waypoint_passage")
+
+    def waypoint_passage_vjp(self, samples, n_samples, waypoints, grad_miss=None, grad_fraction=None, wp_offsets=None,
+                             status=None, grad_samples=None, grad_waypoints=None):
+        """mrs_tg_plan_waypoint_passage_vjp: dL/dsamples [n_paths][capacity][4] and dL/dwaypoints [sum W][4] (device tensors,
+        written; None = not wanted, at least one given) from dL/dmiss and dL/dfraction (grad_miss, grad_fraction [sum W]; None =
+        zero), the indices held fixed; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_waypoint_passage_vjp(self._h, _t_ptr(samples), _t_ptr(n_samples),
+                                                                 int(samples.shape[1]), _t_ptr(wp_offsets), _t_ptr(waypoints),
+                                                                 _t_ptr(status), _t_ptr(grad_miss), _t_ptr(grad_fraction),
+                                                                 _t_ptr(grad_samples), _t_ptr(grad_waypoints)),
+                        "mrs_tg_plan_waypoint_passage_vjp")
 
 
 class RoundRobin:

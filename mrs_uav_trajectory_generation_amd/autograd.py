@@ -1,7 +1,8 @@
-"""The segment-time estimate, the fixed-times solve, the segment maxima, the sampler, the evaluation at given times and the
-deviation from the waypoint path as torch.autograd.Functions: gradients of a loss on the coefficients, the cost, the derivative
-maxima, the samples, the states at chosen times and the deviations reach the waypoints (through the fixed values AND through
-the estimated times), the initial state, the segment times, the limits and the query times.
+"""The segment-time estimate, the fixed-times solve, the segment maxima, the sampler, the evaluation at given times, the
+deviation from the waypoint path and the waypoint passage as torch.autograd.Functions: gradients of a loss on the coefficients,
+the cost, the derivative maxima, the samples, the states at chosen times, the deviations, the miss distances and the passing
+times reach the waypoints (through the fixed values AND through the estimated times), the initial state, the segment times, the
+limits and the query times.
 
 Forward: Plan.solve with time_alloc_method = NONE, no sampling, no waypoints, no limits (the existing kernels, unchanged).
 Backward: Plan.solve_vjp (mrs_tg_plan_solve_vjp, vjp_kernel), the exact chain rule of the linear QP at the returned solution
@@ -312,6 +313,74 @@ def path_deviation(plan, samples, n_samples, waypoints, first_segment=True, stat
     holds every cursor and the branch of every distance fixed; a sample on its segment (deviation 0) and a path with
     status <= 0 (status [n_paths], optional) get and give zero."""
     return _PathDeviation.apply(plan, samples, n_samples, waypoints, first_segment, status)
+
+
+class _WaypointPassage(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, samples, n_samples, waypoints, wp_offsets, status):
+        s = samples.detach().to(torch.float64).contiguous()
+        w = waypoints.detach().to(torch.float64).contiguous()
+        n = n_samples.detach().to(torch.int32).contiguous()
+        if s.dim() != 3 or s.shape[0] != plan.n_paths or s.shape[2] != api.N_DIM:
+            raise ValueError("samples must be [n_paths][capacity][4]")
+        if w.dim() != 2 or w.shape[1] != api.N_DIM:
+            raise ValueError("waypoints must be [sum W][4]")
+        off = None
+        if wp_offsets is None:
+            if w.shape[0] != plan.n_segments + plan.n_paths:
+                raise ValueError("without wp_offsets the waypoints are the plan's vertices [sum V][4]")
+        else:
+            off = wp_offsets.detach().to(device=s.device, dtype=torch.int32).contiguous()
+            if off.dim() != 1 or off.shape[0] != plan.n_paths + 1:
+                raise ValueError("wp_offsets must be [n_paths + 1]")
+        st = None if status is None else status.detach().to(torch.int32).contiguous()
+        index = torch.empty(w.shape[0], dtype=torch.int32, device=s.device)
+        count = torch.empty(plan.n_paths, dtype=torch.int32, device=s.device)
+        miss = torch.empty(w.shape[0], dtype=torch.float64, device=s.device)
+        fraction = torch.empty(w.shape[0], dtype=torch.float64, device=s.device)
+        plan.ctx.use_torch_stream()
+        plan.waypoint_passage(s, n, w, wp_offsets=off, status=st, index=index, count=count, miss=miss, fraction=fraction)
+        ctx.plan, ctx.status, ctx.offsets = plan, st, off
+        ctx.save_for_backward(s, n, w)
+        ctx.mark_non_differentiable(index, count)
+        ctx.set_materialize_grads(False)
+        return index, count, miss, fraction
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, _grad_index, _grad_count, grad_miss, grad_fraction):
+        s, n, w = ctx.saved_tensors
+        want_s, want_w = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        if (grad_miss is None and grad_fraction is None) or not (want_s or want_w):
+            return None, None, None, None, None, None
+        gs = torch.empty_like(s) if want_s else None
+        gw = torch.empty_like(w) if want_w else None
+        gm = None if grad_miss is None else grad_miss.to(torch.float64).contiguous()
+        gf = None if grad_fraction is None else grad_fraction.to(torch.float64).contiguous()
+        plan = ctx.plan
+        plan.ctx.use_torch_stream()   # (the autograd engine runs this on its own thread, on the forward's stream)
+        plan.waypoint_passage_vjp(s, n, w, grad_miss=gm, grad_fraction=gf, wp_offsets=ctx.offsets, status=ctx.status,
+                                  grad_samples=gs, grad_waypoints=gw)
+        return None, gs, None, gw, None, None
+
+
+def waypoint_passage(plan, samples, n_samples, waypoints, wp_offsets=None, status=None):
+    """(index [sum W] int32, count [n_paths] int32, miss [sum W], fraction [sum W]) of Plan.waypoint_passage: where the samples
+    pass the waypoints by getWaypointInTrajectoryIdxs' scan -- waypoint k of a path is passed on the step index[k] -> index[k] + 1,
+    at the distance miss[k], at the place fraction[k] in [0, 1] of that step, so at the time (index[k] + fraction[k]) *
+    sampling_dt; index is -1 and the other two are 0 from the first waypoint not reached on, count is how many were.  miss and
+    fraction are differentiable in samples [n_paths][capacity][4] and waypoints [sum W][4] (float64 device tensors; x, y, z are
+    read, column 3 gets a zero gradient); index and count are not.  waypoints are the ones asked about, which need not be the
+    plan's vertices: wp_offsets [n_paths + 1] (int32, a CSR over exactly the rows of waypoints) says which belong to which path;
+    None means the plan's vertices [sum V][4].  n_samples [n_paths] int32 as the sampler returned it.  The gradient holds every
+    index and the branch of every distance fixed; a waypoint on its step (miss 0) gives nothing through miss, a clamped fraction
+    (0 or 1) nothing through fraction, and a path with status <= 0 (status [n_paths], optional) gets and gives zero.  "Be at
+    waypoint k at time T" and "pass the requested waypoints closely", reached waypoints only:
+
+        >>> index, count, miss, fraction = waypoint_passage(plan, samples, n, requested, wp_offsets=off, status=status)
+        >>> reached = index >= 0
+        >>> loss = ((((index + fraction) * dt - arrival) ** 2 + miss ** 2) * reached).sum()"""
+    return _WaypointPassage.apply(plan, samples, n_samples, waypoints, wp_offsets, status)
 
 
 class _EstimateTimes(torch.autograd.Function):

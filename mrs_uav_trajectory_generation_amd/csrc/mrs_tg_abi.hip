@@ -51,9 +51,9 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 12;  // kernel_id 0 .. 11 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 14;  // kernel_id 0 .. 13 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
-  long long ev_count[kTimedKernels] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // timed launches since profiling was switched on
+  long long ev_count[kTimedKernels] = {};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
   double wall_clock_hz = 1.0e8;  // rate of s_memrealtime (hipDeviceAttributeWallClockRate)
   // plan of the most recent mrs_tg_solve_batch: a caller that sends the same batch shape again (the nodelet's
@@ -233,7 +233,7 @@ int mrs_tg_abi_version(void) { return MRS_TG_ABI_VERSION; }
 int mrs_tg_capabilities(void) {
   return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE |
          MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE | MRS_TG_CAP_DEVIATION |
-         MRS_TG_CAP_ESTIMATE_GRADIENT;
+         MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1154,6 +1154,41 @@ int mrs_tg_plan_estimate_times_vjp(mrs_tg_plan* plan, const double* waypoints, c
   ProfileScope ps(ctx, 11);
   HIP_TRY(ctx, mrs_tg::launch_estimate_times_vjp(plan->view, waypoints, limits, grad_seg_times, grad_waypoints, grad_limits,
                                                  term, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_waypoint_passage(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                 const int32_t* wp_offsets, const double* waypoints, const int32_t* status, int32_t* index,
+                                 int32_t* count, double* miss, double* fraction) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
+  if (!n_samples || !waypoints || (sample_capacity > 0 && !samples))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev and waypoints_dev are required");
+  if (!index && !count && !miss && !fraction)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "every output of mrs_tg_plan_waypoint_passage is NULL");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 12);
+  HIP_TRY(ctx, mrs_tg::launch_waypoint_passage(plan->view, samples, n_samples, sample_capacity, wp_offsets, waypoints, status,
+                                               index, count, miss, fraction, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_waypoint_passage_vjp(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                     const int32_t* wp_offsets, const double* waypoints, const int32_t* status,
+                                     const double* grad_miss, const double* grad_fraction, double* grad_samples,
+                                     double* grad_waypoints) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
+  if (!n_samples || !waypoints || (sample_capacity > 0 && !samples))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev and waypoints_dev are required");
+  if (!grad_samples && !grad_waypoints)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_samples_out and grad_waypoints_out are both NULL");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 13);
+  HIP_TRY(ctx, mrs_tg::launch_waypoint_passage_vjp(plan->view, samples, n_samples, sample_capacity, wp_offsets, waypoints, status,
+                                                   grad_miss, grad_fraction, grad_samples, grad_waypoints, ctx->stream));
   return MRS_TG_OK;
 }
 

@@ -256,6 +256,19 @@ hipError_t launch_path_deviation(const BatchView& b, const double* samples, cons
 hipError_t launch_path_deviation_vjp(const BatchView& b, const double* samples, const int32_t* n_samples,
                                      const double* waypoints, int capacity, const int32_t* status, const double* grad_deviation,
                                      double* grad_samples, double* grad_waypoints, hipStream_t stream);
+// mrs_tg_plan_waypoint_passage / mrs_tg_plan_waypoint_passage_vjp (mrs_tg_passage.hip): where the samples [n_paths][capacity][4]
+// pass the waypoints by getWaypointInTrajectoryIdxs' scan -- index, count, miss distance and foot point per waypoint (every
+// output may be NULL) -- and its backward pass: dL/dsamples and dL/dwaypoints (each may be NULL) from dL/dmiss and dL/dfraction
+// (each may be NULL = zero).  wp_offsets [n_paths + 1] (device) with waypoints [sum W][4], or NULL: the plan's own vertices.
+// status NULL or per path (<= 0: nothing reached, zero rows); reads only, no workspace, no LDS; each timed as the kernel
+// family of the pending ProfileScope
+hipError_t launch_waypoint_passage(const BatchView& b, const double* samples, const int32_t* n_samples, int capacity,
+                                   const int32_t* wp_offsets, const double* waypoints, const int32_t* status, int32_t* index,
+                                   int32_t* count, double* miss, double* fraction, hipStream_t stream);
+hipError_t launch_waypoint_passage_vjp(const BatchView& b, const double* samples, const int32_t* n_samples, int capacity,
+                                       const int32_t* wp_offsets, const double* waypoints, const int32_t* status,
+                                       const double* grad_miss, const double* grad_fraction, double* grad_samples,
+                                       double* grad_waypoints, hipStream_t stream);
 // mrs_tg_plan_estimate_times_vjp (mrs_tg_estimate_vjp.hip): the backward pass of the Euclidean segment-time estimate --
 // dL/dwaypoints [sum V][4], dL/dlimits [n_paths][9] and the term of every segment [sum S] (each may be NULL) from dL/dseg_times
 // (may be NULL when only the terms are wanted); reads only, no workspace; timed as the kernel family of the pending ProfileScope
