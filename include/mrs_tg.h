@@ -194,9 +194,12 @@ enum {
                                       of the samples from the waypoint polyline and its backward pass */
   MRS_TG_CAP_ESTIMATE_GRADIENT = 256, /* mrs_tg_plan_estimate_times and mrs_tg_plan_estimate_times_vjp are exported: the Euclidean
                                          segment-time estimate as a plan step and its backward pass */
-  MRS_TG_CAP_WAYPOINT_PASSAGE = 512   /* mrs_tg_plan_waypoint_passage and mrs_tg_plan_waypoint_passage_vjp are exported: where the
+  MRS_TG_CAP_WAYPOINT_PASSAGE = 512,  /* mrs_tg_plan_waypoint_passage and mrs_tg_plan_waypoint_passage_vjp are exported: where the
                                          samples pass the requested waypoints (index, miss distance, foot point) and its
                                          backward pass */
+  MRS_TG_CAP_BACA = 1024              /* mrs_tg_plan_estimate_times_baca, mrs_tg_plan_estimate_times_baca_vjp and
+                                         mrs_tg_plan_length_gate are exported: the Baca segment-time estimate as a plan step, its
+                                         backward pass, and the length gate on its total */
 };
 
 /* mrs_tg_plan_estimate_times_vjp's term_out_dev: the term of the estimate a segment's time came from */
@@ -205,6 +208,21 @@ enum {
   MRS_TG_ESTIMATE_TERM_VERTICAL = 1,   /* |dz| / v_v: steeper than that */
   MRS_TG_ESTIMATE_TERM_FLOOR = 2,      /* the forward took 0.01 */
   MRS_TG_ESTIMATE_TERM_HEADING = 3     /* 1.5 (t_vel + t_acc) exceeded the distance term, strictly */
+};
+
+/* mrs_tg_plan_estimate_times_baca_vjp's flags_out_dev: the branches of the Baca estimate a segment's time took, as bits */
+enum {
+  MRS_TG_BACA_V_VERTICAL = 1,       /* |inclination| > atan2(v_v, v_h): v_max = |v_v / sin|, else |v_h / cos| */
+  MRS_TG_BACA_A_VERTICAL = 2,       /* the same decision for the acceleration limits */
+  MRS_TG_BACA_J_VERTICAL = 4,       /* and for the jerk limits */
+  MRS_TG_BACA_T1_CAPPED = 8,        /* the acceleration time in front was sqrt(2 distance / a_max), the smaller */
+  MRS_TG_BACA_T2_CAPPED = 16,       /* the acceleration time behind was */
+  MRS_TG_BACA_DOT1_CLAMPED = 32,    /* the cosine of the corner in front was negative: its coefficient is the constant 1 */
+  MRS_TG_BACA_DOT2_CLAMPED = 64,    /* the cosine of the corner behind was */
+  MRS_TG_BACA_FLOOR = 128,          /* the forward took 0.01 */
+  MRS_TG_BACA_HEADING = 256,        /* 1.5 (t_vel + t_acc) exceeded all of that, strictly */
+  MRS_TG_BACA_HEADING_CRUISE = 512, /* the heading term's `reduced >= 0` branch */
+  MRS_TG_BACA_HEADING_ACC = 1024    /* ang > pi/4 */
 };
 
 typedef struct mrs_tg_options {
@@ -673,6 +691,72 @@ int mrs_tg_plan_waypoint_passage_vjp(mrs_tg_plan* plan, const double* samples_de
                                      const int32_t* status_dev, const double* grad_miss_dev, const double* grad_fraction_dev,
                                      double* grad_samples_out_dev, double* grad_waypoints_out_dev);
 
+/* The Baca segment-time estimate as a plan step (MRS_TG_CAP_BACA; baca_times_kernel):
+ * estimateSegmentTimesBaca (vertex.cpp:301-485) -- the reference's yardstick for accepting a trajectory and the clock of its
+ * fallback sampler -- for every path of the plan, where the waypoints are.  waypoints_dev [sum V][4] are the plan's S + 1
+ * vertices per path (x, y, z, unwrapped heading), limits_dev [n_paths][9] (index 3 (k - 1) + group; entries 0 .. 7 are read,
+ * entry 8 is not), both in the caller's path order; seg_times_out_dev [sum S].  One lane per segment.  A segment's neighbours
+ * are the neighbours inside its own path: segment 0 takes the full acceleration time in front, segment S - 1 behind, S = 1
+ * both.  The arithmetic is the host estimate's, operation by operation, without fused multiply-adds, but the result is NOT
+ * promised in the host's bits: atan2, sin and cos are the device's (the estimate is continuous across its inclination
+ * branches, so their last bit moves the value by roundings only; 1e-13 relative).  mrs_tg_estimate_times_baca,
+ * mrs_tg_find_trajectory and mrs_tg_optimize_paths keep their host arithmetic.  Device pointers, asynchronous on the
+ * context's stream. */
+int mrs_tg_plan_estimate_times_baca(mrs_tg_plan* plan, const double* waypoints_dev, const double* limits_dev,
+                                    double* seg_times_out_dev);
+/* Backward pass of mrs_tg_plan_estimate_times_baca (baca_times_vjp_kernel): given grad_seg_times_dev
+ * [sum S] = dL/dt_i, writes dL/dwaypoints (grad_waypoints_out_dev [sum V][4]), dL/dlimits (grad_limits_out_dev [n_paths][9])
+ * and the branches every segment's time took (flags_out_dev [sum S], bits MRS_TG_BACA_*).  At least one of the three must be
+ * given; the two gradients need grad_seg_times_dev, flags_out_dev alone does not.  Every branch is decided by the forward's
+ * own calls in the forward's order and is held fixed.  With G = dL/dt_i, pre, s, e, post the four waypoints a segment reads,
+ * d = e - s, D = |d|, h = sqrt(dx^2 + dy^2), and for L in {v, a, j}: c_L = L_h, q_L = h (horizontal regime) or c_L = L_v,
+ * q_L = |dz| (vertical regime), grad q = (dx/h, dy/h, 0) or (0, 0, sign dz), rho_L = grad q_L / q_L:
+ *   L_max = c_L D / q_L                    (the forward's |L_h / cos| or |L_v / sin| up to roundings)
+ *   full  = v_max/a_max + a_max/j_max      dfull/de = (v_max/a_max)(rho_a - rho_v) + (a_max/j_max)(rho_j - rho_a)
+ *   cap   = sqrt(2 D / a_max)              dcap/de = cap rho_a / 2               dcap/dc_a = -(cap/2)/c_a
+ *   u1 = (s - pre)/n1, u2 = d/D, u3 = (post - e)/n3, dot1 = u1.u2, dot2 = u2.u3    (the forward's unit vectors)
+ *   c1 = 1 (segment 0, or DOT1_CLAMPED), else 1 - dot1;   c2 = 1 (segment S - 1, or DOT2_CLAMPED), else 1 - dot2
+ *   t = D/v_max + t1 + t2,   t_i = c_i full, or cap where T_i_CAPPED
+ *   D/v_max = q_v/c_v   d/de = grad q_v / c_v                         d/dc_v = -(q_v/c_v)/c_v
+ *   t_i = c_i full      d/de = c_i dfull/de + full dc_i/de            d/dc_v = c_i (v_max/a_max)/c_v
+ *                       d/dc_a = -c_i (v_max/a_max)/c_a + c_i (a_max/j_max)/c_a     d/dc_j = -c_i (a_max/j_max)/c_j
+ *   c1 = 1 - dot1       dc1/dpre = (u2 - dot1 u1)/n1   dc1/ds = -(u2 - dot1 u1)/n1 + (u1 - dot1 u2)/D   dc1/de = -(u1 - dot1 u2)/D
+ *   c2 = 1 - dot2       dc2/ds = (u3 - dot2 u2)/D      dc2/de = -(u3 - dot2 u2)/D + (u2 - dot2 u3)/n3   dc2/dpost = -(u2 - dot2 u3)/n3
+ *   d/ds = -d/de for D/v_max, full and cap
+ *   FLOOR    0
+ *   HEADING  dt/de = (0, 0, 0, -1.5 sign(delta)/w), dt/ds its negative;  dt/dw = 1.5 (-ang/w^2 - [cruise] 2/a + [acc] 2/a)
+ *            dt/da = 1.5 ([cruise] 2 w/a^2 - [acc] 2 w/a^2)
+ * with delta the forward's signed wrapped heading difference (start minus end), ang = |delta|, w = limits[2], a = limits[5]:
+ * the heading row of mrs_tg_plan_estimate_times_vjp, with this estimator's `2 *` in front of w^2/a in the cruise branch.  No
+ * transcendental enters a gradient's value.  What is not smooth, and what the call does there:
+ *   ties stay with the forward's comparison, all strict: t_i > cap, dot < 0, the heading term > t, t < 0.01;
+ *   a zero-length neighbour has the zero unit vector as in the forward, and gives no gradient through it;
+ *   FLOOR gives zeros; HEADING gives the heading row only; a relaxed heading (a heading limit >= FLT_MAX) never takes HEADING;
+ *   a zero upstream entry contributes exactly 0;
+ *   a segment that reads a non-finite waypoint or limit, or whose time is not finite, contributes zero rows and has flags = FLOOR;
+ *   limit entry 8 is always 0.
+ * Every sum runs in a fixed order: a segment's part is the sum from 0.0 of its addends in the order above (D/v_max, t1, t2),
+ * times G; a vertex's accumulator starts at 0.0 and takes, of the segments that exist, the post-part of segment v - 2, the
+ * end-part of v - 1, the start-part of v, the pre-part of v + 1 (increasing segment index); a path's nine limit gradients start
+ * at 0.0 and take its segments in increasing index.  Deterministic, no atomics, no workspace, the same bits for a path wherever
+ * it sits in a batch; every output element that belongs to the plan is written exactly once, zeros included.  Device pointers,
+ * asynchronous on the context's stream. */
+int mrs_tg_plan_estimate_times_baca_vjp(mrs_tg_plan* plan, const double* waypoints_dev, const double* limits_dev,
+                                        const double* grad_seg_times_dev, double* grad_waypoints_out_dev,
+                                        double* grad_limits_out_dev, int32_t* flags_out_dev);
+/* The nodelet's gate on a finished trajectory as a plan step (length_gate_kernel): per path the total of
+ * seg_times_dev [sum S] (from 0.0, in increasing index: initial_total_time_baca when the times are the Baca estimate's) into
+ * total_out_dev [n_paths], and into verdict_out_dev [n_paths] one of MRS_TG_FIND_*: REJECTED_CODE first, when status_dev
+ * [n_paths] is given and the code is one the nodelet rejects (accepted: >= 1 except 6, and -1); then, with len =
+ * (double)n_samples_dev[p] * sampling_dt (the raw count a solve leaves), REJECTED_TOO_LONG when len > max_factor * total,
+ * REJECTED_TOO_SHORT when len < min_factor * total, else ACCEPTED.  A trajectory that is not longer than one second passes
+ * (!(len > 1.0)); a factor <= 0 switches its side off.  No fused multiply-add: with the same seg_times the total and the
+ * verdict are mrs_tg_find_trajectory's, bit for bit.  status_dev may be NULL; either output may be NULL, not both.  Device
+ * pointers, asynchronous on the context's stream. */
+int mrs_tg_plan_length_gate(mrs_tg_plan* plan, const double* seg_times_dev, const int32_t* n_samples_dev, double sampling_dt,
+                            double max_factor, double min_factor, const int32_t* status_dev, double* total_out_dev,
+                            int32_t* verdict_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
@@ -682,7 +766,8 @@ int mrs_tg_plan_waypoint_passage_vjp(mrs_tg_plan* plan, const double* samples_de
  * 9 its backward pass (mrs_tg_plan_path_deviation_vjp), 10 the segment-time estimate as a plan step
  * (mrs_tg_plan_estimate_times; inside a solve the estimate is not timed), 11 its backward pass
  * (mrs_tg_plan_estimate_times_vjp), 12 waypoint passage (mrs_tg_plan_waypoint_passage), 13 its backward pass
- * (mrs_tg_plan_waypoint_passage_vjp): fourteen ids, 0 .. 13.
+ * (mrs_tg_plan_waypoint_passage_vjp), 14 the Baca estimate as a plan step (mrs_tg_plan_estimate_times_baca), 15 its backward
+ * pass (mrs_tg_plan_estimate_times_baca_vjp), 16 the length gate (mrs_tg_plan_length_gate): seventeen ids, 0 .. 16.
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

@@ -48,6 +48,7 @@ KERNEL_EVALUATE, KERNEL_EVALUATE_VJP = 6, 7
 KERNEL_DEVIATION, KERNEL_DEVIATION_VJP = 8, 9
 KERNEL_ESTIMATE, KERNEL_ESTIMATE_VJP = 10, 11
 KERNEL_PASSAGE, KERNEL_PASSAGE_VJP = 12, 13
+KERNEL_BACA, KERNEL_BACA_VJP, KERNEL_LENGTH_GATE = 14, 15, 16
 
 
 class MrsTgError(RuntimeError):
@@ -110,6 +111,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_plan_path_deviation", "mrs_tg_plan_path_deviation_vjp",
     "mrs_tg_plan_estimate_times", "mrs_tg_plan_estimate_times_vjp",
     "mrs_tg_plan_waypoint_passage", "mrs_tg_plan_waypoint_passage_vjp",
+    "mrs_tg_plan_estimate_times_baca", "mrs_tg_plan_estimate_times_baca_vjp", "mrs_tg_plan_length_gate",
 ]
 
 _lib = None
@@ -223,6 +225,12 @@ def load_library():
     L.mrs_tg_plan_waypoint_passage.argtypes = [vp, dp, ip, C.c_int32, ip, dp, ip, ip, ip, dp, dp]
     L.mrs_tg_plan_waypoint_passage_vjp.restype = C.c_int
     L.mrs_tg_plan_waypoint_passage_vjp.argtypes = [vp, dp, ip, C.c_int32, ip, dp, ip, dp, dp, dp, dp]
+    L.mrs_tg_plan_estimate_times_baca.restype = C.c_int
+    L.mrs_tg_plan_estimate_times_baca.argtypes = [vp, dp, dp, dp]
+    L.mrs_tg_plan_estimate_times_baca_vjp.restype = C.c_int
+    L.mrs_tg_plan_estimate_times_baca_vjp.argtypes = [vp, dp, dp, dp, dp, dp, ip]
+    L.mrs_tg_plan_length_gate.restype = C.c_int
+    L.mrs_tg_plan_length_gate.argtypes = [vp, dp, ip, C.c_double, C.c_double, C.c_double, ip, dp, ip]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -277,6 +285,10 @@ CAP_EVALUATE = 64          # MRS_TG_CAP_EVALUATE: Plan.evaluate (the state at ca
 CAP_DEVIATION = 128        # MRS_TG_CAP_DEVIATION: Plan.path_deviation (samples against the waypoint polyline), Plan.path_deviation_vjp
 CAP_ESTIMATE_GRADIENT = 256   # MRS_TG_CAP_ESTIMATE_GRADIENT: Plan.estimate_times (the Euclidean estimate as a plan step), Plan.estimate_times_vjp
 CAP_WAYPOINT_PASSAGE = 512    # MRS_TG_CAP_WAYPOINT_PASSAGE: Plan.waypoint_passage (where the samples pass the requested waypoints), Plan.waypoint_passage_vjp
+CAP_BACA = 1024               # MRS_TG_CAP_BACA: Plan.estimate_times_baca (the Baca estimate as a plan step), Plan.estimate_times_baca_vjp, Plan.length_gate
+# Plan.estimate_times_baca_vjp's flags: the branches of the Baca estimate a segment's time took, as bits (MRS_TG_BACA_*)
+BACA_V_VERTICAL, BACA_A_VERTICAL, BACA_J_VERTICAL, BACA_T1_CAPPED, BACA_T2_CAPPED = 1, 2, 4, 8, 16
+BACA_DOT1_CLAMPED, BACA_DOT2_CLAMPED, BACA_FLOOR, BACA_HEADING, BACA_HEADING_CRUISE, BACA_HEADING_ACC = 32, 64, 128, 256, 512, 1024
 # Plan.estimate_times_vjp's term: the term of the estimate a segment's time came from (MRS_TG_ESTIMATE_TERM_*)
 ESTIMATE_TERM_HORIZONTAL, ESTIMATE_TERM_VERTICAL, ESTIMATE_TERM_FLOOR, ESTIMATE_TERM_HEADING = 0, 1, 2, 3
 
@@ -952,6 +964,33 @@ class Plan:
                                                                  _t_ptr(status), _t_ptr(grad_miss), _t_ptr(grad_fraction),
                                                                  _t_ptr(grad_samples), _t_ptr(grad_waypoints)),
                         "mrs_tg_plan_waypoint_passage_vjp")
+
+    def estimate_times_baca(self, waypoints, limits, seg_times):
+        """mrs_tg_plan_estimate_times_baca: the Baca segment-time estimate (estimateSegmentTimesBaca) of waypoints [sum V][4]
+        under limits [n_paths][9] (entries 0 .. 7 are read) into seg_times [sum S] (device tensors; seg_times written) -- within
+        1e-13 of the host's estimate_times_baca, not in its bits; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_estimate_times_baca(self._h, _t_ptr(waypoints), _t_ptr(limits), _t_ptr(seg_times)),
+                        "mrs_tg_plan_estimate_times_baca")
+
+    def estimate_times_baca_vjp(self, waypoints, limits, grad_seg_times=None, grad_waypoints=None, grad_limits=None, flags=None):
+        """mrs_tg_plan_estimate_times_baca_vjp: dL/dwaypoints [sum V][4], dL/dlimits [n_paths][9] and the branches of every
+        segment [sum S] (int32, bits BACA_*) (device tensors, written; None = not wanted, at least one given) from dL/dseg_times
+        (grad_seg_times [sum S]; the gradients need it, flags alone do not), every branch of the forward held fixed;
+        asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_estimate_times_baca_vjp(self._h, _t_ptr(waypoints), _t_ptr(limits),
+                                                                    _t_ptr(grad_seg_times), _t_ptr(grad_waypoints),
+                                                                    _t_ptr(grad_limits), _t_ptr(flags)),
+                        "mrs_tg_plan_estimate_times_baca_vjp")
+
+    def length_gate(self, seg_times, n_samples, sampling_dt, max_factor=3.0, min_factor=0.33, status=None, total=None,
+                    verdict=None):
+        """mrs_tg_plan_length_gate: per path the total of seg_times [sum S] (total [n_paths], written) and the nodelet's verdict
+        on n_samples [n_paths] (int32, the raw count a solve leaves) * sampling_dt against it (verdict [n_paths] int32, written:
+        FIND_REJECTED_CODE first when status [n_paths] is given and rejects, then FIND_REJECTED_TOO_LONG / _TOO_SHORT /
+        FIND_ACCEPTED; a factor <= 0 switches its side off); at least one output; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_length_gate(self._h, _t_ptr(seg_times), _t_ptr(n_samples), float(sampling_dt),
+                                                        float(max_factor), float(min_factor), _t_ptr(status), _t_ptr(total),
+                                                        _t_ptr(verdict)), "mrs_tg_plan_length_gate")
 
 
 class RoundRobin:

@@ -425,6 +425,55 @@ def estimate_times(plan, waypoints, limits):
     return _EstimateTimes.apply(plan, waypoints, limits)
 
 
+class _EstimateTimesBaca(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, waypoints, limits):
+        w = waypoints.detach().to(torch.float64).contiguous()
+        lim = limits.detach().to(torch.float64).contiguous()
+        if w.dim() != 2 or w.shape[0] != plan.n_segments + plan.n_paths or w.shape[1] != api.N_DIM:
+            raise ValueError("waypoints must be [sum V][4]")
+        if lim.dim() != 2 or lim.shape[0] != plan.n_paths or lim.shape[1] != 9:
+            raise ValueError("limits must be [n_paths][9]")
+        times = torch.empty(plan.n_segments, dtype=torch.float64, device=w.device)
+        plan.ctx.use_torch_stream()
+        plan.estimate_times_baca(w, lim, times)
+        ctx.plan = plan
+        ctx.save_for_backward(w, lim)
+        ctx.set_materialize_grads(False)
+        return times
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_times):
+        w, lim = ctx.saved_tensors
+        want_w, want_l = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if grad_times is None or not (want_w or want_l):
+            return None, None, None
+        gw = torch.empty_like(w) if want_w else None
+        gl = torch.empty_like(lim) if want_l else None
+        plan = ctx.plan
+        plan.ctx.use_torch_stream()   # (the autograd engine runs this on its own thread, on the forward's stream)
+        plan.estimate_times_baca_vjp(w, lim, grad_seg_times=grad_times.to(torch.float64).contiguous(), grad_waypoints=gw,
+                                     grad_limits=gl)
+        return None, gw, gl
+
+
+def estimate_times_baca(plan, waypoints, limits):
+    """seg_times [sum S] of Plan.estimate_times_baca: the Baca segment-time estimate (estimateSegmentTimesBaca, the reference's
+    yardstick for the length of a trajectory) -- differentiable in waypoints [sum V][4] (x, y, z, unwrapped heading) and limits
+    [n_paths][9] (float64 device tensors; entries 0 .. 7 are read, entry 8 gets a zero gradient).  The gradient holds every
+    branch of the forward fixed: the inclination regime of v, a and j, the two caps, the clamped corners, the 0.01 s floor
+    (zero gradient), whether the heading term wins and its own two branches; Plan.estimate_times_baca_vjp(flags=...) reports
+    them per segment.  "Is this plan as long as the estimate allows" is a loss on its sum:
+
+        >>> total = torch.zeros(plan.n_paths, dtype=torch.float64, device="cuda").index_add(0, path_of_segment,
+        ...                                                                                  estimate_times_baca(plan, wp, lim))
+        >>> torch.relu(n_samples * dt - 3.0 * total).sum().backward()
+
+    The verdict itself (Plan.length_gate) is not differentiable and has no wrapper here."""
+    return _EstimateTimesBaca.apply(plan, waypoints, limits)
+
+
 def _root(x, p):
     """x^(1/p) for x >= 0 with a finite gradient everywhere: 0 at x = 0 (where the root is never the active term of the
     scaling unless every term is 0, and the max(1, ...) then holds)"""

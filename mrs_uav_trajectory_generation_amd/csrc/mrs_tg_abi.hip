@@ -51,7 +51,7 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 14;  // kernel_id 0 .. 13 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 17;  // kernel_id 0 .. 16 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
   long long ev_count[kTimedKernels] = {};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
@@ -233,7 +233,7 @@ int mrs_tg_abi_version(void) { return MRS_TG_ABI_VERSION; }
 int mrs_tg_capabilities(void) {
   return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE |
          MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE | MRS_TG_CAP_DEVIATION |
-         MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE;
+         MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE | MRS_TG_CAP_BACA;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1189,6 +1189,48 @@ int mrs_tg_plan_waypoint_passage_vjp(mrs_tg_plan* plan, const double* samples, c
   ProfileScope ps(ctx, 13);
   HIP_TRY(ctx, mrs_tg::launch_waypoint_passage_vjp(plan->view, samples, n_samples, sample_capacity, wp_offsets, waypoints, status,
                                                    grad_miss, grad_fraction, grad_samples, grad_waypoints, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_estimate_times_baca(mrs_tg_plan* plan, const double* waypoints, const double* limits, double* seg_times_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!waypoints || !limits || !seg_times_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "waypoints_dev, limits_dev and seg_times_out_dev are required");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 14);
+  HIP_TRY(ctx, mrs_tg::launch_baca_times(plan->view, waypoints, limits, seg_times_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_estimate_times_baca_vjp(mrs_tg_plan* plan, const double* waypoints, const double* limits,
+                                        const double* grad_seg_times, double* grad_waypoints, double* grad_limits,
+                                        int32_t* flags) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!waypoints || !limits) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "waypoints_dev and limits_dev are required");
+  if (!grad_waypoints && !grad_limits && !flags)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "every output of mrs_tg_plan_estimate_times_baca_vjp is NULL");
+  if ((grad_waypoints || grad_limits) && !grad_seg_times)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_waypoints_out_dev and grad_limits_out_dev need grad_seg_times_dev");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 15);
+  HIP_TRY(ctx, mrs_tg::launch_baca_times_vjp(plan->view, waypoints, limits, grad_seg_times, grad_waypoints, grad_limits, flags,
+                                             ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_length_gate(mrs_tg_plan* plan, const double* seg_times, const int32_t* n_samples, double sampling_dt,
+                            double max_factor, double min_factor, const int32_t* status, double* total_out, int32_t* verdict_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!seg_times || !n_samples) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "seg_times_dev and n_samples_dev are required");
+  if (!total_out && !verdict_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "total_out_dev and verdict_out_dev are both NULL");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 16);
+  HIP_TRY(ctx, mrs_tg::launch_length_gate(plan->view, seg_times, n_samples, sampling_dt, max_factor, min_factor, status, total_out,
+                                          verdict_out, ctx->stream));
   return MRS_TG_OK;
 }
 

@@ -274,6 +274,16 @@ hipError_t launch_waypoint_passage_vjp(const BatchView& b, const double* samples
 // (may be NULL when only the terms are wanted); reads only, no workspace; timed as the kernel family of the pending ProfileScope
 hipError_t launch_estimate_times_vjp(const BatchView& b, const double* wp, const double* limits, const double* grad_times,
                                      double* grad_wp, double* grad_limits, int32_t* term, hipStream_t stream);
+// mrs_tg_plan_estimate_times_baca / mrs_tg_plan_estimate_times_baca_vjp / mrs_tg_plan_length_gate (mrs_tg_baca.hip): the Baca
+// segment-time estimate [sum S] of waypoints [sum V][4] under limits [n_paths][9]; its backward pass -- dL/dwaypoints, dL/dlimits
+// and the flags of every segment [sum S] (each may be NULL) from dL/dseg_times (may be NULL when only the flags are wanted); and
+// the length gate: per path the total of seg_times and the verdict on n_samples * dt (either may be NULL; status may be NULL).
+// Reads only, no workspace, no LDS; each timed as the kernel family of the pending ProfileScope
+hipError_t launch_baca_times(const BatchView& b, const double* wp, const double* limits, double* seg_times, hipStream_t stream);
+hipError_t launch_baca_times_vjp(const BatchView& b, const double* wp, const double* limits, const double* grad_times,
+                                 double* grad_wp, double* grad_limits, int32_t* flags, hipStream_t stream);
+hipError_t launch_length_gate(const BatchView& b, const double* seg_times, const int32_t* n_samples, double dt, double max_factor,
+                              double min_factor, const int32_t* status, double* total, int32_t* verdict, hipStream_t stream);
 // phase-split tile kernel (mrs_tg_tile.hip): small and medium batches whose per-path state fits in LDS
 bool tile_kernel_applies(const BatchView& b, bool fused);
 hipError_t launch_solve_tile(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,
