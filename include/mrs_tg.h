@@ -570,8 +570,8 @@ int mrs_tg_plan_evaluate_vjp(mrs_tg_plan* plan, const double* coeffs_dev, const 
  *   segment_max_out_dev [sum S]                   the maximum over the counted samples whose cursor is that segment (0
  *                                                 without any): the reference's segment_safe is segment_max <= max_deviation
  * With status_dev, a path with status <= 0 gets zeros and cursor -1; a path with n <= 1 scans nothing.  A deviation that is
- * not a number never becomes a maximum (the reference's `>`).  The arithmetic is the host's, operation by operation with
- * no fused multiply-add: the bits of mrs_tg_optimize_paths' own scan.  Every output element that belongs to the plan is
+ * not a number never becomes a maximum (the reference's `>`).  The distance is devq::dist (csrc/mrs_tg_deviation.hpp), no
+ * fused multiply-add, the function mrs_tg_optimize_paths' own scan (devq::validate) calls: the same bits.  Every output element that belongs to the plan is
  * written exactly once.  Device pointers (16-byte aligned), asynchronous on the context's stream. */
 int mrs_tg_plan_path_deviation(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev,
                                int32_t sample_capacity, const double* waypoints_dev, int32_t first_segment,
@@ -659,9 +659,9 @@ int mrs_tg_plan_estimate_times_vjp(mrs_tg_plan* plan, const double* waypoints_de
  *   count_out_dev [n_paths]        how many were reached: the reference's idxs.size()
  *   miss_out_dev [sum W]           m of the hit; 0.0 where not reached
  *   fraction_out_dev [sum W]       tau of the hit; 0.0 where not reached
- * With status_dev, a path with status <= 0 gets count 0, indices -1 and zeros; n <= 1 or W = 0 scans nothing.  The arithmetic
- * is the host's, operation by operation with no fused multiply-add: index and count are mrs_tg_waypoint_trajectory_idxs' on
- * the same samples.  Every output element that belongs to the plan is written exactly once, in the caller's path order.
+ * With status_dev, a path with status <= 0 gets count 0, indices -1 and zeros; n <= 1 or W = 0 scans nothing.  The hit
+ * test is passq::hit (csrc/mrs_tg_passage.hpp: devq::dist, no fused multiply-add), which mrs_tg_waypoint_trajectory_idxs calls too:
+ * index and count are its on the same samples.  Every output element that belongs to the plan is written exactly once, in the caller's path order.
  * Device pointers (16-byte aligned), asynchronous on the context's stream. */
 int mrs_tg_plan_waypoint_passage(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev,
                                  int32_t sample_capacity, const int32_t* wp_offsets_dev, const double* waypoints_dev,

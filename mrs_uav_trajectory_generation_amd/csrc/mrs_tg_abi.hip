@@ -1736,7 +1736,7 @@ int mrs_tg_find_trajectory(mrs_tg_ctx* ctx, const mrs_tg_waypoint* wps, int32_t 
     return fail(ctx, MRS_TG_ERR_NOMEM, "out of host memory for a path of %d waypoints", n_wp);
   }
   // accept >= 1 except MAXTIME(6), and -1 (src/mrs_trajectory_generation.cpp:1138-1149)
-  if (!pol::code_accepted(*status_out)) {
+  if (!mrs_tg::baca::code_accepted(*status_out)) {
     ctx->find_rejection = MRS_TG_FIND_REJECTED_CODE;
     ctx->last_error = "optimization failed with code " + std::to_string(*status_out);
     *n_samples_out = 0;
@@ -1746,8 +1746,8 @@ int mrs_tg_find_trajectory(mrs_tg_ctx* ctx, const mrs_tg_waypoint* wps, int32_t 
   // trajectory with more samples than samples_out holds is reported as capacity + 1: the count the check sees is then a
   // LOWER bound of the real one, enough to reject "too long" whenever capacity * dt exceeds the allowed length
   if (opt_in->sampling_dt > 0 && samples_out) {
-    const int verdict = pol::length_check(*n_samples_out, opt_in->sampling_dt, ctx->find_baca_total,
-                                          opt_in->max_trajectory_len_factor, opt_in->min_trajectory_len_factor);
+    const int verdict = mrs_tg::baca::length_check(*n_samples_out, opt_in->sampling_dt, ctx->find_baca_total,
+                                                   opt_in->max_trajectory_len_factor, opt_in->min_trajectory_len_factor);
     if (verdict != 0) {
       char msg[256];
       std::snprintf(msg, sizeof(msg), "trajectory sampling failed: the final trajectory sampling is too %s = %.2f, initial 'baca' "

@@ -1,9 +1,9 @@
 // mrs_tg_baca.hpp -- the Baca segment-time estimate as a plan step, its backward pass and the length gate
 // (mrs_tg_plan_estimate_times_baca, mrs_tg_plan_estimate_times_baca_vjp, mrs_tg_plan_length_gate; baca_times_kernel,
 // baca_times_vjp_kernel, length_gate_kernel).  The forward is estimateSegmentTimesBaca
-// (vertex.cpp:301-485 of the reference) as policy::estimate_times_baca (mrs_tg_policy_host.hpp) writes it, operation by
-// operation, contraction off; classify() below IS that forward -- the kernel's value is classify().value -- and beside the value
-// it says which branches were taken (MRS_TG_BACA_*):
+// (vertex.cpp:301-485 of the reference), operation by operation, contraction off; classify() below IS that forward -- the
+// kernel's value and the host's policy::estimate_times_baca (mrs_tg_policy_host.hpp) are both classify().value -- and beside
+// the value it says which branches were taken (MRS_TG_BACA_*):
 //   V_VERTICAL, A_VERTICAL, J_VERTICAL   |inclination| > atan2(L_v, L_h), decided separately for L = v, a, j
 //   T1_CAPPED, T2_CAPPED                 sqrt(2 distance / a_max) was the smaller (t > cap, strictly)
 //   DOT1_CLAMPED, DOT2_CLAMPED           the corner's cosine was negative (dot < 0, strictly): the coefficient is the constant 1
@@ -62,7 +62,7 @@ constexpr int kVVertical = 1, kAVertical = 2, kJVertical = 4, kT1Capped = 8, kT2
               kDot2Clamped = 64, kFloor = 128, kHeading = 256, kHeadingCruise = 512, kHeadingAcc = 1024;  // MRS_TG_BACA_*
 constexpr int kVerdictAccepted = 0, kVerdictCode = 1, kVerdictTooLong = 2, kVerdictTooShort = 3;           // MRS_TG_FIND_*
 
-// mrs_lib radians::diff as the host estimate writes it (policy::wrap_range, policy::radians_diff): angles into [0, 2 pi)
+// mrs_lib's wrap and radians::diff (angles into [0, 2 pi)); the policy layer's heading unwrap and interpolation use them too
 MRS_TG_HD inline double wrap_range(double a, double lo, double range) {
   MRS_TG_NO_CONTRACT
   double r = fmod(a - lo, range);
@@ -402,8 +402,24 @@ MRS_TG_HD inline void limit_gradient(const double* wp, const double* G, int S, c
   }
 }
 
-// baca_total_time + code_accepted + length_check of mrs_tg_policy_host.hpp for one path: the total from 0.0 in increasing
-// index; status null = no code to reject on
+// the nodelet's gate on the optimiser's code (mrs_trajectory_generation.cpp:1138-1149): >= 1 except 6 (MAXTIME), and -1
+MRS_TG_HD inline bool code_accepted(int status) { return (status >= 1 && status != 6) || status == -1; }
+
+// the length sanity check (:1178-1199): 0 = passes, +1 = "too long", -1 = "too short" (or the two codes the caller names: the
+// plan step's verdicts).  Only trajectories longer than one second are checked; a factor <= 0 switches its side of the check
+// off (the reference has no such switch: its parameters are always loaded, config/public/trajectory_generation.yaml:35-36)
+MRS_TG_HD inline int length_check(int n_samples, double dt, double total, double max_factor, double min_factor, int too_long = 1,
+                                  int too_short = -1) {
+  MRS_TG_NO_CONTRACT
+  const double len = (double)n_samples * dt;
+  if (!(len > 1.0)) return 0;
+  if (max_factor > 0 && len > max_factor * total) return too_long;
+  if (min_factor > 0 && len < min_factor * total) return too_short;
+  return 0;
+}
+
+// initial_total_time_baca, code_accepted and length_check for one path: the total from 0.0 in increasing index; status
+// null = no code to reject on
 struct Gate {
   double total;
   int verdict;
@@ -416,17 +432,12 @@ MRS_TG_HD inline Gate length_gate(const double* seg_times, int S, int n_samples,
   for (int j = 0; j < S; ++j) tot += seg_times[j];
   g.total = tot;
   g.verdict = kVerdictAccepted;
-  if (status) {
-    const int code = *status;
-    if (!((code >= 1 && code != 6) || code == -1)) {
-      g.verdict = kVerdictCode;
-      return g;
-    }
+  if (status && !code_accepted(*status)) {
+    g.verdict = kVerdictCode;
+    return g;
   }
-  const double len = (double)n_samples * dt;
-  if (!(len > 1.0)) return g;
-  if (max_factor > 0 && len > max_factor * tot) g.verdict = kVerdictTooLong;
-  else if (min_factor > 0 && len < min_factor * tot) g.verdict = kVerdictTooShort;
+  static_assert(kVerdictAccepted == 0, "length_check's `passes`");
+  g.verdict = length_check(n_samples, dt, tot, max_factor, min_factor, kVerdictTooLong, kVerdictTooShort);
   return g;
 }
 

@@ -5,9 +5,9 @@
 //   d_i     = dist(s_i, w_c, w_{c+1})          the deviation of sample i, c = c_i
 //   e_i     = dist(w_{c+1}, s_i, s_{i+1})      how close the step to the next sample comes to the next waypoint
 //   c_{i+1} = c_i + 1 if e_i < 0.05 and c_i < S - 1, else c_i;   c_0 = 0
-// dist is distFromSegment (:1533-1554) with the host's operations in the host's order (mrs_tg_policy_host.hpp's
-// dist_from_segment, the oracle's mto_dist_from_segment): no product is contracted into a fused multiply-add, so the CPU and
-// the GPU produce the same bits.  Plain double, __host__ __device__: tests/host/deviation_harness.cpp runs this file under g++.
+// dist is distFromSegment (:1533-1554) in the reference's operations and their order (the oracle's mto_dist_from_segment); it
+// is the only copy: the policy layer's host code and policy_validate_kernel call it, and validate() below is their scan.  No
+// product is contracted into a fused multiply-add, so the CPU and the GPU produce the same bits.  Plain double, __host__ __device__: tests/host/deviation_harness.cpp runs this file under g++.
 //
 // Backward, cursors and branches held fixed.  With p = s_i, a = w_c, b = w_{c+1}, d = d_i, g = dL/dd_i:
 //   coord < 0      dd/dp = (p - a)/d,  dd/da = -dd/dp,           dd/db = 0
@@ -28,26 +28,41 @@ using mrs_tg::accumulate;
 
 constexpr double kAdvanceDistance = 0.05;  // :1448, a constant of the reference
 
-// distFromSegment (:1533-1554): the distance of p from the segment s1 -> s2 (x, y, z; whatever follows is not read)
+// What distFromSegment (:1533-1554) forms before it branches, for p against the segment s1 -> s2 (x, y, z; whatever follows is
+// not read): the two difference vectors, the segment's length, its direction and the place of p's foot point along it.  dist,
+// dist_vjp and passq::fraction (mrs_tg_passage.hpp) all start from this one text.
+struct Foot {
+  double sv[3], d[3];  // s2 - s1, p - s1
+  double n[3];         // sv / len where len * len > 0, else sv
+  double len, coord;   // |sv|, n . d
+};
+MRS_TG_HD inline double norm3(const double (&v)[3]) {
+  MRS_TG_NO_CONTRACT
+  return sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+}
+MRS_TG_HD inline Foot foot(const double* p, const double* s1, const double* s2) {
+  MRS_TG_NO_CONTRACT
+  Foot f;
+  for (int k = 0; k < 3; ++k) f.n[k] = f.sv[k] = s2[k] - s1[k];
+  f.len = norm3(f.sv);
+  if (f.len * f.len > 0)
+    for (int k = 0; k < 3; ++k) f.n[k] /= f.len;
+  for (int k = 0; k < 3; ++k) f.d[k] = p[k] - s1[k];
+  f.coord = f.n[0] * f.d[0] + f.n[1] * f.d[1] + f.n[2] * f.d[2];
+  return f;
+}
+
+// distFromSegment (:1533-1554): the distance of p from the segment s1 -> s2
 MRS_TG_HD inline double dist(const double* p, const double* s1, const double* s2) {
   MRS_TG_NO_CONTRACT
-  const double sv0 = s2[0] - s1[0], sv1 = s2[1] - s1[1], sv2 = s2[2] - s1[2];
-  const double len = sqrt(sv0 * sv0 + sv1 * sv1 + sv2 * sv2);
-  double n0 = sv0, n1 = sv1, n2 = sv2;
-  if (len * len > 0) {
-    n0 /= len;
-    n1 /= len;
-    n2 /= len;
+  const Foot f = foot(p, s1, s2);
+  if (f.coord < 0) return norm3(f.d);
+  if (f.coord > f.len) {
+    const double e[3] = {p[0] - s2[0], p[1] - s2[1], p[2] - s2[2]};
+    return norm3(e);
   }
-  const double d0 = p[0] - s1[0], d1 = p[1] - s1[1], d2 = p[2] - s1[2];
-  const double coord = n0 * d0 + n1 * d1 + n2 * d2;
-  if (coord < 0) return sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-  if (coord > len) {
-    const double e0 = p[0] - s2[0], e1 = p[1] - s2[1], e2 = p[2] - s2[2];
-    return sqrt(e0 * e0 + e1 * e1 + e2 * e2);
-  }
-  const double f0 = p[0] - (s1[0] + n0 * coord), f1 = p[1] - (s1[1] + n1 * coord), f2 = p[2] - (s1[2] + n2 * coord);
-  return sqrt(f0 * f0 + f1 * f1 + f2 * f2);
+  const double e[3] = {p[0] - (s1[0] + f.n[0] * f.coord), p[1] - (s1[1] + f.n[1] * f.coord), p[2] - (s1[2] + f.n[2] * f.coord)};
+  return norm3(e);
 }
 
 // whether the cursor c of a path with S segments moves on behind sample s (next: the sample after it)
@@ -58,43 +73,61 @@ MRS_TG_HD inline bool advances(const double* next_waypoint, const double* s, con
 // whether sample i counts towards the maxima (:1437)
 MRS_TG_HD inline bool counted(int c, int first_segment, int S) { return c > 0 || first_segment != 0 || S + 1 <= 2; }
 
+// validateTrajectorySpatial (:1401-1455) for one path, one sample after the other: samples [n][4], waypoints [n_wp][4] (x, y, z
+// are read).  safe [n_wp - 1] is written in full: 0 where a counted sample of the segment strays further than max_deviation.
+struct Validation {
+  bool is_safe;
+  double max_deviation;  // of the counted samples
+};
+MRS_TG_HD inline Validation validate(const double* samples, int n, const double* waypoints, int n_wp, int first_segment,
+                                     double max_deviation, uint8_t* safe) {
+  const int S = n_wp - 1;
+  Validation v;
+  v.is_safe = true, v.max_deviation = 0.0;
+  for (int i = 0; i < S; ++i) safe[i] = 1;
+  int c = 0;
+  for (int i = 0; i + 1 < n && S >= 1; ++i) {
+    const double* s = samples + (size_t)i * 4;
+    const double* a = waypoints + (size_t)c * 4;
+    const double d = dist(s, a, a + 4);
+    const bool moves_on = advances(a + 4, s, s + 4, c, S);  // (in front of the store to safe[], which may alias the rows)
+    if (counted(c, first_segment, S)) {
+      if (d > v.max_deviation) v.max_deviation = d;
+      if (d > max_deviation) safe[c] = 0, v.is_safe = false;
+    }
+    if (moves_on) ++c;
+  }
+  return v;
+}
+
 // g * dd/dp, g * dd/da, g * dd/db of d = dist(p, a, b), the branch being the forward's
 MRS_TG_HD inline void dist_vjp(const double* p, const double* a, const double* b, double g, double (&gp)[3], double (&ga)[3],
                                double (&gb)[3]) {
   MRS_TG_NO_CONTRACT
   for (int k = 0; k < 3; ++k) gp[k] = ga[k] = gb[k] = 0.0;
   if (g == 0.0) return;
-  const double sv0 = b[0] - a[0], sv1 = b[1] - a[1], sv2 = b[2] - a[2];
-  const double len = sqrt(sv0 * sv0 + sv1 * sv1 + sv2 * sv2);
-  double n0 = sv0, n1 = sv1, n2 = sv2;
-  if (len * len > 0) {
-    n0 /= len;
-    n1 /= len;
-    n2 /= len;
-  }
-  const double d0 = p[0] - a[0], d1 = p[1] - a[1], d2 = p[2] - a[2];
-  const double coord = n0 * d0 + n1 * d1 + n2 * d2;
-  if (coord < 0) {
-    const double d = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+  const Foot f = foot(p, a, b);
+  if (f.coord < 0) {
+    const double d = norm3(f.d);
     if (d == 0.0) return;
-    gp[0] = g * (d0 / d), gp[1] = g * (d1 / d), gp[2] = g * (d2 / d);
+    for (int k = 0; k < 3; ++k) gp[k] = g * (f.d[k] / d);
     for (int k = 0; k < 3; ++k) ga[k] = 0.0 - gp[k];
     return;
   }
-  if (coord > len) {
-    const double e0 = p[0] - b[0], e1 = p[1] - b[1], e2 = p[2] - b[2];
-    const double d = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+  if (f.coord > f.len) {
+    const double e[3] = {p[0] - b[0], p[1] - b[1], p[2] - b[2]};
+    const double d = norm3(e);
     if (d == 0.0) return;
-    gp[0] = g * (e0 / d), gp[1] = g * (e1 / d), gp[2] = g * (e2 / d);
+    for (int k = 0; k < 3; ++k) gp[k] = g * (e[k] / d);
     for (int k = 0; k < 3; ++k) gb[k] = 0.0 - gp[k];
     return;
   }
-  const double f0 = p[0] - (a[0] + n0 * coord), f1 = p[1] - (a[1] + n1 * coord), f2 = p[2] - (a[2] + n2 * coord);
-  const double d = sqrt(f0 * f0 + f1 * f1 + f2 * f2);
+  const double e[3] = {p[0] - (a[0] + f.n[0] * f.coord), p[1] - (a[1] + f.n[1] * f.coord), p[2] - (a[2] + f.n[2] * f.coord)};
+  const double d = norm3(e);
   if (d == 0.0) return;
-  const double tau = len * len > 0 ? coord / len : 0.0;
+  const double tau = f.len * f.len > 0 ? f.coord / f.len : 0.0;
   const double rest = 1.0 - tau;
-  gp[0] = g * (f0 / d), gp[1] = g * (f1 / d), gp[2] = g * (f2 / d);
+  for (int k = 0; k < 3; ++k) gp[k] = g * (e[k] / d);
   for (int k = 0; k < 3; ++k) {
     ga[k] = 0.0 - rest * gp[k];
     gb[k] = 0.0 - tau * gp[k];

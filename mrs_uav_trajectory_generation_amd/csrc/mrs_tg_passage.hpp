@@ -4,8 +4,8 @@
 // waypoint cursor c: for the steps i = 0 .. n-2 of a path with the waypoints w_0 .. w_{W-1}, c = 0 at the start,
 //   m = dist(w_c, s_i, s_{i+1});   if m < 0.1:  index[c] = i, miss[c] = m, fraction[c] = tau, c = c + 1;   stop when c == W
 // dist is devq::dist of mrs_tg_deviation.hpp, unchanged.  tau is the place of the foot point on the step, from the very coord
-// and len that dist forms: 0 when coord < 0 or len * len == 0, 1 when coord > len, otherwise coord / len.  A distance that is
-// not a number is no hit.  Plain double, __host__ __device__, no product contracted into a fused multiply-add:
+// and len that dist forms (devq::foot): 0 when coord < 0 or len * len == 0, 1 when coord > len, otherwise coord / len.  A
+// distance that is not a number is no hit.  Plain double, __host__ __device__, no product contracted into a fused multiply-add:
 // tests/host/passage_harness.cpp runs this file under g++ and the kernels give its bits.
 //
 // Backward, indices and branches held fixed.  For a hit of p = w_k on the step a = s_i, b = s_{i+1} with the upstreams
@@ -33,19 +33,10 @@ constexpr double kPassDistance = 0.1;  // :1487, a constant of the reference
 // tau of the foot point of p on the step a -> b (x, y, z; whatever follows is not read)
 MRS_TG_HD inline double fraction(const double* p, const double* a, const double* b) {
   MRS_TG_NO_CONTRACT
-  const double sv0 = b[0] - a[0], sv1 = b[1] - a[1], sv2 = b[2] - a[2];
-  const double len = sqrt(sv0 * sv0 + sv1 * sv1 + sv2 * sv2);
-  double n0 = sv0, n1 = sv1, n2 = sv2;
-  if (len * len > 0) {
-    n0 /= len;
-    n1 /= len;
-    n2 /= len;
-  }
-  const double d0 = p[0] - a[0], d1 = p[1] - a[1], d2 = p[2] - a[2];
-  const double coord = n0 * d0 + n1 * d1 + n2 * d2;
-  if (coord < 0 || len * len == 0) return 0.0;
-  if (coord > len) return 1.0;
-  return coord / len;
+  const devq::Foot f = devq::foot(p, a, b);
+  if (f.coord < 0 || f.len * f.len == 0) return 0.0;
+  if (f.coord > f.len) return 1.0;
+  return f.coord / f.len;
 }
 
 // g * dtau/dp, g * dtau/da, g * dtau/db of tau = fraction(p, a, b), the branch being the forward's
@@ -54,28 +45,25 @@ MRS_TG_HD inline void fraction_vjp(const double* p, const double* a, const doubl
   MRS_TG_NO_CONTRACT
   for (int k = 0; k < 3; ++k) gp[k] = ga[k] = gb[k] = 0.0;
   if (g == 0.0) return;
-  const double sv[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
-  const double len = sqrt(sv[0] * sv[0] + sv[1] * sv[1] + sv[2] * sv[2]);
-  double n0 = sv[0], n1 = sv[1], n2 = sv[2];
-  if (len * len > 0) {
-    n0 /= len;
-    n1 /= len;
-    n2 /= len;
-  }
-  const double d[3] = {p[0] - a[0], p[1] - a[1], p[2] - a[2]};
-  const double coord = n0 * d[0] + n1 * d[1] + n2 * d[2];
-  if (coord < 0 || len * len == 0 || coord > len) return;
-  const double L2 = len * len;
-  const double tau = coord / len;
+  const devq::Foot f = devq::foot(p, a, b);
+  if (f.coord < 0 || f.len * f.len == 0 || f.coord > f.len) return;
+  const double L2 = f.len * f.len;
+  const double tau = f.coord / f.len;
   const double t2 = 2.0 * tau;
   for (int k = 0; k < 3; ++k) {
-    const double tp = sv[k] / L2;
-    const double tb = (d[k] - t2 * sv[k]) / L2;
+    const double tp = f.sv[k] / L2;
+    const double tb = (f.d[k] - t2 * f.sv[k]) / L2;
     const double ta = (0.0 - tp) - tb;
     gp[k] = g * tp;
     ga[k] = g * ta;
     gb[k] = g * tb;
   }
+}
+
+// the scan's hit test: whether the step a -> b takes the waypoint w; m: its distance from the step (not a number: no hit)
+MRS_TG_HD inline bool hit(const double* w, const double* a, const double* b, double& m) {
+  m = devq::dist(w, a, b);
+  return m < kPassDistance;
 }
 
 // The three rows of one hit: the miss part, then + the fraction part, per coordinate
@@ -99,8 +87,8 @@ inline int scan(const double* waypoints, int W, int wstride, const double* sampl
   for (int i = 0; i + 1 < n && c < W; ++i) {
     const double* w = waypoints + (size_t)c * wstride;
     const double* a = samples + (size_t)i * sstride;
-    const double m = devq::dist(w, a, a + sstride);
-    if (m < kPassDistance) {
+    double m;
+    if (hit(w, a, a + sstride, m)) {
       index[c] = i;
       miss[c] = m;
       fraction_out[c] = fraction(w, a, a + sstride);

@@ -11,9 +11,9 @@
 //                           against the Baca total (:1178-1199), then validateTrajectorySpatial as written -- a sequential
 //                           scan with a waypoint cursor -- on the samples where they are; what travels down is a few words
 //                           per path, one byte per segment, and the samples of the paths that are FINISHED.
-// The arithmetic of the scan is the host's, operation by operation (no contraction into fused multiply-adds: the decisions
-// `distance > max_deviation` and the reported maximum must be the bits mrs_tg_policy_host.hpp::validate_spatial produces;
-// tests/test_gpu_policy.py compares the two routes).
+// The gates are baca::code_accepted and baca::length_check (mrs_tg_baca.hpp) and the scan is devq::validate
+// (mrs_tg_deviation.hpp): the functions the host route of mrs_tg_policy_host.hpp calls, contraction off, so the decisions
+// `distance > max_deviation` and the reported maximum are the same bits on both routes (tests/test_gpu_policy.py compares them).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -55,76 +55,24 @@ __global__ __launch_bounds__(256) void policy_expand_kernel(int n_vertices, int 
   for (int e = 0; e < 10; ++e) out[e] = make_double2(val[2 * e], val[2 * e + 1]);
 }
 
-namespace {
-
-// distFromSegment (:1533-1554) with the host's operations in the host's order
-__device__ __forceinline__ double dist_from_segment_dev(const double* p, const double* s1, const double* s2) {
-#pragma clang fp contract(off)
-  const double sv0 = s2[0] - s1[0], sv1 = s2[1] - s1[1], sv2 = s2[2] - s1[2];
-  const double len = sqrt(sv0 * sv0 + sv1 * sv1 + sv2 * sv2);
-  double n0 = sv0, n1 = sv1, n2 = sv2;
-  if (len * len > 0) {
-    n0 /= len;
-    n1 /= len;
-    n2 /= len;
-  }
-  const double d0 = p[0] - s1[0], d1 = p[1] - s1[1], d2 = p[2] - s1[2];
-  const double coord = n0 * d0 + n1 * d1 + n2 * d2;
-  if (coord < 0) return sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-  if (coord > len) {
-    const double e0 = p[0] - s2[0], e1 = p[1] - s2[1], e2 = p[2] - s2[2];
-    return sqrt(e0 * e0 + e1 * e1 + e2 * e2);
-  }
-  const double f0 = p[0] - (s1[0] + n0 * coord), f1 = p[1] - (s1[1] + n1 * coord), f2 = p[2] - (s1[2] + n2 * coord);
-  return sqrt(f0 * f0 + f1 * f1 + f2 * f2);
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(64) void policy_validate_kernel(PolicyValidateArgs g) {
-#pragma clang fp contract(off)
   const int a = blockIdx.x * 64 + threadIdx.x;
   if (a >= g.n_paths) return;
-  const int s0 = g.seg_offsets[a], S = g.seg_offsets[a + 1] - s0, n_wp = S + 1;
+  const int s0 = g.seg_offsets[a], S = g.seg_offsets[a + 1] - s0;
   const int ns = g.n_samples[a], st = g.status[a];
-  bool ok = (st >= 1 && st != 6) || st == -1;  // :1138-1149
-  if (ok) {                                     // :1178-1199
-    const double len = (double)ns * g.dt;
-    if (len > 1.0 && ((g.max_len_factor > 0 && len > g.max_len_factor * g.baca_total[a]) ||
-                      (g.min_len_factor > 0 && len < g.min_len_factor * g.baca_total[a])))
-      ok = false;
-  }
-  if (ns > g.capacity) ok = false;
-  bool is_safe = true;
-  double max_dev = 0.0;
-  uint8_t* safe = g.safe_out + s0;
-  if (ok && !g.last_round) {  // validateTrajectorySpatial :1401-1455 (the last re-solve is not validated again, :729)
-    for (int i = 0; i < S; ++i) safe[i] = 1;
-    const double* wps = g.wp + (size_t)(s0 + a) * 4;   // (positions: x, y, z of a waypoint are what the scan reads)
-    const double* smp = g.samples + (size_t)a * g.capacity * 4;
-    int widx = 0;
-    for (int i = 0; i + 1 < ns; ++i) {
-      const double* sample = smp + (size_t)i * 4;
-      const double* next = sample + 4;
-      const double* w0 = wps + (size_t)widx * 4;
-      const double* w1 = w0 + 4;
-      const double d_seg = dist_from_segment_dev(sample, w0, w1);
-      const double d_end = dist_from_segment_dev(w1, sample, next);
-      if (widx > 0 || g.first_segment || n_wp <= 2) {
-        if (d_seg > max_dev) max_dev = d_seg;
-        if (d_seg > g.max_deviation) {
-          safe[widx] = 0;
-          is_safe = false;
-        }
-      }
-      if (d_end < 0.05 && widx < n_wp - 2) ++widx;
-    }
-  }
+  const bool ok = baca::code_accepted(st) && baca::length_check(ns, g.dt, g.baca_total[a], g.max_len_factor, g.min_len_factor) == 0 &&
+                  ns <= g.capacity;
+  devq::Validation v;
+  v.is_safe = true, v.max_deviation = 0.0;
+  if (ok && !g.last_round)  // (the last re-solve is not validated again, :729)
+    v = devq::validate(g.samples + (size_t)a * g.capacity * 4, ns, g.wp + (size_t)(s0 + a) * 4, S + 1, g.first_segment,
+                       g.max_deviation, g.safe_out + s0);
+  const bool is_safe = v.is_safe;
   const bool done = !ok || g.last_round || !(g.check_enabled && !is_safe);
   g.ok_out[a] = ok ? 1 : 0;
   g.ns_out[a] = ns;
   g.status_out[a] = st;
-  g.max_dev_out[a] = max_dev;
+  g.max_dev_out[a] = v.max_deviation;
   g.is_safe_out[a] = is_safe ? 1 : 0;
   g.ns_copy[a] = (ok && done) ? (ns < g.capacity ? ns : g.capacity) : 0;  // rows that travel: the finished paths' samples
 }

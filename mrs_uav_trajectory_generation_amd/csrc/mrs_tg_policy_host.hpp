@@ -5,6 +5,9 @@
 //   round) -> nlopt-code gate (:1138-1149) -> length sanity check against the Baca estimate (:1048-1056, :1178-1199) ->
 //   validateTrajectorySpatial (:1401-1455) -> mid-points into unsafe segments (:739-753) -> next round; optional
 //   findTrajectoryFallback (:1215-1395) and override_heading_atan2 (:1582-1597).
+// The arithmetic shared with the plan steps -- distance from a segment, the validation scan, the gates, the waypoint hit test,
+// the Baca estimate -- is not written here: it is called from the host-checkable kernel headers (mrs_tg_deviation.hpp,
+// mrs_tg_passage.hpp, mrs_tg_baca.hpp), which policy_validate_kernel calls too.
 // No HIP type or call appears here: mrs_tg_policy.hip instantiates optimize_paths() with the batched GPU solve and
 // mrs_tg_abi.hip's mrs_tg_find_trajectory uses the vertex builder, the Baca total and the two gates; the same header compiles
 // with g++ and is driven by tests/host/policy_host_harness.cpp with the CPU oracle as the solver on 16 threads under
@@ -30,7 +33,9 @@
 #include <sched.h>
 
 #include "../../include/mrs_tg.h"
+#include "mrs_tg_baca.hpp"
 #include "mrs_tg_knobs.hpp"
+#include "mrs_tg_passage.hpp"
 
 struct mrs_tg_ctx;
 
@@ -79,19 +84,10 @@ int policy_round_device(::mrs_tg_ctx* ctx, const PolicyRoundIn& in);  // (define
 
 namespace policy {
 
-inline double wrap_range(double a, double lo, double range) {
-  double r = std::fmod(a - lo, range);
-  if (r < 0) r += range;
-  return r + lo;
-}
-// mrs_lib radians::diff / radians::interp (angles in [0, 2 pi)), sradians::unwrap
-inline double radians_diff(double minuend, double subtrahend) {
-  const double two_pi = 2.0 * M_PI;
-  double d = wrap_range(minuend, 0.0, two_pi) - wrap_range(subtrahend, 0.0, two_pi);
-  if (d < -M_PI) d += two_pi;
-  else if (d >= M_PI) d -= two_pi;
-  return d;
-}
+using baca::radians_diff;  // mrs_lib radians::diff (angles into [0, 2 pi))
+using baca::wrap_range;
+
+// mrs_lib radians::interp (angles in [0, 2 pi)), sradians::unwrap
 inline double radians_interp(double from, double to, double coeff) {
   return wrap_range(from + coeff * radians_diff(to, from), 0.0, 2.0 * M_PI);
 }
@@ -110,99 +106,16 @@ inline double wrap_yaw(double y) {
   return std::atan2(2.0 * (w * z), 1.0 - 2.0 * (z * z));
 }
 
-inline double dist_from_segment(const double* p, const double* s1, const double* s2) {  // :1533-1554
-  const double sv[3] = {s2[0] - s1[0], s2[1] - s1[1], s2[2] - s1[2]};
-  const double len = std::sqrt(sv[0] * sv[0] + sv[1] * sv[1] + sv[2] * sv[2]);
-  double n[3] = {sv[0], sv[1], sv[2]};
-  if (len * len > 0) {
-    n[0] /= len;
-    n[1] /= len;
-    n[2] /= len;
-  }
-  const double d1[3] = {p[0] - s1[0], p[1] - s1[1], p[2] - s1[2]};
-  const double coord = n[0] * d1[0] + n[1] * d1[1] + n[2] * d1[2];
-  if (coord < 0) return std::sqrt(d1[0] * d1[0] + d1[1] * d1[1] + d1[2] * d1[2]);
-  if (coord > len) {
-    const double d2[3] = {p[0] - s2[0], p[1] - s2[1], p[2] - s2[2]};
-    return std::sqrt(d2[0] * d2[0] + d2[1] * d2[1] + d2[2] * d2[2]);
-  }
-  const double e[3] = {p[0] - (s1[0] + n[0] * coord), p[1] - (s1[1] + n[1] * coord), p[2] - (s1[2] + n[2] * coord)};
-  return std::sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
-}
-
 inline void interpolate_point(const double* a, const double* b, double coeff, double* out) {  // :1612-1625
   for (int k = 0; k < 3; ++k) out[k] = a[k] + coeff * (b[k] - a[k]);
   out[3] = radians_interp(a[3], b[3], coeff);
 }
 
-inline double limit_for_inclination(double inclinator, double lim_v, double lim_h) {  // vertex.cpp:337-353
-  if (inclinator > std::atan2(lim_v, lim_h) || inclinator < -std::atan2(lim_v, lim_h)) return std::fabs(lim_v / std::sin(inclinator));
-  return std::fabs(lim_h / std::cos(inclinator));
-}
-
-inline void unit3(const double* a, const double* b, double* u) {
-  double v[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
-  const double n = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-  if (n * n > 0) {
-    v[0] /= n;
-    v[1] /= n;
-    v[2] /= n;
-  }
-  u[0] = v[0];
-  u[1] = v[1];
-  u[2] = v[2];
-}
-
 // estimateSegmentTimesBaca, /root/reference/src/eth_trajectory_generation/vertex.cpp:301-485; wp [V][4] unwrapped
 inline void estimate_times_baca(int S, const double* wp, const double* lim, std::vector<double>& out) {
-  const double v_h = lim[0], v_v = lim[1], w_hdg = lim[2], a_h = lim[3], a_v = lim[4], a_hdg = lim[5], j_h = lim[6], j_v = lim[7];
-  const int V = S + 1;
-  out.assign(S, 0.0);
-  for (int i = 0; i < S; ++i) {
-    const double* s = wp + (size_t)i * 4;
-    const double* e = s + 4;
-    const double dx = e[0] - s[0], dy = e[1] - s[1], dz = e[2] - s[2];
-    const double distance = std::sqrt(dx * dx + dy * dy + dz * dz);
-    const double inclinator = std::atan2(dz, std::sqrt(dx * dx + dy * dy));
-    const double v_max = limit_for_inclination(inclinator, v_v, v_h);
-    const double a_max = limit_for_inclination(inclinator, a_v, a_h);
-    const double j_max = limit_for_inclination(inclinator, j_v, j_h);
-    double t1 = 0, t2 = 0;
-    const double full = (v_max / a_max) + (a_max / j_max);
-    if (i >= 1) {
-      double u1[3], u2[3];
-      unit3(wp + (size_t)(i - 1) * 4, s, u1);
-      unit3(s, e, u2);
-      const double dot = u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
-      t1 = (1 - (dot < 0 ? 0.0 : dot)) * full;
-    }
-    if (i == 0) t1 = full;
-    if (i == V - 2) t2 = full;
-    if (i < V - 2) {
-      double u1[3], u2[3];
-      unit3(s, e, u1);
-      unit3(e, wp + (size_t)(i + 2) * 4, u2);
-      const double dot = u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
-      t2 = (1 - (dot < 0 ? 0.0 : dot)) * full;
-    }
-    const double cap = std::sqrt(2 * distance / a_max);
-    t1 = std::min(t1, cap);
-    t2 = std::min(t2, cap);
-    double t = distance / v_max + t1 + t2;
-    if (t < 0.01) t = 0.01;
-    // heading rotation time (:457-480)
-    double dh = radians_diff(s[3], e[3]);
-    const double ang = std::fabs(dh);
-    double tv = 0, ta = 0;
-    if (w_hdg < (double)FLT_MAX && a_hdg < (double)FLT_MAX) {
-      const double reduced = (ang - 2 * (w_hdg * w_hdg) / a_hdg) / w_hdg;
-      tv = (reduced < 0) ? ang / w_hdg : reduced;
-      if (ang > M_PI / 4) ta = 2 * (w_hdg / a_hdg);
-    }
-    const double hf = 1.5 * (tv + ta);
-    if (hf > t) t = hf;
-    out[i] = t;
-  }
+  out.resize(S > 0 ? S : 0);
+  const baca::Thresholds th = baca::thresholds(lim);
+  for (int i = 0; i < S; ++i) out[i] = baca::classify(wp, i, S, lim, th).value;
 }
 
 // The policy's per-path host work (vertex building, Baca estimates, spatial validation, mid-point insertion) is independent
@@ -297,7 +210,7 @@ inline void preprocess(const mrs_tg_waypoint* in, int n_in, const mrs_tg_policy_
       for (int j = last_added + 1; j < i + 1; ++j) {
         const double* mid = in[j].coords;
         // quirk B3 of the reference: fabs() wraps the comparison, so the heading test is signed
-        if (dist_from_segment(mid, first, last) > o.path_straightener_max_deviation ||
+        if (devq::dist(mid, first, last) > o.path_straightener_max_deviation ||
             (radians_diff(first[3], mid[3]) > o.path_straightener_max_hdg_deviation) ||
             (radians_diff(last[3], mid[3]) > o.path_straightener_max_hdg_deviation)) {
           segment_is_ok = false;
@@ -321,28 +234,11 @@ inline void preprocess(const mrs_tg_waypoint* in, int n_in, const mrs_tg_policy_
 // validateTrajectorySpatial :1401-1455
 inline bool validate_spatial(const double* samples, int n_samples, const PathState& st, const mrs_tg_policy_options& o,
                       std::vector<uint8_t>& safe, double& max_dev) {
-  const int n_wp = st.n_wp;
-  safe.assign(std::max(n_wp - 1, 0), 1);
-  int widx = 0;
-  bool is_safe = true;
-  max_dev = 0;
-  for (int i = 0; i + 1 < n_samples; ++i) {
-    const double* sample = samples + (size_t)i * 4;
-    const double* next = sample + 4;
-    const double* s0 = st.wps.data() + (size_t)widx * 4;
-    const double* s1 = s0 + 4;
-    const double d_seg = dist_from_segment(sample, s0, s1);
-    const double d_end = dist_from_segment(s1, sample, next);
-    if (widx > 0 || o.max_deviation_first_segment || n_wp <= 2) {
-      if (d_seg > max_dev) max_dev = d_seg;
-      if (d_seg > o.max_deviation) {
-        safe[widx] = 0;
-        is_safe = false;
-      }
-    }
-    if (d_end < 0.05 && widx < n_wp - 2) ++widx;
-  }
-  return is_safe;
+  safe.resize(std::max(st.n_wp - 1, 0));
+  const devq::Validation v = devq::validate(samples, n_samples, st.wps.data(), st.n_wp, o.max_deviation_first_segment,
+                                            o.max_deviation, safe.data());
+  max_dev = v.max_deviation;
+  return v.is_safe;
 }
 
 inline void insert_midpoints(PathState& st, const std::vector<uint8_t>& safe, const mrs_tg_policy_options& o) {  // :739-753
@@ -453,21 +349,6 @@ inline double baca_total_time(int n_seg, const double* wp_unwrapped, const doubl
   for (double t : scratch) tot += t;
   return tot;
 }
-
-// the nodelet's gate on the optimiser's code (:1138-1149): >= 1 except 6 (MAXTIME), and -1
-inline bool code_accepted(int status) { return (status >= 1 && status != 6) || status == -1; }
-
-// the length sanity check (:1178-1199): 0 = passes, +1 = "too long", -1 = "too short".  Only trajectories longer than one
-// second are checked; a factor <= 0 switches its side of the check off (the reference has no such switch: its parameters
-// are always loaded, config/public/trajectory_generation.yaml:35-36)
-inline int length_check(int n_samples, double dt, double baca_total, double max_factor, double min_factor) {
-  const double len = (double)n_samples * dt;
-  if (!(len > 1.0)) return 0;
-  if (max_factor > 0 && len > max_factor * baca_total) return 1;
-  if (min_factor > 0 && len < min_factor * baca_total) return -1;
-  return 0;
-}
-
 
 // a Host with `int round(const PolicyRoundIn&)` and `bool device_round_enabled(size_t active_paths)` runs the rounds' batch-sized work on the device
 template <class H, class = void>
@@ -737,8 +618,8 @@ int optimize_paths(Host& host, int32_t n_paths, const int32_t* wp_offsets, const
       parallel_ranges(A, 128, [&](size_t a0, size_t a1) {
         for (size_t a = a0; a < a1; ++a) {
           const int p = active[a];
-          bool ok = !late && code_accepted(status[a]);  // :1138-1149
-          if (ok && length_check(ns[a], dt, st[p].baca_total, o.max_trajectory_len_factor, o.min_trajectory_len_factor) != 0) ok = false;  // :1178-1199
+          bool ok = !late && baca::code_accepted(status[a]);  // :1138-1149
+          if (ok && baca::length_check(ns[a], dt, st[p].baca_total, o.max_trajectory_len_factor, o.min_trajectory_len_factor) != 0) ok = false;  // :1178-1199
           if (ns[a] > sample_capacity) ok = false;
           st[p].ok = ok;
           st[p].n_samples = ok ? ns[a] : 0;
@@ -797,19 +678,16 @@ int optimize_paths(Host& host, int32_t n_paths, const int32_t* wp_offsets, const
   return MRS_TG_OK;
 }
 
-// getWaypointInTrajectoryIdxs :1461-1499 for one path: returns the number of indices written
+// getWaypointInTrajectoryIdxs :1461-1499 for one path: returns the number of indices written.  Nothing is read when there
+// is no waypoint.
 inline int32_t waypoint_trajectory_idxs(const double* samples, int32_t n_samples, const mrs_tg_waypoint* waypoints,
                                         int32_t n_waypoints, int32_t* idxs_out) {
   if (!samples || !waypoints || !idxs_out) return 0;
-  int widx = 0, n = 0;
-  for (int i = 0; i + 1 < n_samples; ++i) {
-    if (dist_from_segment(waypoints[widx].coords, samples + (size_t)i * 4, samples + (size_t)(i + 1) * 4) < 0.1) {
-      idxs_out[n++] = i;
-      ++widx;
-    }
-    if (widx == n_waypoints) break;
-  }
-  return n;
+  int32_t c = 0;
+  double miss;
+  for (int i = 0; i + 1 < n_samples && c < n_waypoints; ++i)
+    if (passq::hit(waypoints[c].coords, samples + (size_t)i * 4, samples + (size_t)(i + 1) * 4, miss)) idxs_out[c++] = i;
+  return c;
 }
 
 // mrs_tg_default_options: the reference's parameters where it has them

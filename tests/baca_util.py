@@ -68,7 +68,7 @@ def run_gate_harness(exe, gates, env=None):
 
 
 def gate_restatement(seg_times, n_samples, dt, max_factor, min_factor, status=None):
-    """baca_total_time's sum + code_accepted + length_check of csrc/mrs_tg_policy_host.hpp in Python floats (IEEE doubles,
+    """baca_total_time's sum (csrc/mrs_tg_policy_host.hpp) + code_accepted + length_check (csrc/mrs_tg_baca.hpp) in Python floats (IEEE doubles,
     nothing fused) -> (total, verdict)"""
     total = 0.0
     for t in np.asarray(seg_times, dtype=np.float64):

@@ -14,6 +14,7 @@ load_cases = functools.partial(hh.load_cases, "deviation_cases.json")
 build_harness = functools.partial(hh.build, "deviation_harness.cpp")   # (tmp_path, sanitize=False)
 EPS = 2.0 ** -52
 ADVANCE = 0.05
+VALIDATE_THRESHOLDS = (0.05, 0.2)   # the max_deviation values the harness runs devq::validate with
 
 
 def problem(waypoints, samples, n_samples=None, capacity=None, first_segment=1, status=1, upstream=None):
@@ -36,7 +37,8 @@ def scanned_rows(p):
 
 def run_harness(exe, problems, env=None):
     """-> per problem dict(cursor [k] int, deviation [k], max_deviation, argmax, segment_max [S], grad_samples [k][3],
-    grad_waypoints [S + 1][3], raw), k = the rows scanned (0 for a path with status <= 0: nothing is printed for it, its
+    grad_waypoints [S + 1][3], validate {threshold: (is_safe, safe [S] bool, maximum)} for VALIDATE_THRESHOLDS -- what
+    devq::validate returns --, raw), k = the rows scanned (0 for a path with status <= 0: nothing is printed for it, its
     gradients are zeros)"""
     lines = []
     for p in problems:
@@ -51,13 +53,19 @@ def run_harness(exe, problems, env=None):
         S, k = p["waypoints"].shape[0] - 1, scanned_rows(p)
         ks = k if p["status"] > 0 else 0
         x = line.split()
-        assert len(x) == 2 * ks + 2 + S + 3 * k + 3 * (S + 1), (len(x), ks, k, S)
+        nv = len(VALIDATE_THRESHOLDS) * (S + 2)
+        assert len(x) == 2 * ks + 2 + S + 3 * k + 3 * (S + 1) + nv, (len(x), ks, k, S)
+        x, tail = x[:len(x) - nv], x[len(x) - nv:]
+        validate = {}
+        for j, threshold in enumerate(VALIDATE_THRESHOLDS):
+            t = tail[j * (S + 2):(j + 1) * (S + 2)]
+            validate[threshold] = (t[0] == "1", np.array([v == "1" for v in t[1:S + 1]], dtype=bool), float(t[S + 1]))
         head = np.array([float(v) for v in x[:2 * ks]]).reshape(ks, 2)
         rest = [float(v) for v in x[2 * ks + 2:]]
         res.append(dict(cursor=head[:, 0].astype(np.int64), deviation=head[:, 1].copy(), max_deviation=float(x[2 * ks]),
                         argmax=int(x[2 * ks + 1]), segment_max=np.array(rest[:S]),
                         grad_samples=np.array(rest[S:S + 3 * k]).reshape(k, 3),
-                        grad_waypoints=np.array(rest[S + 3 * k:]).reshape(S + 1, 3), raw=line))
+                        grad_waypoints=np.array(rest[S + 3 * k:]).reshape(S + 1, 3), validate=validate, raw=line))
     return res
 
 

@@ -10,8 +10,9 @@
 //   S n_samples capacity first_segment status, waypoints [S + 1][3], samples [m][3] with m = min(n_samples, capacity),
 //   upstream [max(m - 1, 0)]
 // Output per path, one line: per scanned sample its cursor and its deviation; the maximum and its index; the segment
-// maxima [S]; dL/dsamples [max(m - 1, 0)][3]; dL/dwaypoints [S + 1][3].  status <= 0: nothing is scanned.  Doubles are printed
-// with 17 significant digits: the bits survive.
+// maxima [S]; dL/dsamples [max(m - 1, 0)][3]; dL/dwaypoints [S + 1][3]; then what devq::validate -- the scan of the policy
+// layer's host route and of policy_validate_kernel -- returns for max_deviation 0.05 and 0.2: is_safe, safe [S], the maximum.
+// status <= 0: nothing is scanned.  Doubles are printed with 17 significant digits: the bits survive.
 #include <cstdio>
 #include <vector>
 
@@ -58,6 +59,16 @@ int main() {
     for (double x : seg_max) std::printf("%.17g ", x);
     for (double x : gs) std::printf("%.17g ", x);
     for (double x : gw) std::printf("%.17g ", x);
+    std::vector<double> w4((size_t)(S + 1) * 4, 0.0), s4((size_t)m * 4, 0.0);  // (validate reads rows of four)
+    for (size_t e = 0; e < w.size(); ++e) w4[e / 3 * 4 + e % 3] = w[e];
+    for (size_t e = 0; e < s.size(); ++e) s4[e / 3 * 4 + e % 3] = s[e];
+    for (double threshold : {0.05, 0.2}) {
+      std::vector<uint8_t> safe(S, 0);
+      const dq::Validation v = dq::validate(s4.data(), status > 0 ? m : 0, w4.data(), S + 1, first, threshold, safe.data());
+      std::printf("%d ", v.is_safe ? 1 : 0);
+      for (uint8_t f : safe) std::printf("%d ", (int)f);
+      std::printf("%.17g ", v.max_deviation);
+    }
     std::printf("\n");
   }
 }

@@ -91,6 +91,8 @@ def test_forward_is_the_oracles_scan_in_the_same_bits(harness):
         scanned += len(o["cursor"])
         for threshold in (0.05, 0.2):
             ok, safe, mx = du.oracle_validate(po, p, threshold)
+            v_ok, v_safe, v_mx = r["validate"][threshold]   # devq::validate itself: the policy layer's scan on both routes
+            assert v_ok == ok and np.array_equal(v_safe, safe) and du.same_bits(v_mx, mx), (name, threshold)
             assert du.same_bits(r["max_deviation"], mx), (name, threshold)
             assert np.array_equal(r["segment_max"] <= threshold, safe), (name, threshold)
             assert ok == bool(np.all(r["segment_max"] <= threshold)), (name, threshold)

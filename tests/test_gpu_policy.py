@@ -174,8 +174,9 @@ def test_device_rounds_give_the_bits_of_the_host_rounds(gpu_ctx, tmp_path):
     """Round 6: the batch-sized work of a policy round -- vertex expansion, the two gates of findTrajectory, the scan of
     validateTrajectorySpatial (/root/reference/src/mrs_trajectory_generation.cpp:923-977, 1138-1149, 1178-1199, 1401-1455) -- runs on
     the device (mrs_tg_policy_dev.hip) from 64 active requests on; MRS_TG_POLICY_DEVICE=0 (read once per process: a child process)
-    keeps it on the policy's host threads as until round 5, MRS_TG_POLICY_DEVICE=1 sends single requests there too.  Same decisions, same deviations, same samples: bit for bit on every request (the arithmetic
-    of the scan is the host's, operation by operation).  Rows of the caller's sample array beyond a request's n_samples are not
+    keeps it on the policy's host threads as until round 5, MRS_TG_POLICY_DEVICE=1 sends single requests there too.  Same decisions, same deviations, same samples: bit for bit on every request (both routes
+    call one function for the scan, devq::validate of csrc/mrs_tg_deviation.hpp, and one pair for the gates, baca::code_accepted and
+    baca::length_check of csrc/mrs_tg_baca.hpp).  Rows of the caller's sample array beyond a request's n_samples are not
     compared: the host route leaves earlier rounds' longer trajectories there, the device route brings down the final one only."""
     import os
     import subprocess
@@ -244,3 +245,106 @@ def test_device_route_on_small_batches_with_initial_states_stop_at_and_relaxed_h
             n = int(out["n_samples_d%d" % d][p])
             assert np.array_equal(out["samples_d%d" % d][p, :n], dev["samples_d%d" % d][p, :n]), (p, d)
         assert out["success_d%d" % d].sum() >= 36
+
+
+# ---- the edges of the scan and of the two gates on the device route.  devq::validate, baca::code_accepted and
+# baca::length_check (csrc/mrs_tg_deviation.hpp, csrc/mrs_tg_baca.hpp) are what both routes call; these eight requests take the
+# branches the batches above reach rarely or never, each chosen by what the ORACLE does with it.
+EDGE_CAPACITY = 1024
+EDGE_TIGHT_DEVIATION = 0.01
+EDGE_GROUPS = ("two_waypoints", "first_segment_off", "tight", "too_long", "too_short", "length_unchecked")
+EDGE_ROUTE_CHILD = r"""
+import sys
+sys.path.insert(0, %r)
+import numpy as np
+from mrs_uav_trajectory_generation_amd import api
+from tests.test_gpu_policy import _edge_requests
+ctx = api.Context(0)
+np.savez(sys.argv[1], **_edge_requests(ctx))
+"""
+
+
+def _edge_moving_start(p):
+    return dict(heading=p[0, 3], velocity=[0.3, -0.2, 0.1, 0.0], acceleration=[0.0] * 4, jerk=[0.0] * 4)
+
+
+def _edge_cases():
+    """group -> (paths, initial states or None, policy overrides of the product, the same for the oracle).  The oracle has no
+    `factor <= 0 switches the side off`: its equivalent of both factors 0 is a maximum no length reaches and the minimum 0."""
+    two = [pr.random_box_waypoints(1, s) for s in (7002, 7007)]
+    three = [pr.random_walk_waypoints(2, s) for s in (7100, 7106)]
+    gated = [pr.random_box_waypoints(4, 7300)]
+    return {
+        "two_waypoints": (two, [_edge_moving_start(p) for p in two], dict(max_deviation_first_segment=0),
+                          dict(max_deviation_first_segment=0)),
+        "first_segment_off": (three, None, dict(max_deviation_first_segment=0), dict(max_deviation_first_segment=0)),
+        "tight": ([pr.random_box_waypoints(3, 7209)], None, dict(max_deviation=EDGE_TIGHT_DEVIATION),
+                  dict(max_deviation=EDGE_TIGHT_DEVIATION)),
+        "too_long": (gated, None, dict(max_trajectory_len_factor=0.5), dict(max_trajectory_len_factor=0.5)),
+        "too_short": (gated, None, dict(min_trajectory_len_factor=2.0), dict(min_trajectory_len_factor=2.0)),
+        "length_unchecked": (gated, None, dict(max_trajectory_len_factor=0.0, min_trajectory_len_factor=0.0),
+                             dict(max_trajectory_len_factor=1e300, min_trajectory_len_factor=0.0)),
+    }
+
+
+def _edge_requests(ctx):
+    out = {}
+    for name, (paths, inits, overrides, _) in _edge_cases().items():
+        r = api.optimize_paths(ctx, paths, initial_states=inits, policy=api.default_policy_options(**overrides),
+                               sample_capacity=EDGE_CAPACITY)
+        for k, v in r.items():
+            out["%s_%s" % (k, name)] = v
+    return out
+
+
+def test_device_route_on_the_scan_s_and_the_gates_edge_requests(gpu_ctx, tmp_path):
+    """Eight requests through MRS_TG_POLICY_DEVICE=1 (policy_validate_kernel) in a child process against the host route of this
+    process, bit for bit, and against the oracle in success, iterations and n_waypoints: two 2-waypoint paths with
+    max_deviation_first_segment = 0 (only `n_wp <= 2` makes their samples count), two 3-waypoint paths with
+    max_deviation_first_segment = 0, one 4-waypoint path under a max_deviation that subdivides it in every round, and one path
+    under three policies -- rejected as too long, rejected as too short, both factors 0 (neither side checked).  That each
+    request takes its branch is asserted on the oracle's own result."""
+    import os
+    import subprocess
+    import sys
+    cases = _edge_cases()
+    assert tuple(cases) == EDGE_GROUPS and sum(len(c[0]) for c in cases.values()) == 8
+    oracle = {}
+    for name, (paths, inits, _, ref_overrides) in cases.items():
+        oracle[name] = [po.optimize_path(p, initial_state=inits[q] if inits else None, limits=pr.DEFAULT_LIMITS,
+                                         policy=po.default_policy(**ref_overrides), capacity=EDGE_CAPACITY)
+                        for q, p in enumerate(paths)]
+    # ---- the oracle takes the named branches
+    for p, o in zip(cases["two_waypoints"][0], oracle["two_waypoints"]):
+        assert p.shape[0] == 2 and o["success"] == 1
+        assert o["iterations"] >= 1 and o["n_waypoints"] >= 3   # (cursor 0, first segment off: counted through n_wp <= 2 alone)
+    for p, o in zip(cases["first_segment_off"][0], oracle["first_segment_off"]):
+        on = po.optimize_path(p, limits=pr.DEFAULT_LIMITS, policy=po.default_policy(max_deviation_first_segment=1),
+                              capacity=EDGE_CAPACITY)
+        assert p.shape[0] == 3 and o["success"] == 1 and on["success"] == 1
+        assert o["max_deviation"] < on["max_deviation"]          # (the first segment's samples were left out)
+    tight = oracle["tight"][0]
+    assert cases["tight"][0][0].shape[0] == 4 and tight["success"] == 1 and tight["iterations"] >= 3
+    assert tight["iterations"] == po.default_policy().max_deviation_iterations    # subdivided until the last round
+    gated = cases["too_long"][0][0]
+    for name, rejection in (("too_long", 2), ("too_short", 3), ("length_unchecked", 0)):
+        f = po.find_trajectory(gated, limits=pr.DEFAULT_LIMITS, policy=po.default_policy(**cases[name][3]), capacity=EDGE_CAPACITY)
+        assert f["rejection"] == rejection and f["raw_n_samples"] * 0.2 > 1.0, (name, f["rejection"])
+        assert oracle[name][0]["success"] == (1 if rejection == 0 else 0), name
+    # ---- host route of this process, device route of a child, bit for bit
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = _edge_requests(gpu_ctx)
+    dev_path = str(tmp_path / "edge_device_route.npz")
+    subprocess.run([sys.executable, "-c", EDGE_ROUTE_CHILD % root, dev_path], check=True, cwd=root, timeout=600,
+                   env=dict(os.environ, MRS_TG_POLICY_DEVICE="1"))
+    dev = np.load(dev_path)
+    for name in EDGE_GROUPS:
+        for k in ("success", "n_samples", "n_waypoints", "iterations", "max_deviation"):
+            assert np.array_equal(out["%s_%s" % (k, name)], dev["%s_%s" % (k, name)]), (k, name)
+        for q, o in enumerate(oracle[name]):
+            n = int(out["n_samples_" + name][q])
+            assert np.array_equal(out["samples_" + name][q, :n], dev["samples_" + name][q, :n]), (name, q)
+            got = tuple(int(out["%s_%s" % (k, name)][q]) for k in ("success", "iterations", "n_waypoints"))
+            print("EDGE %s[%d]: success, iterations, n_waypoints %s, oracle %s" % (name, q, got,
+                                                                                 (o["success"], o["iterations"], o["n_waypoints"])))
+            assert got == (o["success"], o["iterations"], o["n_waypoints"]), (name, q)

@@ -110,6 +110,39 @@ def test_forward_is_the_oracles_scan_in_the_same_bits(harness):
     assert reached > 400 and reached < wanted
 
 
+def test_library_host_scan_at_its_empty_and_last_step_edges():
+    """mrs_tg_waypoint_trajectory_idxs (the policy layer's host scan, written with passq::hit) against
+    mto_waypoint_trajectory_idxs: no waypoint (0, and nothing read), one waypoint with 0, 1 and 2 samples, and a path whose last
+    waypoint is taken by the last step.  Entries behind the count are left alone.  Needs the built library (build() of
+    __graft_entry__.py), as the GPU tests do, and no GPU: without it this test fails rather than skips, since the function under
+    test exists nowhere else."""
+    import ctypes as C
+    from mrs_uav_trajectory_generation_amd import api
+    L = api.load_library()
+
+    def host(samples3, n, waypoints3):
+        smp = pu._pad4(np.asarray(samples3, dtype=np.float64).reshape(-1, 3))
+        wps = pu._pad4(np.asarray(waypoints3, dtype=np.float64).reshape(-1, 3))
+        arr, _ = api._waypoint_array([wps if len(wps) else np.zeros((1, 4))])
+        idx = np.full(len(wps) + 4, -7, dtype=np.int32)
+        k = L.mrs_tg_waypoint_trajectory_idxs(api._np_ptr(smp if len(smp) else np.zeros((1, 4))), n,
+                                              arr.ctypes.data_as(C.POINTER(api.Waypoint)), len(wps), api._np_ptr(idx))
+        assert np.all(idx[k:] == -7)
+        return k, idx[:k].tolist(), smp, wps
+
+    walk = pu.straight(12)
+    assert host(walk, 12, np.zeros((0, 3)))[:2] == (0, [])          # W = 0: nothing to pass (the waypoint array is not read)
+    one = [[0.3, 0.3, 0.0]]
+    last = [[0.3, 0.3, 0.0], [1.3, 0.32, 0.0], [pu.STEP * 10.5, 0.3, 0.02]]   # w_2 sits on the step 10 -> 11, the last one
+    for n, wps in ((0, one), (1, one), (2, one), (12, one), (12, last), (11, last)):
+        k, idx, smp, w4 = host(walk[:max(n, 0)], n, wps)
+        o = pu.oracle_scan_rows(po, w4, smp if n else np.zeros((1, 4)), n)
+        assert k == o["count"] and idx == o["index"][:k].tolist(), (n, len(wps))
+        if (n, len(wps)) in ((0, 1), (1, 1), (12, 3), (11, 3)):
+            assert k == {(0, 1): 0, (1, 1): 0, (12, 3): 3, (11, 3): 2}[(n, len(wps))], (n, len(wps), k)
+    assert host(walk, 12, last)[1][-1] == 10
+
+
 def _one(p, a, b, **kw):
     return pu.problem([p], [a, b], **kw)
 
