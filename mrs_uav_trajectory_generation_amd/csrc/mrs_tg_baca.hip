@@ -1,6 +1,6 @@
 // mrs_tg_baca.hip -- the Baca segment-time estimate as a plan step (mrs_tg_plan_estimate_times_baca), its backward pass
 // (mrs_tg_plan_estimate_times_baca_vjp) and the length gate (mrs_tg_plan_length_gate); mrs_tg_baca.hpp, DESIGN.md section 4f.
-// baca_times_kernel: one lane per segment, the lane-to-path map of estimate_times_kernel; the lane reads rows i - 1 .. i + 2 of
+// baca_times_kernel: one lane per segment, the lane-to-path map of mrs_tg_batch.hpp; the lane reads rows i - 1 .. i + 2 of
 // its own path.  baca_times_vjp_kernel: one launch, two kinds of lanes.  The first sum V lanes take one vertex each: the lane
 // recomputes its at most four segments from rows v - 3 .. v + 3 of its own path with the forward's own expressions, sums their
 // parts in the header's order and writes its 32-byte gradient row and the flags of the segment that starts at it.  The n_paths
@@ -31,24 +31,6 @@ namespace {
 
 constexpr int kBacaThreads = 256;
 
-// the largest p with first[p] <= x, first[p] = seg_offsets[p] + extra * p (extra 1: a path's first vertex; 0: its first
-// segment): estimate_times_kernel's map, a division for uniform batches, a binary search over seg_offsets otherwise
-__device__ __forceinline__ int path_of(const BatchView& b, int x, int extra) {
-  if (b.uniform_S > 0) return x / (b.uniform_S + extra);
-  int lo = 0, hi = b.n_paths;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (b.seg_offsets[mid] + extra * mid <= x) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ int first_segment(const BatchView& b, int p) { return b.uniform_S > 0 ? p * b.uniform_S : b.seg_offsets[p]; }
-__device__ __forceinline__ int segments_of(const BatchView& b, int p, int seg0) {
-  return b.uniform_S > 0 ? b.uniform_S : b.seg_offsets[p + 1] - seg0;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(kBacaThreads) void baca_times_kernel(BatchView b, const double* __restrict__ wp,
@@ -56,7 +38,7 @@ __global__ __launch_bounds__(kBacaThreads) void baca_times_kernel(BatchView b, c
                                                                   double* __restrict__ seg_times) {
   const int idx = (int)blockIdx.x * kBacaThreads + (int)threadIdx.x;
   if (idx >= b.n_segments) return;
-  const int p = path_of(b, idx, 0);
+  const int p = path_of_segment(b, idx);
   const int seg0 = first_segment(b, p);
   const int S = segments_of(b, p, seg0);
   const double* lim = limits + (size_t)p * baca::kLimits;
@@ -74,7 +56,7 @@ __global__ __launch_bounds__(kBacaThreads) void baca_times_vjp_kernel(BatchView 
   if (idx < n_vertices) {
     if (!grad_wp && !flags) return;
     const int v = idx;
-    const int p = path_of(b, v, 1);
+    const int p = path_of_vertex(b, v);
     const int seg0 = first_segment(b, p);
     const int S = segments_of(b, p, seg0);
     const int j = v - (seg0 + p);  // the vertex within its path, 0 .. S
@@ -117,7 +99,7 @@ __global__ __launch_bounds__(kBacaThreads) void length_gate_kernel(BatchView b, 
 
 hipError_t launch_baca_times(const BatchView& b, const double* wp, const double* limits, double* seg_times, hipStream_t stream) {
   if (b.n_segments == 0) return hipSuccess;
-  MRS_TG_LAUNCH_TIMED(baca_times_kernel, dim3((unsigned)((b.n_segments + kBacaThreads - 1) / kBacaThreads)), dim3(kBacaThreads), 0,
+  MRS_TG_LAUNCH_TIMED(baca_times_kernel, dim3(cdiv(b.n_segments, kBacaThreads)), dim3(kBacaThreads), 0,
                       stream, b, wp, limits, seg_times);
   return hipGetLastError();
 }
@@ -126,7 +108,7 @@ hipError_t launch_baca_times_vjp(const BatchView& b, const double* wp, const dou
                                  double* grad_wp, double* grad_limits, int32_t* flags, hipStream_t stream) {
   if (b.n_paths <= 0) return hipSuccess;
   const long long lanes = (long long)b.n_segments + 2LL * b.n_paths;
-  MRS_TG_LAUNCH_TIMED(baca_times_vjp_kernel, dim3((unsigned)((lanes + kBacaThreads - 1) / kBacaThreads)), dim3(kBacaThreads), 0,
+  MRS_TG_LAUNCH_TIMED(baca_times_vjp_kernel, dim3(cdiv(lanes, kBacaThreads)), dim3(kBacaThreads), 0,
                       stream, b, wp, limits, grad_times, grad_wp, grad_limits, flags);
   return hipGetLastError();
 }
@@ -134,7 +116,7 @@ hipError_t launch_baca_times_vjp(const BatchView& b, const double* wp, const dou
 hipError_t launch_length_gate(const BatchView& b, const double* seg_times, const int32_t* n_samples, double dt, double max_factor,
                               double min_factor, const int32_t* status, double* total, int32_t* verdict, hipStream_t stream) {
   if (b.n_paths <= 0) return hipSuccess;
-  MRS_TG_LAUNCH_TIMED(length_gate_kernel, dim3((unsigned)((b.n_paths + kBacaThreads - 1) / kBacaThreads)), dim3(kBacaThreads), 0,
+  MRS_TG_LAUNCH_TIMED(length_gate_kernel, dim3(cdiv(b.n_paths, kBacaThreads)), dim3(kBacaThreads), 0,
                       stream, b, seg_times, n_samples, dt, max_factor, min_factor, status, total, verdict);
   return hipGetLastError();
 }

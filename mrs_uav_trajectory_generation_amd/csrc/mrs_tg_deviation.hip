@@ -17,40 +17,13 @@
 #include "mrs_tg_device.hpp"
 #include "mrs_tg_deviation.hpp"
 #include "mrs_tg_launch.h"
+#include "mrs_tg_pathwave.hpp"
 
 namespace mrs_tg {
 
 namespace {
 
-typedef double dev_pair __attribute__((ext_vector_type(2)));
-
 constexpr int kDevTileStride = 7;  // doubles between the parked rows [6] of two samples (odd: no bank is hit twice by a row)
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-
-// x, y, z of sample i of a path (zeros behind its n samples)
-__device__ __forceinline__ void load_sample(const double* __restrict__ rows, int i, int n, double (&s)[3]) {
-  s[0] = s[1] = s[2] = 0.0;
-  if (i < n) {
-    const dev_pair* __restrict__ r = reinterpret_cast<const dev_pair*>(rows + (size_t)i * 4);
-    const dev_pair lo = r[0];
-    s[0] = lo.x, s[1] = lo.y, s[2] = rows[(size_t)i * 4 + 2];
-  }
-}
-
-// the sample behind every lane's own: the next lane's, and for lane 63 the first of the next chunk
-__device__ __forceinline__ void neighbour(const double (&cur)[3], const double (&nxt)[3], int lane, double (&nx)[3]) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double down = __shfl_down(cur[k], 1);
-    const double seam = __shfl(nxt[k], 0);
-    nx[k] = lane == 63 ? seam : down;
-  }
-}
 
 // The cursors of a chunk.  c: the cursor at the chunk's first sample, wavefront-uniform; on return the cursor at the next
 // chunk's first sample.  scanned: whether the lane holds a sample of the scan (i < n - 1).  Returns the lane's cursor (-1
@@ -93,23 +66,21 @@ __global__ __launch_bounds__(64) void path_deviation_kernel(BatchView b, const d
   const int lane = threadIdx.x;
   const PathRef pr = path_at(b, blockIdx.x);
   const int S = pr.S;
-  const bool live = status == nullptr || status[pr.p] > 0;
-  int n = live ? min(n_samples[pr.p], capacity) : 0;
-  n = n < 0 ? 0 : n;
+  const int n = live_samples(path_live(status, pr.p), n_samples, pr.p, capacity);
   for (int e = lane; e < 3 * (S + 1); e += 64) s_w[e] = waypoints[(size_t)(pr.v0 + e / 3) * 4 + e % 3];
   for (int i = lane; i < S; i += 64) s_m[i] = 0.0;
   const size_t row0 = (size_t)pr.p * (size_t)capacity;
   const double* __restrict__ rows = samples + row0 * 4;
   double cur[3];
-  load_sample(rows, lane, n, cur);
+  load_xyz(rows, lane, n, cur);
   wave_lds_barrier();
   int c = 0, run_arg = -1;
   double run_max = 0.0;
   for (int k0 = 0; k0 < n - 1; k0 += 64) {
     const int i = k0 + lane;
     double nxt[3], nx[3];
-    load_sample(rows, i + 64, n, nxt);
-    neighbour(cur, nxt, lane, nx);
+    load_xyz(rows, i + 64, n, nxt);
+    seam_neighbour(cur, nxt, lane, nx);
     const bool scanned = i < n - 1;
     const int c_first = c;
     const int mine = resolve_cursors(s_w, cur, nx, scanned, lane, S, c);
@@ -165,7 +136,8 @@ __global__ __launch_bounds__(64) void path_deviation_vjp_kernel(BatchView b, con
   const int lane = threadIdx.x;
   const PathRef pr = path_at(b, blockIdx.x);
   const int S = pr.S;
-  const bool live = status == nullptr || status[pr.p] > 0;
+  // live_samples of mrs_tg_pathwave.hpp, written out: through the function this kernel gets another register allocation
+  const bool live = path_live(status, pr.p);
   int n = live ? min(n_samples[pr.p], capacity) : 0;
   n = n < 0 ? 0 : n;
   for (int e = lane; e < 3 * (S + 1); e += 64) {
@@ -175,7 +147,7 @@ __global__ __launch_bounds__(64) void path_deviation_vjp_kernel(BatchView b, con
   const size_t row0 = (size_t)pr.p * (size_t)capacity;
   const double* __restrict__ rows = samples + row0 * 4;
   double cur[3];
-  load_sample(rows, lane, n, cur);
+  load_xyz(rows, lane, n, cur);
   wave_lds_barrier();
   const int slot = min(lane, 5);  // lanes 0..2: the waypoint at the cursor, 3..5: the one behind it (the others follow lane 5 and store nothing)
   const bool owns = lane < 6;
@@ -185,19 +157,13 @@ __global__ __launch_bounds__(64) void path_deviation_vjp_kernel(BatchView b, con
     const int i = k0 + lane;
     const bool scanned = i < n - 1;
     double nxt[3], nx[3];
-    load_sample(rows, i + 64, n, nxt);
+    load_xyz(rows, i + 64, n, nxt);
     const double g = scanned ? grad_deviation[row0 + i] : 0.0;
-    neighbour(cur, nxt, lane, nx);
+    seam_neighbour(cur, nxt, lane, nx);
     const int mine = resolve_cursors(s_w, cur, nx, scanned, lane, S, c);
     double gp[3] = {0.0, 0.0, 0.0}, ga[3] = {0.0, 0.0, 0.0}, gb[3] = {0.0, 0.0, 0.0};
     if (scanned) devq::dist_vjp(cur, s_w + 3 * mine, s_w + 3 * mine + 3, g, gp, ga, gb);
-    if (grad_samples && scanned) {
-      dev_pair* out = reinterpret_cast<dev_pair*>(grad_samples + (row0 + i) * 4);
-      dev_pair lo, hi;
-      lo.x = gp[0], lo.y = gp[1], hi.x = gp[2], hi.y = 0.0;
-      out[0] = lo;
-      out[1] = hi;
-    }
+    if (grad_samples && scanned) store_xyz0(grad_samples + (row0 + i) * 4, gp);
     if (grad_waypoints) {
       double* row = s_tile + lane * kDevTileStride;
 #pragma unroll
@@ -221,9 +187,9 @@ __global__ __launch_bounds__(64) void path_deviation_vjp_kernel(BatchView b, con
     for (int k = 0; k < 3; ++k) cur[k] = nxt[k];
   }
   if (grad_samples) {
-    dev_pair zero;
+    row_pair zero;
     zero.x = 0.0, zero.y = 0.0;
-    dev_pair* out = reinterpret_cast<dev_pair*>(grad_samples + row0 * 4);
+    row_pair* out = reinterpret_cast<row_pair*>(grad_samples + row0 * 4);
     for (int e = 2 * (n > 1 ? n - 1 : 0) + lane; e < 2 * capacity; e += 64) out[e] = zero;
   }
   if (grad_waypoints) {
@@ -238,7 +204,7 @@ hipError_t launch_path_deviation(const BatchView& b, const double* samples, cons
                                  int capacity, int first_segment, const int32_t* status, double* deviation, int32_t* cursor,
                                  double* max_deviation, int32_t* argmax, double* segment_max, hipStream_t stream) {
   const size_t lds = sizeof(double) * (3 * ((size_t)b.max_segments + 1) + (size_t)b.max_segments);
-  if (b.n_paths == 0) return lds > kLdsPerWorkgroup ? hipErrorInvalidValue : hipSuccess;
+  if (b.n_paths == 0) return empty_batch_lds(lds);
   const auto fwd = MRS_TG_KERNEL(path_deviation_kernel);
   if (hipError_t e = prepare_dynamic_lds(fwd, lds); e != hipSuccess) return e;
   MRS_TG_LAUNCH_TIMED(fwd, dim3((unsigned)b.n_paths), dim3(64), lds, stream, b, samples, n_samples, waypoints, capacity,
@@ -250,7 +216,7 @@ hipError_t launch_path_deviation_vjp(const BatchView& b, const double* samples, 
                                      const double* waypoints, int capacity, const int32_t* status, const double* grad_deviation,
                                      double* grad_samples, double* grad_waypoints, hipStream_t stream) {
   const size_t lds = sizeof(double) * (6 * ((size_t)b.max_segments + 1) + 64 * kDevTileStride) + sizeof(int) * 64;
-  if (b.n_paths == 0) return lds > kLdsPerWorkgroup ? hipErrorInvalidValue : hipSuccess;
+  if (b.n_paths == 0) return empty_batch_lds(lds);
   const auto vjp = MRS_TG_KERNEL(path_deviation_vjp_kernel);
   if (hipError_t e = prepare_dynamic_lds(vjp, lds); e != hipSuccess) return e;
   MRS_TG_LAUNCH_TIMED(vjp, dim3((unsigned)b.n_paths), dim3(64), lds, stream, b, samples, n_samples, waypoints, capacity, status,

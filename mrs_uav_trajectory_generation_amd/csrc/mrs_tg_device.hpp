@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "mrs_tg_batch.hpp"
 #include "mrs_tg_constants.h"
 #include "mrs_tg_hd.hpp"
 #include "mrs_tg_launch.h"
@@ -411,31 +412,7 @@ __device__ __forceinline__ double violation_scaling(const double* __restrict__ m
   return fmax(1.0, fmax(fmax(viol[0], sqrt(viol[1])), cbrt(viol[2])));
 }
 
-// ---------------------------------------------------------------------------------------------
-// batch addressing shared by all kernels
-
-struct PathRef {
-  int p;   // path index in the caller's order
-  int s0;  // first segment (CSR)
-  int S;   // number of segments
-  int v0;  // first vertex
-};
-
-__device__ __forceinline__ PathRef path_at(const BatchView& b, int q) {
-  PathRef r;
-  if (b.uniform_S > 0) {  // every path has the same segment count: the stable sort left the order alone, offsets are arithmetic
-    r.p = q;              // (no dependent loads before a kernel can touch its inputs)
-    r.S = b.uniform_S;
-    r.s0 = q * b.uniform_S;
-    r.v0 = r.s0 + q;
-    return r;
-  }
-  r.p = b.order[q];
-  r.s0 = b.seg_offsets[r.p];
-  r.S = b.seg_offsets[r.p + 1] - r.s0;
-  r.v0 = r.s0 + r.p;
-  return r;
-}
+// (batch addressing shared by all kernels -- PathRef, path_at and the segment / vertex to path map: mrs_tg_batch.hpp)
 
 // constrained values (0 where free) and the free mask of the candidate slots of one vertex
 template <int ND>

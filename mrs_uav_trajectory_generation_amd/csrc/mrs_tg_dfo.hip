@@ -467,7 +467,7 @@ __global__ __launch_bounds__(64) void dfo_sum_cost_kernel(BatchView b, const dou
   cost[p] = jd;
 }
 
-// seg_path[s] = path of segment s (modes 3 / 4)
+// seg_path[s] = path_of_segment(b, s) of mrs_tg_batch.hpp as a table: modes 3 / 4 read it many times
 __global__ __launch_bounds__(64) void dfo_segment_path_kernel(BatchView b, int32_t* __restrict__ seg_path) {
   const int p = blockIdx.x * 64 + threadIdx.x;
   if (p >= b.n_paths) return;
@@ -497,11 +497,11 @@ hipError_t launch_dfo(NonlinearPlan& nl, const BatchView& b, const DfoParams& pr
     if (!nl.d_dfo_segcost && (e = mrs_tg::pool_alloc(&nl.d_dfo_segcost, sizeof(double) * nS * kD)) != hipSuccess) return e;
     if (!nl.d_dfo_seg_path) {
       if ((e = mrs_tg::pool_alloc(&nl.d_dfo_seg_path, sizeof(int32_t) * nS)) != hipSuccess) return e;
-      MRS_TG_LAUNCH(dfo_segment_path_kernel, dim3(cdiv_u(b.n_paths, 64)), dim3(64), 0, stream, b, nl.d_dfo_seg_path);
+      MRS_TG_LAUNCH(dfo_segment_path_kernel, dim3(cdiv(b.n_paths, 64)), dim3(64), 0, stream, b, nl.d_dfo_seg_path);
       if ((e = hipGetLastError()) != hipSuccess) return e;
     }
   }
-  const unsigned pblocks = cdiv_u(b.n_paths, 64), sblocks = cdiv_u(b.n_segments, 64);
+  const unsigned pblocks = cdiv(b.n_paths, 64), sblocks = cdiv(b.n_segments, 64);
   // modes 3 / 4 start from the linear solution at the given times (optimizeTimeAndFreeConstraints :436-438);
   // for every mode this solve also marks position-free vertices (status -2, which stays unless the caller has switched
   // the general solve on: then every linear solve of the search is followed by the 5 x 5-block solve of those paths)

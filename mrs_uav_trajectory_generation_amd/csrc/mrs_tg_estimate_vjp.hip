@@ -24,19 +24,6 @@ namespace {
 
 constexpr int kEvThreads = 256;
 
-// the largest p with first[p] <= x, first[p] = seg_offsets[p] + extra * p (extra 1: a path's first vertex; 0: its first
-// segment): the forward's map, a division for uniform batches, a binary search over seg_offsets otherwise
-__device__ __forceinline__ int path_of(const BatchView& b, int x, int extra) {
-  if (b.uniform_S > 0) return x / (b.uniform_S + extra);
-  int lo = 0, hi = b.n_paths;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (b.seg_offsets[mid] + extra * mid <= x) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(kEvThreads) void estimate_times_vjp_kernel(BatchView b, const double* __restrict__ wp,
@@ -50,9 +37,9 @@ __global__ __launch_bounds__(kEvThreads) void estimate_times_vjp_kernel(BatchVie
   if (idx < n_vertices) {
     if (!grad_wp && !term) return;
     const int v = idx;
-    const int p = path_of(b, v, 1);
-    const int seg0 = b.uniform_S > 0 ? p * b.uniform_S : b.seg_offsets[p];
-    const int S = b.uniform_S > 0 ? b.uniform_S : b.seg_offsets[p + 1] - seg0;
+    const int p = path_of_vertex(b, v);
+    const int seg0 = first_segment(b, p);
+    const int S = segments_of(b, p, seg0);
     const int j = v - (seg0 + p);  // the vertex within its path, 0 .. S
     const int own = seg0 + j;      // the segment that starts here (j < S); own - 1 ends here (j > 0)
     const double* lim = limits + (size_t)p * estvjp::kLimits;
@@ -72,8 +59,8 @@ __global__ __launch_bounds__(kEvThreads) void estimate_times_vjp_kernel(BatchVie
   }
   const int p = idx - n_vertices;
   if (p >= b.n_paths || !grad_limits) return;
-  const int seg0 = b.uniform_S > 0 ? p * b.uniform_S : b.seg_offsets[p];
-  const int S = b.uniform_S > 0 ? b.uniform_S : b.seg_offsets[p + 1] - seg0;
+  const int seg0 = first_segment(b, p);
+  const int S = segments_of(b, p, seg0);
   double g[estvjp::kLimits];
   estvjp::limit_gradient(wp + (size_t)(seg0 + p) * 4, grad_times + seg0, S, limits + (size_t)p * estvjp::kLimits, g);
   double* out = grad_limits + (size_t)p * estvjp::kLimits;
@@ -85,7 +72,7 @@ hipError_t launch_estimate_times_vjp(const BatchView& b, const double* wp, const
                                      double* grad_wp, double* grad_limits, int32_t* term, hipStream_t stream) {
   if (b.n_paths <= 0) return hipSuccess;
   const long long lanes = (long long)b.n_segments + 2LL * b.n_paths;
-  MRS_TG_LAUNCH_TIMED(estimate_times_vjp_kernel, dim3((unsigned)((lanes + kEvThreads - 1) / kEvThreads)), dim3(kEvThreads), 0,
+  MRS_TG_LAUNCH_TIMED(estimate_times_vjp_kernel, dim3(cdiv(lanes, kEvThreads)), dim3(kEvThreads), 0,
                       stream, b, wp, limits, grad_times, grad_wp, grad_limits, term);
   return hipGetLastError();
 }

@@ -17,12 +17,11 @@
 #include "mrs_tg_device.hpp"
 #include "mrs_tg_evaluate.hpp"
 #include "mrs_tg_launch.h"
+#include "mrs_tg_pathwave.hpp"
 
 namespace mrs_tg {
 
 namespace {
-
-typedef double eval_pair __attribute__((ext_vector_type(2)));
 
 constexpr int kEvTileQueries = 32;                       // queries parked per reduction step of the backward pass
 constexpr int kEvTileStride = evalq::kCoeffElems + 1;    // 40 coefficient terms + the time gradient
@@ -73,8 +72,8 @@ __global__ __launch_bounds__(64) void evaluate_kernel(BatchView b, const double*
     }
     if constexpr (NO == 1) {  // 32 bytes per lane: two stores of the wavefront cover 2 KB without a gap
       if (valid) {
-        eval_pair* out = reinterpret_cast<eval_pair*>(states + (row0 + k) * (size_t)kRow);
-        eval_pair lo, hi;
+        row_pair* out = reinterpret_cast<row_pair*>(states + (row0 + k) * (size_t)kRow);
+        row_pair lo, hi;
         lo.x = row[0][0], lo.y = row[0][1], hi.x = row[0][2], hi.y = row[0][3];
         __builtin_nontemporal_store(lo, out);
         __builtin_nontemporal_store(hi, out + 1);
@@ -91,13 +90,13 @@ __global__ __launch_bounds__(64) void evaluate_kernel(BatchView b, const double*
         for (int dd = 0; dd < kD; ++dd) mine[o * kD + dd] = row[o][dd];
       wave_lds_barrier();
       const int pairs = min(64, k_end - k0) * (kRow / 2);
-      eval_pair* out = reinterpret_cast<eval_pair*>(states + (row0 + k0) * (size_t)kRow);
+      row_pair* out = reinterpret_cast<row_pair*>(states + (row0 + k0) * (size_t)kRow);
 #pragma unroll
       for (int i = 0; i < kRow / 2; ++i) {
         const int ch = lane + 64 * i;
         if (ch < pairs) {
           const double* src = s_rows + (ch / (kRow / 2)) * kEvRowStride + (ch % (kRow / 2)) * 2;
-          eval_pair v;
+          row_pair v;
           v.x = src[0], v.y = src[1];
           __builtin_nontemporal_store(v, out + ch);
         }
@@ -134,7 +133,7 @@ __global__ __launch_bounds__(64) void evaluate_vjp_kernel(BatchView b, const dou
     const PathRef pr = path_at(b, q);
     const int S = pr.S;
     // a path the solve gave up on contributes nothing, whatever its coefficients hold
-    const bool live = status == nullptr || status[pr.p] > 0;
+    const bool live = path_live(status, pr.p);
     const size_t row0 = (size_t)pr.p * (size_t)n_queries;
     for (int i = lane; i < S; i += 64) s_T[i] = seg_times[pr.s0 + i];
     if (live && want_time) {  // (only the time gradients read coefficients)
@@ -161,10 +160,10 @@ __global__ __launch_bounds__(64) void evaluate_vjp_kernel(BatchView b, const dou
       double g = 0.0;
       if (at.seg >= 0) {  // (the upstream row of an out-of-range query is never read)
         double G[NO * kD];
-        const eval_pair* __restrict__ up = reinterpret_cast<const eval_pair*>(grad_states + (row0 + k) * (size_t)(NO * kD));
+        const row_pair* __restrict__ up = reinterpret_cast<const row_pair*>(grad_states + (row0 + k) * (size_t)(NO * kD));
 #pragma unroll
         for (int e = 0; e < NO * kD / 2; ++e) {
-          const eval_pair v = __builtin_nontemporal_load(up + e);
+          const row_pair v = __builtin_nontemporal_load(up + e);
           G[2 * e] = v.x, G[2 * e + 1] = v.y;
         }
         evalq::coeff_terms<NO>(G, at.tau, terms);
@@ -205,14 +204,7 @@ __global__ __launch_bounds__(64) void evaluate_vjp_kernel(BatchView b, const dou
       double* __restrict__ gc = grad_coeffs + (size_t)pr.s0 * kD * kN;
       for (int e = lane; e < S * kD * kN; e += 64) gc[e] = s_acc[(e / evalq::kCoeffElems) * kEvTileStride + e % evalq::kCoeffElems];
     }
-    if (grad_times) {
-      // dL/dT_m = -(s_{m+1} + (s_{m+2} + ...)): sampvjp::time_gradients, lane 0 writing
-      double r = 0.0;
-      for (int i = S - 1; i >= 0; --i) {
-        if (lane == 0) grad_times[pr.s0 + i] = 0.0 - r;
-        r = sampvjp::accumulate(s_acc[i * kEvTileStride + evalq::kCoeffElems], r);
-      }
-    }
+    write_time_gradients(s_acc + evalq::kCoeffElems, kEvTileStride, pr.s0, S, lane, grad_times);
     wave_lds_barrier();  // (the next path's staging overwrites what this one read)
   }
 }
@@ -220,9 +212,9 @@ __global__ __launch_bounds__(64) void evaluate_vjp_kernel(BatchView b, const dou
 hipError_t launch_evaluate(const BatchView& b, const double* coeffs, const double* seg_times, const double* query_times,
                            int n_queries, int n_orders, double* states, int32_t* query_segment, double* query_tau,
                            hipStream_t stream) {
-  if (n_orders != 1 && n_orders != kSampleStateOrders) return hipErrorInvalidValue;
+  if (!valid_state_orders(n_orders)) return hipErrorInvalidValue;
   const size_t lds = sizeof(double) * ((size_t)b.max_segments * (2 + kD * kN) + (n_orders == 1 ? 0 : 64 * kEvRowStride));
-  if (b.n_paths == 0 || n_queries == 0) return lds > kLdsPerWorkgroup ? hipErrorInvalidValue : hipSuccess;
+  if (b.n_paths == 0 || n_queries == 0) return empty_batch_lds(lds);
   const auto fwd = n_orders == 1 ? MRS_TG_KERNEL(evaluate_kernel<1>) : MRS_TG_KERNEL(evaluate_kernel<kSampleStateOrders>);
   if (hipError_t e = prepare_dynamic_lds(fwd, lds); e != hipSuccess) return e;
   // one wavefront per path; the queries of few paths are cut into slices (multiples of 64) so that the device has work
@@ -239,10 +231,10 @@ hipError_t launch_evaluate(const BatchView& b, const double* coeffs, const doubl
 hipError_t launch_evaluate_vjp(const BatchView& b, const double* coeffs, const double* seg_times, const double* query_times,
                                int n_queries, int n_orders, const double* grad_states, const int32_t* status,
                                double* grad_coeffs, double* grad_times, double* grad_query, hipStream_t stream) {
-  if (n_orders != 1 && n_orders != kSampleStateOrders) return hipErrorInvalidValue;
+  if (!valid_state_orders(n_orders)) return hipErrorInvalidValue;
   const size_t lds = sizeof(double) * ((size_t)b.max_segments * (2 + kD * kN + kEvTileStride) + kEvTileQueries * kEvTileStride) +
                      sizeof(int) * kEvTileQueries;
-  if (b.n_paths == 0) return lds > kLdsPerWorkgroup ? hipErrorInvalidValue : hipSuccess;
+  if (b.n_paths == 0) return empty_batch_lds(lds);
   const auto vjp = n_orders == 1 ? MRS_TG_KERNEL(evaluate_vjp_kernel<1>) : MRS_TG_KERNEL(evaluate_vjp_kernel<kSampleStateOrders>);
   if (hipError_t e = prepare_dynamic_lds(vjp, lds); e != hipSuccess) return e;
   MRS_TG_LAUNCH_TIMED(vjp, dim3((unsigned)b.n_paths), dim3(64), lds, stream, b, coeffs, seg_times, query_times, n_queries,

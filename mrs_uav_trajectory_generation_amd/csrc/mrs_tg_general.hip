@@ -53,7 +53,7 @@ hipError_t launch_solve_general(const BatchView& b, int d, const uint8_t* mask, 
                                 const int32_t* only, const int32_t* opt_status) {
   if (b.n_paths == 0) return hipSuccess;
   if (!only && !status) return hipErrorInvalidValue;
-  const unsigned grid = (unsigned)(((size_t)b.n_paths * 4 + 63) / 64);
+  const unsigned grid = cdiv((long long)b.n_paths * 4, 64);
   MRS_TG_LAUNCH(solve_general_kernel, dim3(grid), dim3(64), 0, stream, b, d, mask, vals, seg_times, ws, coeffs, status,
                      cost, only, opt_status);
   return hipGetLastError();

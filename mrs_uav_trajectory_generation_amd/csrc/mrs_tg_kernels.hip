@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void estimate_times_kernel(BatchView b, const 
                                                              double* __restrict__ seg_times) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= b.n_segments) return;
-  // path of CSR segment idx: a division for uniform batches, binary search over seg_offsets otherwise
+  // path_of_segment(b, idx) of mrs_tg_batch.hpp, written out: through the function the compiler places the loads of b differently
   int p;
   if (b.uniform_S > 0) {
     p = idx / b.uniform_S;
@@ -242,8 +242,6 @@ __global__ __launch_bounds__(64) void sample_kernel(BatchView b, const double* _
 
 // ---------------------------------------------------------------------------------------------
 // launchers
-
-static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
 hipError_t launch_assemble(const BatchView& b, int d, const double* seg_times, double* H, double* Ainv,
                            hipStream_t stream) {

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "../../include/mrs_tg.h"
+#include "mrs_tg_batch.hpp"
 #include "mrs_tg_hd.hpp"
 #include "mrs_tg_knobs.hpp"
 
@@ -89,6 +90,10 @@ inline hipError_t prepare_dynamic_lds(const Kernel<Args...>& k, size_t bytes) {
   if (bytes > kLdsPerWorkgroup) return hipErrorInvalidValue;
   return bytes > kLdsDefaultLimit ? set_max_dynamic_lds(k, bytes) : hipSuccess;
 }
+// an empty batch launches nothing, but still refuses an oversize LDS need (what a launcher with dynamic LDS returns for it)
+inline hipError_t empty_batch_lds(size_t bytes) { return bytes > kLdsPerWorkgroup ? hipErrorInvalidValue : hipSuccess; }
+// workgroups of `b` items that cover `a`
+inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 // launch with the pending timer, if any
 #define MRS_TG_LAUNCH_TIMED(kernel, grid, block, lds, stream, ...)                                           \
   do {                                                                                                       \
@@ -123,17 +128,7 @@ int solve_batch_samples_only(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* se
                              const mrs_tg_options* opt, double* seg_times_inout, int32_t* status_out, int32_t* n_samples_out,
                              double* samples_out);
 
-// Device-resident structure of a batch (built once per plan).
-struct BatchView {
-  int n_paths;
-  int n_segments;            // sum of S over the batch
-  int max_segments;          // largest S
-  int uniform_S;             // S if every path has the same segment count, else 0
-  const int32_t* seg_offsets;  // [n_paths + 1] CSR over segments (caller's path order)
-  const int32_t* order;        // [n_paths] position q -> path index, sorted by S descending (stable)
-  const int32_t* slot_start;   // [max_segments + 1] slot_start[j] = number of (q, j') pairs with j' < j
-};
-
+// (BatchView, the device-resident structure of a batch: mrs_tg_batch.hpp)
 hipError_t launch_assemble(const BatchView& b, int d, const double* seg_times, double* H, double* Ainv,
                            hipStream_t stream);
 hipError_t launch_solve_linear(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,
@@ -171,6 +166,8 @@ hipError_t launch_sample(const BatchView& b, const double* coeffs, const double*
                          int32_t* n_samples, double* samples, hipStream_t stream);
 // the same walk, every sample with its derivative orders 0..4: states [n_paths][capacity][kSampleStateOrders][4]
 constexpr int kSampleStateOrders = kMaxOrders;
+// the rows of the state kernels carry the position alone or every order: any other n_orders is refused (hipErrorInvalidValue)
+constexpr bool valid_state_orders(int n_orders) { return n_orders == 1 || n_orders == kSampleStateOrders; }
 hipError_t launch_sample_states(const BatchView& b, const double* coeffs, const double* seg_times, double dt, int capacity,
                                 int32_t* n_samples, double* states, hipStream_t stream);
 // ---- the policy layer's per-round device work (mrs_tg_policy_dev.hip) ----

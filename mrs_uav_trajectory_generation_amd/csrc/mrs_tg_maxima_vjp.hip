@@ -74,7 +74,7 @@ __global__ __launch_bounds__(kMvThreads) void segment_maxima_vjp_kernel(int n_se
 hipError_t launch_segment_maxima_vjp(int n_segments, const double* coeffs, const double* seg_times, const double* grad_maxima,
                                      double* grad_coeffs, double* grad_times, double* argmax, hipStream_t stream) {
   if (n_segments <= 0) return hipSuccess;
-  MRS_TG_LAUNCH_TIMED(segment_maxima_vjp_kernel, dim3(cdiv_u(n_segments, kMvSegs)), dim3(kMvThreads), 0, stream, n_segments,
+  MRS_TG_LAUNCH_TIMED(segment_maxima_vjp_kernel, dim3(cdiv(n_segments, kMvSegs)), dim3(kMvThreads), 0, stream, n_segments,
                       coeffs, seg_times, grad_maxima, grad_coeffs, grad_times, argmax);
   return hipGetLastError();
 }

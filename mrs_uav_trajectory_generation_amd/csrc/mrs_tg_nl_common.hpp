@@ -43,6 +43,4 @@ __device__ __forceinline__ double rcp_refined(double x) {
   return y;
 }
 
-static inline unsigned cdiv_u(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
-
 }  // namespace mrs_tg

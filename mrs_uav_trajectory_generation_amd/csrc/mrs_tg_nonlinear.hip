@@ -942,23 +942,41 @@ struct BinTable {
   int group[5], q_begin[5], q_count[5], max_S[5], block_begin[5];
 };
 
-// CAREFUL (optimize_careful_kernel): one listed path per workgroup of 64, the primal cost in every evaluation, `careful_ws`
-// the factor store of its lanes.
-// LEAN (optimize_lean_kernel): plain paths only, the lean sweeps of evaluate_lean; a path it does not take is flagged in
-// `fallback` and left to the general instantiation launched behind it.
-// GENERAL (optimize_general_kernel, with CAREFUL): the listed paths are those with a position-free vertex, every evaluation
-// is evaluate_general, and the start point is read from `start_times` (a copy taken before the fast kernels ran over the
-// batch: they do not know such paths and leave garbage in seg_times for them).
-// LEANSHARED (optimize_lean_shared_kernel, with LEAN): every bin of the launch holds paths of 4 <= S <= G - 4 segments only (the
-// host checks), so evaluate_lean_shared is the ONLY evaluation compiled in -- next to the one-sided sweeps it costs both their
-// registers (124 instead of 28 bytes of scratch).
-template <int DS, bool MASKED4 = false, bool CAREFUL = false, bool LEAN = false, bool GENERAL = false, bool LEANSHARED = false,
-          bool TWOPASS = false>
+// The variants of the outer loop, one per kernel: what optimize_body<V> compiles in.  A variant states what it changes.
+namespace variant {
+struct Defaults {
+  static constexpr int kDS = 1;  // dimensions per lane
+  static constexpr bool kMasked4 = false, kCareful = false, kLean = false, kGeneral = false, kLeanShared = false, kTwoPass = false;
+};
+struct Split : Defaults { static constexpr int kDS = 4; };
+template <bool MASKED4>  // (kMasked4: the end vertices may leave slots free, the masked step at the two ends of the sweep)
+struct Compact : Defaults { static constexpr bool kMasked4 = MASKED4; };
+// one listed path per workgroup of 64, the primal cost in every evaluation, `careful_ws` the factor store of its lanes
+struct Careful : Split { static constexpr bool kCareful = true; };
+// the listed paths are those with a position-free vertex, every evaluation is evaluate_general, and the start point is read
+// from `start_times` (a copy taken before the fast kernels ran over the batch: they do not know such paths and leave garbage
+// in seg_times for them)
+struct General : Careful { static constexpr bool kGeneral = true; };
+// plain paths only, the lean sweeps of evaluate_lean; a path it does not take is flagged in `fallback` and left to the
+// general instantiation launched behind it
+struct Lean : Defaults { static constexpr bool kLean = true; };
+struct LeanMasked : Lean { static constexpr bool kMasked4 = true; };
+// every bin of the launch holds paths of 4 <= S <= G - 4 segments only (the host checks), so evaluate_lean_shared is the ONLY
+// evaluation compiled in -- next to the one-sided sweeps it costs both their registers (124 instead of 28 bytes of scratch)
+struct LeanShared : Lean { static constexpr bool kLeanShared = true; };
+struct LeanSharedEnds : LeanShared { static constexpr bool kMasked4 = true; };
+struct LeanSharedEndsLong : LeanSharedEnds { static constexpr bool kTwoPass = true; };  // two passes of it per wavefront
+}  // namespace variant
+
+template <class V>
 __device__ __forceinline__ void optimize_body(const BatchView& b, const NonlinearParams& prm, const BinTable& bins,
                                               const uint8_t* __restrict__ mask, const double* __restrict__ vals,
                                               double* __restrict__ seg_times, int32_t* __restrict__ opt_status,
                                               double* careful_ws = nullptr, int32_t* __restrict__ fallback = nullptr,
                                               const double* __restrict__ start_times = nullptr) {
+  constexpr int DS = V::kDS;
+  constexpr bool MASKED4 = V::kMasked4, CAREFUL = V::kCareful, LEAN = V::kLean, GENERAL = V::kGeneral,
+                 LEANSHARED = V::kLeanShared, TWOPASS = V::kTwoPass;
   extern __shared__ double lds[];
   MRS_TG_PHASE_MARK(0);
   int bin = 0;
@@ -1615,7 +1633,7 @@ __global__ __launch_bounds__(128, 2) void optimize_split_kernel(BatchView b, Non
                                                                 const double* __restrict__ vals,
                                                                 double* __restrict__ seg_times,
                                                                 int32_t* __restrict__ opt_status) {
-  optimize_body<4>(b, prm, bins, mask, vals, seg_times, opt_status);
+  optimize_body<variant::Split>(b, prm, bins, mask, vals, seg_times, opt_status);
 }
 
 template <bool MASKED4>
@@ -1623,7 +1641,7 @@ __global__ __launch_bounds__(64) void optimize_compact_kernel(BatchView b, Nonli
                                                               const uint8_t* __restrict__ mask,
                                                               const double* __restrict__ vals, double* __restrict__ seg_times,
                                                               int32_t* __restrict__ opt_status) {
-  optimize_body<1, MASKED4>(b, prm, bins, mask, vals, seg_times, opt_status);
+  optimize_body<variant::Compact<MASKED4>>(b, prm, bins, mask, vals, seg_times, opt_status);
 }
 
 __global__ void set_queue_kernel(int32_t* __restrict__ queue, int32_t first_unclaimed) { *queue = first_unclaimed; }
@@ -1644,15 +1662,15 @@ __global__ __launch_bounds__(64, MRS_TG_LEAN_WAVES) void optimize_lean_kernel(Ba
                                                               const uint8_t* __restrict__ mask, const double* __restrict__ vals,
                                                               double* __restrict__ seg_times, int32_t* __restrict__ opt_status,
                                                               int32_t* __restrict__ fallback) {
-  optimize_body<1, false, false, true>(b, prm, bins, mask, vals, seg_times, opt_status, nullptr, fallback);
+  optimize_body<variant::Lean>(b, prm, bins, mask, vals, seg_times, opt_status, nullptr, fallback);
 }
 
-// every path of every bin has 4 <= S <= G - 4 segments: shared half sweeps only (see optimize_body)
+// every path of every bin has 4 <= S <= G - 4 segments: shared half sweeps only (variant::LeanShared)
 __global__ __launch_bounds__(64, MRS_TG_LEAN_WAVES) void optimize_lean_shared_kernel(BatchView b, NonlinearParams prm, BinTable bins,
                                                               const uint8_t* __restrict__ mask, const double* __restrict__ vals,
                                                               double* __restrict__ seg_times, int32_t* __restrict__ opt_status,
                                                               int32_t* __restrict__ fallback) {
-  optimize_body<1, false, false, true, false, true>(b, prm, bins, mask, vals, seg_times, opt_status, nullptr, fallback);
+  optimize_body<variant::LeanShared>(b, prm, bins, mask, vals, seg_times, opt_status, nullptr, fallback);
 }
 
 // ... with paths of 61 .. 121 segments in the launch: two passes of the shared evaluation per wavefront (see there).  Min-snap
@@ -1662,7 +1680,7 @@ __global__ __launch_bounds__(64, MRS_TG_LEAN_WAVES) void optimize_lean_shared_en
                                                               const uint8_t* __restrict__ mask, const double* __restrict__ vals,
                                                               double* __restrict__ seg_times, int32_t* __restrict__ opt_status,
                                                               int32_t* __restrict__ fallback) {
-  optimize_body<1, true, false, true, false, true, true>(b, prm, bins, mask, vals, seg_times, opt_status, nullptr, fallback);
+  optimize_body<variant::LeanSharedEndsLong>(b, prm, bins, mask, vals, seg_times, opt_status, nullptr, fallback);
 }
 
 // shared half sweeps with free slots at the end vertices (objective orders below snap; evaluate_lean_shared<true>): every bin
@@ -1671,7 +1689,7 @@ __global__ __launch_bounds__(64, MRS_TG_LEAN_WAVES) void optimize_lean_shared_en
                                                               const uint8_t* __restrict__ mask, const double* __restrict__ vals,
                                                               double* __restrict__ seg_times, int32_t* __restrict__ opt_status,
                                                               int32_t* __restrict__ fallback) {
-  optimize_body<1, true, false, true, false, true>(b, prm, bins, mask, vals, seg_times, opt_status, nullptr, fallback);
+  optimize_body<variant::LeanSharedEnds>(b, prm, bins, mask, vals, seg_times, opt_status, nullptr, fallback);
 }
 
 // the end vertices may leave slots free (launches whose objective order is below snap: the masked step at the two ends of
@@ -1682,7 +1700,7 @@ __global__ __launch_bounds__(64) void optimize_lean_masked_kernel(BatchView b, N
                                                                   double* __restrict__ seg_times,
                                                                   int32_t* __restrict__ opt_status,
                                                                   int32_t* __restrict__ fallback) {
-  optimize_body<1, true, false, true>(b, prm, bins, mask, vals, seg_times, opt_status, nullptr, fallback);
+  optimize_body<variant::LeanMasked>(b, prm, bins, mask, vals, seg_times, opt_status, nullptr, fallback);
 }
 
 #if MRS_TG_WITH_CAREFUL
@@ -1692,7 +1710,7 @@ __global__ __launch_bounds__(64) void optimize_careful_kernel(BatchView b, Nonli
                                                               const double* __restrict__ vals, double* __restrict__ seg_times,
                                                               int32_t* __restrict__ opt_status, double* __restrict__ ws) {
   BinTable none{};
-  optimize_body<4, false, true>(b, prm, none, mask, vals, seg_times, opt_status, ws);
+  optimize_body<variant::Careful>(b, prm, none, mask, vals, seg_times, opt_status, ws);
 }
 
 #endif
@@ -1722,7 +1740,7 @@ __global__ __launch_bounds__(64) void optimize_general_kernel(BatchView b, Nonli
                                                               int32_t* __restrict__ opt_status, double* __restrict__ ws,
                                                               const double* __restrict__ start_times) {
   BinTable none{};
-  optimize_body<4, false, true, false, true>(b, prm, none, mask, vals, seg_times, opt_status, ws, nullptr, start_times);
+  optimize_body<variant::General>(b, prm, none, mask, vals, seg_times, opt_status, ws, nullptr, start_times);
 }
 
 // per-segment maxima, one (k, group) per blockIdx.y: maxima[seg * 9 + 3 (k-1) + group]
@@ -1767,6 +1785,7 @@ __global__ __launch_bounds__(kMsThreads) void segment_maxima_scaling_kernel(Batc
     const int ls = e >> 2, dim = e & 3, s = seg0 + ls;
     const bool live = s < b.n_segments;
     const int sc = live ? s : b.n_segments - 1;
+    // path_of_segment(b, sc) of mrs_tg_batch.hpp, written out: through the function the compiler places the loads of b differently
     int p;
     if (b.uniform_S > 0) {
       p = sc / b.uniform_S;
@@ -1834,6 +1853,7 @@ __global__ __launch_bounds__(256) void apply_scaling_kernel(BatchView b, const d
                                                             double* __restrict__ seg_times) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= b.n_segments) return;
+  // path_of_segment(b, idx) of mrs_tg_batch.hpp, written out: through the function the compiler places the loads of b differently
   int p;
   if (b.uniform_S > 0) {
     p = idx / b.uniform_S;  // one division instead of log2(P) dependent loads of the search below (5 -> 3 us at 1024 x 10)
@@ -1990,7 +2010,7 @@ int nonlinear_plan_build(NonlinearPlan& nl, const std::vector<int32_t>& so, cons
   nl.wide_blocks = 0;
   if (groups) {
     build_bins(nl.wide_bins, so, order, [](int S) { return group_for_wide(S); });
-    for (const NonlinearBin& bin : nl.wide_bins) nl.wide_blocks += (int)cdiv_u(bin.q_count, 64 / bin.group);
+    for (const NonlinearBin& bin : nl.wide_bins) nl.wide_blocks += (int)cdiv(bin.q_count, 64 / bin.group);
   }
   nl.ends_bins.clear();
   if (groups && P > 0 && group_for_ends(max_S) != 0)
@@ -2094,7 +2114,7 @@ hipError_t nonlinear_prepare_general(NonlinearPlan& nl, const BatchView& b, cons
     if (cap) *cap = (int)n;
   }
   if ((e = hipMemsetAsync(nl.d_general, 0, sizeof(int32_t) * 4, stream)) != hipSuccess) return e;
-  MRS_TG_LAUNCH(general_list_kernel, dim3(cdiv_u(b.n_paths, 256)), dim3(256), 0, stream, b, mask, nl.d_general);
+  MRS_TG_LAUNCH(general_list_kernel, dim3(cdiv(b.n_paths, 256)), dim3(256), 0, stream, b, mask, nl.d_general);
   return hipGetLastError();
 }
 
@@ -2152,7 +2172,7 @@ static size_t fill_bin_table(BinTable& bt, const std::vector<NonlinearBin>& bins
     bt.q_count[i] = bin.q_count;
     bt.max_S[i] = bin.max_S;
     bt.block_begin[i] = *blocks;
-    *blocks += (int)cdiv_u(bin.q_count, 64 / bin.group);
+    *blocks += (int)cdiv(bin.q_count, 64 / bin.group);
     lds = std::max(lds, lds_of(bin));
   }
   return lds;
@@ -2443,10 +2463,10 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
     return e;
   // 3. per-segment maxima and time scaling
   if (route.certified_maxima)
-    MRS_TG_LAUNCH(segment_maxima_scaling_kernel, dim3(cdiv_u(b.n_segments, kMsSegs)), dim3(kMsThreads), 0, stream, b, coeffs,
+    MRS_TG_LAUNCH(segment_maxima_scaling_kernel, dim3(cdiv(b.n_segments, kMsSegs)), dim3(kMsThreads), 0, stream, b, coeffs,
                        seg_times, limits, nl.d_maxima);
   else
-    MRS_TG_LAUNCH(segment_maxima9_kernel, dim3(cdiv_u(b.n_segments, 64), 9), dim3(64), 0, stream, b.n_segments,
+    MRS_TG_LAUNCH(segment_maxima9_kernel, dim3(cdiv(b.n_segments, 64), 9), dim3(64), 0, stream, b.n_segments,
                        coeffs, seg_times, nl.d_maxima);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   // 3b + 4 in one launch
@@ -2461,11 +2481,11 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
     tail.maxima = nl.d_maxima;
     return launch_solve_rows(b, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status, stream, tail);
   }
-  MRS_TG_LAUNCH(apply_scaling_kernel, dim3(cdiv_u(b.n_segments, 256)), dim3(256), 0, stream, b, nl.d_maxima, limits,
+  MRS_TG_LAUNCH(apply_scaling_kernel, dim3(cdiv(b.n_segments, 256)), dim3(256), 0, stream, b, nl.d_maxima, limits,
                      nl.d_opt_status, seg_times);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (!prm.reference_status) {
-    MRS_TG_LAUNCH(runaway_kernel, dim3(cdiv_u(b.n_paths, 256)), dim3(256), 0, stream, b, seg_times, nl.d_sum_t0, nl.d_opt_status);
+    MRS_TG_LAUNCH(runaway_kernel, dim3(cdiv(b.n_paths, 256)), dim3(256), 0, stream, b, seg_times, nl.d_sum_t0, nl.d_opt_status);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   // 4. updateSegmentTimes + solveLinear with the scaled times (nonlinear_impl.h:405-408), final status
@@ -2486,7 +2506,7 @@ hipError_t launch_cost_gradient(NonlinearPlan& nl, const BatchView& b, int d, co
     const int per_block = 64 / bin.group;
     const size_t lds_bytes = ((size_t)per_block * gradient_lds_doubles(bin.max_S, nl.dim_split == 4) + kBlockConsts) * sizeof(double);
     if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-    const dim3 grid(cdiv_u(bin.q_count, per_block));
+    const dim3 grid(cdiv(bin.q_count, per_block));
     const auto gradient = nl.dim_split == 4 ? MRS_TG_KERNEL(cost_gradient_kernel<4>) : MRS_TG_KERNEL(cost_gradient_kernel<1>);
     MRS_TG_LAUNCH(gradient, grid, dim3(64), lds_bytes, stream, b, d, bin.group, bin.q_begin, bin.q_count, bin.max_S, mask, vals,
                   seg_times, cost, grad, only);
@@ -2498,7 +2518,7 @@ hipError_t launch_cost_gradient(NonlinearPlan& nl, const BatchView& b, int d, co
 hipError_t launch_segment_maxima(const BatchView& b, const double* coeffs, const double* seg_times, double* maxima,
                                  hipStream_t stream) {
   if (b.n_segments == 0) return hipSuccess;
-  MRS_TG_LAUNCH(segment_maxima9_kernel, dim3(cdiv_u(b.n_segments, 64), 9), dim3(64), 0, stream, b.n_segments, coeffs,
+  MRS_TG_LAUNCH(segment_maxima9_kernel, dim3(cdiv(b.n_segments, 64), 9), dim3(64), 0, stream, b.n_segments, coeffs,
                      seg_times, maxima);
   return hipGetLastError();
 }

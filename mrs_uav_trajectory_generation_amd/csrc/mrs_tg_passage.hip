@@ -19,32 +19,11 @@
 #include "mrs_tg_device.hpp"
 #include "mrs_tg_launch.h"
 #include "mrs_tg_passage.hpp"
+#include "mrs_tg_pathwave.hpp"
 
 namespace mrs_tg {
 
 namespace {
-
-typedef double pass_pair __attribute__((ext_vector_type(2)));
-
-// x, y, z of row i of [n][4] rows (zeros behind them)
-__device__ __forceinline__ void load_row(const double* __restrict__ rows, int i, int n, double (&s)[3]) {
-  s[0] = s[1] = s[2] = 0.0;
-  if (i < n) {
-    const pass_pair* __restrict__ r = reinterpret_cast<const pass_pair*>(rows + (size_t)i * 4);
-    const pass_pair lo = r[0];
-    s[0] = lo.x, s[1] = lo.y, s[2] = rows[(size_t)i * 4 + 2];
-  }
-}
-
-// the sample behind every lane's own: the next lane's, and for lane 63 the first of the next chunk
-__device__ __forceinline__ void step_end(const double (&cur)[3], const double (&nxt)[3], int lane, double (&nx)[3]) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double down = __shfl_down(cur[k], 1);
-    const double seam = __shfl(nxt[k], 0);
-    nx[k] = lane == 63 ? seam : down;
-  }
-}
 
 // what a path's call is about: its samples, its waypoints (wp: row 0 is w_0), their number
 struct PassagePath {
@@ -57,9 +36,7 @@ __device__ __forceinline__ PassagePath passage_path(const BatchView& b, const in
   const PathRef pr = path_at(b, blockIdx.x);
   PassagePath pp;
   pp.p = pr.p;
-  const bool live = status == nullptr || status[pr.p] > 0;
-  int n = live ? min(n_samples[pr.p], capacity) : 0;
-  pp.n = n < 0 ? 0 : n;
+  pp.n = live_samples(path_live(status, pr.p), n_samples, pr.p, capacity);
   int w0 = pr.v0, W = pr.S + 1;
   if (wp_offsets) {
     w0 = wp_offsets[pr.p];
@@ -102,7 +79,7 @@ __device__ __forceinline__ Hit resolve_hits(const double* __restrict__ wp, int W
     ++c;
 #pragma unroll
     for (int k = 0; k < 3; ++k) wc[k] = wn[k];
-    load_row(wp, c + 1, W, wn);
+    load_xyz(wp, c + 1, W, wn);
   }
   return h;
 }
@@ -123,15 +100,15 @@ __global__ __launch_bounds__(64) void waypoint_passage_kernel(BatchView b, const
   const double* __restrict__ wp = waypoints + pp.w0 * 4;
   const bool scans = n > 1 && W > 0;
   double cur[3], wc[3], wn[3];
-  load_row(rows, lane, scans ? n : 0, cur);
-  load_row(wp, 0, scans ? W : 0, wc);
-  load_row(wp, 1, scans ? W : 0, wn);
+  load_xyz(rows, lane, scans ? n : 0, cur);
+  load_xyz(wp, 0, scans ? W : 0, wc);
+  load_xyz(wp, 1, scans ? W : 0, wn);
   int c = 0;
   for (int k0 = 0; scans && k0 < n - 1 && c < W; k0 += 64) {
     const int i = k0 + lane;
     double nxt[3], nx[3];
-    load_row(rows, i + 64, n, nxt);
-    step_end(cur, nxt, lane, nx);
+    load_xyz(rows, i + 64, n, nxt);
+    seam_neighbour(cur, nxt, lane, nx);
     const Hit h = resolve_hits(wp, W, cur, nx, i < n - 1, lane, c, wc, wn);
     if (h.k >= 0) {
       if (index) index[pp.w0 + h.k] = i;
@@ -165,9 +142,9 @@ __global__ __launch_bounds__(64) void waypoint_passage_vjp_kernel(BatchView b, c
   const double* __restrict__ wp = waypoints + pp.w0 * 4;
   const bool scans = n > 1 && W > 0;
   double cur[3], wc[3], wn[3];
-  load_row(rows, lane, scans ? n : 0, cur);
-  load_row(wp, 0, scans ? W : 0, wc);
-  load_row(wp, 1, scans ? W : 0, wn);
+  load_xyz(rows, lane, scans ? n : 0, cur);
+  load_xyz(wp, 0, scans ? W : 0, wc);
+  load_xyz(wp, 1, scans ? W : 0, wn);
   int c = 0, k0 = 0;
   // the b-contribution of lane 63's hit, on its way to the next chunk's lane 0 (wavefront-uniform)
   bool carried = false;
@@ -175,8 +152,8 @@ __global__ __launch_bounds__(64) void waypoint_passage_vjp_kernel(BatchView b, c
   for (; scans && k0 < n && c < W; k0 += 64) {
     const int i = k0 + lane;
     double nxt[3], nx[3];
-    load_row(rows, i + 64, n, nxt);
-    step_end(cur, nxt, lane, nx);
+    load_xyz(rows, i + 64, n, nxt);
+    seam_neighbour(cur, nxt, lane, nx);
     const Hit h = resolve_hits(wp, W, cur, nx, i < n - 1, lane, c, wc, wn);
     const bool hit = h.k >= 0;
     // (the upstreams of a waypoint are read once it is known to be reached: those of the others never are)
@@ -197,37 +174,25 @@ __global__ __launch_bounds__(64) void waypoint_passage_vjp_kernel(BatchView b, c
       carry[k] = lane_value(gb[k], 63);
     }
     carried = (hits >> 63) != 0;
-    if (grad_samples && i < capacity) {
-      pass_pair* out = reinterpret_cast<pass_pair*>(grad_samples + (pp.row0 + i) * 4);
-      pass_pair lo, hi;
-      lo.x = row[0], lo.y = row[1], hi.x = row[2], hi.y = 0.0;
-      out[0] = lo;
-      out[1] = hi;
-    }
-    if (grad_waypoints && hit) {
-      pass_pair* out = reinterpret_cast<pass_pair*>(grad_waypoints + (pp.w0 + h.k) * 4);
-      pass_pair lo, hi;
-      lo.x = gp[0], lo.y = gp[1], hi.x = gp[2], hi.y = 0.0;
-      out[0] = lo;
-      out[1] = hi;
-    }
+    if (grad_samples && i < capacity) store_xyz0(grad_samples + (pp.row0 + i) * 4, row);
+    if (grad_waypoints && hit) store_xyz0(grad_waypoints + (pp.w0 + h.k) * 4, gp);
 #pragma unroll
     for (int k = 0; k < 3; ++k) cur[k] = nxt[k];
   }
-  pass_pair zero;
+  row_pair zero;
   zero.x = 0.0, zero.y = 0.0;
   if (grad_samples) {
     // the rows behind the chunks that were run: zeros, but for the row behind a hit on the last lane of the last chunk
-    pass_pair* out = reinterpret_cast<pass_pair*>(grad_samples + pp.row0 * 4);
+    row_pair* out = reinterpret_cast<row_pair*>(grad_samples + pp.row0 * 4);
     for (int e = 2 * k0 + lane; e < 2 * capacity; e += 64) {
-      pass_pair v = zero;
+      row_pair v = zero;
       if (carried && e == 2 * k0) v.x = passq::accumulate(0.0, carry[0]), v.y = passq::accumulate(0.0, carry[1]);
       if (carried && e == 2 * k0 + 1) v.x = passq::accumulate(0.0, carry[2]);
       out[e] = v;
     }
   }
   if (grad_waypoints) {
-    pass_pair* out = reinterpret_cast<pass_pair*>(grad_waypoints + pp.w0 * 4);
+    row_pair* out = reinterpret_cast<row_pair*>(grad_waypoints + pp.w0 * 4);
     for (int e = 2 * c + lane; e < 2 * W; e += 64) out[e] = zero;
   }
 }

@@ -80,14 +80,14 @@ __global__ __launch_bounds__(64) void policy_validate_kernel(PolicyValidateArgs 
 hipError_t launch_policy_expand(int n_vertices, int d, const double* wp, const int32_t* vinfo, const double* init, uint8_t* mask,
                                 double* vals, hipStream_t stream) {
   if (n_vertices <= 0) return hipSuccess;
-  MRS_TG_LAUNCH(policy_expand_kernel, dim3((unsigned)((n_vertices + 255) / 256)), dim3(256), 0, stream, n_vertices, d, wp, vinfo, init,
+  MRS_TG_LAUNCH(policy_expand_kernel, dim3(cdiv(n_vertices, 256)), dim3(256), 0, stream, n_vertices, d, wp, vinfo, init,
                 mask, vals);
   return hipGetLastError();
 }
 
 hipError_t launch_policy_validate(const PolicyValidateArgs& args, hipStream_t stream) {
   if (args.n_paths <= 0) return hipSuccess;
-  MRS_TG_LAUNCH(policy_validate_kernel, dim3((unsigned)((args.n_paths + 63) / 64)), dim3(64), 0, stream, args);
+  MRS_TG_LAUNCH(policy_validate_kernel, dim3(cdiv(args.n_paths, 64)), dim3(64), 0, stream, args);
   return hipGetLastError();
 }
 

@@ -41,7 +41,7 @@ __global__ __launch_bounds__(64) void refine_kernel(BatchView b, int d, const ui
 hipError_t launch_refine(const BatchView& b, int d, const uint8_t* mask, const double* vals, const double* seg_times, double* ws,
                          double* coeffs, const int32_t* status, double* cost, hipStream_t stream) {
   if (b.n_paths == 0) return hipSuccess;
-  const unsigned grid = (unsigned)(((size_t)b.n_paths * 4 + 63) / 64);
+  const unsigned grid = cdiv((long long)b.n_paths * 4, 64);
   MRS_TG_LAUNCH(refine_kernel, dim3(grid), dim3(64), 0, stream, b, d, mask, vals, seg_times, ws, coeffs, status, cost);
   return hipGetLastError();
 }

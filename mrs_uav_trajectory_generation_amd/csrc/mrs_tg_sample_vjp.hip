@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mrs_tg_launch.h"
+#include "mrs_tg_pathwave.hpp"
 #include "mrs_tg_sample_vjp.hpp"
 #include "mrs_tg_sampling.hpp"
 
@@ -132,6 +133,7 @@ __global__ __launch_bounds__(64) void sample_vjp_kernel(BatchView b, const doubl
     const PathRef pr = path_at(b, q);
     const int S = pr.S;
     // a path the solve gave up on contributes nothing, whatever its coefficients hold
+    // (path_live of mrs_tg_pathwave.hpp, written out: through the function the compiler swaps the operands of this conjunction)
     const bool live = want_grad && (status == nullptr || status[pr.p] > 0);
     for (int i = lane; i < S; i += 64) s_T[i] = seg_times[pr.s0 + i];
     if (live && grad_times) {  // (only the time partials read coefficients)
@@ -155,12 +157,7 @@ __global__ __launch_bounds__(64) void sample_vjp_kernel(BatchView b, const doubl
       sink.close_segments(S);  // the last segment with samples, and zero rows for every segment behind it
       if (grad_times) {
         wave_lds_barrier();
-        // dL/dT_i = -(s_{i+1} + (s_{i+2} + ...)): sampvjp::time_gradients, lane 0 writing
-        double r = 0.0;
-        for (int i = S - 1; i >= 0; --i) {
-          if (lane == 0) grad_times[pr.s0 + i] = 0.0 - r;
-          r = sampvjp::accumulate(s_sum[i], r);
-        }
+        write_time_gradients(s_sum, 1, pr.s0, S, lane, grad_times);
       }
     }
     __syncthreads();  // (the next path's staging overwrites what this walk read)
@@ -172,7 +169,7 @@ hipError_t launch_sample_vjp(const BatchView& b, const double* coeffs, const dou
                              double* grad_times, int32_t* sample_segment, double* sample_time, int32_t* n_samples,
                              hipStream_t stream) {
   if (b.n_paths == 0) return hipSuccess;
-  if (n_orders != 1 && n_orders != kSampleStateOrders) return hipErrorInvalidValue;
+  if (!valid_state_orders(n_orders)) return hipErrorInvalidValue;
   const double* acc_table = nullptr;
   int acc_n = 0;
   AccPin pin;  // (released when this function returns: behind the enqueue of the kernel that reads the table)

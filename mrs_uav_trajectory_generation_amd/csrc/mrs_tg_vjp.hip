@@ -63,7 +63,7 @@ hipError_t launch_vjp(const BatchView& b, int d, const uint8_t* mask, const doub
                       const double* coeffs, const int32_t* status, const double* grad_coeffs, const double* grad_cost, double* ws,
                       double* grad_vals, double* grad_times, hipStream_t stream) {
   if (b.n_paths == 0) return hipSuccess;
-  const unsigned grid = (unsigned)(((size_t)b.n_paths * 4 + 63) / 64);
+  const unsigned grid = cdiv((long long)b.n_paths * 4, 64);
   MRS_TG_LAUNCH_TIMED(vjp_kernel, dim3(grid), dim3(64), 0, stream, b, d, mask, vals, seg_times, coeffs, status, grad_coeffs,
                       grad_cost, ws, grad_vals, grad_times);
   return hipGetLastError();
