@@ -42,6 +42,43 @@ void set_global_error(const std::string& s) {
 
 static std::atomic<int> g_live_contexts{0};
 
+// A block a context keeps across calls and only ever replaces by a larger one: a device block from the pool, or pinned host
+// memory (hipHostMalloc).  A device block goes back to the pool with its stream synchronised, which is the pool's contract
+// (every user of these blocks ends its call with a synchronise, so that one finds an idle stream; it runs when a block grows,
+// never in a steady-state call).
+struct GrowBlock {
+  enum Kind { kDevicePool, kPinnedHost };
+  Kind kind;
+  void* ptr = nullptr;
+  size_t bytes = 0;
+  explicit GrowBlock(Kind k) : kind(k) {}
+  // what the synchronise before a device block's return said: a stream that has faulted is reported, not passed over
+  hipError_t release(hipStream_t stream) {
+    hipError_t e = hipSuccess;
+    if (ptr && kind == kDevicePool) {
+      e = hipStreamSynchronize(stream);
+      mrs_tg::pool_free(ptr);
+    } else if (ptr) {
+      (void)hipHostFree(ptr);
+    }
+    ptr = nullptr;
+    bytes = 0;
+    return e;
+  }
+  // at least `need` bytes; a block that has to grow is allocated with need / headroom_divisor more (0: exactly `need`).  A
+  // need of 0 bytes allocates nothing and leaves an empty block empty (ptr null), for every kind of block
+  hipError_t ensure(size_t need, size_t headroom_divisor, hipStream_t stream) {
+    if (bytes >= need && (ptr || need == 0)) return hipSuccess;
+    const hipError_t synced = release(stream);
+    if (synced != hipSuccess) return synced;
+    const size_t want = need + (headroom_divisor ? need / headroom_divisor : 0);
+    const hipError_t e = kind == kDevicePool ? mrs_tg::pool_alloc(&ptr, want) : hipHostMalloc(&ptr, want, hipHostMallocDefault);
+    if (e != hipSuccess) ptr = nullptr;
+    else bytes = want;
+    return e;
+  }
+};
+
 struct mrs_tg_ctx {
   int device = -1;
   hipStream_t own_stream = nullptr;
@@ -61,13 +98,10 @@ struct mrs_tg_ctx {
   mrs_tg_plan* cached_plan = nullptr;
   // mrs_tg_solve_batch's transfer arenas, kept across calls: one device block holding every input and output array of a
   // call, and a pinned host block (hipHostMalloc) through which the small host arrays travel packed, one copy each way
-  void* d_arena = nullptr;
-  size_t d_arena_bytes = 0;
-  void* h_arena = nullptr;
-  size_t h_arena_bytes = 0;
+  GrowBlock d_arena{GrowBlock::kDevicePool};
+  GrowBlock h_arena{GrowBlock::kPinnedHost};
   // pinned host scratch of mrs_tg_optimize_paths (the arrays of its rounds), kept across calls
-  void* h_scratch = nullptr;
-  size_t h_scratch_bytes = 0;
+  GrowBlock h_scratch{GrowBlock::kPinnedHost};
   // what the most recent mrs_tg_find_trajectory decided (mrs_tg_find_trajectory_info)
   int32_t find_rejection = 0;
   double find_baca_total = 0.0;
@@ -334,9 +368,7 @@ void mrs_tg_destroy(mrs_tg_ctx* ctx) {
     for (hipEvent_t e : ctx->ev_stop[i])
       if (e) (void)hipEventDestroy(e);
   }
-  if (ctx->d_arena) (void)mrs_tg::pool_free(ctx->d_arena);
-  if (ctx->h_arena) (void)hipHostFree(ctx->h_arena);
-  if (ctx->h_scratch) (void)hipHostFree(ctx->h_scratch);
+  for (GrowBlock* b : {&ctx->d_arena, &ctx->h_arena, &ctx->h_scratch}) (void)b->release(ctx->stream);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
   if (--g_live_contexts == 0) {  // the sampling tables and the cached device blocks go with the last context
@@ -1242,27 +1274,45 @@ namespace mrs_tg {
 
 void* ctx_host_scratch(mrs_tg_ctx* ctx, size_t bytes) {
   if (!ctx) return nullptr;
-  if (ctx->h_scratch_bytes >= bytes && ctx->h_scratch) return ctx->h_scratch;
-  if (ctx->h_scratch) (void)hipHostFree(ctx->h_scratch);
-  ctx->h_scratch = nullptr;
-  ctx->h_scratch_bytes = 0;
-  const size_t want = bytes + bytes / 4;  // (a later round's arrays are a little larger: its paths have more waypoints)
-  if (hipHostMalloc(&ctx->h_scratch, want, hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->h_scratch = nullptr;
-    return nullptr;
-  }
-  ctx->h_scratch_bytes = want;
-  return ctx->h_scratch;
+  // (a quarter more: a later round's arrays are a little larger, its paths have more waypoints)
+  if (ctx->h_scratch.ensure(bytes, 4, ctx->stream) != hipSuccess) (void)hipGetLastError();
+  return ctx->h_scratch.ptr;
 }
 
 }  // namespace mrs_tg
 }  // extern "C++"
 
-static int solve_batch_impl(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* so, const double* wp, const uint8_t* mask,
-                            const double* vals, const double* limits, const mrs_tg_options* opt, double* seg_times,
-                            double* coeffs, int32_t* status, double* cost, int32_t* n_samples, double* samples,
-                            bool coeffs_required);
+namespace {
+
+struct SyncOnExit {  // nothing of a call is in flight when it returns, on error paths as well (the arenas are reused)
+  hipStream_t st;
+  ~SyncOnExit() { (void)hipStreamSynchronize(st); }
+};
+
+// device-side address of a host range the GPU can address as a whole: first AND last byte must be pinned and lie in the
+// same mapping (a range that mrs_tg_host_register covers only in part, or an allocation shorter than the batch implies,
+// takes the copying route -- where a short array is a host-side fault of the caller's, not a GPU page fault)
+void* pinned_address(const void* ptr, size_t bytes) {
+  auto query = [](const void* q, hipPointerAttribute_t* at) {
+    if (hipPointerGetAttributes(at, q) != hipSuccess) {
+      (void)hipGetLastError();  // an ordinary (pageable) pointer is reported as an error by some runtimes
+      return false;
+    }
+    return at->type == hipMemoryTypeHost;
+  };
+  hipPointerAttribute_t first, last;
+  if (!query(ptr, &first)) return nullptr;
+  void* dev_first = first.devicePointer ? first.devicePointer : const_cast<void*>(ptr);
+  if (bytes > 1) {
+    const char* end = static_cast<const char*>(ptr) + (bytes - 1);
+    if (!query(end, &last)) return nullptr;
+    const char* dev_last = static_cast<const char*>(last.devicePointer ? last.devicePointer : (void*)end);
+    if (dev_last - static_cast<const char*>(dev_first) != (ptrdiff_t)(bytes - 1)) return nullptr;  // two mappings
+  }
+  return dev_first;
+}
+
+}  // namespace
 
 // the plan of the previous call is kept: the same batch shape again (a server's fixed batch, the re-solves of the nodelet's
 // deviation loop) costs no analysis, no structure upload and no workspace allocation
@@ -1301,51 +1351,15 @@ int policy_round_device(mrs_tg_ctx* ctx, const PolicyRoundIn& in) {
   mrs_tg_plan* plan = nullptr;
   int rc = cached_plan_for(ctx, in.n_paths, in.seg_offsets, &plan);
   if (rc != MRS_TG_OK) return rc;
-  // device arena: [the block's input region] | results (small) | mask | values | times | coefficients | cost | status | n | rows | samples
-  auto up = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
-  size_t off = L.in_bytes;
-  const size_t o_res = off;
-  off += L.samples - L.in_bytes;  // the small results, laid out as in the block
-  const size_t o_mask = off;
-  off += up(nV * 5);
-  const size_t o_vals = off;
-  off += up(nV * 20 * sizeof(double));
-  const size_t o_t = off;
-  off += up(nS * sizeof(double));
-  const size_t o_c = off;
-  off += up(nS * 40 * sizeof(double));
-  const size_t o_cost = off;
-  off += up(A * sizeof(double));
-  const size_t o_st = off;
-  off += up(A * sizeof(int32_t));
-  const size_t o_ns = off;
-  off += up(A * sizeof(int32_t));
-  const size_t o_rows = off;
-  off += up(A * sizeof(int32_t));
-  const size_t o_smp = off;
-  off += up(A * (size_t)cap * 4 * sizeof(double));
-  if (ctx->d_arena_bytes < off) {
-    if (ctx->d_arena) {
-      (void)hipStreamSynchronize(s);  // pool contract: no work in flight on a block that is given back
-      (void)mrs_tg::pool_free(ctx->d_arena);
-    }
-    ctx->d_arena = nullptr;
-    ctx->d_arena_bytes = 0;
-    const size_t want = off + off / 2;  // (the next round's paths have more waypoints: one allocation for a request's rounds)
-    HIP_TRY(ctx, mrs_tg::pool_alloc(&ctx->d_arena, want));
-    ctx->d_arena_bytes = want;
-  }
-  char* d = static_cast<char*>(ctx->d_arena);
-  struct SyncOnExit {  // nothing of this call is in flight when it returns, on error paths as well (the arena is reused)
-    hipStream_t st;
-    ~SyncOnExit() { (void)hipStreamSynchronize(st); }
-  } sync_on_exit{s};
-  // is the block memory the GPU addresses (hipHostMalloc: ctx_host_scratch)?  Then one copy kernel moves the inputs, and the
-  // results are written into it directly
-  hipPointerAttribute_t at;
-  bool pinned = hipPointerGetAttributes(&at, in.block) == hipSuccess && at.type == hipMemoryTypeHost;
-  if (!pinned) (void)hipGetLastError();
-  char* blk_dev = pinned ? static_cast<char*>(at.devicePointer ? at.devicePointer : (void*)in.block) : nullptr;
+  const PolicyRoundArena R = policy_round_arena(L, A, nS, cap);
+  // (half as much again: the next round's paths have more waypoints -- one allocation for a request's rounds)
+  HIP_TRY(ctx, ctx->d_arena.ensure(R.total_bytes, 2, s));
+  char* d = static_cast<char*>(ctx->d_arena.ptr);
+  SyncOnExit sync_on_exit{s};
+  // is the whole block memory the GPU addresses (hipHostMalloc: ctx_host_scratch)?  Then one copy kernel moves the inputs,
+  // and the results are written into it directly
+  char* blk_dev = static_cast<char*>(pinned_address(in.block, L.total_bytes));
+  const bool pinned = blk_dev != nullptr;
   if (pinned) {
     mrs_tg::CopyList upl;
     upl.add(blk_dev, d, L.in_bytes);
@@ -1354,23 +1368,22 @@ int policy_round_device(mrs_tg_ctx* ctx, const PolicyRoundIn& in) {
     HIP_TRY(ctx, hipMemcpyAsync(d, in.block, L.in_bytes, hipMemcpyHostToDevice, s));
   }
   const double* wp_d = reinterpret_cast<const double*>(d + L.wp);
-  uint8_t* mask_d = reinterpret_cast<uint8_t*>(d + o_mask);
-  double* vals_d = reinterpret_cast<double*>(d + o_vals);
+  uint8_t* mask_d = reinterpret_cast<uint8_t*>(d + R.mask);
+  double* vals_d = reinterpret_cast<double*>(d + R.vals);
   HIP_TRY(ctx, mrs_tg::launch_policy_expand((int)nV, in.opt.derivative_to_optimize, wp_d, reinterpret_cast<const int32_t*>(d + L.vinfo),
                                             reinterpret_cast<const double*>(d + L.init), mask_d, vals_d, s));
   mrs_tg_options opt = in.opt;
   opt.estimate_times = 1;
   opt.sample_capacity = cap;
   opt.flags |= MRS_TG_FLAG_REFERENCE_STATUS;  // the length check below is the reference's answer to a runaway (:1178-1199)
-  int32_t* st_d = reinterpret_cast<int32_t*>(d + o_st);
-  int32_t* ns_d = reinterpret_cast<int32_t*>(d + o_ns);
-  double* smp_d = reinterpret_cast<double*>(d + o_smp);
-  rc = mrs_tg_plan_solve(plan, wp_d, mask_d, vals_d, reinterpret_cast<const double*>(d + L.lim), &opt, reinterpret_cast<double*>(d + o_t),
-                         reinterpret_cast<double*>(d + o_c), st_d, reinterpret_cast<double*>(d + o_cost), ns_d, smp_d);
+  int32_t* st_d = reinterpret_cast<int32_t*>(d + R.status);
+  int32_t* ns_d = reinterpret_cast<int32_t*>(d + R.n_samples);
+  double* smp_d = reinterpret_cast<double*>(d + R.samples);
+  rc = mrs_tg_plan_solve(plan, wp_d, mask_d, vals_d, reinterpret_cast<const double*>(d + L.lim), &opt, reinterpret_cast<double*>(d + R.times),
+                         reinterpret_cast<double*>(d + R.coeffs), st_d, reinterpret_cast<double*>(d + R.cost), ns_d, smp_d);
   if (rc != MRS_TG_OK) return rc;
   // gates + validateTrajectorySpatial where the samples are; the small results go where the host reads them
   char* res = pinned ? blk_dev : d;  // (res + L.<field> addresses the field in either place: the arena mirrors the block)
-  (void)o_res;
   mrs_tg::PolicyValidateArgs va{};
   va.n_paths = in.n_paths;
   va.seg_offsets = reinterpret_cast<const int32_t*>(d + L.so);
@@ -1393,12 +1406,12 @@ int policy_round_device(mrs_tg_ctx* ctx, const PolicyRoundIn& in) {
   va.max_dev_out = reinterpret_cast<double*>(res + L.max_dev);
   va.is_safe_out = reinterpret_cast<uint8_t*>(res + L.is_safe);
   va.safe_out = reinterpret_cast<uint8_t*>(res + L.safe);
-  va.ns_copy = reinterpret_cast<int32_t*>(d + o_rows);
+  va.ns_copy = reinterpret_cast<int32_t*>(d + R.rows);
   HIP_TRY(ctx, mrs_tg::launch_policy_validate(va, s));
   if (pinned) {  // the finished paths' rows only
     HIP_TRY(ctx, mrs_tg::launch_copy_samples(smp_d, reinterpret_cast<double*>(blk_dev + L.samples), va.ns_copy, in.n_paths, cap, s));
   } else {
-    HIP_TRY(ctx, hipMemcpyAsync(in.block + L.ok, d + o_res, L.samples - L.ok, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(in.block + L.ok, d + R.results, L.samples - L.ok, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipMemcpyAsync(in.block + L.samples, smp_d, A * (size_t)cap * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
   }
   HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -1407,6 +1420,166 @@ int policy_round_device(mrs_tg_ctx* ctx, const PolicyRoundIn& in) {
 
 }  // namespace mrs_tg
 }  // extern "C++"
+
+extern "C++" {
+namespace {
+
+using mrs_tg::A_WP, mrs_tg::A_MASK, mrs_tg::A_VALS, mrs_tg::A_LIM, mrs_tg::A_T;                // (the array table: mrs_tg_transfer.hpp)
+using mrs_tg::A_C, mrs_tg::A_ST, mrs_tg::A_COST, mrs_tg::A_NS, mrs_tg::A_SMP, mrs_tg::A_COUNT;
+
+// One call of the one-call interface between its plan and its kernels: the arrays (mrs_tg_transfer.hpp says how each one
+// travels), their layout in the context's two arenas, and the steps that move them.
+struct HostCall {
+  mrs_tg_ctx* ctx;
+  hipStream_t s;
+  int32_t n_paths, sample_capacity;
+  mrs_tg::TransferArray arr[A_COUNT];
+  mrs_tg::TransferLayout lay;
+  bool zero_copy = false;
+  char* dbase() const { return static_cast<char*>(ctx->d_arena.ptr); }
+  char* staged(int id) const { return static_cast<char*>(ctx->h_arena.ptr) + lay.host_offset(arr[id]); }
+  char* span(size_t device_offset) const { return static_cast<char*>(ctx->h_arena.ptr) + (device_offset - lay.span_begin); }
+  // where the kernels find array `id`: the caller's own (pinned) memory under zero copy, its slot of the arena otherwise
+  template <class T>
+  T* dev(int id) const {
+    const mrs_tg::TransferArray& a = arr[id];
+    return static_cast<T*>((zero_copy && a.pinned && a.bytes) ? a.pinned : static_cast<void*>(dbase() + a.off));
+  }
+
+  // grow-only, exactly what the largest call so far needed
+  int ensure_arenas() {
+    HIP_TRY(ctx, ctx->d_arena.ensure(lay.device_bytes, 0, s));
+    HIP_TRY(ctx, ctx->h_arena.ensure(lay.host_bytes, 0, s));
+    return MRS_TG_OK;
+  }
+
+  // host to device: pinned arrays and the staged span in one copy kernel, large pageable arrays by the runtime
+  int upload() const {
+    if (zero_copy) return MRS_TG_OK;
+    mrs_tg::CopyList up;
+    bool listed = true;
+    for (int id : mrs_tg::kUploadOrder) {
+      const mrs_tg::TransferArray& a = arr[id];
+      if (!a.src || !a.bytes) continue;
+      if (a.staged) std::memcpy(staged(id), a.src, a.bytes);
+      else if (a.pinned) listed = up.add(a.pinned, dbase() + a.off, a.bytes) && listed;
+      else HIP_TRY(ctx, hipMemcpyAsync(dbase() + a.off, a.src, a.bytes, hipMemcpyHostToDevice, s));
+    }
+    if (lay.in_span_end > lay.span_begin)
+      listed = up.add(span(lay.span_begin), dbase() + lay.span_begin, lay.in_span_end - lay.span_begin) && listed;
+    if (!listed) return fail(ctx, MRS_TG_ERR_HIP, "more than %d copies in one upload", mrs_tg::kCopyMax);
+    HIP_TRY(ctx, mrs_tg::launch_copy_many(up, s));
+    return MRS_TG_OK;
+  }
+
+  // device to host, likewise; the staged outputs reach the caller in unpack_staged(), behind the synchronisation
+  int download() const {
+    if (zero_copy) return MRS_TG_OK;
+    mrs_tg::CopyList down;
+    bool listed = true;
+    if (lay.span_end > lay.out_span_begin)
+      listed = down.add(dbase() + lay.out_span_begin, span(lay.out_span_begin), lay.span_end - lay.out_span_begin);
+    for (int id : mrs_tg::kDownloadOrder) {
+      const mrs_tg::TransferArray& a = arr[id];
+      if (!a.dst || !a.bytes || a.staged) continue;
+      if (a.pinned && id == A_SMP)  // only the rows every path has produced (its capacity is sized for the longest acceptable one)
+        HIP_TRY(ctx, mrs_tg::launch_copy_samples(dev<const double>(A_SMP), static_cast<double*>(a.pinned), dev<const int32_t>(A_NS),
+                                                 n_paths, sample_capacity, s));
+      else if (a.pinned) listed = down.add(dbase() + a.off, a.pinned, a.bytes) && listed;
+      else HIP_TRY(ctx, hipMemcpyAsync(a.dst, dbase() + a.off, a.bytes, hipMemcpyDeviceToHost, s));
+    }
+    if (!listed) return fail(ctx, MRS_TG_ERR_HIP, "more than %d copies in one download", mrs_tg::kCopyMax);
+    HIP_TRY(ctx, mrs_tg::launch_copy_many(down, s));
+    return MRS_TG_OK;
+  }
+
+  void unpack_staged() const {
+    if (zero_copy) return;
+    for (int id : mrs_tg::kDownloadOrder)
+      if (arr[id].dst && arr[id].bytes && arr[id].staged) std::memcpy(arr[id].dst, staged(id), arr[id].bytes);
+  }
+};
+
+}  // namespace
+}  // extern "C++"
+
+static int solve_batch_impl(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* so, const double* wp, const uint8_t* mask,
+                            const double* vals, const double* limits, const mrs_tg_options* opt, double* seg_times,
+                            double* coeffs, int32_t* status, double* cost, int32_t* n_samples, double* samples,
+                            bool coeffs_required) {
+  // ---- check
+  if (!ctx) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "ctx is NULL");
+  int rc = check_options(ctx, opt);
+  if (rc != MRS_TG_OK) return rc;
+  if (!so || !mask || !vals || !seg_times || (!coeffs && coeffs_required) || !status)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "seg_offsets, fixed_mask, fixed_values, seg_times, coeffs_out, status_out are required");
+  if (n_paths == 0) return MRS_TG_OK;
+  const auto t_call = std::chrono::steady_clock::now();
+  // ---- plan
+  mrs_tg_plan* plan = nullptr;
+  if ((rc = cached_plan_for(ctx, n_paths, so, &plan)) != MRS_TG_OK) return rc;
+  const size_t nS = (size_t)so[n_paths], nV = nS + (size_t)n_paths, P = (size_t)n_paths;
+  const bool sampling = opt->sampling_dt > 0;
+  if (sampling && !n_samples) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_samples_out is required when sampling");
+  const size_t samp_doubles = sampling && samples ? P * (size_t)opt->sample_capacity * 4 : 0;
+  HIP_TRY(ctx, use_device(ctx->device));
+  HostCall call{ctx, ctx->stream, n_paths, opt->sample_capacity};
+
+  // ---- classify and lay out (the table and the three ways an array travels: mrs_tg_transfer.hpp)
+  // (the waypoints travel when something reads them: the time estimate, or kernels told that positions are the waypoints)
+  const bool want_wp = wp != nullptr && (opt->estimate_times != 0 || (opt->flags & MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS) != 0);
+  auto array = [stage_max = mrs_tg::knob::stage_max_bytes()](const void* src, void* dst, size_t bytes) {
+    return mrs_tg::classify(src, dst, bytes, stage_max, pinned_address);
+  };
+  call.arr[A_WP] = array(want_wp ? wp : nullptr, nullptr, want_wp ? nV * 4 * sizeof(double) : 0);
+  call.arr[A_MASK] = array(mask, nullptr, nV * 5);
+  call.arr[A_VALS] = array(vals, nullptr, nV * 20 * sizeof(double));
+  call.arr[A_LIM] = array(limits, nullptr, limits ? P * 9 * sizeof(double) : 0);
+  call.arr[A_T] = array(seg_times, seg_times, nS * sizeof(double));
+  call.arr[A_C] = array(nullptr, coeffs, nS * 40 * sizeof(double));
+  call.arr[A_ST] = array(nullptr, status, P * sizeof(int32_t));
+  call.arr[A_COST] = array(nullptr, cost, P * sizeof(double));
+  call.arr[A_NS] = array(nullptr, sampling ? n_samples : nullptr, P * sizeof(int32_t));
+  call.arr[A_SMP] = array(nullptr, samp_doubles ? samples : nullptr, samp_doubles * sizeof(double));
+  call.lay = mrs_tg::lay_out(call.arr);
+  // ---- ensure arenas
+  if ((rc = call.ensure_arenas()) != MRS_TG_OK) return rc;
+  SyncOnExit sync_on_exit{call.s};
+
+  // ---- infer flags and hint: the masks are in host memory here.  The moving-start hint matters to the outer loop's launch
+  // shape only (small batches of 13-15 segments; launch_nonlinear)
+  mrs_tg_options local = *opt;
+  const mrs_tg::ConstraintScan scan = mrs_tg::scan_constraints(
+      n_paths, so, mask, vals, local.derivative_to_optimize, !(local.flags & MRS_TG_FLAG_GENERAL_PATTERNS),
+      !(local.flags & MRS_TG_FLAG_CONSTRAINED_SLOTS),
+      local.time_alloc_method == MRS_TG_TIME_ALLOC_MELLINGER && n_paths <= 1536 && plan->view.max_segments >= 13 &&
+          plan->view.max_segments <= 15);
+  if (scan.general_patterns) local.flags |= MRS_TG_FLAG_GENERAL_PATTERNS;
+  if (scan.constrained_slots) local.flags |= MRS_TG_FLAG_CONSTRAINED_SLOTS;
+  mrs_tg::HintScope moving_scope(mrs_tg::set_moving_starts_hint, scan.moving_starts);
+  // ---- decide zero copy: one pass over every array (fixed times, default solve) and every array the caller passed is pinned
+  call.zero_copy = mrs_tg::knob::zero_copy() && local.time_alloc_method == MRS_TG_TIME_ALLOC_NONE && !local.estimate_times &&
+                   (local.flags & (MRS_TG_FLAG_GENERAL_PATTERNS | MRS_TG_FLAG_MATERIALIZED_BLOCKS)) == 0 &&
+                   mrs_tg::rows_kernel_applies(plan->view, sampling) && (!sampling || mrs_tg::rows_tail_sampling_pays(plan->view)) &&
+                   mrs_tg::every_array_pinned(call.arr);
+
+  // ---- upload, deduct the spent budget, solve, download, synchronise, unpack
+  if ((rc = call.upload()) != MRS_TG_OK) return rc;
+  if (local.max_time_s > 0) {  // what is left of the caller's budget when the kernels start
+    const double spent = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count();
+    local.max_time_s = local.max_time_s - spent > 1.0e-9 ? local.max_time_s - spent : 1.0e-9;
+  }
+  // (estimate_times without waypoints is refused by mrs_tg_plan_solve, as before)
+  rc = mrs_tg_plan_solve(plan, want_wp ? call.dev<double>(A_WP) : nullptr, call.dev<uint8_t>(A_MASK), call.dev<double>(A_VALS),
+                         limits ? call.dev<double>(A_LIM) : nullptr, &local, call.dev<double>(A_T), call.dev<double>(A_C),
+                         call.dev<int32_t>(A_ST), call.dev<double>(A_COST), sampling ? call.dev<int32_t>(A_NS) : nullptr,
+                         samp_doubles ? call.dev<double>(A_SMP) : nullptr);
+  if (rc != MRS_TG_OK) return rc;
+  if ((rc = call.download()) != MRS_TG_OK) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(call.s));
+  call.unpack_staged();
+  return MRS_TG_OK;
+}
 
 int mrs_tg_solve_batch(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* so, const double* wp, const uint8_t* mask,
                        const double* vals, const double* limits, const mrs_tg_options* opt, double* seg_times,
@@ -1425,233 +1598,6 @@ int solve_batch_samples_only(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* so
 }
 }  // namespace mrs_tg
 }  // extern "C++"
-
-static int solve_batch_impl(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* so, const double* wp, const uint8_t* mask,
-                            const double* vals, const double* limits, const mrs_tg_options* opt, double* seg_times,
-                            double* coeffs, int32_t* status, double* cost, int32_t* n_samples, double* samples,
-                            bool coeffs_required) {
-  if (!ctx) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "ctx is NULL");
-  int rc = check_options(ctx, opt);
-  if (rc != MRS_TG_OK) return rc;
-  if (!so || !mask || !vals || !seg_times || (!coeffs && coeffs_required) || !status)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "seg_offsets, fixed_mask, fixed_values, seg_times, coeffs_out, status_out are required");
-  if (n_paths == 0) return MRS_TG_OK;
-  const auto t_call = std::chrono::steady_clock::now();
-  mrs_tg_plan* plan = nullptr;
-  if ((rc = cached_plan_for(ctx, n_paths, so, &plan)) != MRS_TG_OK) return rc;
-  const size_t nS = (size_t)so[n_paths], nV = nS + (size_t)n_paths;
-  const bool sampling = opt->sampling_dt > 0;
-  if (sampling && !n_samples) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_samples_out is required when sampling");
-  const size_t samp_doubles = sampling && samples ? (size_t)n_paths * (size_t)opt->sample_capacity * 4 : 0;
-  HIP_TRY(ctx, use_device(ctx->device));
-  hipStream_t s = ctx->stream;
-
-  // ---- the arrays of the call.  Every one gets its place in ONE device block kept by the context (no allocation per call
-  // once a batch shape has been seen).  How an array travels depends on where the caller keeps it:
-  //   * pinned host memory (mrs_tg_host_alloc / mrs_tg_host_register, or any hipHostMalloc'ed block), which the GPU
-  //     addresses directly: all pinned inputs are gathered by ONE copy kernel, all pinned outputs scattered by one (a
-  //     kernel launch costs the host ~3 us, a hipMemcpyAsync 10-25 us, and seven of those were half of a 1024-path call).
-  //     Fixed-times mode with every array pinned needs no copy at all: the solve kernel reads the caller's inputs once and
-  //     writes the caller's outputs once, over PCIe, while it computes;
-  //   * pageable memory, small (<= stage_max bytes): packed into the context's pinned staging block, which travels with the
-  //     pinned arrays in the same copy kernel -- one transfer each way, no synchronisation in between;
-  //   * pageable memory, large: hipMemcpyAsync on the caller's buffer (the runtime pins the pages in place; staging 3 MB
-  //     of coefficients through another host copy costs more than that).
-  // Waypoints are only read by the time estimator: not uploaded when estimate_times is off.
-  const size_t stage_max = mrs_tg::knob::stage_max_bytes();
-  const bool zero_copy_allowed = mrs_tg::knob::zero_copy();
-  struct Arr {
-    const void* src;  // host source (inputs)
-    void* dst;        // host destination (outputs)
-    size_t bytes;
-    bool staged;
-    void* pinned;     // device-side address of the caller's array when it lives in pinned memory
-    size_t off;       // offset in the device arena
-  };
-  // device-side address of a host range the GPU can address as a whole: first AND last byte must be pinned and lie in the
-  // same mapping (a range that mrs_tg_host_register covers only in part, or an allocation shorter than the batch implies,
-  // takes the copying route -- where a short array is a host-side fault of the caller's, not a GPU page fault)
-  auto pinned_address = [](const void* ptr, size_t bytes) -> void* {
-    auto query = [](const void* q, hipPointerAttribute_t* at) {
-      if (hipPointerGetAttributes(at, q) != hipSuccess) {
-        (void)hipGetLastError();  // an ordinary (pageable) pointer is reported as an error by some runtimes
-        return false;
-      }
-      return at->type == hipMemoryTypeHost;
-    };
-    hipPointerAttribute_t first, last;
-    if (!query(ptr, &first)) return nullptr;
-    void* dev_first = first.devicePointer ? first.devicePointer : const_cast<void*>(ptr);
-    if (bytes > 1) {
-      const char* end = static_cast<const char*>(ptr) + (bytes - 1);
-      if (!query(end, &last)) return nullptr;
-      const char* dev_last = static_cast<const char*>(last.devicePointer ? last.devicePointer : (void*)end);
-      if (dev_last - static_cast<const char*>(dev_first) != (ptrdiff_t)(bytes - 1)) return nullptr;  // two mappings
-    }
-    return dev_first;
-  };
-  auto make = [&](const void* src, void* dst, size_t bytes) {
-    const void* host = src ? src : dst;
-    Arr a{src, dst, bytes, false, nullptr, 0};
-    if (host != nullptr && bytes > 0) {
-      a.pinned = pinned_address(host, bytes);
-      a.staged = a.pinned == nullptr && bytes <= stage_max;
-    }
-    return a;
-  };
-  // (the waypoints travel when something reads them: the time estimate, or kernels told that positions are the waypoints)
-  const bool want_wp = wp != nullptr && (opt->estimate_times != 0 || (opt->flags & MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS) != 0);
-  enum { A_WP, A_MASK, A_VALS, A_LIM, A_T, A_C, A_ST, A_COST, A_NS, A_SMP, A_COUNT };
-  Arr arr[A_COUNT] = {
-      make(want_wp ? wp : nullptr, nullptr, want_wp ? nV * 4 * sizeof(double) : 0),
-      make(mask, nullptr, nV * 5),
-      make(vals, nullptr, nV * 20 * sizeof(double)),
-      make(limits, nullptr, limits ? (size_t)n_paths * 9 * sizeof(double) : 0),
-      make(seg_times, seg_times, nS * sizeof(double)),
-      make(nullptr, coeffs, nS * 40 * sizeof(double)),
-      make(nullptr, status, (size_t)n_paths * sizeof(int32_t)),
-      make(nullptr, cost, (size_t)n_paths * sizeof(double)),   // the kernels want a cost buffer even when the caller does not
-      make(nullptr, sampling ? n_samples : nullptr, (size_t)n_paths * sizeof(int32_t)),
-      make(nullptr, samp_doubles ? samples : nullptr, samp_doubles * sizeof(double)),
-  };
-  // device layout: unstaged inputs | staged inputs | seg_times (in and out) | staged outputs | unstaged outputs: the staged
-  // arrays of each direction are one contiguous span, and the host arena mirrors [staged inputs | seg_times | staged outputs]
-  const int in_ids[4] = {A_WP, A_MASK, A_VALS, A_LIM};
-  const int out_ids[5] = {A_C, A_ST, A_COST, A_NS, A_SMP};
-  auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  size_t off = 0;
-  for (int id : in_ids)
-    if (!arr[id].staged) { arr[id].off = off; off += align(arr[id].bytes); }
-  const size_t span_begin = off;
-  for (int id : in_ids)
-    if (arr[id].staged) { arr[id].off = off; off += align(arr[id].bytes); }
-  const size_t t_off = off;
-  arr[A_T].off = off;
-  off += align(arr[A_T].bytes);
-  const size_t in_span_end = arr[A_T].staged ? off : t_off;
-  const size_t out_span_begin = arr[A_T].staged ? t_off : off;
-  for (int id : out_ids)
-    if (arr[id].staged) { arr[id].off = off; off += align(arr[id].bytes); }
-  const size_t span_end = off;
-  for (int id : out_ids)
-    if (!arr[id].staged) { arr[id].off = off; off += align(arr[id].bytes ? arr[id].bytes : 8); }
-  const size_t d_need = off ? off : 256, h_need = span_end - span_begin;
-  if (ctx->d_arena_bytes < d_need) {
-    if (ctx->d_arena) (void)mrs_tg::pool_free(ctx->d_arena);
-    ctx->d_arena = nullptr;
-    ctx->d_arena_bytes = 0;
-    HIP_TRY(ctx, mrs_tg::pool_alloc(&ctx->d_arena, d_need));
-    ctx->d_arena_bytes = d_need;
-  }
-  if (ctx->h_arena_bytes < h_need) {
-    if (ctx->h_arena) (void)hipHostFree(ctx->h_arena);
-    ctx->h_arena = nullptr;
-    ctx->h_arena_bytes = 0;
-    HIP_TRY(ctx, hipHostMalloc(&ctx->h_arena, h_need, hipHostMallocDefault));
-    ctx->h_arena_bytes = h_need;
-  }
-  char* dbase = static_cast<char*>(ctx->d_arena);
-  char* hbase = static_cast<char*>(ctx->h_arena) - span_begin;  // hbase + device offset = the array's place in the host arena
-  struct SyncOnExit {  // nothing of this call is in flight when it returns, on error paths as well (the arenas are reused)
-    hipStream_t st;
-    ~SyncOnExit() { (void)hipStreamSynchronize(st); }
-  } sync_on_exit{s};
-
-  mrs_tg_options local = *opt;
-  if (!(local.flags & MRS_TG_FLAG_GENERAL_PATTERNS)) {
-    // the masks are in host memory here: a vertex without a position constraint switches the general solver on
-    for (size_t v = 0; v < nV; ++v)
-      if (mask[v * 5] == 0) {
-        local.flags |= MRS_TG_FLAG_GENERAL_PATTERNS;
-        break;
-      }
-  }
-  if (!(local.flags & MRS_TG_FLAG_CONSTRAINED_SLOTS) && local.derivative_to_optimize == 4) {
-    // ... and an interior vertex with a constrained derivative slot (a stop_at waypoint) the instantiations that take it
-    for (int32_t p = 0; p < n_paths && !(local.flags & MRS_TG_FLAG_CONSTRAINED_SLOTS); ++p)
-      for (size_t v = (size_t)so[p] + p + 1; v < (size_t)so[p + 1] + p; ++v)
-        if (mask[v * 5 + 1] | mask[v * 5 + 2] | mask[v * 5 + 3] | mask[v * 5 + 4]) {
-          local.flags |= MRS_TG_FLAG_CONSTRAINED_SLOTS;
-          break;
-        }
-  }
-  // ... and a path that starts from a moving state (non-zero constrained derivatives at its first vertex): a hint for the
-  // outer loop's launch shape only (small batches of 13-15 segments; launch_nonlinear)
-  bool moving_starts = false;
-  if (local.time_alloc_method == MRS_TG_TIME_ALLOC_MELLINGER && n_paths <= 1536 && plan->view.max_segments >= 13 &&
-      plan->view.max_segments <= 15) {
-    for (int32_t p = 0; p < n_paths && !moving_starts; ++p) {
-      const size_t v = (size_t)so[p] + p;
-      for (int k = 1; k < 5 && !moving_starts; ++k)
-        if (mask[v * 5 + k])
-          for (int q = 0; q < 4; ++q) moving_starts = moving_starts || vals[(v * 5 + k) * 4 + q] != 0.0;
-    }
-  }
-  mrs_tg::HintScope moving_scope(mrs_tg::set_moving_starts_hint, moving_starts);
-  // zero copy: one pass over every array (fixed times, default solve) and every array the caller passed is pinned
-  bool zero_copy = zero_copy_allowed && local.time_alloc_method == MRS_TG_TIME_ALLOC_NONE && !local.estimate_times &&
-                   (local.flags & (MRS_TG_FLAG_GENERAL_PATTERNS | MRS_TG_FLAG_MATERIALIZED_BLOCKS)) == 0 &&
-                   mrs_tg::rows_kernel_applies(plan->view, sampling) && (!sampling || mrs_tg::rows_tail_sampling_pays(plan->view));
-  for (int id = 0; id < A_COUNT && zero_copy; ++id) {
-    const Arr& a = arr[id];
-    if (id == A_LIM) continue;  // the fixed-times solve never reads the limits: a pageable limits array does not decide this
-    if ((a.src || a.dst) && a.bytes && !a.pinned) zero_copy = false;
-  }
-  // where the kernels find array `id`: the caller's own (pinned) memory under zero copy, its slot of the arena otherwise
-  auto dev = [&](int id) -> void* {
-    const Arr& a = arr[id];
-    return (zero_copy && a.pinned && a.bytes) ? a.pinned : static_cast<void*>(dbase + a.off);
-  };
-
-  // ---- host to device
-  if (!zero_copy) {
-    mrs_tg::CopyList up;
-    for (int id : {A_WP, A_MASK, A_VALS, A_LIM, A_T}) {
-      const Arr& a = arr[id];
-      if (!a.src || !a.bytes) continue;
-      if (a.staged) std::memcpy(hbase + a.off, a.src, a.bytes);
-      else if (a.pinned) up.add(a.pinned, dbase + a.off, a.bytes);
-      else HIP_TRY(ctx, hipMemcpyAsync(dbase + a.off, a.src, a.bytes, hipMemcpyHostToDevice, s));
-    }
-    if (in_span_end > span_begin) up.add(hbase + span_begin, dbase + span_begin, in_span_end - span_begin);
-    HIP_TRY(ctx, mrs_tg::launch_copy_many(up, s));
-  }
-  if (local.max_time_s > 0) {  // what is left of the caller's budget when the kernels start
-    const double spent = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count();
-    local.max_time_s = local.max_time_s - spent > 1.0e-9 ? local.max_time_s - spent : 1.0e-9;
-  }
-  // (estimate_times without waypoints is refused by mrs_tg_plan_solve, as before)
-  rc = mrs_tg_plan_solve(plan, want_wp ? static_cast<double*>(dev(A_WP)) : nullptr, static_cast<uint8_t*>(dev(A_MASK)),
-                         static_cast<double*>(dev(A_VALS)), limits ? static_cast<double*>(dev(A_LIM)) : nullptr, &local,
-                         static_cast<double*>(dev(A_T)), static_cast<double*>(dev(A_C)), static_cast<int32_t*>(dev(A_ST)),
-                         static_cast<double*>(dev(A_COST)), sampling ? static_cast<int32_t*>(dev(A_NS)) : nullptr,
-                         samp_doubles ? static_cast<double*>(dev(A_SMP)) : nullptr);
-  if (rc != MRS_TG_OK) return rc;
-
-  // ---- device to host: pinned arrays and the staged span in one copy kernel, large pageable arrays by the runtime; one
-  // synchronisation
-  if (!zero_copy) {
-    mrs_tg::CopyList down;
-    if (span_end > out_span_begin) down.add(dbase + out_span_begin, hbase + out_span_begin, span_end - out_span_begin);
-    for (int id : {A_T, A_C, A_ST, A_COST, A_NS, A_SMP}) {
-      const Arr& a = arr[id];
-      if (!a.dst || !a.bytes || a.staged) continue;
-      if (a.pinned && id == A_SMP)  // only the rows every path has produced (its capacity is sized for the longest acceptable one)
-        HIP_TRY(ctx, mrs_tg::launch_copy_samples(static_cast<const double*>(dev(A_SMP)), static_cast<double*>(a.pinned),
-                                                 static_cast<const int32_t*>(dev(A_NS)), n_paths, opt->sample_capacity, s));
-      else if (a.pinned) down.add(dbase + a.off, a.pinned, a.bytes);
-      else HIP_TRY(ctx, hipMemcpyAsync(a.dst, dbase + a.off, a.bytes, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(ctx, mrs_tg::launch_copy_many(down, s));
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  if (!zero_copy)
-    for (int id : {A_T, A_C, A_ST, A_COST, A_NS, A_SMP}) {
-      const Arr& a = arr[id];
-      if (a.dst && a.bytes && a.staged) std::memcpy(a.dst, hbase + a.off, a.bytes);
-    }
-  return MRS_TG_OK;
-}
 
 // Pinned host memory for the arrays of mrs_tg_solve_batch / mrs_tg_optimize_paths: buffers allocated (or registered) here
 // are read and written by the GPU's DMA engines directly, with no staging copy on either side.

@@ -10,6 +10,7 @@
 #include "mrs_tg_batch.hpp"
 #include "mrs_tg_hd.hpp"
 #include "mrs_tg_knobs.hpp"
+#include "mrs_tg_transfer.hpp"
 
 struct mrs_tg_ctx;
 
@@ -135,22 +136,7 @@ hipError_t launch_solve_linear(const BatchView& b, int d, bool fused, const uint
                                const double* seg_times, const double* H, const double* Ainv, double* ws,
                                double* coeffs, int32_t* status, double* cost, const int32_t* status_in,
                                hipStream_t stream, const double* pos_wp = nullptr);
-// Up to kCopyMax flat copies in ONE launch: how mrs_tg_solve_batch moves arrays between pinned host memory (which the
-// GPU addresses directly) and the device -- a kernel launch costs the host ~3 us, a hipMemcpyAsync 10-25 us.
-constexpr int kCopyMax = 8;
-struct CopyList {
-  const void* src[kCopyMax];
-  void* dst[kCopyMax];
-  unsigned long long bytes[kCopyMax];
-  int n = 0;
-  void add(const void* s, void* d, size_t b) {
-    if (b == 0 || s == nullptr || d == nullptr) return;
-    src[n] = s;
-    dst[n] = d;
-    bytes[n] = b;
-    ++n;
-  }
-};
+// (CopyList, up to kCopyMax flat copies in ONE launch: mrs_tg_transfer.hpp)
 hipError_t launch_copy_many(const CopyList& cl, hipStream_t stream);
 // samples [n_paths][capacity][4]: only the min(n_samples[p], capacity) rows a path has produced are copied (a sample buffer
 // is sized for the longest trajectory the caller would accept; a typical one uses a fraction of it)

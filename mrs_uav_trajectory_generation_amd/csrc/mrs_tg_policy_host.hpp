@@ -36,6 +36,7 @@
 #include "mrs_tg_baca.hpp"
 #include "mrs_tg_knobs.hpp"
 #include "mrs_tg_passage.hpp"
+#include "mrs_tg_transfer.hpp"
 
 struct mrs_tg_ctx;
 
@@ -49,7 +50,7 @@ struct PolicyRoundLayout {
   size_t ok, ns, status, max_dev, is_safe, safe, samples, total_bytes;   // results
 };
 inline PolicyRoundLayout policy_round_layout(size_t A, size_t nS, int32_t capacity) {
-  auto up = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+  constexpr auto up = align_slot;
   const size_t nV = nS + A;
   PolicyRoundLayout L{};
   size_t off = 0;
@@ -69,6 +70,30 @@ inline PolicyRoundLayout policy_round_layout(size_t A, size_t nS, int32_t capaci
   L.samples = off, off += up(A * (size_t)capacity * 4 * sizeof(double));  // rows of the FINISHED paths only
   L.total_bytes = off;
   return L;
+}
+// The device arena of the same round: [the block's input region] | results, laid out as in the block up to its samples |
+// what the solve reads and writes | the rows to copy per path | samples.  (arena + a.results - L.in_bytes + L.<result field>
+// is the field's mirror: a.results == L.in_bytes.)
+struct PolicyRoundArena {
+  size_t results, mask, vals, times, coeffs, cost, status, n_samples, rows, samples, total_bytes;
+};
+inline PolicyRoundArena policy_round_arena(const PolicyRoundLayout& L, size_t A, size_t nS, int32_t capacity) {
+  constexpr auto up = align_slot;
+  const size_t nV = nS + A;
+  PolicyRoundArena a{};
+  size_t off = L.in_bytes;
+  a.results = off, off += L.samples - L.in_bytes;
+  a.mask = off, off += up(nV * 5);
+  a.vals = off, off += up(nV * 20 * sizeof(double));
+  a.times = off, off += up(nS * sizeof(double));
+  a.coeffs = off, off += up(nS * 40 * sizeof(double));
+  a.cost = off, off += up(A * sizeof(double));
+  a.status = off, off += up(A * sizeof(int32_t));
+  a.n_samples = off, off += up(A * sizeof(int32_t));
+  a.rows = off, off += up(A * sizeof(int32_t));               // min(n_samples, capacity) of the finished paths, 0 otherwise
+  a.samples = off, off += up(A * (size_t)capacity * 4 * sizeof(double));
+  a.total_bytes = off;
+  return a;
 }
 constexpr int kVertexFirst = 1, kVertexLast = 2, kVertexStop = 4, kVertexInit = 8;
 struct PolicyRoundIn {
