@@ -484,6 +484,7 @@ __device__ __forceinline__ void solve_rows_body(const BatchView& b, int d, int p
         rs.seg0 = seg0;
         // vertices a side eliminates: [0, m) or (m, S]; a fully constrained end vertex (every rest-to-rest path has two)
         // has nothing to eliminate -- its rows are identity rows, its couplings are masked -- and is left out
+        // (tests/solve_rows_util.py::schedule is a hand-kept second copy of mid and nact: an edit here needs the same edit there)
         {
           const int len = rs.dir ? pr.S - rs.mid : rs.mid;
           const double* ef = vtx0 + (size_t)(rs.dir ? pr.S : 0) * kRVtxRec + kRVtxFree;

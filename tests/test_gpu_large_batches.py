@@ -68,7 +68,11 @@ def test_linear_ragged_large_batch(gpu_ctx):
 
 
 def test_long_paths_one_per_tile(gpu_ctx):
-    batch = pr.random_batch(6, 120, seed0=8100)             # 120 segments: one path per LDS tile
+    """Six paths of 120 segments.  The name is from the time when such a batch went to the tile kernel (one path per LDS tile);
+    since the rows kernel took over, the fixed-times solve and the closing solves of the Mellinger pipeline below run
+    solve_rows_kernel, one path per wavefront, above its 64 KB opt-in (the tile kernel takes over at 180 segments:
+    tests/test_gpu_solve_rows_lengths.py holds the rows kernel's lengths and that hand-over)."""
+    batch = pr.random_batch(6, 120, seed0=8100)
     out = gpu_ctx.solve_batch(batch, None)
     assert np.all(out["status"] == 1)
     _subset_vs_oracle(batch, out, list(range(6)), 1e-6)
