@@ -197,9 +197,12 @@ enum {
   MRS_TG_CAP_WAYPOINT_PASSAGE = 512,  /* mrs_tg_plan_waypoint_passage and mrs_tg_plan_waypoint_passage_vjp are exported: where the
                                          samples pass the requested waypoints (index, miss distance, foot point) and its
                                          backward pass */
-  MRS_TG_CAP_BACA = 1024              /* mrs_tg_plan_estimate_times_baca, mrs_tg_plan_estimate_times_baca_vjp and
+  MRS_TG_CAP_BACA = 1024,             /* mrs_tg_plan_estimate_times_baca, mrs_tg_plan_estimate_times_baca_vjp and
                                          mrs_tg_plan_length_gate are exported: the Baca segment-time estimate as a plan step, its
                                          backward pass, and the length gate on its total */
+  MRS_TG_CAP_FALLBACK_SAMPLE = 2048   /* mrs_tg_plan_unwrap_headings, mrs_tg_plan_fallback_sample and
+                                         mrs_tg_plan_fallback_sample_vjp are exported: the fallback sampler (findTrajectoryFallback)
+                                         as a plan step, its backward pass, and the heading unwrap in front of its clock */
 };
 
 /* mrs_tg_plan_estimate_times_vjp's term_out_dev: the term of the estimate a segment's time came from */
@@ -757,6 +760,52 @@ int mrs_tg_plan_length_gate(mrs_tg_plan* plan, const double* seg_times_dev, cons
                             double max_factor, double min_factor, const int32_t* status_dev, double* total_out_dev,
                             int32_t* verdict_out_dev);
 
+/* The heading unwrap as a plan step (MRS_TG_CAP_FALLBACK_SAMPLE; unwrap_headings_kernel): the
+ * sequential sradians::unwrap of findTrajectory / findTrajectoryFallback (:1233-1241) for every path of the plan.  waypoints_dev
+ * [sum V][4]; in waypoints_out_dev [sum V][4] vertex v of a path carries its heading unwrapped against the UNWRAPPED heading of
+ * vertex v - 1 (vertex 0 against itself), x, y, z copied.  One lane per path.  fmod, additions and comparisons only: the host's
+ * bits.  waypoints_out_dev == waypoints_dev is allowed; any other overlap is not.  What mrs_tg_plan_estimate_times_baca wants
+ * for its fourth column.  Device pointers, asynchronous on the context's stream. */
+int mrs_tg_plan_unwrap_headings(mrs_tg_plan* plan, const double* waypoints_dev, double* waypoints_out_dev);
+/* The fallback sampler as a plan step (fallback_sample_kernel): the interpolation loop of
+ * findTrajectoryFallback (:1327-1381) -- what a request gets that asks for it or runs over its time budget -- for every path of
+ * the plan: constant-rate interpolation of the waypoint polyline on seg_times_dev [sum S] (the reference: the Baca estimate of
+ * the unwrapped waypoints under the fallback's limits, mrs_tg_plan_estimate_times_baca).  waypoints_dev [sum V][4] are the RAW
+ * waypoints (x, y, z, heading as requested: :1362 interpolates those), stop_at_dev [sum V] (may be NULL: nobody stops; a path's
+ * first entry is ignored, its last never read) says where the trajectory dwells.  With insert = (int)round(stopping_time /
+ * sampling_dt), segment i of a path of S segments with time t gives
+ *   nd = (t > 0.1) ? ceil(t / sampling_dt) : 0          (strictly; a NaN or negative time: 0)
+ *   rows = nd + (nd > 0 && i == S - 1) + ((nd > 0 && i > 0 && stop_at[i]) ? insert : 0)
+ * and its row r (0-based) is, with j = max(r - inserted rows, 0) and coeff = (double)j * (1.0 / nd),
+ *   a + coeff (b - a) for x, y, z (no fused multiply-add: the host's bits) and
+ *   wrap_yaw(radians::interp(a_heading, b_heading, coeff)), the quaternion round trip setFromYaw / getYaw (sin, cos and atan2
+ *   are the device's: the heading is the host's up to their roundings, a last-bit flip between -pi and pi included).
+ * samples_out_dev [n_paths][sample_capacity][4]; n_samples_out_dev [n_paths] follows the solve's convention: the count when it
+ * fits, sample_capacity + 1 when it does not, and rows from min(count, sample_capacity) on are NOT written.
+ * seg_first_row_out_dev [sum S] (may be NULL): the row at which a segment's samples start, saturated at sample_capacity + 1; a
+ * segment without rows reports the row at which the next one starts.  A path none of whose segments is longer than 0.1 s has
+ * no rows; one whose last segment has none does not reach its last waypoint (the reference's behaviour).  Counts are 64-bit
+ * sums; a time of +inf takes part with a count of 2^31.  One wavefront per path.  MRS_TG_ERR_INVALID_ARG, before any launch:
+ * sampling_dt not positive and finite, stopping_time negative or not finite, an insert that does not fit int32,
+ * sample_capacity < 1 or > INT32_MAX - 1, a missing mandatory pointer.  Device pointers, asynchronous on the context's stream. */
+int mrs_tg_plan_fallback_sample(mrs_tg_plan* plan, const double* waypoints_dev, const uint8_t* stop_at_dev,
+                                const double* seg_times_dev, double sampling_dt, double stopping_time, int32_t sample_capacity,
+                                int32_t* n_samples_out_dev, double* samples_out_dev, int32_t* seg_first_row_out_dev);
+/* Backward pass of mrs_tg_plan_fallback_sample (fallback_sample_vjp_kernel): given grad_samples_dev
+ * [n_paths][sample_capacity][4] = dL/dsamples, writes dL/dwaypoints (grad_waypoints_out_dev [sum V][4]).  The counts are the
+ * forward's (the same device function on the same stop_at_dev, seg_times_dev, sampling_dt and stopping_time) and are held fixed:
+ * seg_times receives no gradient.  Row r of segment i gives vertex i the weight 1.0 - coeff and vertex i + 1 the weight coeff,
+ * all four columns alike: the heading column is the almost-everywhere derivative of wrap_yaw o radians::interp, its wrap seams
+ * and the direction chosen at a heading difference of exactly +-pi held fixed.  Every sum runs in a fixed order: vertex v's row
+ * starts at 0.0, takes the rows of segment v - 1 in increasing row index, each addend coeff * g rounded and then added, then the
+ * rows of segment v in increasing row index, each addend (1.0 - coeff) * g.  Only rows below min(count, sample_capacity) are
+ * read.  Deterministic, no atomics, no workspace, the same bits for a path wherever it sits in a batch; every element of
+ * grad_waypoints_out_dev that belongs to the plan is written exactly once, zeros included.  The argument checks are the
+ * forward's.  Device pointers, asynchronous on the context's stream. */
+int mrs_tg_plan_fallback_sample_vjp(mrs_tg_plan* plan, const uint8_t* stop_at_dev, const double* seg_times_dev, double sampling_dt,
+                                    double stopping_time, int32_t sample_capacity, const double* grad_samples_dev,
+                                    double* grad_waypoints_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
@@ -767,7 +816,9 @@ int mrs_tg_plan_length_gate(mrs_tg_plan* plan, const double* seg_times_dev, cons
  * (mrs_tg_plan_estimate_times; inside a solve the estimate is not timed), 11 its backward pass
  * (mrs_tg_plan_estimate_times_vjp), 12 waypoint passage (mrs_tg_plan_waypoint_passage), 13 its backward pass
  * (mrs_tg_plan_waypoint_passage_vjp), 14 the Baca estimate as a plan step (mrs_tg_plan_estimate_times_baca), 15 its backward
- * pass (mrs_tg_plan_estimate_times_baca_vjp), 16 the length gate (mrs_tg_plan_length_gate): seventeen ids, 0 .. 16.
+ * pass (mrs_tg_plan_estimate_times_baca_vjp), 16 the length gate (mrs_tg_plan_length_gate), 17 the heading unwrap
+ * (mrs_tg_plan_unwrap_headings), 18 the fallback sampler (mrs_tg_plan_fallback_sample), 19 its backward pass
+ * (mrs_tg_plan_fallback_sample_vjp): twenty ids, 0 .. 19.
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

@@ -49,6 +49,7 @@ KERNEL_DEVIATION, KERNEL_DEVIATION_VJP = 8, 9
 KERNEL_ESTIMATE, KERNEL_ESTIMATE_VJP = 10, 11
 KERNEL_PASSAGE, KERNEL_PASSAGE_VJP = 12, 13
 KERNEL_BACA, KERNEL_BACA_VJP, KERNEL_LENGTH_GATE = 14, 15, 16
+KERNEL_UNWRAP_HEADINGS, KERNEL_FALLBACK_SAMPLE, KERNEL_FALLBACK_SAMPLE_VJP = 17, 18, 19
 
 
 class MrsTgError(RuntimeError):
@@ -112,6 +113,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_plan_estimate_times", "mrs_tg_plan_estimate_times_vjp",
     "mrs_tg_plan_waypoint_passage", "mrs_tg_plan_waypoint_passage_vjp",
     "mrs_tg_plan_estimate_times_baca", "mrs_tg_plan_estimate_times_baca_vjp", "mrs_tg_plan_length_gate",
+    "mrs_tg_plan_unwrap_headings", "mrs_tg_plan_fallback_sample", "mrs_tg_plan_fallback_sample_vjp",
 ]
 
 _lib = None
@@ -231,6 +233,12 @@ def load_library():
     L.mrs_tg_plan_estimate_times_baca_vjp.argtypes = [vp, dp, dp, dp, dp, dp, ip]
     L.mrs_tg_plan_length_gate.restype = C.c_int
     L.mrs_tg_plan_length_gate.argtypes = [vp, dp, ip, C.c_double, C.c_double, C.c_double, ip, dp, ip]
+    L.mrs_tg_plan_unwrap_headings.restype = C.c_int
+    L.mrs_tg_plan_unwrap_headings.argtypes = [vp, dp, dp]
+    L.mrs_tg_plan_fallback_sample.restype = C.c_int
+    L.mrs_tg_plan_fallback_sample.argtypes = [vp, dp, vp, dp, C.c_double, C.c_double, C.c_int32, ip, dp, ip]
+    L.mrs_tg_plan_fallback_sample_vjp.restype = C.c_int
+    L.mrs_tg_plan_fallback_sample_vjp.argtypes = [vp, vp, dp, C.c_double, C.c_double, C.c_int32, dp, dp]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -286,6 +294,7 @@ CAP_DEVIATION = 128        # MRS_TG_CAP_DEVIATION: Plan.path_deviation (samples 
 CAP_ESTIMATE_GRADIENT = 256   # MRS_TG_CAP_ESTIMATE_GRADIENT: Plan.estimate_times (the Euclidean estimate as a plan step), Plan.estimate_times_vjp
 CAP_WAYPOINT_PASSAGE = 512    # MRS_TG_CAP_WAYPOINT_PASSAGE: Plan.waypoint_passage (where the samples pass the requested waypoints), Plan.waypoint_passage_vjp
 CAP_BACA = 1024               # MRS_TG_CAP_BACA: Plan.estimate_times_baca (the Baca estimate as a plan step), Plan.estimate_times_baca_vjp, Plan.length_gate
+CAP_FALLBACK_SAMPLE = 2048    # MRS_TG_CAP_FALLBACK_SAMPLE: Plan.unwrap_headings, Plan.fallback_sample (findTrajectoryFallback's rows as a plan step), Plan.fallback_sample_vjp
 # Plan.estimate_times_baca_vjp's flags: the branches of the Baca estimate a segment's time took, as bits (MRS_TG_BACA_*)
 BACA_V_VERTICAL, BACA_A_VERTICAL, BACA_J_VERTICAL, BACA_T1_CAPPED, BACA_T2_CAPPED = 1, 2, 4, 8, 16
 BACA_DOT1_CLAMPED, BACA_DOT2_CLAMPED, BACA_FLOOR, BACA_HEADING, BACA_HEADING_CRUISE, BACA_HEADING_ACC = 32, 64, 128, 256, 512, 1024
@@ -991,6 +1000,36 @@ class Plan:
         self.ctx._check(self._L.mrs_tg_plan_length_gate(self._h, _t_ptr(seg_times), _t_ptr(n_samples), float(sampling_dt),
                                                         float(max_factor), float(min_factor), _t_ptr(status), _t_ptr(total),
                                                         _t_ptr(verdict)), "mrs_tg_plan_length_gate")
+
+    def unwrap_headings(self, waypoints, waypoints_out=None):
+        """mrs_tg_plan_unwrap_headings: the headings of waypoints [sum V][4] unwrapped along every path (vertex v against the
+        unwrapped vertex v - 1) into waypoints_out (device tensors; None = in place), x, y, z copied, in the host's bits;
+        asynchronous on the context's stream."""
+        out = waypoints if waypoints_out is None else waypoints_out
+        self.ctx._check(self._L.mrs_tg_plan_unwrap_headings(self._h, _t_ptr(waypoints), _t_ptr(out)),
+                        "mrs_tg_plan_unwrap_headings")
+
+    def fallback_sample(self, waypoints, seg_times, sampling_dt, sample_capacity, n_samples, samples, stop_at=None,
+                        stopping_time=2.0, seg_first_row=None):
+        """mrs_tg_plan_fallback_sample: findTrajectoryFallback's rows -- constant-rate interpolation of the RAW waypoints
+        [sum V][4] on seg_times [sum S], a dwell of round(stopping_time / sampling_dt) repeated rows where stop_at [sum V]
+        (uint8, optional) is set -- into samples [n_paths][sample_capacity][4] and n_samples [n_paths] int32 (the count, or
+        sample_capacity + 1 when it does not fit; rows from the count on are not written); seg_first_row [sum S] int32
+        (optional) gets the row every segment starts at.  Device tensors; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_fallback_sample(self._h, _t_ptr(waypoints), _t_ptr(stop_at), _t_ptr(seg_times),
+                                                            float(sampling_dt), float(stopping_time), int(sample_capacity),
+                                                            _t_ptr(n_samples), _t_ptr(samples), _t_ptr(seg_first_row)),
+                        "mrs_tg_plan_fallback_sample")
+
+    def fallback_sample_vjp(self, seg_times, sampling_dt, sample_capacity, grad_samples, grad_waypoints, stop_at=None,
+                            stopping_time=2.0):
+        """mrs_tg_plan_fallback_sample_vjp: dL/dwaypoints [sum V][4] (written, zeros included) from dL/dsamples
+        [n_paths][sample_capacity][4] with the forward's counts held fixed (seg_times gets no gradient), every sum in a
+        stated order; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_fallback_sample_vjp(self._h, _t_ptr(stop_at), _t_ptr(seg_times), float(sampling_dt),
+                                                                float(stopping_time), int(sample_capacity),
+                                                                _t_ptr(grad_samples), _t_ptr(grad_waypoints)),
+                        "mrs_tg_plan_fallback_sample_vjp")
 
 
 class RoundRobin:

@@ -474,6 +474,91 @@ def estimate_times_baca(plan, waypoints, limits):
     return _EstimateTimesBaca.apply(plan, waypoints, limits)
 
 
+_FLT_MAX = 3.4028234663852886e+38   # (double)FLT_MAX: a relaxed heading's limits (:1285-1288)
+
+
+class _FallbackSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, waypoints, seg_times, sampling_dt, sample_capacity, stop_at, stopping_time):
+        w = waypoints.detach().to(torch.float64).contiguous()
+        t = seg_times.detach().to(torch.float64).contiguous()
+        if w.dim() != 2 or w.shape[0] != plan.n_segments + plan.n_paths or w.shape[1] != api.N_DIM:
+            raise ValueError("waypoints must be [sum V][4]")
+        if t.dim() != 1 or t.shape[0] != plan.n_segments:
+            raise ValueError("seg_times must be [sum S]")
+        stop = None if stop_at is None else stop_at.detach().to(torch.uint8).contiguous()
+        if stop is not None and (stop.dim() != 1 or stop.shape[0] != w.shape[0]):
+            raise ValueError("stop_at must be [sum V]")
+        cap = int(sample_capacity)
+        n = torch.empty(plan.n_paths, dtype=torch.int32, device=w.device)
+        # (the kernel writes the rows a path has; the rows at or beyond its count stay zero)
+        out = torch.zeros((plan.n_paths, cap, api.N_DIM), dtype=torch.float64, device=w.device)
+        plan.ctx.use_torch_stream()
+        plan.fallback_sample(w, t, float(sampling_dt), cap, n, out, stop_at=stop, stopping_time=float(stopping_time))
+        ctx.plan, ctx.dt, ctx.cap, ctx.stop, ctx.stopping_time = plan, float(sampling_dt), cap, stop, float(stopping_time)
+        ctx.save_for_backward(t)
+        ctx.mark_non_differentiable(n)
+        ctx.set_materialize_grads(False)
+        return out, n
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, _grad_n):
+        (t,) = ctx.saved_tensors
+        if grad_out is None or not ctx.needs_input_grad[1]:
+            return None, None, None, None, None, None, None
+        plan = ctx.plan
+        gw = torch.empty((plan.n_segments + plan.n_paths, api.N_DIM), dtype=torch.float64, device=t.device)
+        plan.ctx.use_torch_stream()   # (the autograd engine runs this on its own thread, on the forward's stream)
+        plan.fallback_sample_vjp(t, ctx.dt, ctx.cap, grad_out.to(torch.float64).contiguous(), gw, stop_at=ctx.stop,
+                                 stopping_time=ctx.stopping_time)
+        return None, gw, None, None, None, None, None
+
+
+def fallback_sample(plan, waypoints, seg_times, sampling_dt, sample_capacity, stop_at=None, stopping_time=2.0):
+    """(samples [n_paths][capacity][4], n_samples [n_paths] int32) of Plan.fallback_sample: the rows of findTrajectoryFallback
+    -- constant-rate interpolation of the RAW waypoints [sum V][4] on seg_times [sum S] (the reference: the Baca estimate), a
+    dwell of round(stopping_time / sampling_dt) repeated rows where stop_at [sum V] (uint8, optional) is set -- differentiable in
+    waypoints (float64 device tensors).  Rows at or beyond a path's n_samples are zero (n_samples = capacity + 1: more rows than
+    fit, the first capacity are there).  The counts are piecewise constant in seg_times and held fixed: seg_times gets no
+    gradient.  All four columns carry the interpolation weights; the heading column is the almost-everywhere derivative, its
+    wrap seams and the direction chosen at a heading difference of exactly pi held fixed.  The output is what path_deviation and
+    waypoint_passage read."""
+    return _FallbackSample.apply(plan, waypoints, seg_times, sampling_dt, sample_capacity, stop_at, stopping_time)
+
+
+def fallback_trajectory(plan, waypoints, limits, sampling_dt, sample_capacity, stop_at=None, relax_heading=None,
+                        speed_factor=1.0, accel_factor=1.0, stopping_time=2.0):
+    """(samples, n_samples) of the reference's whole findTrajectoryFallback on the device: the headings of waypoints
+    [sum V][4] unwrapped along every path (Plan.unwrap_headings), limits [n_paths][9] with entries 0, 1 times speed_factor and
+    3, 4 times accel_factor (_fallback_sampling_speed_factor_, _accel_factor_) and entries 2, 5, 8 lifted to FLT_MAX where
+    relax_heading [n_paths] (bool, optional) is set, the Baca estimate of that (Plan.estimate_times_baca, detached: the clock
+    gets no gradient), then fallback_sample on the RAW waypoints -- differentiable in waypoints through the rows alone."""
+    w = waypoints.detach().to(torch.float64).contiguous()
+    lim = limits.detach().to(torch.float64).clone()
+    # every shape is checked before the first launch: the unwrap and the clock below read and write [sum V] rows
+    if w.dim() != 2 or w.shape[0] != plan.n_segments + plan.n_paths or w.shape[1] != api.N_DIM:
+        raise ValueError("waypoints must be [sum V][4]")
+    if lim.dim() != 2 or lim.shape[0] != plan.n_paths or lim.shape[1] != 9:
+        raise ValueError("limits must be [n_paths][9]")
+    if stop_at is not None and (stop_at.dim() != 1 or stop_at.shape[0] != w.shape[0]):
+        raise ValueError("stop_at must be [sum V]")
+    if relax_heading is not None:
+        relax_heading = torch.as_tensor(relax_heading, device=lim.device).to(torch.bool)
+        if relax_heading.dim() != 1 or relax_heading.shape[0] != plan.n_paths:
+            raise ValueError("relax_heading must be [n_paths]")
+    lim[:, 0:2] *= float(speed_factor)
+    lim[:, 3:5] *= float(accel_factor)
+    if relax_heading is not None:
+        lim[:, [2, 5, 8]] = torch.where(relax_heading[:, None], torch.full_like(lim[:, [2, 5, 8]], _FLT_MAX), lim[:, [2, 5, 8]])
+    unwrapped = torch.empty_like(w)
+    times = torch.empty(plan.n_segments, dtype=torch.float64, device=w.device)
+    plan.ctx.use_torch_stream()
+    plan.unwrap_headings(w, unwrapped)
+    plan.estimate_times_baca(unwrapped, lim.contiguous(), times)
+    return fallback_sample(plan, waypoints, times, sampling_dt, sample_capacity, stop_at=stop_at, stopping_time=stopping_time)
+
+
 def _root(x, p):
     """x^(1/p) for x >= 0 with a finite gradient everywhere: 0 at x = 0 (where the root is never the active term of the
     scaling unless every term is 0, and the max(1, ...) then holds)"""

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/mrs_tg.h"
+#include "mrs_tg_fallback.hpp"
 #include "mrs_tg_launch.h"
 #include "mrs_tg_nonlinear.h"
 #include "mrs_tg_policy_host.hpp"
@@ -88,7 +89,7 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 17;  // kernel_id 0 .. 16 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 20;  // kernel_id 0 .. 19 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
   long long ev_count[kTimedKernels] = {};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
@@ -267,7 +268,7 @@ int mrs_tg_abi_version(void) { return MRS_TG_ABI_VERSION; }
 int mrs_tg_capabilities(void) {
   return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE |
          MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE | MRS_TG_CAP_DEVIATION |
-         MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE | MRS_TG_CAP_BACA;
+         MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE | MRS_TG_CAP_BACA | MRS_TG_CAP_FALLBACK_SAMPLE;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1263,6 +1264,62 @@ int mrs_tg_plan_length_gate(mrs_tg_plan* plan, const double* seg_times, const in
   ProfileScope ps(ctx, 16);
   HIP_TRY(ctx, mrs_tg::launch_length_gate(plan->view, seg_times, n_samples, sampling_dt, max_factor, min_factor, status, total_out,
                                           verdict_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_unwrap_headings(mrs_tg_plan* plan, const double* waypoints, double* waypoints_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!waypoints || !waypoints_out) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "waypoints_dev and waypoints_out_dev are required");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 17);
+  HIP_TRY(ctx, mrs_tg::launch_unwrap_headings(plan->view, waypoints, waypoints_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+// what the two fallback calls check before any launch -> MRS_TG_OK and the dwell's row count
+static int fallback_arguments(mrs_tg_ctx* ctx, double sampling_dt, double stopping_time, int32_t sample_capacity,
+                              int32_t* insert) {
+  if (!(sampling_dt > 0.0) || !std::isfinite(sampling_dt))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sampling_dt must be positive and finite");
+  if (!(stopping_time >= 0.0) || !std::isfinite(stopping_time))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "stopping_time must be non-negative and finite");
+  if (!mrs_tg::fbq::insert_count(stopping_time, sampling_dt, insert))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "round(stopping_time / sampling_dt) does not fit int32");
+  if (sample_capacity < 1 || sample_capacity > mrs_tg::fbq::kMaxCapacity)  // (capacity + 1 is a value the outputs report)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity must be in [1, %d]", mrs_tg::fbq::kMaxCapacity);
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_fallback_sample(mrs_tg_plan* plan, const double* waypoints, const uint8_t* stop_at, const double* seg_times,
+                                double sampling_dt, double stopping_time, int32_t sample_capacity, int32_t* n_samples_out,
+                                double* samples_out, int32_t* seg_first_row_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!waypoints || !seg_times || !n_samples_out || !samples_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "waypoints_dev, seg_times_dev, n_samples_out_dev and samples_out_dev are required");
+  int32_t insert = 0;
+  if (const int rc = fallback_arguments(ctx, sampling_dt, stopping_time, sample_capacity, &insert); rc != MRS_TG_OK) return rc;
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 18);
+  HIP_TRY(ctx, mrs_tg::launch_fallback_sample(plan->view, waypoints, stop_at, seg_times, sampling_dt, insert, sample_capacity,
+                                              n_samples_out, samples_out, seg_first_row_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_fallback_sample_vjp(mrs_tg_plan* plan, const uint8_t* stop_at, const double* seg_times, double sampling_dt,
+                                    double stopping_time, int32_t sample_capacity, const double* grad_samples,
+                                    double* grad_waypoints_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!seg_times || !grad_samples || !grad_waypoints_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "seg_times_dev, grad_samples_dev and grad_waypoints_out_dev are required");
+  int32_t insert = 0;
+  if (const int rc = fallback_arguments(ctx, sampling_dt, stopping_time, sample_capacity, &insert); rc != MRS_TG_OK) return rc;
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 19);
+  HIP_TRY(ctx, mrs_tg::launch_fallback_sample_vjp(plan->view, stop_at, seg_times, sampling_dt, insert, sample_capacity,
+                                                  grad_samples, grad_waypoints_out, ctx->stream));
   return MRS_TG_OK;
 }
 

@@ -267,6 +267,17 @@ hipError_t launch_baca_times_vjp(const BatchView& b, const double* wp, const dou
                                  double* grad_wp, double* grad_limits, int32_t* flags, hipStream_t stream);
 hipError_t launch_length_gate(const BatchView& b, const double* seg_times, const int32_t* n_samples, double dt, double max_factor,
                               double min_factor, const int32_t* status, double* total, int32_t* verdict, hipStream_t stream);
+// mrs_tg_plan_unwrap_headings / mrs_tg_plan_fallback_sample / mrs_tg_plan_fallback_sample_vjp (mrs_tg_fallback.hip): the headings
+// of waypoints [sum V][4] unwrapped along every path (out may be wp); the fallback sampler's rows [n_paths][capacity][4] of the
+// waypoint polyline on seg_times [sum S] with `insert` repeated rows at a stop_at waypoint (stop_at [sum V] and seg_first_row
+// [sum S] may be NULL); and its backward pass, dL/dwaypoints [sum V][4] from dL/dsamples.  Reads only, no workspace, LDS sized by the plan's longest path;
+// each timed as the kernel family of the pending ProfileScope
+hipError_t launch_unwrap_headings(const BatchView& b, const double* wp, double* out, hipStream_t stream);
+hipError_t launch_fallback_sample(const BatchView& b, const double* waypoints, const uint8_t* stop_at, const double* seg_times,
+                                  double dt, int insert, int capacity, int32_t* n_samples, double* samples,
+                                  int32_t* seg_first_row, hipStream_t stream);
+hipError_t launch_fallback_sample_vjp(const BatchView& b, const uint8_t* stop_at, const double* seg_times, double dt, int insert,
+                                      int capacity, const double* grad_samples, double* grad_waypoints, hipStream_t stream);
 // phase-split tile kernel (mrs_tg_tile.hip): small and medium batches whose per-path state fits in LDS
 bool tile_kernel_applies(const BatchView& b, bool fused);
 hipError_t launch_solve_tile(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,
