@@ -200,9 +200,12 @@ enum {
   MRS_TG_CAP_BACA = 1024,             /* mrs_tg_plan_estimate_times_baca, mrs_tg_plan_estimate_times_baca_vjp and
                                          mrs_tg_plan_length_gate are exported: the Baca segment-time estimate as a plan step, its
                                          backward pass, and the length gate on its total */
-  MRS_TG_CAP_FALLBACK_SAMPLE = 2048   /* mrs_tg_plan_unwrap_headings, mrs_tg_plan_fallback_sample and
+  MRS_TG_CAP_FALLBACK_SAMPLE = 2048,  /* mrs_tg_plan_unwrap_headings, mrs_tg_plan_fallback_sample and
                                          mrs_tg_plan_fallback_sample_vjp are exported: the fallback sampler (findTrajectoryFallback)
                                          as a plan step, its backward pass, and the heading unwrap in front of its clock */
+  MRS_TG_CAP_PATH_EDIT = 4096         /* mrs_tg_plan_preprocess_path, mrs_tg_plan_insert_midpoints and mrs_tg_plan_path_edit_vjp
+                                         are exported: the two steps that change the number of waypoints of a path (preprocessPath's
+                                         thinning, the mid-points of unsafe segments) and their one backward pass */
 };
 
 /* mrs_tg_plan_estimate_times_vjp's term_out_dev: the term of the estimate a segment's time came from */
@@ -806,6 +809,55 @@ int mrs_tg_plan_fallback_sample_vjp(mrs_tg_plan* plan, const uint8_t* stop_at_de
                                     double stopping_time, int32_t sample_capacity, const double* grad_samples_dev,
                                     double* grad_waypoints_out_dev);
 
+/* Path thinning as a plan step (MRS_TG_CAP_PATH_EDIT; thin_path_kernel, vertex_offsets_kernel, edit_write_kernel; DESIGN.md
+ * section 11e): preprocessPath (:431-500) for every path of the plan, where the waypoints are.  The plan is the plan of the INPUT
+ * paths: waypoints_dev [sum V][4] are its S + 1 vertices per path with their RAW headings, stop_at_dev [sum V] may be NULL
+ * (nobody stops).  Vertex i of a path of n vertices is kept behind the last kept vertex `last` as the reference's loop decides:
+ * the first and the last vertex always; an interior one is dropped when the straightener is enabled, n >= 3 and every vertex j
+ * in (last, i] stays within straightener_max_deviation of the segment wp[last] -> wp[i + 1] and passes both SIGNED heading
+ * comparisons (quirk B3 of the reference: radians::diff(first, mid) > limit, radians::diff(last, mid) > limit, no absolute value),
+ * else when sqrt(dx^2 + dy^2 + dz^2) < min_waypoint_distance against wp[last].  Comparisons as the host writes them: a NaN
+ * compares false everywhere.  No fused multiply-add, sqrt and fmod only: the rows mrs_tg_optimize_paths keeps, bit for bit.
+ * The result is PACKED, the batch a new plan can be created on: vertex_offsets_out_dev [n_paths + 1] (the first vertex of every
+ * edited path in the caller's path order, the total behind them), waypoints_out_dev [sum V][4] and, each NULL or written,
+ * stop_at_out_dev [sum V] and source_out_dev [sum V]: the batch-wide index of the input vertex an output vertex copies.  Every
+ * element below vertex_offsets_out[n_paths] is written exactly once, nothing at or behind it.  The caller reads
+ * vertex_offsets_out back (n_paths + 1 integers) to create the next plan: mrs_tg_plan_create takes host offsets.  The outputs may
+ * not overlap the inputs.  Three launches on the context's stream (one wavefront per path decides and counts, ONE workgroup sums
+ * the counts, one lane per output vertex writes); no kernel waits for another workgroup, no atomics.  MRS_TG_ERR_INVALID_ARG,
+ * before any launch: a missing mandatory pointer; a negative or NaN min_waypoint_distance or straightener threshold; sum V beyond
+ * int32.  Device pointers, asynchronous on the context's stream. */
+int mrs_tg_plan_preprocess_path(mrs_tg_plan* plan, const double* waypoints_dev, const uint8_t* stop_at_dev,
+                                double min_waypoint_distance, int32_t straightener_enabled, double straightener_max_deviation,
+                                double straightener_max_hdg_deviation, int32_t* vertex_offsets_out_dev, double* waypoints_out_dev,
+                                uint8_t* stop_at_out_dev, int32_t* source_out_dev);
+/* Mid-point subdivision as a plan step (insert_midpoints_kernel, vertex_offsets_kernel, edit_write_kernel; DESIGN.md section
+ * 11e): :739-753 of optimize() for every path of the plan.  segment_max_dev [sum S] is mrs_tg_plan_path_deviation's
+ * segment_max_out; a segment is unsafe when segment_max > max_deviation (the reference's d_seg > max_deviation on the maxima the
+ * deviation step reports; a NaN is never unsafe).  Original segment s of a path of V vertices gets the mid-point
+ * interpolatePoint(a, b, 0.5) (a + 0.5 (b - a) for x, y, z without a fused multiply-add, radians::interp for the raw heading: the
+ * host's bits) when it is unsafe AND (s > 0 OR first_segment OR V <= 2), V counted before any insertion.  A path with
+ * active_dev[p] == 0 (active_dev [n_paths], NULL = all) is copied unchanged: finished or failed paths.  The result is packed as
+ * mrs_tg_plan_preprocess_path packs it: vertex_offsets_out_dev [n_paths + 1], waypoints_out_dev [sum V + sum S][4] and, each
+ * NULL or written, stop_at_out_dev (0 for a mid-point), source_out_dev (for a mid-point the first vertex of its segment) and
+ * inserted_out_dev (1 for a mid-point).  A subdivided path may exceed MRS_TG_MAX_SEGMENTS: the step reports it, and
+ * mrs_tg_plan_create refuses it.  MRS_TG_ERR_INVALID_ARG, before any launch: a missing mandatory pointer; a negative or NaN
+ * max_deviation; sum V + sum S beyond int32.  Device pointers, asynchronous on the context's stream. */
+int mrs_tg_plan_insert_midpoints(mrs_tg_plan* plan, const double* waypoints_dev, const uint8_t* stop_at_dev,
+                                 const double* segment_max_dev, double max_deviation, int32_t first_segment,
+                                 const uint8_t* active_dev, int32_t* vertex_offsets_out_dev, double* waypoints_out_dev,
+                                 uint8_t* stop_at_out_dev, int32_t* source_out_dev, uint8_t* inserted_out_dev);
+/* Backward pass of both edit steps (path_edit_vjp_kernel): given vertex_offsets_dev, source_dev and
+ * inserted_dev as the step wrote them (inserted_dev NULL after thinning) and grad_waypoints_edited_dev [sum V'][4] = dL/d(edited
+ * waypoints), writes dL/dwaypoints (grad_waypoints_out_dev [sum V][4]) of the plan's INPUT vertices.  Nothing is recomputed: one
+ * lane per input vertex finds its copies in its path's run of source_dev, which is non-decreasing, by binary search.  Vertex v's
+ * row starts at 0.0 and takes, in this order, 0.5 * g (rounded, then added) of the mid-point of the segment in front of it, g of
+ * its own copy, 0.5 * g of the mid-point of its own segment.  All four columns alike: the heading column is the almost-everywhere
+ * derivative of radians::interp, its wrap held fixed.  A dropped vertex gets a zero row.  Deterministic, no atomics; every element
+ * that belongs to the plan is written exactly once.  Device pointers, asynchronous on the context's stream. */
+int mrs_tg_plan_path_edit_vjp(mrs_tg_plan* plan, const int32_t* vertex_offsets_dev, const int32_t* source_dev,
+                              const uint8_t* inserted_dev, const double* grad_waypoints_edited_dev, double* grad_waypoints_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
@@ -818,7 +870,9 @@ int mrs_tg_plan_fallback_sample_vjp(mrs_tg_plan* plan, const uint8_t* stop_at_de
  * (mrs_tg_plan_waypoint_passage_vjp), 14 the Baca estimate as a plan step (mrs_tg_plan_estimate_times_baca), 15 its backward
  * pass (mrs_tg_plan_estimate_times_baca_vjp), 16 the length gate (mrs_tg_plan_length_gate), 17 the heading unwrap
  * (mrs_tg_plan_unwrap_headings), 18 the fallback sampler (mrs_tg_plan_fallback_sample), 19 its backward pass
- * (mrs_tg_plan_fallback_sample_vjp): twenty ids, 0 .. 19.
+ * (mrs_tg_plan_fallback_sample_vjp), 20 path thinning (mrs_tg_plan_preprocess_path), 21 mid-point subdivision
+ * (mrs_tg_plan_insert_midpoints; both timed from their first launch to their last), 22 their backward pass
+ * (mrs_tg_plan_path_edit_vjp): twenty-three ids, 0 .. 22.
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

@@ -50,6 +50,7 @@ KERNEL_ESTIMATE, KERNEL_ESTIMATE_VJP = 10, 11
 KERNEL_PASSAGE, KERNEL_PASSAGE_VJP = 12, 13
 KERNEL_BACA, KERNEL_BACA_VJP, KERNEL_LENGTH_GATE = 14, 15, 16
 KERNEL_UNWRAP_HEADINGS, KERNEL_FALLBACK_SAMPLE, KERNEL_FALLBACK_SAMPLE_VJP = 17, 18, 19
+KERNEL_PREPROCESS_PATH, KERNEL_INSERT_MIDPOINTS, KERNEL_PATH_EDIT_VJP = 20, 21, 22
 
 
 class MrsTgError(RuntimeError):
@@ -114,6 +115,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_plan_waypoint_passage", "mrs_tg_plan_waypoint_passage_vjp",
     "mrs_tg_plan_estimate_times_baca", "mrs_tg_plan_estimate_times_baca_vjp", "mrs_tg_plan_length_gate",
     "mrs_tg_plan_unwrap_headings", "mrs_tg_plan_fallback_sample", "mrs_tg_plan_fallback_sample_vjp",
+    "mrs_tg_plan_preprocess_path", "mrs_tg_plan_insert_midpoints", "mrs_tg_plan_path_edit_vjp",
 ]
 
 _lib = None
@@ -239,6 +241,12 @@ def load_library():
     L.mrs_tg_plan_fallback_sample.argtypes = [vp, dp, vp, dp, C.c_double, C.c_double, C.c_int32, ip, dp, ip]
     L.mrs_tg_plan_fallback_sample_vjp.restype = C.c_int
     L.mrs_tg_plan_fallback_sample_vjp.argtypes = [vp, vp, dp, C.c_double, C.c_double, C.c_int32, dp, dp]
+    L.mrs_tg_plan_preprocess_path.restype = C.c_int
+    L.mrs_tg_plan_preprocess_path.argtypes = [vp, dp, vp, C.c_double, C.c_int32, C.c_double, C.c_double, ip, dp, vp, ip]
+    L.mrs_tg_plan_insert_midpoints.restype = C.c_int
+    L.mrs_tg_plan_insert_midpoints.argtypes = [vp, dp, vp, dp, C.c_double, C.c_int32, vp, ip, dp, vp, ip, vp]
+    L.mrs_tg_plan_path_edit_vjp.restype = C.c_int
+    L.mrs_tg_plan_path_edit_vjp.argtypes = [vp, ip, ip, vp, dp, dp]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -294,6 +302,7 @@ CAP_DEVIATION = 128        # MRS_TG_CAP_DEVIATION: Plan.path_deviation (samples 
 CAP_ESTIMATE_GRADIENT = 256   # MRS_TG_CAP_ESTIMATE_GRADIENT: Plan.estimate_times (the Euclidean estimate as a plan step), Plan.estimate_times_vjp
 CAP_WAYPOINT_PASSAGE = 512    # MRS_TG_CAP_WAYPOINT_PASSAGE: Plan.waypoint_passage (where the samples pass the requested waypoints), Plan.waypoint_passage_vjp
 CAP_BACA = 1024               # MRS_TG_CAP_BACA: Plan.estimate_times_baca (the Baca estimate as a plan step), Plan.estimate_times_baca_vjp, Plan.length_gate
+CAP_PATH_EDIT = 4096          # MRS_TG_CAP_PATH_EDIT: Plan.preprocess_path (preprocessPath's thinning), Plan.insert_midpoints (the mid-points of unsafe segments), Plan.path_edit_vjp
 CAP_FALLBACK_SAMPLE = 2048    # MRS_TG_CAP_FALLBACK_SAMPLE: Plan.unwrap_headings, Plan.fallback_sample (findTrajectoryFallback's rows as a plan step), Plan.fallback_sample_vjp
 # Plan.estimate_times_baca_vjp's flags: the branches of the Baca estimate a segment's time took, as bits (MRS_TG_BACA_*)
 BACA_V_VERTICAL, BACA_A_VERTICAL, BACA_J_VERTICAL, BACA_T1_CAPPED, BACA_T2_CAPPED = 1, 2, 4, 8, 16
@@ -1030,6 +1039,41 @@ class Plan:
                                                                 float(stopping_time), int(sample_capacity),
                                                                 _t_ptr(grad_samples), _t_ptr(grad_waypoints)),
                         "mrs_tg_plan_fallback_sample_vjp")
+
+    def preprocess_path(self, waypoints, vertex_offsets, waypoints_out, min_waypoint_distance=0.05, stop_at=None,
+                        straightener_enabled=False, straightener_max_deviation=0.0, straightener_max_hdg_deviation=0.0,
+                        stop_at_out=None, source=None):
+        """mrs_tg_plan_preprocess_path: preprocessPath's thinning of waypoints [sum V][4] (raw headings; stop_at [sum V] uint8,
+        optional) into a PACKED batch: vertex_offsets [n_paths + 1] int32, waypoints_out [sum V][4] and, optional, stop_at_out
+        [sum V] uint8 and source [sum V] int32 (the input vertex every output vertex copies) -- rows below
+        vertex_offsets[n_paths] are written, the rest is not; device tensors, asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_preprocess_path(self._h, _t_ptr(waypoints), _t_ptr(stop_at),
+                                                            float(min_waypoint_distance), 1 if straightener_enabled else 0,
+                                                            float(straightener_max_deviation),
+                                                            float(straightener_max_hdg_deviation), _t_ptr(vertex_offsets),
+                                                            _t_ptr(waypoints_out), _t_ptr(stop_at_out), _t_ptr(source)),
+                        "mrs_tg_plan_preprocess_path")
+
+    def insert_midpoints(self, waypoints, segment_max, max_deviation, vertex_offsets, waypoints_out, first_segment=True,
+                         stop_at=None, active=None, stop_at_out=None, source=None, inserted=None):
+        """mrs_tg_plan_insert_midpoints: a mid-point into every segment whose segment_max [sum S] (Plan.path_deviation's)
+        exceeds max_deviation, by the reference's rule (:739-753), for the paths active [n_paths] uint8 (optional: all) marks;
+        the others are copied.  Packed as preprocess_path packs: vertex_offsets [n_paths + 1] int32, waypoints_out
+        [sum V + sum S][4] and, optional, stop_at_out uint8, source int32, inserted uint8 [sum V + sum S]; device tensors,
+        asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_insert_midpoints(self._h, _t_ptr(waypoints), _t_ptr(stop_at), _t_ptr(segment_max),
+                                                             float(max_deviation), 1 if first_segment else 0, _t_ptr(active),
+                                                             _t_ptr(vertex_offsets), _t_ptr(waypoints_out), _t_ptr(stop_at_out),
+                                                             _t_ptr(source), _t_ptr(inserted)),
+                        "mrs_tg_plan_insert_midpoints")
+
+    def path_edit_vjp(self, vertex_offsets, source, grad_waypoints_edited, grad_waypoints, inserted=None):
+        """mrs_tg_plan_path_edit_vjp: dL/dwaypoints [sum V][4] of this (the input) plan's vertices (written, zeros included) from
+        dL/d(edited waypoints) [sum V'][4] and what the edit step wrote (vertex_offsets, source, inserted; inserted None after
+        thinning), every sum in a stated order; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_path_edit_vjp(self._h, _t_ptr(vertex_offsets), _t_ptr(source), _t_ptr(inserted),
+                                                          _t_ptr(grad_waypoints_edited), _t_ptr(grad_waypoints)),
+                        "mrs_tg_plan_path_edit_vjp")
 
 
 class RoundRobin:

@@ -76,7 +76,18 @@ two segment times as well -- estimate, solve, feasibility scaling, re-solve, sam
     >>> samples, n = sample(plan, coeffs, times, 0.2, 512, status)
     >>> deviation, cursor = path_deviation(plan, samples, n, wp, first_segment=True, status=status)
     >>> torch.relu(deviation - 0.05).sum().backward()             # wp.grad (values, polyline AND times), lim.grad
+
+preprocess_path and insert_midpoints (Plan.preprocess_path / Plan.insert_midpoints forward, Plan.path_edit_vjp backward:
+mrs_tg_plan_path_edit_vjp) are the two stages that change the number of waypoints: they return the plan of
+the edited batch with its waypoints, so the chain above carries on behind an unsafe segment and its gradient still arrives at
+the requested waypoints -- a copy passes its row on, a mid-point gives half of its row to each end of its segment:
+
+    >>> plan1, wp1, stop1, source = preprocess_path(plan, wp, min_waypoint_distance=0.05)
+    >>> ...                                                       # estimate, solve, sample on plan1 / wp1
+    >>> plan1.path_deviation(samples.detach(), n, wp1.detach(), segment_max=segment_max)   # [sum S] of plan1, preallocated
+    >>> plan2, wp2, stop2, source, inserted = insert_midpoints(plan1, wp1, segment_max, 0.05)
 """
+import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -557,6 +568,100 @@ def fallback_trajectory(plan, waypoints, limits, sampling_dt, sample_capacity, s
     plan.unwrap_headings(w, unwrapped)
     plan.estimate_times_baca(unwrapped, lim.contiguous(), times)
     return fallback_sample(plan, waypoints, times, sampling_dt, sample_capacity, stop_at=stop_at, stopping_time=stopping_time)
+
+
+class _PathEdit(torch.autograd.Function):
+    """both edit steps: thin (segment_max None) or subdivide; the outputs cut to the edited batch's size, which the forward reads
+    back with the offsets"""
+
+    @staticmethod
+    def forward(ctx, plan, waypoints, stop_at, segment_max, args):
+        w = waypoints.detach().to(torch.float64).contiguous()
+        n_v = plan.n_segments + plan.n_paths
+        if w.dim() != 2 or w.shape[0] != n_v or w.shape[1] != api.N_DIM:
+            raise ValueError("waypoints must be [sum V][4]")
+        stop = None if stop_at is None else stop_at.detach().to(torch.uint8).contiguous()
+        if stop is not None and (stop.dim() != 1 or stop.shape[0] != n_v):
+            raise ValueError("stop_at must be [sum V]")
+        dev = w.device
+        subdivide = segment_max is not None
+        upper = n_v + (plan.n_segments if subdivide else 0)
+        offsets = torch.empty(plan.n_paths + 1, dtype=torch.int32, device=dev)
+        out = torch.empty((upper, api.N_DIM), dtype=torch.float64, device=dev)
+        stop_out = torch.empty(upper, dtype=torch.uint8, device=dev)
+        source = torch.empty(upper, dtype=torch.int32, device=dev)
+        inserted = torch.empty(upper, dtype=torch.uint8, device=dev) if subdivide else None
+        plan.ctx.use_torch_stream()
+        if subdivide:
+            m = segment_max.detach().to(torch.float64).contiguous()
+            if m.dim() != 1 or m.shape[0] != plan.n_segments:
+                raise ValueError("segment_max must be [sum S]")
+            active = args.get("active")
+            if active is not None:
+                active = active.detach().to(torch.uint8).contiguous()
+                if active.dim() != 1 or active.shape[0] != plan.n_paths:
+                    raise ValueError("active must be [n_paths]")
+            plan.insert_midpoints(w, m, args["max_deviation"], offsets, out, first_segment=args["first_segment"], stop_at=stop,
+                                  active=active, stop_at_out=stop_out, source=source, inserted=inserted)
+        else:
+            plan.preprocess_path(w, offsets, out, min_waypoint_distance=args["min_waypoint_distance"], stop_at=stop,
+                                 straightener_enabled=args["straightener_enabled"],
+                                 straightener_max_deviation=args["straightener_max_deviation"],
+                                 straightener_max_hdg_deviation=args["straightener_max_hdg_deviation"], stop_at_out=stop_out,
+                                 source=source)
+        total = int(offsets[-1].item())   # the one readback: the caller needs the offsets on the host for the next plan anyway
+        out, stop_out, source = out[:total], stop_out[:total], source[:total]
+        inserted = inserted[:total] if subdivide else torch.zeros(0, dtype=torch.uint8, device=dev)
+        ctx.plan, ctx.subdivide = plan, subdivide
+        ctx.save_for_backward(offsets, source, inserted)
+        ctx.mark_non_differentiable(stop_out, source, inserted, offsets)
+        ctx.set_materialize_grads(False)
+        return out, stop_out, source, inserted, offsets
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, *_):
+        offsets, source, inserted = ctx.saved_tensors
+        if grad_out is None or not ctx.needs_input_grad[1]:
+            return None, None, None, None, None
+        plan = ctx.plan
+        gw = torch.empty((plan.n_segments + plan.n_paths, api.N_DIM), dtype=torch.float64, device=source.device)
+        plan.ctx.use_torch_stream()   # (the autograd engine runs this on its own thread, on the forward's stream)
+        plan.path_edit_vjp(offsets, source, grad_out.to(torch.float64).contiguous(), gw,
+                           inserted=inserted if ctx.subdivide else None)
+        return None, gw, None, None, None
+
+
+def _edited_plan(plan, offsets):
+    off = offsets.cpu().numpy().astype("int64")
+    return api.Plan(plan.ctx, off - np.arange(off.size))   # a path of V vertices has V - 1 segments
+
+
+def preprocess_path(plan, waypoints, min_waypoint_distance=0.05, stop_at=None, straightener_enabled=False,
+                    straightener_max_deviation=0.0, straightener_max_hdg_deviation=0.0):
+    """(new plan, waypoints [sum V'][4], stop_at [sum V'] uint8, source [sum V'] int32) of Plan.preprocess_path: preprocessPath's
+    thinning of waypoints [sum V][4] (raw headings; stop_at [sum V] uint8, optional) -- the packed batch the new plan is created
+    on.  The kept rows are copies: differentiable in waypoints through Plan.path_edit_vjp, a dropped vertex gets a zero row; which
+    vertices are kept is piecewise constant and held fixed.  source[k] is the input vertex row k copies.  One readback (the
+    offsets) per call."""
+    args = dict(min_waypoint_distance=float(min_waypoint_distance), straightener_enabled=bool(straightener_enabled),
+                straightener_max_deviation=float(straightener_max_deviation),
+                straightener_max_hdg_deviation=float(straightener_max_hdg_deviation))
+    out, stop_out, source, _, offsets = _PathEdit.apply(plan, waypoints, stop_at, None, args)
+    return _edited_plan(plan, offsets), out, stop_out, source
+
+
+def insert_midpoints(plan, waypoints, segment_max, max_deviation, first_segment=True, stop_at=None, active=None):
+    """(new plan, waypoints [sum V'][4], stop_at [sum V'] uint8, source [sum V'] int32, inserted [sum V'] uint8) of
+    Plan.insert_midpoints: a mid-point into every segment whose segment_max [sum S] (path_deviation's fourth result) exceeds
+    max_deviation, by the reference's rule, for the paths active [n_paths] (optional: all) marks.  Differentiable in waypoints
+    through Plan.path_edit_vjp: a copy carries its gradient, a mid-point gives half of its to each end of its segment, all four
+    columns alike (the heading column is the almost-everywhere derivative of radians::interp, its wrap held fixed); which
+    segments are subdivided is held fixed, segment_max gets no gradient.  Raises when a subdivided path is longer than a plan
+    takes (api.MrsTgError from mrs_tg_plan_create).  One readback (the offsets) per call."""
+    args = dict(max_deviation=float(max_deviation), first_segment=bool(first_segment), active=active)
+    out, stop_out, source, inserted, offsets = _PathEdit.apply(plan, waypoints, stop_at, segment_max, args)
+    return _edited_plan(plan, offsets), out, stop_out, source, inserted
 
 
 def _root(x, p):

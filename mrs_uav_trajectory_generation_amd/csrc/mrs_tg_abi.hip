@@ -24,6 +24,7 @@
 
 #include "../../include/mrs_tg.h"
 #include "mrs_tg_fallback.hpp"
+#include "mrs_tg_pathedit.hpp"
 #include "mrs_tg_launch.h"
 #include "mrs_tg_nonlinear.h"
 #include "mrs_tg_policy_host.hpp"
@@ -89,7 +90,7 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 20;  // kernel_id 0 .. 19 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 23;  // kernel_id 0 .. 22 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
   long long ev_count[kTimedKernels] = {};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
@@ -121,6 +122,7 @@ struct mrs_tg_plan {
   size_t ws_doubles = 0;
   double* d_H = nullptr;
   double* d_Ainv = nullptr;
+  int32_t* d_edit_ws = nullptr;  // one int32 per vertex: what the path-edit steps pass from their first launch to their last
   mrs_tg::NonlinearPlan nl;
 };
 
@@ -268,7 +270,8 @@ int mrs_tg_abi_version(void) { return MRS_TG_ABI_VERSION; }
 int mrs_tg_capabilities(void) {
   return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE |
          MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE | MRS_TG_CAP_DEVIATION |
-         MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE | MRS_TG_CAP_BACA | MRS_TG_CAP_FALLBACK_SAMPLE;
+         MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE | MRS_TG_CAP_BACA | MRS_TG_CAP_FALLBACK_SAMPLE |
+         MRS_TG_CAP_PATH_EDIT;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -510,6 +513,7 @@ void mrs_tg_plan_destroy(mrs_tg_plan* plan) {
   if (plan->d_ws) (void)mrs_tg::pool_free(plan->d_ws);
   if (plan->d_H) (void)mrs_tg::pool_free(plan->d_H);
   if (plan->d_Ainv) (void)mrs_tg::pool_free(plan->d_Ainv);
+  if (plan->d_edit_ws) (void)mrs_tg::pool_free(plan->d_edit_ws);
   delete plan;
 }
 
@@ -1320,6 +1324,70 @@ int mrs_tg_plan_fallback_sample_vjp(mrs_tg_plan* plan, const uint8_t* stop_at, c
   ProfileScope ps(ctx, 19);
   HIP_TRY(ctx, mrs_tg::launch_fallback_sample_vjp(plan->view, stop_at, seg_times, sampling_dt, insert, sample_capacity,
                                                   grad_samples, grad_waypoints_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+// what the two path-edit steps check before any launch: the bound on the edited batch's vertices fits int32, the scratch is there
+static int path_edit_ready(mrs_tg_plan* plan, long long upper_bound) {
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (upper_bound > 2147483647ll)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "the edited batch may have %lld vertices, which does not fit int32", upper_bound);
+  HIP_TRY(ctx, use_device(ctx->device));
+  if (!plan->d_edit_ws) {
+    const size_t n = (size_t)plan->view.n_segments + (size_t)plan->view.n_paths;
+    HIP_TRY(ctx, mrs_tg::pool_alloc(&plan->d_edit_ws, sizeof(int32_t) * (n ? n : 1)));
+  }
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_preprocess_path(mrs_tg_plan* plan, const double* waypoints, const uint8_t* stop_at, double min_waypoint_distance,
+                                int32_t straightener_enabled, double straightener_max_deviation,
+                                double straightener_max_hdg_deviation, int32_t* vertex_offsets_out, double* waypoints_out,
+                                uint8_t* stop_at_out, int32_t* source_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!waypoints || !vertex_offsets_out || !waypoints_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "waypoints_dev, vertex_offsets_out_dev and waypoints_out_dev are required");
+  if (!(min_waypoint_distance >= 0.0) || !(straightener_max_deviation >= 0.0) || !(straightener_max_hdg_deviation >= 0.0))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
+                "min_waypoint_distance and the straightener's thresholds must be non-negative numbers");
+  if (const int rc = path_edit_ready(plan, (long long)plan->view.n_segments + plan->view.n_paths); rc != MRS_TG_OK) return rc;
+  const mrs_tg::pathq::ThinOptions o{min_waypoint_distance, straightener_enabled != 0, straightener_max_deviation,
+                                     straightener_max_hdg_deviation};
+  ProfileScope ps(ctx, 20);
+  HIP_TRY(ctx, mrs_tg::launch_preprocess_path(plan->view, waypoints, stop_at, o, plan->d_edit_ws, vertex_offsets_out, waypoints_out,
+                                              stop_at_out, source_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_insert_midpoints(mrs_tg_plan* plan, const double* waypoints, const uint8_t* stop_at, const double* segment_max,
+                                 double max_deviation, int32_t first_segment, const uint8_t* active, int32_t* vertex_offsets_out,
+                                 double* waypoints_out, uint8_t* stop_at_out, int32_t* source_out, uint8_t* inserted_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!waypoints || !segment_max || !vertex_offsets_out || !waypoints_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
+                "waypoints_dev, segment_max_dev, vertex_offsets_out_dev and waypoints_out_dev are required");
+  if (!(max_deviation >= 0.0)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "max_deviation must be a non-negative number");
+  if (const int rc = path_edit_ready(plan, 2ll * plan->view.n_segments + plan->view.n_paths); rc != MRS_TG_OK) return rc;
+  ProfileScope ps(ctx, 21);
+  HIP_TRY(ctx, mrs_tg::launch_insert_midpoints(plan->view, waypoints, stop_at, segment_max, max_deviation, first_segment != 0, active,
+                                               plan->d_edit_ws, vertex_offsets_out, waypoints_out, stop_at_out, source_out,
+                                               inserted_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_path_edit_vjp(mrs_tg_plan* plan, const int32_t* vertex_offsets, const int32_t* source, const uint8_t* inserted,
+                              const double* grad_waypoints_edited, double* grad_waypoints_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!vertex_offsets || !source || !grad_waypoints_edited || !grad_waypoints_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
+                "vertex_offsets_dev, source_dev, grad_waypoints_edited_dev and grad_waypoints_out_dev are required");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 22);
+  HIP_TRY(ctx, mrs_tg::launch_path_edit_vjp(plan->view, vertex_offsets, source, inserted, grad_waypoints_edited, grad_waypoints_out,
+                                            ctx->stream));
   return MRS_TG_OK;
 }
 

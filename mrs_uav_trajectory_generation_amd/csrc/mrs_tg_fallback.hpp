@@ -30,6 +30,7 @@
 
 #include "mrs_tg_baca.hpp"
 #include "mrs_tg_hd.hpp"
+#include "mrs_tg_pathedit.hpp"
 
 namespace mrs_tg {
 namespace fbq {
@@ -38,6 +39,7 @@ using baca::kPi;
 using baca::radians_diff;
 using baca::wrap_range;
 using mrs_tg::accumulate;
+using pathq::interp_heading;  // mrs_lib radians::interp (angles into [0, 2 pi)): the one copy, mrs_tg_pathedit.hpp
 
 constexpr double kMinSegmentTime = 1e-1;        // :1336, strictly
 constexpr int32_t kMaxCapacity = 2147483646;   // the largest sample_capacity: capacity + 1, which the outputs report, fits int32
@@ -51,12 +53,6 @@ MRS_TG_HD inline double unwrap(double what, double from) {
   if (d < -kPi) d += two_pi;
   else if (d >= kPi) d -= two_pi;
   return from + d;
-}
-
-// mrs_lib radians::interp (angles into [0, 2 pi))
-MRS_TG_HD inline double interp_heading(double from, double to, double c) {
-  MRS_TG_NO_CONTRACT
-  return wrap_range(from + c * radians_diff(to, from), 0.0, 2.0 * kPi);
 }
 
 // the yaw a sample carries after EigenTrajectoryPoint::setFromYaw / getYaw: quaternionFromYaw = (cos(y / 2), 0, 0, sin(y / 2)),

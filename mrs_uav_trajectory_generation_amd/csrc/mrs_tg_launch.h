@@ -16,6 +16,10 @@ struct mrs_tg_ctx;
 
 namespace mrs_tg {
 
+namespace pathq {
+struct ThinOptions;  // mrs_tg_pathedit.hpp
+}
+
 // Per-dispatch timing (mrs_tg_set_profiling): the next launch of the kernel family a ProfileScope names carries these
 // events on the launch itself (hipExtLaunchKernelGGL), so their difference is the dispatch's own start-to-end time.
 struct KernelTimer {
@@ -278,6 +282,23 @@ hipError_t launch_fallback_sample(const BatchView& b, const double* waypoints, c
                                   int32_t* seg_first_row, hipStream_t stream);
 hipError_t launch_fallback_sample_vjp(const BatchView& b, const uint8_t* stop_at, const double* seg_times, double dt, int insert,
                                       int capacity, const double* grad_samples, double* grad_waypoints, hipStream_t stream);
+// mrs_tg_plan_preprocess_path / mrs_tg_plan_insert_midpoints / mrs_tg_plan_path_edit_vjp (mrs_tg_pathedit.hip): the two steps that
+// change the number of vertices of a path -- preprocessPath's thinning of waypoints [sum V][4] and the mid-points of the segments
+// whose segment_max [sum S] exceeds max_deviation (active [n_paths] may be NULL: every path) -- each as a PACKED batch: offsets
+// [n_paths + 1] (written: the edited paths' first vertices and their total), waypoints_out, stop_out, source_out, inserted_out
+// (rows below offsets[n_paths] written once; the last three may be NULL); ws: one int32 per vertex of the plan.  Three launches
+// each (decide and count per path, one workgroup for the offsets, one lane per output vertex), timed from the first to the last
+// as the kernel family of the pending ProfileScope.  Their backward pass: dL/dwaypoints [sum V][4] from dL/dedited rows.
+constexpr int kPathEditScanChunk = 1024;  // paths the offsets' one workgroup takes at a time
+hipError_t launch_preprocess_path(const BatchView& b, const double* waypoints, const uint8_t* stop_at,
+                                  const pathq::ThinOptions& o, int32_t* ws, int32_t* offsets, double* waypoints_out,
+                                  uint8_t* stop_out, int32_t* source_out, hipStream_t stream);
+hipError_t launch_insert_midpoints(const BatchView& b, const double* waypoints, const uint8_t* stop_at, const double* segment_max,
+                                   double max_deviation, int first_segment, const uint8_t* active, int32_t* ws, int32_t* offsets,
+                                   double* waypoints_out, uint8_t* stop_out, int32_t* source_out, uint8_t* inserted_out,
+                                   hipStream_t stream);
+hipError_t launch_path_edit_vjp(const BatchView& b, const int32_t* offsets, const int32_t* source, const uint8_t* inserted,
+                                const double* grad_edited, double* grad_waypoints, hipStream_t stream);
 // phase-split tile kernel (mrs_tg_tile.hip): small and medium batches whose per-path state fits in LDS
 bool tile_kernel_applies(const BatchView& b, bool fused);
 hipError_t launch_solve_tile(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,

@@ -36,6 +36,7 @@
 #include "mrs_tg_baca.hpp"
 #include "mrs_tg_knobs.hpp"
 #include "mrs_tg_passage.hpp"
+#include "mrs_tg_pathedit.hpp"
 #include "mrs_tg_transfer.hpp"
 
 struct mrs_tg_ctx;
@@ -112,10 +113,8 @@ namespace policy {
 using baca::radians_diff;  // mrs_lib radians::diff (angles into [0, 2 pi))
 using baca::wrap_range;
 
-// mrs_lib radians::interp (angles in [0, 2 pi)), sradians::unwrap
-inline double radians_interp(double from, double to, double coeff) {
-  return wrap_range(from + coeff * radians_diff(to, from), 0.0, 2.0 * M_PI);
-}
+// mrs_lib radians::interp (angles in [0, 2 pi)): mrs_tg_pathedit.hpp's; sradians::unwrap
+inline double radians_interp(double from, double to, double coeff) { return pathq::interp_heading(from, to, coeff); }
 inline double sradians_unwrap(double what, double from) {
   const double two_pi = 2.0 * M_PI;
   double d = wrap_range(what, -M_PI, two_pi) - wrap_range(from, -M_PI, two_pi);
@@ -131,10 +130,7 @@ inline double wrap_yaw(double y) {
   return std::atan2(2.0 * (w * z), 1.0 - 2.0 * (z * z));
 }
 
-inline void interpolate_point(const double* a, const double* b, double coeff, double* out) {  // :1612-1625
-  for (int k = 0; k < 3; ++k) out[k] = a[k] + coeff * (b[k] - a[k]);
-  out[3] = radians_interp(a[3], b[3], coeff);
-}
+using pathq::interpolate_point;  // :1612-1625
 
 // estimateSegmentTimesBaca, /root/reference/src/eth_trajectory_generation/vertex.cpp:301-485; wp [V][4] unwrapped
 inline void estimate_times_baca(int S, const double* wp, const double* lim, std::vector<double>& out) {
@@ -222,33 +218,19 @@ struct PathState {
   double baca_total = 0.0;
 };
 
+// the thinning decision is pathq::keeps (mrs_tg_pathedit.hpp), which thin_path_kernel calls too
 inline void preprocess(const mrs_tg_waypoint* in, int n_in, const mrs_tg_policy_options& o, PathState& st) {  // :431-500
   st.wps.clear();
   st.stop.clear();
+  static_assert(sizeof(mrs_tg_waypoint) % sizeof(double) == 0 && offsetof(mrs_tg_waypoint, coords) == 0, "rows of doubles");
+  const size_t stride = sizeof(mrs_tg_waypoint) / sizeof(double);
+  const double* rows = reinterpret_cast<const double*>(in);  // x, y, z, heading in front of every `stride` doubles
+  const pathq::ThinOptions thin{o.min_waypoint_distance, o.path_straightener_enabled, o.path_straightener_max_deviation,
+                                o.path_straightener_max_hdg_deviation};
   int last_added = 0;
   for (int i = 0; i < n_in; ++i) {
+    if (!pathq::keeps(rows, stride, n_in, last_added, i, thin)) continue;
     const double* w = in[i].coords;
-    if (o.path_straightener_enabled && n_in >= 3 && i > 0 && i < n_in - 1) {
-      const double* first = in[last_added].coords;
-      const double* last = in[i + 1].coords;
-      bool segment_is_ok = true;
-      for (int j = last_added + 1; j < i + 1; ++j) {
-        const double* mid = in[j].coords;
-        // quirk B3 of the reference: fabs() wraps the comparison, so the heading test is signed
-        if (devq::dist(mid, first, last) > o.path_straightener_max_deviation ||
-            (radians_diff(first[3], mid[3]) > o.path_straightener_max_hdg_deviation) ||
-            (radians_diff(last[3], mid[3]) > o.path_straightener_max_hdg_deviation)) {
-          segment_is_ok = false;
-          break;
-        }
-      }
-      if (segment_is_ok) continue;
-    }
-    if (i > 0 && i < n_in - 1) {
-      const double* first = in[last_added].coords;
-      const double dx = first[0] - w[0], dy = first[1] - w[1], dz = first[2] - w[2];
-      if (std::sqrt(dx * dx + dy * dy + dz * dz) < o.min_waypoint_distance) continue;
-    }
     st.wps.insert(st.wps.end(), w, w + 4);
     st.stop.push_back(in[i].stop_at);
     last_added = i;
@@ -267,9 +249,10 @@ inline bool validate_spatial(const double* samples, int n_samples, const PathSta
 }
 
 inline void insert_midpoints(PathState& st, const std::vector<uint8_t>& safe, const mrs_tg_policy_options& o) {  // :739-753
+  const int V = st.n_wp;  // (the reference tests the size where nothing has been inserted yet: pathq::inserts)
   int w = 0, sidx = 0;
   while (w < st.n_wp - 1) {
-    if (!safe[sidx] && (w > 0 || o.max_deviation_first_segment || st.n_wp <= 2)) {
+    if (pathq::inserts(!safe[sidx], sidx, o.max_deviation_first_segment, V)) {
       double mid[4];
       interpolate_point(st.wps.data() + (size_t)w * 4, st.wps.data() + (size_t)(w + 1) * 4, 0.5, mid);
       st.wps.insert(st.wps.begin() + (size_t)(w + 1) * 4, mid, mid + 4);
