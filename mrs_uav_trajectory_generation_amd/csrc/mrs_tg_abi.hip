@@ -44,43 +44,6 @@ void set_global_error(const std::string& s) {
 
 static std::atomic<int> g_live_contexts{0};
 
-// A block a context keeps across calls and only ever replaces by a larger one: a device block from the pool, or pinned host
-// memory (hipHostMalloc).  A device block goes back to the pool with its stream synchronised, which is the pool's contract
-// (every user of these blocks ends its call with a synchronise, so that one finds an idle stream; it runs when a block grows,
-// never in a steady-state call).
-struct GrowBlock {
-  enum Kind { kDevicePool, kPinnedHost };
-  Kind kind;
-  void* ptr = nullptr;
-  size_t bytes = 0;
-  explicit GrowBlock(Kind k) : kind(k) {}
-  // what the synchronise before a device block's return said: a stream that has faulted is reported, not passed over
-  hipError_t release(hipStream_t stream) {
-    hipError_t e = hipSuccess;
-    if (ptr && kind == kDevicePool) {
-      e = hipStreamSynchronize(stream);
-      mrs_tg::pool_free(ptr);
-    } else if (ptr) {
-      (void)hipHostFree(ptr);
-    }
-    ptr = nullptr;
-    bytes = 0;
-    return e;
-  }
-  // at least `need` bytes; a block that has to grow is allocated with need / headroom_divisor more (0: exactly `need`).  A
-  // need of 0 bytes allocates nothing and leaves an empty block empty (ptr null), for every kind of block
-  hipError_t ensure(size_t need, size_t headroom_divisor, hipStream_t stream) {
-    if (bytes >= need && (ptr || need == 0)) return hipSuccess;
-    const hipError_t synced = release(stream);
-    if (synced != hipSuccess) return synced;
-    const size_t want = need + (headroom_divisor ? need / headroom_divisor : 0);
-    const hipError_t e = kind == kDevicePool ? mrs_tg::pool_alloc(&ptr, want) : hipHostMalloc(&ptr, want, hipHostMallocDefault);
-    if (e != hipSuccess) ptr = nullptr;
-    else bytes = want;
-    return e;
-  }
-};
-
 struct mrs_tg_ctx {
   int device = -1;
   hipStream_t own_stream = nullptr;
@@ -98,12 +61,14 @@ struct mrs_tg_ctx {
   // plan of the most recent mrs_tg_solve_batch: a caller that sends the same batch shape again (the nodelet's
   // deviation loop, a server's fixed batch size) skips the analysis, the uploads and the device allocations
   mrs_tg_plan* cached_plan = nullptr;
-  // mrs_tg_solve_batch's transfer arenas, kept across calls: one device block holding every input and output array of a
-  // call, and a pinned host block (hipHostMalloc) through which the small host arrays travel packed, one copy each way
-  GrowBlock d_arena{GrowBlock::kDevicePool};
-  GrowBlock h_arena{GrowBlock::kPinnedHost};
+  // mrs_tg_solve_batch's transfer arenas, kept across calls and only ever replaced by larger ones: one device block holding
+  // every input and output array of a call, and a pinned host block (hipHostMalloc) through which the small host arrays travel
+  // packed, one copy each way.  The device block grows behind a synchronise of the stream (StreamIdle; every user of it ends
+  // its call with a synchronise, so that one finds an idle stream, and it runs when the block grows, never in a steady-state call)
+  mrs_tg::DeviceBlock<char> d_arena;
+  mrs_tg::Block<char, mrs_tg::PinnedAlloc> h_arena;
   // pinned host scratch of mrs_tg_optimize_paths (the arrays of its rounds), kept across calls
-  GrowBlock h_scratch{GrowBlock::kPinnedHost};
+  mrs_tg::Block<char, mrs_tg::PinnedAlloc> h_scratch;
   // what the most recent mrs_tg_find_trajectory decided (mrs_tg_find_trajectory_info)
   int32_t find_rejection = 0;
   double find_baca_total = 0.0;
@@ -114,15 +79,11 @@ struct mrs_tg_plan {
   mrs_tg::BatchView view{};
   std::vector<int32_t> order_host;
   std::vector<int32_t> seg_offsets_host;
-  int32_t* d_seg_offsets = nullptr;
-  int32_t* d_order = nullptr;
-  int32_t* d_slot_start = nullptr;
-  // lazily allocated scratch
-  double* d_ws = nullptr;
-  size_t ws_doubles = 0;
-  double* d_H = nullptr;
-  double* d_Ainv = nullptr;
-  int32_t* d_edit_ws = nullptr;  // one int32 per vertex: what the path-edit steps pass from their first launch to their last
+  mrs_tg::DeviceBlock<int32_t> d_seg_offsets;  // seg_offsets | order | slot_start in one block (view has the three parts)
+  // scratch, allocated on first use; mrs_tg_plan_destroy synchronises and then deletes the plan with its blocks
+  mrs_tg::DeviceBlock<double> d_ws;  // grows with what a call needs, behind a synchronise (StreamIdle)
+  mrs_tg::DeviceBlock<double> d_H, d_Ainv;  // MRS_TG_FLAG_MATERIALIZED_BLOCKS: both or neither (ensure_both)
+  mrs_tg::DeviceBlock<int32_t> d_edit_ws;  // one int32 per vertex: what a path-edit step passes from its first launch to its last
   mrs_tg::NonlinearPlan nl;
 };
 
@@ -200,27 +161,6 @@ hipError_t use_device(int device) {
   return hipSetDevice(device);                                                        // have switched: ask, do not remember)
 }
 
-int ensure_ws(mrs_tg_plan* plan, size_t doubles) {
-  if (plan->ws_doubles >= doubles) return MRS_TG_OK;
-  if (plan->d_ws) {
-    (void)hipStreamSynchronize(plan->ctx->stream);  // pool contract: no work in flight on a block that is given back
-    mrs_tg::pool_free(plan->d_ws);
-  }
-  plan->d_ws = nullptr;
-  plan->ws_doubles = 0;
-  HIP_TRY(plan->ctx, mrs_tg::pool_alloc(&plan->d_ws, doubles * sizeof(double)));
-  plan->ws_doubles = doubles;
-  return MRS_TG_OK;
-}
-
-int ensure_blocks(mrs_tg_plan* plan) {
-  if (plan->d_H) return MRS_TG_OK;
-  const size_t bytes = mrs_tg_plan_block_bytes(plan);
-  HIP_TRY(plan->ctx, mrs_tg::pool_alloc(&plan->d_H, bytes));
-  HIP_TRY(plan->ctx, mrs_tg::pool_alloc(&plan->d_Ainv, bytes));
-  return MRS_TG_OK;
-}
-
 int check_options(mrs_tg_ctx* ctx, const mrs_tg_options* opt) {
   if (!opt) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "options is NULL");
   if (opt->derivative_to_optimize < 0 || opt->derivative_to_optimize > 4)
@@ -247,21 +187,6 @@ int report_error(mrs_tg_ctx* ctx, int code, const char* fmt, ...) {
   return fail(ctx, code, "%s", buf);
 }
 }  // namespace mrs_tg
-
-namespace {
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)mrs_tg::pool_free(p);
-  }
-  hipError_t alloc(size_t bytes) { return mrs_tg::pool_alloc(&p, bytes ? bytes : 8); }
-  template <class T>
-  T* as() {
-    return static_cast<T*>(p);
-  }
-};
-}  // namespace
-
 
 extern "C" {
 
@@ -372,7 +297,6 @@ void mrs_tg_destroy(mrs_tg_ctx* ctx) {
     for (hipEvent_t e : ctx->ev_stop[i])
       if (e) (void)hipEventDestroy(e);
   }
-  for (GrowBlock* b : {&ctx->d_arena, &ctx->h_arena, &ctx->h_scratch}) (void)b->release(ctx->stream);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
   if (--g_live_contexts == 0) {  // the sampling tables and the cached device blocks go with the last context
@@ -485,18 +409,17 @@ int mrs_tg_plan_create(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* so, mrs_
   if (n_paths == 0) packed.push_back(0);
   const size_t off_slot = packed.size();
   packed.insert(packed.end(), slot_start.begin(), slot_start.end());
-  if ((e = mrs_tg::pool_alloc(&plan->d_seg_offsets, sizeof(int32_t) * packed.size())) != hipSuccess ||
-      (e = hipMemcpy(plan->d_seg_offsets, packed.data(), sizeof(int32_t) * packed.size(), hipMemcpyHostToDevice)) != hipSuccess)
+  if ((e = plan->d_seg_offsets.ensure(packed.size())) != hipSuccess ||
+      (e = hipMemcpy(plan->d_seg_offsets.get(), packed.data(), sizeof(int32_t) * packed.size(), hipMemcpyHostToDevice)) !=
+          hipSuccess)
     return cleanup(fail(ctx, MRS_TG_ERR_HIP, "plan allocation failed: %s", hipGetErrorString(e)));
-  plan->d_order = plan->d_seg_offsets + off_order;        // (parts of the one block: mrs_tg_plan_destroy frees d_seg_offsets)
-  plan->d_slot_start = plan->d_seg_offsets + off_slot;
   plan->view.n_paths = n_paths;
   plan->view.n_segments = so[n_paths];
   plan->view.max_segments = max_S;
   plan->view.uniform_S = (n_paths > 0 && min_S == max_S) ? max_S : 0;
-  plan->view.seg_offsets = plan->d_seg_offsets;
-  plan->view.order = plan->d_order;
-  plan->view.slot_start = plan->d_slot_start;
+  plan->view.seg_offsets = plan->d_seg_offsets.get();
+  plan->view.order = plan->view.seg_offsets + off_order;  // (views into the one block)
+  plan->view.slot_start = plan->view.seg_offsets + off_slot;
   const int rc = mrs_tg::nonlinear_plan_build(plan->nl, plan->seg_offsets_host, plan->order_host);
   if (rc != 0) return cleanup(fail(ctx, MRS_TG_ERR_HIP, "nonlinear plan setup failed"));
   *plan_out = plan;
@@ -507,14 +430,7 @@ void mrs_tg_plan_destroy(mrs_tg_plan* plan) {
   if (!plan) return;
   (void)use_device(plan->ctx->device);
   (void)hipStreamSynchronize(plan->ctx->stream);
-  mrs_tg::nonlinear_plan_free(plan->nl);
-  if (plan->d_seg_offsets) (void)mrs_tg::pool_free(plan->d_seg_offsets);
-  // (d_order and d_slot_start are parts of the block d_seg_offsets heads)
-  if (plan->d_ws) (void)mrs_tg::pool_free(plan->d_ws);
-  if (plan->d_H) (void)mrs_tg::pool_free(plan->d_H);
-  if (plan->d_Ainv) (void)mrs_tg::pool_free(plan->d_Ainv);
-  if (plan->d_edit_ws) (void)mrs_tg::pool_free(plan->d_edit_ws);
-  delete plan;
+  delete plan;  // its blocks go back to the pool behind the synchronise above
 }
 
 int32_t mrs_tg_plan_n_paths(const mrs_tg_plan* plan) { return plan ? plan->view.n_paths : 0; }
@@ -627,13 +543,14 @@ int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
   } else {
     const bool fused = (opt->flags & MRS_TG_FLAG_MATERIALIZED_BLOCKS) == 0;  // the default since ABI 2
     const bool general = (opt->flags & MRS_TG_FLAG_GENERAL_PATTERNS) != 0;   // position-free vertices may occur
-    if ((rc = ensure_ws(plan, general ? std::max(mrs_tg::linear_workspace_doubles(b), mrs_tg::general_workspace_doubles(b))
-                                      : mrs_tg::linear_workspace_doubles(b))) != MRS_TG_OK)
-      return rc;
+    HIP_TRY(ctx, plan->d_ws.ensure(general ? std::max(mrs_tg::linear_workspace_doubles(b), mrs_tg::general_workspace_doubles(b))
+                                           : mrs_tg::linear_workspace_doubles(b),
+                                   mrs_tg::StreamIdle{ctx->stream}));
     if (!fused) {
-      if ((rc = ensure_blocks(plan)) != MRS_TG_OK) return rc;
+      const size_t block_doubles = mrs_tg_plan_block_bytes(plan) / sizeof(double);
+      HIP_TRY(ctx, mrs_tg::ensure_both(plan->d_H, block_doubles, plan->d_Ainv, block_doubles));
       ProfileScope ps(ctx, 0);
-      HIP_TRY(ctx, mrs_tg::launch_assemble(b, d, seg_times, plan->d_H, plan->d_Ainv, ctx->stream));
+      HIP_TRY(ctx, mrs_tg::launch_assemble(b, d, seg_times, plan->d_H.get(), plan->d_Ainv.get(), ctx->stream));
     }
     ProfileScope ps(ctx, 1);
     if (fused && !general && solve_sampling_dt > 0 && mrs_tg::rows_tail_sampling_pays(b)) {  // solve and sample in one launch
@@ -645,16 +562,17 @@ int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
       HIP_TRY(ctx, mrs_tg::launch_solve_rows(b, d, mask, vals, seg_times, coeffs, status, cost, nullptr, ctx->stream, tail));
       sampled = true;
     } else {
-      HIP_TRY(ctx, mrs_tg::launch_solve_linear(b, d, fused, mask, vals, seg_times, plan->d_H, plan->d_Ainv, plan->d_ws,
-                                               coeffs, status, cost, nullptr, ctx->stream, general ? nullptr : pos_wp));
+      HIP_TRY(ctx, mrs_tg::launch_solve_linear(b, d, fused, mask, vals, seg_times, plan->d_H.get(), plan->d_Ainv.get(),
+                                               plan->d_ws.get(), coeffs, status, cost, nullptr, ctx->stream,
+                                               general ? nullptr : pos_wp));
     }
     // the paths the fast kernels sent back with status -2 (a vertex without a position constraint): 5 x 5 vertex blocks
     if (general)
-      HIP_TRY(ctx, mrs_tg::launch_solve_general(b, d, mask, vals, seg_times, plan->d_ws, coeffs, status, cost, ctx->stream));
+      HIP_TRY(ctx, mrs_tg::launch_solve_general(b, d, mask, vals, seg_times, plan->d_ws.get(), coeffs, status, cost, ctx->stream));
   }
   if (refine) {  // every mode's final solve: the paths with status > 0 at the returned times (the dry run allocates nothing)
-    if (!mrs_tg::dry_run() && (rc = ensure_ws(plan, mrs_tg::refine_workspace_doubles(b))) != MRS_TG_OK) return rc;
-    HIP_TRY(ctx, mrs_tg::launch_refine(b, d, mask, vals, seg_times, plan->d_ws, coeffs, status, cost, ctx->stream));
+    if (!mrs_tg::dry_run()) HIP_TRY(ctx, plan->d_ws.ensure(mrs_tg::refine_workspace_doubles(b), mrs_tg::StreamIdle{ctx->stream}));
+    HIP_TRY(ctx, mrs_tg::launch_refine(b, d, mask, vals, seg_times, plan->d_ws.get(), coeffs, status, cost, ctx->stream));
   }
   if (opt->sampling_dt > 0 && !sampled)
     HIP_TRY(ctx, mrs_tg::launch_sample(b, coeffs, seg_times, opt->sampling_dt, opt->sample_capacity, n_samples, samples,
@@ -698,9 +616,6 @@ int mrs_tg_plan_bind_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* m
                   "MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS: %lld vertices whose position constraint is absent or differs from their waypoint",
                   bad);
   }
-  mrs_tg_bound_solve* b = new (std::nothrow) mrs_tg_bound_solve{plan, wp, mask, vals, limits, *opt, seg_times, coeffs, status, cost,
-                                                                n_samples, samples};
-  if (!b) return fail(plan->ctx, MRS_TG_ERR_NOMEM, "out of host memory");
   // A fixed-times default solve can go out in grouped launches (mrs_tg_bound_solve_launch_group), whose saturated-device kernel
   // wants one factor store per batch of the group for paths that need the general step.  SMALL plans reserve it HERE, once,
   // so that the first large group does not pay an allocation and a stream synchronisation inside somebody's timed region;
@@ -711,12 +626,12 @@ int mrs_tg_plan_bind_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* m
       !(opt->flags & (MRS_TG_FLAG_MATERIALIZED_BLOCKS | MRS_TG_FLAG_GENERAL_PATTERNS)) &&
       mrs_tg::quad_kernel_applies(plan->view, (long long)plan->view.n_paths * mrs_tg::kRowsGroupMax, false) &&
       (size_t)mrs_tg::kRowsGroupMax * mrs_tg::linear_workspace_doubles(plan->view) * sizeof(double) <= kGroupWsPresizeBytes) {
-    const int rcw = ensure_ws(plan, (size_t)mrs_tg::kRowsGroupMax * mrs_tg::linear_workspace_doubles(plan->view));
-    if (rcw != MRS_TG_OK) {
-      delete b;
-      return rcw;
-    }
+    HIP_TRY(plan->ctx, plan->d_ws.ensure((size_t)mrs_tg::kRowsGroupMax * mrs_tg::linear_workspace_doubles(plan->view),
+                                         mrs_tg::StreamIdle{plan->ctx->stream}));
   }
+  mrs_tg_bound_solve* b = new (std::nothrow) mrs_tg_bound_solve{plan, wp, mask, vals, limits, *opt, seg_times, coeffs, status, cost,
+                                                                n_samples, samples};
+  if (!b) return fail(plan->ctx, MRS_TG_ERR_NOMEM, "out of host memory");
   *bound_out = b;
   return MRS_TG_OK;
 }
@@ -929,9 +844,8 @@ int mrs_tg_bound_solve_launch_group(mrs_tg_bound_solve* const* bound, int32_t n_
     if (mrs_tg::quad_kernel_applies(plan->view, (long long)plan->view.n_paths * g.n, false)) {
       // the dispatch carries more paths than the rows kernel has wavefront slots for: four lanes per path, factors in LDS
       // (one factor store per batch of THIS group; grows when a larger group comes, never shrinks)
-      int rc = ensure_ws(plan, (size_t)g.n * mrs_tg::linear_workspace_doubles(plan->view));
-      if (rc != MRS_TG_OK) return rc;
-      HIP_TRY(ctx, mrs_tg::launch_solve_quad_group(plan->view, first->opt.derivative_to_optimize, g, plan->d_ws, ctx->stream));
+      HIP_TRY(ctx, plan->d_ws.ensure((size_t)g.n * mrs_tg::linear_workspace_doubles(plan->view), mrs_tg::StreamIdle{ctx->stream}));
+      HIP_TRY(ctx, mrs_tg::launch_solve_quad_group(plan->view, first->opt.derivative_to_optimize, g, plan->d_ws.get(), ctx->stream));
     } else {
       HIP_TRY(ctx, mrs_tg::launch_solve_rows_group(plan->view, first->opt.derivative_to_optimize, g, ctx->stream));
     }
@@ -1030,10 +944,9 @@ int mrs_tg_plan_solve_vjp(mrs_tg_plan* plan, int32_t d, const uint8_t* mask, con
   if (d < 0 || d > 4) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "derivative_to_optimize %d outside [0, 4]", d);
   HIP_TRY(ctx, use_device(ctx->device));
   const mrs_tg::BatchView& b = plan->view;
-  int rc = ensure_ws(plan, mrs_tg::vjp_workspace_doubles(b));
-  if (rc != MRS_TG_OK) return rc;
+  HIP_TRY(ctx, plan->d_ws.ensure(mrs_tg::vjp_workspace_doubles(b), mrs_tg::StreamIdle{ctx->stream}));
   ProfileScope ps(ctx, 3);
-  HIP_TRY(ctx, mrs_tg::launch_vjp(b, d, mask, vals, seg_times, coeffs, status, grad_coeffs, grad_cost, plan->d_ws, grad_vals,
+  HIP_TRY(ctx, mrs_tg::launch_vjp(b, d, mask, vals, seg_times, coeffs, status, grad_coeffs, grad_cost, plan->d_ws.get(), grad_vals,
                                   grad_times, ctx->stream));
   return MRS_TG_OK;
 }
@@ -1044,8 +957,8 @@ int mrs_tg_plan_careful_count(mrs_tg_plan* plan, int32_t* count_out) {
   *count_out = 0;
   HIP_TRY(ctx, use_device(ctx->device));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (!plan->nl.d_careful) return MRS_TG_OK;  // no outer loop has run on this plan
-  HIP_TRY(ctx, hipMemcpy(count_out, plan->nl.d_careful + 2, sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (!plan->nl.d_careful.get()) return MRS_TG_OK;  // no outer loop has run on this plan
+  HIP_TRY(ctx, hipMemcpy(count_out, plan->nl.d_careful.get() + 2, sizeof(int32_t), hipMemcpyDeviceToHost));
   return MRS_TG_OK;
 }
 
@@ -1333,10 +1246,7 @@ static int path_edit_ready(mrs_tg_plan* plan, long long upper_bound) {
   if (upper_bound > 2147483647ll)
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "the edited batch may have %lld vertices, which does not fit int32", upper_bound);
   HIP_TRY(ctx, use_device(ctx->device));
-  if (!plan->d_edit_ws) {
-    const size_t n = (size_t)plan->view.n_segments + (size_t)plan->view.n_paths;
-    HIP_TRY(ctx, mrs_tg::pool_alloc(&plan->d_edit_ws, sizeof(int32_t) * (n ? n : 1)));
-  }
+  HIP_TRY(ctx, plan->d_edit_ws.ensure((size_t)plan->view.n_segments + (size_t)plan->view.n_paths));
   return MRS_TG_OK;
 }
 
@@ -1355,8 +1265,8 @@ int mrs_tg_plan_preprocess_path(mrs_tg_plan* plan, const double* waypoints, cons
   const mrs_tg::pathq::ThinOptions o{min_waypoint_distance, straightener_enabled != 0, straightener_max_deviation,
                                      straightener_max_hdg_deviation};
   ProfileScope ps(ctx, 20);
-  HIP_TRY(ctx, mrs_tg::launch_preprocess_path(plan->view, waypoints, stop_at, o, plan->d_edit_ws, vertex_offsets_out, waypoints_out,
-                                              stop_at_out, source_out, ctx->stream));
+  HIP_TRY(ctx, mrs_tg::launch_preprocess_path(plan->view, waypoints, stop_at, o, plan->d_edit_ws.get(), vertex_offsets_out,
+                                              waypoints_out, stop_at_out, source_out, ctx->stream));
   return MRS_TG_OK;
 }
 
@@ -1372,7 +1282,7 @@ int mrs_tg_plan_insert_midpoints(mrs_tg_plan* plan, const double* waypoints, con
   if (const int rc = path_edit_ready(plan, 2ll * plan->view.n_segments + plan->view.n_paths); rc != MRS_TG_OK) return rc;
   ProfileScope ps(ctx, 21);
   HIP_TRY(ctx, mrs_tg::launch_insert_midpoints(plan->view, waypoints, stop_at, segment_max, max_deviation, first_segment != 0, active,
-                                               plan->d_edit_ws, vertex_offsets_out, waypoints_out, stop_at_out, source_out,
+                                               plan->d_edit_ws.get(), vertex_offsets_out, waypoints_out, stop_at_out, source_out,
                                                inserted_out, ctx->stream));
   return MRS_TG_OK;
 }
@@ -1400,8 +1310,8 @@ namespace mrs_tg {
 void* ctx_host_scratch(mrs_tg_ctx* ctx, size_t bytes) {
   if (!ctx) return nullptr;
   // (a quarter more: a later round's arrays are a little larger, its paths have more waypoints)
-  if (ctx->h_scratch.ensure(bytes, 4, ctx->stream) != hipSuccess) (void)hipGetLastError();
-  return ctx->h_scratch.ptr;
+  if (ctx->h_scratch.ensure(bytes, mrs_tg::PinnedAlloc::idle, bytes / 4) != hipSuccess) (void)hipGetLastError();
+  return ctx->h_scratch.get();
 }
 
 }  // namespace mrs_tg
@@ -1478,8 +1388,8 @@ int policy_round_device(mrs_tg_ctx* ctx, const PolicyRoundIn& in) {
   if (rc != MRS_TG_OK) return rc;
   const PolicyRoundArena R = policy_round_arena(L, A, nS, cap);
   // (half as much again: the next round's paths have more waypoints -- one allocation for a request's rounds)
-  HIP_TRY(ctx, ctx->d_arena.ensure(R.total_bytes, 2, s));
-  char* d = static_cast<char*>(ctx->d_arena.ptr);
+  HIP_TRY(ctx, ctx->d_arena.ensure(R.total_bytes, mrs_tg::StreamIdle{s}, R.total_bytes / 2));
+  char* d = ctx->d_arena.get();
   SyncOnExit sync_on_exit{s};
   // is the whole block memory the GPU addresses (hipHostMalloc: ctx_host_scratch)?  Then one copy kernel moves the inputs,
   // and the results are written into it directly
@@ -1561,9 +1471,9 @@ struct HostCall {
   mrs_tg::TransferArray arr[A_COUNT];
   mrs_tg::TransferLayout lay;
   bool zero_copy = false;
-  char* dbase() const { return static_cast<char*>(ctx->d_arena.ptr); }
-  char* staged(int id) const { return static_cast<char*>(ctx->h_arena.ptr) + lay.host_offset(arr[id]); }
-  char* span(size_t device_offset) const { return static_cast<char*>(ctx->h_arena.ptr) + (device_offset - lay.span_begin); }
+  char* dbase() const { return ctx->d_arena.get(); }
+  char* staged(int id) const { return ctx->h_arena.get() + lay.host_offset(arr[id]); }
+  char* span(size_t device_offset) const { return ctx->h_arena.get() + (device_offset - lay.span_begin); }
   // where the kernels find array `id`: the caller's own (pinned) memory under zero copy, its slot of the arena otherwise
   template <class T>
   T* dev(int id) const {
@@ -1573,8 +1483,8 @@ struct HostCall {
 
   // grow-only, exactly what the largest call so far needed
   int ensure_arenas() {
-    HIP_TRY(ctx, ctx->d_arena.ensure(lay.device_bytes, 0, s));
-    HIP_TRY(ctx, ctx->h_arena.ensure(lay.host_bytes, 0, s));
+    HIP_TRY(ctx, ctx->d_arena.ensure(lay.device_bytes, mrs_tg::StreamIdle{s}));
+    HIP_TRY(ctx, ctx->h_arena.ensure(lay.host_bytes));
     return MRS_TG_OK;
   }
 

@@ -487,65 +487,67 @@ hipError_t launch_dfo(NonlinearPlan& nl, const BatchView& b, const DfoParams& pr
   const size_t nS = (size_t)(b.n_segments > 0 ? b.n_segments : 1), P = (size_t)b.n_paths;
   const size_t NV = dfo_var_total(b.n_segments, b.n_paths);
   const bool with_free = prm.mode >= 3;
-  if (!nl.d_dfo_vec && (e = mrs_tg::pool_alloc(&nl.d_dfo_vec, sizeof(double) * 6 * NV)) != hipSuccess) return e;
-  if (!nl.d_dfo_f && (e = mrs_tg::pool_alloc(&nl.d_dfo_f, sizeof(double) * 3 * P)) != hipSuccess) return e;
-  if (!cost) cost = nl.d_dfo_f + 2 * P;  // J_d per evaluation needs a buffer even when the caller does not want it
-  if (!nl.d_dfo_state && (e = mrs_tg::pool_alloc(&nl.d_dfo_state, sizeof(int32_t) * kDfoInts * P)) != hipSuccess) return e;
-  if (!nl.d_dfo_deadline && (e = mrs_tg::pool_alloc(&nl.d_dfo_deadline, sizeof(long long))) != hipSuccess) return e;
+  if ((e = nl.d_dfo_vec.ensure(6 * NV)) != hipSuccess) return e;
+  if ((e = nl.d_dfo_f.ensure(3 * P)) != hipSuccess) return e;
+  if (!cost) cost = nl.d_dfo_f.get() + 2 * P;  // J_d per evaluation needs a buffer even when the caller does not want it
+  if ((e = nl.d_dfo_state.ensure(kDfoInts * P)) != hipSuccess) return e;
+  if ((e = nl.d_dfo_deadline.ensure(1)) != hipSuccess) return e;
   if (with_free) {
-    if (!nl.d_dfo_fidx && (e = mrs_tg::pool_alloc(&nl.d_dfo_fidx, sizeof(int32_t) * (nS + P) * kHalf)) != hipSuccess) return e;
-    if (!nl.d_dfo_segcost && (e = mrs_tg::pool_alloc(&nl.d_dfo_segcost, sizeof(double) * nS * kD)) != hipSuccess) return e;
-    if (!nl.d_dfo_seg_path) {
-      if ((e = mrs_tg::pool_alloc(&nl.d_dfo_seg_path, sizeof(int32_t) * nS)) != hipSuccess) return e;
-      MRS_TG_LAUNCH(dfo_segment_path_kernel, dim3(cdiv(b.n_paths, 64)), dim3(64), 0, stream, b, nl.d_dfo_seg_path);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+    if ((e = nl.d_dfo_fidx.ensure((nS + P) * kHalf)) != hipSuccess) return e;
+    if ((e = nl.d_dfo_segcost.ensure(nS * kD)) != hipSuccess) return e;
+    e = nl.d_dfo_seg_path.ensure_filled(nS, [&](int32_t* seg_path) {
+      MRS_TG_LAUNCH(dfo_segment_path_kernel, dim3(cdiv(b.n_paths, 64)), dim3(64), 0, stream, b, seg_path);
+      return hipGetLastError();
+    });
+    if (e != hipSuccess) return e;
   }
   const unsigned pblocks = cdiv(b.n_paths, 64), sblocks = cdiv(b.n_segments, 64);
   // modes 3 / 4 start from the linear solution at the given times (optimizeTimeAndFreeConstraints :436-438);
   // for every mode this solve also marks position-free vertices (status -2, which stays unless the caller has switched
   // the general solve on: then every linear solve of the search is followed by the 5 x 5-block solve of those paths)
   if (general && (e = nonlinear_prepare_general(nl, b, mask, seg_times, false, nullptr, stream)) != hipSuccess) return e;
-  const int32_t* general_flag = general ? nl.d_general + 4 : nullptr;
-  if ((e = launch_solve_linear(b, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws, coeffs, status,
-                               cost, nullptr, stream)) != hipSuccess)
+  const int32_t* general_flag = general ? nl.d_general.get() + 4 : nullptr;
+  if ((e = launch_solve_linear(b, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs,
+                               status, cost, nullptr, stream)) != hipSuccess)
     return e;
-  if (general && (e = launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws, coeffs, status, cost,
-                                           stream, general_flag, nullptr)) != hipSuccess)
+  if (general && (e = launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws.get(), coeffs,
+                                           status, cost, stream, general_flag, nullptr)) != hipSuccess)
     return e;
   MRS_TG_LAUNCH_EXT(dfo_init_kernel, dim3(pblocks), dim3(64), 0, stream, kt.start, nullptr, 0, b, prm, mask, limits, seg_times,
-                        coeffs, nl.d_dfo_vec, nl.d_dfo_f, nl.d_dfo_state, nl.d_dfo_fidx, nl.d_dfo_deadline);
+                    coeffs, nl.d_dfo_vec.get(), nl.d_dfo_f.get(), nl.d_dfo_state.get(), nl.d_dfo_fidx.get(),
+                    nl.d_dfo_deadline.get());
   if ((e = hipGetLastError()) != hipSuccess) return e;
   // NLopt's maxeval <= 0 means "no limit"; the host loop needs one
   const int rounds = prm.max_iterations > 0 ? prm.max_iterations : 1000;
   for (int r = 0; r < rounds; ++r) {
     if (with_free) {
       MRS_TG_LAUNCH(dfo_free_eval_kernel, dim3(sblocks, kD), dim3(64), 0, stream, b, prm.derivative, mask, vals,
-                         nl.d_dfo_fidx, nl.d_dfo_state, nl.d_dfo_vec, nl.d_dfo_seg_path, seg_times, coeffs,
-                         nl.d_dfo_segcost);
+                         nl.d_dfo_fidx.get(), nl.d_dfo_state.get(), nl.d_dfo_vec.get(), nl.d_dfo_seg_path.get(), seg_times, coeffs,
+                         nl.d_dfo_segcost.get());
       if ((e = hipGetLastError()) != hipSuccess) return e;
     } else if (r > 0) {  // round 0 evaluates the start point, solved above
-      if ((e = launch_solve_linear(b, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws, coeffs,
+      if ((e = launch_solve_linear(b, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs,
                                    nullptr, cost, nullptr, stream)) != hipSuccess)
         return e;
-      if (general && (e = launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws, coeffs, nullptr,
-                                               cost, stream, general_flag, nullptr)) != hipSuccess)
+      if (general && (e = launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws.get(), coeffs,
+                                               nullptr, cost, stream, general_flag, nullptr)) != hipSuccess)
         return e;
     }
     MRS_TG_LAUNCH(segment_maxima4_kernel, dim3(sblocks, 3), dim3(64), 0, stream, b.n_segments, coeffs, seg_times,
-                       nl.d_maxima);
+                       nl.d_maxima.get());
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    MRS_TG_LAUNCH(dfo_step_kernel, dim3(pblocks), dim3(64), 0, stream, b, prm, limits, cost, nl.d_dfo_segcost,
-                       nl.d_maxima, seg_times, nl.d_dfo_vec, nl.d_dfo_f, nl.d_dfo_state, nl.d_dfo_deadline);
+    MRS_TG_LAUNCH(dfo_step_kernel, dim3(pblocks), dim3(64), 0, stream, b, prm, limits, cost, nl.d_dfo_segcost.get(),
+                  nl.d_maxima.get(), seg_times, nl.d_dfo_vec.get(), nl.d_dfo_f.get(), nl.d_dfo_state.get(),
+                  nl.d_dfo_deadline.get());
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   // paths that stopped early were re-evaluated at their final point every round; paths that used the whole budget
   // hold the trajectory of their last trial: both are "the last evaluated point"
   if (with_free) {  // J_d of the last evaluated point for the caller
-    MRS_TG_LAUNCH(dfo_sum_cost_kernel, dim3(pblocks), dim3(64), 0, stream, b, nl.d_dfo_segcost, cost);
+    MRS_TG_LAUNCH(dfo_sum_cost_kernel, dim3(pblocks), dim3(64), 0, stream, b, nl.d_dfo_segcost.get(), cost);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  MRS_TG_LAUNCH_EXT(dfo_finalize_kernel, dim3(pblocks), dim3(64), 0, stream, nullptr, kt.stop, 0, b.n_paths, nl.d_dfo_state,
+  MRS_TG_LAUNCH_EXT(dfo_finalize_kernel, dim3(pblocks), dim3(64), 0, stream, nullptr, kt.stop, 0, b.n_paths, nl.d_dfo_state.get(),
                         status);
   return hipGetLastError();
 }

@@ -486,7 +486,7 @@ hipError_t sample_acc_table(double dt, int capacity, hipStream_t stream, const d
       return hipErrorOutOfMemory;
     }
     en.blk->device = dev;
-    if ((e = pool_alloc(&en.blk->d, sizeof(double) * (size_t)n)) != hipSuccess) {
+    if ((e = pool_alloc_bytes(reinterpret_cast<void**>(&en.blk->d), sizeof(double) * (size_t)n)) != hipSuccess) {
       delete en.blk;
       g_acc_cache.erase(it);
       return e;
@@ -574,18 +574,18 @@ hipError_t count_position_mismatches(const BatchView& b, const double* wp, const
   *count_out = 0;
   const int n_vertices = b.n_segments + b.n_paths;
   if (n_vertices == 0) return hipSuccess;
-  unsigned long long* d_count = nullptr;
-  hipError_t e = pool_alloc(&d_count, sizeof(unsigned long long));
+  DeviceBlock<unsigned long long> d_count;  // (leaves the scope behind the synchronise below)
+  hipError_t e = d_count.ensure(1);
   if (e != hipSuccess) return e;
   unsigned long long h = 0;
-  e = hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream);
+  e = hipMemsetAsync(d_count.get(), 0, sizeof(unsigned long long), stream);
   if (e == hipSuccess) {
-    MRS_TG_LAUNCH(position_mismatch_kernel, dim3(cdiv(n_vertices, 256)), dim3(256), 0, stream, n_vertices, wp, mask, vals, d_count);
+    MRS_TG_LAUNCH(position_mismatch_kernel, dim3(cdiv(n_vertices, 256)), dim3(256), 0, stream, n_vertices, wp, mask, vals,
+                  d_count.get());
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&h, d_count.get(), sizeof(h), hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  pool_free(d_count);
   *count_out = (long long)h;
   return e;
 }

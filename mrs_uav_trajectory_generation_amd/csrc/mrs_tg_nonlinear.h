@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "mrs_tg_launch.h"
+#include "mrs_tg_pool.h"
 
 namespace mrs_tg {
 
@@ -58,6 +59,7 @@ struct NonlinearBin {
   int min_S;      // smallest
 };
 
+// (its device blocks go back to the pool with the plan: mrs_tg_plan_destroy synchronises, then deletes)
 struct NonlinearPlan {
   std::vector<NonlinearBin> bins;
   std::vector<NonlinearBin> bins1;   // the one-lane-per-vector groups of a plan whose own choice is the dimension split (regroup_possible)
@@ -71,29 +73,27 @@ struct NonlinearPlan {
   // S + 4 lanes, for the shared half sweeps with free ends (optimize_lean_shared_ends_kernel); empty when a path is too long
   std::vector<NonlinearBin> ends_bins;
   int dim_split = 1;               // lanes per time vector in the outer loop: 1 (compact) or 4 (one per dimension)
-  double* d_ws = nullptr;          // factor store of the per-lane linear solve
-  size_t ws_doubles = 0;
-  int32_t* d_opt_status = nullptr; // stopping reason of the outer loop per path
-  double* d_maxima = nullptr;      // [n_segments][9] per-segment maxima
-  int32_t* d_queue = nullptr;      // the lean kernel's path queue (one counter)
-  double* d_sum_t0 = nullptr;      // [n_paths] sum of the times the outer loop started from (runaway test)
-  int32_t* d_fallback = nullptr;   // [n_paths] by position: 1 = the prefix / suffix kernel left the path to the sweeping kernel
-  int32_t* d_careful = nullptr;    // [0] count, [2] count of the last completed call, [4..] list of guarded paths
-  double* d_careful_ws = nullptr;  // factor store of optimize_careful_kernel's lanes
-  size_t careful_ws_doubles = 0;
+  DeviceBlock<double> d_ws;          // factor store of the per-lane linear solve
+  DeviceBlock<int32_t> d_opt_status; // stopping reason of the outer loop per path
+  DeviceBlock<double> d_maxima;      // [n_segments][9] per-segment maxima
+  DeviceBlock<int32_t> d_queue;      // the lean kernel's path queue (one counter)
+  DeviceBlock<double> d_sum_t0;      // [n_paths] sum of the times the outer loop started from (runaway test)
+  DeviceBlock<int32_t> d_fallback;   // [n_paths] by position: 1 = the prefix / suffix kernel left the path to the sweeping kernel
+  DeviceBlock<int32_t> d_careful;    // [0] count, [2] count of the last completed call, [4..] list of guarded paths
+  DeviceBlock<double> d_careful_ws;  // factor store of optimize_careful_kernel's lanes
   // paths with a position-free vertex (MRS_TG_FLAG_GENERAL_PATTERNS), allocated on first use
-  int32_t* d_general = nullptr;          // [0] count | [4 + p] flag by path | [4 + n_paths + k] list of positions
-  double* d_general_ws = nullptr;        // factor store of optimize_general_kernel's lanes
-  double* d_general_solve_ws = nullptr;  // factor store of solve_general_kernel (general_workspace_doubles)
-  double* d_general_t0 = nullptr;        // [n_segments] the times the call started from
+  DeviceBlock<int32_t> d_general;          // [0] count | [4 + p] flag by path | [4 + n_paths + k] list of positions
+  DeviceBlock<double> d_general_ws;        // factor store of optimize_general_kernel's lanes
+  DeviceBlock<double> d_general_solve_ws;  // factor store of solve_general_kernel (general_workspace_doubles)
+  DeviceBlock<double> d_general_t0;        // [n_segments] the times the call started from
   // gradient-free modes (0, 1, 3, 4), allocated on first use
-  double* d_dfo_vec = nullptr;       // x | x0 | best | h | lb | ub, each 21 n_segments + 20 n_paths doubles
-  double* d_dfo_f = nullptr;         // fbest | f_sweep | J_d scratch, 3 * n_paths doubles
-  int32_t* d_dfo_state = nullptr;    // phase, i, sg, neval, improved, ret, done, n_var per path
-  int32_t* d_dfo_fidx = nullptr;     // modes 3/4: free-constraint index of every (vertex, derivative), -1 if fixed
-  double* d_dfo_segcost = nullptr;   // modes 3/4: J_d share of every (segment, dimension)
-  int32_t* d_dfo_seg_path = nullptr; // modes 3/4: path of every segment
-  long long* d_dfo_deadline = nullptr; // wall-clock deadline of the running search (0 = none), written by its first kernel
+  DeviceBlock<double> d_dfo_vec;       // x | x0 | best | h | lb | ub, each 21 n_segments + 20 n_paths doubles
+  DeviceBlock<double> d_dfo_f;         // fbest | f_sweep | J_d scratch, 3 * n_paths doubles
+  DeviceBlock<int32_t> d_dfo_state;    // phase, i, sg, neval, improved, ret, done, n_var per path
+  DeviceBlock<int32_t> d_dfo_fidx;     // modes 3/4: free-constraint index of every (vertex, derivative), -1 if fixed
+  DeviceBlock<double> d_dfo_segcost;   // modes 3/4: J_d share of every (segment, dimension)
+  DeviceBlock<int32_t> d_dfo_seg_path; // modes 3/4: path of every segment
+  DeviceBlock<long long> d_dfo_deadline; // wall-clock deadline of the running search (0 = none), written by its first kernel
 };
 
 // shared by the launchers of mrs_tg_nonlinear.hip and mrs_tg_dfo.hip: the plan's lazily allocated buffers, and the flags / list
@@ -106,7 +106,6 @@ hipError_t nonlinear_prepare_general(NonlinearPlan& nl, const BatchView& b, cons
 bool careful_rerun_built();
 
 int nonlinear_plan_build(NonlinearPlan& nl, const std::vector<int32_t>& seg_offsets, const std::vector<int32_t>& order);
-void nonlinear_plan_free(NonlinearPlan& nl);
 
 // general: paths with a position-free vertex may occur (MRS_TG_FLAG_GENERAL_PATTERNS); they take the 5 x 5-block route
 // (optimize_general_kernel / solve_general_kernel) behind the fast kernels, the others are untouched by it.

@@ -2018,60 +2018,18 @@ int nonlinear_plan_build(NonlinearPlan& nl, const std::vector<int32_t>& so, cons
   return 0;
 }
 
-template <class T>
-static void release(T*& p) {
-  if (p) (void)mrs_tg::pool_free(p);
-  p = nullptr;
-}
-
-void nonlinear_plan_free(NonlinearPlan& nl) {
-  release(nl.d_ws);
-  release(nl.d_opt_status);
-  release(nl.d_maxima);
-  release(nl.d_sum_t0);
-  release(nl.d_queue);
-  release(nl.d_general);
-  release(nl.d_general_ws);
-  release(nl.d_general_solve_ws);
-  release(nl.d_general_t0);
-  release(nl.d_careful);
-  release(nl.d_fallback);
-  release(nl.d_careful_ws);
-  release(nl.d_dfo_vec);
-  release(nl.d_dfo_f);
-  release(nl.d_dfo_state);
-  release(nl.d_dfo_fidx);
-  release(nl.d_dfo_segcost);
-  release(nl.d_dfo_seg_path);
-  release(nl.d_dfo_deadline);
-  nl.ws_doubles = 0;
-  nl.careful_ws_doubles = 0;
-}
-
 constexpr int kCarefulCap = 1024;  // paths per call that can be re-run with primal costs; further ones keep the fast result
 
 bool careful_rerun_built() { return MRS_TG_WITH_CAREFUL != 0; }
 
 hipError_t nonlinear_ensure_buffers(NonlinearPlan& nl, const BatchView& b) {
   hipError_t e;
-  const size_t need = linear_workspace_doubles(b);
-  if (nl.ws_doubles < need) {
-    release(nl.d_ws);
-    nl.ws_doubles = 0;
-    if ((e = mrs_tg::pool_alloc(&nl.d_ws, need * sizeof(double))) != hipSuccess) return e;
-    nl.ws_doubles = need;
-  }
-  if (!nl.d_opt_status && (e = mrs_tg::pool_alloc(&nl.d_opt_status, sizeof(int32_t) * (size_t)(b.n_paths > 0 ? b.n_paths : 1))) != hipSuccess)
-    return e;
-  if (!nl.d_maxima && (e = mrs_tg::pool_alloc(&nl.d_maxima, sizeof(double) * 9 * (size_t)(b.n_segments > 0 ? b.n_segments : 1))) != hipSuccess)
-    return e;
-  if (!nl.d_sum_t0 && (e = mrs_tg::pool_alloc(&nl.d_sum_t0, sizeof(double) * (size_t)(b.n_paths > 0 ? b.n_paths : 1))) != hipSuccess)
-    return e;
-  if (!nl.d_careful) {
-    if ((e = mrs_tg::pool_alloc(&nl.d_careful, sizeof(int32_t) * (4 + kCarefulCap))) != hipSuccess) return e;
-    if ((e = hipMemset(nl.d_careful, 0, sizeof(int32_t) * 4)) != hipSuccess) return e;  // once per plan: every call leaves the counter at zero
-  }
-  return hipSuccess;
+  if ((e = nl.d_ws.ensure(linear_workspace_doubles(b))) != hipSuccess) return e;
+  if ((e = nl.d_opt_status.ensure((size_t)b.n_paths)) != hipSuccess) return e;
+  if ((e = nl.d_maxima.ensure(9 * (size_t)(b.n_segments > 0 ? b.n_segments : 1))) != hipSuccess) return e;
+  if ((e = nl.d_sum_t0.ensure((size_t)b.n_paths)) != hipSuccess) return e;
+  // once per plan: every call leaves the counter at zero
+  return nl.d_careful.ensure_filled(4 + kCarefulCap, [](int32_t* p) { return hipMemset(p, 0, sizeof(int32_t) * 4); });
 }
 
 // Lean sweeps for plain paths (optimize_lean_kernel): two wavefronts per SIMD where the general sweeping kernel has one.
@@ -2083,11 +2041,6 @@ static bool lean_applies(int dim_split) {
   return dim_split == 1;
 }
 
-static hipError_t ensure_fallback(NonlinearPlan& nl, const BatchView& b) {
-  if (nl.d_fallback) return hipSuccess;
-  return mrs_tg::pool_alloc(&nl.d_fallback, sizeof(int32_t) * (size_t)(b.n_paths > 0 ? b.n_paths : 1));
-}
-
 // Buffers of the pipelines' route for paths with a position-free vertex, and the list / flags of this call's batch
 // (general_list_kernel).  `outer_loop`: also the factor store of optimize_general_kernel's lanes and the copy of the start
 // times; returns the number of paths one launch of that kernel takes in *cap.
@@ -2095,26 +2048,21 @@ hipError_t nonlinear_prepare_general(NonlinearPlan& nl, const BatchView& b, cons
                                   bool outer_loop, int* cap, hipStream_t stream) {
   hipError_t e;
   const size_t P = (size_t)b.n_paths;
-  if (!nl.d_general && (e = mrs_tg::pool_alloc(&nl.d_general, sizeof(int32_t) * (4 + 2 * P))) != hipSuccess) return e;
-  if (!nl.d_general_solve_ws &&
-      (e = mrs_tg::pool_alloc(&nl.d_general_solve_ws, sizeof(double) * general_workspace_doubles(b))) != hipSuccess)
-    return e;
+  if ((e = nl.d_general.ensure(4 + 2 * P)) != hipSuccess) return e;
+  if ((e = nl.d_general_solve_ws.ensure(general_workspace_doubles(b))) != hipSuccess) return e;
   if (outer_loop) {
     // as many paths per launch as a 2 GB factor store holds (64 lanes x S vertices x kGenWs doubles each)
     const size_t per_path = (size_t)64 * (size_t)b.max_segments * kGenWs;
     const size_t n = std::min<size_t>(P, std::max<size_t>((size_t)16, ((size_t)1 << 28) / per_path));
-    if (!nl.d_general_ws && (e = mrs_tg::pool_alloc(&nl.d_general_ws, sizeof(double) * per_path * n)) != hipSuccess) return e;
-    if (!nl.d_general_t0 &&
-        (e = mrs_tg::pool_alloc(&nl.d_general_t0, sizeof(double) * (size_t)std::max(b.n_segments, 1))) != hipSuccess)
-      return e;
-    if (!dry_run() &&
-        (e = hipMemcpyAsync(nl.d_general_t0, seg_times, sizeof(double) * (size_t)b.n_segments, hipMemcpyDeviceToDevice, stream)) !=
-            hipSuccess)
+    if ((e = nl.d_general_ws.ensure(per_path * n)) != hipSuccess) return e;
+    if ((e = nl.d_general_t0.ensure((size_t)b.n_segments)) != hipSuccess) return e;
+    if (!dry_run() && (e = hipMemcpyAsync(nl.d_general_t0.get(), seg_times, sizeof(double) * (size_t)b.n_segments,
+                                          hipMemcpyDeviceToDevice, stream)) != hipSuccess)
       return e;
     if (cap) *cap = (int)n;
   }
-  if ((e = hipMemsetAsync(nl.d_general, 0, sizeof(int32_t) * 4, stream)) != hipSuccess) return e;
-  MRS_TG_LAUNCH(general_list_kernel, dim3(cdiv(b.n_paths, 256)), dim3(256), 0, stream, b, mask, nl.d_general);
+  if ((e = hipMemsetAsync(nl.d_general.get(), 0, sizeof(int32_t) * 4, stream)) != hipSuccess) return e;
+  MRS_TG_LAUNCH(general_list_kernel, dim3(cdiv(b.n_paths, 256)), dim3(256), 0, stream, b, mask, nl.d_general.get());
   return hipGetLastError();
 }
 
@@ -2327,19 +2275,19 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
   // paths with a position-free vertex (the caller says there may be some): flagged and listed, their start times kept aside
   int general_cap = 0;
   if (general && (e = nonlinear_prepare_general(nl, b, mask, seg_times, true, &general_cap, stream)) != hipSuccess) return e;
-  const int32_t* general_flag = general ? nl.d_general + 4 : nullptr;
+  const int32_t* general_flag = general ? nl.d_general.get() + 4 : nullptr;
   // 1. outer loop: every bin in one launch
   NonlinearParams prm = prm_in;
   prm.lean_shared = knob::lean_shared();
   prm.ends_min_segments = kEndsMinSegments;
   if (!route.estimate_in_kernel) prm.estimate_wp = prm.estimate_limits = nullptr;
-  prm.sum_t0 = nl.d_sum_t0;
+  prm.sum_t0 = nl.d_sum_t0.get();
   prm.deadline = nullptr;
   if (prm_in.time_budget_ticks > 0) {
-    if (!nl.d_dfo_deadline && (e = mrs_tg::pool_alloc(&nl.d_dfo_deadline, sizeof(long long))) != hipSuccess) return e;
-    MRS_TG_LAUNCH(set_deadline_kernel, dim3(1), dim3(1), 0, stream, nl.d_dfo_deadline, prm_in.time_budget_ticks);
+    if ((e = nl.d_dfo_deadline.ensure(1)) != hipSuccess) return e;
+    MRS_TG_LAUNCH(set_deadline_kernel, dim3(1), dim3(1), 0, stream, nl.d_dfo_deadline.get(), prm_in.time_budget_ticks);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    prm.deadline = nl.d_dfo_deadline;
+    prm.deadline = nl.d_dfo_deadline.get();
   }
   int careful_cap = 0;
   if (careful) {
@@ -2347,15 +2295,9 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
     const size_t per_path = (size_t)64 * (size_t)b.max_segments * ws_per_vertex<1>();
     careful_cap = (int)std::min<size_t>((size_t)kCarefulCap, std::max<size_t>((size_t)16, ((size_t)1 << 28) / per_path));
     careful_cap = std::min(careful_cap, b.n_paths);
-    const size_t need = per_path * (size_t)careful_cap;
-    if (nl.careful_ws_doubles < need) {
-      release(nl.d_careful_ws);
-      nl.careful_ws_doubles = 0;
-      if ((e = mrs_tg::pool_alloc(&nl.d_careful_ws, need * sizeof(double))) != hipSuccess) return e;
-      nl.careful_ws_doubles = need;
-    }
-    prm.careful_count = nl.d_careful;
-    prm.careful_list = nl.d_careful + 4;
+    if ((e = nl.d_careful_ws.ensure(per_path * (size_t)careful_cap)) != hipSuccess) return e;
+    prm.careful_count = nl.d_careful.get();
+    prm.careful_list = nl.d_careful.get() + 4;
     prm.careful_cap = careful_cap;
   } else {
     prm.careful_count = nullptr;
@@ -2369,42 +2311,43 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
   // 1a. the lean kernel
   if (route.lean) {
     const OuterLaunch& L = route.lean_launch;
-    if ((e = ensure_fallback(nl, b)) != hipSuccess) return e;
+    if ((e = nl.d_fallback.ensure((size_t)b.n_paths)) != hipSuccess) return e;
     prm.queue_next = nullptr;
     if (route.queued) {
-      if (!nl.d_queue && (e = mrs_tg::pool_alloc(&nl.d_queue, sizeof(int32_t) * 4)) != hipSuccess) return e;
-      MRS_TG_LAUNCH(set_queue_kernel, dim3(1), dim3(1), 0, stream, nl.d_queue, L.blocks * (64 / L.bins.group[0]));
+      if ((e = nl.d_queue.ensure(4)) != hipSuccess) return e;
+      MRS_TG_LAUNCH(set_queue_kernel, dim3(1), dim3(1), 0, stream, nl.d_queue.get(), L.blocks * (64 / L.bins.group[0]));
       if ((e = hipGetLastError()) != hipSuccess) return e;
-      prm.queue_next = nl.d_queue;
+      prm.queue_next = nl.d_queue.get();
     }
     if (L.lds_bytes > 64 * 1024 && (e = set_max_dynamic_lds(route.lean_kernel, L.lds_bytes)) != hipSuccess) return e;
     MRS_TG_LAUNCH_EXT(route.lean_kernel, dim3(L.blocks), dim3(64), L.lds_bytes, stream, kt.start, nullptr, 0, b, prm, L.bins, mask,
-                      vals, seg_times, nl.d_opt_status, nl.d_fallback);
+                      vals, seg_times, nl.d_opt_status.get(), nl.d_fallback.get());
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    prm.only_flagged = nl.d_fallback;
+    prm.only_flagged = nl.d_fallback.get();
     prm.queue_next = nullptr;
   }
   // 1b. the sweeping kernel
   {
     const hipEvent_t ev_start = route.lean ? nullptr : kt.start, ev_stop = (careful || general) ? nullptr : kt.stop;
     if (route.wave) {
-      if ((e = launch_optimize_wave(b, prm, mask, vals, seg_times, nl.d_opt_status, stream, ev_start, ev_stop)) != hipSuccess) return e;
+      e = launch_optimize_wave(b, prm, mask, vals, seg_times, nl.d_opt_status.get(), stream, ev_start, ev_stop);
+      if (e != hipSuccess) return e;
     } else {
       const OuterLaunch& L = route.sweep_launch;
       if (!route.sweep_fits) return hipErrorInvalidValue;
       if (L.lds_bytes > 64 * 1024 && (e = set_max_dynamic_lds(route.sweep_kernel, L.lds_bytes)) != hipSuccess) return e;
       MRS_TG_LAUNCH_EXT(route.sweep_kernel, dim3(L.blocks), dim3(L.threads), L.lds_bytes, stream, ev_start, ev_stop, 0, b, prm, L.bins,
-                        mask, vals, seg_times, nl.d_opt_status);
+                        mask, vals, seg_times, nl.d_opt_status.get());
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
 #if MRS_TG_WITH_CAREFUL
     if (careful) {
       const size_t clds = ((size_t)group_lds_doubles(b.max_segments, true) + kBlockConsts) * sizeof(double);
       if ((e = prepare_dynamic_lds(MRS_TG_KERNEL(optimize_careful_kernel), clds)) != hipSuccess) return e;
-      MRS_TG_LAUNCH_EXT(optimize_careful_kernel, dim3(careful_cap), dim3(64), clds, stream, nullptr,
-                            general ? nullptr : kt.stop, 0, b, prm, mask, vals, seg_times, nl.d_opt_status, nl.d_careful_ws);
+      MRS_TG_LAUNCH_EXT(optimize_careful_kernel, dim3(careful_cap), dim3(64), clds, stream, nullptr, general ? nullptr : kt.stop,
+                        0, b, prm, mask, vals, seg_times, nl.d_opt_status.get(), nl.d_careful_ws.get());
       if ((e = hipGetLastError()) != hipSuccess) return e;
-      MRS_TG_LAUNCH(careful_close_kernel, dim3(1), dim3(1), 0, stream, nl.d_careful);
+      MRS_TG_LAUNCH(careful_close_kernel, dim3(1), dim3(1), 0, stream, nl.d_careful.get());
       if ((e = hipGetLastError()) != hipSuccess) return e;
     }
 #else
@@ -2418,16 +2361,16 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
       NonlinearParams gp = prm;
       gp.only_flagged = nullptr;
       gp.queue_next = nullptr;
-      gp.careful_count = nl.d_general;
+      gp.careful_count = nl.d_general.get();
       gp.careful_cap = general_cap;
       for (int off = 0; off < b.n_paths; off += general_cap) {
         const bool last = off + general_cap >= b.n_paths;
-        gp.careful_list = nl.d_general + 4 + b.n_paths + off;
+        gp.careful_list = nl.d_general.get() + 4 + b.n_paths + off;
         MRS_TG_LAUNCH_EXT(optimize_general_kernel, dim3(general_cap), dim3(64), glds, stream, nullptr, last ? kt.stop : nullptr,
-                              0, b, gp, mask, vals, seg_times, nl.d_opt_status, nl.d_general_ws, nl.d_general_t0);
+                              0, b, gp, mask, vals, seg_times, nl.d_opt_status.get(), nl.d_general_ws.get(), nl.d_general_t0.get());
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if (!last) {
-          MRS_TG_LAUNCH(general_advance_kernel, dim3(1), dim3(1), 0, stream, nl.d_general, general_cap);
+          MRS_TG_LAUNCH(general_advance_kernel, dim3(1), dim3(1), 0, stream, nl.d_general.get(), general_cap);
           if ((e = hipGetLastError()) != hipSuccess) return e;
         }
       }
@@ -2437,8 +2380,8 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
   auto closing_tail = [&]() {
     RowsTail tail;
     tail.limits = limits;
-    tail.opt_status = nl.d_opt_status;
-    tail.sum_t0 = prm.reference_status ? nullptr : nl.d_sum_t0;  // (no runaway test: MRS_TG_FLAG_REFERENCE_STATUS)
+    tail.opt_status = nl.d_opt_status.get();
+    tail.sum_t0 = prm.reference_status ? nullptr : nl.d_sum_t0.get();  // (no runaway test: MRS_TG_FLAG_REFERENCE_STATUS)
     tail.seg_times_out = seg_times;
     if (route.tail_samples) {
       tail.sampling_dt = sampling_dt;
@@ -2452,49 +2395,51 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
   if (route.closing == Closing::kRowsPipeline) {
     RowsTail tail = closing_tail();
     tail.maxima_in_launch = true;
-    return launch_solve_rows(b, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status, stream, tail);
+    return launch_solve_rows(b, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status.get(), stream, tail);
   }
   // 2. trajectory of the last evaluated point (scaleSegmentTimesWithViolation works on poly_opt_'s state)
-  if ((e = launch_solve_linear(b, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws, coeffs, nullptr,
+  if ((e = launch_solve_linear(b, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs, nullptr,
                                nullptr, nullptr, stream, prm.pos_wp)) != hipSuccess)
     return e;
-  if (general && (e = launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws, coeffs, nullptr, nullptr,
-                                           stream, general_flag, nullptr)) != hipSuccess)
+  if (general && (e = launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws.get(), coeffs,
+                                           nullptr, nullptr, stream, general_flag, nullptr)) != hipSuccess)
     return e;
   // 3. per-segment maxima and time scaling
   if (route.certified_maxima)
     MRS_TG_LAUNCH(segment_maxima_scaling_kernel, dim3(cdiv(b.n_segments, kMsSegs)), dim3(kMsThreads), 0, stream, b, coeffs,
-                       seg_times, limits, nl.d_maxima);
+                       seg_times, limits, nl.d_maxima.get());
   else
     MRS_TG_LAUNCH(segment_maxima9_kernel, dim3(cdiv(b.n_segments, 64), 9), dim3(64), 0, stream, b.n_segments,
-                       coeffs, seg_times, nl.d_maxima);
+                       coeffs, seg_times, nl.d_maxima.get());
   if ((e = hipGetLastError()) != hipSuccess) return e;
   // 3b + 4 in one launch
   if (route.closing == Closing::kQuadTail) {
     RowsTail tail = closing_tail();
-    tail.maxima = nl.d_maxima;
+    tail.maxima = nl.d_maxima.get();
     tail.pos_wp = prm.pos_wp;
-    return launch_solve_quad(b, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status, nl.d_ws, stream, tail);
+    return launch_solve_quad(b, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status.get(),
+                             nl.d_ws.get(), stream, tail);
   }
   if (route.closing == Closing::kRowsTail) {
     RowsTail tail = closing_tail();
-    tail.maxima = nl.d_maxima;
-    return launch_solve_rows(b, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status, stream, tail);
+    tail.maxima = nl.d_maxima.get();
+    return launch_solve_rows(b, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status.get(), stream, tail);
   }
-  MRS_TG_LAUNCH(apply_scaling_kernel, dim3(cdiv(b.n_segments, 256)), dim3(256), 0, stream, b, nl.d_maxima, limits,
-                     nl.d_opt_status, seg_times);
+  MRS_TG_LAUNCH(apply_scaling_kernel, dim3(cdiv(b.n_segments, 256)), dim3(256), 0, stream, b, nl.d_maxima.get(), limits,
+                     nl.d_opt_status.get(), seg_times);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (!prm.reference_status) {
-    MRS_TG_LAUNCH(runaway_kernel, dim3(cdiv(b.n_paths, 256)), dim3(256), 0, stream, b, seg_times, nl.d_sum_t0, nl.d_opt_status);
+    MRS_TG_LAUNCH(runaway_kernel, dim3(cdiv(b.n_paths, 256)), dim3(256), 0, stream, b, seg_times, nl.d_sum_t0.get(),
+                  nl.d_opt_status.get());
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   // 4. updateSegmentTimes + solveLinear with the scaled times (nonlinear_impl.h:405-408), final status
-  if ((e = launch_solve_linear(b, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws, coeffs, status, cost,
-                               nl.d_opt_status, stream)) != hipSuccess)
+  if ((e = launch_solve_linear(b, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs, status, cost,
+                               nl.d_opt_status.get(), stream)) != hipSuccess)
     return e;
   if (general)
-    return launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws, coeffs, status, cost, stream,
-                                general_flag, nl.d_opt_status);
+    return launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws.get(), coeffs, status, cost, stream,
+                                general_flag, nl.d_opt_status.get());
   return hipSuccess;
 }
 
