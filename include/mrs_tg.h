@@ -133,6 +133,8 @@ enum {
                                          1.03 instead of 1.34 times its compulsory bytes.  Results are bit-identical.
                                          mrs_tg_plan_bind_solve CHECKS the statement once, on the arrays as they are at bind
                                          time, and refuses the bind with MRS_TG_ERR_INVALID_ARG if it does not hold;
+                                         mrs_tg_solve_batch, which holds the three arrays in host memory, checks it on every
+                                         call (O(V) on the host, before anything is uploaded or launched) and fails the same way;
                                          mrs_tg_plan_solve trusts it: the flag only changes launches that take the
                                          saturated-device kernel (>= 6144 paths per dispatch), so a statement that is false -- or
                                          has become false because the arrays of a bound solve were rewritten in place -- gives the
@@ -155,7 +157,12 @@ enum {
                                          feasibility scaling multiplied the total time by more than MRS_TG_RUNAWAY_TIME_FACTOR)
                                          is switched off.  For callers that apply the reference's own answer to a runaway, the
                                          length check against the Baca estimate (src/...cpp:1178-1199): mrs_tg_find_trajectory and
-                                         mrs_tg_optimize_paths set the flag themselves.  The rule measures against the Euclidean
+                                         mrs_tg_optimize_paths set the flag themselves, and ONLY where the upper side of that check
+                                         really runs -- the seam when it samples (sampling_dt > 0, samples_out given) and
+                                         max_trajectory_len_factor > 0, the policy when its max_trajectory_len_factor > 0.
+                                         Elsewhere (an mrs_tg_options opt{} has both factors 0) nothing of the reference would
+                                         answer a runaway, so the product's rule stays on and the path is rejected by its code,
+                                         -4.  The rule measures against the Euclidean
                                          estimate, which is 0.01-0.03 s for waypoints a few centimetres apart: such a path is
                                          stretched 25-fold by a perfectly healthy scaling, and the reference never checks a
                                          trajectory shorter than one second.  Coefficients, times and samples are the same bits
@@ -757,8 +764,11 @@ int mrs_tg_plan_estimate_times_baca_vjp(mrs_tg_plan* plan, const double* waypoin
  * (double)n_samples_dev[p] * sampling_dt (the raw count a solve leaves), REJECTED_TOO_LONG when len > max_factor * total,
  * REJECTED_TOO_SHORT when len < min_factor * total, else ACCEPTED.  A trajectory that is not longer than one second passes
  * (!(len > 1.0)); a factor <= 0 switches its side off.  No fused multiply-add: with the same seg_times the total and the
- * verdict are mrs_tg_find_trajectory's, bit for bit.  status_dev may be NULL; either output may be NULL, not both.  Device
- * pointers, asynchronous on the context's stream. */
+ * verdict are mrs_tg_find_trajectory's, bit for bit.  The step has no capacity argument: a count of sample_capacity + 1 (the
+ * sampler's overflow report, a LOWER bound of the real count) must not be handed to it as it is -- it can come back as
+ * REJECTED_TOO_SHORT; the caller refuses n_samples > sample_capacity itself, as mrs_tg_optimize_paths does, or switches the
+ * lower side off for such a path, as mrs_tg_find_trajectory does.  status_dev may be NULL; either output may be NULL, not
+ * both.  Device pointers, asynchronous on the context's stream. */
 int mrs_tg_plan_length_gate(mrs_tg_plan* plan, const double* seg_times_dev, const int32_t* n_samples_dev, double sampling_dt,
                             double max_factor, double min_factor, const int32_t* status_dev, double* total_out_dev,
                             int32_t* verdict_out_dev);
@@ -917,7 +927,13 @@ typedef struct mrs_tg_initial_state { /* the TrackerCommand fields read at src/.
  * *n_samples_out > 0 exactly where the reference returns the states; *n_samples_out = 0 where it returns {} (status_out,
  * seg_times_out and coeffs_out still hold what was computed; mrs_tg_last_error(ctx) has the reference's message and
  * mrs_tg_find_trajectory_info says which gate).  samples_out [sample_capacity][4]; a trajectory with more samples than that
- * which passes the gates is reported as sample_capacity + 1.  initial_state may be NULL. */
+ * which passes the gates is reported as sample_capacity + 1: that count is a lower bound of the real one, so the upper side of
+ * the sanity check still applies to it (already too long is too long) and the lower side does not (an overflow is never "too
+ * short").  A runaway of the feasibility scaling (MRS_TG_RUNAWAY_TIME_FACTOR) is answered as in the reference, by the upper
+ * side of the sanity check, where that side runs: sampling_dt > 0, samples_out given and max_trajectory_len_factor > 0 (the
+ * solve then runs under MRS_TG_FLAG_REFERENCE_STATUS).  Where it does not run -- no sampling, or the factor <= 0, a switch the
+ * reference does not have -- the product's own rule answers: status MRS_TG_STATUS_ROUNDOFF_LIMITED, MRS_TG_FIND_REJECTED_CODE,
+ * no samples.  initial_state may be NULL. */
 int mrs_tg_find_trajectory(mrs_tg_ctx* ctx, const mrs_tg_waypoint* waypoints, int32_t n_waypoints,
                            const mrs_tg_initial_state* initial_state, const double* limits9,
                            const mrs_tg_options* opt, int32_t relax_heading, double* seg_times_out,

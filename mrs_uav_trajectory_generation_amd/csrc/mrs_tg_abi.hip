@@ -1410,10 +1410,17 @@ int policy_round_device(mrs_tg_ctx* ctx, const PolicyRoundIn& in) {
   mrs_tg_options opt = in.opt;
   opt.estimate_times = 1;
   opt.sample_capacity = cap;
-  opt.flags |= MRS_TG_FLAG_REFERENCE_STATUS;  // the length check below is the reference's answer to a runaway (:1178-1199)
+  // the length check below is the reference's answer to a runaway (:1178-1199) where its upper side runs; with that side off
+  // the product's own runaway rule answers (MRS_TG_STATUS_ROUNDOFF_LIMITED: rejected by code), as on the host route
+  if (in.max_len_factor > 0) opt.flags |= MRS_TG_FLAG_REFERENCE_STATUS;
   int32_t* st_d = reinterpret_cast<int32_t*>(d + R.status);
   int32_t* ns_d = reinterpret_cast<int32_t*>(d + R.n_samples);
   double* smp_d = reinterpret_cast<double*>(d + R.samples);
+  // the moving-start hint, as mrs_tg_solve_batch sets it on the host route from the same condition (the launch shape of the
+  // outer loop depends on it: launch_nonlinear); the round's builder read it off the initial states
+  mrs_tg::HintScope moving_scope(mrs_tg::set_moving_starts_hint,
+                                 in.moving_starts != 0 &&
+                                     mrs_tg::wants_moving_starts(opt.time_alloc_method, A, plan->view.max_segments));
   rc = mrs_tg_plan_solve(plan, wp_d, mask_d, vals_d, reinterpret_cast<const double*>(d + L.lim), &opt, reinterpret_cast<double*>(d + R.times),
                          reinterpret_cast<double*>(d + R.coeffs), st_d, reinterpret_cast<double*>(d + R.cost), ns_d, smp_d);
   if (rc != MRS_TG_OK) return rc;
@@ -1553,6 +1560,16 @@ static int solve_batch_impl(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* so,
   // ---- plan
   mrs_tg_plan* plan = nullptr;
   if ((rc = cached_plan_for(ctx, n_paths, so, &plan)) != MRS_TG_OK) return rc;
+  // the caller's statement, checked on the host arrays (the offsets are valid behind the plan) before any array of the call
+  // is uploaded or any kernel launched; mrs_tg_plan_bind_solve checks it on the device.  The kernels read positions from
+  // either array, by the launch's size.  (Without the waypoints array the flag is refused by mrs_tg_plan_solve, as before.)
+  if ((opt->flags & MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS) && wp) {
+    const long long bad = mrs_tg::count_position_mismatches_host(n_paths, so, wp, mask, vals);
+    if (bad != 0)
+      return fail(ctx, MRS_TG_ERR_INVALID_ARG,
+                  "MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS: %lld vertices whose position constraint is absent or differs from their waypoint",
+                  bad);
+  }
   const size_t nS = (size_t)so[n_paths], nV = nS + (size_t)n_paths, P = (size_t)n_paths;
   const bool sampling = opt->sampling_dt > 0;
   if (sampling && !n_samples) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_samples_out is required when sampling");
@@ -1587,8 +1604,7 @@ static int solve_batch_impl(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* so,
   const mrs_tg::ConstraintScan scan = mrs_tg::scan_constraints(
       n_paths, so, mask, vals, local.derivative_to_optimize, !(local.flags & MRS_TG_FLAG_GENERAL_PATTERNS),
       !(local.flags & MRS_TG_FLAG_CONSTRAINED_SLOTS),
-      local.time_alloc_method == MRS_TG_TIME_ALLOC_MELLINGER && n_paths <= 1536 && plan->view.max_segments >= 13 &&
-          plan->view.max_segments <= 15);
+      mrs_tg::wants_moving_starts(local.time_alloc_method, (size_t)n_paths, plan->view.max_segments));
   if (scan.general_patterns) local.flags |= MRS_TG_FLAG_GENERAL_PATTERNS;
   if (scan.constrained_slots) local.flags |= MRS_TG_FLAG_CONSTRAINED_SLOTS;
   mrs_tg::HintScope moving_scope(mrs_tg::set_moving_starts_hint, scan.moving_starts);
@@ -1706,8 +1722,10 @@ int mrs_tg_find_trajectory(mrs_tg_ctx* ctx, const mrs_tg_waypoint* wps, int32_t 
     mrs_tg_options opt = *opt_in;
     opt.estimate_times = 1;
     // the reference's own status rule: a runaway of the feasibility scaling keeps the outer loop's code and is discarded by
-    // the length check below, as at :1178-1199 (a 5 cm path whose estimate is 0.025 s is no runaway: it is never checked)
-    opt.flags |= MRS_TG_FLAG_REFERENCE_STATUS;
+    // the length check below, as at :1178-1199 (a 5 cm path whose estimate is 0.025 s is no runaway: it is never checked) --
+    // where the upper side of that check really runs.  Without sampling, or with that side switched off (a factor <= 0: the
+    // reference has no such switch), the product's own runaway rule answers: MRS_TG_STATUS_ROUNDOFF_LIMITED, rejected by code
+    if (opt_in->sampling_dt > 0 && samples_out && opt_in->max_trajectory_len_factor > 0) opt.flags |= MRS_TG_FLAG_REFERENCE_STATUS;
     const int32_t so[2] = {0, S};
     double cost = 0.0;
     int rc = mrs_tg_solve_batch(ctx, 1, so, wp.data(), mask.data(), vals.data(), lim, &opt, seg_times_out, coeffs_out,
@@ -1725,10 +1743,13 @@ int mrs_tg_find_trajectory(mrs_tg_ctx* ctx, const mrs_tg_waypoint* wps, int32_t 
   }
   // "validate the temporal sampling of the trajectory" (:1178-1199): states.size() * sampling_dt against the Baca total.  A
   // trajectory with more samples than samples_out holds is reported as capacity + 1: the count the check sees is then a
-  // LOWER bound of the real one, enough to reject "too long" whenever capacity * dt exceeds the allowed length
+  // LOWER bound of the real one, enough to reject "too long" whenever capacity * dt exceeds the allowed length -- and no
+  // ground for "too short": the lower side is skipped for it
   if (opt_in->sampling_dt > 0 && samples_out) {
+    const bool overflowed = *n_samples_out > opt_in->sample_capacity;
     const int verdict = mrs_tg::baca::length_check(*n_samples_out, opt_in->sampling_dt, ctx->find_baca_total,
-                                                   opt_in->max_trajectory_len_factor, opt_in->min_trajectory_len_factor);
+                                                   opt_in->max_trajectory_len_factor,
+                                                   overflowed ? 0.0 : opt_in->min_trajectory_len_factor);
     if (verdict != 0) {
       char msg[256];
       std::snprintf(msg, sizeof(msg), "trajectory sampling failed: the final trajectory sampling is too %s = %.2f, initial 'baca' "

@@ -105,7 +105,16 @@ struct PolicyRoundIn {
   mrs_tg_options opt;
   double max_len_factor, min_len_factor, max_deviation;
   int32_t first_segment, check_enabled, last_round, sample_capacity;
+  // a request of the round starts from a moving state (a non-zero velocity / acceleration / jerk of its initial state): what
+  // scan_constraints reads off the expanded vertices on the host route.  Wanted, and therefore set, only for the shapes whose
+  // outer-loop launch depends on it (wants_moving_starts below)
+  int32_t moving_starts;
 };
+// the batches whose outer-loop launch shape depends on the moving-start hint (launch_nonlinear: small batches of 13-15 segments),
+// the same condition on both policy routes and in mrs_tg_solve_batch
+inline bool wants_moving_starts(int time_alloc_method, size_t n_paths, int max_segments) {
+  return time_alloc_method == MRS_TG_TIME_ALLOC_MELLINGER && n_paths <= 1536 && max_segments >= 13 && max_segments <= 15;
+}
 int policy_round_device(::mrs_tg_ctx* ctx, const PolicyRoundIn& in);  // (defined in mrs_tg_abi.hip: the GPU build only)
 
 namespace policy {
@@ -470,6 +479,19 @@ int optimize_paths(Host& host, int32_t n_paths, const int32_t* wp_offsets, const
         bool any_stop = false;
         for (size_t a = 0; a < A && !any_stop; ++a)
           for (int i = 1; i + 1 < st[active[a]].n_wp && !any_stop; ++i) any_stop = st[active[a]].stop[i] != 0;
+        // the moving-start hint of this round's solve: mrs_tg_solve_batch reads it off the vertices (scan_constraints), which
+        // exist on the device only here -- a first vertex constrains exactly the initial state's velocity, acceleration and jerk
+        int max_segments = 0;
+        for (size_t a = 0; a < A; ++a) max_segments = std::max(max_segments, (int)(so[a + 1] - so[a]));
+        bool moving_starts = false;
+        if (wants_moving_starts(o.solver.time_alloc_method, A, max_segments) && has_initial_state && initial_states)
+          for (size_t a = 0; a < A && !moving_starts; ++a) {
+            const int p = active[a];
+            if (!has_initial_state[p]) continue;
+            for (int k = 0; k < 4; ++k)
+              moving_starts = moving_starts || initial_states[p].velocity[k] != 0.0 || initial_states[p].acceleration[k] != 0.0 ||
+                              initial_states[p].jerk[k] != 0.0;
+          }
         parallel_ranges(A, 128, [&](size_t a0, size_t a1) {
           std::vector<double> tb;
           for (size_t a = a0; a < a1; ++a) {
@@ -512,6 +534,7 @@ int optimize_paths(Host& host, int32_t n_paths, const int32_t* wp_offsets, const
         in.check_enabled = o.check_deviation_enabled;
         in.last_round = round == o.max_deviation_iterations;
         in.sample_capacity = sample_capacity;
+        in.moving_starts = moving_starts;
         const double t1 = now();
         t_build += t1 - t0;
         const int rc = host.round(in);
@@ -614,7 +637,9 @@ int optimize_paths(Host& host, int32_t n_paths, const int32_t* wp_offsets, const
       mrs_tg_options so_opt = o.solver;
       so_opt.estimate_times = 1;
       so_opt.sample_capacity = sample_capacity;
-      so_opt.flags |= MRS_TG_FLAG_REFERENCE_STATUS;  // the length check below is the reference's answer to a runaway (:1178-1199)
+      // the length check below is the reference's answer to a runaway (:1178-1199) where its upper side runs; with that side
+      // off the product's own runaway rule answers (MRS_TG_STATUS_ROUNDOFF_LIMITED: rejected by code)
+      if (o.max_trajectory_len_factor > 0) so_opt.flags |= MRS_TG_FLAG_REFERENCE_STATUS;
       if (o.max_execution_time_s > 0) so_opt.max_time_s = 2.0 * 0.95 * budget_left;  // :899
       const double t1 = now();
       t_build += t1 - t0;

@@ -1,11 +1,13 @@
 // mrs_tg_transfer.hpp -- the transfer plan of the one-call host interface (mrs_tg_solve_batch / solve_batch_samples_only in
-// mrs_tg_abi.hip): which arrays a call has, how each one travels, where each one lies in the context's arenas, and what the
-// caller's masks say about the batch.  Plain C++17 arithmetic without a HIP type or call: mrs_tg_abi.hip enqueues what this
-// header decides, and tests/host/transfer_harness.cpp runs the same functions under g++ and the sanitizers.
+// mrs_tg_abi.hip): which arrays a call has, how each one travels, where each one lies in the context's arenas, what the
+// caller's masks say about the batch, and whether the caller's statement about its positions holds.  Plain C++17 arithmetic
+// without a HIP type or call: mrs_tg_abi.hip enqueues what this header decides, and tests/host/transfer_harness.cpp runs the
+// same functions under g++ and the sanitizers.
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 namespace mrs_tg {
 
@@ -152,6 +154,19 @@ inline ConstraintScan scan_constraints(int32_t n_paths, const int32_t* so, const
           for (int q = 0; q < 4; ++q) moving = moving || vals[(v * 5 + k) * 4 + q] != 0.0;
     }
   return ConstraintScan{general, slots, moving};
+}
+
+// MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS on host arrays: the number of vertices whose position is unconstrained or whose
+// constrained position differs from the waypoint -- position_mismatch_kernel's criterion (mrs_tg_kernels.hip), bit for bit
+// as there: a NaN equals the NaN of the same bits and nothing else, -0.0 differs from 0.0.  O(V), no early exit: the count is
+// what the caller is told.
+inline long long count_position_mismatches_host(int32_t n_paths, const int32_t* so, const double* wp, const uint8_t* mask,
+                                                const double* vals) {
+  const size_t nV = n_paths > 0 ? (size_t)so[n_paths] + (size_t)n_paths : 0;
+  long long bad = 0;
+  for (size_t v = 0; v < nV; ++v)
+    bad += mask[v * 5] == 0 || std::memcmp(wp + v * 4, vals + v * 20, 4 * sizeof(double)) != 0;
+  return bad;
 }
 
 }  // namespace mrs_tg

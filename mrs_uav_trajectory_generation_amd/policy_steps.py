@@ -97,7 +97,8 @@ def optimize_paths(ctx, paths, limits=None, stop_flags=None, relax_heading=None,
     opt = api.Options.from_buffer_copy(pol.solver)
     opt.estimate_times = 1
     opt.sample_capacity = cap
-    opt.flags |= api.FLAG_REFERENCE_STATUS               # the length gate is the reference's answer to a runaway (:1178-1199)
+    if pol.max_trajectory_len_factor > 0:                # the length gate is the reference's answer to a runaway (:1178-1199)
+        opt.flags |= api.FLAG_REFERENCE_STATUS           # where its upper side runs; else the product's own rule (-4) answers
     if any_stop and d == 4:
         opt.flags |= api.FLAG_CONSTRAINED_SLOTS
 

@@ -1,7 +1,8 @@
 // transfer_harness.cpp -- the transfer plan of the one-call host interface (csrc/mrs_tg_transfer.hpp: the array table,
-// classify, lay_out, every_array_pinned, scan_constraints, CopyList::add) and the device arena of a policy round
-// (csrc/mrs_tg_policy_host.hpp: policy_round_arena) compiled with plain g++ for the CPU.  "Pinned" is whatever the harness says
-// it is: classify takes the question as a callable.  tests/test_transfer_host.py drives it and restates what it prints.
+// classify, lay_out, every_array_pinned, scan_constraints, count_position_mismatches_host, CopyList::add) and the device arena
+// of a policy round (csrc/mrs_tg_policy_host.hpp: policy_round_arena) compiled with plain g++ for the CPU.  "Pinned" is whatever
+// the harness says it is: classify takes the question as a callable.  tests/test_transfer_host.py drives it and restates what
+// it prints.
 //
 //   g++ -std=c++17 -O2 -ffp-contract=off tests/host/transfer_harness.cpp -o transfer_harness && ./transfer_harness < in
 //
@@ -14,6 +15,9 @@
 //          device_bytes host_bytes every_array_pinned
 //   scan n_paths derivative want_general want_slots want_moving, seg_offsets [n_paths + 1], mask [nV][5], values [nV][5][4]
 //       -> general_patterns constrained_slots moving_starts
+//   mismatch n_paths (0 allowed), seg_offsets [n_paths + 1], waypoints [nV][4], mask [nV][5], values [nV][5][4]
+//       -> count_position_mismatches_host: vertices whose position bit is unset or whose constrained position is not, bit for
+//          bit, the waypoint ("nan" and "-nan" read as NaNs of either sign bit)
 //   arena n_paths n_segments capacity
 //       -> the fields of policy_round_arena in order, then in_bytes, samples and total_bytes of policy_round_layout
 //   copylist
@@ -163,6 +167,26 @@ int scan() {
   return 0;
 }
 
+int mismatch() {
+  int n_paths;
+  if (std::scanf("%d", &n_paths) != 1 || n_paths < 0) return 2;
+  std::vector<int32_t> so((size_t)n_paths + 1);
+  for (int32_t& x : so)
+    if (std::scanf("%d", &x) != 1) return 2;
+  const size_t nV = n_paths ? (size_t)so.back() + (size_t)n_paths : 0;
+  // (exactly sized: a read beyond a batch's last vertex is the sanitizer build's to find)
+  std::vector<double> wp(nV * 4), vals(nV * 20);
+  std::vector<uint8_t> mask(nV * 5);
+  for (double& w : wp)
+    if (std::scanf("%lf", &w) != 1) return 2;
+  for (uint8_t& m : mask)
+    if (std::scanf("%hhu", &m) != 1) return 2;
+  for (double& v : vals)
+    if (std::scanf("%lf", &v) != 1) return 2;
+  std::printf("%lld\n", count_position_mismatches_host(n_paths, so.data(), wp.data(), mask.data(), vals.data()));
+  return 0;
+}
+
 int arena() {
   size_t A, nS;
   int cap;
@@ -193,6 +217,7 @@ int main() {
     const int rc = !std::strcmp(cmd, "enumerate") ? enumerate()
                    : !std::strcmp(cmd, "layout")  ? layout()
                    : !std::strcmp(cmd, "scan")    ? scan()
+                   : !std::strcmp(cmd, "mismatch") ? mismatch()
                    : !std::strcmp(cmd, "arena")   ? arena()
                    : !std::strcmp(cmd, "copylist") ? copylist()
                                                    : 2;

@@ -1,7 +1,7 @@
 """The transfer plan of the one-call host interface on the CPU: csrc/mrs_tg_transfer.hpp (array table, classify, lay_out,
-every_array_pinned, scan_constraints, CopyList::add) and policy_round_arena of csrc/mrs_tg_policy_host.hpp, compiled by g++ into
+every_array_pinned, scan_constraints, count_position_mismatches_host, CopyList::add) and policy_round_arena of csrc/mrs_tg_policy_host.hpp, compiled by g++ into
 tests/host/transfer_harness.cpp.  The layout is checked exhaustively against its invariants inside the harness and, for named
-cases, against a restatement here; the scans against brute force in numpy.  No GPU."""
+cases, against a restatement here; the scans and the position check against brute force in numpy.  No GPU."""
 import numpy as np
 import pytest
 
@@ -215,6 +215,101 @@ def test_scan_constraints_against_brute_force(harness):
     assert got["three_paths_1_2_4/interior_slot"] == "0 1 0" and got["three_paths_1_2_4/interior_slot_not_min_snap"] == "0 0 0"
 
 
+# ---- count_position_mismatches_host: MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS checked on host arrays (mrs_tg_solve_batch) ----
+
+def _text(x):
+    """a double as text that reads back to the same bits, the sign bit of a NaN included (repr() drops it)"""
+    x = float(x)
+    if x != x:
+        return "-nan" if np.array(x).view(np.uint64) >> np.uint64(63) else "nan"
+    return repr(x)
+
+
+def _mismatch_problems():
+    """name -> (seg_offsets, waypoints, mask, values, the count the case is there for).  The criterion is
+    position_mismatch_kernel's: position bit unset, or the four doubles of the constrained position not the waypoint's BITS"""
+    problems = {}
+    for bname, S in (("one_path_one_segment", [1]), ("ragged_1_2_4", [1, 2, 4]), ("64_paths_of_10", [10] * 64)):
+        so, mask, vals = _plain_batch(S)
+        wp = vals[:, 0].copy()
+        nV = wp.shape[0]
+        mid, last = nV // 2, nV - 1
+
+        def variant(name, expected, edit=None):
+            w, m, v = wp.copy(), mask.copy(), vals.copy()
+            if edit:
+                edit(w, m, v)
+            problems["%s/%s" % (bname, name)] = (so, w, m, v, expected)
+
+        def one_value(w, m, v):
+            w[last, 3] = np.nextafter(w[last, 3], np.inf)       # one ulp, in the last double of the batch
+
+        def one_bit(w, m, v):
+            m[mid, 0] = 0
+
+        def both_at_one_vertex(w, m, v):                        # a vertex counts once
+            m[0, 0] = 0
+            w[0, 1] += 1.0
+
+        def other_slots_do_not_matter(w, m, v):                 # derivative slots and their values are not the statement's
+            m[:, 1:] = 1
+            v[:, 1:] = 7.0
+
+        def nan_of_the_same_bits(w, m, v):                      # the solve reads the same bits from either array: no mismatch
+            w[mid, 2] = v[mid, 0, 2] = np.nan
+
+        def nan_in_the_waypoint_only(w, m, v):
+            w[mid, 2] = np.nan
+
+        def nan_of_the_other_sign(w, m, v):
+            w[mid, 2], v[mid, 0, 2] = np.nan, -np.nan
+
+        def zero_of_the_other_sign(w, m, v):
+            w[0, 0], v[0, 0, 0] = 0.0, -0.0
+
+        def every_vertex(w, m, v):
+            m[:, 0] = 0
+
+        variant("true_statement", 0)
+        variant("one_value", 1, one_value)
+        variant("one_unset_bit", 1, one_bit)
+        variant("bit_and_value_at_one_vertex", 1, both_at_one_vertex)
+        variant("other_slots_do_not_matter", 0, other_slots_do_not_matter)
+        variant("nan_of_the_same_bits", 0, nan_of_the_same_bits)
+        variant("nan_in_the_waypoint_only", 1, nan_in_the_waypoint_only)
+        variant("nan_of_the_other_sign", 1, nan_of_the_other_sign)
+        variant("zero_of_the_other_sign", 1, zero_of_the_other_sign)
+        variant("every_vertex", nV, every_vertex)
+    problems["empty_batch"] = (np.zeros(1, dtype=int), np.zeros((0, 4)), np.zeros((0, 5), dtype=np.uint8), np.zeros((0, 5, 4)), 0)
+    return problems
+
+
+def _mismatch_brute_force(so, wp, mask, vals, _):
+    same_bits = np.ascontiguousarray(wp).view(np.uint64) == np.ascontiguousarray(vals[:, 0]).view(np.uint64)
+    return int(np.sum((mask[:, 0] == 0) | ~same_bits.all(axis=1)))
+
+
+def _mismatch_line(so, wp, mask, vals, _):
+    return "mismatch %d %s %s %s %s\n" % (len(so) - 1, " ".join(map(str, so)), " ".join(_text(x) for x in wp.reshape(-1)),
+                                          " ".join(map(str, mask.reshape(-1))), " ".join(_text(x) for x in vals.reshape(-1)))
+
+
+def _check_mismatches(exe, env=None):
+    problems = _mismatch_problems()
+    got = hh.run(exe, [_mismatch_line(*p) for p in problems.values()], len(problems), env=env)
+    for (name, p), line in zip(problems.items(), got):
+        assert int(line) == _mismatch_brute_force(*p) == p[4], (name, line)
+    return got
+
+
+def test_position_mismatch_count_against_brute_force(harness):
+    """zero mismatches, one value, one unset bit, NaNs (the kernel's answer: equal bits are equal), a ragged batch, an empty one"""
+    got = dict(zip(_mismatch_problems(), _check_mismatches(harness)))
+    assert got["empty_batch"] == "0" and got["ragged_1_2_4/true_statement"] == "0" and got["ragged_1_2_4/every_vertex"] == "10"
+    lines = {name: _mismatch_line(*p) for name, p in _mismatch_problems().items()}
+    assert len(set(lines.values())) == len(lines)   # no variant repeats another problem (the signs of NaN and zero reach the text)
+
+
 # ---- policy_round_arena, CopyList ----
 
 ARENA_SHAPES = [(1, 1, 0), (1, 1, 1), (3, 7, 16), (64, 640, 256)]
@@ -250,5 +345,6 @@ def test_harness_under_address_and_undefined_behaviour_sanitizers(tmp_path, harn
     env = dict(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     assert _check_named(san, env=env) == _check_named(harness)
     assert _check_scans(san, env=env) == _check_scans(harness)
+    assert _check_mismatches(san, env=env) == _check_mismatches(harness)
     assert _check_arena(san, env=env) == _check_arena(harness)
     assert hh.run(san, _enumerate_lines()[:2] + ["copylist\n"], 3, env=env) == hh.run(harness, _enumerate_lines()[:2] + ["copylist\n"], 3)
