@@ -210,9 +210,12 @@ enum {
   MRS_TG_CAP_FALLBACK_SAMPLE = 2048,  /* mrs_tg_plan_unwrap_headings, mrs_tg_plan_fallback_sample and
                                          mrs_tg_plan_fallback_sample_vjp are exported: the fallback sampler (findTrajectoryFallback)
                                          as a plan step, its backward pass, and the heading unwrap in front of its clock */
-  MRS_TG_CAP_PATH_EDIT = 4096         /* mrs_tg_plan_preprocess_path, mrs_tg_plan_insert_midpoints and mrs_tg_plan_path_edit_vjp
+  MRS_TG_CAP_PATH_EDIT = 4096,        /* mrs_tg_plan_preprocess_path, mrs_tg_plan_insert_midpoints and mrs_tg_plan_path_edit_vjp
                                          are exported: the two steps that change the number of waypoints of a path (preprocessPath's
                                          thinning, the mid-points of unsafe segments) and their one backward pass */
+  MRS_TG_CAP_TRAVEL_HEADING = 8192    /* mrs_tg_plan_travel_heading and mrs_tg_plan_travel_heading_vjp are exported: the heading
+                                         along the direction of travel (override_heading_atan2) as a plan step and its backward
+                                         pass */
 };
 
 /* mrs_tg_plan_estimate_times_vjp's term_out_dev: the term of the estimate a segment's time came from */
@@ -868,6 +871,43 @@ int mrs_tg_plan_insert_midpoints(mrs_tg_plan* plan, const double* waypoints_dev,
 int mrs_tg_plan_path_edit_vjp(mrs_tg_plan* plan, const int32_t* vertex_offsets_dev, const int32_t* source_dev,
                               const uint8_t* inserted_dev, const double* grad_waypoints_edited_dev, double* grad_waypoints_out_dev);
 
+/* The heading along the direction of travel as a plan step (MRS_TG_CAP_TRAVEL_HEADING; travel_heading_kernel, DESIGN.md section
+ * 11f): getTrajectoryReference with override_heading_atan2 (mrs_trajectory_generation.cpp:1578-1603) for every path of the plan,
+ * on samples where they are.  samples_dev [n_paths][sample_capacity][4] and n_samples_dev [n_paths] are what a solve, a sampler or
+ * the fallback sampler left; n = min(n_samples, sample_capacity) rows count (a count of sample_capacity + 1 is sample_capacity
+ * rows).  For the rows i = 0 .. n-2, with (dx, dy) = (x, y)_{i+1} - (x, y)_i and dist = sqrt(dx dx + dy dy) (written out, no
+ * hypot, no fused multiply-add: csrc/mrs_tg_heading.hpp),
+ *   heading_i = heading_{i-1}  if dist < min_step and i > 0,   else atan2(dy, dx)   (row i is then a SOURCE).
+ * Row 0 is always a source (a zero step gives 0); a distance that is not a number makes a source with a heading that is not a
+ * number, which the slow rows behind it carry.  Row n-1 keeps its heading; n <= 1 changes nothing; rows from n on are not
+ * written; with status_dev (may be NULL) a path with status <= 0 is not touched.  A carried row holds exactly the bits of its
+ * source's heading: a copy, not a second atan2.  atan2 is the device's: a source's heading is the host's up to its rounding.
+ * The reference decides on std::hypot; the written-out distance is within an ulp of it, so the decision can differ from
+ * mrs_tg_optimize_paths' host loop only for a step within an ulp of min_step.
+ * samples_out_dev may be samples_dev: then only the heading of the rows 0 .. n-2 is stored.  Otherwise the rows 0 .. n-1 are
+ * written whole, x, y, z (and the heading of row n-1) copied bit for bit, and the two arrays may not overlap.  source_out_dev
+ * [n_paths][sample_capacity] (may be NULL): the row whose step gave this row's heading, -1 for row n-1, not written from n on.
+ * One wavefront per path; no LDS, no atomics, no workspace; the plan contributes its path count and its context.
+ * MRS_TG_ERR_INVALID_ARG, before any launch: a negative sample_capacity, a missing mandatory pointer, a min_step that is not
+ * finite (0.05 is the reference's).  Device pointers (16-byte aligned), asynchronous on the context's stream. */
+int mrs_tg_plan_travel_heading(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev, int32_t sample_capacity,
+                               const int32_t* status_dev, double min_step, double* samples_out_dev, int32_t* source_out_dev);
+/* Backward pass of mrs_tg_plan_travel_heading (travel_heading_vjp_kernel): given grad_out_dev
+ * [n_paths][sample_capacity][4] = dL/d(output rows), writes dL/dsamples (grad_samples_out_dev [n_paths][sample_capacity][4]) of
+ * the INPUT rows samples_dev.  The sources are recomputed as the forward computes them and held fixed.  x, y, z of the upstream
+ * pass through; row n-1 passes its heading entry through; every other heading entry is 0 (the input headings of the rows
+ * 0 .. n-2 are not read by the forward).  A source s collects G_s, the sum of grad_out[i][3] over the rows i of its run -- from s
+ * up to but excluding the next source, at most row n-2 -- from 0.0 in increasing i; with r2 = dx dx + dy dy of its step it adds
+ *   (+dy / r2 * G_s, -dx / r2 * G_s) to x, y of row s   and   (-dy / r2 * G_s, +dx / r2 * G_s) to x, y of row s + 1,
+ * both exactly 0 when r2 == 0.  The terms of a row's x (and y) are added in this order: the upstream, the term of the row's own
+ * step, the term of the step of the row in front.  Rows from n on are zero; with status_dev, a path with status <= 0 gets zero
+ * rows.  Deterministic, no atomics, no workspace, the same bits on every call and for a path wherever it sits in a batch; every
+ * element that belongs to the plan is written exactly once.  grad_out_dev and grad_samples_out_dev may not overlap.  The
+ * argument checks are the forward's.  Device pointers, asynchronous on the context's stream. */
+int mrs_tg_plan_travel_heading_vjp(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev,
+                                   int32_t sample_capacity, const int32_t* status_dev, double min_step, const double* grad_out_dev,
+                                   double* grad_samples_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
@@ -882,7 +922,8 @@ int mrs_tg_plan_path_edit_vjp(mrs_tg_plan* plan, const int32_t* vertex_offsets_d
  * (mrs_tg_plan_unwrap_headings), 18 the fallback sampler (mrs_tg_plan_fallback_sample), 19 its backward pass
  * (mrs_tg_plan_fallback_sample_vjp), 20 path thinning (mrs_tg_plan_preprocess_path), 21 mid-point subdivision
  * (mrs_tg_plan_insert_midpoints; both timed from their first launch to their last), 22 their backward pass
- * (mrs_tg_plan_path_edit_vjp): twenty-three ids, 0 .. 22.
+ * (mrs_tg_plan_path_edit_vjp), 23 the heading along the direction of travel (mrs_tg_plan_travel_heading), 24 its backward pass
+ * (mrs_tg_plan_travel_heading_vjp): twenty-five ids, 0 .. 24.
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

@@ -51,6 +51,7 @@ KERNEL_PASSAGE, KERNEL_PASSAGE_VJP = 12, 13
 KERNEL_BACA, KERNEL_BACA_VJP, KERNEL_LENGTH_GATE = 14, 15, 16
 KERNEL_UNWRAP_HEADINGS, KERNEL_FALLBACK_SAMPLE, KERNEL_FALLBACK_SAMPLE_VJP = 17, 18, 19
 KERNEL_PREPROCESS_PATH, KERNEL_INSERT_MIDPOINTS, KERNEL_PATH_EDIT_VJP = 20, 21, 22
+KERNEL_TRAVEL_HEADING, KERNEL_TRAVEL_HEADING_VJP = 23, 24
 
 
 class MrsTgError(RuntimeError):
@@ -116,6 +117,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_plan_estimate_times_baca", "mrs_tg_plan_estimate_times_baca_vjp", "mrs_tg_plan_length_gate",
     "mrs_tg_plan_unwrap_headings", "mrs_tg_plan_fallback_sample", "mrs_tg_plan_fallback_sample_vjp",
     "mrs_tg_plan_preprocess_path", "mrs_tg_plan_insert_midpoints", "mrs_tg_plan_path_edit_vjp",
+    "mrs_tg_plan_travel_heading", "mrs_tg_plan_travel_heading_vjp",
 ]
 
 _lib = None
@@ -247,6 +249,10 @@ def load_library():
     L.mrs_tg_plan_insert_midpoints.argtypes = [vp, dp, vp, dp, C.c_double, C.c_int32, vp, ip, dp, vp, ip, vp]
     L.mrs_tg_plan_path_edit_vjp.restype = C.c_int
     L.mrs_tg_plan_path_edit_vjp.argtypes = [vp, ip, ip, vp, dp, dp]
+    L.mrs_tg_plan_travel_heading.restype = C.c_int
+    L.mrs_tg_plan_travel_heading.argtypes = [vp, dp, ip, C.c_int32, ip, C.c_double, dp, ip]
+    L.mrs_tg_plan_travel_heading_vjp.restype = C.c_int
+    L.mrs_tg_plan_travel_heading_vjp.argtypes = [vp, dp, ip, C.c_int32, ip, C.c_double, dp, dp]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -304,6 +310,7 @@ CAP_WAYPOINT_PASSAGE = 512    # MRS_TG_CAP_WAYPOINT_PASSAGE: Plan.waypoint_passa
 CAP_BACA = 1024               # MRS_TG_CAP_BACA: Plan.estimate_times_baca (the Baca estimate as a plan step), Plan.estimate_times_baca_vjp, Plan.length_gate
 CAP_PATH_EDIT = 4096          # MRS_TG_CAP_PATH_EDIT: Plan.preprocess_path (preprocessPath's thinning), Plan.insert_midpoints (the mid-points of unsafe segments), Plan.path_edit_vjp
 CAP_FALLBACK_SAMPLE = 2048    # MRS_TG_CAP_FALLBACK_SAMPLE: Plan.unwrap_headings, Plan.fallback_sample (findTrajectoryFallback's rows as a plan step), Plan.fallback_sample_vjp
+CAP_TRAVEL_HEADING = 8192     # MRS_TG_CAP_TRAVEL_HEADING: Plan.travel_heading (the heading along the direction of travel, override_heading_atan2), Plan.travel_heading_vjp
 # Plan.estimate_times_baca_vjp's flags: the branches of the Baca estimate a segment's time took, as bits (MRS_TG_BACA_*)
 BACA_V_VERTICAL, BACA_A_VERTICAL, BACA_J_VERTICAL, BACA_T1_CAPPED, BACA_T2_CAPPED = 1, 2, 4, 8, 16
 BACA_DOT1_CLAMPED, BACA_DOT2_CLAMPED, BACA_FLOOR, BACA_HEADING, BACA_HEADING_CRUISE, BACA_HEADING_ACC = 32, 64, 128, 256, 512, 1024
@@ -1074,6 +1081,27 @@ class Plan:
         self.ctx._check(self._L.mrs_tg_plan_path_edit_vjp(self._h, _t_ptr(vertex_offsets), _t_ptr(source), _t_ptr(inserted),
                                                           _t_ptr(grad_waypoints_edited), _t_ptr(grad_waypoints)),
                         "mrs_tg_plan_path_edit_vjp")
+
+    def travel_heading(self, samples, n_samples, samples_out=None, status=None, min_step=0.05, source=None):
+        """mrs_tg_plan_travel_heading: getTrajectoryReference's override_heading_atan2 on samples [n_paths][capacity][4]
+        (n_samples [n_paths] int32): the heading of the rows 0 .. n-2 becomes atan2 of the step to the next row, a row that moves
+        less than min_step keeping the heading of the row in front; row n-1 keeps its own.  samples_out None = in place (only
+        those headings are stored), else rows 0 .. n-1 are written whole; source [n_paths][capacity] int32 (optional) gets the
+        row whose step gave a row's heading, -1 for row n-1.  A path with status [n_paths] <= 0 (optional) is not touched.
+        Device tensors; asynchronous on the context's stream."""
+        out = samples if samples_out is None else samples_out
+        self.ctx._check(self._L.mrs_tg_plan_travel_heading(self._h, _t_ptr(samples), _t_ptr(n_samples), int(samples.shape[1]),
+                                                           _t_ptr(status), float(min_step), _t_ptr(out), _t_ptr(source)),
+                        "mrs_tg_plan_travel_heading")
+
+    def travel_heading_vjp(self, samples, n_samples, grad_out, grad_samples, status=None, min_step=0.05):
+        """mrs_tg_plan_travel_heading_vjp: dL/dsamples [n_paths][capacity][4] of the INPUT rows (written, zeros included) from
+        dL/d(output rows) (grad_out [n_paths][capacity][4]), the sources recomputed from samples and held fixed, every sum in a
+        stated order; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_travel_heading_vjp(self._h, _t_ptr(samples), _t_ptr(n_samples),
+                                                               int(samples.shape[1]), _t_ptr(status), float(min_step),
+                                                               _t_ptr(grad_out), _t_ptr(grad_samples)),
+                        "mrs_tg_plan_travel_heading_vjp")
 
 
 class RoundRobin:

@@ -86,6 +86,17 @@ the requested waypoints -- a copy passes its row on, a mid-point gives half of i
     >>> ...                                                       # estimate, solve, sample on plan1 / wp1
     >>> plan1.path_deviation(samples.detach(), n, wp1.detach(), segment_max=segment_max)   # [sum S] of plan1, preallocated
     >>> plan2, wp2, stop2, source, inserted = insert_midpoints(plan1, wp1, segment_max, 0.05)
+
+travel_heading (Plan.travel_heading forward, Plan.travel_heading_vjp backward: mrs_tg_plan_travel_heading /
+mrs_tg_plan_travel_heading_vjp) is the last stage before the answer leaves: with override_heading_atan2
+the tracker receives the direction of travel as the heading, a row that barely moves keeping the heading of the row in front.
+A loss on the heading the tracker actually gets -- here: look where a point of interest is -- reaches the waypoints through it:
+
+    >>> samples, n = sample(plan, coeffs, times, 0.2, 512, status)
+    >>> rows, source = travel_heading(plan, samples, n, status=status)        # a fresh tensor; source: the row whose step it was
+    >>> valid = torch.arange(512, device=n.device)[None, :] < n[:, None] - 1  # the last row keeps its sampled yaw
+    >>> bearing = torch.atan2(poi[1] - rows[..., 1], poi[0] - rows[..., 0])
+    >>> ((1.0 - torch.cos(rows[..., 3] - bearing)) * valid).sum().backward()  # fv.grad, times.grad
 """
 import numpy as np
 import torch
@@ -568,6 +579,51 @@ def fallback_trajectory(plan, waypoints, limits, sampling_dt, sample_capacity, s
     plan.unwrap_headings(w, unwrapped)
     plan.estimate_times_baca(unwrapped, lim.contiguous(), times)
     return fallback_sample(plan, waypoints, times, sampling_dt, sample_capacity, stop_at=stop_at, stopping_time=stopping_time)
+
+
+class _TravelHeading(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, samples, n_samples, status, min_step):
+        s = samples.detach().to(torch.float64).contiguous()
+        n = n_samples.detach().to(torch.int32).contiguous()
+        if s.dim() != 3 or s.shape[0] != plan.n_paths or s.shape[2] != api.N_DIM:
+            raise ValueError("samples must be [n_paths][capacity][4]")
+        if n.dim() != 1 or n.shape[0] != plan.n_paths:
+            raise ValueError("n_samples must be [n_paths]")
+        st = None if status is None else status.detach().to(torch.int32).contiguous()
+        # (the kernel writes the rows a live path has; the rows behind them and the rows of a path with status <= 0 stay zero)
+        out = torch.zeros_like(s)
+        source = torch.full(s.shape[:2], -1, dtype=torch.int32, device=s.device)
+        plan.ctx.use_torch_stream()
+        plan.travel_heading(s, n, samples_out=out, status=st, min_step=float(min_step), source=source)
+        ctx.plan, ctx.status, ctx.min_step = plan, st, float(min_step)
+        ctx.save_for_backward(s, n)
+        ctx.mark_non_differentiable(source)
+        ctx.set_materialize_grads(False)
+        return out, source
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, _grad_source):
+        s, n = ctx.saved_tensors
+        if grad_out is None or not ctx.needs_input_grad[1]:
+            return None, None, None, None, None
+        gs = torch.empty_like(s)
+        plan = ctx.plan
+        plan.ctx.use_torch_stream()   # (the autograd engine runs this on its own thread, on the forward's stream)
+        plan.travel_heading_vjp(s, n, grad_out.to(torch.float64).contiguous(), gs, status=ctx.status, min_step=ctx.min_step)
+        return None, gs, None, None, None
+
+
+def travel_heading(plan, samples, n_samples, status=None, min_step=0.05):
+    """(reference [n_paths][capacity][4], source [n_paths][capacity] int32) of Plan.travel_heading: the rows the tracker receives
+    under override_heading_atan2 -- x, y, z of samples [n_paths][capacity][4], the heading of the rows 0 .. n-2 replaced by the
+    direction of the step to the next row, a row that moves less than min_step keeping the heading of the row in front; row n-1
+    keeps its own.  A fresh tensor, differentiable in samples (float64 device tensor; n_samples [n_paths] int32 as the sampler
+    returned it); rows from n on and the rows of a path with status <= 0 (status [n_paths], optional) are zero and give zero.
+    source is the row whose step gave a row's heading (-1 for row n-1 and behind).  The gradient holds the sources fixed: the
+    heading of a run of slow rows flows into the two rows of its source's step, nothing into the headings the step replaces."""
+    return _TravelHeading.apply(plan, samples, n_samples, status, min_step)
 
 
 class _PathEdit(torch.autograd.Function):

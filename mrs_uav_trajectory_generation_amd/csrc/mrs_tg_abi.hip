@@ -53,7 +53,7 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 23;  // kernel_id 0 .. 22 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 25;  // kernel_id 0 .. 24 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
   long long ev_count[kTimedKernels] = {};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
@@ -196,7 +196,7 @@ int mrs_tg_capabilities(void) {
   return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE |
          MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE | MRS_TG_CAP_DEVIATION |
          MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE | MRS_TG_CAP_BACA | MRS_TG_CAP_FALLBACK_SAMPLE |
-         MRS_TG_CAP_PATH_EDIT;
+         MRS_TG_CAP_PATH_EDIT | MRS_TG_CAP_TRAVEL_HEADING;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1298,6 +1298,43 @@ int mrs_tg_plan_path_edit_vjp(mrs_tg_plan* plan, const int32_t* vertex_offsets, 
   ProfileScope ps(ctx, 22);
   HIP_TRY(ctx, mrs_tg::launch_path_edit_vjp(plan->view, vertex_offsets, source, inserted, grad_waypoints_edited, grad_waypoints_out,
                                             ctx->stream));
+  return MRS_TG_OK;
+}
+
+// what the two heading calls check before any launch
+static int travel_heading_arguments(mrs_tg_ctx* ctx, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                    double min_step) {
+  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
+  if (!n_samples || (sample_capacity > 0 && !samples))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev and n_samples_dev are required");
+  if (!std::isfinite(min_step)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "min_step must be finite");
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_travel_heading(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                               const int32_t* status, double min_step, double* samples_out, int32_t* source_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (const int rc = travel_heading_arguments(ctx, samples, n_samples, sample_capacity, min_step); rc != MRS_TG_OK) return rc;
+  if (sample_capacity > 0 && !samples_out) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_out_dev is required");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 23);
+  HIP_TRY(ctx, mrs_tg::launch_travel_heading(plan->view.n_paths, samples, n_samples, sample_capacity, status, min_step, samples_out,
+                                             source_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_travel_heading_vjp(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                   const int32_t* status, double min_step, const double* grad_out, double* grad_samples) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (const int rc = travel_heading_arguments(ctx, samples, n_samples, sample_capacity, min_step); rc != MRS_TG_OK) return rc;
+  if (sample_capacity > 0 && (!grad_out || !grad_samples))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_out_dev and grad_samples_out_dev are required");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 24);
+  HIP_TRY(ctx, mrs_tg::launch_travel_heading_vjp(plan->view.n_paths, samples, n_samples, sample_capacity, status, min_step, grad_out,
+                                                 grad_samples, ctx->stream));
   return MRS_TG_OK;
 }
 

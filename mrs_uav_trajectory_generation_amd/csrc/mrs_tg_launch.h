@@ -299,6 +299,16 @@ hipError_t launch_insert_midpoints(const BatchView& b, const double* waypoints, 
                                    hipStream_t stream);
 hipError_t launch_path_edit_vjp(const BatchView& b, const int32_t* offsets, const int32_t* source, const uint8_t* inserted,
                                 const double* grad_edited, double* grad_waypoints, hipStream_t stream);
+// mrs_tg_plan_travel_heading / mrs_tg_plan_travel_heading_vjp (mrs_tg_heading.hip): the heading of the rows 0 .. n-2 of samples
+// [n_paths][capacity][4] set to the direction of the step to the next row, a row that moves less than min_step keeping the
+// heading in front of it (samples_out may be samples; source_out [n_paths][capacity] may be NULL); and its backward pass,
+// dL/dsamples from the upstream on the output rows, the sources held fixed.  One wavefront per path; reads only, no LDS, no
+// workspace; each timed as the kernel family of the pending ProfileScope
+hipError_t launch_travel_heading(int n_paths, const double* samples, const int32_t* n_samples, int capacity, const int32_t* status,
+                                 double min_step, double* samples_out, int32_t* source_out, hipStream_t stream);
+hipError_t launch_travel_heading_vjp(int n_paths, const double* samples, const int32_t* n_samples, int capacity,
+                                     const int32_t* status, double min_step, const double* grad_out, double* grad_samples,
+                                     hipStream_t stream);
 // phase-split tile kernel (mrs_tg_tile.hip): small and medium batches whose per-path state fits in LDS
 bool tile_kernel_applies(const BatchView& b, bool fused);
 hipError_t launch_solve_tile(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,

@@ -1,5 +1,5 @@
 // mrs_tg_pathwave.hpp -- what the kernels that give ONE WAVEFRONT ONE PATH share around their own loops (mrs_tg_sample_vjp.hip,
-// mrs_tg_evaluate.hip, mrs_tg_deviation.hip, mrs_tg_passage.hip).  Device only; only what they spell the same way AND compile
+// mrs_tg_evaluate.hip, mrs_tg_deviation.hip, mrs_tg_passage.hip, mrs_tg_heading.hip).  Device only; only what they spell the same way AND compile
 // to the same code through a function: the chunk loops and the loops that stage a path into LDS stay written out.
 #pragma once
 #include "mrs_tg_device.hpp"

@@ -6,10 +6,17 @@ from the request to the answer:
     with its samples (Plan.solve), both gates (Plan.length_gate on the solve's status), the deviation scan (Plan.path_deviation),
     the mid-points of the unsafe segments (Plan.insert_midpoints), the plan of the next round.
 
+With policy.fallback_sampling a round's solve and both gates give way to the reference's findTrajectoryFallback (:1215-1395),
+from the steps that exist: the heading unwrap, the limits scaled by fallback_speed_factor and fallback_accel_factor, the Baca
+estimate of that, and Plan.fallback_sample on the RAW waypoints with stop_at and fallback_stopping_time; a path is ok when its
+rows fit the capacity; the deviation scan and the mid-points go on as before.  With policy.override_heading_atan2 the finished
+samples get getTrajectoryReference's heading along the direction of travel (:1578-1603) where they are: ONE Plan.travel_heading
+over samples_out in place, behind the rounds, on the device's success and n_samples.
+
 Per round ONE readback: the offsets of the subdivided batch with the verdicts (a few words per path).  The rounds end as :729
 does: round max_deviation_iterations is solved and not validated again.  mrs_tg_optimize_paths does not run through this module;
 it is the same loop with the two edit stages on the host, and tests/test_gpu_pathedit_loop.py holds the two to the same answers.
-Not here: initial states, override_heading_atan2, the fallback sampler and a time budget."""
+Not here: initial states and a time budget (max_execution_time_s > 0 is refused)."""
 import ctypes as C
 
 import numpy as np
@@ -48,8 +55,8 @@ def optimize_paths(ctx, paths, limits=None, stop_flags=None, relax_heading=None,
     pol = policy or api.default_policy_options()
     P, cap = len(paths), int(sample_capacity)
     d, dt = int(pol.solver.derivative_to_optimize), float(pol.solver.sampling_dt)
-    if pol.fallback_sampling or pol.override_heading_atan2 or pol.max_execution_time_s > 0:
-        raise ValueError("policy_steps composes the optimiser's rounds only: no fallback sampler, heading override or time budget")
+    if pol.max_execution_time_s > 0:
+        raise ValueError("policy_steps has no clock: a time budget (max_execution_time_s > 0) is not served")
     if not dt > 0 or not 2 <= d <= 4 or cap <= 0:
         raise ValueError("sampling_dt > 0, derivative_to_optimize in 2 .. 4 and sample_capacity > 0 are required")
     arrs = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 4) for p in paths]
@@ -121,21 +128,30 @@ def optimize_paths(ctx, paths, limits=None, stop_flags=None, relax_heading=None,
         try:
             unwrapped = torch.empty_like(wp)
             plan.unwrap_headings(wp.contiguous(), unwrapped)                                 # :925-936
-            mask, vals = _vertices(so.astype(np.int64), unwrapped, stop, d)                  # :923-977
             baca = torch.empty(n_s, dtype=torch.float64, device=dev)
-            plan.estimate_times_baca(unwrapped, lim_d, baca)                                 # initial_total_time_baca, :1048-1056
-            times = torch.zeros(n_s, dtype=torch.float64, device=dev)
-            coeffs = torch.empty((n_s, api.N_DIM, api.N_COEFF), dtype=torch.float64, device=dev)
-            status = torch.zeros(A, dtype=torch.int32, device=dev)
-            cost = torch.zeros(A, dtype=torch.float64, device=dev)
             ns = torch.zeros(A, dtype=torch.int32, device=dev)
             samples = torch.zeros((A, cap, api.N_DIM), dtype=torch.float64, device=dev)
-            plan.solve(opt, mask, vals, times, coeffs, status, cost=cost, waypoints=unwrapped, limits=lim_d, n_samples=ns,
-                       samples=samples)
-            verdict = torch.empty(A, dtype=torch.int32, device=dev)
-            plan.length_gate(baca, ns, dt, max_factor=pol.max_trajectory_len_factor, min_factor=pol.min_trajectory_len_factor,
-                             status=status, verdict=verdict)                                 # :1138-1149, :1178-1199
-            ok = (verdict == api.FIND_ACCEPTED) & (ns <= cap)
+            if pol.fallback_sampling:                                                        # findTrajectoryFallback, :1215-1395
+                lim_fb = lim_d.clone()
+                lim_fb[:, 0:2] *= float(pol.fallback_speed_factor)
+                lim_fb[:, 3:5] *= float(pol.fallback_accel_factor)
+                plan.estimate_times_baca(unwrapped, lim_fb, baca)
+                plan.fallback_sample(wp.contiguous(), baca, dt, cap, ns, samples, stop_at=stop.contiguous(),
+                                     stopping_time=pol.fallback_stopping_time)
+                ok = ns <= cap
+            else:
+                mask, vals = _vertices(so.astype(np.int64), unwrapped, stop, d)              # :923-977
+                plan.estimate_times_baca(unwrapped, lim_d, baca)                             # initial_total_time_baca, :1048-1056
+                times = torch.zeros(n_s, dtype=torch.float64, device=dev)
+                coeffs = torch.empty((n_s, api.N_DIM, api.N_COEFF), dtype=torch.float64, device=dev)
+                status = torch.zeros(A, dtype=torch.int32, device=dev)
+                cost = torch.zeros(A, dtype=torch.float64, device=dev)
+                plan.solve(opt, mask, vals, times, coeffs, status, cost=cost, waypoints=unwrapped, limits=lim_d, n_samples=ns,
+                           samples=samples)
+                verdict = torch.empty(A, dtype=torch.int32, device=dev)
+                plan.length_gate(baca, ns, dt, max_factor=pol.max_trajectory_len_factor,
+                                 min_factor=pol.min_trajectory_len_factor, status=status, verdict=verdict)   # :1138-1149, :1178-1199
+                ok = (verdict == api.FIND_ACCEPTED) & (ns <= cap)
             worst = torch.zeros(A, dtype=torch.float64, device=dev)
             go_on = torch.zeros(A, dtype=torch.bool, device=dev)
             offsets = torch.zeros(A + 1, dtype=torch.int32, device=dev)
@@ -182,5 +198,11 @@ def optimize_paths(ctx, paths, limits=None, stop_flags=None, relax_heading=None,
     # a path that was still being subdivided when it outgrew a plan, or whose rounds ran out, keeps what the loop left it
     lost = np.setdiff1d(np.arange(P), np.flatnonzero(success))
     n_samples[lost] = 0
+    if pol.override_heading_atan2:                       # getTrajectoryReference :1578-1603, where the samples are
+        plan = api.Plan(ctx, np.arange(P + 1, dtype=np.int32))
+        try:
+            plan.travel_heading(samples_out, torch.from_numpy(n_samples).to(dev), status=torch.from_numpy(success).to(dev))
+        finally:
+            plan.close()
     return dict(success=success, n_samples=n_samples, samples=samples_out, max_deviation=max_dev, n_waypoints=n_wp,
                 iterations=iters)
