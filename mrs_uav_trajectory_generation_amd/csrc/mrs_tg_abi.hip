@@ -459,9 +459,11 @@ int mrs_tg_plan_assemble(mrs_tg_plan* plan, int32_t d, const double* seg_times_d
   return MRS_TG_OK;
 }
 
-int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, const double* vals, const double* limits,
+// mrs_tg_plan_solve, for every entry point that ends in it.  moving_start_seen: the caller has the first vertices in host
+// memory and saw one that moves (mrs_tg_solve_batch, the policy's device round); a device-resident caller cannot say
+static int plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, const double* vals, const double* limits,
                       const mrs_tg_options* opt, double* seg_times, double* coeffs, int32_t* status, double* cost,
-                      int32_t* n_samples, double* samples) {
+                      int32_t* n_samples, double* samples, bool moving_start_seen) {
   if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
   mrs_tg_ctx* ctx = plan->ctx;
   int rc = check_options(ctx, opt);
@@ -489,8 +491,8 @@ int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
   }
   const double* pos_wp = (opt->flags & MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS) ? wp : nullptr;
   const int d = opt->derivative_to_optimize;
-  mrs_tg::HintScope shared_scope(mrs_tg::set_shared_device_hint, (opt->flags & MRS_TG_FLAG_SHARED_DEVICE) != 0);
-  mrs_tg::HintScope slots_scope(mrs_tg::set_constrained_slots_hint, (opt->flags & MRS_TG_FLAG_CONSTRAINED_SLOTS) != 0);
+  const mrs_tg::RouteHints hints =
+      mrs_tg::route_hints(opt->flags, moving_start_seen, opt->time_alloc_method, (size_t)b.n_paths, b.max_segments);
   bool sampled = false;  // the sampling rode on the final solve's launch
   // MRS_TG_FLAG_REFINE: the refinement pass follows the final solve, so no sampling rides on a solve launch -- the solves go
   // out exactly as in the same call without sampling, and the sampler reads the refined coefficients
@@ -515,7 +517,7 @@ int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
     prm.initial_stepsize_rel = opt->initial_stepsize_rel;
     prm.time_budget_ticks = opt->max_time_s > 0 ? budget_ticks(ctx, opt->max_time_s) : 0;
     ProfileScope ps(ctx, 2);
-    HIP_TRY(ctx, mrs_tg::launch_dfo(plan->nl, b, prm, mask, vals, limits, seg_times, coeffs, status, cost, ctx->stream,
+    HIP_TRY(ctx, mrs_tg::launch_dfo(plan->nl, b, hints, prm, mask, vals, limits, seg_times, coeffs, status, cost, ctx->stream,
                                     (opt->flags & MRS_TG_FLAG_GENERAL_PATTERNS) != 0));
   } else if (opt->time_alloc_method == MRS_TG_TIME_ALLOC_MELLINGER) {
     mrs_tg::NonlinearParams prm;
@@ -537,8 +539,8 @@ int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
     prm.pos_wp = pos_wp;
     prm.reference_status = (opt->flags & MRS_TG_FLAG_REFERENCE_STATUS) != 0;
     ProfileScope ps(ctx, 2);
-    HIP_TRY(ctx, mrs_tg::launch_nonlinear(plan->nl, b, prm, mask, vals, limits, seg_times, coeffs, status, cost, ctx->stream,
-                                          solve_sampling_dt, opt->sample_capacity, n_samples, samples, &sampled,
+    HIP_TRY(ctx, mrs_tg::launch_nonlinear(plan->nl, b, hints, prm, mask, vals, limits, seg_times, coeffs, status, cost,
+                                          ctx->stream, solve_sampling_dt, opt->sample_capacity, n_samples, samples, &sampled,
                                           (opt->flags & MRS_TG_FLAG_GENERAL_PATTERNS) != 0));
   } else {
     const bool fused = (opt->flags & MRS_TG_FLAG_MATERIALIZED_BLOCKS) == 0;  // the default since ABI 2
@@ -559,10 +561,11 @@ int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
       tail.sample_capacity = opt->sample_capacity;
       tail.n_samples = n_samples;
       tail.samples = samples;
-      HIP_TRY(ctx, mrs_tg::launch_solve_rows(b, d, mask, vals, seg_times, coeffs, status, cost, nullptr, ctx->stream, tail));
+      HIP_TRY(ctx, mrs_tg::launch_solve_rows(b, hints, d, mask, vals, seg_times, coeffs, status, cost, nullptr, ctx->stream,
+                                             tail));
       sampled = true;
     } else {
-      HIP_TRY(ctx, mrs_tg::launch_solve_linear(b, d, fused, mask, vals, seg_times, plan->d_H.get(), plan->d_Ainv.get(),
+      HIP_TRY(ctx, mrs_tg::launch_solve_linear(b, hints, d, fused, mask, vals, seg_times, plan->d_H.get(), plan->d_Ainv.get(),
                                                plan->d_ws.get(), coeffs, status, cost, nullptr, ctx->stream,
                                                general ? nullptr : pos_wp));
     }
@@ -578,6 +581,12 @@ int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
     HIP_TRY(ctx, mrs_tg::launch_sample(b, coeffs, seg_times, opt->sampling_dt, opt->sample_capacity, n_samples, samples,
                                        ctx->stream));
   return MRS_TG_OK;
+}
+
+int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, const double* vals, const double* limits,
+                      const mrs_tg_options* opt, double* seg_times, double* coeffs, int32_t* status, double* cost,
+                      int32_t* n_samples, double* samples) {
+  return plan_solve(plan, wp, mask, vals, limits, opt, seg_times, coeffs, status, cost, n_samples, samples, false);
 }
 
 static constexpr size_t kGroupWsPresizeBytes = (size_t)256 << 20;  // bind-time reservation of a grouped launch's factor stores
@@ -821,7 +830,7 @@ int mrs_tg_bound_solve_launch_group(mrs_tg_bound_solve* const* bound, int32_t n_
     mrs_tg_plan* plan = first->plan;
     mrs_tg_ctx* ctx = plan->ctx;
     mrs_tg::RowsGroup g;
-    bool group_constrained_slots = false;
+    mrs_tg::RouteHints hints;  // (of the dispatch: the batches' other hints have no say in a grouped launch)
     for (; g.n < mrs_tg::kRowsGroupMax && k < n_launches; ++k, ++g.n) {
       const mrs_tg_bound_solve* b = bound[k % n_bound];
       if (b->plan != plan || b->opt.derivative_to_optimize != first->opt.derivative_to_optimize) break;
@@ -833,19 +842,19 @@ int mrs_tg_bound_solve_launch_group(mrs_tg_bound_solve* const* bound, int32_t n_
       g.status[g.n] = b->status;
       g.cost[g.n] = b->cost;
       g.pos_wp[g.n] = (b->opt.flags & MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS) ? b->wp : nullptr;
-      group_constrained_slots = group_constrained_slots || (b->opt.flags & MRS_TG_FLAG_CONSTRAINED_SLOTS) != 0;
+      // MRS_TG_FLAG_CONSTRAINED_SLOTS of any batch of the group: the dispatch runs the instantiations that take stop_at
+      // vertices inside the specialised sweeps
+      hints.constrained_slots = hints.constrained_slots || (b->opt.flags & MRS_TG_FLAG_CONSTRAINED_SLOTS) != 0;
     }
     if (plan->view.n_paths == 0) continue;
     HIP_TRY(ctx, use_device(ctx->device));
     ProfileScope ps(ctx, 1);
-    // MRS_TG_FLAG_CONSTRAINED_SLOTS of any batch of the group: the dispatch runs the instantiations that take stop_at vertices
-    // inside the specialised sweeps (the hint was only set by mrs_tg_plan_solve)
-    mrs_tg::HintScope hint_scope(mrs_tg::set_constrained_slots_hint, group_constrained_slots);
     if (mrs_tg::quad_kernel_applies(plan->view, (long long)plan->view.n_paths * g.n, false)) {
       // the dispatch carries more paths than the rows kernel has wavefront slots for: four lanes per path, factors in LDS
       // (one factor store per batch of THIS group; grows when a larger group comes, never shrinks)
       HIP_TRY(ctx, plan->d_ws.ensure((size_t)g.n * mrs_tg::linear_workspace_doubles(plan->view), mrs_tg::StreamIdle{ctx->stream}));
-      HIP_TRY(ctx, mrs_tg::launch_solve_quad_group(plan->view, first->opt.derivative_to_optimize, g, plan->d_ws.get(), ctx->stream));
+      HIP_TRY(ctx, mrs_tg::launch_solve_quad_group(plan->view, hints, first->opt.derivative_to_optimize, g, plan->d_ws.get(),
+                                                   ctx->stream));
     } else {
       HIP_TRY(ctx, mrs_tg::launch_solve_rows_group(plan->view, first->opt.derivative_to_optimize, g, ctx->stream));
     }
@@ -1453,13 +1462,11 @@ int policy_round_device(mrs_tg_ctx* ctx, const PolicyRoundIn& in) {
   int32_t* st_d = reinterpret_cast<int32_t*>(d + R.status);
   int32_t* ns_d = reinterpret_cast<int32_t*>(d + R.n_samples);
   double* smp_d = reinterpret_cast<double*>(d + R.samples);
-  // the moving-start hint, as mrs_tg_solve_batch sets it on the host route from the same condition (the launch shape of the
-  // outer loop depends on it: launch_nonlinear); the round's builder read it off the initial states
-  mrs_tg::HintScope moving_scope(mrs_tg::set_moving_starts_hint,
-                                 in.moving_starts != 0 &&
-                                     mrs_tg::wants_moving_starts(opt.time_alloc_method, A, plan->view.max_segments));
-  rc = mrs_tg_plan_solve(plan, wp_d, mask_d, vals_d, reinterpret_cast<const double*>(d + L.lim), &opt, reinterpret_cast<double*>(d + R.times),
-                         reinterpret_cast<double*>(d + R.coeffs), st_d, reinterpret_cast<double*>(d + R.cost), ns_d, smp_d);
+  // a moving start, as mrs_tg_solve_batch passes it on the host route (the launch shape of the outer loop depends on it:
+  // launch_nonlinear); the round's builder read it off the initial states
+  rc = plan_solve(plan, wp_d, mask_d, vals_d, reinterpret_cast<const double*>(d + L.lim), &opt, reinterpret_cast<double*>(d + R.times),
+                  reinterpret_cast<double*>(d + R.coeffs), st_d, reinterpret_cast<double*>(d + R.cost), ns_d, smp_d,
+                  in.moving_starts != 0);
   if (rc != MRS_TG_OK) return rc;
   // gates + validateTrajectorySpatial where the samples are; the small results go where the host reads them
   char* res = pinned ? blk_dev : d;  // (res + L.<field> addresses the field in either place: the arena mirrors the block)
@@ -1635,8 +1642,8 @@ static int solve_batch_impl(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* so,
   if ((rc = call.ensure_arenas()) != MRS_TG_OK) return rc;
   SyncOnExit sync_on_exit{call.s};
 
-  // ---- infer flags and hint: the masks are in host memory here.  The moving-start hint matters to the outer loop's launch
-  // shape only (small batches of 13-15 segments; launch_nonlinear)
+  // ---- infer flags and the moving start the solve is told of: the masks are in host memory here.  A moving start matters to
+  // the outer loop's launch shape only (small batches of 13-15 segments; launch_nonlinear)
   mrs_tg_options local = *opt;
   const mrs_tg::ConstraintScan scan = mrs_tg::scan_constraints(
       n_paths, so, mask, vals, local.derivative_to_optimize, !(local.flags & MRS_TG_FLAG_GENERAL_PATTERNS),
@@ -1644,7 +1651,6 @@ static int solve_batch_impl(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* so,
       mrs_tg::wants_moving_starts(local.time_alloc_method, (size_t)n_paths, plan->view.max_segments));
   if (scan.general_patterns) local.flags |= MRS_TG_FLAG_GENERAL_PATTERNS;
   if (scan.constrained_slots) local.flags |= MRS_TG_FLAG_CONSTRAINED_SLOTS;
-  mrs_tg::HintScope moving_scope(mrs_tg::set_moving_starts_hint, scan.moving_starts);
   // ---- decide zero copy: one pass over every array (fixed times, default solve) and every array the caller passed is pinned
   call.zero_copy = mrs_tg::knob::zero_copy() && local.time_alloc_method == MRS_TG_TIME_ALLOC_NONE && !local.estimate_times &&
                    (local.flags & (MRS_TG_FLAG_GENERAL_PATTERNS | MRS_TG_FLAG_MATERIALIZED_BLOCKS)) == 0 &&
@@ -1658,10 +1664,10 @@ static int solve_batch_impl(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* so,
     local.max_time_s = local.max_time_s - spent > 1.0e-9 ? local.max_time_s - spent : 1.0e-9;
   }
   // (estimate_times without waypoints is refused by mrs_tg_plan_solve, as before)
-  rc = mrs_tg_plan_solve(plan, want_wp ? call.dev<double>(A_WP) : nullptr, call.dev<uint8_t>(A_MASK), call.dev<double>(A_VALS),
-                         limits ? call.dev<double>(A_LIM) : nullptr, &local, call.dev<double>(A_T), call.dev<double>(A_C),
-                         call.dev<int32_t>(A_ST), call.dev<double>(A_COST), sampling ? call.dev<int32_t>(A_NS) : nullptr,
-                         samp_doubles ? call.dev<double>(A_SMP) : nullptr);
+  rc = plan_solve(plan, want_wp ? call.dev<double>(A_WP) : nullptr, call.dev<uint8_t>(A_MASK), call.dev<double>(A_VALS),
+                  limits ? call.dev<double>(A_LIM) : nullptr, &local, call.dev<double>(A_T), call.dev<double>(A_C),
+                  call.dev<int32_t>(A_ST), call.dev<double>(A_COST), sampling ? call.dev<int32_t>(A_NS) : nullptr,
+                  samp_doubles ? call.dev<double>(A_SMP) : nullptr, scan.moving_starts);
   if (rc != MRS_TG_OK) return rc;
   if ((rc = call.download()) != MRS_TG_OK) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(call.s));

@@ -477,8 +477,8 @@ __global__ __launch_bounds__(64) void dfo_segment_path_kernel(BatchView b, int32
 // ---------------------------------------------------------------------------------------------
 // host side
 
-hipError_t launch_dfo(NonlinearPlan& nl, const BatchView& b, const DfoParams& prm, const uint8_t* mask, const double* vals,
-                      const double* limits, double* seg_times, double* coeffs, int32_t* status, double* cost,
+hipError_t launch_dfo(NonlinearPlan& nl, const BatchView& b, const RouteHints& hints, const DfoParams& prm, const uint8_t* mask,
+                      const double* vals, const double* limits, double* seg_times, double* coeffs, int32_t* status, double* cost,
                       hipStream_t stream, bool general) {
   const KernelTimer kt = take_kernel_timer();  // family 2: the whole search, dfo_init_kernel to dfo_finalize_kernel
   if (b.n_paths == 0) return hipSuccess;
@@ -507,7 +507,7 @@ hipError_t launch_dfo(NonlinearPlan& nl, const BatchView& b, const DfoParams& pr
   // the general solve on: then every linear solve of the search is followed by the 5 x 5-block solve of those paths)
   if (general && (e = nonlinear_prepare_general(nl, b, mask, seg_times, false, nullptr, stream)) != hipSuccess) return e;
   const int32_t* general_flag = general ? nl.d_general.get() + 4 : nullptr;
-  if ((e = launch_solve_linear(b, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs,
+  if ((e = launch_solve_linear(b, hints, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs,
                                status, cost, nullptr, stream)) != hipSuccess)
     return e;
   if (general && (e = launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws.get(), coeffs,
@@ -526,7 +526,7 @@ hipError_t launch_dfo(NonlinearPlan& nl, const BatchView& b, const DfoParams& pr
                          nl.d_dfo_segcost.get());
       if ((e = hipGetLastError()) != hipSuccess) return e;
     } else if (r > 0) {  // round 0 evaluates the start point, solved above
-      if ((e = launch_solve_linear(b, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs,
+      if ((e = launch_solve_linear(b, hints, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs,
                                    nullptr, cost, nullptr, stream)) != hipSuccess)
         return e;
       if (general && (e = launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws.get(), coeffs,

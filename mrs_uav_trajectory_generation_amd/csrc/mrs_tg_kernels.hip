@@ -261,18 +261,18 @@ hipError_t launch_assemble(const BatchView& b, int d, const double* seg_times, d
 // lanes of the 1-lane variant alone fill the machine
 static inline bool use_split_dims(int n_paths) { return n_paths <= 32768; }
 
-hipError_t launch_solve_linear(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,
-                               const double* seg_times, const double* H, const double* Ainv, double* ws,
+hipError_t launch_solve_linear(const BatchView& b, const RouteHints& hints, int d, bool fused, const uint8_t* mask,
+                               const double* vals, const double* seg_times, const double* H, const double* Ainv, double* ws,
                                double* coeffs, int32_t* status, double* cost, const int32_t* status_in,
                                hipStream_t stream, const double* pos_wp) {
   if (b.n_paths == 0) return hipSuccess;
   if (fused && ws != nullptr && quad_kernel_applies(b, b.n_paths, false)) {  // saturated device: four lanes per path, factors in LDS
     RowsTail tail;
     tail.pos_wp = pos_wp;
-    return launch_solve_quad(b, d, mask, vals, seg_times, coeffs, status, cost, status_in, ws, stream, tail);
+    return launch_solve_quad(b, hints, d, mask, vals, seg_times, coeffs, status, cost, status_in, ws, stream, tail);
   }
   if (fused && rows_kernel_applies(b))
-    return launch_solve_rows(b, d, mask, vals, seg_times, coeffs, status, cost, status_in, stream);
+    return launch_solve_rows(b, hints, d, mask, vals, seg_times, coeffs, status, cost, status_in, stream);
   if (tile_kernel_applies(b, fused))
     return launch_solve_tile(b, d, fused, mask, vals, seg_times, H, Ainv, coeffs, status, cost, status_in, stream);
   // (the one-lane-per-path solve from materialised blocks -- 512 registers and 264 bytes of scratch per lane -- is gone: a

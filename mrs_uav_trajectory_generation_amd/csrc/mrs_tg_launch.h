@@ -25,32 +25,13 @@ struct ThinOptions;  // mrs_tg_pathedit.hpp
 struct KernelTimer {
   hipEvent_t start = nullptr, stop = nullptr;
 };
-// Hint of the calling thread's current ABI call (MRS_TG_FLAG_SHARED_DEVICE): other batches are in flight on the device, so
-// launch shapes that leave wavefront slots free are preferred over the lowest latency of this launch alone.
-void set_shared_device_hint(bool on);
-bool shared_device_hint();
-// Hint of the calling thread's current ABI call (MRS_TG_FLAG_CONSTRAINED_SLOTS): the batch may hold vertices with constrained
-// derivative slots beside its paths' ends; min-snap launches then use the instantiations that take such vertices
-void set_constrained_slots_hint(bool on);
-bool constrained_slots_hint();
-// Hint of the calling thread's current ABI call: some paths start from a moving state (non-zero constrained derivatives at
-// their first vertex).  Set by mrs_tg_solve_batch from the values it holds in host memory (a device-resident caller has no
-// flag for it); read by launch_nonlinear's choice between the plan's dimension split and lane groups
-void set_moving_starts_hint(bool on);
-bool moving_starts_hint();
-// a hint set for the scope of one ABI call of the calling thread and cleared behind it
-struct HintScope {
-  void (*set)(bool);
-  HintScope(void (*setter)(bool), bool on) : set(setter) { set(on); }
-  ~HintScope() { set(false); }
-  HintScope(const HintScope&) = delete;
-  HintScope& operator=(const HintScope&) = delete;
-};
+KernelTimer take_kernel_timer();  // the pending pair (null events when nothing is pending); consumed by the call
+void set_kernel_timer(hipEvent_t start, hipEvent_t stop);  // arms the next timed launch of this thread
+// (RouteHints, what a solve tells its launchers beside the batch and the options: mrs_tg_transfer.hpp.  Every launcher that
+// reads a hint, or calls one that does, takes them as an argument without a default.)
 // compute units of the calling thread's current device, looked up once per device ordinal (a process may drive devices of
 // different sizes or partitions); 256 while the runtime cannot say
 int device_compute_units();
-KernelTimer take_kernel_timer();  // the pending pair (null events when nothing is pending); consumed by the call
-void set_kernel_timer(hipEvent_t start, hipEvent_t stop);  // arms the next timed launch of this thread
 // Kernel trace (mrs_tg_kernel_trace): every launch of the library notes its kernel's name in a small per-thread ring, so
 // that a test or the benchmark can SAY which kernels a call ran instead of inferring it from batch sizes (one pointer store)
 void note_kernel(const char* name);
@@ -136,8 +117,8 @@ int solve_batch_samples_only(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* se
 // (BatchView, the device-resident structure of a batch: mrs_tg_batch.hpp)
 hipError_t launch_assemble(const BatchView& b, int d, const double* seg_times, double* H, double* Ainv,
                            hipStream_t stream);
-hipError_t launch_solve_linear(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,
-                               const double* seg_times, const double* H, const double* Ainv, double* ws,
+hipError_t launch_solve_linear(const BatchView& b, const RouteHints& hints, int d, bool fused, const uint8_t* mask,
+                               const double* vals, const double* seg_times, const double* H, const double* Ainv, double* ws,
                                double* coeffs, int32_t* status, double* cost, const int32_t* status_in,
                                hipStream_t stream, const double* pos_wp = nullptr);
 // (CopyList, up to kCopyMax flat copies in ONE launch: mrs_tg_transfer.hpp)
@@ -363,9 +344,9 @@ bool rows_kernel_applies(const BatchView& b, bool with_sampling = false);
 bool rows_tail_sampling_pays(const BatchView& b);
 // solve -> maxima -> scaling -> solve -> sampling of a pipeline in one launch of the rows kernel (small batches)
 bool rows_pipeline_applies(const BatchView& b);
-hipError_t launch_solve_rows(const BatchView& b, int d, const uint8_t* mask, const double* vals, const double* seg_times,
-                             double* coeffs, int32_t* status, double* cost, const int32_t* status_in, hipStream_t stream,
-                             const RowsTail& tail = RowsTail());
+hipError_t launch_solve_rows(const BatchView& b, const RouteHints& hints, int d, const uint8_t* mask, const double* vals,
+                             const double* seg_times, double* coeffs, int32_t* status, double* cost, const int32_t* status_in,
+                             hipStream_t stream, const RowsTail& tail = RowsTail());
 
 // up to kRowsGroupMax batches of one plan solved by one launch (fixed-times default solve): per batch its arrays
 constexpr int kRowsGroupMax = 16;
@@ -386,9 +367,10 @@ hipError_t launch_solve_rows_group(const BatchView& b, int d, const RowsGroup& g
 // store (linear_workspace_doubles per batch), used by wavefronts whose paths need the general masked step.  tail: the
 // feasibility scaling of a Mellinger pipeline's last solve (no sampling on this launch).
 bool quad_kernel_applies(const BatchView& b, long long paths_in_launch, bool with_sampling);
-hipError_t launch_solve_quad(const BatchView& b, int d, const uint8_t* mask, const double* vals, const double* seg_times,
-                             double* coeffs, int32_t* status, double* cost, const int32_t* status_in, double* ws,
-                             hipStream_t stream, const RowsTail& tail = RowsTail());
-hipError_t launch_solve_quad_group(const BatchView& b, int d, const RowsGroup& g, double* ws, hipStream_t stream);
+hipError_t launch_solve_quad(const BatchView& b, const RouteHints& hints, int d, const uint8_t* mask, const double* vals,
+                             const double* seg_times, double* coeffs, int32_t* status, double* cost, const int32_t* status_in,
+                             double* ws, hipStream_t stream, const RowsTail& tail = RowsTail());
+hipError_t launch_solve_quad_group(const BatchView& b, const RouteHints& hints, int d, const RowsGroup& g, double* ws,
+                                   hipStream_t stream);
 
 }  // namespace mrs_tg

@@ -111,13 +111,14 @@ int nonlinear_plan_build(NonlinearPlan& nl, const std::vector<int32_t>& seg_offs
 // (optimize_general_kernel / solve_general_kernel) behind the fast kernels, the others are untouched by it.
 // sampling_dt > 0: the caller wants the result sampled; when the final solve runs on the rows kernel the sampling rides
 // on that launch (*sampled_out = true) and the caller must not launch the sampler again
-hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const NonlinearParams& prm, const uint8_t* mask,
-                            const double* vals, const double* limits, double* seg_times, double* coeffs,
+// hints: the call's (RouteHints, mrs_tg_transfer.hpp), for the outer loop's route and for every solve either launcher runs
+hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const RouteHints& hints, const NonlinearParams& prm,
+                            const uint8_t* mask, const double* vals, const double* limits, double* seg_times, double* coeffs,
                             int32_t* status, double* cost, hipStream_t stream, double sampling_dt = 0.0,
                             int sample_capacity = 0, int32_t* n_samples = nullptr, double* samples = nullptr,
                             bool* sampled_out = nullptr, bool general = false);
-hipError_t launch_dfo(NonlinearPlan& nl, const BatchView& b, const DfoParams& prm, const uint8_t* mask, const double* vals,
-                      const double* limits, double* seg_times, double* coeffs, int32_t* status, double* cost,
+hipError_t launch_dfo(NonlinearPlan& nl, const BatchView& b, const RouteHints& hints, const DfoParams& prm, const uint8_t* mask,
+                      const double* vals, const double* limits, double* seg_times, double* coeffs, int32_t* status, double* cost,
                       hipStream_t stream, bool general = false);
 hipError_t launch_cost_gradient(NonlinearPlan& nl, const BatchView& b, int d, const uint8_t* mask, const double* vals,
                                 const double* seg_times, double* cost, double* grad, hipStream_t stream);

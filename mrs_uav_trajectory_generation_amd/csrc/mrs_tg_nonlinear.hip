@@ -2126,7 +2126,7 @@ static size_t fill_bin_table(BinTable& bt, const std::vector<NonlinearBin>& bins
   return lds;
 }
 
-// hints: those of the calling thread's ABI call (constrained_slots_hint, moving_starts_hint); compute_units: of the current device
+// constrained_slots, moving_starts: the call's hints (RouteHints, launch_nonlinear's argument); compute_units: of the current device
 // (device_compute_units); estimate: the search starts from the estimate; samples_wanted: the caller asked for samples
 static NonlinearRoute route_nonlinear(const NonlinearPlan& nl, const BatchView& b, int derivative, bool constrained_slots,
                                       bool moving_starts, int compute_units, bool estimate, bool general, bool careful,
@@ -2257,8 +2257,8 @@ static NonlinearRoute route_nonlinear(const NonlinearPlan& nl, const BatchView& 
   return r;
 }
 
-hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const NonlinearParams& prm_in, const uint8_t* mask,
-                            const double* vals, const double* limits, double* seg_times, double* coeffs,
+hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const RouteHints& hints, const NonlinearParams& prm_in,
+                            const uint8_t* mask, const double* vals, const double* limits, double* seg_times, double* coeffs,
                             int32_t* status, double* cost, hipStream_t stream, double sampling_dt, int sample_capacity,
                             int32_t* n_samples, double* samples, bool* sampled_out, bool general) {
   if (sampled_out) *sampled_out = false;
@@ -2267,7 +2267,7 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
   if (e != hipSuccess) return e;
   const bool careful = prm_in.careful_cap != 0;  // the caller asked for the careful re-run (MRS_TG_FLAG_CAREFUL_COST)
   const NonlinearRoute route =
-      route_nonlinear(nl, b, prm_in.derivative, constrained_slots_hint(), moving_starts_hint(), device_compute_units(),
+      route_nonlinear(nl, b, prm_in.derivative, hints.constrained_slots, hints.moving_starts, device_compute_units(),
                       prm_in.estimate_wp != nullptr, general, careful, sampling_dt > 0.0 && n_samples != nullptr);
   if (prm_in.estimate_wp && !route.estimate_in_kernel &&
       (e = launch_estimate_times(b, prm_in.estimate_wp, prm_in.estimate_limits, seg_times, stream)) != hipSuccess)
@@ -2395,11 +2395,12 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
   if (route.closing == Closing::kRowsPipeline) {
     RowsTail tail = closing_tail();
     tail.maxima_in_launch = true;
-    return launch_solve_rows(b, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status.get(), stream, tail);
+    return launch_solve_rows(b, hints, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status.get(), stream,
+                             tail);
   }
   // 2. trajectory of the last evaluated point (scaleSegmentTimesWithViolation works on poly_opt_'s state)
-  if ((e = launch_solve_linear(b, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs, nullptr,
-                               nullptr, nullptr, stream, prm.pos_wp)) != hipSuccess)
+  if ((e = launch_solve_linear(b, hints, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs,
+                               nullptr, nullptr, nullptr, stream, prm.pos_wp)) != hipSuccess)
     return e;
   if (general && (e = launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws.get(), coeffs,
                                            nullptr, nullptr, stream, general_flag, nullptr)) != hipSuccess)
@@ -2417,13 +2418,14 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
     RowsTail tail = closing_tail();
     tail.maxima = nl.d_maxima.get();
     tail.pos_wp = prm.pos_wp;
-    return launch_solve_quad(b, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status.get(),
+    return launch_solve_quad(b, hints, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status.get(),
                              nl.d_ws.get(), stream, tail);
   }
   if (route.closing == Closing::kRowsTail) {
     RowsTail tail = closing_tail();
     tail.maxima = nl.d_maxima.get();
-    return launch_solve_rows(b, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status.get(), stream, tail);
+    return launch_solve_rows(b, hints, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status.get(), stream,
+                             tail);
   }
   MRS_TG_LAUNCH(apply_scaling_kernel, dim3(cdiv(b.n_segments, 256)), dim3(256), 0, stream, b, nl.d_maxima.get(), limits,
                      nl.d_opt_status.get(), seg_times);
@@ -2434,8 +2436,8 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const Nonline
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   // 4. updateSegmentTimes + solveLinear with the scaled times (nonlinear_impl.h:405-408), final status
-  if ((e = launch_solve_linear(b, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs, status, cost,
-                               nl.d_opt_status.get(), stream)) != hipSuccess)
+  if ((e = launch_solve_linear(b, hints, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs,
+                               status, cost, nl.d_opt_status.get(), stream)) != hipSuccess)
     return e;
   if (general)
     return launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws.get(), coeffs, status, cost, stream,

@@ -107,14 +107,9 @@ struct PolicyRoundIn {
   int32_t first_segment, check_enabled, last_round, sample_capacity;
   // a request of the round starts from a moving state (a non-zero velocity / acceleration / jerk of its initial state): what
   // scan_constraints reads off the expanded vertices on the host route.  Wanted, and therefore set, only for the shapes whose
-  // outer-loop launch depends on it (wants_moving_starts below)
+  // outer-loop launch depends on it (wants_moving_starts, mrs_tg_transfer.hpp)
   int32_t moving_starts;
 };
-// the batches whose outer-loop launch shape depends on the moving-start hint (launch_nonlinear: small batches of 13-15 segments),
-// the same condition on both policy routes and in mrs_tg_solve_batch
-inline bool wants_moving_starts(int time_alloc_method, size_t n_paths, int max_segments) {
-  return time_alloc_method == MRS_TG_TIME_ALLOC_MELLINGER && n_paths <= 1536 && max_segments >= 13 && max_segments <= 15;
-}
 int policy_round_device(::mrs_tg_ctx* ctx, const PolicyRoundIn& in);  // (defined in mrs_tg_abi.hip: the GPU build only)
 
 namespace policy {

@@ -116,16 +116,18 @@ void pool_release_cached() {
 // ---- per-dispatch timing (mrs_tg_launch.h): armed by the ABI layer for the kernel it wants timed, consumed by the
 // launcher of that kernel; per thread, because contexts are driven from one thread each
 static thread_local KernelTimer t_kernel_timer;
-static thread_local bool t_shared_device = false;
 
-void set_shared_device_hint(bool on) { t_shared_device = on; }
-bool shared_device_hint() { return t_shared_device; }
-static thread_local bool t_constrained_slots = false;
-void set_constrained_slots_hint(bool on) { t_constrained_slots = on; }
-bool constrained_slots_hint() { return t_constrained_slots; }
-static thread_local bool t_moving_starts = false;
-bool moving_starts_hint() { return t_moving_starts; }
-void set_moving_starts_hint(bool on) { t_moving_starts = on; }
+void set_kernel_timer(hipEvent_t start, hipEvent_t stop) {
+  t_kernel_timer.start = start;
+  t_kernel_timer.stop = stop;
+}
+
+KernelTimer take_kernel_timer() {
+  const KernelTimer k = t_kernel_timer;
+  t_kernel_timer = KernelTimer{};
+  return k;
+}
+
 int device_compute_units() {
   static std::mutex mu;
   static std::map<int, int> cus_of;  // device ordinal -> compute units
@@ -140,15 +142,11 @@ int device_compute_units() {
   }
   return it->second;
 }
+
+// ---- dry run (mrs_tg_plan_explain): per thread, like the timer
 static thread_local bool t_dry_run = false;
 bool dry_run() { return t_dry_run; }
 void set_dry_run(bool on) { t_dry_run = on; }
-
-
-void set_kernel_timer(hipEvent_t start, hipEvent_t stop) {
-  t_kernel_timer.start = start;
-  t_kernel_timer.stop = stop;
-}
 
 // ---- kernel trace (mrs_tg_kernel_trace): names are string literals of the launch macros, kept by pointer
 static constexpr int kTraceCap = 32;
@@ -169,12 +167,6 @@ int kernel_trace(const char** names_out, int capacity) {
   int n = 0;
   for (unsigned k = first; k < t_trace_n && n < capacity; ++k) names_out[n++] = t_trace[k % kTraceCap];
   return n;
-}
-
-KernelTimer take_kernel_timer() {
-  const KernelTimer k = t_kernel_timer;
-  t_kernel_timer = KernelTimer{};
-  return k;
 }
 
 }  // namespace mrs_tg

@@ -1427,13 +1427,13 @@ bool quad_kernel_applies(const BatchView& b, long long paths_in_launch, bool wit
   return quad_lds_doubles(b.max_segments) * sizeof(double) <= kQuadLdsBudget;
 }
 
-hipError_t launch_solve_quad(const BatchView& b, int d, const uint8_t* mask, const double* vals, const double* seg_times,
-                             double* coeffs, int32_t* status, double* cost, const int32_t* status_in, double* ws,
-                             hipStream_t stream, const RowsTail& tail) {
+hipError_t launch_solve_quad(const BatchView& b, const RouteHints& hints, int d, const uint8_t* mask, const double* vals,
+                             const double* seg_times, double* coeffs, int32_t* status, double* cost, const int32_t* status_in,
+                             double* ws, hipStream_t stream, const RowsTail& tail) {
   // objective orders below snap leave jerk and / or snap free at the end vertices of a rest-to-rest path: the instantiation
   // that eliminates such end vertices (two more records per path in LDS), while its LDS fits; MRS_TG_QUAD_ENDS=0: the general
   // step for those paths, as until round 5
-  const bool ends = knob::quad_ends() && (d < 4 || constrained_slots_hint()) &&
+  const bool ends = knob::quad_ends() && (d < 4 || hints.constrained_slots) &&
                     quad_lds_doubles(b.max_segments, true) * sizeof(double) <= kQuadLdsBudget;
   const bool wp = tail.pos_wp != nullptr;
   if (!ends && !(d < 4) && duo_pays(b.n_paths)) {  // few wavefronts: eight lanes per path, the chain cut in the middle
@@ -1461,9 +1461,10 @@ hipError_t launch_solve_quad(const BatchView& b, int d, const uint8_t* mask, con
   return hipGetLastError();
 }
 
-hipError_t launch_solve_quad_group(const BatchView& b, int d, const RowsGroup& g, double* ws, hipStream_t stream) {
+hipError_t launch_solve_quad_group(const BatchView& b, const RouteHints& hints, int d, const RowsGroup& g, double* ws,
+                                   hipStream_t stream) {
   if (g.n < 1 || g.n > kRowsGroupMax) return hipErrorInvalidValue;
-  const bool ends = knob::quad_ends() && (d < 4 || constrained_slots_hint()) &&
+  const bool ends = knob::quad_ends() && (d < 4 || hints.constrained_slots) &&
                     quad_lds_doubles(b.max_segments, true) * sizeof(double) <= kQuadLdsBudget;
   const size_t lds_bytes = quad_lds_doubles(b.max_segments, ends) * sizeof(double);
   bool wp = true;

@@ -712,9 +712,9 @@ bool rows_pipeline_applies(const BatchView& b) {
          rows_lds_bytes(b.max_segments, 1, true, true) <= kRowsLdsBudget;
 }
 
-hipError_t launch_solve_rows(const BatchView& b, int d, const uint8_t* mask, const double* vals, const double* seg_times,
-                             double* coeffs, int32_t* status, double* cost, const int32_t* status_in, hipStream_t stream,
-                             const RowsTail& tail) {
+hipError_t launch_solve_rows(const BatchView& b, const RouteHints& hints, int d, const uint8_t* mask, const double* vals,
+                             const double* seg_times, double* coeffs, int32_t* status, double* cost, const int32_t* status_in,
+                             hipStream_t stream, const RowsTail& tail) {
   const bool sampling = tail.sampling_dt > 0.0;
   RowsTail tail_k = tail;  // (the copy the kernel gets: with the sampling walk's table filled in)
   AccPin pin;  // (released when this function returns: behind the enqueue of the kernel that reads the table)
@@ -738,7 +738,7 @@ hipError_t launch_solve_rows(const BatchView& b, int d, const uint8_t* mask, con
   // when the caller says other batches share the device: at 255 VGPRs a SIMD holds two wavefronts, so 1024 one-path
   // wavefronts per launch let two launches run side by side, 512 two-path wavefronts four (1024 x 10, four streams:
   // 4.9 -> 4.1 us per step; alone on the device the two-path launch is 0.9 us slower)
-  int ppw = (b.n_paths <= 2048 && !(shared_device_hint() && !sampling)) ? 1 : 2;
+  int ppw = (b.n_paths <= 2048 && !(hints.shared_device && !sampling)) ? 1 : 2;
   if (knob::rows_ppw()) ppw = knob::rows_ppw();  // MRS_TG_ROWS_PPW=1|2
   if (rows_lds_bytes(b.max_segments, 2, sampling) > kRowsLdsBudget) ppw = 1;
   const size_t lds_bytes = rows_lds_bytes(b.max_segments, ppw, sampling);

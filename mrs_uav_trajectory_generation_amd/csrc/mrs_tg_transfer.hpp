@@ -1,6 +1,7 @@
 // mrs_tg_transfer.hpp -- the transfer plan of the one-call host interface (mrs_tg_solve_batch / solve_batch_samples_only in
 // mrs_tg_abi.hip): which arrays a call has, how each one travels, where each one lies in the context's arenas, what the
-// caller's masks say about the batch, and whether the caller's statement about its positions holds.  Plain C++17 arithmetic
+// caller's masks say about the batch, whether the caller's statement about its positions holds, and the hints a solve hands
+// its launchers (RouteHints).  Plain C++17 arithmetic
 // without a HIP type or call: mrs_tg_abi.hip enqueues what this header decides, and tests/host/transfer_harness.cpp runs the
 // same functions under g++ and the sanitizers.
 #pragma once
@@ -8,6 +9,8 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+
+#include "../../include/mrs_tg.h"
 
 namespace mrs_tg {
 
@@ -154,6 +157,31 @@ inline ConstraintScan scan_constraints(int32_t n_paths, const int32_t* so, const
           for (int q = 0; q < 4; ++q) moving = moving || vals[(v * 5 + k) * 4 + q] != 0.0;
     }
   return ConstraintScan{general, slots, moving};
+}
+
+// the batches whose outer-loop launch shape depends on a moving start (launch_nonlinear: small batches of 13-15 segments), the
+// same condition on both policy routes and in mrs_tg_solve_batch
+inline bool wants_moving_starts(int time_alloc_method, size_t n_paths, int max_segments) {
+  return time_alloc_method == MRS_TG_TIME_ALLOC_MELLINGER && n_paths <= 1536 && max_segments >= 13 && max_segments <= 15;
+}
+// shared_device: other batches are in flight on the device, so launch shapes that leave wavefront slots free are preferred over
+// the lowest latency of this launch alone (launch_solve_rows).  constrained_slots: the batch may hold vertices with constrained
+// derivative slots beside its paths' ends; min-snap launches then use the instantiations that take such vertices
+// (launch_solve_quad, launch_solve_quad_group, launch_nonlinear).  moving_starts: some paths start from a moving state (non-zero
+// constrained derivatives at their first vertex); launch_nonlinear's choice between the plan's dimension split and lane groups.
+struct RouteHints {            // what a call tells the routers beside its batch and options; never a kernel argument
+  bool shared_device = false;      // MRS_TG_FLAG_SHARED_DEVICE
+  bool constrained_slots = false;  // MRS_TG_FLAG_CONSTRAINED_SLOTS
+  bool moving_starts = false;      // the caller saw a moving start AND the shape is one whose route depends on it
+};
+// the hints of one solve: its option flags, and what its caller saw of its paths' first vertices (a device-resident caller has
+// no flag for a moving start and says false)
+inline RouteHints route_hints(int flags, bool moving_start_seen, int time_alloc_method, size_t n_paths, int max_segments) {
+  RouteHints h;
+  h.shared_device = (flags & MRS_TG_FLAG_SHARED_DEVICE) != 0;
+  h.constrained_slots = (flags & MRS_TG_FLAG_CONSTRAINED_SLOTS) != 0;
+  h.moving_starts = moving_start_seen && wants_moving_starts(time_alloc_method, n_paths, max_segments);
+  return h;
 }
 
 // MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS on host arrays: the number of vertices whose position is unconstrained or whose

@@ -101,7 +101,7 @@ int main(int argc, char** argv) {
       CK(hipMemcpyAsync(Tw, dT, (size_t)P * S * 8, hipMemcpyDeviceToDevice, st));
       CK(hipEventRecord(e0, st));
       set_kernel_timer(k0, k1);  // rides on the outer-loop launch(es) of the call
-      CK(launch_nonlinear(nl, b, prm, dmask, dvals, dlim, Tw, coeffs, status, cost, st));
+      CK(launch_nonlinear(nl, b, RouteHints{}, prm, dmask, dvals, dlim, Tw, coeffs, status, cost, st));
       CK(hipEventRecord(e1, st));
       CK(hipEventSynchronize(e1));
       float ms;

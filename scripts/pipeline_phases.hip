@@ -116,16 +116,16 @@ int main(int argc, char** argv) {
   timed("separate launches (solve, maxima, solve with scaling + sampling)", [&] {
     RowsTail t2 = tail;
     t2.maxima = maxima;
-    CK(launch_solve_rows(b, d, dmask, dvals, Tw, coeffs, nullptr, nullptr, nullptr, st));
+    CK(launch_solve_rows(b, RouteHints{}, d, dmask, dvals, Tw, coeffs, nullptr, nullptr, nullptr, st));
     CK(launch_segment_maxima(b, coeffs, Tw, maxima, st));
-    CK(launch_solve_rows(b, d, dmask, dvals, Tw, coeffs, status, cost, opt_status, st, t2));
+    CK(launch_solve_rows(b, RouteHints{}, d, dmask, dvals, Tw, coeffs, status, cost, opt_status, st, t2));
   });
   std::vector<double> c_sep((size_t)P * S * 40), c_one((size_t)P * S * 40);
   CK(hipMemcpy(c_sep.data(), coeffs, c_sep.size() * 8, hipMemcpyDeviceToHost));
   timed("one launch", [&] {
     RowsTail t2 = tail;
     t2.maxima_in_launch = true;
-    CK(launch_solve_rows(b, d, dmask, dvals, Tw, coeffs, status, cost, opt_status, st, t2));
+    CK(launch_solve_rows(b, RouteHints{}, d, dmask, dvals, Tw, coeffs, status, cost, opt_status, st, t2));
   });
   CK(hipMemcpy(c_one.data(), coeffs, c_one.size() * 8, hipMemcpyDeviceToHost));
   size_t diff = 0;

@@ -22,7 +22,7 @@ int main(int argc, char** argv) {
   BatchView b{P, S, S, S, to_dev(so), to_dev(order), to_dev(slot)};
   double *coeffs, *cost; int32_t* status;
   CK(hipMalloc(&coeffs, S * 40 * 8)); CK(hipMalloc(&cost, 8)); CK(hipMalloc(&status, 4));
-  CK(launch_solve_rows(b, d, to_dev(mask), to_dev(vals), to_dev(T), coeffs, status, cost, nullptr, 0));
+  CK(launch_solve_rows(b, RouteHints{}, d, to_dev(mask), to_dev(vals), to_dev(T), coeffs, status, cost, nullptr, 0));
   CK(hipDeviceSynchronize());
   std::vector<double> dbg(64 * 24 * 2);
   CK(hipMemcpyFromSymbol(dbg.data(), HIP_SYMBOL(g_rows_debug), dbg.size() * 8));

@@ -111,11 +111,11 @@ int main(int argc, char** argv) {
   // the rows kernel (one lane per unknown): the library's fused linear solve
   for (int ppw = 1; ppw <= 2; ++ppw) {
     setenv("MRS_TG_ROWS_PPW", ppw == 1 ? "1" : "2", 1);
-    for (int i = 0; i < 10; ++i) CK(launch_solve_rows(b, d, dmask, dvals, dT, coeffs, status, cost, nullptr, st));
+    for (int i = 0; i < 10; ++i) CK(launch_solve_rows(b, RouteHints{}, d, dmask, dvals, dT, coeffs, status, cost, nullptr, st));
     CK(hipStreamSynchronize(st));
     const int n = 200;
     CK(hipEventRecord(e0, st));
-    for (int i = 0; i < n; ++i) CK(launch_solve_rows(b, d, dmask, dvals, dT, coeffs, status, cost, nullptr, st));
+    for (int i = 0; i < n; ++i) CK(launch_solve_rows(b, RouteHints{}, d, dmask, dvals, dT, coeffs, status, cost, nullptr, st));
     CK(hipEventRecord(e1, st));
     CK(hipEventSynchronize(e1));
     float ms;
@@ -168,7 +168,7 @@ int main(int argc, char** argv) {
     for (int i = 0; i < n + 3; ++i) {
       CK(hipMemcpyAsync(Tw, dT, (size_t)P * S * 8, hipMemcpyDeviceToDevice, st));
       CK(hipEventRecord(e0, st));
-      CK(launch_nonlinear(nl, b, prm, dmask, dvals, dlim, Tw, coeffs, status, cost, st));
+      CK(launch_nonlinear(nl, b, RouteHints{}, prm, dmask, dvals, dlim, Tw, coeffs, status, cost, st));
       CK(hipEventRecord(e1, st));
       CK(hipEventSynchronize(e1));
       float ms;

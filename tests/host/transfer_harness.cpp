@@ -1,5 +1,5 @@
 // transfer_harness.cpp -- the transfer plan of the one-call host interface (csrc/mrs_tg_transfer.hpp: the array table,
-// classify, lay_out, every_array_pinned, scan_constraints, count_position_mismatches_host, CopyList::add) and the device arena
+// classify, lay_out, every_array_pinned, scan_constraints, count_position_mismatches_host, CopyList::add, route_hints) and the device arena
 // of a policy round (csrc/mrs_tg_policy_host.hpp: policy_round_arena) compiled with plain g++ for the CPU.  "Pinned" is whatever
 // the harness says it is: classify takes the question as a callable.  tests/test_transfer_host.py drives it and restates what
 // it prints.
@@ -22,6 +22,8 @@
 //       -> the fields of policy_round_arena in order, then in_bytes, samples and total_bytes of policy_round_layout
 //   copylist
 //       -> kCopyMax, n after kCopyMax + 1 adds, how many adds were refused
+//   hints flags moving_start_seen time_alloc_method n_paths max_segments
+//       -> route_hints: shared_device constrained_slots moving_starts, then wants_moving_starts of the last three arguments
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -209,6 +211,16 @@ int copylist() {
   return 0;
 }
 
+int hints() {
+  int flags, seen, method, max_segments;
+  size_t n_paths;
+  if (std::scanf("%d %d %d %zu %d", &flags, &seen, &method, &n_paths, &max_segments) != 5) return 2;
+  const RouteHints h = route_hints(flags, seen != 0, method, n_paths, max_segments);
+  std::printf("%d %d %d %d\n", (int)h.shared_device, (int)h.constrained_slots, (int)h.moving_starts,
+              (int)wants_moving_starts(method, n_paths, max_segments));
+  return 0;
+}
+
 }  // namespace
 
 int main() {
@@ -220,6 +232,7 @@ int main() {
                    : !std::strcmp(cmd, "mismatch") ? mismatch()
                    : !std::strcmp(cmd, "arena")   ? arena()
                    : !std::strcmp(cmd, "copylist") ? copylist()
+                   : !std::strcmp(cmd, "hints")   ? hints()
                                                    : 2;
     if (rc) return rc;
   }

@@ -1,7 +1,10 @@
 """The transfer plan of the one-call host interface on the CPU: csrc/mrs_tg_transfer.hpp (array table, classify, lay_out,
-every_array_pinned, scan_constraints, count_position_mismatches_host, CopyList::add) and policy_round_arena of csrc/mrs_tg_policy_host.hpp, compiled by g++ into
+every_array_pinned, scan_constraints, count_position_mismatches_host, CopyList::add, route_hints) and policy_round_arena of csrc/mrs_tg_policy_host.hpp, compiled by g++ into
 tests/host/transfer_harness.cpp.  The layout is checked exhaustively against its invariants inside the harness and, for named
 cases, against a restatement here; the scans and the position check against brute force in numpy.  No GPU."""
+import os
+import re
+
 import numpy as np
 import pytest
 
@@ -340,6 +343,61 @@ def test_a_full_copy_list_refuses_the_next_copy(harness):
     assert n == k_max == 8 and refused == 1
 
 
+# ---- route_hints: what a solve tells its launchers, from its option flags and what its caller saw of the first vertices ----
+
+def _header_enum(prefix):
+    """name -> value of every enumerator of include/mrs_tg.h that starts with `prefix`"""
+    with open(os.path.join(hh.ROOT, "include", "mrs_tg.h")) as f:
+        found = dict((name, int(value)) for name, value in re.findall(r"\b(%s\w+)\s*=\s*(-?\d+)" % prefix, f.read()))
+    assert found, prefix
+    return found
+
+
+MELLINGER = "MRS_TG_TIME_ALLOC_MELLINGER"
+# (time-allocation method by name, paths, longest path): the shape that is inside the window and its neighbours across each edge
+HINT_INSIDE = (MELLINGER, 1536, 13)
+HINT_EDGES = [((MELLINGER, 1536, 13), (MELLINGER, 1537, 13)), ((MELLINGER, 1536, 13), (MELLINGER, 1536, 12)),
+              ((MELLINGER, 1536, 15), (MELLINGER, 1536, 16)), ((MELLINGER, 1, 15), (MELLINGER, 1, 16)),
+              ((MELLINGER, 1, 13), (MELLINGER, 1, 12))]
+
+
+def _hint_cases():
+    """(flags, seen, method, paths, segments) of every case: every flag bit alone, none and all of them, on every shape; the
+    shapes are the window's neighbours under Mellinger and the inside shape under every other method"""
+    flags, methods = _header_enum("MRS_TG_FLAG_"), _header_enum("MRS_TG_TIME_ALLOC_")
+    shapes = sorted(set(s for pair in HINT_EDGES for s in pair) | set((m, HINT_INSIDE[1], HINT_INSIDE[2]) for m in methods))
+    every = 0
+    for bit in flags.values():
+        every |= bit
+    return [(f, seen, methods[m], n, S) for f in [0, every] + sorted(flags.values()) for seen in (0, 1) for m, n, S in shapes]
+
+
+def _check_hints(exe, env=None):
+    flags, methods = _header_enum("MRS_TG_FLAG_"), _header_enum("MRS_TG_TIME_ALLOC_")
+    shared, slots = flags["MRS_TG_FLAG_SHARED_DEVICE"], flags["MRS_TG_FLAG_CONSTRAINED_SLOTS"]
+    assert len(set(flags.values())) == len(flags) and all(bit & (bit - 1) == 0 for bit in flags.values())   # one bit each
+    cases = _hint_cases()
+    got = hh.run(exe, ["hints %d %d %d %d %d\n" % c for c in cases], len(cases), env=env)
+    wants = {}
+    for (f, seen, method, n, S), line in zip(cases, got):
+        h_shared, h_slots, h_moving, wanted = [int(x) for x in line.split()]
+        # each of the two flags sets its own field and no other; every other bit of the header sets none
+        assert (h_shared, h_slots) == (int(f & shared != 0), int(f & slots != 0)), (f, line)
+        # a moving start: seen AND a shape inside wants_moving_starts' window -- whatever the flags are
+        assert h_moving == int(seen and wanted), (f, seen, method, n, S, line)
+        assert wants.setdefault((method, n, S), wanted) == wanted   # the window does not depend on flags or on `seen`
+    # the cases lie on both sides of every edge of the window as wants_moving_starts draws it (move them when it moves)
+    for inside, outside in HINT_EDGES:
+        assert wants[(methods[inside[0]],) + inside[1:]] == 1 and wants[(methods[outside[0]],) + outside[1:]] == 0, (inside, outside)
+    for name, m in methods.items():
+        assert wants[(m,) + HINT_INSIDE[1:]] == int(name == MELLINGER), name
+    return got
+
+
+def test_route_hints_follow_their_flags_and_the_moving_start_window(harness):
+    _check_hints(harness)
+
+
 def test_harness_under_address_and_undefined_behaviour_sanitizers(tmp_path, harness):
     san = hh.build("transfer_harness.cpp", tmp_path, sanitize=True)
     env = dict(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
@@ -347,4 +405,5 @@ def test_harness_under_address_and_undefined_behaviour_sanitizers(tmp_path, harn
     assert _check_scans(san, env=env) == _check_scans(harness)
     assert _check_mismatches(san, env=env) == _check_mismatches(harness)
     assert _check_arena(san, env=env) == _check_arena(harness)
+    assert _check_hints(san, env=env) == _check_hints(harness)
     assert hh.run(san, _enumerate_lines()[:2] + ["copylist\n"], 3, env=env) == hh.run(harness, _enumerate_lines()[:2] + ["copylist\n"], 3)
