@@ -555,20 +555,29 @@ static int plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
       HIP_TRY(ctx, mrs_tg::launch_assemble(b, d, seg_times, plan->d_H.get(), plan->d_Ainv.get(), ctx->stream));
     }
     ProfileScope ps(ctx, 1);
-    if (fused && !general && solve_sampling_dt > 0 && mrs_tg::rows_tail_sampling_pays(b)) {  // solve and sample in one launch
-      mrs_tg::RowsTail tail;
+    mrs_tg::SolveOperands op;
+    op.mask = mask;
+    op.vals = vals;
+    op.seg_times = seg_times;
+    op.H = plan->d_H.get();
+    op.Ainv = plan->d_Ainv.get();
+    op.ws = plan->d_ws.get();
+    op.coeffs = coeffs;
+    op.status = status;
+    op.cost = cost;
+    op.pos_wp = general ? nullptr : pos_wp;
+    mrs_tg::SolveRequest request = mrs_tg::solve_request(d, fused, hints, op);
+    request.sampling = solve_sampling_dt > 0 && !general;  // solve and sample in one launch, where the route takes it
+    const mrs_tg::SolveRoute route = mrs_tg::route_solve(b, request);
+    mrs_tg::RowsTail tail;
+    if (route.sampling) {
       tail.sampling_dt = opt->sampling_dt;
       tail.sample_capacity = opt->sample_capacity;
       tail.n_samples = n_samples;
       tail.samples = samples;
-      HIP_TRY(ctx, mrs_tg::launch_solve_rows(b, hints, d, mask, vals, seg_times, coeffs, status, cost, nullptr, ctx->stream,
-                                             tail));
-      sampled = true;
-    } else {
-      HIP_TRY(ctx, mrs_tg::launch_solve_linear(b, hints, d, fused, mask, vals, seg_times, plan->d_H.get(), plan->d_Ainv.get(),
-                                               plan->d_ws.get(), coeffs, status, cost, nullptr, ctx->stream,
-                                               general ? nullptr : pos_wp));
     }
+    HIP_TRY(ctx, mrs_tg::launch_solve_linear(b, route, op, ctx->stream, tail));
+    sampled = route.sampling;
     // the paths the fast kernels sent back with status -2 (a vertex without a position constraint): 5 x 5 vertex blocks
     if (general)
       HIP_TRY(ctx, mrs_tg::launch_solve_general(b, d, mask, vals, seg_times, plan->d_ws.get(), coeffs, status, cost, ctx->stream));
@@ -590,6 +599,17 @@ int mrs_tg_plan_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* mask, 
 }
 
 static constexpr size_t kGroupWsPresizeBytes = (size_t)256 << 20;  // bind-time reservation of a grouped launch's factor stores
+
+// the route of a grouped dispatch of `group` batches of one plan (the plan's factor store is grown for it where it needs one)
+static mrs_tg::SolveRoute group_route(const mrs_tg::BatchView& b, int d, const mrs_tg::RouteHints& hints, int group, bool waypoints) {
+  mrs_tg::SolveRequest request;
+  request.derivative = d;
+  request.group = group;
+  request.waypoints = waypoints;
+  request.hints = hints;
+  request.compute_units = mrs_tg::solve_compute_units();
+  return mrs_tg::route_solve(b, request);
+}
 
 struct mrs_tg_bound_solve {
   mrs_tg_plan* plan;
@@ -633,7 +653,7 @@ int mrs_tg_plan_bind_solve(mrs_tg_plan* plan, const double* wp, const uint8_t* m
   // mrs_tg_bound_solve_launch_group sizes the store for the group it actually launches.
   if (opt->time_alloc_method == MRS_TG_TIME_ALLOC_NONE && !opt->estimate_times && opt->sampling_dt <= 0 &&
       !(opt->flags & (MRS_TG_FLAG_MATERIALIZED_BLOCKS | MRS_TG_FLAG_GENERAL_PATTERNS)) &&
-      mrs_tg::quad_kernel_applies(plan->view, (long long)plan->view.n_paths * mrs_tg::kRowsGroupMax, false) &&
+      mrs_tg::uses_factor_store(group_route(plan->view, opt->derivative_to_optimize, mrs_tg::RouteHints{}, mrs_tg::kRowsGroupMax, false)) &&
       (size_t)mrs_tg::kRowsGroupMax * mrs_tg::linear_workspace_doubles(plan->view) * sizeof(double) <= kGroupWsPresizeBytes) {
     HIP_TRY(plan->ctx, plan->d_ws.ensure((size_t)mrs_tg::kRowsGroupMax * mrs_tg::linear_workspace_doubles(plan->view),
                                          mrs_tg::StreamIdle{plan->ctx->stream}));
@@ -831,6 +851,7 @@ int mrs_tg_bound_solve_launch_group(mrs_tg_bound_solve* const* bound, int32_t n_
     mrs_tg_ctx* ctx = plan->ctx;
     mrs_tg::RowsGroup g;
     mrs_tg::RouteHints hints;  // (of the dispatch: the batches' other hints have no say in a grouped launch)
+    bool waypoints = true;     // every batch of the group states that its positions are its waypoints
     for (; g.n < mrs_tg::kRowsGroupMax && k < n_launches; ++k, ++g.n) {
       const mrs_tg_bound_solve* b = bound[k % n_bound];
       if (b->plan != plan || b->opt.derivative_to_optimize != first->opt.derivative_to_optimize) break;
@@ -842,6 +863,7 @@ int mrs_tg_bound_solve_launch_group(mrs_tg_bound_solve* const* bound, int32_t n_
       g.status[g.n] = b->status;
       g.cost[g.n] = b->cost;
       g.pos_wp[g.n] = (b->opt.flags & MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS) ? b->wp : nullptr;
+      waypoints = waypoints && g.pos_wp[g.n] != nullptr;
       // MRS_TG_FLAG_CONSTRAINED_SLOTS of any batch of the group: the dispatch runs the instantiations that take stop_at
       // vertices inside the specialised sweeps
       hints.constrained_slots = hints.constrained_slots || (b->opt.flags & MRS_TG_FLAG_CONSTRAINED_SLOTS) != 0;
@@ -849,14 +871,14 @@ int mrs_tg_bound_solve_launch_group(mrs_tg_bound_solve* const* bound, int32_t n_
     if (plan->view.n_paths == 0) continue;
     HIP_TRY(ctx, use_device(ctx->device));
     ProfileScope ps(ctx, 1);
-    if (mrs_tg::quad_kernel_applies(plan->view, (long long)plan->view.n_paths * g.n, false)) {
-      // the dispatch carries more paths than the rows kernel has wavefront slots for: four lanes per path, factors in LDS
-      // (one factor store per batch of THIS group; grows when a larger group comes, never shrinks)
+    const mrs_tg::SolveRoute route = group_route(plan->view, first->opt.derivative_to_optimize, hints, g.n, waypoints);
+    if (mrs_tg::uses_factor_store(route)) {
+      // the dispatch carries more paths than the rows kernel has wavefront slots for: four or eight lanes per path, factors in
+      // LDS (one factor store per batch of THIS group; grows when a larger group comes, never shrinks)
       HIP_TRY(ctx, plan->d_ws.ensure((size_t)g.n * mrs_tg::linear_workspace_doubles(plan->view), mrs_tg::StreamIdle{ctx->stream}));
-      HIP_TRY(ctx, mrs_tg::launch_solve_quad_group(plan->view, hints, first->opt.derivative_to_optimize, g, plan->d_ws.get(),
-                                                   ctx->stream));
+      HIP_TRY(ctx, mrs_tg::launch_solve_quad_group(plan->view, route, g, plan->d_ws.get(), ctx->stream));
     } else {
-      HIP_TRY(ctx, mrs_tg::launch_solve_rows_group(plan->view, first->opt.derivative_to_optimize, g, ctx->stream));
+      HIP_TRY(ctx, mrs_tg::launch_solve_rows_group(plan->view, route, g, ctx->stream));
     }
   }
   return MRS_TG_OK;

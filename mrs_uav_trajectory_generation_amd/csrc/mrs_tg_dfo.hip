@@ -507,9 +507,18 @@ hipError_t launch_dfo(NonlinearPlan& nl, const BatchView& b, const RouteHints& h
   // the general solve on: then every linear solve of the search is followed by the 5 x 5-block solve of those paths)
   if (general && (e = nonlinear_prepare_general(nl, b, mask, seg_times, false, nullptr, stream)) != hipSuccess) return e;
   const int32_t* general_flag = general ? nl.d_general.get() + 4 : nullptr;
-  if ((e = launch_solve_linear(b, hints, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs,
-                               status, cost, nullptr, stream)) != hipSuccess)
-    return e;
+  // every linear solve of the search: one route (the batch, the objective order and the hints do not change between rounds)
+  SolveOperands op;
+  op.mask = mask;
+  op.vals = vals;
+  op.seg_times = seg_times;
+  op.ws = nl.d_ws.get();
+  op.coeffs = coeffs;
+  op.status = status;
+  op.cost = cost;
+  const SolveRoute solve_route = route_solve(b, solve_request(prm.derivative, true, hints, op));
+  if ((e = launch_solve_linear(b, solve_route, op, stream)) != hipSuccess) return e;
+  op.status = nullptr;  // (the rounds' solves: coefficients and cost only)
   if (general && (e = launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws.get(), coeffs,
                                            status, cost, stream, general_flag, nullptr)) != hipSuccess)
     return e;
@@ -526,9 +535,7 @@ hipError_t launch_dfo(NonlinearPlan& nl, const BatchView& b, const RouteHints& h
                          nl.d_dfo_segcost.get());
       if ((e = hipGetLastError()) != hipSuccess) return e;
     } else if (r > 0) {  // round 0 evaluates the start point, solved above
-      if ((e = launch_solve_linear(b, hints, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs,
-                                   nullptr, cost, nullptr, stream)) != hipSuccess)
-        return e;
+      if ((e = launch_solve_linear(b, solve_route, op, stream)) != hipSuccess) return e;
       if (general && (e = launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws.get(), coeffs,
                                                nullptr, cost, stream, general_flag, nullptr)) != hipSuccess)
         return e;

@@ -257,32 +257,24 @@ hipError_t launch_assemble(const BatchView& b, int d, const double* seg_times, d
   return hipGetLastError();
 }
 
-// four lanes per path shorten the dependency chain ~4x but repeat the factorisation: worth it until the
-// lanes of the 1-lane variant alone fill the machine
-static inline bool use_split_dims(int n_paths) { return n_paths <= 32768; }
-
-hipError_t launch_solve_linear(const BatchView& b, const RouteHints& hints, int d, bool fused, const uint8_t* mask,
-                               const double* vals, const double* seg_times, const double* H, const double* Ainv, double* ws,
-                               double* coeffs, int32_t* status, double* cost, const int32_t* status_in,
-                               hipStream_t stream, const double* pos_wp) {
-  if (b.n_paths == 0) return hipSuccess;
-  if (fused && ws != nullptr && quad_kernel_applies(b, b.n_paths, false)) {  // saturated device: four lanes per path, factors in LDS
-    RowsTail tail;
-    tail.pos_wp = pos_wp;
-    return launch_solve_quad(b, hints, d, mask, vals, seg_times, coeffs, status, cost, status_in, ws, stream, tail);
+// the dispatcher over the route's family (route_solve, mrs_tg_solve_route.hpp); the lane kernel's launch is its own
+hipError_t launch_solve_linear(const BatchView& b, const SolveRoute& route, const SolveOperands& op, hipStream_t stream,
+                               const RowsTail& tail) {
+  switch (route.family) {
+    case SolveFamily::kNone: return route.group == 0 ? hipSuccess : hipErrorInvalidValue;
+    case SolveFamily::kDuo:
+    case SolveFamily::kQuad: return route.group == 0 ? launch_solve_quad(b, route, op, stream, tail) : hipErrorInvalidValue;
+    case SolveFamily::kRows:
+    case SolveFamily::kRowsPipeline: return route.group == 0 ? launch_solve_rows(b, route, op, stream, tail) : hipErrorInvalidValue;
+    case SolveFamily::kTile: return launch_solve_tile(b, route, op, stream);
+    case SolveFamily::kLane: break;
   }
-  if (fused && rows_kernel_applies(b))
-    return launch_solve_rows(b, hints, d, mask, vals, seg_times, coeffs, status, cost, status_in, stream);
-  if (tile_kernel_applies(b, fused))
-    return launch_solve_tile(b, d, fused, mask, vals, seg_times, H, Ainv, coeffs, status, cost, status_in, stream);
-  // (the one-lane-per-path solve from materialised blocks -- 512 registers and 264 bytes of scratch per lane -- is gone: a
-  // blocks solve of a batch the tile kernel does not take runs four lanes per path whatever its size)
   // (the parentheses are part of the names these launches have always noted)
-  const bool split = use_split_dims(b.n_paths) || !fused;
-  const auto linear = !split ? MRS_TG_KERNEL((solve_linear_kernel<4, true>))
-                      : fused ? MRS_TG_KERNEL((solve_linear_kernel<1, true>)) : MRS_TG_KERNEL((solve_linear_kernel<1, false>));
-  const dim3 grid(split ? cdiv((long long)b.n_paths * 4, 64) : cdiv(b.n_paths, 64));
-  MRS_TG_LAUNCH_TIMED(linear, grid, dim3(64), 0, stream, b, d, mask, vals, seg_times, H, Ainv, ws, coeffs, status, cost, status_in);
+  const auto linear = route.lanes_per_path == 1 ? MRS_TG_KERNEL((solve_linear_kernel<4, true>))
+                      : route.fused             ? MRS_TG_KERNEL((solve_linear_kernel<1, true>))
+                                                : MRS_TG_KERNEL((solve_linear_kernel<1, false>));
+  MRS_TG_LAUNCH_TIMED(linear, dim3(route.grid_x), dim3(route.threads), 0, stream, b, route.derivative, op.mask, op.vals, op.seg_times,
+                      op.H, op.Ainv, op.ws, op.coeffs, op.status, op.cost, op.status_in);
   return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 #include "mrs_tg_batch.hpp"
 #include "mrs_tg_hd.hpp"
 #include "mrs_tg_knobs.hpp"
+#include "mrs_tg_solve_route.hpp"
 #include "mrs_tg_transfer.hpp"
 
 struct mrs_tg_ctx;
@@ -67,10 +68,10 @@ template <class... Args>
 inline hipError_t set_max_dynamic_lds(const Kernel<Args...>& k, size_t bytes) {
   return hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
-// The dynamic LDS of a launch: a workgroup cannot have more than a compute unit's 160 KB (hipErrorInvalidValue, which the ABI
-// words for its caller), and more than the 64 KB a launch may ask for by default needs the kernel's limit raised first (a
-// driver call, so only then).  A launcher that returns early for an empty batch refuses an oversize need before it does.
-constexpr size_t kLdsPerWorkgroup = 160 * 1024, kLdsDefaultLimit = 64 * 1024;
+// The dynamic LDS of a launch (kLdsPerWorkgroup, kLdsDefaultLimit: mrs_tg_solve_route.hpp): a workgroup cannot have more than a
+// compute unit's 160 KB (hipErrorInvalidValue, which the ABI words for its caller), and more than the 64 KB a launch may ask for
+// by default needs the kernel's limit raised first (a driver call, so only then).  A launcher that returns early for an empty
+// batch refuses an oversize need before it does.
 template <class... Args>
 inline hipError_t prepare_dynamic_lds(const Kernel<Args...>& k, size_t bytes) {
   if (bytes > kLdsPerWorkgroup) return hipErrorInvalidValue;
@@ -117,10 +118,6 @@ int solve_batch_samples_only(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* se
 // (BatchView, the device-resident structure of a batch: mrs_tg_batch.hpp)
 hipError_t launch_assemble(const BatchView& b, int d, const double* seg_times, double* H, double* Ainv,
                            hipStream_t stream);
-hipError_t launch_solve_linear(const BatchView& b, const RouteHints& hints, int d, bool fused, const uint8_t* mask,
-                               const double* vals, const double* seg_times, const double* H, const double* Ainv, double* ws,
-                               double* coeffs, int32_t* status, double* cost, const int32_t* status_in,
-                               hipStream_t stream, const double* pos_wp = nullptr);
 // (CopyList, up to kCopyMax flat copies in ONE launch: mrs_tg_transfer.hpp)
 hipError_t launch_copy_many(const CopyList& cl, hipStream_t stream);
 // samples [n_paths][capacity][4]: only the min(n_samples[p], capacity) rows a path has produced are copied (a sample buffer
@@ -290,12 +287,6 @@ hipError_t launch_travel_heading(int n_paths, const double* samples, const int32
 hipError_t launch_travel_heading_vjp(int n_paths, const double* samples, const int32_t* n_samples, int capacity,
                                      const int32_t* status, double min_step, const double* grad_out, double* grad_samples,
                                      hipStream_t stream);
-// phase-split tile kernel (mrs_tg_tile.hip): small and medium batches whose per-path state fits in LDS
-bool tile_kernel_applies(const BatchView& b, bool fused);
-hipError_t launch_solve_tile(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,
-                             const double* seg_times, const double* H, const double* Ainv, double* coeffs,
-                             int32_t* status, double* cost, const int32_t* status_in, hipStream_t stream);
-
 // What the rows kernel can do around its solve for the same path, in the same launch:
 //   before: the feasibility scaling of the segment times (scaleSegmentTimesWithViolation's T_i <- s_i T_i from the
 //           per-segment maxima, written back to seg_times) -- the last stage before the final solve of the Mellinger pipeline;
@@ -336,18 +327,6 @@ struct AccPin {
 hipError_t sample_acc_table(double dt, int capacity, hipStream_t stream, const double** table_out, int* n_out, AccPin* pin);
 void sample_tables_release();  // frees every table (with the last context of the process)
 
-// one lane per unknown, no materialised blocks (mrs_tg_rows.hip): the fused linear solve of every path that fits its LDS record
-bool rows_kernel_applies(const BatchView& b, bool with_sampling = false);
-// sampling on the solve's launch pays while a wavefront holds one path (small batches: one launch and one staging pass
-// less, 1024 x 10 nonlinear 138 -> 132 us); with two paths per wavefront the walks of the two run one after the other and
-// the separate sampler (one wavefront per path) is faster (8192 x 10: 483 vs 548 us)
-bool rows_tail_sampling_pays(const BatchView& b);
-// solve -> maxima -> scaling -> solve -> sampling of a pipeline in one launch of the rows kernel (small batches)
-bool rows_pipeline_applies(const BatchView& b);
-hipError_t launch_solve_rows(const BatchView& b, const RouteHints& hints, int d, const uint8_t* mask, const double* vals,
-                             const double* seg_times, double* coeffs, int32_t* status, double* cost, const int32_t* status_in,
-                             hipStream_t stream, const RowsTail& tail = RowsTail());
-
 // up to kRowsGroupMax batches of one plan solved by one launch (fixed-times default solve): per batch its arrays
 constexpr int kRowsGroupMax = 16;
 struct RowsGroup {
@@ -360,17 +339,48 @@ struct RowsGroup {
   const double* pos_wp[kRowsGroupMax];  // per batch: waypoints under MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS, else nullptr
   int n = 0;
 };
-hipError_t launch_solve_rows_group(const BatchView& b, int d, const RowsGroup& g, hipStream_t stream);
 
-// four lanes per path, factors in LDS (mrs_tg_quad.hip): the fixed-times solve of launches that carry more paths than the rows
-// kernel has wavefront slots for (paths_in_launch: of all batches a grouped launch carries).  ws: the plan's global factor
-// store (linear_workspace_doubles per batch), used by wavefronts whose paths need the general masked step.  tail: the
-// feasibility scaling of a Mellinger pipeline's last solve (no sampling on this launch).
-bool quad_kernel_applies(const BatchView& b, long long paths_in_launch, bool with_sampling);
-hipError_t launch_solve_quad(const BatchView& b, const RouteHints& hints, int d, const uint8_t* mask, const double* vals,
-                             const double* seg_times, double* coeffs, int32_t* status, double* cost, const int32_t* status_in,
-                             double* ws, hipStream_t stream, const RowsTail& tail = RowsTail());
-hipError_t launch_solve_quad_group(const BatchView& b, const RouteHints& hints, int d, const RowsGroup& g, double* ws,
-                                   hipStream_t stream);
+// ---- the fixed-times solve: route first (route_solve, mrs_tg_solve_route.hpp), then a launcher that enqueues what the route says ----
+// the operands of a solve, as the kernels take them (device addresses; the optional ones may be null)
+struct SolveOperands {
+  const uint8_t* mask = nullptr;      // [n_vertices][5]
+  const double* vals = nullptr;       // [n_vertices][5][4]
+  const double* seg_times = nullptr;  // [n_segments]
+  const double* H = nullptr;          // the materialised blocks (a solve that is not fused)
+  const double* Ainv = nullptr;
+  double* ws = nullptr;               // the global factor store (linear_workspace_doubles): the four- and eight-lane kernels' general
+                                      // step, the lane kernel's back substitution
+  double* coeffs = nullptr;           // [n_segments][4][10]
+  int32_t* status = nullptr;          // [n_paths], optional
+  double* cost = nullptr;             // [n_paths], optional
+  const int32_t* status_in = nullptr; // [n_paths], optional: the search's status, merged into status
+  const double* pos_wp = nullptr;     // MRS_TG_FLAG_POSITIONS_ARE_WAYPOINTS: the compact [vertex][4] array (SolveRequest::waypoints)
+};
+// the request of a library call: the hints, the factor store and waypoints as the operands have them, and the compute units
+// duo_pays has always counted (of the first device that asked, for the whole process)
+int solve_compute_units();
+inline SolveRequest solve_request(int d, bool fused, const RouteHints& hints, const SolveOperands& op) {
+  SolveRequest q;
+  q.derivative = d;
+  q.fused = fused;
+  q.factor_store = op.ws != nullptr;
+  q.waypoints = op.pos_wp != nullptr;
+  q.hints = hints;
+  q.compute_units = solve_compute_units();
+  return q;
+}
+// Enqueues the single launch `route` describes (its family's launcher below); tail: what rides on the launch -- the route says
+// which of it the launch takes (scales, maxima_in_launch, sampling).  A grouped route goes to the group launchers.
+hipError_t launch_solve_linear(const BatchView& b, const SolveRoute& route, const SolveOperands& op, hipStream_t stream,
+                               const RowsTail& tail = RowsTail());
+hipError_t launch_solve_tile(const BatchView& b, const SolveRoute& route, const SolveOperands& op, hipStream_t stream);
+hipError_t launch_solve_rows(const BatchView& b, const SolveRoute& route, const SolveOperands& op, hipStream_t stream,
+                             const RowsTail& tail = RowsTail());
+hipError_t launch_solve_quad(const BatchView& b, const SolveRoute& route, const SolveOperands& op, hipStream_t stream,
+                             const RowsTail& tail = RowsTail());
+// grouped (route.group batches of one plan): g.n must be the route's group.  ws: the plan's factor store, one
+// linear_workspace_doubles per batch, for the wavefronts of the four- and eight-lane kernels that take the general masked step
+hipError_t launch_solve_rows_group(const BatchView& b, const SolveRoute& route, const RowsGroup& g, hipStream_t stream);
+hipError_t launch_solve_quad_group(const BatchView& b, const SolveRoute& route, const RowsGroup& g, double* ws, hipStream_t stream);
 
 }  // namespace mrs_tg

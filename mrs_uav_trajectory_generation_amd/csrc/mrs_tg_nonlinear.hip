@@ -2079,7 +2079,7 @@ struct OuterLaunch {
   size_t lds_bytes = 0;
 };
 
-// what follows the outer loop
+// what follows the outer loop: a reading of the closing solves' routes (NonlinearRoute::first_solve, final_solve)
 enum class Closing {
   kRowsPipeline,  // solve -> maxima -> scaling -> solve (-> sampling) in one launch of the rows kernel
   kQuadTail,      // solve, maxima, then the scaling on the quad kernel's final solve (the caller's sampler follows)
@@ -2103,8 +2103,16 @@ struct NonlinearRoute {
   bool careful = false;             // 1c. the careful re-run follows
   bool general = false;             // 1d. the outer loop of the paths with a position-free vertex follows (and their solves below)
   bool certified_maxima = true;     // segment_maxima_scaling_kernel, else every entry searched (segment_maxima9_kernel)
-  Closing closing = Closing::kSeparate;
-  bool tail_samples = false;        // the sampling rides on the closing launch
+  // the closing solves, routed as every fixed-times solve is (route_solve): the trajectory of the last evaluated point (not
+  // launched where the final solve takes the maxima into its own launch), and the solve at the scaled times
+  SolveRoute first_solve, final_solve;
+  Closing closing() const {
+    return final_solve.maxima_in_launch           ? Closing::kRowsPipeline
+           : !final_solve.scales                  ? Closing::kSeparate
+           : uses_factor_store(final_solve)       ? Closing::kQuadTail
+                                                  : Closing::kRowsTail;
+  }
+  bool tail_samples() const { return final_solve.sampling; }  // the sampling rides on the closing launch
 };
 
 // the kernel's table of `bins`; returns the largest lds_of(bin) and leaves the workgroup count in *blocks
@@ -2126,11 +2134,13 @@ static size_t fill_bin_table(BinTable& bt, const std::vector<NonlinearBin>& bins
   return lds;
 }
 
-// constrained_slots, moving_starts: the call's hints (RouteHints, launch_nonlinear's argument); compute_units: of the current device
-// (device_compute_units); estimate: the search starts from the estimate; samples_wanted: the caller asked for samples
-static NonlinearRoute route_nonlinear(const NonlinearPlan& nl, const BatchView& b, int derivative, bool constrained_slots,
-                                      bool moving_starts, int compute_units, bool estimate, bool general, bool careful,
-                                      bool samples_wanted) {
+// hints: the call's (RouteHints, launch_nonlinear's argument); compute_units: of the current device (device_compute_units);
+// closing: the request of the closing solves as solve_request fills it (objective order, hints, factor store, waypoints and the
+// compute units the solve routes by); estimate: the search starts from the estimate; samples_wanted: the caller asked for samples
+static NonlinearRoute route_nonlinear(const NonlinearPlan& nl, const BatchView& b, const RouteHints& hints, int compute_units,
+                                      const SolveRequest& closing, bool estimate, bool general, bool careful, bool samples_wanted) {
+  const int derivative = closing.derivative;
+  const bool constrained_slots = hints.constrained_slots, moving_starts = hints.moving_starts;
   NonlinearRoute r;
   r.general = general;
   r.careful = careful;
@@ -2242,18 +2252,15 @@ static NonlinearRoute route_nonlinear(const NonlinearPlan& nl, const BatchView& 
   r.certified_maxima = knob::maxima_bounds();  // MRS_TG_MAXIMA_BOUNDS=0: every entry searched
   // 2-4 in one launch for the small batches whose wavefronts hold one path (solve_rows_pipeline_kernel, mrs_tg_rows.hip); else
   // 3b + 4 in one launch where the quad kernel (saturated device; the caller's sampler follows) or the rows kernel applies:
-  // its staging pass scales the times of its own path, the rows kernel's tail samples
-  const bool quad = quad_kernel_applies(b, b.n_paths, false);
-  const bool rows_samples = samples_wanted && rows_tail_sampling_pays(b);
-  if (!general && !quad && rows_pipeline_applies(b)) {
-    r.closing = Closing::kRowsPipeline;
-    r.tail_samples = samples_wanted;
-  } else if (!general && quad) {
-    r.closing = Closing::kQuadTail;
-  } else if (!general && rows_kernel_applies(b, rows_samples)) {
-    r.closing = Closing::kRowsTail;
-    r.tail_samples = rows_samples;
-  }
+  // its staging pass scales the times of its own path, the rows kernel's tail samples.  Paths with a position-free vertex:
+  // every stage a launch of its own, the final solve without the waypoints
+  r.first_solve = route_solve(b, closing);
+  SolveRequest final_request = closing;
+  final_request.stage = SolveStage::kClosing;
+  final_request.maxima_in_launch = final_request.scale_from_maxima = !general;
+  final_request.sampling = samples_wanted && !general;
+  final_request.waypoints = closing.waypoints && !general;
+  r.final_solve = route_solve(b, final_request);
   return r;
 }
 
@@ -2266,8 +2273,15 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const RouteHi
   hipError_t e = nonlinear_ensure_buffers(nl, b);
   if (e != hipSuccess) return e;
   const bool careful = prm_in.careful_cap != 0;  // the caller asked for the careful re-run (MRS_TG_FLAG_CAREFUL_COST)
+  SolveOperands op;  // of the closing solves
+  op.mask = mask;
+  op.vals = vals;
+  op.seg_times = seg_times;
+  op.ws = nl.d_ws.get();
+  op.coeffs = coeffs;
+  op.pos_wp = prm_in.pos_wp;
   const NonlinearRoute route =
-      route_nonlinear(nl, b, prm_in.derivative, hints.constrained_slots, hints.moving_starts, device_compute_units(),
+      route_nonlinear(nl, b, hints, device_compute_units(), solve_request(prm_in.derivative, true, hints, op),
                       prm_in.estimate_wp != nullptr, general, careful, sampling_dt > 0.0 && n_samples != nullptr);
   if (prm_in.estimate_wp && !route.estimate_in_kernel &&
       (e = launch_estimate_times(b, prm_in.estimate_wp, prm_in.estimate_limits, seg_times, stream)) != hipSuccess)
@@ -2376,32 +2390,34 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const RouteHi
       }
     }
   }
-  // the RowsTail of the closing launch: the feasibility scaling in front of its solve, the sampling behind it
-  auto closing_tail = [&]() {
-    RowsTail tail;
+  // the final solve's operands, and the RowsTail of a closing launch: the feasibility scaling in front of its solve, the
+  // sampling behind it
+  SolveOperands final_op = op;
+  final_op.status = status;
+  final_op.cost = cost;
+  final_op.status_in = nl.d_opt_status.get();
+  if (!route.final_solve.wp) final_op.pos_wp = nullptr;
+  const Closing closing = route.closing();
+  RowsTail tail;
+  if (closing != Closing::kSeparate) {
     tail.limits = limits;
     tail.opt_status = nl.d_opt_status.get();
     tail.sum_t0 = prm.reference_status ? nullptr : nl.d_sum_t0.get();  // (no runaway test: MRS_TG_FLAG_REFERENCE_STATUS)
     tail.seg_times_out = seg_times;
-    if (route.tail_samples) {
+    if (route.tail_samples()) {
       tail.sampling_dt = sampling_dt;
       tail.sample_capacity = sample_capacity;
       tail.n_samples = n_samples;
       tail.samples = samples;
       if (sampled_out) *sampled_out = true;
     }
-    return tail;
-  };
-  if (route.closing == Closing::kRowsPipeline) {
-    RowsTail tail = closing_tail();
+  }
+  if (closing == Closing::kRowsPipeline) {
     tail.maxima_in_launch = true;
-    return launch_solve_rows(b, hints, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status.get(), stream,
-                             tail);
+    return launch_solve_linear(b, route.final_solve, final_op, stream, tail);
   }
   // 2. trajectory of the last evaluated point (scaleSegmentTimesWithViolation works on poly_opt_'s state)
-  if ((e = launch_solve_linear(b, hints, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs,
-                               nullptr, nullptr, nullptr, stream, prm.pos_wp)) != hipSuccess)
-    return e;
+  if ((e = launch_solve_linear(b, route.first_solve, op, stream)) != hipSuccess) return e;
   if (general && (e = launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws.get(), coeffs,
                                            nullptr, nullptr, stream, general_flag, nullptr)) != hipSuccess)
     return e;
@@ -2414,18 +2430,9 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const RouteHi
                        coeffs, seg_times, nl.d_maxima.get());
   if ((e = hipGetLastError()) != hipSuccess) return e;
   // 3b + 4 in one launch
-  if (route.closing == Closing::kQuadTail) {
-    RowsTail tail = closing_tail();
+  if (closing != Closing::kSeparate) {
     tail.maxima = nl.d_maxima.get();
-    tail.pos_wp = prm.pos_wp;
-    return launch_solve_quad(b, hints, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status.get(),
-                             nl.d_ws.get(), stream, tail);
-  }
-  if (route.closing == Closing::kRowsTail) {
-    RowsTail tail = closing_tail();
-    tail.maxima = nl.d_maxima.get();
-    return launch_solve_rows(b, hints, prm.derivative, mask, vals, seg_times, coeffs, status, cost, nl.d_opt_status.get(), stream,
-                             tail);
+    return launch_solve_linear(b, route.final_solve, final_op, stream, tail);
   }
   MRS_TG_LAUNCH(apply_scaling_kernel, dim3(cdiv(b.n_segments, 256)), dim3(256), 0, stream, b, nl.d_maxima.get(), limits,
                      nl.d_opt_status.get(), seg_times);
@@ -2436,9 +2443,7 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const RouteHi
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   // 4. updateSegmentTimes + solveLinear with the scaled times (nonlinear_impl.h:405-408), final status
-  if ((e = launch_solve_linear(b, hints, prm.derivative, true, mask, vals, seg_times, nullptr, nullptr, nl.d_ws.get(), coeffs,
-                               status, cost, nl.d_opt_status.get(), stream)) != hipSuccess)
-    return e;
+  if ((e = launch_solve_linear(b, route.final_solve, final_op, stream)) != hipSuccess) return e;
   if (general)
     return launch_solve_general(b, prm.derivative, mask, vals, seg_times, nl.d_general_solve_ws.get(), coeffs, status, cost, stream,
                                 general_flag, nl.d_opt_status.get());

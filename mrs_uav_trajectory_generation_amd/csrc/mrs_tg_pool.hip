@@ -145,6 +145,14 @@ int device_compute_units() {
 
 // ---- dry run (mrs_tg_plan_explain): per thread, like the timer
 static thread_local bool t_dry_run = false;
+// (of the FIRST device that routes a solve, for the whole process: the two-sided kernel's threshold is a tuning figure, results
+// do not depend on it; a process that drives devices of different sizes routes as it always has -- changing that is for
+// another day)
+int solve_compute_units() {
+  static const int cus = device_compute_units();
+  return cus;
+}
+
 bool dry_run() { return t_dry_run; }
 void set_dry_run(bool on) { t_dry_run = on; }
 

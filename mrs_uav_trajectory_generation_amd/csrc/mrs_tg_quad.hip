@@ -57,18 +57,12 @@
 
 namespace mrs_tg {
 
-constexpr int kQdPaths = 16;  // paths per wavefront
+// (kQdPaths, 16 paths per wavefront; the record's size kQdRec; quad_lds_doubles: mrs_tg_solve_route.hpp)
 // LDS record of (vertex, path): L off-diagonal [6] | 1 / diag L [4] | z [4 rows][4 dimensions].  W = L^-1 E is NOT kept: the
 // back substitution forms W x_{v+1} as L^-1 (E x_{v+1}) from the segment's time again (~25 instructions more per vertex,
 // 16 doubles less per record: five wavefronts per CU instead of three at 10 segments)
-constexpr int kQdL = 0, kQdLinv = 6, kQdZ = 10, kQdRec = 26;
-
-// ends: records for the two end vertices as well (solve_quad_body<WP, true>: end vertices with free slots are eliminated)
-__host__ __device__ constexpr size_t quad_lds_doubles(int Smax, bool ends = false) {
-  return (size_t)(ends ? Smax + 1 : (Smax > 1 ? Smax - 1 : 1)) * kQdRec * kQdPaths + (size_t)Smax * kQdPaths  // records | times
-         + (ends ? (size_t)(Smax + 1) * 2 : 0)  // ends: the free mask of every (vertex, path), one byte each
-      ;
-}
+constexpr int kQdL = 0, kQdLinv = 6, kQdZ = 10;
+static_assert(kQdZ + 4 * kD == kQdRec, "the record fills its size");
 
 // T^(m + 1 - 2d), m = 0..8, the objective order as select masks (no branch tree per segment)
 __device__ __forceinline__ void quad_powers(double T, bool d1, bool d2, bool d4, double (&p2)[9]) {
@@ -629,17 +623,7 @@ __device__ __forceinline__ void solve_quad_body(const BatchView& b, int d, const
 // kernel": loads and stores share one in-order counter on gfx950, so a load or a scratch reload in the loops waits for the
 // coefficient stores in flight).  Min-snap only (the launchers send nothing else).  Paths of up to 24 segments:
 // the routing's only length rule is quad_kernel_applies, the four-lane record store within kQuadLdsBudget.
-constexpr int kDuoPaths = 8;  // paths per wavefront
-
-// the coefficient exchange of a uniform wavefront (solve_duo_body's backward loop): one chunk of 4 dimensions x 10 coefficients
-// per (path, side); the last of the sixteen chunks has a place of its own behind the path indices, the others lie in record rows
-constexpr int kDuoXchgChunk = kD * kN;  // doubles
-
-__host__ __device__ constexpr size_t duo_lds_doubles(int Smax) {
-  return (size_t)(Smax > 1 ? Smax - 1 : 1) * kQdRec * kDuoPaths + (size_t)Smax * kDuoPaths +  // records | times
-         (size_t)(Smax + 1) * kD * kDuoPaths + kDuoPaths / 2 +                                  // | position constraints | path indices
-         kDuoXchgChunk;                                                                         // | the sixteenth exchange chunk
-}
+// (kDuoPaths, 8 paths per wavefront; kDuoXchgChunk, the chunk of the coefficient exchange; duo_lds_doubles: mrs_tg_solve_route.hpp)
 // The chunk's 320 bytes change neither residency nor routing: the headline's 10 segments stay at eight wavefronts per CU (two per
 // SIMD) within the CU's 160 KB, and at every length the four-lane kernel's record store -- the routing's only length rule,
 // quad_kernel_applies -- is the larger of the two, so whatever that rule admits (24 segments today) fits kQuadLdsBudget here too.
@@ -1402,103 +1386,52 @@ __global__ __launch_bounds__(64, MRS_TG_QUAD_GROUP_WAVES) void solve_quad_group_
 }
 
 // ---------------------------------------------------------------------------------------------
-// launcher
+// launchers: what the route says (route_solve, mrs_tg_solve_route.hpp), enqueued
 
-static constexpr size_t kQuadLdsBudget = 80 * 1024;  // at least two wavefronts per CU
 static_assert(duo_lds_doubles(24) * sizeof(double) <= kQuadLdsBudget, "the two-sided kernel at the longest routed length");
 
-// The two-sided kernel takes a launch whose quad wavefronts (16 paths each) would leave SIMDs idle or barely covered: fewer than
-// 1.25 per SIMD.  MRS_TG_DUO=0: never, =1: whenever the pattern allows (tuning / test knob).
-static bool duo_pays(long long paths_in_launch) {
-  if (const int forced = knob::duo_forced(); forced >= 0) return forced != 0;  // (read at every call: tests run both kernels)
-  // (of the FIRST device used, for the whole process: the threshold is a tuning figure, results do not depend on it; a
-  // process that drives devices of different sizes routes as it always has -- changing that is for another day)
-  static const int cus = device_compute_units();
-  return (paths_in_launch + kQdPaths - 1) / kQdPaths < (long long)cus * 4 * 5 / 4;
-}
-
-// the two-sided kernels' `uniform_loops` argument: bit 0 MRS_TG_DUO_UNIFORM, bit 1 MRS_TG_DUO_STORE_THROUGH (the grouped kernel
-// alone looks at it); both read at every call
-static int duo_loop_bits() { return (knob::duo_uniform() ? 1 : 0) | (knob::duo_store_through() ? 2 : 0); }
-
-bool quad_kernel_applies(const BatchView& b, long long paths_in_launch, bool with_sampling) {
-  if (b.n_paths == 0 || with_sampling) return false;
-  if (paths_in_launch < knob::quad_min_paths()) return false;
-  return quad_lds_doubles(b.max_segments) * sizeof(double) <= kQuadLdsBudget;
-}
-
-hipError_t launch_solve_quad(const BatchView& b, const RouteHints& hints, int d, const uint8_t* mask, const double* vals,
-                             const double* seg_times, double* coeffs, int32_t* status, double* cost, const int32_t* status_in,
-                             double* ws, hipStream_t stream, const RowsTail& tail) {
-  // objective orders below snap leave jerk and / or snap free at the end vertices of a rest-to-rest path: the instantiation
-  // that eliminates such end vertices (two more records per path in LDS), while its LDS fits; MRS_TG_QUAD_ENDS=0: the general
-  // step for those paths, as until round 5
-  const bool ends = knob::quad_ends() && (d < 4 || hints.constrained_slots) &&
-                    quad_lds_doubles(b.max_segments, true) * sizeof(double) <= kQuadLdsBudget;
-  const bool wp = tail.pos_wp != nullptr;
-  if (!ends && !(d < 4) && duo_pays(b.n_paths)) {  // few wavefronts: eight lanes per path, the chain cut in the middle
-    const size_t lds_duo = duo_lds_doubles(b.max_segments) * sizeof(double);
-    const auto duo = wp ? MRS_TG_KERNEL(solve_duo_kernel<true>) : MRS_TG_KERNEL(solve_duo_kernel<false>);
-    if (lds_duo > 64 * 1024) {
-      hipError_t e = set_max_dynamic_lds(duo, kQuadLdsBudget);
-      if (e != hipSuccess) return e;
-    }
-    const unsigned grid_duo = (unsigned)((b.n_paths + kDuoPaths - 1) / kDuoPaths);
-    MRS_TG_LAUNCH_TIMED(duo, dim3(grid_duo), dim3(64), lds_duo, stream, b, d, mask, vals, seg_times, coeffs, status, cost, status_in,
-                        ws, tail, duo_loop_bits());
+hipError_t launch_solve_quad(const BatchView& b, const SolveRoute& route, const SolveOperands& op, hipStream_t stream,
+                             const RowsTail& tail) {
+  RowsTail tail_k = tail;
+  tail_k.pos_wp = op.pos_wp;
+  if (route.family == SolveFamily::kDuo) {  // few wavefronts: eight lanes per path, the chain cut in the middle
+    const auto duo = route.wp ? MRS_TG_KERNEL(solve_duo_kernel<true>) : MRS_TG_KERNEL(solve_duo_kernel<false>);
+    if (route.raise_lds_to)
+      if (hipError_t e = set_max_dynamic_lds(duo, route.raise_lds_to); e != hipSuccess) return e;
+    MRS_TG_LAUNCH_TIMED(duo, dim3(route.grid_x), dim3(route.threads), route.lds_bytes, stream, b, route.derivative, op.mask, op.vals,
+                        op.seg_times, op.coeffs, op.status, op.cost, op.status_in, op.ws, tail_k, route.loop_bits);
     return hipGetLastError();
   }
-  const size_t lds_bytes = quad_lds_doubles(b.max_segments, ends) * sizeof(double);
-  const auto quad = ends ? (wp ? MRS_TG_KERNEL(solve_quad_kernel<true, true>) : MRS_TG_KERNEL(solve_quad_kernel<false, true>))
-                         : (wp ? MRS_TG_KERNEL(solve_quad_kernel<true>) : MRS_TG_KERNEL(solve_quad_kernel<false>));
-  if (lds_bytes > 64 * 1024) {
-    hipError_t e = set_max_dynamic_lds(quad, kQuadLdsBudget);
-    if (e != hipSuccess) return e;
-  }
-  const unsigned grid = (unsigned)((b.n_paths + kQdPaths - 1) / kQdPaths);
-  MRS_TG_LAUNCH_TIMED(quad, dim3(grid), dim3(64), lds_bytes, stream, b, d, mask, vals, seg_times, coeffs, status, cost, status_in, ws,
-                      tail);
+  const auto quad = route.ends ? (route.wp ? MRS_TG_KERNEL(solve_quad_kernel<true, true>) : MRS_TG_KERNEL(solve_quad_kernel<false, true>))
+                               : (route.wp ? MRS_TG_KERNEL(solve_quad_kernel<true>) : MRS_TG_KERNEL(solve_quad_kernel<false>));
+  if (route.raise_lds_to)
+    if (hipError_t e = set_max_dynamic_lds(quad, route.raise_lds_to); e != hipSuccess) return e;
+  MRS_TG_LAUNCH_TIMED(quad, dim3(route.grid_x), dim3(route.threads), route.lds_bytes, stream, b, route.derivative, op.mask, op.vals,
+                      op.seg_times, op.coeffs, op.status, op.cost, op.status_in, op.ws, tail_k);
   return hipGetLastError();
 }
 
-hipError_t launch_solve_quad_group(const BatchView& b, const RouteHints& hints, int d, const RowsGroup& g, double* ws,
-                                   hipStream_t stream) {
-  if (g.n < 1 || g.n > kRowsGroupMax) return hipErrorInvalidValue;
-  const bool ends = knob::quad_ends() && (d < 4 || hints.constrained_slots) &&
-                    quad_lds_doubles(b.max_segments, true) * sizeof(double) <= kQuadLdsBudget;
-  const size_t lds_bytes = quad_lds_doubles(b.max_segments, ends) * sizeof(double);
-  bool wp = true;
-  for (int j = 0; j < g.n; ++j) wp = wp && g.pos_wp[j] != nullptr;
-  if (!ends && !(d < 4) && duo_pays((long long)b.n_paths * g.n)) {
-    const size_t lds_duo = duo_lds_doubles(b.max_segments) * sizeof(double);
-    // the lean instantiation (solve_duo_body, LEAN): whole-uniform batches of an even length from 4 on, every wavefront full,
-    // both loop knobs on.  Its name in the trace is the family's -- an interface -- unless MRS_TG_TRACE_INSTANTIATIONS asks
-    const int loop_bits = duo_loop_bits();
-    const bool lean = b.uniform_S >= 4 && b.uniform_S % 2 == 0 && b.n_paths % kDuoPaths == 0 && loop_bits == 3 && knob::duo_lean();
-    const bool spell = lean && knob::trace_instantiations();
-    const auto duo = lean ? (wp ? kernel_as(solve_duo_group_kernel<true, true>, spell ? "solve_duo_group_kernel<true, true>" : "solve_duo_group_kernel<true>")
-                                : kernel_as(solve_duo_group_kernel<false, true>, spell ? "solve_duo_group_kernel<false, true>" : "solve_duo_group_kernel<false>"))
-                          : (wp ? MRS_TG_KERNEL(solve_duo_group_kernel<true>) : MRS_TG_KERNEL(solve_duo_group_kernel<false>));
-    if (lds_duo > 64 * 1024) {
-      hipError_t e = set_max_dynamic_lds(duo, kQuadLdsBudget);
-      if (e != hipSuccess) return e;
-    }
-    const int per_batch_duo = (b.n_paths + kDuoPaths - 1) / kDuoPaths;
-    const dim3 grid_duo((unsigned)per_batch_duo, (unsigned)g.n);  // (x: the batch's workgroups, y: the batch)
-    const size_t wsd_duo = linear_workspace_doubles(b);
-    MRS_TG_LAUNCH_TIMED(duo, grid_duo, dim3(64), lds_duo, stream, b, d, g, ws, wsd_duo, loop_bits);
+hipError_t launch_solve_quad_group(const BatchView& b, const SolveRoute& route, const RowsGroup& g, double* ws, hipStream_t stream) {
+  if (g.n < 1 || g.n > kRowsGroupMax || g.n != route.group || !uses_factor_store(route)) return hipErrorInvalidValue;
+  const size_t ws_batch_doubles = linear_workspace_doubles(b);
+  if (route.family == SolveFamily::kDuo) {
+    // The lean instantiation's name in the trace is the family's -- an interface -- unless MRS_TG_TRACE_INSTANTIATIONS asks
+    const bool spell = route.lean && knob::trace_instantiations();
+    const auto duo = route.lean ? (route.wp ? kernel_as(solve_duo_group_kernel<true, true>, spell ? "solve_duo_group_kernel<true, true>" : "solve_duo_group_kernel<true>")
+                                            : kernel_as(solve_duo_group_kernel<false, true>, spell ? "solve_duo_group_kernel<false, true>" : "solve_duo_group_kernel<false>"))
+                                : (route.wp ? MRS_TG_KERNEL(solve_duo_group_kernel<true>) : MRS_TG_KERNEL(solve_duo_group_kernel<false>));
+    if (route.raise_lds_to)
+      if (hipError_t e = set_max_dynamic_lds(duo, route.raise_lds_to); e != hipSuccess) return e;
+    MRS_TG_LAUNCH_TIMED(duo, dim3(route.grid_x, route.grid_y), dim3(route.threads), route.lds_bytes, stream, b, route.derivative, g, ws,
+                        ws_batch_doubles, route.loop_bits);
     return hipGetLastError();
   }
-  const auto quad = ends ? (wp ? MRS_TG_KERNEL(solve_quad_group_kernel<true, true>) : MRS_TG_KERNEL(solve_quad_group_kernel<false, true>))
-                         : (wp ? MRS_TG_KERNEL(solve_quad_group_kernel<true>) : MRS_TG_KERNEL(solve_quad_group_kernel<false>));
-  if (lds_bytes > 64 * 1024) {
-    hipError_t e = set_max_dynamic_lds(quad, kQuadLdsBudget);
-    if (e != hipSuccess) return e;
-  }
-  const int per_batch = (b.n_paths + kQdPaths - 1) / kQdPaths;
-  const dim3 grid((unsigned)(per_batch * g.n));
-  const size_t wsd = linear_workspace_doubles(b);
-  MRS_TG_LAUNCH_TIMED(quad, grid, dim3(64), lds_bytes, stream, b, d, g, ws, wsd, per_batch);
+  const auto quad = route.ends ? (route.wp ? MRS_TG_KERNEL(solve_quad_group_kernel<true, true>) : MRS_TG_KERNEL(solve_quad_group_kernel<false, true>))
+                               : (route.wp ? MRS_TG_KERNEL(solve_quad_group_kernel<true>) : MRS_TG_KERNEL(solve_quad_group_kernel<false>));
+  if (route.raise_lds_to)
+    if (hipError_t e = set_max_dynamic_lds(quad, route.raise_lds_to); e != hipSuccess) return e;
+  MRS_TG_LAUNCH_TIMED(quad, dim3(route.grid_x), dim3(route.threads), route.lds_bytes, stream, b, route.derivative, g, ws, ws_batch_doubles,
+                      route.blocks_per_batch);
   return hipGetLastError();
 }
 

@@ -41,13 +41,10 @@ namespace mrs_tg {
 //            | parking space for the four eliminated columns of a long path (12 each)
 //   segment: q[k] = T^(2 + k - 2d), k = 0..3 | T | pad | p_i - p_{i+1} per dimension
 //   cost   : one partial per (segment, dimension)
-constexpr int kRVtxDer = 0, kRVtxFree = 20, kRVtxX = 24, kRVtxPark = 40, kRVtxRec = 88;
-constexpr int kRSegPow = 0, kRSegT = 4, kRSegDp = 6, kRSegRec = 10;
-
-__host__ __device__ constexpr int rows_path_doubles(int S) {
-  const int base = (S + 1) * kRVtxRec + S * kRSegRec + S * kD;
-  return base + (base & 1) + 2;  // 16-byte aligned records, paths of a wavefront off each other's banks
-}
+// (the record sizes kRVtxRec, kRSegRec and a path's stride rows_path_doubles: mrs_tg_solve_route.hpp)
+constexpr int kRVtxDer = 0, kRVtxFree = 20, kRVtxX = 24, kRVtxPark = 40;
+constexpr int kRSegPow = 0, kRSegT = 4, kRSegDp = 6;
+static_assert(kRVtxPark + 4 * 12 == kRVtxRec && kRSegDp + kD == kRSegRec, "the records fill their sizes");
 
 // (LDS only: a fence over every address space also drains the global-memory counter -- s_waitcnt vmcnt(0) -- and the
 // wavefront then sits out the write latency of the coefficients it has just stored before it may add up its cost or sample)
@@ -681,95 +678,41 @@ __global__ __launch_bounds__(64, MRS_TG_ROWS_WAVES) void solve_rows_group_kernel
 }
 
 // ---------------------------------------------------------------------------------------------
-// launcher
+// launchers: what the route says (route_solve, mrs_tg_solve_route.hpp), enqueued
 
-static constexpr size_t kRowsLdsBudget = 144 * 1024;
-
-// LDS of one wavefront: the records of its paths, and for a launch that samples the times and coefficients of those paths
-// plus one sample buffer
-static size_t rows_lds_bytes(int Smax, int ppw, bool sampling, bool maxima = false) {
-  size_t doubles = (size_t)ppw * rows_path_doubles(Smax);
-  if (sampling || maxima) doubles += (size_t)ppw * (size_t)Smax * (kD * kN + 1) + kSampleBuffer + kSampleBuffer / 4 + 2;
-  if (maxima) doubles += (size_t)Smax * 9 + 10;  // + the path's nine limits
-  return doubles * sizeof(double);
-}
-
-bool rows_kernel_applies(const BatchView& b, bool with_sampling) {
-  if (b.n_paths == 0) return false;
-  if (!knob::rows_kernel()) return false;  // MRS_TG_ROWS_KERNEL=0 falls back to the tile and lane kernels
-  return rows_lds_bytes(b.max_segments, 1, with_sampling) <= kRowsLdsBudget;
-}
-
-bool rows_tail_sampling_pays(const BatchView& b) { return b.n_paths <= 2048 && rows_kernel_applies(b, true); }
-
-bool rows_pipeline_applies(const BatchView& b) {
-  // up to one solving wavefront per SIMD (its helper shares the SIMD of another path's solver): 1024 x 10 pipeline 106.6 ->
-  // 101.0 us; at 2048 paths two solvers share every SIMD and the separate launches win (153 vs 169 us)
-  // (long paths: the separate launches again -- one 80-segment request 0.399 -> 0.379 ms, 64 x 80 0.706 -> 0.682, 48 / 49 segments
-  // on either side of a first threshold 0.182 / 0.176, equal at 30
-  // segments; the results are the same bits either way, tests/test_gpu_pipeline_shortcuts.py)
-  return knob::rows_pipeline() && b.n_paths > 0 && b.n_paths <= 1024 && b.max_segments <= 32 &&
-         rows_lds_bytes(b.max_segments, 1, true, true) <= kRowsLdsBudget;
-}
-
-hipError_t launch_solve_rows(const BatchView& b, const RouteHints& hints, int d, const uint8_t* mask, const double* vals,
-                             const double* seg_times, double* coeffs, int32_t* status, double* cost, const int32_t* status_in,
-                             hipStream_t stream, const RowsTail& tail) {
-  const bool sampling = tail.sampling_dt > 0.0;
+hipError_t launch_solve_rows(const BatchView& b, const SolveRoute& route, const SolveOperands& op, hipStream_t stream,
+                             const RowsTail& tail) {
   RowsTail tail_k = tail;  // (the copy the kernel gets: with the sampling walk's table filled in)
   AccPin pin;  // (released when this function returns: behind the enqueue of the kernel that reads the table)
-  if (sampling && !dry_run()) {
+  if (route.sampling && !dry_run()) {
     hipError_t et = sample_acc_table(tail.sampling_dt, tail.sample_capacity, stream, &tail_k.sample_acc, &tail_k.sample_acc_n, &pin);
     if (et != hipSuccess) return et;
   }
-  if (tail.maxima_in_launch) {
-    if (!tail.limits || !tail.opt_status || !tail.seg_times_out) return hipErrorInvalidValue;
-    const size_t lds_bytes = rows_lds_bytes(b.max_segments, 1, true, true);
-    if (lds_bytes > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)solve_rows_pipeline_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)kRowsLdsBudget);
-      if (e != hipSuccess) return e;
-    }
-    MRS_TG_LAUNCH_TIMED(solve_rows_pipeline_kernel, dim3((unsigned)b.n_paths), dim3(128), lds_bytes, stream, b, d, b.max_segments,
-                        mask, vals, seg_times, coeffs, status, cost, status_in, tail_k);
+  if (route.family == SolveFamily::kRowsPipeline) {
+    if (!tail.maxima_in_launch || !tail.limits || !tail.opt_status || !tail.seg_times_out) return hipErrorInvalidValue;
+    const auto pipeline = MRS_TG_KERNEL(solve_rows_pipeline_kernel);
+    if (route.raise_lds_to)
+      if (hipError_t e = set_max_dynamic_lds(pipeline, route.raise_lds_to); e != hipSuccess) return e;
+    MRS_TG_LAUNCH_TIMED(pipeline, dim3(route.grid_x), dim3(route.threads), route.lds_bytes, stream, b, route.derivative, b.max_segments,
+                        op.mask, op.vals, op.seg_times, op.coeffs, op.status, op.cost, op.status_in, tail_k);
     return hipGetLastError();
   }
-  // one path per wavefront while that still leaves SIMDs idle (256 CUs x 4); two paths per wavefront otherwise -- and
-  // when the caller says other batches share the device: at 255 VGPRs a SIMD holds two wavefronts, so 1024 one-path
-  // wavefronts per launch let two launches run side by side, 512 two-path wavefronts four (1024 x 10, four streams:
-  // 4.9 -> 4.1 us per step; alone on the device the two-path launch is 0.9 us slower)
-  int ppw = (b.n_paths <= 2048 && !(hints.shared_device && !sampling)) ? 1 : 2;
-  if (knob::rows_ppw()) ppw = knob::rows_ppw();  // MRS_TG_ROWS_PPW=1|2
-  if (rows_lds_bytes(b.max_segments, 2, sampling) > kRowsLdsBudget) ppw = 1;
-  const size_t lds_bytes = rows_lds_bytes(b.max_segments, ppw, sampling);
-  const bool with_tail = sampling || tail.maxima != nullptr;
-  const auto rows = with_tail ? MRS_TG_KERNEL(solve_rows_kernel<1>) : MRS_TG_KERNEL(solve_rows_kernel<0>);
-  if (lds_bytes > 64 * 1024) {  // beyond the default limit of a launch: raise it (a driver call, so only when needed)
-    hipError_t e = set_max_dynamic_lds(rows, kRowsLdsBudget);
-    if (e != hipSuccess) return e;
-  }
-  const unsigned grid = (unsigned)((b.n_paths + ppw - 1) / ppw);
+  const auto rows = route.with_tail ? MRS_TG_KERNEL(solve_rows_kernel<1>) : MRS_TG_KERNEL(solve_rows_kernel<0>);
+  if (route.raise_lds_to)  // beyond the default limit of a launch: raise it (a driver call, so only when needed)
+    if (hipError_t e = set_max_dynamic_lds(rows, route.raise_lds_to); e != hipSuccess) return e;
   // (tail_k is the caller's tail unless the launch samples)
-  MRS_TG_LAUNCH_TIMED(rows, dim3(grid), dim3(64), lds_bytes, stream, b, d, ppw, b.max_segments, mask, vals, seg_times, coeffs, status,
-                      cost, status_in, tail_k);
+  MRS_TG_LAUNCH_TIMED(rows, dim3(route.grid_x), dim3(route.threads), route.lds_bytes, stream, b, route.derivative, route.per_workgroup,
+                      b.max_segments, op.mask, op.vals, op.seg_times, op.coeffs, op.status, op.cost, op.status_in, tail_k);
   return hipGetLastError();
 }
 
-hipError_t launch_solve_rows_group(const BatchView& b, int d, const RowsGroup& g, hipStream_t stream) {
-  if (g.n < 1 || g.n > kRowsGroupMax) return hipErrorInvalidValue;
-  // two paths per wavefront as soon as the launch carries more than one small batch: a host that groups launches keeps
-  // several of them in flight (on alternating streams), and at 255 VGPRs a SIMD holds two wavefronts (launch_solve_rows)
-  int ppw = ((long long)b.n_paths * g.n <= 1024) ? 1 : 2;
-  if (knob::rows_ppw()) ppw = knob::rows_ppw();  // MRS_TG_ROWS_PPW=1|2
-  if (rows_lds_bytes(b.max_segments, 2, false) > kRowsLdsBudget) ppw = 1;
-  const size_t lds_bytes = rows_lds_bytes(b.max_segments, ppw, false);
-  if (lds_bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)solve_rows_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRowsLdsBudget);
-    if (e != hipSuccess) return e;
-  }
-  const int per_batch = (b.n_paths + ppw - 1) / ppw;
-  MRS_TG_LAUNCH_TIMED(solve_rows_group_kernel, dim3((unsigned)(per_batch * g.n)), dim3(64), lds_bytes, stream, b, d, ppw,
-                      b.max_segments, g, per_batch);
+hipError_t launch_solve_rows_group(const BatchView& b, const SolveRoute& route, const RowsGroup& g, hipStream_t stream) {
+  if (g.n < 1 || g.n > kRowsGroupMax || g.n != route.group || route.family != SolveFamily::kRows) return hipErrorInvalidValue;
+  const auto rows = MRS_TG_KERNEL(solve_rows_group_kernel);
+  if (route.raise_lds_to)
+    if (hipError_t e = set_max_dynamic_lds(rows, route.raise_lds_to); e != hipSuccess) return e;
+  MRS_TG_LAUNCH_TIMED(rows, dim3(route.grid_x), dim3(route.threads), route.lds_bytes, stream, b, route.derivative, route.per_workgroup,
+                      b.max_segments, g, route.blocks_per_batch);
   return hipGetLastError();
 }
 

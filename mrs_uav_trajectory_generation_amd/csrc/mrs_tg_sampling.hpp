@@ -15,8 +15,7 @@ namespace mrs_tg {
 // once, one lane per sample whatever its segment -- with the evaluation inside the chunk loop (one segment per chunk,
 // ~30 of 64 lanes busy, 40 broadcast LDS reads and the Horner chains in front of the next chunk's additions) the kernel
 // took 25 us for 1024 paths of ~300 samples; 1024 x 10 nonlinear 147 -> us.
-constexpr int kSampleBuffer = 192;  // samples parked per flush.  1024 made the LDS block of a 10-segment path 13.5 KB (11 wavefronts
-                                    // per CU); 192: 5.2 KB, 30 per CU -- 8192 x 10: 50 -> 40 us (scripts/tile_phases.hip), 1024 x 10 unchanged
+// (kSampleBuffer, the samples parked per flush: mrs_tg_solve_route.hpp, with the LDS footprints it is part of)
 
 // One wavefront (all 64 lanes, wave-uniform control flow).  s_T [S] segment times, s_c [S][4][10] coefficients, s_t / s_seg
 // the sample buffer (kSampleBuffer entries each); out: the path's [capacity][4] samples or nullptr (count only).

@@ -36,24 +36,11 @@ namespace mrs_tg {
 // adds of two terms each: commutative, so bit-reproducible); phase B reads them from the slots it then overwrites
 // with L and z.  (An earlier layout kept the four pieces in the segment records and summed them inside the serial
 // chain: 11.4 KB per path instead of 7.5 KB, one workgroup per CU instead of two at eight paths per tile.)
-constexpr int kSegRec = 16 + 4;            // coupling block EM (as its consumer reads it), qf[dim]
-constexpr int kVtxRec = 42 + 20 + 2 + 2;   // D[10] -> L[10] | W[16] | Y[4][4] -> z[4][4] | d[5][4] | free bits, flags | pad
+// (kSegRec, kVtxRec, kHandOver, the per-path stride tile_path_doubles and kTileThreads: mrs_tg_solve_route.hpp)
 // (the pad takes the record off a multiple of 16 doubles = the 32-bank period of ds_read2_b64 / ds_write: the two
 // directions of a path work on different vertices and met on the same banks at every access of phase B --
 // SQ_LDS_BANK_CONFLICT was 27 % of the kernel's LDS cycles, profiles/round1_pmc_sq_linear_step.csv)
-constexpr int kHandOver = 10 + 16;         // per path: the backward direction's Schur update for the middle vertex
 
-// Per-path LDS stride.  Both record sizes are multiples of 8 doubles, so the unpadded stride put every path of a
-// tile on the same banks ((a/4) mod 32 for ds_read2_b64 / ds_write*): the 16-lane groups of phase B (two paths x two
-// directions) then hit one bank with up to four distinct addresses.  A stride of 4 (mod 16) doubles shifts each
-// path by 8 banks.
-__host__ __device__ constexpr int tile_path_doubles(int S) {
-  const int base = S * kSegRec + (S + 1) * kVtxRec + kHandOver;
-  return base + ((4 - base % 16) + 16) % 16;
-}
-
-
-constexpr int kTileThreads = 256;
 constexpr int kTileWorkers = kTileThreads - 64;
 
 // Two workgroups per CU (eight wavefronts, two per SIMD) need <= 256 VGPRs.  The blocks variant sits just below that
@@ -561,40 +548,14 @@ __global__ __launch_bounds__(kTileThreads, 2) void solve_tile_kernel(BatchView b
 }
 
 // ---------------------------------------------------------------------------------------------
-// launcher: returns false when the tile kernel does not apply (caller falls back to the per-lane kernel)
+// launcher: what the route says (route_solve, mrs_tg_solve_route.hpp), enqueued
 
-static constexpr size_t kTileLdsBudget = 144 * 1024;
-
-bool tile_kernel_applies(const BatchView& b, bool fused) {
-  // measured, 10 segments, one batch in flight, us per linear step / nonlinear pipeline (tile vs lane kernels):
-  //   blocks: 8192 paths 61 vs 83, 32768 271 vs 385, 65536 516 vs 572;
-  //   fused:  4096 316 vs 343, 8192 513 vs 537, 16384 840 vs 886, 32768 1498 vs 1639, 65536 2861 vs 2872
-  // -- since the vertex-accumulator layout (two workgroups per CU at eight paths per tile) the tile kernel wins at
-  // every size tried on uniform batches.  Ragged batches (3..30 segments: every tile is sized and looped for the
-  // longest path of the batch) cross over earlier: blocks 4096 paths 130 vs 163, 8192 225 vs 234, 16384 478 vs 349;
-  // fused 2048 779 vs 857, 4096 744 vs 736, 8192 1070 vs 960 (scripts/ragged_tile_sweep.py).
-  const long long max_paths = knob::tile_max_paths((b.uniform_S > 0) ? (1ll << 40) : (fused ? 4096 : 8192));
-  if (b.n_paths == 0 || b.n_paths > max_paths) return false;
-  // 32-bit byte offsets into the block buffers (load_H_blocks32)
-  if (!fused && (unsigned long long)b.max_segments * 800ull * (unsigned long long)b.n_paths > 0xFFFFFFFFull) return false;
-  return (size_t)tile_path_doubles(b.max_segments) * sizeof(double) <= kTileLdsBudget;
-}
-
-hipError_t launch_solve_tile(const BatchView& b, int d, bool fused, const uint8_t* mask, const double* vals,
-                             const double* seg_times, const double* H, const double* Ainv, double* coeffs,
-                             int32_t* status, double* cost, const int32_t* status_in, hipStream_t stream) {
-  const size_t per_path = (size_t)tile_path_doubles(b.max_segments) * sizeof(double);
-  int TP = (int)(kTileLdsBudget / per_path);
-  if (TP > 8) TP = 8;  // phase B runs eight lanes per path inside wavefront 0
-  // more, smaller tiles so that every CU gets work (256 CUs) and several tiles share a CU
-  while (TP > 4 && (b.n_paths + TP - 1) / TP < 512) TP >>= 1;
-  const size_t lds_bytes = per_path * (size_t)TP;
-  const unsigned grid = (unsigned)((b.n_paths + TP - 1) / TP);
-  const auto tile = fused ? MRS_TG_KERNEL(solve_tile_kernel<true>) : MRS_TG_KERNEL(solve_tile_kernel<false>);
-  hipError_t e = set_max_dynamic_lds(tile, kTileLdsBudget);
-  if (e != hipSuccess) return e;
-  MRS_TG_LAUNCH_TIMED(tile, dim3(grid), dim3(kTileThreads), lds_bytes, stream, b, d, TP, b.max_segments, mask, vals, seg_times, H, Ainv,
-                      coeffs, status, cost, status_in);
+hipError_t launch_solve_tile(const BatchView& b, const SolveRoute& route, const SolveOperands& op, hipStream_t stream) {
+  const auto tile = route.fused ? MRS_TG_KERNEL(solve_tile_kernel<true>) : MRS_TG_KERNEL(solve_tile_kernel<false>);
+  if (route.per_workgroup < 1) return hipErrorInvalidValue;  // (a forced route of paths too long for a tile)
+  if (hipError_t e = set_max_dynamic_lds(tile, route.raise_lds_to); e != hipSuccess) return e;
+  MRS_TG_LAUNCH_TIMED(tile, dim3(route.grid_x), dim3(route.threads), route.lds_bytes, stream, b, route.derivative, route.per_workgroup,
+                      b.max_segments, op.mask, op.vals, op.seg_times, op.H, op.Ainv, op.coeffs, op.status, op.cost, op.status_in);
   return hipGetLastError();
 }
 

@@ -98,6 +98,19 @@ int main(int argc, char** argv) {
   tail.sample_capacity = cap;
   tail.n_samples = ns;
   tail.samples = samples;
+  // the rows kernel whatever the size rules say: the request forces the family
+  SolveRequest rows;
+  rows.derivative = d;
+  rows.force = SolveFamily::kRows;
+  SolveOperands op;
+  op.mask = dmask;
+  op.vals = dvals;
+  op.seg_times = Tw;
+  op.coeffs = coeffs;
+  SolveOperands op_final = op;
+  op_final.status = status;
+  op_final.cost = cost;
+  op_final.status_in = opt_status;
   const int n = 50;
   auto timed = [&](const char* what, auto&& body) {
     float total = 0;
@@ -116,16 +129,20 @@ int main(int argc, char** argv) {
   timed("separate launches (solve, maxima, solve with scaling + sampling)", [&] {
     RowsTail t2 = tail;
     t2.maxima = maxima;
-    CK(launch_solve_rows(b, RouteHints{}, d, dmask, dvals, Tw, coeffs, nullptr, nullptr, nullptr, st));
+    CK(launch_solve_rows(b, route_solve(b, rows), op, st));
     CK(launch_segment_maxima(b, coeffs, Tw, maxima, st));
-    CK(launch_solve_rows(b, RouteHints{}, d, dmask, dvals, Tw, coeffs, status, cost, opt_status, st, t2));
+    SolveRequest scaled = rows;
+    scaled.scale_from_maxima = scaled.sampling = true;
+    CK(launch_solve_rows(b, route_solve(b, scaled), op_final, st, t2));
   });
   std::vector<double> c_sep((size_t)P * S * 40), c_one((size_t)P * S * 40);
   CK(hipMemcpy(c_sep.data(), coeffs, c_sep.size() * 8, hipMemcpyDeviceToHost));
   timed("one launch", [&] {
     RowsTail t2 = tail;
     t2.maxima_in_launch = true;
-    CK(launch_solve_rows(b, RouteHints{}, d, dmask, dvals, Tw, coeffs, status, cost, opt_status, st, t2));
+    SolveRequest one = rows;
+    one.maxima_in_launch = one.sampling = true;
+    CK(launch_solve_rows(b, route_solve(b, one), op_final, st, t2));
   });
   CK(hipMemcpy(c_one.data(), coeffs, c_one.size() * 8, hipMemcpyDeviceToHost));
   size_t diff = 0;

@@ -22,7 +22,13 @@ int main(int argc, char** argv) {
   BatchView b{P, S, S, S, to_dev(so), to_dev(order), to_dev(slot)};
   double *coeffs, *cost; int32_t* status;
   CK(hipMalloc(&coeffs, S * 40 * 8)); CK(hipMalloc(&cost, 8)); CK(hipMalloc(&status, 4));
-  CK(launch_solve_rows(b, RouteHints{}, d, to_dev(mask), to_dev(vals), to_dev(T), coeffs, status, cost, nullptr, 0));
+  SolveRequest rows;  // the rows kernel whatever the size rules say
+  rows.derivative = d;
+  rows.force = SolveFamily::kRows;
+  SolveOperands op;
+  op.mask = to_dev(mask); op.vals = to_dev(vals); op.seg_times = to_dev(T);
+  op.coeffs = coeffs; op.status = status; op.cost = cost;
+  CK(launch_solve_rows(b, route_solve(b, rows), op, 0));
   CK(hipDeviceSynchronize());
   std::vector<double> dbg(64 * 24 * 2);
   CK(hipMemcpyFromSymbol(dbg.data(), HIP_SYMBOL(g_rows_debug), dbg.size() * 8));

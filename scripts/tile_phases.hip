@@ -86,12 +86,26 @@ int main(int argc, char** argv) {
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
+  SolveOperands op;
+  op.mask = dmask;
+  op.vals = dvals;
+  op.seg_times = dT;
+  op.H = H;
+  op.Ainv = A;
+  op.coeffs = coeffs;
+  op.status = status;
+  op.cost = cost;
   for (int fused = 0; fused < 2; ++fused) {
-    for (int i = 0; i < 10; ++i) CK(launch_solve_tile(b, d, fused, dmask, dvals, dT, H, A, coeffs, status, cost, nullptr, st));
+    SolveRequest tile;  // the tile kernel whatever the size rules say: the request forces the family
+    tile.derivative = d;
+    tile.fused = fused != 0;
+    tile.force = SolveFamily::kTile;
+    const SolveRoute tile_route = route_solve(b, tile);
+    for (int i = 0; i < 10; ++i) CK(launch_solve_tile(b, tile_route, op, st));
     CK(hipStreamSynchronize(st));
     const int n = 200;
     CK(hipEventRecord(e0, st));
-    for (int i = 0; i < n; ++i) CK(launch_solve_tile(b, d, fused, dmask, dvals, dT, H, A, coeffs, status, cost, nullptr, st));
+    for (int i = 0; i < n; ++i) CK(launch_solve_tile(b, tile_route, op, st));
     CK(hipEventRecord(e1, st));
     CK(hipEventSynchronize(e1));
     float ms;
@@ -111,11 +125,15 @@ int main(int argc, char** argv) {
   // the rows kernel (one lane per unknown): the library's fused linear solve
   for (int ppw = 1; ppw <= 2; ++ppw) {
     setenv("MRS_TG_ROWS_PPW", ppw == 1 ? "1" : "2", 1);
-    for (int i = 0; i < 10; ++i) CK(launch_solve_rows(b, RouteHints{}, d, dmask, dvals, dT, coeffs, status, cost, nullptr, st));
+    SolveRequest rows;  // (forced as well)
+    rows.derivative = d;
+    rows.force = SolveFamily::kRows;
+    const SolveRoute rows_route = route_solve(b, rows);
+    for (int i = 0; i < 10; ++i) CK(launch_solve_rows(b, rows_route, op, st));
     CK(hipStreamSynchronize(st));
     const int n = 200;
     CK(hipEventRecord(e0, st));
-    for (int i = 0; i < n; ++i) CK(launch_solve_rows(b, RouteHints{}, d, dmask, dvals, dT, coeffs, status, cost, nullptr, st));
+    for (int i = 0; i < n; ++i) CK(launch_solve_rows(b, rows_route, op, st));
     CK(hipEventRecord(e1, st));
     CK(hipEventSynchronize(e1));
     float ms;

@@ -21,7 +21,7 @@ VTX_REC, SEG_REC, N_DIM, N_COEFF = 88, 10, 4, 10     # kRVtxRec, kRSegRec, kD, k
 SAMPLE_BUFFER = 192                                  # kSampleBuffer
 LDS_BUDGET = 144 * 1024                              # kRowsLdsBudget
 LDS_DEFAULT = 64 * 1024                              # above it the launch raises its dynamic-LDS limit first
-TAIL_MAX_PATHS = 2048                                # rows_tail_sampling_pays
+TAIL_MAX_PATHS = 2048                                # rows_tail_sampling_pays (mrs_tg_solve_route.hpp)
 
 
 def schedule(S, mask_first, mask_last):
@@ -84,7 +84,7 @@ def lds_bytes(Smax, ppw, sampling):
 
 
 def route(Smax, n_paths, shared=False, sampling=False):
-    """what launch_solve_rows does with a fixed-times default solve of fewer than 6144 paths:
+    """what route_solve (mrs_tg_solve_route.hpp) gives a fixed-times default solve of fewer than 6144 paths:
     dict(rows, ppw, tail, raised) -- rows False: the batch goes to the tile / lane kernels"""
     if lds_bytes(Smax, 1, False) > LDS_BUDGET:
         return dict(rows=False, ppw=0, tail=False, raised=False)
