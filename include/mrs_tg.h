@@ -213,9 +213,27 @@ enum {
   MRS_TG_CAP_PATH_EDIT = 4096,        /* mrs_tg_plan_preprocess_path, mrs_tg_plan_insert_midpoints and mrs_tg_plan_path_edit_vjp
                                          are exported: the two steps that change the number of waypoints of a path (preprocessPath's
                                          thinning, the mid-points of unsafe segments) and their one backward pass */
-  MRS_TG_CAP_TRAVEL_HEADING = 8192    /* mrs_tg_plan_travel_heading and mrs_tg_plan_travel_heading_vjp are exported: the heading
+  MRS_TG_CAP_TRAVEL_HEADING = 8192,   /* mrs_tg_plan_travel_heading and mrs_tg_plan_travel_heading_vjp are exported: the heading
                                          along the direction of travel (override_heading_atan2) as a plan step and its backward
                                          pass */
+  MRS_TG_CAP_INITIAL_CONDITION = 16384 /* mrs_tg_plan_initial_condition, mrs_tg_plan_prepend_initial_condition,
+                                         mrs_tg_plan_splice_prediction and their three backward passes are exported: where a
+                                         trajectory starts (prepareInitialCondition), the waypoint put in front of the request
+                                         and the prediction in front of a trajectory from the future, as plan steps */
+};
+
+/* mrs_tg_plan_initial_condition's decision_out_dev: what prepareInitialCondition and the first-waypoint rule decided for a
+ * path, as bits.  One of FROM_TRACKER, FROM_UAV, FROM_PREDICTION is set exactly where PREPEND is; FROM_FUTURE goes with
+ * FROM_PREDICTION; DROP_FIRST stands for itself; INVALID stands alone. */
+enum {
+  MRS_TG_IC_PREPEND = 1,          /* the path has an initial condition: a waypoint goes in front, the state block holds it */
+  MRS_TG_IC_FROM_FUTURE = 2,      /* sample at 0.2 s and splice the prediction in front afterwards */
+  MRS_TG_IC_DROP_FIRST = 4,       /* erase the first requested waypoint before prepending (:650-655) */
+  MRS_TG_IC_FROM_TRACKER = 8,     /* the state is the tracker command */
+  MRS_TG_IC_FROM_UAV = 16,        /* ... the UAV state lifted by the takeoff height, derivatives zero (before takeoff) */
+  MRS_TG_IC_FROM_PREDICTION = 32, /* ... row k of the prediction */
+  MRS_TG_IC_INVALID = 64          /* a NaN time offset, a NaN age of a tracker command that is present, or n_pred outside
+                                     [0, pred_capacity]: no initial condition, the caller fails the path */
 };
 
 /* mrs_tg_plan_estimate_times_vjp's term_out_dev: the term of the estimate a segment's time came from */
@@ -908,6 +926,101 @@ int mrs_tg_plan_travel_heading_vjp(mrs_tg_plan* plan, const double* samples_dev,
                                    int32_t sample_capacity, const int32_t* status_dev, double min_step, const double* grad_out_dev,
                                    double* grad_samples_out_dev);
 
+/* Where a trajectory starts, as a plan step (MRS_TG_CAP_INITIAL_CONDITION; initial_condition_kernel, csrc/mrs_tg_initial.hpp,
+ * DESIGN.md section 11g): prepareInitialCondition (mrs_trajectory_generation.cpp:506-614) and the first-waypoint rule
+ * (:650-655) for every path of the plan, one lane per path; the batched form of mrs_tg_prepare_initial_condition, the same
+ * table and the same bins.  The plan contributes its path count and its context only (mrs_tg_plan_create refuses a path without
+ * a segment, and a request of one waypoint is the normal case here): the requested waypoints are addressed by
+ * vertex_offsets_dev [n_paths + 1], of which this call reads the counts for the n_path_waypoints >= 2 rule; a path may have no
+ * vertex or one.  Inputs, [n_paths] each:
+ *   flags_dev                 bit 0 a tracker command is present, bit 1 a UAV state is present, bit 2 dont_prepend
+ *   tracker_dev [.][4][4]     row 0 the pose x, y, z, heading, rows 1 .. 3 velocity, acceleration, jerk (xyz + the heading's)
+ *   tracker_age_dev           now - its stamp (> 1.0: stale);   uav_pose_dev [.][4]  x, y, z, heading
+ *   path_time_offset_dev      path stamp - now (0 for an unstamped path)
+ *   pred_*_dev [.][pred_capacity][4], n_pred_dev   the prediction in mrs_tg_prediction's layout, n_pred rows of it valid
+ *                             (pred_capacity 0: the arrays may be NULL)
+ * takeoff_height is one scalar.  Outputs: decision_out_dev (MRS_TG_IC_*), sample_offset_out_dev (k, as
+ * mrs_tg_prepare_initial_condition reports it: set when the tracker command is used for an offset > 0.2 s, else 0) and
+ * initial_out_dev [.][4][4]: row 0 the prepended waypoint, whose heading is also the state's heading, rows 1 .. 3 the
+ * derivatives; the whole block is zero where MRS_TG_IC_PREPEND is not set.  Every value is a copy of an input but
+ * z + takeoff_height.  k and the 0.2 s threshold are evaluated in double, in the host's order, the quotient by a division.
+ * MRS_TG_ERR_INVALID_ARG, before any launch: a missing pointer (all are mandatory), a negative pred_capacity, a NaN
+ * takeoff_height.  Device pointers (16-byte aligned), asynchronous on the context's stream. */
+int mrs_tg_plan_initial_condition(mrs_tg_plan* plan, const int32_t* flags_dev, const double* tracker_dev,
+                                  const double* tracker_age_dev, const double* uav_pose_dev, double takeoff_height,
+                                  const double* path_time_offset_dev, const int32_t* vertex_offsets_dev,
+                                  const double* pred_position_dev, const double* pred_velocity_dev,
+                                  const double* pred_acceleration_dev, const double* pred_jerk_dev, const int32_t* n_pred_dev,
+                                  int32_t pred_capacity, int32_t* decision_out_dev, int32_t* sample_offset_out_dev,
+                                  double* initial_out_dev);
+/* Backward pass of mrs_tg_plan_initial_condition (initial_condition_vjp_kernel), the decision and k held fixed: given
+ * grad_initial_dev [n_paths][4][4] writes grad_tracker_out_dev [n_paths][4][4] (the block where FROM_TRACKER is set),
+ * grad_uav_out_dev [n_paths][4] (row 0 of the block where FROM_UAV is set) and the four grad_pred_*_out_dev
+ * [n_paths][pred_capacity][4], where row k of each carries row 0 .. 3 of the block where FROM_PREDICTION is set.  Every
+ * other element is zero.  Copies only; every element of every output is written exactly once; the same bits on every call. */
+int mrs_tg_plan_initial_condition_vjp(mrs_tg_plan* plan, const int32_t* decision_dev, const int32_t* sample_offset_dev,
+                                      const double* grad_initial_dev, int32_t pred_capacity, double* grad_tracker_out_dev,
+                                      double* grad_uav_out_dev, double* grad_pred_position_out_dev,
+                                      double* grad_pred_velocity_out_dev, double* grad_pred_acceleration_out_dev,
+                                      double* grad_pred_jerk_out_dev);
+
+/* The edit of :649-672 as a plan step (prepend_count_kernel, vertex_offsets_kernel, prepend_write_kernel): per path the first
+ * requested waypoint goes where decision_dev has MRS_TG_IC_DROP_FIRST (and the path has one), and row 0 of initial_dev
+ * [n_paths][4][4] comes in front where it has MRS_TG_IC_PREPEND, with stop_at 0.  waypoints_dev [n_vertices][4] and stop_at_dev
+ * [n_vertices] (may be NULL: zeros) are addressed by vertex_offsets_dev [n_paths + 1], n_vertices = vertex_offsets[n_paths] as
+ * the caller built it.  The result is packed as mrs_tg_plan_preprocess_path packs it: vertex_offsets_out_dev [n_paths + 1],
+ * waypoints_out_dev (room for n_vertices + n_paths rows; the rows below vertex_offsets_out[n_paths] are written once, nothing
+ * at or behind it), stop_at_out_dev and source_out_dev (may be NULL; the batch-wide input vertex, -1 for the prepended row).
+ * Three launches (count, one workgroup sums, one lane per output vertex writes); no atomics, no waiting between workgroups.
+ * A path may come out with no vertex or one: mrs_tg_plan_create refuses it, the caller fails it ("the path is empty").
+ * MRS_TG_ERR_INVALID_ARG, before any launch: a missing mandatory pointer, a negative n_vertices, n_vertices + n_paths beyond
+ * int32. */
+int mrs_tg_plan_prepend_initial_condition(mrs_tg_plan* plan, const int32_t* vertex_offsets_dev, int32_t n_vertices,
+                                          const double* waypoints_dev, const uint8_t* stop_at_dev, const int32_t* decision_dev,
+                                          const double* initial_dev, int32_t* vertex_offsets_out_dev, double* waypoints_out_dev,
+                                          uint8_t* stop_at_out_dev, int32_t* source_out_dev);
+/* Its backward pass (prepend_vjp_kernel): grad_waypoints_edited_dev [n_vertices_edited][4] on the packed result, addressed by
+ * vertex_offsets_edited_dev as the forward wrote it, gives grad_waypoints_out_dev [n_vertices][4] of the requested vertices (a
+ * dropped vertex gets a zero row) and grad_initial_row_out_dev [n_paths][4], the gradient of row 0 of the state block (zero
+ * where nothing was prepended).  Copies only; every element written exactly once. */
+int mrs_tg_plan_prepend_initial_condition_vjp(mrs_tg_plan* plan, const int32_t* vertex_offsets_dev, int32_t n_vertices,
+                                              const int32_t* decision_dev, const int32_t* vertex_offsets_edited_dev,
+                                              int32_t n_vertices_edited, const double* grad_waypoints_edited_dev,
+                                              double* grad_waypoints_out_dev, double* grad_initial_row_out_dev);
+
+/* The pre-trajectory of a path stamped in the future (:801-840) as a plan step (splice_prediction_kernel), on samples where
+ * they are; the batched form of mrs_tg_splice_prediction.  samples_dev [n_paths][sample_capacity][4], n_samples_dev and
+ * status_dev (may be NULL: every path is live) are what a solve or a sampler left; decision_dev and sample_offset_dev (k) are
+ * mrs_tg_plan_initial_condition's; prediction_age_dev [n_paths] = now - the stamp of the prediction held after the solve;
+ * pred_position_dev [n_paths][pred_capacity][4] with n_pred_dev rows valid.  With k2 = int(floor((age - 0.01) / 0.2)) + 1: where
+ * a path is live, MRS_TG_IC_FROM_FUTURE is set, k > 0 and k > k2, prediction rows 0 .. k-1 go in front of the n rows, in that
+ * order, and n_samples_out = n + k.  If n + k > sample_capacity nothing of that path is written and the count n + k is still
+ * reported.  k > n_pred (or a NaN age) sets MRS_TG_STATUS_INVALID_ARGS in status_out_dev [n_paths] (may be NULL, may be
+ * status_dev; every other path passes its status on, 1 without status_dev) and leaves the path alone: the host function
+ * refuses that case.  A path is left alone, rows and count, if its status is <= 0, if its n_samples is outside
+ * [0, sample_capacity] (sample_capacity + 1: a sampler overflow), or if it needs no splice.
+ * samples_out_dev may be samples_dev: the shift then walks the chunks of 64 rows from the last to the first, each chunk loading
+ * all its rows before it stores any, and writes the prefix after the lowest chunk, which is correct for every k.  Out of place
+ * the two arrays may not overlap; rows 0 .. n + k - 1 are written whole, and a live path that is left alone has its rows
+ * copied.  In both forms no row at or behind the new count is written.  n_samples_out_dev may be n_samples_dev.  One wavefront
+ * per path; no LDS, no atomics.  MRS_TG_ERR_INVALID_ARG, before any launch: a missing mandatory pointer, a negative
+ * sample_capacity or pred_capacity, sample_capacity + pred_capacity beyond int32. */
+int mrs_tg_plan_splice_prediction(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev,
+                                  int32_t sample_capacity, const int32_t* status_dev, const int32_t* decision_dev,
+                                  const int32_t* sample_offset_dev, const double* prediction_age_dev,
+                                  const double* pred_position_dev, const int32_t* n_pred_dev, int32_t pred_capacity,
+                                  double* samples_out_dev, int32_t* n_samples_out_dev, int32_t* status_out_dev);
+/* Its backward pass (splice_prediction_vjp_kernel); n_samples_dev and status_dev are the forward's INPUTS.  Where the forward
+ * spliced: grad_samples[i] = grad_out[i + k] for i < n and grad_pred_position[i] = grad_out[i] for i < k, zero everywhere else
+ * that belongs to the path.  Where nothing was spliced grad_samples is the rows 0 .. n-1 of grad_out (none for a path with
+ * status <= 0) and the prediction's rows are zero.  grad_out_dev, grad_samples_out_dev [n_paths][sample_capacity][4],
+ * grad_pred_position_out_dev [n_paths][pred_capacity][4].  Copies only; every element written exactly once. */
+int mrs_tg_plan_splice_prediction_vjp(mrs_tg_plan* plan, const int32_t* n_samples_dev, int32_t sample_capacity,
+                                      const int32_t* status_dev, const int32_t* decision_dev, const int32_t* sample_offset_dev,
+                                      const double* prediction_age_dev, const int32_t* n_pred_dev, int32_t pred_capacity,
+                                      const double* grad_out_dev, double* grad_samples_out_dev,
+                                      double* grad_pred_position_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
@@ -923,7 +1036,10 @@ int mrs_tg_plan_travel_heading_vjp(mrs_tg_plan* plan, const double* samples_dev,
  * (mrs_tg_plan_fallback_sample_vjp), 20 path thinning (mrs_tg_plan_preprocess_path), 21 mid-point subdivision
  * (mrs_tg_plan_insert_midpoints; both timed from their first launch to their last), 22 their backward pass
  * (mrs_tg_plan_path_edit_vjp), 23 the heading along the direction of travel (mrs_tg_plan_travel_heading), 24 its backward pass
- * (mrs_tg_plan_travel_heading_vjp): twenty-five ids, 0 .. 24.
+ * (mrs_tg_plan_travel_heading_vjp), 25 the initial condition (mrs_tg_plan_initial_condition), 26 the prepended waypoint
+ * (mrs_tg_plan_prepend_initial_condition, timed from its first launch to its last), 27 the prediction splice
+ * (mrs_tg_plan_splice_prediction), 28, 29, 30 their backward passes (mrs_tg_plan_splice_prediction_vjp,
+ * mrs_tg_plan_initial_condition_vjp, mrs_tg_plan_prepend_initial_condition_vjp): thirty-one ids, 0 .. 30.
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

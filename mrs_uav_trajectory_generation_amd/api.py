@@ -52,6 +52,8 @@ KERNEL_BACA, KERNEL_BACA_VJP, KERNEL_LENGTH_GATE = 14, 15, 16
 KERNEL_UNWRAP_HEADINGS, KERNEL_FALLBACK_SAMPLE, KERNEL_FALLBACK_SAMPLE_VJP = 17, 18, 19
 KERNEL_PREPROCESS_PATH, KERNEL_INSERT_MIDPOINTS, KERNEL_PATH_EDIT_VJP = 20, 21, 22
 KERNEL_TRAVEL_HEADING, KERNEL_TRAVEL_HEADING_VJP = 23, 24
+KERNEL_INITIAL_CONDITION, KERNEL_PREPEND_INITIAL_CONDITION, KERNEL_SPLICE_PREDICTION = 25, 26, 27
+KERNEL_SPLICE_PREDICTION_VJP, KERNEL_INITIAL_CONDITION_VJP, KERNEL_PREPEND_INITIAL_CONDITION_VJP = 28, 29, 30
 
 
 class MrsTgError(RuntimeError):
@@ -118,6 +120,8 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_plan_unwrap_headings", "mrs_tg_plan_fallback_sample", "mrs_tg_plan_fallback_sample_vjp",
     "mrs_tg_plan_preprocess_path", "mrs_tg_plan_insert_midpoints", "mrs_tg_plan_path_edit_vjp",
     "mrs_tg_plan_travel_heading", "mrs_tg_plan_travel_heading_vjp",
+    "mrs_tg_plan_initial_condition", "mrs_tg_plan_initial_condition_vjp", "mrs_tg_plan_prepend_initial_condition",
+    "mrs_tg_plan_prepend_initial_condition_vjp", "mrs_tg_plan_splice_prediction", "mrs_tg_plan_splice_prediction_vjp",
 ]
 
 _lib = None
@@ -253,6 +257,18 @@ def load_library():
     L.mrs_tg_plan_travel_heading.argtypes = [vp, dp, ip, C.c_int32, ip, C.c_double, dp, ip]
     L.mrs_tg_plan_travel_heading_vjp.restype = C.c_int
     L.mrs_tg_plan_travel_heading_vjp.argtypes = [vp, dp, ip, C.c_int32, ip, C.c_double, dp, dp]
+    L.mrs_tg_plan_initial_condition.restype = C.c_int
+    L.mrs_tg_plan_initial_condition.argtypes = [vp, ip, dp, dp, dp, C.c_double, dp, ip, dp, dp, dp, dp, ip, C.c_int32, ip, ip, dp]
+    L.mrs_tg_plan_initial_condition_vjp.restype = C.c_int
+    L.mrs_tg_plan_initial_condition_vjp.argtypes = [vp, ip, ip, dp, C.c_int32, dp, dp, dp, dp, dp, dp]
+    L.mrs_tg_plan_prepend_initial_condition.restype = C.c_int
+    L.mrs_tg_plan_prepend_initial_condition.argtypes = [vp, ip, C.c_int32, dp, vp, ip, dp, ip, dp, vp, ip]
+    L.mrs_tg_plan_prepend_initial_condition_vjp.restype = C.c_int
+    L.mrs_tg_plan_prepend_initial_condition_vjp.argtypes = [vp, ip, C.c_int32, ip, ip, C.c_int32, dp, dp, dp]
+    L.mrs_tg_plan_splice_prediction.restype = C.c_int
+    L.mrs_tg_plan_splice_prediction.argtypes = [vp, dp, ip, C.c_int32, ip, ip, ip, dp, dp, ip, C.c_int32, dp, ip, ip]
+    L.mrs_tg_plan_splice_prediction_vjp.restype = C.c_int
+    L.mrs_tg_plan_splice_prediction_vjp.argtypes = [vp, ip, C.c_int32, ip, ip, ip, dp, ip, C.c_int32, dp, dp, dp]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -311,6 +327,10 @@ CAP_BACA = 1024               # MRS_TG_CAP_BACA: Plan.estimate_times_baca (the B
 CAP_PATH_EDIT = 4096          # MRS_TG_CAP_PATH_EDIT: Plan.preprocess_path (preprocessPath's thinning), Plan.insert_midpoints (the mid-points of unsafe segments), Plan.path_edit_vjp
 CAP_FALLBACK_SAMPLE = 2048    # MRS_TG_CAP_FALLBACK_SAMPLE: Plan.unwrap_headings, Plan.fallback_sample (findTrajectoryFallback's rows as a plan step), Plan.fallback_sample_vjp
 CAP_TRAVEL_HEADING = 8192     # MRS_TG_CAP_TRAVEL_HEADING: Plan.travel_heading (the heading along the direction of travel, override_heading_atan2), Plan.travel_heading_vjp
+CAP_INITIAL_CONDITION = 16384  # MRS_TG_CAP_INITIAL_CONDITION: Plan.initial_condition, Plan.prepend_initial_condition, Plan.splice_prediction and their three backward passes
+# Plan.initial_condition's decision word (MRS_TG_IC_*) and its flags input (bit 0 tracker command, bit 1 UAV state, bit 2 dont_prepend)
+IC_PREPEND, IC_FROM_FUTURE, IC_DROP_FIRST, IC_FROM_TRACKER, IC_FROM_UAV, IC_FROM_PREDICTION, IC_INVALID = 1, 2, 4, 8, 16, 32, 64
+IC_FLAG_TRACKER, IC_FLAG_UAV, IC_FLAG_DONT_PREPEND = 1, 2, 4
 # Plan.estimate_times_baca_vjp's flags: the branches of the Baca estimate a segment's time took, as bits (MRS_TG_BACA_*)
 BACA_V_VERTICAL, BACA_A_VERTICAL, BACA_J_VERTICAL, BACA_T1_CAPPED, BACA_T2_CAPPED = 1, 2, 4, 8, 16
 BACA_DOT1_CLAMPED, BACA_DOT2_CLAMPED, BACA_FLOOR, BACA_HEADING, BACA_HEADING_CRUISE, BACA_HEADING_ACC = 32, 64, 128, 256, 512, 1024
@@ -1102,6 +1122,75 @@ class Plan:
                                                                int(samples.shape[1]), _t_ptr(status), float(min_step),
                                                                _t_ptr(grad_out), _t_ptr(grad_samples)),
                         "mrs_tg_plan_travel_heading_vjp")
+
+    def initial_condition(self, flags, tracker, tracker_age, uav_pose, takeoff_height, path_time_offset, vertex_offsets,
+                          prediction, n_pred, decision, sample_offset, initial):
+        """mrs_tg_plan_initial_condition: prepareInitialCondition and the first-waypoint rule for every path, one lane per path.
+        [n_paths] each: flags int32 (IC_FLAG_*), tracker [.][4][4] (pose, velocity, acceleration, jerk; xyz + the heading's),
+        tracker_age, uav_pose [.][4], path_time_offset, n_pred int32; vertex_offsets [n_paths + 1] int32 of the requested
+        waypoints; prediction: the four arrays [.][pred_capacity][4] position, velocity, acceleration, jerk.  Written: decision
+        int32 (IC_*), sample_offset int32 (k) and initial [.][4][4] (row 0 the prepended waypoint, rows 1 .. 3 the derivatives;
+        zeros where IC_PREPEND is not set).  Device tensors; asynchronous on the context's stream."""
+        pos, vel, acc, jerk = prediction
+        self.ctx._check(self._L.mrs_tg_plan_initial_condition(
+            self._h, _t_ptr(flags), _t_ptr(tracker), _t_ptr(tracker_age), _t_ptr(uav_pose), float(takeoff_height),
+            _t_ptr(path_time_offset), _t_ptr(vertex_offsets), _t_ptr(pos), _t_ptr(vel), _t_ptr(acc), _t_ptr(jerk), _t_ptr(n_pred),
+            int(pos.shape[1]), _t_ptr(decision), _t_ptr(sample_offset), _t_ptr(initial)), "mrs_tg_plan_initial_condition")
+
+    def initial_condition_vjp(self, decision, sample_offset, grad_initial, grad_tracker, grad_uav, grad_prediction):
+        """mrs_tg_plan_initial_condition_vjp: from grad_initial [n_paths][4][4], the decision and k held fixed, grad_tracker
+        [.][4][4], grad_uav [.][4] and the four grad_prediction arrays [.][pred_capacity][4] (row k of each; all written, zeros
+        included); asynchronous on the context's stream."""
+        pos, vel, acc, jerk = grad_prediction
+        self.ctx._check(self._L.mrs_tg_plan_initial_condition_vjp(
+            self._h, _t_ptr(decision), _t_ptr(sample_offset), _t_ptr(grad_initial), int(pos.shape[1]), _t_ptr(grad_tracker),
+            _t_ptr(grad_uav), _t_ptr(pos), _t_ptr(vel), _t_ptr(acc), _t_ptr(jerk)), "mrs_tg_plan_initial_condition_vjp")
+
+    def prepend_initial_condition(self, vertex_offsets, waypoints, decision, initial, vertex_offsets_out, waypoints_out,
+                                  stop_at=None, stop_at_out=None, source=None):
+        """mrs_tg_plan_prepend_initial_condition: the first requested waypoint goes where decision has IC_DROP_FIRST, row 0 of
+        initial [n_paths][4][4] comes in front (stop_at 0) where it has IC_PREPEND.  waypoints [n_vertices][4] addressed by
+        vertex_offsets [n_paths + 1] int32 (a path may have no vertex or one); packed as preprocess_path packs:
+        vertex_offsets_out [n_paths + 1] int32, waypoints_out [n_vertices + n_paths][4] and, optional, stop_at_out uint8 and
+        source int32 (the input vertex, -1 for the prepended row).  Device tensors; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_prepend_initial_condition(
+            self._h, _t_ptr(vertex_offsets), int(waypoints.shape[0]), _t_ptr(waypoints), _t_ptr(stop_at), _t_ptr(decision),
+            _t_ptr(initial), _t_ptr(vertex_offsets_out), _t_ptr(waypoints_out), _t_ptr(stop_at_out), _t_ptr(source)),
+            "mrs_tg_plan_prepend_initial_condition")
+
+    def prepend_initial_condition_vjp(self, vertex_offsets, decision, vertex_offsets_edited, grad_waypoints_edited,
+                                      grad_waypoints, grad_initial_row):
+        """mrs_tg_plan_prepend_initial_condition_vjp: grad_waypoints [n_vertices][4] of the requested vertices (a dropped one
+        gets zeros) and grad_initial_row [n_paths][4] (row 0 of the state block) from grad_waypoints_edited [n_edited][4];
+        asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_prepend_initial_condition_vjp(
+            self._h, _t_ptr(vertex_offsets), int(grad_waypoints.shape[0]), _t_ptr(decision), _t_ptr(vertex_offsets_edited),
+            int(grad_waypoints_edited.shape[0]), _t_ptr(grad_waypoints_edited), _t_ptr(grad_waypoints), _t_ptr(grad_initial_row)),
+            "mrs_tg_plan_prepend_initial_condition_vjp")
+
+    def splice_prediction(self, samples, n_samples, decision, sample_offset, prediction_age, pred_position, n_pred,
+                          samples_out=None, n_samples_out=None, status=None, status_out=None):
+        """mrs_tg_plan_splice_prediction: where a path is live, IC_FROM_FUTURE is set and k = sample_offset exceeds the
+        prediction's current index, prediction rows 0 .. k-1 go in front of the n rows of samples [n_paths][capacity][4] and
+        n_samples_out = n + k (reported, nothing written, when that exceeds the capacity).  samples_out / n_samples_out None =
+        in place.  status_out [n_paths] int32 (optional) passes status on, -2 where the prediction has fewer than k rows.
+        Device tensors; asynchronous on the context's stream."""
+        out = samples if samples_out is None else samples_out
+        n_out = n_samples if n_samples_out is None else n_samples_out
+        self.ctx._check(self._L.mrs_tg_plan_splice_prediction(
+            self._h, _t_ptr(samples), _t_ptr(n_samples), int(samples.shape[1]), _t_ptr(status), _t_ptr(decision),
+            _t_ptr(sample_offset), _t_ptr(prediction_age), _t_ptr(pred_position), _t_ptr(n_pred), int(pred_position.shape[1]),
+            _t_ptr(out), _t_ptr(n_out), _t_ptr(status_out)), "mrs_tg_plan_splice_prediction")
+
+    def splice_prediction_vjp(self, n_samples, decision, sample_offset, prediction_age, n_pred, grad_out, grad_samples,
+                              grad_pred_position, status=None):
+        """mrs_tg_plan_splice_prediction_vjp: grad_samples [n_paths][capacity][4] and grad_pred_position
+        [n_paths][pred_capacity][4] (all written, zeros included) from grad_out [n_paths][capacity][4]; n_samples and status are
+        the forward's inputs; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_splice_prediction_vjp(
+            self._h, _t_ptr(n_samples), int(grad_out.shape[1]), _t_ptr(status), _t_ptr(decision), _t_ptr(sample_offset),
+            _t_ptr(prediction_age), _t_ptr(n_pred), int(grad_pred_position.shape[1]), _t_ptr(grad_out), _t_ptr(grad_samples),
+            _t_ptr(grad_pred_position)), "mrs_tg_plan_splice_prediction_vjp")
 
 
 class RoundRobin:

@@ -626,6 +626,162 @@ def travel_heading(plan, samples, n_samples, status=None, min_step=0.05):
     return _TravelHeading.apply(plan, samples, n_samples, status, min_step)
 
 
+def _f64(t):
+    return t.detach().to(torch.float64).contiguous()
+
+
+def _i32(t):
+    return t.detach().to(torch.int32).contiguous()
+
+
+class _InitialCondition(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, tracker, uav_pose, pos, vel, acc, jerk, fixed):
+        P = plan.n_paths
+        tr, uav = _f64(tracker), _f64(uav_pose)
+        pred = tuple(_f64(a) for a in (pos, vel, acc, jerk))
+        if tr.shape != (P, 4, 4) or uav.shape != (P, 4):
+            raise ValueError("tracker must be [n_paths][4][4] and uav_pose [n_paths][4]")
+        if any(a.dim() != 3 or a.shape != pred[0].shape or a.shape[0] != P or a.shape[2] != api.N_DIM for a in pred):
+            raise ValueError("the prediction's four arrays must be [n_paths][pred_capacity][4]")
+        dev = tr.device
+        decision = torch.empty(P, dtype=torch.int32, device=dev)
+        k = torch.empty(P, dtype=torch.int32, device=dev)
+        initial = torch.empty((P, 4, 4), dtype=torch.float64, device=dev)
+        plan.ctx.use_torch_stream()
+        plan.initial_condition(_i32(fixed["flags"]), tr, _f64(fixed["tracker_age"]), uav, fixed["takeoff_height"],
+                               _f64(fixed["path_time_offset"]), _i32(fixed["vertex_offsets"]), pred, _i32(fixed["n_pred"]),
+                               decision, k, initial)
+        ctx.plan, ctx.pred_capacity = plan, pred[0].shape[1]
+        ctx.save_for_backward(decision, k)
+        ctx.mark_non_differentiable(decision, k)
+        ctx.set_materialize_grads(False)
+        return initial, decision, k
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_initial, *_):
+        decision, k = ctx.saved_tensors
+        if grad_initial is None or not any(ctx.needs_input_grad[1:7]):
+            return (None,) * 8
+        plan, P, dev = ctx.plan, ctx.plan.n_paths, decision.device
+        gt = torch.empty((P, 4, 4), dtype=torch.float64, device=dev)
+        gu = torch.empty((P, 4), dtype=torch.float64, device=dev)
+        gp = tuple(torch.empty((P, ctx.pred_capacity, api.N_DIM), dtype=torch.float64, device=dev) for _ in range(4))
+        plan.ctx.use_torch_stream()
+        plan.initial_condition_vjp(decision, k, grad_initial.to(torch.float64).contiguous(), gt, gu, gp)
+        return (None, gt, gu) + gp + (None,)
+
+
+def initial_condition(plan, flags, tracker, tracker_age, uav_pose, takeoff_height, path_time_offset, vertex_offsets, prediction,
+                      n_pred):
+    """(initial [n_paths][4][4], decision [n_paths] int32, sample_offset [n_paths] int32) of Plan.initial_condition:
+    prepareInitialCondition for every path -- row 0 of a block the waypoint to prepend, rows 1 .. 3 the derivatives, zeros where
+    the decision has no api.IC_PREPEND.  Differentiable in tracker [n_paths][4][4], uav_pose [n_paths][4] and the four prediction
+    arrays (a tuple position, velocity, acceleration, jerk, [n_paths][pred_capacity][4] each): every value is a copy, so the
+    gradient of a block lands on the tracker command, on the UAV pose (row 0) or on row k of the prediction, whichever the
+    decision took.  The decision and k are piecewise constant and held fixed.  Device tensors."""
+    fixed = dict(flags=flags, tracker_age=tracker_age, takeoff_height=float(takeoff_height), path_time_offset=path_time_offset,
+                 vertex_offsets=vertex_offsets, n_pred=n_pred)
+    pos, vel, acc, jerk = prediction
+    return _InitialCondition.apply(plan, tracker, uav_pose, pos, vel, acc, jerk, fixed)
+
+
+class _PrependInitialCondition(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, waypoints, initial, vertex_offsets, decision, stop_at):
+        w, ini = _f64(waypoints).reshape(-1, api.N_DIM), _f64(initial)
+        vo, dec = _i32(vertex_offsets), _i32(decision)
+        P, n_v, dev = plan.n_paths, w.shape[0], w.device
+        if ini.shape != (P, 4, 4) or vo.shape != (P + 1,) or dec.shape != (P,):
+            raise ValueError("initial must be [n_paths][4][4], vertex_offsets [n_paths + 1] and decision [n_paths]")
+        stop = None if stop_at is None else stop_at.detach().to(torch.uint8).contiguous()
+        offsets = torch.empty(P + 1, dtype=torch.int32, device=dev)
+        out = torch.empty((n_v + P, api.N_DIM), dtype=torch.float64, device=dev)
+        stop_out = torch.empty(n_v + P, dtype=torch.uint8, device=dev)
+        source = torch.empty(n_v + P, dtype=torch.int32, device=dev)
+        plan.ctx.use_torch_stream()
+        plan.prepend_initial_condition(vo, w, dec, ini, offsets, out, stop_at=stop, stop_at_out=stop_out, source=source)
+        total = int(offsets[-1].item())   # the one readback: the caller needs the offsets on the host for the next plan anyway
+        out, stop_out, source = out[:total], stop_out[:total], source[:total]
+        ctx.plan, ctx.n_v = plan, n_v
+        ctx.save_for_backward(vo, dec, offsets)
+        ctx.mark_non_differentiable(stop_out, source, offsets)
+        ctx.set_materialize_grads(False)
+        return out, stop_out, source, offsets
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, *_):
+        vo, dec, offsets = ctx.saved_tensors
+        if grad_out is None or not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+            return (None,) * 6
+        plan, P, dev = ctx.plan, ctx.plan.n_paths, vo.device
+        gw = torch.empty((ctx.n_v, api.N_DIM), dtype=torch.float64, device=dev)
+        row = torch.empty((P, api.N_DIM), dtype=torch.float64, device=dev)
+        plan.ctx.use_torch_stream()
+        plan.prepend_initial_condition_vjp(vo, dec, offsets, grad_out.to(torch.float64).contiguous(), gw, row)
+        gi = torch.zeros((P, 4, 4), dtype=torch.float64, device=dev)
+        gi[:, 0, :] = row
+        return None, gw, gi, None, None, None
+
+
+def prepend_initial_condition(plan, waypoints, initial, vertex_offsets, decision, stop_at=None):
+    """(waypoints [sum V'][4], stop_at [sum V'] uint8, source [sum V'] int32, offsets [n_paths + 1] int32) of
+    Plan.prepend_initial_condition: per path the first requested waypoint dropped where decision has api.IC_DROP_FIRST, row 0 of
+    initial [n_paths][4][4] put in front where it has api.IC_PREPEND.  waypoints [n_vertices][4] are addressed by vertex_offsets
+    [n_paths + 1] int32; a path may request no waypoint or one.  Differentiable in waypoints and in row 0 of initial (copies; a
+    dropped vertex gets a zero row).  The edited batch is what a plan is created on (offsets minus arange, once every path has two
+    vertices).  One readback (the offsets) per call."""
+    return _PrependInitialCondition.apply(plan, waypoints, initial, vertex_offsets, decision, stop_at)
+
+
+class _SplicePrediction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, samples, pred_position, n_samples, status, fixed):
+        s, pp, n = _f64(samples), _f64(pred_position), _i32(n_samples)
+        P = plan.n_paths
+        if s.dim() != 3 or s.shape[0] != P or s.shape[2] != api.N_DIM or pp.dim() != 3 or pp.shape[0] != P or pp.shape[2] != api.N_DIM:
+            raise ValueError("samples must be [n_paths][capacity][4] and the prediction's positions [n_paths][pred_capacity][4]")
+        st = None if status is None else _i32(status)
+        dec, k, age, n_pred = _i32(fixed["decision"]), _i32(fixed["sample_offset"]), _f64(fixed["prediction_age"]), _i32(fixed["n_pred"])
+        # (the kernel writes the rows a live path has; the rows behind them and the rows of a path with status <= 0 stay zero)
+        out = torch.zeros_like(s)
+        n_out = torch.empty_like(n)
+        st_out = torch.empty_like(n)
+        plan.ctx.use_torch_stream()
+        plan.splice_prediction(s, n, dec, k, age, pp, n_pred, samples_out=out, n_samples_out=n_out, status=st, status_out=st_out)
+        ctx.plan, ctx.status, ctx.shapes = plan, st, (s.shape, pp.shape)
+        ctx.save_for_backward(n, dec, k, age, n_pred)
+        ctx.mark_non_differentiable(n_out, st_out)
+        ctx.set_materialize_grads(False)
+        return out, n_out, st_out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, *_):
+        n, dec, k, age, n_pred = ctx.saved_tensors
+        if grad_out is None or not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+            return (None,) * 6
+        plan = ctx.plan
+        gs = torch.empty(ctx.shapes[0], dtype=torch.float64, device=n.device)
+        gp = torch.empty(ctx.shapes[1], dtype=torch.float64, device=n.device)
+        plan.ctx.use_torch_stream()
+        plan.splice_prediction_vjp(n, dec, k, age, n_pred, grad_out.to(torch.float64).contiguous(), gs, gp, status=ctx.status)
+        return None, gs, gp, None, None, None
+
+
+def splice_prediction(plan, samples, n_samples, decision, sample_offset, prediction_age, pred_position, n_pred, status=None):
+    """(samples [n_paths][capacity][4], n_samples [n_paths] int32, status [n_paths] int32) of Plan.splice_prediction, out of
+    place: the first k = sample_offset rows of the prediction's positions in front of the samples of every live path from the
+    future whose k exceeds the prediction's current index; every other live path's rows copied; rows behind a path's count and
+    the rows of a path with status <= 0 are zero.  A count above the capacity means nothing was spliced; status -2 means the
+    prediction has fewer than k rows.  Differentiable in samples and pred_position [n_paths][pred_capacity][4] (copies); the
+    decision, k and the counts are held fixed."""
+    fixed = dict(decision=decision, sample_offset=sample_offset, prediction_age=prediction_age, n_pred=n_pred)
+    return _SplicePrediction.apply(plan, samples, pred_position, n_samples, status, fixed)
+
+
 class _PathEdit(torch.autograd.Function):
     """both edit steps: thin (segment_max None) or subdivide; the outputs cut to the edited batch's size, which the forward reads
     back with the offsets"""

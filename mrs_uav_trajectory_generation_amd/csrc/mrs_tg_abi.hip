@@ -53,7 +53,7 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 25;  // kernel_id 0 .. 24 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 31;  // kernel_id 0 .. 30 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
   long long ev_count[kTimedKernels] = {};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
@@ -196,7 +196,7 @@ int mrs_tg_capabilities(void) {
   return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE |
          MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE | MRS_TG_CAP_DEVIATION |
          MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE | MRS_TG_CAP_BACA | MRS_TG_CAP_FALLBACK_SAMPLE |
-         MRS_TG_CAP_PATH_EDIT | MRS_TG_CAP_TRAVEL_HEADING;
+         MRS_TG_CAP_PATH_EDIT | MRS_TG_CAP_TRAVEL_HEADING | MRS_TG_CAP_INITIAL_CONDITION;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1366,6 +1366,160 @@ int mrs_tg_plan_travel_heading_vjp(mrs_tg_plan* plan, const double* samples, con
   ProfileScope ps(ctx, 24);
   HIP_TRY(ctx, mrs_tg::launch_travel_heading_vjp(plan->view.n_paths, samples, n_samples, sample_capacity, status, min_step, grad_out,
                                                  grad_samples, ctx->stream));
+  return MRS_TG_OK;
+}
+
+// ---- initial condition, prepend and prediction splice as plan steps (mrs_tg_initial.hip) ------------------------------------
+
+// what the six calls check of their sizes before any launch: no negative capacity, no sum beyond int32
+static int initial_sizes(mrs_tg_ctx* ctx, const mrs_tg_plan* plan, long long n_vertices, long long sample_capacity,
+                         long long pred_capacity) {
+  if (n_vertices < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_vertices %lld is negative", n_vertices);
+  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %lld is negative", sample_capacity);
+  if (pred_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "pred_capacity %lld is negative", pred_capacity);
+  if (n_vertices + plan->view.n_paths > 2147483647ll)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "%lld requested vertices and %d prepended ones do not fit int32", n_vertices,
+                plan->view.n_paths);
+  if (sample_capacity + pred_capacity > 2147483647ll)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %lld + pred_capacity %lld does not fit int32", sample_capacity,
+                pred_capacity);
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_initial_condition(mrs_tg_plan* plan, const int32_t* flags, const double* tracker, const double* tracker_age,
+                                  const double* uav_pose, double takeoff_height, const double* path_time_offset,
+                                  const int32_t* vertex_offsets, const double* pred_position, const double* pred_velocity,
+                                  const double* pred_acceleration, const double* pred_jerk, const int32_t* n_pred,
+                                  int32_t pred_capacity, int32_t* decision_out, int32_t* sample_offset_out, double* initial_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (const int rc = initial_sizes(ctx, plan, 0, 0, pred_capacity); rc != MRS_TG_OK) return rc;
+  if (!flags || !tracker || !tracker_age || !uav_pose || !path_time_offset || !vertex_offsets || !n_pred)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
+                "flags_dev, tracker_dev, tracker_age_dev, uav_pose_dev, path_time_offset_dev, vertex_offsets_dev and n_pred_dev "
+                "are required");
+  if (pred_capacity > 0 && (!pred_position || !pred_velocity || !pred_acceleration || !pred_jerk))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "a prediction with rows needs all four arrays");
+  if (!decision_out || !sample_offset_out || !initial_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "decision_out_dev, sample_offset_out_dev and initial_out_dev are required");
+  if (std::isnan(takeoff_height)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "takeoff_height is NaN");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 25);
+  const double* const pred[4] = {pred_position, pred_velocity, pred_acceleration, pred_jerk};
+  HIP_TRY(ctx, mrs_tg::launch_initial_condition(plan->view.n_paths, flags, tracker, tracker_age, uav_pose, takeoff_height,
+                                                path_time_offset, vertex_offsets, pred, n_pred, pred_capacity, decision_out,
+                                                sample_offset_out, initial_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_initial_condition_vjp(mrs_tg_plan* plan, const int32_t* decision, const int32_t* sample_offset,
+                                      const double* grad_initial, int32_t pred_capacity, double* grad_tracker_out,
+                                      double* grad_uav_out, double* grad_pred_position_out, double* grad_pred_velocity_out,
+                                      double* grad_pred_acceleration_out, double* grad_pred_jerk_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (const int rc = initial_sizes(ctx, plan, 0, 0, pred_capacity); rc != MRS_TG_OK) return rc;
+  if (!decision || !sample_offset || !grad_initial || !grad_tracker_out || !grad_uav_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
+                "decision_dev, sample_offset_dev, grad_initial_dev, grad_tracker_out_dev and grad_uav_out_dev are required");
+  if (pred_capacity > 0 && (!grad_pred_position_out || !grad_pred_velocity_out || !grad_pred_acceleration_out || !grad_pred_jerk_out))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "a prediction with rows needs all four gradient arrays");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 29);
+  double* const grad_pred[4] = {grad_pred_position_out, grad_pred_velocity_out, grad_pred_acceleration_out, grad_pred_jerk_out};
+  HIP_TRY(ctx, mrs_tg::launch_initial_condition_vjp(plan->view.n_paths, decision, sample_offset, grad_initial, pred_capacity,
+                                                    grad_tracker_out, grad_uav_out, grad_pred, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_prepend_initial_condition(mrs_tg_plan* plan, const int32_t* vertex_offsets, int32_t n_vertices,
+                                          const double* waypoints, const uint8_t* stop_at, const int32_t* decision,
+                                          const double* initial, int32_t* vertex_offsets_out, double* waypoints_out,
+                                          uint8_t* stop_at_out, int32_t* source_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (const int rc = initial_sizes(ctx, plan, n_vertices, 0, 0); rc != MRS_TG_OK) return rc;
+  if (!vertex_offsets || !decision || !initial || !vertex_offsets_out || !waypoints_out || (n_vertices > 0 && !waypoints))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
+                "vertex_offsets_dev, waypoints_dev, decision_dev, initial_dev, vertex_offsets_out_dev and waypoints_out_dev are "
+                "required");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 26);
+  HIP_TRY(ctx, mrs_tg::launch_prepend_initial_condition(plan->view.n_paths, n_vertices, vertex_offsets, waypoints, stop_at, decision,
+                                                        initial, vertex_offsets_out, waypoints_out, stop_at_out, source_out,
+                                                        ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_prepend_initial_condition_vjp(mrs_tg_plan* plan, const int32_t* vertex_offsets, int32_t n_vertices,
+                                              const int32_t* decision, const int32_t* vertex_offsets_edited, int32_t n_vertices_edited,
+                                              const double* grad_waypoints_edited, double* grad_waypoints_out,
+                                              double* grad_initial_row_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (const int rc = initial_sizes(ctx, plan, n_vertices, 0, 0); rc != MRS_TG_OK) return rc;
+  if (n_vertices_edited < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_vertices_edited %d is negative", n_vertices_edited);
+  if (!vertex_offsets || !decision || !vertex_offsets_edited || !grad_initial_row_out || (n_vertices > 0 && !grad_waypoints_out) ||
+      (n_vertices_edited > 0 && !grad_waypoints_edited))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
+                "vertex_offsets_dev, decision_dev, vertex_offsets_edited_dev, grad_waypoints_edited_dev, grad_waypoints_out_dev and "
+                "grad_initial_row_out_dev are required");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 30);
+  HIP_TRY(ctx, mrs_tg::launch_prepend_initial_condition_vjp(plan->view.n_paths, n_vertices, vertex_offsets, decision,
+                                                            vertex_offsets_edited, n_vertices_edited, grad_waypoints_edited,
+                                                            grad_waypoints_out, grad_initial_row_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+// what the splice and its backward pass check of the arrays they share
+static int splice_arguments(mrs_tg_ctx* ctx, const mrs_tg_plan* plan, const int32_t* n_samples, int32_t sample_capacity,
+                            const int32_t* decision, const int32_t* sample_offset, const double* prediction_age,
+                            const int32_t* n_pred, int32_t pred_capacity) {
+  if (const int rc = initial_sizes(ctx, plan, 0, sample_capacity, pred_capacity); rc != MRS_TG_OK) return rc;
+  if (!n_samples || !decision || !sample_offset || !prediction_age || !n_pred)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
+                "n_samples_dev, decision_dev, sample_offset_dev, prediction_age_dev and n_pred_dev are required");
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_splice_prediction(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                  const int32_t* status, const int32_t* decision, const int32_t* sample_offset,
+                                  const double* prediction_age, const double* pred_position, const int32_t* n_pred,
+                                  int32_t pred_capacity, double* samples_out, int32_t* n_samples_out, int32_t* status_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (const int rc = splice_arguments(ctx, plan, n_samples, sample_capacity, decision, sample_offset, prediction_age, n_pred,
+                                      pred_capacity);
+      rc != MRS_TG_OK)
+    return rc;
+  if (!n_samples_out || (sample_capacity > 0 && (!samples || !samples_out)) || (pred_capacity > 0 && !pred_position))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, pred_position_dev, samples_out_dev and n_samples_out_dev are required");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 27);
+  HIP_TRY(ctx, mrs_tg::launch_splice_prediction(plan->view.n_paths, samples, n_samples, sample_capacity, status, decision,
+                                                sample_offset, prediction_age, pred_position, n_pred, pred_capacity, samples_out,
+                                                n_samples_out, status_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_splice_prediction_vjp(mrs_tg_plan* plan, const int32_t* n_samples, int32_t sample_capacity, const int32_t* status,
+                                      const int32_t* decision, const int32_t* sample_offset, const double* prediction_age,
+                                      const int32_t* n_pred, int32_t pred_capacity, const double* grad_out, double* grad_samples_out,
+                                      double* grad_pred_position_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (const int rc = splice_arguments(ctx, plan, n_samples, sample_capacity, decision, sample_offset, prediction_age, n_pred,
+                                      pred_capacity);
+      rc != MRS_TG_OK)
+    return rc;
+  if ((sample_capacity > 0 && (!grad_out || !grad_samples_out)) || (pred_capacity > 0 && !grad_pred_position_out))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_out_dev, grad_samples_out_dev and grad_pred_position_out_dev are required");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 28);
+  HIP_TRY(ctx, mrs_tg::launch_splice_prediction_vjp(plan->view.n_paths, n_samples, sample_capacity, status, decision, sample_offset,
+                                                    prediction_age, n_pred, pred_capacity, grad_out, grad_samples_out,
+                                                    grad_pred_position_out, ctx->stream));
   return MRS_TG_OK;
 }
 

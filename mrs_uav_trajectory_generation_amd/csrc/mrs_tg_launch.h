@@ -277,6 +277,40 @@ hipError_t launch_insert_midpoints(const BatchView& b, const double* waypoints, 
                                    hipStream_t stream);
 hipError_t launch_path_edit_vjp(const BatchView& b, const int32_t* offsets, const int32_t* source, const uint8_t* inserted,
                                 const double* grad_edited, double* grad_waypoints, hipStream_t stream);
+// the one workgroup that turns the counts at offsets[1 ..] into offsets (vertex_offsets_kernel), for an edit that counts by itself;
+// start / stop: the events of the caller's multi-launch timing that fall on this launch (may be null)
+hipError_t launch_vertex_offsets(int n_paths, int32_t* offsets, hipEvent_t start, hipEvent_t stop, hipStream_t stream);
+// mrs_tg_plan_initial_condition, mrs_tg_plan_prepend_initial_condition, mrs_tg_plan_splice_prediction and their backward passes
+// (mrs_tg_initial.hip, mrs_tg_initial.hpp): the state a trajectory starts from, per path, from the tracker command, the UAV state
+// or row k of the prediction pred[0 .. 3] = position, velocity, acceleration, jerk [n_paths][pred_capacity][4]; the edit that
+// drops the first requested vertex and puts row 0 of that state in front, packed as the path edits pack (three launches, timed
+// from the first to the last); the k prediction rows in front of the samples of a path from the future, in place or out of
+// place.  The requested vertices are addressed by vertex_offsets [n_paths + 1] (n_vertices = vertex_offsets[n_paths]); a path
+// may have none.  Backward: copies and zeros.  Each timed as the kernel family of the pending ProfileScope.
+hipError_t launch_initial_condition(int n_paths, const int32_t* flags, const double* tracker, const double* tracker_age,
+                                    const double* uav_pose, double takeoff_height, const double* path_time_offset,
+                                    const int32_t* vertex_offsets, const double* const pred[4], const int32_t* n_pred,
+                                    int pred_capacity, int32_t* decision_out, int32_t* sample_offset_out, double* initial_out,
+                                    hipStream_t stream);
+hipError_t launch_initial_condition_vjp(int n_paths, const int32_t* decision, const int32_t* sample_offset,
+                                        const double* grad_initial, int pred_capacity, double* grad_tracker, double* grad_uav,
+                                        double* const grad_pred[4], hipStream_t stream);
+hipError_t launch_prepend_initial_condition(int n_paths, int n_vertices, const int32_t* vertex_offsets, const double* waypoints,
+                                            const uint8_t* stop_at, const int32_t* decision, const double* initial,
+                                            int32_t* offsets, double* waypoints_out, uint8_t* stop_out, int32_t* source_out,
+                                            hipStream_t stream);
+hipError_t launch_prepend_initial_condition_vjp(int n_paths, int n_vertices, const int32_t* vertex_offsets, const int32_t* decision,
+                                                const int32_t* offsets, int n_edited, const double* grad_edited,
+                                                double* grad_waypoints, double* grad_initial_row, hipStream_t stream);
+hipError_t launch_splice_prediction(int n_paths, const double* samples, const int32_t* n_samples, int capacity,
+                                    const int32_t* status, const int32_t* decision, const int32_t* sample_offset,
+                                    const double* prediction_age, const double* pred_position, const int32_t* n_pred,
+                                    int pred_capacity, double* samples_out, int32_t* n_samples_out, int32_t* status_out,
+                                    hipStream_t stream);
+hipError_t launch_splice_prediction_vjp(int n_paths, const int32_t* n_samples, int capacity, const int32_t* status,
+                                        const int32_t* decision, const int32_t* sample_offset, const double* prediction_age,
+                                        const int32_t* n_pred, int pred_capacity, const double* grad_out, double* grad_samples,
+                                        double* grad_pred_position, hipStream_t stream);
 // mrs_tg_plan_travel_heading / mrs_tg_plan_travel_heading_vjp (mrs_tg_heading.hip): the heading of the rows 0 .. n-2 of samples
 // [n_paths][capacity][4] set to the direction of the step to the next row, a row that moves less than min_step keeping the
 // heading in front of it (samples_out may be samples; source_out [n_paths][capacity] may be NULL); and its backward pass,

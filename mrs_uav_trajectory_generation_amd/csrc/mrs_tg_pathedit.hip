@@ -41,17 +41,6 @@ __device__ __forceinline__ int wave_inclusive_sum(int v, int lane) {
   return v;
 }
 
-// the largest p in [0, n) with first[p] <= x (first non-decreasing, first[0] <= x)
-__device__ __forceinline__ int last_not_above(const int32_t* __restrict__ first, int n, int x) {
-  int lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (first[mid] <= x) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(64) void thin_path_kernel(BatchView b, const double* __restrict__ waypoints, pathq::ThinOptions o,
@@ -188,6 +177,11 @@ __global__ __launch_bounds__(kWriteThreads) void path_edit_vjp_kernel(BatchView 
   out[1] = hi;
 }
 
+hipError_t launch_vertex_offsets(int n_paths, int32_t* offsets, hipEvent_t start, hipEvent_t stop, hipStream_t stream) {
+  MRS_TG_LAUNCH_EXT(vertex_offsets_kernel, dim3(1), dim3(kPathEditScanChunk), 0, stream, start, stop, 0, n_paths, offsets);
+  return hipGetLastError();
+}
+
 namespace {
 
 // the launches behind the decision kernel: the offsets, then the rows; `kt` carries the call's timer from the first launch to the last
@@ -195,9 +189,9 @@ hipError_t finish_edit(bool subdivide, const BatchView& b, const KernelTimer& kt
                        const uint8_t* stop_at, const int32_t* ws, int upper, int32_t* offsets, double* waypoints_out,
                        uint8_t* stop_out, int32_t* source_out, uint8_t* inserted_out, hipStream_t stream) {
   const bool rows = b.n_paths > 0 && upper > 0;
-  MRS_TG_LAUNCH_EXT(vertex_offsets_kernel, dim3(1), dim3(kPathEditScanChunk), 0, stream, first_launch ? kt.start : nullptr,
-                    rows ? nullptr : kt.stop, 0, b.n_paths, offsets);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  if (hipError_t e = launch_vertex_offsets(b.n_paths, offsets, first_launch ? kt.start : nullptr, rows ? nullptr : kt.stop, stream);
+      e != hipSuccess)
+    return e;
   if (!rows) return hipSuccess;
   const auto write = subdivide ? MRS_TG_KERNEL(edit_write_kernel<true>) : MRS_TG_KERNEL(edit_write_kernel<false>);
   MRS_TG_LAUNCH_EXT(write, dim3(cdiv(upper, kWriteThreads)), dim3(kWriteThreads), 0, stream, nullptr, kt.stop, 0, b, waypoints,

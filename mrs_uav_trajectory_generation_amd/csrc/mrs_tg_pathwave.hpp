@@ -1,5 +1,5 @@
 // mrs_tg_pathwave.hpp -- what the kernels that give ONE WAVEFRONT ONE PATH share around their own loops (mrs_tg_sample_vjp.hip,
-// mrs_tg_evaluate.hip, mrs_tg_deviation.hip, mrs_tg_passage.hip, mrs_tg_heading.hip).  Device only; only what they spell the same way AND compile
+// mrs_tg_evaluate.hip, mrs_tg_deviation.hip, mrs_tg_passage.hip, mrs_tg_heading.hip, mrs_tg_pathedit.hip, mrs_tg_initial.hip).  Device only; only what they spell the same way AND compile
 // to the same code through a function: the chunk loops and the loops that stage a path into LDS stay written out.
 #pragma once
 #include "mrs_tg_device.hpp"
@@ -15,6 +15,18 @@ __device__ __forceinline__ bool path_live(const int32_t* status, int p) { return
 __device__ __forceinline__ int live_samples(bool live, const int32_t* n_samples, int p, int capacity) {
   const int n = live ? min(n_samples[p], capacity) : 0;
   return n < 0 ? 0 : n;
+}
+
+// the largest p in [0, n) with first[p] <= x (first non-decreasing, first[0] <= x): the path of an element of a packed batch from
+// the batch's offsets, a path without elements never being the answer for an element of a path behind it
+__device__ __forceinline__ int last_not_above(const int32_t* __restrict__ first, int n, int x) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (first[mid] <= x) lo = mid;
+    else hi = mid;
+  }
+  return lo;
 }
 
 __device__ __forceinline__ double wave_max(double v) {
