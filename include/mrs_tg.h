@@ -216,10 +216,31 @@ enum {
   MRS_TG_CAP_TRAVEL_HEADING = 8192,   /* mrs_tg_plan_travel_heading and mrs_tg_plan_travel_heading_vjp are exported: the heading
                                          along the direction of travel (override_heading_atan2) as a plan step and its backward
                                          pass */
-  MRS_TG_CAP_INITIAL_CONDITION = 16384 /* mrs_tg_plan_initial_condition, mrs_tg_plan_prepend_initial_condition,
+  MRS_TG_CAP_INITIAL_CONDITION = 16384, /* mrs_tg_plan_initial_condition, mrs_tg_plan_prepend_initial_condition,
                                          mrs_tg_plan_splice_prediction and their three backward passes are exported: where a
                                          trajectory starts (prepareInitialCondition), the waypoint put in front of the request
                                          and the prediction in front of a trajectory from the future, as plan steps */
+  MRS_TG_CAP_REQUEST = 32768            /* mrs_tg_plan_request_vertices, mrs_tg_plan_request_limits and their two backward passes
+                                         are exported: the vertices and the limits findTrajectory derives from a request, as plan
+                                         steps */
+};
+
+/* mrs_tg_plan_request_limits' flags_dev: what the request asks of its limits */
+enum {
+  MRS_TG_REQ_OVERRIDE = 1,      /* override_constraints: the six override values replace the horizontal and vertical limits */
+  MRS_TG_REQ_RELAX_HEADING = 2  /* relax_heading: the three heading limits become (double)FLT_MAX */
+};
+
+/* mrs_tg_plan_request_limits' branch_out_dev: which branches the limits of a path took, as bits; what its backward pass is
+ * driven by */
+enum {
+  MRS_TG_LIM_OVERRIDDEN = 1,       /* the override replaced the six values */
+  MRS_TG_LIM_OVERRIDE_REFUSED = 2, /* the override was asked for and refused: the state is not strictly inside it (:1001-1008) */
+  MRS_TG_LIM_RELAXED = 4,          /* the heading limits were relaxed */
+  MRS_TG_LIM_V_DESCENDING = 8,     /* the vertical speed of the constraints is the descending one (strictly smaller) */
+  MRS_TG_LIM_A_DESCENDING = 16,    /* ... the vertical acceleration */
+  MRS_TG_LIM_J_DESCENDING = 32,    /* ... the vertical jerk */
+  MRS_TG_LIM_FALLBACK = 64         /* findTrajectoryFallback's variant: no can_change test, the two factors applied */
 };
 
 /* mrs_tg_plan_initial_condition's decision_out_dev: what prepareInitialCondition and the first-waypoint rule decided for a
@@ -1021,6 +1042,69 @@ int mrs_tg_plan_splice_prediction_vjp(mrs_tg_plan* plan, const int32_t* n_sample
                                       const double* grad_out_dev, double* grad_samples_out_dev,
                                       double* grad_pred_position_out_dev);
 
+/* The vertices findTrajectory builds from a request (mrs_trajectory_generation.cpp:923-977), as a plan step
+ * (MRS_TG_CAP_REQUEST; request_vertices_kernel, csrc/mrs_tg_request.hpp); the batched form of the
+ * vertex construction of mrs_tg_optimize_paths' host loop, the same bits.  waypoints_dev [sum V][4] are the RAW waypoints of
+ * the plan's paths; stop_at_dev [sum V] (may be NULL: none); has_state_dev [n_paths] (may be NULL: no path has a state) with
+ * state_dev [n_paths][4][4], the block mrs_tg_plan_initial_condition writes: row 0 column 3 the heading, rows 1 .. 3 velocity,
+ * acceleration and jerk of (x, y, z, heading); a block is read only where has_state is non-zero.  Per path of V vertices:
+ *   last = has_state ? state[0][3] : raw[0][3];   for every vertex  h_i = unwrap(raw[i][3], last), last = h_i
+ * (sradians::unwrap, fmod and additions: the host's bits), waypoints_out[i] = (x, y, z, h_i), mask[i][0] = 1,
+ * values[i][0][:] = waypoints_out[i]; the first and the last vertex have mask[1 .. d] = 1; the first vertex of a path with a
+ * state has mask[1 .. 3] = 1 (for d = 2 too) and values[1 .. 3][:] = state[1 .. 3][:]; a vertex between the ends with stop_at
+ * has mask[1 .. 3] = 1; stop_at on an end changes nothing; every other mask byte is 0 and every other value +0.0.
+ * waypoints_out_dev [sum V][4], fixed_mask_out_dev [sum V][5] and fixed_values_out_dev [sum V][5][4] may each be NULL, not all;
+ * waypoints_out_dev may be waypoints_dev.  One launch, one wavefront per path, the chain a wave-uniform loop over chunks of 64
+ * vertices; no LDS, no atomics, no workspace; every element written exactly once.
+ * MRS_TG_ERR_INVALID_ARG, before any launch: waypoints_dev NULL, derivative_to_optimize outside 2 .. 4, has_state_dev without
+ * state_dev, no output at all.  Device pointers (16-byte aligned), asynchronous on the context's stream. */
+int mrs_tg_plan_request_vertices(mrs_tg_plan* plan, const double* waypoints_dev, const uint8_t* stop_at_dev,
+                                 const uint8_t* has_state_dev, const double* state_dev, int32_t derivative_to_optimize,
+                                 double* waypoints_out_dev, uint8_t* fixed_mask_out_dev, double* fixed_values_out_dev);
+/* Its backward pass (request_vertices_vjp_kernel), every branch held fixed: the unwrap adds a piecewise-constant multiple of
+ * 2 pi, so dh_i/draw_i = 1 and dh_i/d(state heading) = 0.  From grad_waypoints_dev [sum V][4] (on waypoints_out) and
+ * grad_fixed_values_dev [sum V][5][4] (each may be NULL = zero, not both):
+ *   grad_waypoints_out[i][:] = grad_waypoints[i][:] + grad_fixed_values[i][0][:]          (one addition)
+ *   grad_state_out[p][1 .. 3][:] = grad_fixed_values[first vertex of p][1 .. 3][:] where the path has a state, else zeros;
+ *   grad_state_out[p][0][:] = 0.
+ * Upstreams on value slots the forward writes as constant zeros are dropped.  grad_waypoints_out_dev [sum V][4] and
+ * grad_state_out_dev [n_paths][4][4] may each be NULL, not both.  One lane per vertex; every element written exactly once, zeros
+ * included; no atomics. */
+int mrs_tg_plan_request_vertices_vjp(mrs_tg_plan* plan, const uint8_t* has_state_dev, const double* grad_waypoints_dev,
+                                     const double* grad_fixed_values_dev, double* grad_waypoints_out_dev,
+                                     double* grad_state_out_dev);
+/* The limits findTrajectory derives from a request (:981-1038; fallback != 0: findTrajectoryFallback's variant, :1252-1299), as a
+ * plan step (request_limits_kernel, one lane per path); the plan contributes its path count and its context.
+ *   constraints_dev [n_paths][12]  horizontal speed, acceleration, jerk; vertical ascending / descending speed; ascending /
+ *                                  descending acceleration; ascending / descending jerk; heading speed, acceleration, jerk
+ *   override_dev [n_paths][6]      override velocity h, v; acceleration h, v; jerk h, v, as the reference's override_max_*_
+ *                                  members hold them (its callbacks put the horizontal jerk into the vertical member: that is
+ *                                  the caller's business); may be NULL together with flags_dev
+ *   flags_dev [n_paths]            MRS_TG_REQ_*; NULL = 0
+ *   has_state_dev, state_dev       as mrs_tg_plan_request_vertices takes them
+ * limits_out_dev [n_paths][9] = {v_h, v_v, v_hdg, a_h, a_v, a_hdg, j_h, j_v, j_hdg}.  A vertical limit is
+ * (desc < asc) ? desc : asc (a tie takes the ascending value).  With MRS_TG_REQ_OVERRIDE and fallback == 0 the override replaces
+ * the six horizontal and vertical values if can_change holds: true without a state, else hypot(vx, vy) < o[0],
+ * hypot(ax, ay) < o[2], hypot(jx, jy) < o[4], |vz| < o[1], |az| < o[3], |jz| < o[5], all strict (a NaN refuses); with
+ * fallback != 0 it replaces them unconditionally.  MRS_TG_REQ_RELAX_HEADING: the three heading limits are (double)FLT_MAX.
+ * fallback != 0: afterwards entries 0 and 1 are multiplied by speed_factor, 3 and 4 by accel_factor.  hypot is the device's:
+ * the decision can differ from the host's only for a state within an ulp of the override.  branch_out_dev [n_paths]
+ * (MRS_TG_LIM_*; the *_DESCENDING bits say which side of a pair the constraints' minimum is, overridden or not).  Either output
+ * may be NULL, not both.  MRS_TG_ERR_INVALID_ARG, before any launch: constraints_dev NULL, flags_dev without override_dev,
+ * has_state_dev without state_dev, no output at all. */
+int mrs_tg_plan_request_limits(mrs_tg_plan* plan, const double* constraints_dev, const double* override_dev,
+                               const int32_t* flags_dev, const uint8_t* has_state_dev, const double* state_dev, int32_t fallback,
+                               double speed_factor, double accel_factor, double* limits_out_dev, int32_t* branch_out_dev);
+/* Its backward pass (request_limits_vjp_kernel), the branch word held fixed; fallback and the factors are the forward's.  With
+ * g_k = grad_limits[k], times the fallback's factor on k = 0, 1, 3, 4: the entry that supplied limit k gets g_k -- the override
+ * entry where MRS_TG_LIM_OVERRIDDEN is set, else the constraint (the winning side of a vertical pair); a relaxed heading limit
+ * gives nothing; the state gets no gradient.  grad_constraints_out_dev [n_paths][12] and grad_override_out_dev [n_paths][6] may
+ * each be NULL, not both; every element written exactly once, zeros included.  MRS_TG_ERR_INVALID_ARG: branch_dev or
+ * grad_limits_dev NULL (no upstream), no output at all. */
+int mrs_tg_plan_request_limits_vjp(mrs_tg_plan* plan, const int32_t* branch_dev, int32_t fallback, double speed_factor,
+                                   double accel_factor, const double* grad_limits_dev, double* grad_constraints_out_dev,
+                                   double* grad_override_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
@@ -1039,7 +1123,9 @@ int mrs_tg_plan_splice_prediction_vjp(mrs_tg_plan* plan, const int32_t* n_sample
  * (mrs_tg_plan_travel_heading_vjp), 25 the initial condition (mrs_tg_plan_initial_condition), 26 the prepended waypoint
  * (mrs_tg_plan_prepend_initial_condition, timed from its first launch to its last), 27 the prediction splice
  * (mrs_tg_plan_splice_prediction), 28, 29, 30 their backward passes (mrs_tg_plan_splice_prediction_vjp,
- * mrs_tg_plan_initial_condition_vjp, mrs_tg_plan_prepend_initial_condition_vjp): thirty-one ids, 0 .. 30.
+ * mrs_tg_plan_initial_condition_vjp, mrs_tg_plan_prepend_initial_condition_vjp), 31 the request's vertices
+ * (mrs_tg_plan_request_vertices), 32 their backward pass (mrs_tg_plan_request_vertices_vjp), 33 the request's limits
+ * (mrs_tg_plan_request_limits), 34 their backward pass (mrs_tg_plan_request_limits_vjp): thirty-five ids, 0 .. 34.
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

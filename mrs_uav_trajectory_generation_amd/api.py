@@ -54,6 +54,7 @@ KERNEL_PREPROCESS_PATH, KERNEL_INSERT_MIDPOINTS, KERNEL_PATH_EDIT_VJP = 20, 21, 
 KERNEL_TRAVEL_HEADING, KERNEL_TRAVEL_HEADING_VJP = 23, 24
 KERNEL_INITIAL_CONDITION, KERNEL_PREPEND_INITIAL_CONDITION, KERNEL_SPLICE_PREDICTION = 25, 26, 27
 KERNEL_SPLICE_PREDICTION_VJP, KERNEL_INITIAL_CONDITION_VJP, KERNEL_PREPEND_INITIAL_CONDITION_VJP = 28, 29, 30
+KERNEL_REQUEST_VERTICES, KERNEL_REQUEST_VERTICES_VJP, KERNEL_REQUEST_LIMITS, KERNEL_REQUEST_LIMITS_VJP = 31, 32, 33, 34
 
 
 class MrsTgError(RuntimeError):
@@ -122,6 +123,8 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_plan_travel_heading", "mrs_tg_plan_travel_heading_vjp",
     "mrs_tg_plan_initial_condition", "mrs_tg_plan_initial_condition_vjp", "mrs_tg_plan_prepend_initial_condition",
     "mrs_tg_plan_prepend_initial_condition_vjp", "mrs_tg_plan_splice_prediction", "mrs_tg_plan_splice_prediction_vjp",
+    "mrs_tg_plan_request_vertices", "mrs_tg_plan_request_vertices_vjp", "mrs_tg_plan_request_limits",
+    "mrs_tg_plan_request_limits_vjp",
 ]
 
 _lib = None
@@ -269,6 +272,14 @@ def load_library():
     L.mrs_tg_plan_splice_prediction.argtypes = [vp, dp, ip, C.c_int32, ip, ip, ip, dp, dp, ip, C.c_int32, dp, ip, ip]
     L.mrs_tg_plan_splice_prediction_vjp.restype = C.c_int
     L.mrs_tg_plan_splice_prediction_vjp.argtypes = [vp, ip, C.c_int32, ip, ip, ip, dp, ip, C.c_int32, dp, dp, dp]
+    L.mrs_tg_plan_request_vertices.restype = C.c_int
+    L.mrs_tg_plan_request_vertices.argtypes = [vp, dp, bp, bp, dp, C.c_int32, dp, bp, dp]
+    L.mrs_tg_plan_request_vertices_vjp.restype = C.c_int
+    L.mrs_tg_plan_request_vertices_vjp.argtypes = [vp, bp, dp, dp, dp, dp]
+    L.mrs_tg_plan_request_limits.restype = C.c_int
+    L.mrs_tg_plan_request_limits.argtypes = [vp, dp, dp, ip, bp, dp, C.c_int32, C.c_double, C.c_double, dp, ip]
+    L.mrs_tg_plan_request_limits_vjp.restype = C.c_int
+    L.mrs_tg_plan_request_limits_vjp.argtypes = [vp, ip, C.c_int32, C.c_double, C.c_double, dp, dp, dp]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -331,6 +342,10 @@ CAP_INITIAL_CONDITION = 16384  # MRS_TG_CAP_INITIAL_CONDITION: Plan.initial_cond
 # Plan.initial_condition's decision word (MRS_TG_IC_*) and its flags input (bit 0 tracker command, bit 1 UAV state, bit 2 dont_prepend)
 IC_PREPEND, IC_FROM_FUTURE, IC_DROP_FIRST, IC_FROM_TRACKER, IC_FROM_UAV, IC_FROM_PREDICTION, IC_INVALID = 1, 2, 4, 8, 16, 32, 64
 IC_FLAG_TRACKER, IC_FLAG_UAV, IC_FLAG_DONT_PREPEND = 1, 2, 4
+CAP_REQUEST = 32768   # MRS_TG_CAP_REQUEST: Plan.request_vertices, Plan.request_limits (findTrajectory's vertices and limits as plan steps) and their two backward passes
+# Plan.request_limits' flags input (MRS_TG_REQ_*) and its branch word (MRS_TG_LIM_*)
+REQ_OVERRIDE, REQ_RELAX_HEADING = 1, 2
+LIM_OVERRIDDEN, LIM_OVERRIDE_REFUSED, LIM_RELAXED, LIM_V_DESCENDING, LIM_A_DESCENDING, LIM_J_DESCENDING, LIM_FALLBACK = 1, 2, 4, 8, 16, 32, 64
 # Plan.estimate_times_baca_vjp's flags: the branches of the Baca estimate a segment's time took, as bits (MRS_TG_BACA_*)
 BACA_V_VERTICAL, BACA_A_VERTICAL, BACA_J_VERTICAL, BACA_T1_CAPPED, BACA_T2_CAPPED = 1, 2, 4, 8, 16
 BACA_DOT1_CLAMPED, BACA_DOT2_CLAMPED, BACA_FLOOR, BACA_HEADING, BACA_HEADING_CRUISE, BACA_HEADING_ACC = 32, 64, 128, 256, 512, 1024
@@ -1191,6 +1206,49 @@ class Plan:
             self._h, _t_ptr(n_samples), int(grad_out.shape[1]), _t_ptr(status), _t_ptr(decision), _t_ptr(sample_offset),
             _t_ptr(prediction_age), _t_ptr(n_pred), int(grad_pred_position.shape[1]), _t_ptr(grad_out), _t_ptr(grad_samples),
             _t_ptr(grad_pred_position)), "mrs_tg_plan_splice_prediction_vjp")
+
+    def request_vertices(self, waypoints, waypoints_out=None, fixed_mask=None, fixed_values=None, stop_at=None, has_state=None,
+                         state=None, derivative_to_optimize=4):
+        """mrs_tg_plan_request_vertices: the vertices findTrajectory builds (:923-977) from the RAW waypoints [sum V][4] -- the
+        headings unwrapped along every path, the chain starting from the heading of state [n_paths][4][4] (row 0 column 3; rows
+        1 .. 3 velocity, acceleration, jerk) where has_state [n_paths] uint8 says the path has one, else from its first raw
+        heading -- into waypoints_out [sum V][4] (may be waypoints), fixed_mask [sum V][5] uint8 and fixed_values [sum V][5][4]
+        (each optional, not all None): positions fixed everywhere, derivatives 1 .. d at the ends, 1 .. 3 (the state's rows) at
+        the first vertex of a path with a state, 1 .. 3 (zero) at a stop_at [sum V] uint8 vertex between the ends.  Device
+        tensors; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_request_vertices(
+            self._h, _t_ptr(waypoints), _t_ptr(stop_at), _t_ptr(has_state), _t_ptr(state), int(derivative_to_optimize),
+            _t_ptr(waypoints_out), _t_ptr(fixed_mask), _t_ptr(fixed_values)), "mrs_tg_plan_request_vertices")
+
+    def request_vertices_vjp(self, grad_waypoints=None, grad_fixed_values=None, grad_waypoints_out=None, grad_state=None,
+                             has_state=None):
+        """mrs_tg_plan_request_vertices_vjp: grad_waypoints_out [sum V][4] = grad_waypoints + grad_fixed_values[:, 0] (an upstream
+        that is None counts as zero, not both) and grad_state [n_paths][4][4] (rows 1 .. 3 from the first vertex's value rows
+        where has_state, zeros elsewhere); all written, zeros included; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_request_vertices_vjp(
+            self._h, _t_ptr(has_state), _t_ptr(grad_waypoints), _t_ptr(grad_fixed_values), _t_ptr(grad_waypoints_out),
+            _t_ptr(grad_state)), "mrs_tg_plan_request_vertices_vjp")
+
+    def request_limits(self, constraints, limits=None, branch=None, override=None, flags=None, has_state=None, state=None,
+                       fallback=False, speed_factor=1.0, accel_factor=1.0):
+        """mrs_tg_plan_request_limits: limits [n_paths][9] (v, a, j x horizontal, vertical, heading) and branch [n_paths] int32
+        (LIM_*) from constraints [n_paths][12] (horizontal v, a, j; vertical ascending / descending v, a, j pairwise; heading v,
+        a, j), override [n_paths][6] (v h, v; a h, v; j h, v) with flags [n_paths] int32 (REQ_*; flags needs override) and the
+        state as request_vertices takes it: the smaller of a vertical pair, the override where can_change holds against the
+        state (fallback: always), the relaxed heading, and with fallback the speed / acceleration factors on entries 0, 1 / 3, 4.
+        Device tensors; asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_request_limits(
+            self._h, _t_ptr(constraints), _t_ptr(override), _t_ptr(flags), _t_ptr(has_state), _t_ptr(state), int(bool(fallback)),
+            float(speed_factor), float(accel_factor), _t_ptr(limits), _t_ptr(branch)), "mrs_tg_plan_request_limits")
+
+    def request_limits_vjp(self, branch, grad_limits, grad_constraints=None, grad_override=None, fallback=False, speed_factor=1.0,
+                           accel_factor=1.0):
+        """mrs_tg_plan_request_limits_vjp: grad_constraints [n_paths][12] and grad_override [n_paths][6] (all written, zeros
+        included) from grad_limits [n_paths][9], the branch word held fixed; fallback and the factors are the forward's;
+        asynchronous on the context's stream."""
+        self.ctx._check(self._L.mrs_tg_plan_request_limits_vjp(
+            self._h, _t_ptr(branch), int(bool(fallback)), float(speed_factor), float(accel_factor), _t_ptr(grad_limits),
+            _t_ptr(grad_constraints), _t_ptr(grad_override)), "mrs_tg_plan_request_limits_vjp")
 
 
 class RoundRobin:

@@ -97,6 +97,18 @@ A loss on the heading the tracker actually gets -- here: look where a point of i
     >>> valid = torch.arange(512, device=n.device)[None, :] < n[:, None] - 1  # the last row keeps its sampled yaw
     >>> bearing = torch.atan2(poi[1] - rows[..., 1], poi[0] - rows[..., 0])
     >>> ((1.0 - torch.cos(rows[..., 3] - bearing)) * valid).sum().backward()  # fv.grad, times.grad
+
+request_vertices and request_limits (Plan.request_vertices / Plan.request_limits forward, Plan.request_vertices_vjp /
+Plan.request_limits_vjp backward) are where a request becomes the solver's inputs: the headings unwrapped
+from the state's heading with the constraint mask and values, and the limits from the constraints, the override and the state.
+With them the chain starts at the RAW request and the state's velocity gets a gradient:
+
+    >>> raw = waypoints.clone().requires_grad_(); st = state.clone().requires_grad_(); c = constraints.clone().requires_grad_()
+    >>> lim = request_limits(plan, c, state=st)
+    >>> wp, mask, fv = request_vertices(plan, raw, state=st)
+    >>> times = estimate_times(plan, wp, lim)
+    >>> coeffs, _, status = solve(plan, mask, fv, times); samples, n = sample(plan, coeffs, times, 0.2, 512, status)
+    >>> ((samples[..., :3] - target) ** 2).sum().backward()            # raw.grad, st.grad (rows 1 .. 3), c.grad
 """
 import numpy as np
 import torch
@@ -780,6 +792,119 @@ def splice_prediction(plan, samples, n_samples, decision, sample_offset, predict
     decision, k and the counts are held fixed."""
     fixed = dict(decision=decision, sample_offset=sample_offset, prediction_age=prediction_age, n_pred=n_pred)
     return _SplicePrediction.apply(plan, samples, pred_position, n_samples, status, fixed)
+
+
+def _u8(t):
+    return None if t is None else t.detach().to(torch.uint8).contiguous()
+
+
+class _RequestVertices(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, waypoints, state, has_state, stop_at, derivative):
+        w = _f64(waypoints)
+        P, n_v, dev = plan.n_paths, plan.n_segments + plan.n_paths, w.device
+        if w.dim() != 2 or w.shape[0] != n_v or w.shape[1] != api.N_DIM:
+            raise ValueError("waypoints must be [sum V][4]")
+        st = None if state is None else _f64(state)
+        if st is not None and st.shape != (P, 4, 4):
+            raise ValueError("state must be [n_paths][4][4]")
+        has = None
+        if st is not None:
+            has = torch.ones(P, dtype=torch.uint8, device=dev) if has_state is None else _u8(has_state)
+            if has.shape != (P,):
+                raise ValueError("has_state must be [n_paths]")
+        unwrapped = torch.empty_like(w)
+        mask = torch.empty((n_v, 5), dtype=torch.uint8, device=dev)
+        vals = torch.empty((n_v, 5, api.N_DIM), dtype=torch.float64, device=dev)
+        plan.ctx.use_torch_stream()
+        plan.request_vertices(w, unwrapped, mask, vals, stop_at=_u8(stop_at), has_state=has, state=st,
+                              derivative_to_optimize=int(derivative))
+        ctx.plan, ctx.has = plan, has
+        ctx.mark_non_differentiable(mask)
+        ctx.set_materialize_grads(False)
+        return unwrapped, mask, vals
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_unwrapped, _grad_mask, grad_vals):
+        want_w, want_s = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if (grad_unwrapped is None and grad_vals is None) or not (want_w or want_s):
+            return (None,) * 6
+        plan, P, n_v = ctx.plan, ctx.plan.n_paths, ctx.plan.n_segments + ctx.plan.n_paths
+        dev = (grad_vals if grad_unwrapped is None else grad_unwrapped).device
+        gw = torch.empty((n_v, api.N_DIM), dtype=torch.float64, device=dev) if want_w else None
+        gs = torch.empty((P, 4, 4), dtype=torch.float64, device=dev) if want_s else None
+        plan.ctx.use_torch_stream()
+        plan.request_vertices_vjp(None if grad_unwrapped is None else grad_unwrapped.to(torch.float64).contiguous(),
+                                  None if grad_vals is None else grad_vals.to(torch.float64).contiguous(), gw, gs, has_state=ctx.has)
+        return None, gw, gs, None, None, None
+
+
+def request_vertices(plan, waypoints, state=None, has_state=None, stop_at=None, derivative_to_optimize=4):
+    """(unwrapped [sum V][4], mask [sum V][5] uint8, values [sum V][5][4]) of Plan.request_vertices: the vertices findTrajectory
+    builds from the RAW waypoints [sum V][4] of a request -- the headings unwrapped along every path, from the heading of state
+    [n_paths][4][4] (row 0 column 3; rows 1 .. 3 velocity, acceleration, jerk: the block initial_condition returns) where
+    has_state [n_paths] says so (None: every path, if state is given), the state's rows fixed at the first vertex.
+    Differentiable in waypoints and state, every branch held fixed: the unwrap adds a piecewise-constant multiple of 2 pi, so a
+    waypoint collects the gradients of its unwrapped row and of its position values, the state's rows 1 .. 3 those of the first
+    vertex's value rows, and the state's heading nothing.  With it the chain request -> vertices -> times -> solve -> samples ->
+    loss starts at the raw request."""
+    return _RequestVertices.apply(plan, waypoints, state, has_state, stop_at, derivative_to_optimize)
+
+
+class _RequestLimits(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, constraints, override, fixed):
+        c = _f64(constraints)
+        P, dev = plan.n_paths, c.device
+        if c.shape != (P, 12):
+            raise ValueError("constraints must be [n_paths][12]")
+        o = None if override is None else _f64(override)
+        if o is not None and o.shape != (P, 6):
+            raise ValueError("override must be [n_paths][6]")
+        flags = None if fixed["flags"] is None else _i32(fixed["flags"])
+        st = None if fixed["state"] is None else _f64(fixed["state"])
+        has = None
+        if st is not None:
+            has = torch.ones(P, dtype=torch.uint8, device=dev) if fixed["has_state"] is None else _u8(fixed["has_state"])
+        limits = torch.empty((P, 9), dtype=torch.float64, device=dev)
+        branch = torch.empty(P, dtype=torch.int32, device=dev)
+        ctx.factors = dict(fallback=bool(fixed["fallback"]), speed_factor=float(fixed["speed_factor"]),
+                           accel_factor=float(fixed["accel_factor"]))
+        plan.ctx.use_torch_stream()
+        plan.request_limits(c, limits, branch, override=o, flags=flags, has_state=has, state=st, **ctx.factors)
+        ctx.plan = plan
+        ctx.save_for_backward(branch)
+        ctx.mark_non_differentiable(branch)
+        ctx.set_materialize_grads(False)
+        return limits, branch
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_limits, _grad_branch):
+        want_c, want_o = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if grad_limits is None or not (want_c or want_o):
+            return None, None, None, None
+        (branch,) = ctx.saved_tensors
+        P, dev = ctx.plan.n_paths, branch.device
+        gc = torch.empty((P, 12), dtype=torch.float64, device=dev) if want_c else None
+        go = torch.empty((P, 6), dtype=torch.float64, device=dev) if want_o else None
+        ctx.plan.ctx.use_torch_stream()
+        ctx.plan.request_limits_vjp(branch, grad_limits.to(torch.float64).contiguous(), gc, go, **ctx.factors)
+        return None, gc, go, None
+
+
+def request_limits(plan, constraints, override=None, flags=None, state=None, has_state=None, fallback=False, speed_factor=1.0,
+                   accel_factor=1.0, return_branch=False):
+    """limits [n_paths][9] of Plan.request_limits (with return_branch: (limits, branch [n_paths] int32, api.LIM_*)): what
+    findTrajectory (fallback: findTrajectoryFallback) derives from constraints [n_paths][12], override [n_paths][6] with flags
+    [n_paths] int32 (api.REQ_*) and the state.  Differentiable in constraints and override, the branch word held fixed: the
+    entry that supplied a limit gets its gradient (times the fallback's factor on the four scaled entries) -- the override entry
+    where the override was taken, else the smaller side of a vertical pair; a relaxed heading limit and the state get nothing."""
+    fixed = dict(flags=flags, state=state, has_state=has_state, fallback=fallback, speed_factor=speed_factor,
+                 accel_factor=accel_factor)
+    limits, branch = _RequestLimits.apply(plan, constraints, override, fixed)
+    return (limits, branch) if return_branch else limits
 
 
 class _PathEdit(torch.autograd.Function):

@@ -53,7 +53,7 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 31;  // kernel_id 0 .. 30 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 35;  // kernel_id 0 .. 34 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
   long long ev_count[kTimedKernels] = {};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
@@ -196,7 +196,7 @@ int mrs_tg_capabilities(void) {
   return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE |
          MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE | MRS_TG_CAP_DEVIATION |
          MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE | MRS_TG_CAP_BACA | MRS_TG_CAP_FALLBACK_SAMPLE |
-         MRS_TG_CAP_PATH_EDIT | MRS_TG_CAP_TRAVEL_HEADING | MRS_TG_CAP_INITIAL_CONDITION;
+         MRS_TG_CAP_PATH_EDIT | MRS_TG_CAP_TRAVEL_HEADING | MRS_TG_CAP_INITIAL_CONDITION | MRS_TG_CAP_REQUEST;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1520,6 +1520,73 @@ int mrs_tg_plan_splice_prediction_vjp(mrs_tg_plan* plan, const int32_t* n_sample
   HIP_TRY(ctx, mrs_tg::launch_splice_prediction_vjp(plan->view.n_paths, n_samples, sample_capacity, status, decision, sample_offset,
                                                     prediction_age, n_pred, pred_capacity, grad_out, grad_samples_out,
                                                     grad_pred_position_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+// ---- the request's vertices and limits as plan steps (mrs_tg_request.hip) -------------------------------------------------------
+
+int mrs_tg_plan_request_vertices(mrs_tg_plan* plan, const double* waypoints, const uint8_t* stop_at, const uint8_t* has_state,
+                                 const double* state, int32_t derivative_to_optimize, double* waypoints_out, uint8_t* fixed_mask_out,
+                                 double* fixed_values_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!waypoints) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "waypoints_dev is required");
+  if (derivative_to_optimize < 2 || derivative_to_optimize > 4)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "derivative_to_optimize must be 2, 3 or 4 (got %d)", derivative_to_optimize);
+  if (has_state && !state) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "has_state_dev without state_dev");
+  if (!waypoints_out && !fixed_mask_out && !fixed_values_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "waypoints_out_dev, fixed_mask_out_dev and fixed_values_out_dev are all NULL");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 31);
+  HIP_TRY(ctx, mrs_tg::launch_request_vertices(plan->view, waypoints, stop_at, has_state, state, derivative_to_optimize,
+                                               waypoints_out, fixed_mask_out, fixed_values_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_request_vertices_vjp(mrs_tg_plan* plan, const uint8_t* has_state, const double* grad_waypoints,
+                                     const double* grad_fixed_values, double* grad_waypoints_out, double* grad_state_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!grad_waypoints && !grad_fixed_values)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_waypoints_dev and grad_fixed_values_dev are both NULL: no upstream");
+  if (!grad_waypoints_out && !grad_state_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_waypoints_out_dev and grad_state_out_dev are both NULL");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 32);
+  HIP_TRY(ctx, mrs_tg::launch_request_vertices_vjp(plan->view, has_state, grad_waypoints, grad_fixed_values, grad_waypoints_out,
+                                                   grad_state_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_request_limits(mrs_tg_plan* plan, const double* constraints, const double* override_, const int32_t* flags,
+                               const uint8_t* has_state, const double* state, int32_t fallback, double speed_factor,
+                               double accel_factor, double* limits_out, int32_t* branch_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!constraints) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "constraints_dev is required");
+  if (flags && !override_) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "flags_dev without override_dev");
+  if (has_state && !state) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "has_state_dev without state_dev");
+  if (!limits_out && !branch_out) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "limits_out_dev and branch_out_dev are both NULL");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 33);
+  HIP_TRY(ctx, mrs_tg::launch_request_limits(plan->view.n_paths, constraints, override_, flags, has_state, state, fallback != 0,
+                                             speed_factor, accel_factor, limits_out, branch_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_request_limits_vjp(mrs_tg_plan* plan, const int32_t* branch, int32_t fallback, double speed_factor,
+                                   double accel_factor, const double* grad_limits, double* grad_constraints_out,
+                                   double* grad_override_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (!branch) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "branch_dev is required");
+  if (!grad_limits) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_limits_dev is NULL: no upstream");
+  if (!grad_constraints_out && !grad_override_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_constraints_out_dev and grad_override_out_dev are both NULL");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 34);
+  HIP_TRY(ctx, mrs_tg::launch_request_limits_vjp(plan->view.n_paths, branch, fallback != 0, speed_factor, accel_factor, grad_limits,
+                                                 grad_constraints_out, grad_override_out, ctx->stream));
   return MRS_TG_OK;
 }
 

@@ -1,5 +1,5 @@
 // mrs_tg_hd.hpp -- what the host-checkable kernel headers share (mrs_tg_refine.hpp, mrs_tg_vjp.hpp, mrs_tg_maxima_vjp.hpp,
-// mrs_tg_sample_vjp.hpp, mrs_tg_evaluate.hpp, mrs_tg_deviation.hpp, mrs_tg_estimate_vjp.hpp, mrs_tg_passage.hpp, mrs_tg_baca.hpp, mrs_tg_fallback.hpp, mrs_tg_pathedit.hpp, mrs_tg_heading.hpp, mrs_tg_initial.hpp) and the device headers take their shape constants from.
+// mrs_tg_sample_vjp.hpp, mrs_tg_evaluate.hpp, mrs_tg_deviation.hpp, mrs_tg_estimate_vjp.hpp, mrs_tg_passage.hpp, mrs_tg_baca.hpp, mrs_tg_fallback.hpp, mrs_tg_pathedit.hpp, mrs_tg_heading.hpp, mrs_tg_initial.hpp, mrs_tg_request.hpp) and the device headers take their shape constants from.
 // Plain C++17 without a HIP include: hipcc compiles it for both sides, g++ compiles it for the harnesses under tests/host/,
 // which run the same headers on the CPU.  DESIGN.md section 4a states the convention these headers follow.
 #pragma once

@@ -321,6 +321,25 @@ hipError_t launch_travel_heading(int n_paths, const double* samples, const int32
 hipError_t launch_travel_heading_vjp(int n_paths, const double* samples, const int32_t* n_samples, int capacity,
                                      const int32_t* status, double min_step, const double* grad_out, double* grad_samples,
                                      hipStream_t stream);
+// mrs_tg_plan_request_vertices / mrs_tg_plan_request_limits and their backward passes (mrs_tg_request.hip, mrs_tg_request.hpp): the
+// vertices findTrajectory builds from the raw waypoints [sum V][4] -- headings unwrapped along every path from the state's
+// heading (state [n_paths][4][4], has_state [n_paths] or null: none), mask [sum V][5], values [sum V][5][4]; every output may be
+// null, waypoints_out may be waypoints -- and the limits [n_paths][9] with their branch word from constraints [n_paths][12], the
+// override [n_paths][6] (read where flags says so) and the fallback's factors.  Backward: copies, one addition per waypoint entry,
+// one multiplication per scaled limit; every element of every output written once.  One wavefront per path (vertices), one lane
+// per vertex (their backward pass), one lane per path (limits); no LDS, no workspace; each timed as the kernel family of the
+// pending ProfileScope
+hipError_t launch_request_vertices(const BatchView& b, const double* waypoints, const uint8_t* stop_at, const uint8_t* has_state,
+                                   const double* state, int d, double* waypoints_out, uint8_t* mask, double* vals,
+                                   hipStream_t stream);
+hipError_t launch_request_vertices_vjp(const BatchView& b, const uint8_t* has_state, const double* grad_wp, const double* grad_vals,
+                                       double* grad_raw, double* grad_state, hipStream_t stream);
+hipError_t launch_request_limits(int n_paths, const double* constraints, const double* override_, const int32_t* flags,
+                                 const uint8_t* has_state, const double* state, int fallback, double speed_factor,
+                                 double accel_factor, double* limits, int32_t* branch, hipStream_t stream);
+hipError_t launch_request_limits_vjp(int n_paths, const int32_t* branch, int fallback, double speed_factor, double accel_factor,
+                                     const double* grad_limits, double* grad_constraints, double* grad_override,
+                                     hipStream_t stream);
 // What the rows kernel can do around its solve for the same path, in the same launch:
 //   before: the feasibility scaling of the segment times (scaleSegmentTimesWithViolation's T_i <- s_i T_i from the
 //           per-segment maxima, written back to seg_times) -- the last stage before the final solve of the Mellinger pipeline;

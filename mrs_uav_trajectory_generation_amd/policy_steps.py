@@ -1,8 +1,8 @@
 """The reference's optimize() (src/mrs_trajectory_generation.cpp:620-851) composed from plan steps, the waypoints on the device
 from the request to the answer:
 
-    thinning (Plan.preprocess_path) -> per round: heading unwrap (Plan.unwrap_headings), the vertices findTrajectory builds
-    (:923-977, torch on the device, requests without an initial state), the Baca estimate (Plan.estimate_times_baca), the solve
+    thinning (Plan.preprocess_path) -> per round: the vertices findTrajectory builds, their headings unwrapped from the initial
+    state's (:923-977, Plan.request_vertices, one launch), the Baca estimate (Plan.estimate_times_baca), the solve
     with its samples (Plan.solve), both gates (Plan.length_gate on the solve's status), the deviation scan (Plan.path_deviation),
     the mid-points of the unsafe segments (Plan.insert_midpoints), the plan of the next round.
 
@@ -45,53 +45,6 @@ MAX_SEGMENTS = 256                  # MRS_TG_MAX_SEGMENTS: the longest path a pl
 FUTURE_SAMPLING_DT = 0.2            # sampling_dt of a path from the future (:692-697)
 
 
-def _vertices(so, unwrapped, stop, d, state=None):
-    """mask [sum V][5], values [sum V][5][4] as policy::build_vertices builds them: every vertex constrains its position, the
-    ends their derivatives 1 .. d to zero, a stop_at vertex between them its derivatives 1 .. 3.  state = (has [A] bool, rows
-    [A][4][4]: the heading in [.][0][3], velocity, acceleration, jerk in rows 1 .. 3): the first vertex of a path that has one
-    fixes its derivatives 1 .. 3 to those rows (:946-957)."""
-    dev = unwrapped.device
-    n_v = unwrapped.shape[0]
-    first = torch.as_tensor(so[:-1] + np.arange(so.size - 1), dtype=torch.int64, device=dev)
-    last = torch.as_tensor(so[1:] + np.arange(so.size - 1), dtype=torch.int64, device=dev)
-    end = torch.zeros(n_v, dtype=torch.bool, device=dev)
-    end[first] = True
-    end[last] = True
-    mask = torch.zeros((n_v, 5), dtype=torch.uint8, device=dev)
-    mask[:, 0] = 1
-    mask[:, 1:d + 1] = end[:, None].to(torch.uint8)
-    mask[:, 1:4] |= ((stop != 0) & ~end)[:, None].to(torch.uint8)
-    vals = torch.zeros((n_v, 5, api.N_DIM), dtype=torch.float64, device=dev)
-    vals[:, 0, :] = unwrapped
-    if state is not None:
-        has, rows = state
-        at = first[has]
-        mask[at, 1:4] = 1
-        vals[at, 1:4, :] = rows[has][:, 1:4, :]
-    return mask, vals
-
-
-def _unwrap_from_state(so, unwrapped, state):
-    """the unwrap of :925-936 starts from the initial state's heading, not from the first waypoint's: sradians::unwrap of the
-    first heading against the state's, and the whole path moved by what that changes (a multiple of 2 pi; nothing where the
-    state's heading is the first waypoint's, as it is for a prepended state)"""
-    has, rows = state
-    if not bool(has.any()):
-        return
-    dev = unwrapped.device
-    first = torch.as_tensor(so[:-1] + np.arange(so.size - 1), dtype=torch.int64, device=dev)
-    two_pi = 2.0 * np.pi
-
-    def wrapped(x):
-        return x - two_pi * torch.floor((x + np.pi) / two_pi)
-    what, start = unwrapped[first, 3], rows[:, 0, 3]
-    diff = wrapped(what) - wrapped(start)
-    diff = torch.where(diff < -np.pi, diff + two_pi, torch.where(diff >= np.pi, diff - two_pi, diff))
-    shift = torch.where(has & (what != start), start + diff - what, torch.zeros_like(what))
-    counts = torch.as_tensor(np.diff(so).astype(np.int64) + 1, device=dev)
-    unwrapped[:, 3] += torch.repeat_interleave(shift, counts, output_size=unwrapped.shape[0])
-
-
 def _as_device(a, dtype, dev):
     """a numpy array or a device tensor -> a contiguous device tensor of dtype"""
     if isinstance(a, torch.Tensor):
@@ -99,8 +52,33 @@ def _as_device(a, dtype, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dtype).contiguous()
 
 
+def _request_limits(ctx, pol, constraints, override, override_flags, state, P, dev):
+    """[P][2][9]: findTrajectory's limits (:981-1038) and findTrajectoryFallback's (:1252-1299) of every request, one
+    Plan.request_limits each, from constraints [P][12], override [P][6] and override_flags [P] (api.REQ_*)"""
+    c = _as_device(constraints, torch.float64, dev).reshape(P, 12)
+    flags = None if override_flags is None else _as_device(override_flags, torch.int32, dev).reshape(P)
+    o = None if override is None else _as_device(override, torch.float64, dev).reshape(P, 6)
+    if flags is None and o is not None:
+        raise ValueError("override= needs override_flags= (api.REQ_OVERRIDE where it applies)")
+    if flags is not None and o is None:
+        if bool((flags & api.REQ_OVERRIDE).any()):
+            raise ValueError("override_flags asks for an override: give override=")
+        o = torch.zeros((P, 6), dtype=torch.float64, device=dev)
+    has, rows = (None, None) if state is None else (state[0].to(torch.uint8).contiguous(), state[1].contiguous())
+    both = torch.empty((2, P, 9), dtype=torch.float64, device=dev)
+    plan = api.Plan(ctx, np.arange(P + 1, dtype=np.int32))   # (the step takes the path count and the context from it)
+    try:
+        plan.request_limits(c, both[0], override=o, flags=flags, has_state=has, state=rows)
+        plan.request_limits(c, both[1], override=o, flags=flags, has_state=has, state=rows, fallback=True,
+                            speed_factor=float(pol.fallback_speed_factor), accel_factor=float(pol.fallback_accel_factor))
+    finally:
+        plan.close()
+    return both.permute(1, 0, 2).contiguous()
+
+
 def optimize_paths(ctx, paths, limits=None, stop_flags=None, relax_heading=None, policy=None, sample_capacity=4096,
-                   initial_states=None, has_initial_state=None, initial=None):
+                   initial_states=None, has_initial_state=None, initial=None, constraints=None, override=None,
+                   override_flags=None):
     """optimize() for a list of waypoint paths ([n][4] arrays, n >= 2; n >= 1 with initial=) -> dict(success, n_samples,
     max_deviation, n_waypoints, iterations: numpy [P]; samples: a device tensor [P][sample_capacity][4], rows behind a path's
     n_samples are zero), the fields of api.optimize_paths.
@@ -109,8 +87,15 @@ def optimize_paths(ctx, paths, limits=None, stop_flags=None, relax_heading=None,
     initial: dict(flags [P] int32, tracker [P][4][4], tracker_age [P], uav_pose [P][4], takeoff_height, path_time_offset [P],
     prediction = (position, velocity, acceleration, jerk), each [P][pred_capacity][4], n_pred [P] int32, prediction_age [P]) of
     numpy arrays or device tensors, the arguments of Plan.initial_condition and Plan.splice_prediction: the initial condition is
-    decided, prepended and spliced on the device.  With it the result also has decision and sample_offset (numpy [P])."""
+    decided, prepended and spliced on the device.  With it the result also has decision and sample_offset (numpy [P]).
+    constraints [P][12], override [P][6], override_flags [P] (api.REQ_OVERRIDE, api.REQ_RELAX_HEADING), in place of limits= and
+    relax_heading=: the limits of the solve and of the fallback sampler are derived on the device as findTrajectory and
+    findTrajectoryFallback derive them (Plan.request_limits, once each), the override tested against the initial state."""
     from .problem import DEFAULT_LIMITS
+    if constraints is None and (override is not None or override_flags is not None):
+        raise ValueError("override= and override_flags= go with constraints=")
+    if constraints is not None and (limits is not None or relax_heading is not None):
+        raise ValueError("constraints= and limits= / relax_heading= are two ways to give the limits: give one")
     pol = policy or api.default_policy_options()
     P, cap = len(paths), int(sample_capacity)
     d, dt = int(pol.solver.derivative_to_optimize), float(pol.solver.sampling_dt)
@@ -197,7 +182,9 @@ def optimize_paths(ctx, paths, limits=None, stop_flags=None, relax_heading=None,
         return wp[vtx], stop[vtx], lim_d[keep_d], None if state is None else (state[0][keep_d], state[1][keep_d])
 
     lim_d = torch.from_numpy(lim).to(dev)
-    if (counts < 2).any():                               # "the path is empty (after postprocessing)" :676-681
+    if constraints is not None:                          # [P][2][9]: the solve's limits and the fallback sampler's
+        lim_d = _request_limits(ctx, pol, constraints, override, override_flags, state, P, dev)
+    if (counts < 2).any():                              # "the path is empty (after postprocessing)" :676-681
         first = np.concatenate([[0], np.cumsum(np.diff(off) if initial is not None else counts)])[:-1]
         keep = np.flatnonzero(counts >= 2)
         wp, stop, lim_d, state = select(keep, first, counts, wp, stop, lim_d, state)
@@ -313,28 +300,35 @@ def _rounds(ctx, pol, opt, dt, cap, d, ids, so, wp, stop, lim_d, state, elapsed,
         plan = api.Plan(ctx, so)
         try:
             unwrapped = torch.empty_like(wp)
-            plan.unwrap_headings(wp.contiguous(), unwrapped)                                 # :925-936
             baca = torch.empty(n_s, dtype=torch.float64, device=dev)
             ns = torch.zeros(A, dtype=torch.int32, device=dev)
             samples = torch.zeros((A, cap, api.N_DIM), dtype=torch.float64, device=dev)
+            requested = lim_d.dim() == 3      # constraints=: [.][0] findTrajectory's limits, [.][1] findTrajectoryFallback's
             if use_fallback:                                                                 # findTrajectoryFallback, :1215-1395
-                lim_fb = lim_d.clone()
-                lim_fb[:, 0:2] *= float(pol.fallback_speed_factor)
-                lim_fb[:, 3:5] *= float(pol.fallback_accel_factor)
+                plan.unwrap_headings(wp.contiguous(), unwrapped)                             # :1233-1241, from the first waypoint
+                if requested:
+                    lim_fb = lim_d[:, 1].contiguous()
+                else:
+                    lim_fb = lim_d.clone()
+                    lim_fb[:, 0:2] *= float(pol.fallback_speed_factor)
+                    lim_fb[:, 3:5] *= float(pol.fallback_accel_factor)
                 plan.estimate_times_baca(unwrapped, lim_fb, baca)
                 plan.fallback_sample(wp.contiguous(), baca, dt, cap, ns, samples, stop_at=stop.contiguous(),
                                      stopping_time=pol.fallback_stopping_time)
                 ok = ns <= cap
             else:
-                if state is not None:
-                    _unwrap_from_state(so.astype(np.int64), unwrapped, state)
-                mask, vals = _vertices(so.astype(np.int64), unwrapped, stop, d, state)       # :923-977
-                plan.estimate_times_baca(unwrapped, lim_d, baca)                             # initial_total_time_baca, :1048-1056
+                lim_solve = lim_d[:, 0].contiguous() if requested else lim_d
+                mask = torch.empty((n_v, 5), dtype=torch.uint8, device=dev)
+                vals = torch.empty((n_v, 5, api.N_DIM), dtype=torch.float64, device=dev)
+                has, rows = (None, None) if state is None else (state[0].to(torch.uint8).contiguous(), state[1].contiguous())
+                plan.request_vertices(wp.contiguous(), unwrapped, mask, vals, stop_at=stop.contiguous(), has_state=has, state=rows,
+                                      derivative_to_optimize=d)                             # :923-977, the unwrap from the state
+                plan.estimate_times_baca(unwrapped, lim_solve, baca)                         # initial_total_time_baca, :1048-1056
                 times = torch.zeros(n_s, dtype=torch.float64, device=dev)
                 coeffs = torch.empty((n_s, api.N_DIM, api.N_COEFF), dtype=torch.float64, device=dev)
                 status = torch.zeros(A, dtype=torch.int32, device=dev)
                 cost = torch.zeros(A, dtype=torch.float64, device=dev)
-                plan.solve(opt, mask, vals, times, coeffs, status, cost=cost, waypoints=unwrapped, limits=lim_d, n_samples=ns,
+                plan.solve(opt, mask, vals, times, coeffs, status, cost=cost, waypoints=unwrapped, limits=lim_solve, n_samples=ns,
                            samples=samples)
                 verdict = torch.empty(A, dtype=torch.int32, device=dev)
                 plan.length_gate(baca, ns, dt, max_factor=pol.max_trajectory_len_factor,

@@ -1,0 +1,226 @@
+// request_harness.cpp -- csrc/mrs_tg_request.hpp (the vertices and the limits of a request, as the kernels of
+// mrs_tg_request.hip run them, and their backward passes) compiled with plain g++ next to the host statements of the same
+// arithmetic: policy::build_vertices (csrc/mrs_tg_policy_host.hpp) and, for the limits, a restatement written here from the
+// reference's lines (mrs_trajectory_generation.cpp:981-1038 and :1252-1299; what include/mrs_tg_service.hpp's limits_for,
+// policy::effective_limits and the fallback's two factors do between them).  tests/test_request_host.py compares the answers;
+// tests/test_gpu_request.py holds the kernels to the L lines' output.
+//
+//   g++ -std=c++17 -O2 -ffp-contract=off tests/host/request_harness.cpp -o request_harness && ./request_harness < in
+//
+// Input, one problem per line group, any number until end of input; doubles in any form strtod reads:
+//   V n d has_state  state[16]  raw[n*4]  stop[n]
+//        -> same_wp same_mask same_vals same_in_place   (1 = the bytes of policy::build_vertices; in place: wp_out == raw)
+//   L flags has_state fallback speed_factor accel_factor  c[12] o[6] state[16]
+//        -> branch lim[9] | lim_ref[9]                  (doubles as %a)
+//   G n d has_state  state[16]  raw[n*4]  stop[n]
+//        -> g_raw[n*4] g_state[16] | fd_raw[n*4] fd_state[16]
+//        the backward pass on the upstream g[e] = ((7 e + 3) mod 11) - 5 over waypoints_out then values, against central
+//        differences (step 0.25) of the forward, output element by output element
+//   H flags has_state fallback speed_factor accel_factor  c[12] o[6] state[16]
+//        -> g_c[12] g_o[6] | fd_c[12] fd_o[6]           the same for the limits, upstream g[k] = ((7 k + 3) mod 11) - 5
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "../../mrs_uav_trajectory_generation_amd/csrc/mrs_tg_policy_host.hpp"
+#include "../../mrs_uav_trajectory_generation_amd/csrc/mrs_tg_request.hpp"
+
+namespace rq = mrs_tg::reqq;
+namespace pol = mrs_tg::policy;
+
+static bool read_doubles(double* to, size_t n) {
+  for (size_t e = 0; e < n; ++e)
+    if (std::scanf("%lf", &to[e]) != 1) return false;
+  return true;
+}
+static void print_doubles(const double* v, size_t n) {
+  for (size_t e = 0; e < n; ++e) std::printf("%a ", v[e]);
+}
+static double upstream(size_t e) { return (double)((7 * e + 3) % 11) - 5.0; }
+
+struct VertexProblem {
+  int n = 0, d = 0, has = 0;
+  double state[16];
+  std::vector<double> raw;
+  std::vector<uint8_t> stop;
+  bool read() {
+    if (std::scanf("%d %d %d", &n, &d, &has) != 3 || n < 1 || n > 100000) return false;
+    if (!read_doubles(state, 16)) return false;
+    raw.resize((size_t)n * 4);
+    if (!read_doubles(raw.data(), raw.size())) return false;
+    stop.resize(n);
+    for (int i = 0; i < n; ++i) {
+      int s = 0;
+      if (std::scanf("%d", &s) != 1) return false;
+      stop[i] = (uint8_t)s;
+    }
+    return true;
+  }
+};
+
+static int vertices() {
+  VertexProblem q;
+  if (!q.read()) return 2;
+  const size_t n = q.n;
+  mrs_tg_initial_state init{};
+  init.heading = q.state[3];
+  for (int k = 0; k < 4; ++k) init.velocity[k] = q.state[4 + k], init.acceleration[k] = q.state[8 + k], init.jerk[k] = q.state[12 + k];
+  std::vector<double> wp_ref(n * 4, -1.0), vals_ref(n * 20, -1.0), wp(n * 4, -2.0), vals(n * 20, -2.0);
+  std::vector<uint8_t> mask_ref(n * 5, 0xff), mask(n * 5, 0xfe);
+  pol::build_vertices(q.raw.data(), q.stop.data(), q.n, q.has ? &init : nullptr, q.d, wp_ref.data(), mask_ref.data(), vals_ref.data());
+  rq::vertices(q.raw.data(), q.stop.data(), q.n, q.has != 0, q.state, q.d, wp.data(), mask.data(), vals.data());
+  std::vector<double> in_place = q.raw;
+  rq::vertices(in_place.data(), q.stop.data(), q.n, q.has != 0, q.state, q.d, in_place.data(), nullptr, nullptr);
+  std::printf("%d %d %d %d\n", (int)(std::memcmp(wp.data(), wp_ref.data(), n * 32) == 0),
+              (int)(std::memcmp(mask.data(), mask_ref.data(), n * 5) == 0),
+              (int)(std::memcmp(vals.data(), vals_ref.data(), n * 160) == 0),
+              (int)(std::memcmp(in_place.data(), wp_ref.data(), n * 32) == 0));
+  return 0;
+}
+
+struct LimitProblem {
+  int flags = 0, has = 0, fallback = 0;
+  double sf = 1.0, af = 1.0, c[12], o[6], state[16];
+  bool read() {
+    return std::scanf("%d %d %d %lf %lf", &flags, &has, &fallback, &sf, &af) == 5 && read_doubles(c, 12) && read_doubles(o, 6) &&
+           read_doubles(state, 16);
+  }
+};
+
+// the reference's lines, in its own order and with its own calls
+static void reference_limits(const LimitProblem& q, double* lim) {
+  const double* c = q.c;
+  const double* o = q.o;
+  const double* vel = q.state + 4;
+  const double* acc = q.state + 8;
+  const double* jerk = q.state + 12;
+  const bool override_constraints = (q.flags & 1) != 0, relax_heading = (q.flags & 2) != 0;
+  double v_h, a_h, j_h, v_v, a_v, j_v;
+  const double vertical_speed_lim = std::min(c[3], c[4]);
+  const double vertical_acceleration_lim = std::min(c[5], c[6]);
+  if (!q.fallback) {  // :985-1026
+    v_h = c[0], a_h = c[1];
+    v_v = vertical_speed_lim, a_v = vertical_acceleration_lim;
+    j_h = c[2], j_v = std::min(c[7], c[8]);
+    if (override_constraints) {
+      bool can_change = true;
+      if (q.has) {
+        can_change = (hypot(vel[0], vel[1]) < o[0]) && (hypot(acc[0], acc[1]) < o[2]) && (hypot(jerk[0], jerk[1]) < o[4]) &&
+                     (fabs(vel[2]) < o[1]) && (fabs(acc[2]) < o[3]) && (fabs(jerk[2]) < o[5]);
+      }
+      if (can_change) v_h = o[0], a_h = o[2], j_h = o[4], v_v = o[1], a_v = o[3], j_v = o[5];
+    }
+  } else if (override_constraints) {  // :1259-1267
+    v_h = o[0], a_h = o[2], j_h = o[4], v_v = o[1], a_v = o[3], j_v = o[5];
+  } else {  // :1270-1280
+    v_h = c[0], a_h = c[1];
+    v_v = vertical_speed_lim, a_v = vertical_acceleration_lim;
+    j_h = c[2], j_v = std::min(c[7], c[8]);
+  }
+  double v_hdg = c[9], a_hdg = c[10], j_hdg = c[11];
+  if (relax_heading) v_hdg = a_hdg = j_hdg = std::numeric_limits<float>::max();
+  if (q.fallback) {  // :1295-1299
+    v_h *= q.sf, v_v *= q.sf;
+    a_h *= q.af, a_v *= q.af;
+  }
+  const double out[9] = {v_h, v_v, v_hdg, a_h, a_v, a_hdg, j_h, j_v, j_hdg};
+  std::memcpy(lim, out, sizeof out);
+}
+
+static int limits() {
+  LimitProblem q;
+  if (!q.read()) return 2;
+  double lim[9], ref[9];
+  const int32_t branch = rq::limits(q.c, q.o, q.flags, q.has != 0, q.state, q.fallback != 0, q.sf, q.af, lim);
+  reference_limits(q, ref);
+  std::printf("%d ", branch);
+  print_doubles(lim, 9);
+  std::printf("| ");
+  print_doubles(ref, 9);
+  std::printf("\n");
+  return 0;
+}
+
+static int vertices_backward() {
+  VertexProblem q;
+  if (!q.read()) return 2;
+  const size_t n = q.n, n_out = n * 4 + n * 20;
+  std::vector<double> g(n_out);
+  for (size_t e = 0; e < n_out; ++e) g[e] = upstream(e);
+  const double* g_wp = g.data();
+  const double* g_vals = g.data() + n * 4;
+  std::vector<double> g_raw(n * 4);
+  double g_state[16];
+  for (size_t i = 0; i < n; ++i) {
+    double row[4];
+    rq::vertex_vjp(g_wp + i * 4, g_vals + i * 20, row);
+    std::memcpy(&g_raw[i * 4], row, sizeof row);
+  }
+  rq::state_vjp(q.has != 0, g_vals, g_state);
+  // central differences, output element by output element
+  auto forward = [&](const std::vector<double>& raw, const double* state, std::vector<double>& out) {
+    out.assign(n_out, 0.0);
+    rq::vertices(raw.data(), q.stop.data(), q.n, q.has != 0, state, q.d, out.data(), nullptr, out.data() + n * 4);
+  };
+  const double h = 0.25;
+  std::vector<double> fd(n * 4 + 16), plus, minus;
+  for (size_t e = 0; e < n * 4 + 16; ++e) {
+    std::vector<double> raw_p = q.raw, raw_m = q.raw;
+    double st_p[16], st_m[16];
+    std::memcpy(st_p, q.state, sizeof st_p), std::memcpy(st_m, q.state, sizeof st_m);
+    if (e < n * 4) raw_p[e] += h, raw_m[e] -= h;
+    else st_p[e - n * 4] += h, st_m[e - n * 4] -= h;
+    forward(raw_p, st_p, plus), forward(raw_m, st_m, minus);
+    double s = 0.0;
+    for (size_t k = 0; k < n_out; ++k) s += g[k] * ((plus[k] - minus[k]) / (2.0 * h));
+    fd[e] = s;
+  }
+  print_doubles(g_raw.data(), n * 4);
+  print_doubles(g_state, 16);
+  std::printf("| ");
+  print_doubles(fd.data(), fd.size());
+  std::printf("\n");
+  return 0;
+}
+
+static int limits_backward() {
+  LimitProblem q;
+  if (!q.read()) return 2;
+  double lim[9], g[9], g_c[12], g_o[6];
+  for (int k = 0; k < 9; ++k) g[k] = upstream(k);
+  const int32_t branch = rq::limits(q.c, q.o, q.flags, q.has != 0, q.state, q.fallback != 0, q.sf, q.af, lim);
+  rq::limits_vjp(branch, q.fallback != 0, q.sf, q.af, g, g_c, g_o);
+  const double h = 0.25;
+  double fd[18];
+  for (int e = 0; e < 18; ++e) {
+    LimitProblem p = q, m = q;
+    (e < 12 ? p.c[e] : p.o[e - 12]) += h;
+    (e < 12 ? m.c[e] : m.o[e - 12]) -= h;
+    double lp[9], lm[9];
+    rq::limits(p.c, p.o, p.flags, p.has != 0, p.state, p.fallback != 0, p.sf, p.af, lp);
+    rq::limits(m.c, m.o, m.flags, m.has != 0, m.state, m.fallback != 0, m.sf, m.af, lm);
+    double s = 0.0;
+    for (int k = 0; k < 9; ++k) s += g[k] * ((lp[k] - lm[k]) / (2.0 * h));
+    fd[e] = s;
+  }
+  print_doubles(g_c, 12);
+  print_doubles(g_o, 6);
+  std::printf("| ");
+  print_doubles(fd, 18);
+  std::printf("\n");
+  return 0;
+}
+
+int main() {
+  for (;;) {
+    char what = 0;
+    if (std::scanf(" %c", &what) != 1) return 0;
+    int rc = 2;
+    if (what == 'V') rc = vertices();
+    if (what == 'L') rc = limits();
+    if (what == 'G') rc = vertices_backward();
+    if (what == 'H') rc = limits_backward();
+    if (rc != 0) return rc;
+  }
+}
