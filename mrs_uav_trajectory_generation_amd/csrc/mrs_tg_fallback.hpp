@@ -45,7 +45,7 @@ constexpr double kMinSegmentTime = 1e-1;        // :1336, strictly
 constexpr int32_t kMaxCapacity = 2147483646;   // the largest sample_capacity: capacity + 1, which the outputs report, fits int32
 constexpr double kCountClamp = 2147483648.0;    // 2^31: what a segment's nd enters the 64-bit counts with at most
 
-// mrs_lib sradians::unwrap: `what` brought to within pi of `from` (policy::sradians_unwrap, operation by operation)
+// mrs_lib sradians::unwrap: `what` brought to within pi of `from`.  The one definition: the policy layer and reqq call it
 MRS_TG_HD inline double unwrap(double what, double from) {
   MRS_TG_NO_CONTRACT
   const double two_pi = 2.0 * kPi;

@@ -11,7 +11,8 @@
 // same operations.  The two distances are within an ulp of each other: the decision can differ from the host loop's
 // (mrs_tg_policy_host.hpp) only for a step within an ulp of min_step.  atan2 is the one place a libm enters: the device's in
 // the kernel, the host's in the harness.  No product is contracted into a fused multiply-add.  Plain double,
-// __host__ __device__: tests/host/heading_harness.cpp runs this file under g++.
+// __host__ __device__: tests/host/heading_harness.cpp runs this file under g++.  The host loop takes kMinStep, is_source and
+// heading_of from here and keeps std::hypot for its distance: the rule and its constant are written in this file only.
 //
 // Backward, sources held fixed.  A source s with the rows s .. e-1 of its run (e the next source, at most n-1) collects
 //   G_s = dL/dheading_s + ... + dL/dheading_{e-1}      from 0.0, in increasing row index (accumulate)

@@ -11,8 +11,9 @@
 //                           against the Baca total (:1178-1199), then validateTrajectorySpatial as written -- a sequential
 //                           scan with a waypoint cursor -- on the samples where they are; what travels down is a few words
 //                           per path, one byte per segment, and the samples of the paths that are FINISHED.
-// The gates are baca::code_accepted and baca::length_check (mrs_tg_baca.hpp) and the scan is devq::validate
-// (mrs_tg_deviation.hpp): the functions the host route of mrs_tg_policy_host.hpp calls, contraction off, so the decisions
+// The mask and the values are reqq::vertex_mask and reqq::vertex_values (mrs_tg_request.hpp), the gates are baca::code_accepted
+// and baca::length_check (mrs_tg_baca.hpp) and the scan is devq::validate (mrs_tg_deviation.hpp): the functions the host route
+// of mrs_tg_policy_host.hpp calls, contraction off, so the vertices are the same bytes and the decisions
 // `distance > max_deviation` and the reported maximum are the same bits on both routes (tests/test_gpu_policy.py compares them).
 #include <hip/hip_runtime.h>
 
@@ -23,7 +24,7 @@
 
 namespace mrs_tg {
 
-// vinfo[v] = path index (position in the round's batch) << 4 | flags
+// vinfo[v] = path index (position in the round's batch) << 4 | flags; init [path][4][4], the state rows reqq reads
 __global__ __launch_bounds__(256) void policy_expand_kernel(int n_vertices, int d, const double* __restrict__ wp,
                                                             const int32_t* __restrict__ vinfo, const double* __restrict__ init,
                                                             uint8_t* __restrict__ mask, double* __restrict__ vals) {
@@ -32,22 +33,13 @@ __global__ __launch_bounds__(256) void policy_expand_kernel(int n_vertices, int 
   const int info = vinfo[v];
   const int a = info >> 4;
   const bool first = info & kVertexFirst, last = info & kVertexLast, stop = info & kVertexStop, has_init = info & kVertexInit;
-  uint8_t m[5] = {1, 0, 0, 0, 0};
-  double val[20];
+  double w[kD];
 #pragma unroll
-  for (int e = 0; e < 20; ++e) val[e] = 0.0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) val[k] = wp[(size_t)v * 4 + k];
-  if (first || last) {  // makeStartOrEnd(., d): derivatives 1 .. d at rest (:940-976)
-    for (int k = 1; k <= d; ++k) m[k] = 1;
-    if (first && has_init) {  // the initial state's velocity / acceleration / jerk (:946-957)
-      m[1] = m[2] = m[3] = 1;
-#pragma unroll
-      for (int e = 0; e < 12; ++e) val[4 + e] = init[(size_t)a * 12 + e];
-    }
-  } else if (stop) {  // a stop_at waypoint (:969-973)
-    m[1] = m[2] = m[3] = 1;
-  }
+  for (int k = 0; k < kD; ++k) w[k] = wp[(size_t)v * 4 + k];
+  uint8_t m[kB];
+  double val[reqq::kVertexValues];
+  reqq::vertex_mask(first, last, has_init, stop, d, m);
+  reqq::vertex_values(w, first && has_init, init + (size_t)a * reqq::kState, val);
 #pragma unroll
   for (int k = 0; k < 5; ++k) mask[(size_t)v * 5 + k] = m[k];
   double2* out = reinterpret_cast<double2*>(vals + (size_t)v * 20);

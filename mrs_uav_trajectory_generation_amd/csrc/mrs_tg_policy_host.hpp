@@ -6,8 +6,10 @@
 //   validateTrajectorySpatial (:1401-1455) -> mid-points into unsafe segments (:739-753) -> next round; optional
 //   findTrajectoryFallback (:1215-1395) and override_heading_atan2 (:1582-1597).
 // The arithmetic shared with the plan steps -- distance from a segment, the validation scan, the gates, the waypoint hit test,
-// the Baca estimate -- is not written here: it is called from the host-checkable kernel headers (mrs_tg_deviation.hpp,
-// mrs_tg_passage.hpp, mrs_tg_baca.hpp), which policy_validate_kernel calls too.
+// the Baca estimate, thinning and mid-points, the vertex rule and the limits' tail, the heading unwrap, the yaw round trip and
+// the fallback's rows, the direction-of-travel rule -- is not written here: it is called from the host-checkable kernel headers
+// (mrs_tg_deviation.hpp, mrs_tg_passage.hpp, mrs_tg_baca.hpp, mrs_tg_pathedit.hpp, mrs_tg_request.hpp, mrs_tg_fallback.hpp,
+// mrs_tg_heading.hpp), which policy_validate_kernel, policy_expand_kernel and the plan steps' kernels call too.
 // No HIP type or call appears here: mrs_tg_policy.hip instantiates optimize_paths() with the batched GPU solve and
 // mrs_tg_abi.hip's mrs_tg_find_trajectory uses the vertex builder, the Baca total and the two gates; the same header compiles
 // with g++ and is driven by tests/host/policy_host_harness.cpp with the CPU oracle as the solver on 16 threads under
@@ -16,8 +18,8 @@
 #pragma once
 
 #include <algorithm>
-#include <cfloat>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -34,9 +36,12 @@
 
 #include "../../include/mrs_tg.h"
 #include "mrs_tg_baca.hpp"
+#include "mrs_tg_fallback.hpp"
+#include "mrs_tg_heading.hpp"
 #include "mrs_tg_knobs.hpp"
 #include "mrs_tg_passage.hpp"
 #include "mrs_tg_pathedit.hpp"
+#include "mrs_tg_request.hpp"
 #include "mrs_tg_transfer.hpp"
 
 struct mrs_tg_ctx;
@@ -56,7 +61,7 @@ inline PolicyRoundLayout policy_round_layout(size_t A, size_t nS, int32_t capaci
   PolicyRoundLayout L{};
   size_t off = 0;
   L.wp = off, off += up(nV * 4 * sizeof(double));          // unwrapped waypoints [vertex][4]
-  L.init = off, off += up(A * 12 * sizeof(double));        // initial velocity / acceleration / jerk [path][3][4]
+  L.init = off, off += up(A * reqq::kState * sizeof(double));  // the initial state as reqq reads it [path][4][4] (state_rows)
   L.lim = off, off += up(A * 9 * sizeof(double));          // limits after relax_heading [path][9]
   L.baca = off, off += up(A * sizeof(double));             // initial_total_time_baca [path]
   L.vinfo = off, off += up(nV * sizeof(int32_t));          // position of the vertex's path << 4 | kVertex* flags
@@ -113,26 +118,6 @@ struct PolicyRoundIn {
 int policy_round_device(::mrs_tg_ctx* ctx, const PolicyRoundIn& in);  // (defined in mrs_tg_abi.hip: the GPU build only)
 
 namespace policy {
-
-using baca::radians_diff;  // mrs_lib radians::diff (angles into [0, 2 pi))
-using baca::wrap_range;
-
-// mrs_lib radians::interp (angles in [0, 2 pi)): mrs_tg_pathedit.hpp's; sradians::unwrap
-inline double radians_interp(double from, double to, double coeff) { return pathq::interp_heading(from, to, coeff); }
-inline double sradians_unwrap(double what, double from) {
-  const double two_pi = 2.0 * M_PI;
-  double d = wrap_range(what, -M_PI, two_pi) - wrap_range(from, -M_PI, two_pi);
-  if (d < -M_PI) d += two_pi;
-  else if (d >= M_PI) d -= two_pi;
-  return from + d;
-}
-// the yaw a sample carries after EigenTrajectoryPoint::setFromYaw / getYaw (the nodelet reads it back at :1599):
-// quaternionFromYaw = (cos(yaw / 2), 0, 0, sin(yaw / 2)), yawFromQuaternion = atan2(2 (w z + x y), 1 - 2 (y^2 + z^2))
-// (include/eth_mav_msgs/common.h:130-140) -- the round trip's own arithmetic, not atan2(sin, cos), which differs in the last bit
-inline double wrap_yaw(double y) {
-  const double w = std::cos(y * 0.5), z = std::sin(y * 0.5);
-  return std::atan2(2.0 * (w * z), 1.0 - 2.0 * (z * z));
-}
 
 using pathq::interpolate_point;  // :1612-1625
 
@@ -269,47 +254,33 @@ inline void insert_midpoints(PathState& st, const std::vector<uint8_t>& safe, co
   }
 }
 
-// findTrajectoryFallback :1215-1395
+// findTrajectoryFallback :1215-1395: the rows are fbq's (mrs_tg_fallback.hpp), which fallback_sample_kernel runs too.  Returns
+// the number of rows, also where it exceeds the capacity (the rows below the capacity are written)
 inline int fallback_sampling(const PathState& st, const double* limits9, bool relax_heading, const mrs_tg_policy_options& o, double dt,
                       double* out, int capacity) {
-  const int n_wp = st.n_wp;
-  std::vector<double> wps(st.wps);
-  double last = wps[3];
-  for (int i = 0; i < n_wp; ++i) {
-    wps[(size_t)i * 4 + 3] = sradians_unwrap(st.wps[(size_t)i * 4 + 3], last);
-    last = wps[(size_t)i * 4 + 3];
-  }
+  const int S = st.n_wp - 1;
+  std::vector<double> wps(st.wps.size());
+  fbq::unwrap_path(st.wps.data(), st.n_wp, wps.data());
   double lim[9];
   std::memcpy(lim, limits9, sizeof(lim));
-  lim[0] *= o.fallback_speed_factor;
-  lim[1] *= o.fallback_speed_factor;
-  lim[3] *= o.fallback_accel_factor;
-  lim[4] *= o.fallback_accel_factor;
-  if (relax_heading) lim[2] = lim[5] = lim[8] = (double)FLT_MAX;
+  // (reqq::limits relaxes first and scales second, as the reference does: the two steps touch disjoint entries, the order cannot show)
+  reqq::scale_fallback_limits(lim, o.fallback_speed_factor, o.fallback_accel_factor);
+  if (relax_heading) reqq::relax_heading_limits(lim);
   std::vector<double> t_baca;
-  estimate_times_baca(n_wp - 1, wps.data(), lim, t_baca);
-  int count = 0;
-  for (int i = 0; i < n_wp - 1; ++i) {
-    int n_samples = 0;
-    double step = 0;
-    if (t_baca[i] > 1e-1) {
-      n_samples = (int)std::ceil(t_baca[i] / dt);
-      step = (n_samples > 0) ? 1.0 / (double)n_samples : 0.5;
-    }
-    if (n_samples > 0 && i == n_wp - 2) ++n_samples;
-    for (int j = 0; j < n_samples; ++j) {
-      double p[4];
-      interpolate_point(st.wps.data() + (size_t)i * 4, st.wps.data() + (size_t)(i + 1) * 4, j * step, p);
-      p[3] = wrap_yaw(p[3]);
-      int repeat = 1;
-      if (j == 0 && i > 0 && st.stop[i]) repeat += (int)std::round(o.fallback_stopping_time / dt);
-      for (int r = 0; r < repeat; ++r) {
-        if (count < capacity) std::memcpy(out + (size_t)count * 4, p, sizeof(p));
-        ++count;
-      }
-    }
+  estimate_times_baca(S, wps.data(), lim, t_baca);
+  int32_t insert = 0;
+  // a stopping time that gives no dwell a path can have (negative, not a number, beyond int32) gives no trajectory, as the
+  // plan step refuses it: more rows than fit
+  const bool dwell_ok = fbq::insert_count(o.fallback_stopping_time, dt, &insert);
+  long long count = dwell_ok ? 0 : (long long)capacity + 1;  // 64-bit until it is returned
+  for (int i = 0; dwell_ok && i < S; ++i) {
+    const fbq::SegmentRows seg = fbq::segment_rows(t_baca[i], dt, insert, i, S, st.stop[i] != 0);
+    const double* a = st.wps.data() + (size_t)i * 4;  // (the rows interpolate the RAW headings, :1362)
+    for (long long r = 0; r < seg.rows && count + r < capacity; ++r)
+      fbq::row_at(a, a + 4, fbq::row_coeff(seg.nd, seg.dwell, r), out + (size_t)(count + r) * 4);
+    count += seg.rows;
   }
-  return count;
+  return (int)std::min<long long>(count, INT_MAX);
 }
 
 // ---- the single-path seam: the pieces of findTrajectory() around the solver -------------------------------------------
@@ -317,41 +288,25 @@ inline int fallback_sampling(const PathState& st, const double* limits9, bool re
 // the limits findTrajectory hands to the estimators and the optimiser: relax_heading lifts the heading limits (:1030-1038)
 inline void effective_limits(const double* limits9, bool relax_heading, double* lim_out) {
   for (int k = 0; k < 9; ++k) lim_out[k] = limits9[k];
-  if (relax_heading) lim_out[2] = lim_out[5] = lim_out[8] = (double)FLT_MAX;
+  if (relax_heading) reqq::relax_heading_limits(lim_out);
 }
 
-// The vertices findTrajectory builds for one path (:923-977): headings unwrapped along the path from the initial state's
-// heading (:925-936), every vertex constrains its position (:944, :963, :967), the ends are makeStartOrEnd(0, d) with the
-// initial state's velocity / acceleration / jerk at the first one (:946-957), stop_at vertices pin derivatives 1..3 to
-// zero (:969-973).  wps_raw [n_wp][4] raw headings; wp_out [n_wp][4], mask_out [n_wp][5], vals_out [n_wp][5][4].
+// an initial state as the [4][4] rows reqq reads: row 0 column 3 the heading, rows 1 .. 3 velocity, acceleration, jerk; a null
+// state gives zeros (and is not read by a path that has none)
+inline void state_rows(const mrs_tg_initial_state* init, double* state) {
+  for (int e = 0; e < reqq::kState; ++e) state[e] = 0.0;
+  if (!init) return;
+  state[3] = init->heading;
+  for (int k = 0; k < 4; ++k) state[4 + k] = init->velocity[k], state[8 + k] = init->acceleration[k], state[12 + k] = init->jerk[k];
+}
+
+// The vertices findTrajectory builds for one path (:923-977) are reqq::vertices (mrs_tg_request.hpp): this is the call from
+// the ABI's types.  wps_raw [n_wp][4] raw headings; wp_out [n_wp][4], mask_out [n_wp][5], vals_out [n_wp][5][4], each or null.
 inline void build_vertices(const double* wps_raw, const uint8_t* stop_at, int n_wp, const mrs_tg_initial_state* init, int d,
                            double* wp_out, uint8_t* mask_out, double* vals_out) {
-  std::memset(vals_out, 0, sizeof(double) * 20 * (size_t)n_wp);
-  std::memset(mask_out, 0, 5 * (size_t)n_wp);
-  double last_heading = init ? init->heading : wps_raw[3];
-  for (int i = 0; i < n_wp; ++i) {
-    double* w = wp_out + (size_t)i * 4;
-    for (int k = 0; k < 3; ++k) w[k] = wps_raw[(size_t)i * 4 + k];
-    w[3] = sradians_unwrap(wps_raw[(size_t)i * 4 + 3], last_heading);
-    last_heading = w[3];
-    uint8_t* m = mask_out + (size_t)i * 5;
-    double* vv = vals_out + (size_t)i * 20;
-    m[0] = 1;
-    for (int k = 0; k < 4; ++k) vv[k] = w[k];
-    if (i == 0 || i == n_wp - 1) {
-      for (int k = 1; k <= d; ++k) m[k] = 1;
-      if (i == 0 && init) {
-        m[1] = m[2] = m[3] = 1;
-        for (int k = 0; k < 4; ++k) {
-          vv[4 + k] = init->velocity[k];
-          vv[8 + k] = init->acceleration[k];
-          vv[12 + k] = init->jerk[k];
-        }
-      }
-    } else if (stop_at && stop_at[i]) {
-      m[1] = m[2] = m[3] = 1;
-    }
-  }
+  double state[reqq::kState];
+  state_rows(init, state);
+  reqq::vertices(wps_raw, stop_at, n_wp, init != nullptr, state, d, wp_out, mask_out, vals_out);
 }
 
 // initial_total_time_baca (:1048-1056): the sum of estimateSegmentTimesBaca over the path's vertices
@@ -494,21 +449,13 @@ int optimize_paths(Host& host, int32_t n_paths, const int32_t* wp_offsets, const
             const PathState& s = st[p];
             const bool has_init = has_initial_state && has_initial_state[p] && initial_states;
             const size_t v0 = (size_t)so[a] + a;
-            // headings unwrapped along the path from the initial state's heading (:925-936)
-            double last_heading = has_init ? initial_states[p].heading : s.wps[3];
-            for (int i = 0; i < s.n_wp; ++i) {
-              double* w = wp + (v0 + i) * 4;
-              for (int k = 0; k < 3; ++k) w[k] = s.wps[(size_t)i * 4 + k];
-              w[3] = sradians_unwrap(s.wps[(size_t)i * 4 + 3], last_heading);
-              last_heading = w[3];
+            // the unwrapped waypoints only (:925-936): mask and values are expanded on the device, from vinfo and the state rows
+            double* state = init + a * reqq::kState;
+            state_rows(has_init ? &initial_states[p] : nullptr, state);
+            reqq::vertices(s.wps.data(), nullptr, s.n_wp, has_init, state, d, wp + v0 * 4, nullptr, nullptr);
+            for (int i = 0; i < s.n_wp; ++i)
               vinfo[v0 + i] = (int32_t)(a << 4) | (i == 0 ? kVertexFirst : 0) | (i == s.n_wp - 1 ? kVertexLast : 0) |
                               ((i > 0 && i < s.n_wp - 1 && s.stop[i]) ? kVertexStop : 0) | ((i == 0 && has_init) ? kVertexInit : 0);
-            }
-            for (int k = 0; k < 4; ++k) {
-              init[a * 12 + k] = has_init ? initial_states[p].velocity[k] : 0.0;
-              init[a * 12 + 4 + k] = has_init ? initial_states[p].acceleration[k] : 0.0;
-              init[a * 12 + 8 + k] = has_init ? initial_states[p].jerk[k] : 0.0;
-            }
             effective_limits(limits + (size_t)p * 9, relax_heading && relax_heading[p], lim + a * 9);
             st[p].baca_total = baca[a] = baca_total_time(s.n_wp - 1, wp + v0 * 4, lim + a * 9, tb);
           }
@@ -697,9 +644,11 @@ int optimize_paths(Host& host, int32_t n_paths, const int32_t* wp_offsets, const
       for (int it = 0; it + 1 < s.n_samples; ++it) {
         double* a = smp + (size_t)it * 4;
         const double* b = a + 4;
-        const double dist = std::hypot(b[1] - a[1], b[0] - a[0]);
-        if (dist < 0.05 && it > 0) a[3] = smp[(size_t)(it - 1) * 4 + 3];
-        else a[3] = std::atan2(b[1] - a[1], b[0] - a[0]);
+        // the rule is hdg's (mrs_tg_heading.hpp); the distance stays the reference's std::hypot, which hdg::step_xy's written-out
+        // square root may miss by an ulp at the threshold
+        const double dx = b[0] - a[0], dy = b[1] - a[1];
+        if (hdg::is_source(it, std::hypot(dy, dx), hdg::kMinStep)) a[3] = hdg::heading_of(dx, dy);
+        else a[3] = smp[(size_t)(it - 1) * 4 + 3];
       }
     }
   }

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(64) void request_vertices_kernel(BatchView b, const
     if (waypoints_out) store_pairs(waypoints_out + v * 4, w, 2);
     if (mask) {
       uint8_t m[kB];
-      reqq::vertex_mask(i, V, has, stop_at != nullptr && stop_at[v] != 0, d, m);
+      reqq::vertex_mask(i == 0, i == V - 1, has, stop_at != nullptr && stop_at[v] != 0, d, m);
 #pragma unroll
       for (int k = 0; k < kB; ++k) mask[v * kB + k] = m[k];
     }

@@ -1,9 +1,9 @@
 // mrs_tg_request.hpp -- the two pieces of findTrajectory() that turn a request into the solver's inputs, as the plan steps run
 // them (mrs_tg_request.hip: mrs_tg_plan_request_vertices, mrs_tg_plan_request_limits and their backward passes); DESIGN.md
 // section 11h.  The stages are the vertices (mrs_trajectory_generation.cpp:923-977 of the reference) and the limits (:981-1038;
-// findTrajectoryFallback's variant :1252-1299).  The host statements of the same arithmetic are policy::build_vertices
-// (mrs_tg_policy_host.hpp), limits_for (include/mrs_tg_service.hpp) and policy::effective_limits; tests/host/request_harness.cpp
-// holds this file to them.
+// findTrajectoryFallback's variant :1252-1299).  This is the one definition of the vertex rule and of the limits' two tail steps
+// under csrc/: the policy layer (mrs_tg_policy_host.hpp, policy_expand_kernel) calls it.  limits_for (include/mrs_tg_service.hpp)
+// is the public header's own statement; tests/host/request_harness.cpp holds this file to restatements of the reference's lines.
 //   vertices     the headings unwrapped along the path, THE CHAIN h_i = unwrap(raw_i, h_{i-1}) STARTING FROM THE STATE'S HEADING
 //                where the path has a state and from the first raw heading where it has none (fbq::unwrap, the one copy); every
 //                vertex constrains its position, the ends their derivatives 1 .. d, the first vertex of a path with a state its
@@ -42,16 +42,16 @@ constexpr int32_t kOverridden = 1, kOverrideRefused = 2, kRelaxed = 4, kVDescend
 // what the chain starts from (:925): the state's heading, state[0][3], or the first raw heading
 MRS_TG_HD inline double chain_start(bool has_state, const double* state, const double* raw) { return has_state ? state[3] : raw[3]; }
 
-// the mask [5] of vertex i of V (:940-976)
-MRS_TG_HD inline void vertex_mask(int i, int V, bool has_state, bool stop, int d, uint8_t (&m)[kB]) {
+// the mask [5] of a vertex (:940-976): first / last of its path, has_state and stop as the caller knows them
+MRS_TG_HD inline void vertex_mask(bool first, bool last, bool has_state, bool stop, int d, uint8_t (&m)[kB]) {
   m[0] = 1;
   MRS_TG_UNROLL
   for (int k = 1; k < kB; ++k) m[k] = 0;
-  if (i == 0 || i == V - 1) {
+  if (first || last) {
     MRS_TG_UNROLL
     for (int k = 1; k < kB; ++k)
       if (k <= d) m[k] = 1;
-    if (i == 0 && has_state) m[1] = m[2] = m[3] = 1;  // (d = 2 too, as the host does)
+    if (first && has_state) m[1] = m[2] = m[3] = 1;  // (d = 2 too: the state's rows 1 .. 3 are always pinned)
   } else if (stop) {
     m[1] = m[2] = m[3] = 1;
   }
@@ -84,7 +84,7 @@ MRS_TG_HD inline void vertices(const double* raw, const uint8_t* stop_at, int V,
       for (int k = 0; k < kD; ++k) wp_out[(size_t)i * 4 + k] = w[k];
     if (mask_out) {
       uint8_t m[kB];
-      vertex_mask(i, V, has_state, stop_at != nullptr && stop_at[i] != 0, d, m);
+      vertex_mask(i == 0, i == V - 1, has_state, stop_at != nullptr && stop_at[i] != 0, d, m);
       for (int k = 0; k < kB; ++k) mask_out[(size_t)i * kB + k] = m[k];
     }
     if (vals_out) {
@@ -133,6 +133,14 @@ MRS_TG_HD constexpr int32_t descending_bit(int k) { return k == 1 ? kVDescending
 // the fallback's factor on lim[k] (:1295-1299): the speed factor on 0 and 1, the acceleration factor on 3 and 4
 MRS_TG_HD inline bool fallback_scaled(int k) { return k == 0 || k == 1 || k == 3 || k == 4; }
 MRS_TG_HD inline double fallback_factor(int k, double speed_factor, double accel_factor) { return k < 3 ? speed_factor : accel_factor; }
+// the two tail steps of the limits, on a lim[9] row: relax_heading (:1030-1038) and the fallback's two factors (:1295-1299)
+MRS_TG_HD inline void relax_heading_limits(double* lim) { lim[2] = lim[5] = lim[8] = (double)FLT_MAX; }
+MRS_TG_HD inline void scale_fallback_limits(double* lim, double speed_factor, double accel_factor) {
+  MRS_TG_NO_CONTRACT
+  MRS_TG_UNROLL
+  for (int k = 0; k < kLimits; ++k)
+    if (fallback_scaled(k)) lim[k] = lim[k] * fallback_factor(k, speed_factor, accel_factor);
+}
 
 // can_change of :1001-1008: six strict comparisons of the state (rows 1 .. 3 = velocity, acceleration, jerk) with the override
 MRS_TG_HD inline bool can_change(const double* state, const double* o) {
@@ -166,14 +174,10 @@ MRS_TG_HD inline int32_t limits(const double* c, const double* o, int32_t flags,
     branch |= take ? kOverridden : kOverrideRefused;
   }
   if (flags & kReqRelaxHeading) {
-    lim[2] = lim[5] = lim[8] = (double)FLT_MAX;
+    relax_heading_limits(lim);
     branch |= kRelaxed;
   }
-  if (fallback) {  // after the override, as the reference does
-    MRS_TG_UNROLL
-    for (int k = 0; k < kLimits; ++k)
-      if (fallback_scaled(k)) lim[k] = lim[k] * fallback_factor(k, speed_factor, accel_factor);
-  }
+  if (fallback) scale_fallback_limits(lim, speed_factor, accel_factor);  // after the override, as the reference does
   return branch;
 }
 

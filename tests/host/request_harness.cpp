@@ -1,15 +1,16 @@
 // request_harness.cpp -- csrc/mrs_tg_request.hpp (the vertices and the limits of a request, as the kernels of
-// mrs_tg_request.hip run them, and their backward passes) compiled with plain g++ next to the host statements of the same
-// arithmetic: policy::build_vertices (csrc/mrs_tg_policy_host.hpp) and, for the limits, a restatement written here from the
-// reference's lines (mrs_trajectory_generation.cpp:981-1038 and :1252-1299; what include/mrs_tg_service.hpp's limits_for,
-// policy::effective_limits and the fallback's two factors do between them).  tests/test_request_host.py compares the answers;
-// tests/test_gpu_request.py holds the kernels to the L lines' output.
+// mrs_tg_request.hip run them, and their backward passes) compiled with plain g++ next to restatements of the same arithmetic
+// written here from the reference's lines: reference_vertices (mrs_trajectory_generation.cpp:923-977; the loop the policy layer
+// had of its own until policy::build_vertices became a call of reqq::vertices) and reference_limits (:981-1038 and :1252-1299;
+// what include/mrs_tg_service.hpp's limits_for, the relaxed heading and the fallback's two factors do between them).
+// tests/test_request_host.py compares the answers; tests/test_gpu_request.py holds the kernels to the L lines' output.
 //
 //   g++ -std=c++17 -O2 -ffp-contract=off tests/host/request_harness.cpp -o request_harness && ./request_harness < in
 //
 // Input, one problem per line group, any number until end of input; doubles in any form strtod reads:
 //   V n d has_state  state[16]  raw[n*4]  stop[n]
-//        -> same_wp same_mask same_vals same_in_place   (1 = the bytes of policy::build_vertices; in place: wp_out == raw)
+//        -> same_wp same_mask same_vals same_in_place   (1 = the bytes of reference_vertices, from reqq::vertices on the state
+//           block as given AND from policy::build_vertices on the mrs_tg_initial_state; in place: wp_out == raw)
 //   L flags has_state fallback speed_factor accel_factor  c[12] o[6] state[16]
 //        -> branch lim[9] | lim_ref[9]                  (doubles as %a)
 //   G n d has_state  state[16]  raw[n*4]  stop[n]
@@ -59,6 +60,47 @@ struct VertexProblem {
   }
 };
 
+// The vertices findTrajectory builds for one path (:923-977), in the reference's own order: headings unwrapped along the path
+// from the initial state's heading (:925-936), every vertex constrains its position (:944, :963, :967), the ends are
+// makeStartOrEnd(0, d) with the initial state's velocity / acceleration / jerk at the first one (:946-957), stop_at vertices pin
+// derivatives 1..3 to zero (:969-973).  sradians::unwrap is written out here too.
+static double reference_unwrap(double what, double from) {
+  const double two_pi = 2.0 * M_PI;
+  double d = mrs_tg::baca::wrap_range(what, -M_PI, two_pi) - mrs_tg::baca::wrap_range(from, -M_PI, two_pi);
+  if (d < -M_PI) d += two_pi;
+  else if (d >= M_PI) d -= two_pi;
+  return from + d;
+}
+static void reference_vertices(const double* wps_raw, const uint8_t* stop_at, int n_wp, const mrs_tg_initial_state* init, int d,
+                               double* wp_out, uint8_t* mask_out, double* vals_out) {
+  std::memset(vals_out, 0, sizeof(double) * 20 * (size_t)n_wp);
+  std::memset(mask_out, 0, 5 * (size_t)n_wp);
+  double last_heading = init ? init->heading : wps_raw[3];
+  for (int i = 0; i < n_wp; ++i) {
+    double* w = wp_out + (size_t)i * 4;
+    for (int k = 0; k < 3; ++k) w[k] = wps_raw[(size_t)i * 4 + k];
+    w[3] = reference_unwrap(wps_raw[(size_t)i * 4 + 3], last_heading);
+    last_heading = w[3];
+    uint8_t* m = mask_out + (size_t)i * 5;
+    double* vv = vals_out + (size_t)i * 20;
+    m[0] = 1;
+    for (int k = 0; k < 4; ++k) vv[k] = w[k];
+    if (i == 0 || i == n_wp - 1) {
+      for (int k = 1; k <= d; ++k) m[k] = 1;
+      if (i == 0 && init) {
+        m[1] = m[2] = m[3] = 1;
+        for (int k = 0; k < 4; ++k) {
+          vv[4 + k] = init->velocity[k];
+          vv[8 + k] = init->acceleration[k];
+          vv[12 + k] = init->jerk[k];
+        }
+      }
+    } else if (stop_at && stop_at[i]) {
+      m[1] = m[2] = m[3] = 1;
+    }
+  }
+}
+
 static int vertices() {
   VertexProblem q;
   if (!q.read()) return 2;
@@ -68,13 +110,18 @@ static int vertices() {
   for (int k = 0; k < 4; ++k) init.velocity[k] = q.state[4 + k], init.acceleration[k] = q.state[8 + k], init.jerk[k] = q.state[12 + k];
   std::vector<double> wp_ref(n * 4, -1.0), vals_ref(n * 20, -1.0), wp(n * 4, -2.0), vals(n * 20, -2.0);
   std::vector<uint8_t> mask_ref(n * 5, 0xff), mask(n * 5, 0xfe);
-  pol::build_vertices(q.raw.data(), q.stop.data(), q.n, q.has ? &init : nullptr, q.d, wp_ref.data(), mask_ref.data(), vals_ref.data());
+  reference_vertices(q.raw.data(), q.stop.data(), q.n, q.has ? &init : nullptr, q.d, wp_ref.data(), mask_ref.data(), vals_ref.data());
   rq::vertices(q.raw.data(), q.stop.data(), q.n, q.has != 0, q.state, q.d, wp.data(), mask.data(), vals.data());
+  // ... and through the conversion of the ABI's initial state the policy layer makes
+  std::vector<double> wp_pol(n * 4, -3.0), vals_pol(n * 20, -3.0);
+  std::vector<uint8_t> mask_pol(n * 5, 0xfd);
+  pol::build_vertices(q.raw.data(), q.stop.data(), q.n, q.has ? &init : nullptr, q.d, wp_pol.data(), mask_pol.data(), vals_pol.data());
   std::vector<double> in_place = q.raw;
   rq::vertices(in_place.data(), q.stop.data(), q.n, q.has != 0, q.state, q.d, in_place.data(), nullptr, nullptr);
-  std::printf("%d %d %d %d\n", (int)(std::memcmp(wp.data(), wp_ref.data(), n * 32) == 0),
-              (int)(std::memcmp(mask.data(), mask_ref.data(), n * 5) == 0),
-              (int)(std::memcmp(vals.data(), vals_ref.data(), n * 160) == 0),
+  std::printf("%d %d %d %d\n",
+              (int)(std::memcmp(wp.data(), wp_ref.data(), n * 32) == 0 && std::memcmp(wp_pol.data(), wp_ref.data(), n * 32) == 0),
+              (int)(std::memcmp(mask.data(), mask_ref.data(), n * 5) == 0 && std::memcmp(mask_pol.data(), mask_ref.data(), n * 5) == 0),
+              (int)(std::memcmp(vals.data(), vals_ref.data(), n * 160) == 0 && std::memcmp(vals_pol.data(), vals_ref.data(), n * 160) == 0),
               (int)(std::memcmp(in_place.data(), wp_ref.data(), n * 32) == 0));
   return 0;
 }

@@ -139,7 +139,7 @@ def _hex(tokens):
 
 
 def run_vertices(exe, problems):
-    """-> [len(problems)][4]: 1 where waypoints, mask, values and the in-place waypoints have policy::build_vertices' bytes"""
+    """-> [len(problems)][4]: 1 where waypoints, mask, values and the in-place waypoints have the bytes of the harness's restatement"""
     out = hh.run(exe, [_vertex_line("V", q) for q in problems], len(problems))
     return np.array([[int(t) for t in line.split()] for line in out], dtype=np.int64)
 

@@ -1,6 +1,6 @@
 """The request's vertices and limits on the CPU: csrc/mrs_tg_request.hpp (what the kernels of mrs_tg_request.hip run) compiled by
-g++ into tests/host/request_harness.cpp NEXT TO policy::build_vertices (csrc/mrs_tg_policy_host.hpp) and a restatement of the
-reference's limit lines.  Vertices and limits are compared in bits; the backward passes against central differences of the
+g++ into tests/host/request_harness.cpp NEXT TO restatements of the reference's vertex lines and limit lines (the policy layer's
+policy::build_vertices, a call of the header by now, is held to the vertex restatement too).  Vertices and limits are compared in bits; the backward passes against central differences of the
 forward -- exact for every copy and for the fallback's one multiplication, and for the heading, whose forward rounds in its fmod
 and additions, within the bound stated at HEADING_FD_BOUND.  No GPU."""
 import numpy as np
