@@ -220,9 +220,12 @@ enum {
                                          mrs_tg_plan_splice_prediction and their three backward passes are exported: where a
                                          trajectory starts (prepareInitialCondition), the waypoint put in front of the request
                                          and the prediction in front of a trajectory from the future, as plan steps */
-  MRS_TG_CAP_REQUEST = 32768            /* mrs_tg_plan_request_vertices, mrs_tg_plan_request_limits and their two backward passes
+  MRS_TG_CAP_REQUEST = 32768,           /* mrs_tg_plan_request_vertices, mrs_tg_plan_request_limits and their two backward passes
                                          are exported: the vertices and the limits findTrajectory derives from a request, as plan
                                          steps */
+  MRS_TG_CAP_MUTUAL_CLEARANCE = 65536   /* mrs_tg_plan_mutual_clearance and mrs_tg_plan_mutual_clearance_vjp are exported: how close
+                                         the paths of one group (a swarm) come to each other at common steps, the nearest
+                                         neighbour's index, and the backward pass */
 };
 
 /* mrs_tg_plan_request_limits' flags_dev: what the request asks of its limits */
@@ -1105,6 +1108,60 @@ int mrs_tg_plan_request_limits_vjp(mrs_tg_plan* plan, const int32_t* branch_dev,
                                    double accel_factor, const double* grad_limits_dev, double* grad_constraints_out_dev,
                                    double* grad_override_out_dev);
 
+/* Mutual clearance within groups of paths as a plan step (MRS_TG_CAP_MUTUAL_CLEARANCE; mutual_clearance_kernel,
+ * csrc/mrs_tg_clearance.hpp): how close the UAVs of one swarm come to each other, when, and who the
+ * neighbour is -- on the rows a sampler left, where they are.  The plan contributes its path count and its context; segments play
+ * no part and every array is in the caller's path order.  The paths are partitioned into GROUPS, contiguous runs of paths:
+ * group_offsets_dev [n_groups + 1] (int32; well-formed offsets start at 0, do not decrease and end at n_paths).  All paths share
+ * the sampling dt: row r of path p sits at the common step first_step[p] + r (first_step_dev [n_paths] int32, NULL = all 0,
+ * values in [-2^30, 2^30]).  samples_dev [n_paths][sample_capacity][4] and n_samples_dev [n_paths] are what a solve or a sampler
+ * left; a path has n = min(n_samples, sample_capacity) live rows (a count of sample_capacity + 1 is sample_capacity rows), none
+ * with status_dev (may be NULL) <= 0 -- such a path is neither a subject nor a neighbour.  For every live row (p, r) at step s and
+ * every other path j of p's group with a live row at step s, with d = row_p - row_j and kappa = z_scale (finite, positive; 1.0
+ * the Euclidean distance, below 1 vertical separation weighs less),
+ *   c = sqrt((dx dx + dy dy) + (kappa dz)(kappa dz))        products and sums in this order, no fused multiply-add
+ * and the row's clearance is the minimum over j, taken with a strict < from +inf in increasing j: a tie goes to the lowest path
+ * index, a distance that is not a number never becomes a minimum.  Outputs, each may be NULL, not all:
+ *   clearance_out_dev [n_paths][sample_capacity]      the minimum; +inf where no neighbour has a row at that step, in the rows
+ *                                                     from n on and on dead paths (relu(R - c) needs no mask)
+ *   partner_out_dev [n_paths][sample_capacity] int32  the neighbour's path index in the batch, -1 exactly where clearance is +inf
+ *   min_clearance_out_dev [n_paths]                   the minimum over the path's rows, +inf without any
+ *   argmin_out_dev [n_paths][2] int32                 the first row whose clearance is strictly below every row in front of it,
+ *                                                     and its partner; {-1, -1} without any
+ * One workgroup per path, one lane per row, the group's other paths the outer loop of a chunk of 64 rows; the per-path minimum
+ * is combined in the order "smaller value, then lower row", which no split changes.  No atomics, no workspace; every output
+ * element that belongs to the plan is written exactly once; the same bits on every call and for a path wherever its group sits
+ * in the batch.  Group bounds are clamped into [0, n_paths] and every row index is checked against its path's live rows, so no
+ * read leaves the plan's arrays whatever group_offsets_dev and first_step_dev hold; a path that offsets which are not
+ * well-formed leave outside its group's range has no neighbours.  Out of scope: a path counts only on the steps where it has
+ * rows ("hovers at its last row" is the caller's padding: repeat the row and raise n_samples); groups that are not contiguous.
+ * MRS_TG_ERR_INVALID_ARG, before any launch: plan, n_samples_dev or group_offsets_dev NULL, samples_dev NULL with a positive
+ * capacity, n_groups < 0, a negative sample_capacity, a z_scale that is not finite and positive, no output given, samples_dev
+ * not 16-byte aligned or another array not aligned to its element.  n_paths == 0 or sample_capacity == 0: success, nothing is
+ * launched or written.  Device pointers, asynchronous on the context's stream. */
+int mrs_tg_plan_mutual_clearance(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev, int32_t sample_capacity,
+                                 const int32_t* group_offsets_dev, int32_t n_groups, const int32_t* first_step_dev,
+                                 const int32_t* status_dev, double z_scale, double* clearance_out_dev, int32_t* partner_out_dev,
+                                 double* min_clearance_out_dev, int32_t* argmin_out_dev);
+/* Backward pass of mrs_tg_plan_mutual_clearance (mutual_clearance_vjp_kernel), the partners held fixed:
+ * given grad_clearance_dev [n_paths][sample_capacity] = dL/dclearance and partner_dev, the forward's partner_out_dev (an input),
+ * writes grad_samples_out_dev [n_paths][sample_capacity][4] = dL/dsamples: column 3 zero, rows from n on zero, dead paths zero.
+ * For a row (i, .) at step s with upstream g, partner j and d = row_i - row_j,
+ *   g dc/drow_i = (g (dx / c), g (dy / c), g ((kappa (kappa dz)) / c))    each quotient rounded, then the product
+ *   g dc/drow_j = 0.0 - that, entry by entry.
+ * Row (j, r) at step s has one accumulator per coordinate: it starts at 0.0 and takes first the row's own term against its own
+ * partner, then, in increasing path index i over the group with i != j, the second form of every i whose row at step s names j
+ * as its partner; every addition is one rounded addition.  Exactly 0 come from: g == 0 (so the +inf rows never make a NaN),
+ * c == 0 (coincident rows), a partner entry that is -1, outside the row's own group, the row's own path, or a path without a
+ * live row at that step -- none of which is dereferenced.  No gradient flows through the choice of the partner.  A gather, one
+ * lane per output row: deterministic, no atomics, no workspace, every element written exactly once, the same bits on every call
+ * and wherever the group sits in the batch.  grad_samples_out_dev may not overlap an input.  The argument checks are the
+ * forward's, with partner_dev, grad_clearance_dev and grad_samples_out_dev (16-byte aligned) required. */
+int mrs_tg_plan_mutual_clearance_vjp(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev,
+                                     int32_t sample_capacity, const int32_t* group_offsets_dev, int32_t n_groups,
+                                     const int32_t* first_step_dev, const int32_t* status_dev, double z_scale,
+                                     const int32_t* partner_dev, const double* grad_clearance_dev, double* grad_samples_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
@@ -1125,7 +1182,8 @@ int mrs_tg_plan_request_limits_vjp(mrs_tg_plan* plan, const int32_t* branch_dev,
  * (mrs_tg_plan_splice_prediction), 28, 29, 30 their backward passes (mrs_tg_plan_splice_prediction_vjp,
  * mrs_tg_plan_initial_condition_vjp, mrs_tg_plan_prepend_initial_condition_vjp), 31 the request's vertices
  * (mrs_tg_plan_request_vertices), 32 their backward pass (mrs_tg_plan_request_vertices_vjp), 33 the request's limits
- * (mrs_tg_plan_request_limits), 34 their backward pass (mrs_tg_plan_request_limits_vjp): thirty-five ids, 0 .. 34.
+ * (mrs_tg_plan_request_limits), 34 their backward pass (mrs_tg_plan_request_limits_vjp), 35 the mutual clearance
+ * (mrs_tg_plan_mutual_clearance), 36 its backward pass (mrs_tg_plan_mutual_clearance_vjp): thirty-seven ids, 0 .. 36.
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

@@ -55,6 +55,7 @@ KERNEL_TRAVEL_HEADING, KERNEL_TRAVEL_HEADING_VJP = 23, 24
 KERNEL_INITIAL_CONDITION, KERNEL_PREPEND_INITIAL_CONDITION, KERNEL_SPLICE_PREDICTION = 25, 26, 27
 KERNEL_SPLICE_PREDICTION_VJP, KERNEL_INITIAL_CONDITION_VJP, KERNEL_PREPEND_INITIAL_CONDITION_VJP = 28, 29, 30
 KERNEL_REQUEST_VERTICES, KERNEL_REQUEST_VERTICES_VJP, KERNEL_REQUEST_LIMITS, KERNEL_REQUEST_LIMITS_VJP = 31, 32, 33, 34
+KERNEL_MUTUAL_CLEARANCE, KERNEL_MUTUAL_CLEARANCE_VJP = 35, 36
 
 
 class MrsTgError(RuntimeError):
@@ -125,6 +126,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_plan_prepend_initial_condition_vjp", "mrs_tg_plan_splice_prediction", "mrs_tg_plan_splice_prediction_vjp",
     "mrs_tg_plan_request_vertices", "mrs_tg_plan_request_vertices_vjp", "mrs_tg_plan_request_limits",
     "mrs_tg_plan_request_limits_vjp",
+    "mrs_tg_plan_mutual_clearance", "mrs_tg_plan_mutual_clearance_vjp",
 ]
 
 _lib = None
@@ -280,6 +282,10 @@ def load_library():
     L.mrs_tg_plan_request_limits.argtypes = [vp, dp, dp, ip, bp, dp, C.c_int32, C.c_double, C.c_double, dp, ip]
     L.mrs_tg_plan_request_limits_vjp.restype = C.c_int
     L.mrs_tg_plan_request_limits_vjp.argtypes = [vp, ip, C.c_int32, C.c_double, C.c_double, dp, dp, dp]
+    L.mrs_tg_plan_mutual_clearance.restype = C.c_int
+    L.mrs_tg_plan_mutual_clearance.argtypes = [vp, dp, ip, C.c_int32, ip, C.c_int32, ip, ip, C.c_double, dp, ip, dp, ip]
+    L.mrs_tg_plan_mutual_clearance_vjp.restype = C.c_int
+    L.mrs_tg_plan_mutual_clearance_vjp.argtypes = [vp, dp, ip, C.c_int32, ip, C.c_int32, ip, ip, C.c_double, ip, dp, dp]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -343,6 +349,7 @@ CAP_INITIAL_CONDITION = 16384  # MRS_TG_CAP_INITIAL_CONDITION: Plan.initial_cond
 IC_PREPEND, IC_FROM_FUTURE, IC_DROP_FIRST, IC_FROM_TRACKER, IC_FROM_UAV, IC_FROM_PREDICTION, IC_INVALID = 1, 2, 4, 8, 16, 32, 64
 IC_FLAG_TRACKER, IC_FLAG_UAV, IC_FLAG_DONT_PREPEND = 1, 2, 4
 CAP_REQUEST = 32768   # MRS_TG_CAP_REQUEST: Plan.request_vertices, Plan.request_limits (findTrajectory's vertices and limits as plan steps) and their two backward passes
+CAP_MUTUAL_CLEARANCE = 65536   # MRS_TG_CAP_MUTUAL_CLEARANCE: Plan.mutual_clearance (the nearest other path of a row's group at the same step), Plan.mutual_clearance_vjp
 # Plan.request_limits' flags input (MRS_TG_REQ_*) and its branch word (MRS_TG_LIM_*)
 REQ_OVERRIDE, REQ_RELAX_HEADING = 1, 2
 LIM_OVERRIDDEN, LIM_OVERRIDE_REFUSED, LIM_RELAXED, LIM_V_DESCENDING, LIM_A_DESCENDING, LIM_J_DESCENDING, LIM_FALLBACK = 1, 2, 4, 8, 16, 32, 64
@@ -515,6 +522,21 @@ def pinned_copy(a):
 
 def _t_ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def check_group_offsets(group_offsets, n_paths):
+    """Host group offsets of Plan.mutual_clearance as a contiguous int32 array [n_groups + 1], or ValueError: they start at 0,
+    do not decrease and end at n_paths (a group may be empty).  No device is needed."""
+    try:
+        raw = np.asarray(group_offsets)
+    except Exception as e:
+        raise ValueError("group_offsets is not an array of integers: %s" % e)
+    if raw.ndim != 1 or raw.size < 1 or raw.dtype.kind not in "iu":
+        raise ValueError("group_offsets must be a one-dimensional array of at least one integer")
+    g = raw.astype(np.int64)
+    if g[0] != 0 or g[-1] != int(n_paths) or np.any(np.diff(g) < 0):
+        raise ValueError("group_offsets must start at 0, not decrease and end at n_paths = %d (got %s)" % (n_paths, g.tolist()))
+    return np.ascontiguousarray(g, dtype=np.int32)
 
 
 class Context:
@@ -984,6 +1006,49 @@ class Plan:
                                                                int(samples.shape[1]), _t_ptr(waypoints), _t_ptr(status),
                                                                _t_ptr(grad_deviation), _t_ptr(grad_samples),
                                                                _t_ptr(grad_waypoints)), "mrs_tg_plan_path_deviation_vjp")
+
+    def _group_offsets_dev(self, group_offsets, like):
+        """group_offsets as mrs_tg_plan_mutual_clearance takes them: a device int32 tensor is the caller's statement and passes
+        as it is; a host sequence or array is checked (check_group_offsets: ValueError) and uploaded to `like`'s device -- a
+        blocking copy, so a caller in a loop keeps the tensor this returns"""
+        import torch
+        if isinstance(group_offsets, torch.Tensor) and group_offsets.is_cuda:
+            if group_offsets.dtype != torch.int32 or group_offsets.dim() != 1 or group_offsets.numel() < 1 or \
+                    not group_offsets.is_contiguous():
+                raise ValueError("group_offsets on the device must be a contiguous int32 tensor [n_groups + 1]")
+            return group_offsets
+        if isinstance(group_offsets, torch.Tensor):
+            group_offsets = group_offsets.numpy()
+        g = torch.from_numpy(check_group_offsets(group_offsets, self.n_paths)).to(like.device)
+        torch.cuda.current_stream(like.device).synchronize()
+        return g
+
+    def mutual_clearance(self, samples, n_samples, group_offsets, first_step=None, status=None, z_scale=1.0, clearance=None,
+                         partner=None, min_clearance=None, argmin=None):
+        """mrs_tg_plan_mutual_clearance: per row of samples [n_paths][capacity][4] (n_samples [n_paths] int32) the distance to the
+        nearest other path of the row's group at the same common step -- group_offsets [n_groups + 1] (a device int32 tensor, or
+        a host sequence, which is checked and uploaded), first_step [n_paths] int32 (None: all 0), z_scale the weight of the
+        vertical separation -- into clearance [n_paths][capacity] (+inf without a neighbour), partner [n_paths][capacity] (int32,
+        the neighbour's path index, -1 where clearance is +inf), min_clearance [n_paths] and argmin [n_paths][2] (int32: row,
+        partner) (device tensors, written; None = not wanted, at least one given); asynchronous on the context's stream."""
+        g = self._group_offsets_dev(group_offsets, samples)
+        self.ctx._check(self._L.mrs_tg_plan_mutual_clearance(self._h, _t_ptr(samples), _t_ptr(n_samples), int(samples.shape[1]),
+                                                             _t_ptr(g), int(g.numel()) - 1, _t_ptr(first_step), _t_ptr(status),
+                                                             float(z_scale), _t_ptr(clearance), _t_ptr(partner),
+                                                             _t_ptr(min_clearance), _t_ptr(argmin)),
+                        "mrs_tg_plan_mutual_clearance")
+
+    def mutual_clearance_vjp(self, samples, n_samples, group_offsets, partner, grad_clearance, grad_samples, first_step=None,
+                             status=None, z_scale=1.0):
+        """mrs_tg_plan_mutual_clearance_vjp: dL/dsamples [n_paths][capacity][4] (grad_samples, written, zeros included) from
+        dL/dclearance (grad_clearance [n_paths][capacity]) with the forward's partner [n_paths][capacity] (int32) held fixed;
+        the other arguments are the forward's; asynchronous on the context's stream."""
+        g = self._group_offsets_dev(group_offsets, samples)
+        self.ctx._check(self._L.mrs_tg_plan_mutual_clearance_vjp(self._h, _t_ptr(samples), _t_ptr(n_samples),
+                                                                 int(samples.shape[1]), _t_ptr(g), int(g.numel()) - 1,
+                                                                 _t_ptr(first_step), _t_ptr(status), float(z_scale),
+                                                                 _t_ptr(partner), _t_ptr(grad_clearance), _t_ptr(grad_samples)),
+                        "mrs_tg_plan_mutual_clearance_vjp")
 
     def estimate_times(self, waypoints, limits, seg_times):
         """mrs_tg_plan_estimate_times: the Euclidean segment-time estimate of waypoints [sum V][4] under limits [n_paths][9] into

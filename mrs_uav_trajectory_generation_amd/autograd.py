@@ -109,6 +109,21 @@ With them the chain starts at the RAW request and the state's velocity gets a gr
     >>> times = estimate_times(plan, wp, lim)
     >>> coeffs, _, status = solve(plan, mask, fv, times); samples, n = sample(plan, coeffs, times, 0.2, 512, status)
     >>> ((samples[..., :3] - target) ** 2).sum().backward()            # raw.grad, st.grad (rows 1 .. 3), c.grad
+
+mutual_clearance (Plan.mutual_clearance forward, Plan.mutual_clearance_vjp backward: mrs_tg_plan_mutual_clearance /
+mrs_tg_plan_mutual_clearance_vjp) answers the first question a swarm asks of its trajectories: how close
+do its UAVs come to each other, when, and who is the neighbour.  The paths of ONE plan are partitioned into groups; for every
+row the stage gives the distance to the nearest other path of the row's group at the same step and that path's index -- one
+launch, no [N][N][Q] temporary, a fixed order of every sum.  The neighbour is held fixed in the backward pass.  A swarm of four
+paths in one plan, kept 2 m apart:
+
+    >>> plan = api.Plan(ctx, seg_offsets)                               # four paths
+    >>> fv = fixed_values.clone().requires_grad_(); times = seg_times.clone().requires_grad_()
+    >>> coeffs, _, status = solve(plan, fixed_mask, fv, times)
+    >>> samples, n = sample(plan, coeffs, times, 0.2, 512, status)
+    >>> clearance, partner = mutual_clearance(plan, samples, n, [0, 4], status=status)   # one group; all start at step 0
+    >>> torch.relu(2.0 - clearance).sum().backward()                    # +inf where nobody is near in time: no mask; fv.grad, times.grad
+    >>> closest = clearance.amin(dim=1)                                 # per UAV; partner says to whom
 """
 import numpy as np
 import torch
@@ -636,6 +651,59 @@ def travel_heading(plan, samples, n_samples, status=None, min_step=0.05):
     source is the row whose step gave a row's heading (-1 for row n-1 and behind).  The gradient holds the sources fixed: the
     heading of a run of slow rows flows into the two rows of its source's step, nothing into the headings the step replaces."""
     return _TravelHeading.apply(plan, samples, n_samples, status, min_step)
+
+
+class _MutualClearance(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, samples, n_samples, group_offsets, first_step, status, z_scale):
+        s = samples.detach().to(torch.float64).contiguous()
+        n = n_samples.detach().to(torch.int32).contiguous()
+        if s.dim() != 3 or s.shape[0] != plan.n_paths or s.shape[2] != api.N_DIM:
+            raise ValueError("samples must be [n_paths][capacity][4]")
+        if n.dim() != 1 or n.shape[0] != plan.n_paths:
+            raise ValueError("n_samples must be [n_paths]")
+        fs = None if first_step is None else first_step.detach().to(torch.int32).contiguous()
+        if fs is not None and (fs.dim() != 1 or fs.shape[0] != plan.n_paths):
+            raise ValueError("first_step must be [n_paths]")
+        st = None if status is None else status.detach().to(torch.int32).contiguous()
+        g = plan._group_offsets_dev(group_offsets, s)
+        # (a call without rows launches nothing: the neutral values are there beforehand)
+        clearance = torch.full(s.shape[:2], float("inf"), dtype=torch.float64, device=s.device)
+        partner = torch.full(s.shape[:2], -1, dtype=torch.int32, device=s.device)
+        plan.ctx.use_torch_stream()
+        plan.mutual_clearance(s, n, g, first_step=fs, status=st, z_scale=float(z_scale), clearance=clearance, partner=partner)
+        ctx.plan, ctx.first_step, ctx.status, ctx.z_scale = plan, fs, st, float(z_scale)
+        ctx.save_for_backward(s, n, g, partner)
+        ctx.mark_non_differentiable(partner)
+        ctx.set_materialize_grads(False)
+        return clearance, partner
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_clearance, _grad_partner):
+        s, n, g, partner = ctx.saved_tensors
+        if grad_clearance is None or not ctx.needs_input_grad[1]:
+            return None, None, None, None, None, None, None
+        gs = torch.zeros_like(s)
+        plan = ctx.plan
+        plan.ctx.use_torch_stream()   # (the autograd engine runs this on its own thread, on the forward's stream)
+        plan.mutual_clearance_vjp(s, n, g, partner, grad_clearance.to(torch.float64).contiguous(), gs, first_step=ctx.first_step,
+                                  status=ctx.status, z_scale=ctx.z_scale)
+        return None, gs, None, None, None, None, None
+
+
+def mutual_clearance(plan, samples, n_samples, group_offsets, first_step=None, status=None, z_scale=1.0):
+    """(clearance [n_paths][capacity], partner [n_paths][capacity] int32) of Plan.mutual_clearance: for every live row of samples
+    [n_paths][capacity][4] the distance sqrt(dx^2 + dy^2 + (z_scale dz)^2) to the nearest OTHER path of the row's group at the
+    same common step, and that path's index in the batch.  The groups (swarms) are contiguous runs of paths: group_offsets
+    [n_groups + 1], a device int32 tensor or a host sequence (checked: starts at 0, does not decrease, ends at n_paths); row r
+    of path p sits at step first_step[p] + r (first_step [n_paths] int32, None: all paths start together); n_samples [n_paths]
+    int32 as the sampler returned it.  Differentiable in samples (float64 device tensor; x, y, z are read, column 3 gets a zero
+    gradient).  Rows without a neighbour at their step, rows from n on and the rows of a path with status <= 0 (status
+    [n_paths], optional) hold clearance +inf and partner -1 and get and give zero: relu(R - clearance) needs no mask.  The
+    gradient holds every partner fixed; coincident rows (clearance 0) contribute zero.  A path counts only on the steps where
+    it has rows -- to let a UAV hover at its last row, repeat that row up to the horizon and raise n_samples."""
+    return _MutualClearance.apply(plan, samples, n_samples, group_offsets, first_step, status, z_scale)
 
 
 def _f64(t):

@@ -53,7 +53,7 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 35;  // kernel_id 0 .. 34 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 37;  // kernel_id 0 .. 36 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
   long long ev_count[kTimedKernels] = {};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
@@ -196,7 +196,8 @@ int mrs_tg_capabilities(void) {
   return (mrs_tg::careful_rerun_built() ? MRS_TG_CAP_CAREFUL_COST : 0) | MRS_TG_CAP_FUTURE_PATHS | MRS_TG_CAP_REFINE |
          MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE | MRS_TG_CAP_DEVIATION |
          MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE | MRS_TG_CAP_BACA | MRS_TG_CAP_FALLBACK_SAMPLE |
-         MRS_TG_CAP_PATH_EDIT | MRS_TG_CAP_TRAVEL_HEADING | MRS_TG_CAP_INITIAL_CONDITION | MRS_TG_CAP_REQUEST;
+         MRS_TG_CAP_PATH_EDIT | MRS_TG_CAP_TRAVEL_HEADING | MRS_TG_CAP_INITIAL_CONDITION | MRS_TG_CAP_REQUEST |
+         MRS_TG_CAP_MUTUAL_CLEARANCE;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1587,6 +1588,69 @@ int mrs_tg_plan_request_limits_vjp(mrs_tg_plan* plan, const int32_t* branch, int
   ProfileScope ps(ctx, 34);
   HIP_TRY(ctx, mrs_tg::launch_request_limits_vjp(plan->view.n_paths, branch, fallback != 0, speed_factor, accel_factor, grad_limits,
                                                  grad_constraints_out, grad_override_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+// ---- mutual clearance within groups of paths as a plan step (mrs_tg_clearance.hip) ----------------------------------------------
+
+// what the two clearance calls check before any launch
+static int mutual_clearance_arguments(mrs_tg_ctx* ctx, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                      const int32_t* group_offsets, int32_t n_groups, const int32_t* first_step,
+                                      const int32_t* status, double z_scale) {
+  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
+  if (n_groups < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_groups %d is negative", n_groups);
+  if (!n_samples || !group_offsets || (sample_capacity > 0 && !samples))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev and group_offsets_dev are required");
+  if (!(std::isfinite(z_scale) && z_scale > 0.0)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "z_scale must be finite and positive");
+  if (((uintptr_t)samples & 15u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev is not 16-byte aligned");
+  if ((((uintptr_t)n_samples | (uintptr_t)group_offsets | (uintptr_t)first_step | (uintptr_t)status) & 3u) != 0)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "an int32 array is not 4-byte aligned");
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_mutual_clearance(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                 const int32_t* group_offsets, int32_t n_groups, const int32_t* first_step, const int32_t* status,
+                                 double z_scale, double* clearance_out, int32_t* partner_out, double* min_clearance_out,
+                                 int32_t* argmin_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (const int rc = mutual_clearance_arguments(ctx, samples, n_samples, sample_capacity, group_offsets, n_groups, first_step,
+                                                status, z_scale);
+      rc != MRS_TG_OK)
+    return rc;
+  if (sample_capacity > 0 && !clearance_out && !partner_out && !min_clearance_out && !argmin_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "every output of mrs_tg_plan_mutual_clearance is NULL");
+  if ((((uintptr_t)clearance_out | (uintptr_t)min_clearance_out) & 7u) != 0 ||
+      (((uintptr_t)partner_out | (uintptr_t)argmin_out) & 3u) != 0)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "an output array is not aligned to its element");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 35);
+  HIP_TRY(ctx, mrs_tg::launch_mutual_clearance(plan->view.n_paths, samples, n_samples, sample_capacity, group_offsets, n_groups,
+                                               first_step, status, z_scale, clearance_out, partner_out, min_clearance_out,
+                                               argmin_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_mutual_clearance_vjp(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                     const int32_t* group_offsets, int32_t n_groups, const int32_t* first_step,
+                                     const int32_t* status, double z_scale, const int32_t* partner, const double* grad_clearance,
+                                     double* grad_samples_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (const int rc = mutual_clearance_arguments(ctx, samples, n_samples, sample_capacity, group_offsets, n_groups, first_step,
+                                                status, z_scale);
+      rc != MRS_TG_OK)
+    return rc;
+  if (sample_capacity > 0 && (!partner || !grad_clearance || !grad_samples_out))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "partner_dev, grad_clearance_dev and grad_samples_out_dev are required");
+  if (((uintptr_t)grad_samples_out & 15u) != 0 || ((uintptr_t)grad_clearance & 7u) != 0 || ((uintptr_t)partner & 3u) != 0)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
+                "grad_samples_out_dev is not 16-byte aligned, or grad_clearance_dev or partner_dev not to its element");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 36);
+  HIP_TRY(ctx, mrs_tg::launch_mutual_clearance_vjp(plan->view.n_paths, samples, n_samples, sample_capacity, group_offsets, n_groups,
+                                                   first_step, status, z_scale, partner, grad_clearance, grad_samples_out,
+                                                   ctx->stream));
   return MRS_TG_OK;
 }
 

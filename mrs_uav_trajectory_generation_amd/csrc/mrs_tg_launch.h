@@ -340,6 +340,20 @@ hipError_t launch_request_limits(int n_paths, const double* constraints, const d
 hipError_t launch_request_limits_vjp(int n_paths, const int32_t* branch, int fallback, double speed_factor, double accel_factor,
                                      const double* grad_limits, double* grad_constraints, double* grad_override,
                                      hipStream_t stream);
+// mrs_tg_plan_mutual_clearance / mrs_tg_plan_mutual_clearance_vjp (mrs_tg_clearance.hip, mrs_tg_clearance.hpp): per row of samples
+// [n_paths][capacity][4] the distance to the nearest other path of the row's group at the same common step (group_offsets
+// [n_groups + 1], first_step [n_paths] or null: all 0; z_scale weighs the vertical separation) and that path's index, per path
+// the minimum over its rows and where it is (every output may be null); and its backward pass, dL/dsamples from dL/dclearance
+// with the partners held fixed, a gather.  status null or per path (<= 0: no rows, nobody's neighbour).  One workgroup per path;
+// reads only, no workspace, no dynamic LDS; each timed as the kernel family of the pending ProfileScope
+hipError_t launch_mutual_clearance(int n_paths, const double* samples, const int32_t* n_samples, int capacity,
+                                   const int32_t* group_offsets, int n_groups, const int32_t* first_step, const int32_t* status,
+                                   double z_scale, double* clearance, int32_t* partner, double* min_clearance, int32_t* argmin,
+                                   hipStream_t stream);
+hipError_t launch_mutual_clearance_vjp(int n_paths, const double* samples, const int32_t* n_samples, int capacity,
+                                       const int32_t* group_offsets, int n_groups, const int32_t* first_step,
+                                       const int32_t* status, double z_scale, const int32_t* partner, const double* grad_clearance,
+                                       double* grad_samples, hipStream_t stream);
 // What the rows kernel can do around its solve for the same path, in the same launch:
 //   before: the feasibility scaling of the segment times (scaleSegmentTimesWithViolation's T_i <- s_i T_i from the
 //           per-segment maxima, written back to seg_times) -- the last stage before the final solve of the Mellinger pipeline;
