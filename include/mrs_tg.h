@@ -223,9 +223,12 @@ enum {
   MRS_TG_CAP_REQUEST = 32768,           /* mrs_tg_plan_request_vertices, mrs_tg_plan_request_limits and their two backward passes
                                          are exported: the vertices and the limits findTrajectory derives from a request, as plan
                                          steps */
-  MRS_TG_CAP_MUTUAL_CLEARANCE = 65536   /* mrs_tg_plan_mutual_clearance and mrs_tg_plan_mutual_clearance_vjp are exported: how close
+  MRS_TG_CAP_MUTUAL_CLEARANCE = 65536,  /* mrs_tg_plan_mutual_clearance and mrs_tg_plan_mutual_clearance_vjp are exported: how close
                                          the paths of one group (a swarm) come to each other at common steps, the nearest
                                          neighbour's index, and the backward pass */
+  MRS_TG_CAP_OBSTACLE_CLEARANCE = 131072 /* mrs_tg_plan_obstacle_clearance and mrs_tg_plan_obstacle_clearance_vjp are exported: the
+                                         signed distance of every row to the nearest sphere or point of the path's obstacle set,
+                                         that obstacle's index, and the backward pass */
 };
 
 /* mrs_tg_plan_request_limits' flags_dev: what the request asks of its limits */
@@ -1162,6 +1165,65 @@ int mrs_tg_plan_mutual_clearance_vjp(mrs_tg_plan* plan, const double* samples_de
                                      const int32_t* first_step_dev, const int32_t* status_dev, double z_scale,
                                      const int32_t* partner_dev, const double* grad_clearance_dev, double* grad_samples_out_dev);
 
+/* Clearance from static obstacles as a plan step (MRS_TG_CAP_OBSTACLE_CLEARANCE; obstacle_clearance_kernel,
+ * csrc/mrs_tg_obstacle.hpp): how close every row a sampler left comes to a map, and which obstacle of
+ * the map that is.  The plan contributes its path count and its context; segments play no part and every array is in the
+ * caller's path order.  An obstacle is four doubles (x, y, z, radius): a sphere, or with radius 0 a point of a cloud.  The
+ * obstacles live in one array obstacles_dev [n_obstacles][4], partitioned into SETS, contiguous runs: set_offsets_dev
+ * [n_sets + 1] (int32; well-formed offsets start at 0, do not decrease and end at n_obstacles).  path_set_dev [n_paths] (int32)
+ * names the set each path sees; NULL = every path sees set 0.  A path sees no obstacle when its path_set entry is outside
+ * [0, n_sets), when its set is empty or when it is dead.  samples_dev [n_paths][sample_capacity][4] and n_samples_dev [n_paths]
+ * are what a solve or a sampler left; a path has n = min(n_samples, sample_capacity) live rows (a count of sample_capacity + 1
+ * is sample_capacity rows), none with status_dev (may be NULL) <= 0.  For every live row (x, y, z, .) of path p and every
+ * obstacle k of p's set, with kappa = z_scale (finite, positive; 1.0 the Euclidean distance, below 1 vertical separation
+ * weighs less),
+ *   dx = x - ox,  dy = y - oy,  dz = kappa (z - oz)
+ *   s = sqrt((dx dx + dy dy) + dz dz),  c = s - radius      products and sums in this order, no fused multiply-add
+ * c is signed: negative inside a sphere.  The row's clearance is the minimum of c over k, taken with a strict < from +inf in
+ * increasing k: a tie goes to the lowest obstacle index, a c that is not a number never becomes a minimum.  Coordinates and
+ * radii are ordinary data: a NaN coordinate makes that obstacle lose, an infinite radius is what the arithmetic makes of it.
+ * Outputs, each may be NULL, not all:
+ *   clearance_out_dev [n_paths][sample_capacity]      the minimum; +inf where the path sees no obstacle, in the rows from n on
+ *                                                     and on dead paths (relu(R - c) needs no mask)
+ *   nearest_out_dev [n_paths][sample_capacity] int32  the nearest obstacle's index in the WHOLE obstacles array, -1 exactly where
+ *                                                     clearance is +inf
+ *   min_clearance_out_dev [n_paths]                   the minimum over the path's rows, +inf without any
+ *   argmin_out_dev [n_paths][2] int32                 the first row whose clearance is strictly below every row in front of it,
+ *                                                     and its obstacle; {-1, -1} without any
+ * One workgroup per path, one lane per row, the obstacles of the path's set the inner loop in increasing index, read as
+ * wavefront-uniform data; the per-path minimum is combined in the order "smaller value, then lower row", which no split
+ * changes.  No atomics, no workspace; every output element that belongs to the plan is written exactly once; the same bits on
+ * every call and for a path wherever it sits in the batch and wherever its set sits in the array.  Set bounds are clamped into
+ * [0, n_obstacles] with end >= begin, so no read leaves the obstacle array whatever set_offsets_dev and path_set_dev hold.  Out
+ * of scope: a gradient with respect to the obstacles (a static map); a spatial index over them; a small batch against a large
+ * map uses one workgroup per path and so a part of the device.
+ * MRS_TG_ERR_INVALID_ARG, before any launch: plan, n_samples_dev or set_offsets_dev NULL, samples_dev NULL with a positive
+ * capacity, obstacles_dev NULL with n_obstacles > 0, a negative n_obstacles, n_sets or sample_capacity, a z_scale that is not
+ * finite and positive, no output given, samples_dev or obstacles_dev not 16-byte aligned or another array not aligned to its
+ * element.  n_paths == 0 or sample_capacity == 0: success, nothing is launched or written.  n_obstacles == 0 or n_sets == 0: the
+ * kernel runs and writes +inf / -1 everywhere.  Device pointers, asynchronous on the context's stream. */
+int mrs_tg_plan_obstacle_clearance(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev,
+                                   int32_t sample_capacity, const double* obstacles_dev, int32_t n_obstacles,
+                                   const int32_t* set_offsets_dev, int32_t n_sets, const int32_t* path_set_dev,
+                                   const int32_t* status_dev, double z_scale, double* clearance_out_dev,
+                                   int32_t* nearest_out_dev, double* min_clearance_out_dev, int32_t* argmin_out_dev);
+/* Backward pass of mrs_tg_plan_obstacle_clearance (obstacle_clearance_vjp_kernel), the nearest obstacles
+ * held fixed: given grad_clearance_dev [n_paths][sample_capacity] = dL/dclearance and nearest_dev, the forward's nearest_out_dev
+ * (an input), writes grad_samples_out_dev [n_paths][sample_capacity][4] = dL/dsamples: column 3 zero, rows from n on zero, dead
+ * paths zero.  For a live row with upstream g, nearest obstacle k and dx, dy, dz, s as in the forward,
+ *   dL/drow = (g (dx / s), g (dy / s), g ((kappa dz) / s))      each quotient rounded, then the product.
+ * Exactly 0 come from: g == 0 (so the +inf rows never make a NaN), s == 0 (a row on a centre), a nearest entry that is -1 or
+ * outside the path's own clamped set -- none of which dereferences an obstacle.  No gradient flows through the choice of the
+ * obstacle, and there is none with respect to the obstacles.  One lane per output row: deterministic, no atomics, no workspace,
+ * every element written exactly once, the same bits on every call and wherever the path sits in the batch.
+ * grad_samples_out_dev may not overlap an input.  The argument checks are the forward's, with nearest_dev, grad_clearance_dev
+ * and grad_samples_out_dev (16-byte aligned) required. */
+int mrs_tg_plan_obstacle_clearance_vjp(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev,
+                                       int32_t sample_capacity, const double* obstacles_dev, int32_t n_obstacles,
+                                       const int32_t* set_offsets_dev, int32_t n_sets, const int32_t* path_set_dev,
+                                       const int32_t* status_dev, double z_scale, const int32_t* nearest_dev,
+                                       const double* grad_clearance_dev, double* grad_samples_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
@@ -1183,7 +1245,8 @@ int mrs_tg_plan_mutual_clearance_vjp(mrs_tg_plan* plan, const double* samples_de
  * mrs_tg_plan_initial_condition_vjp, mrs_tg_plan_prepend_initial_condition_vjp), 31 the request's vertices
  * (mrs_tg_plan_request_vertices), 32 their backward pass (mrs_tg_plan_request_vertices_vjp), 33 the request's limits
  * (mrs_tg_plan_request_limits), 34 their backward pass (mrs_tg_plan_request_limits_vjp), 35 the mutual clearance
- * (mrs_tg_plan_mutual_clearance), 36 its backward pass (mrs_tg_plan_mutual_clearance_vjp): thirty-seven ids, 0 .. 36.
+ * (mrs_tg_plan_mutual_clearance), 36 its backward pass (mrs_tg_plan_mutual_clearance_vjp), 37 the clearance from obstacles
+ * (mrs_tg_plan_obstacle_clearance), 38 its backward pass (mrs_tg_plan_obstacle_clearance_vjp): thirty-nine ids, 0 .. 38.
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

@@ -56,6 +56,7 @@ KERNEL_INITIAL_CONDITION, KERNEL_PREPEND_INITIAL_CONDITION, KERNEL_SPLICE_PREDIC
 KERNEL_SPLICE_PREDICTION_VJP, KERNEL_INITIAL_CONDITION_VJP, KERNEL_PREPEND_INITIAL_CONDITION_VJP = 28, 29, 30
 KERNEL_REQUEST_VERTICES, KERNEL_REQUEST_VERTICES_VJP, KERNEL_REQUEST_LIMITS, KERNEL_REQUEST_LIMITS_VJP = 31, 32, 33, 34
 KERNEL_MUTUAL_CLEARANCE, KERNEL_MUTUAL_CLEARANCE_VJP = 35, 36
+KERNEL_OBSTACLE_CLEARANCE, KERNEL_OBSTACLE_CLEARANCE_VJP = 37, 38
 
 
 class MrsTgError(RuntimeError):
@@ -127,6 +128,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_plan_request_vertices", "mrs_tg_plan_request_vertices_vjp", "mrs_tg_plan_request_limits",
     "mrs_tg_plan_request_limits_vjp",
     "mrs_tg_plan_mutual_clearance", "mrs_tg_plan_mutual_clearance_vjp",
+    "mrs_tg_plan_obstacle_clearance", "mrs_tg_plan_obstacle_clearance_vjp",
 ]
 
 _lib = None
@@ -286,6 +288,10 @@ def load_library():
     L.mrs_tg_plan_mutual_clearance.argtypes = [vp, dp, ip, C.c_int32, ip, C.c_int32, ip, ip, C.c_double, dp, ip, dp, ip]
     L.mrs_tg_plan_mutual_clearance_vjp.restype = C.c_int
     L.mrs_tg_plan_mutual_clearance_vjp.argtypes = [vp, dp, ip, C.c_int32, ip, C.c_int32, ip, ip, C.c_double, ip, dp, dp]
+    L.mrs_tg_plan_obstacle_clearance.restype = C.c_int
+    L.mrs_tg_plan_obstacle_clearance.argtypes = [vp, dp, ip, C.c_int32, dp, C.c_int32, ip, C.c_int32, ip, ip, C.c_double, dp, ip, dp, ip]
+    L.mrs_tg_plan_obstacle_clearance_vjp.restype = C.c_int
+    L.mrs_tg_plan_obstacle_clearance_vjp.argtypes = [vp, dp, ip, C.c_int32, dp, C.c_int32, ip, C.c_int32, ip, ip, C.c_double, ip, dp, dp]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -350,6 +356,7 @@ IC_PREPEND, IC_FROM_FUTURE, IC_DROP_FIRST, IC_FROM_TRACKER, IC_FROM_UAV, IC_FROM
 IC_FLAG_TRACKER, IC_FLAG_UAV, IC_FLAG_DONT_PREPEND = 1, 2, 4
 CAP_REQUEST = 32768   # MRS_TG_CAP_REQUEST: Plan.request_vertices, Plan.request_limits (findTrajectory's vertices and limits as plan steps) and their two backward passes
 CAP_MUTUAL_CLEARANCE = 65536   # MRS_TG_CAP_MUTUAL_CLEARANCE: Plan.mutual_clearance (the nearest other path of a row's group at the same step), Plan.mutual_clearance_vjp
+CAP_OBSTACLE_CLEARANCE = 131072   # MRS_TG_CAP_OBSTACLE_CLEARANCE: Plan.obstacle_clearance (the nearest sphere or point of the path's obstacle set, signed), Plan.obstacle_clearance_vjp
 # Plan.request_limits' flags input (MRS_TG_REQ_*) and its branch word (MRS_TG_LIM_*)
 REQ_OVERRIDE, REQ_RELAX_HEADING = 1, 2
 LIM_OVERRIDDEN, LIM_OVERRIDE_REFUSED, LIM_RELAXED, LIM_V_DESCENDING, LIM_A_DESCENDING, LIM_J_DESCENDING, LIM_FALLBACK = 1, 2, 4, 8, 16, 32, 64
@@ -537,6 +544,39 @@ def check_group_offsets(group_offsets, n_paths):
     if g[0] != 0 or g[-1] != int(n_paths) or np.any(np.diff(g) < 0):
         raise ValueError("group_offsets must start at 0, not decrease and end at n_paths = %d (got %s)" % (n_paths, g.tolist()))
     return np.ascontiguousarray(g, dtype=np.int32)
+
+
+def check_set_offsets(set_offsets, n_obstacles):
+    """Host set offsets of Plan.obstacle_clearance as a contiguous int32 array [n_sets + 1], or ValueError: they start at 0, do
+    not decrease and end at n_obstacles (a set may be empty).  No device is needed."""
+    try:
+        raw = np.asarray(set_offsets)
+    except Exception as e:
+        raise ValueError("set_offsets is not an array of integers: %s" % e)
+    if raw.ndim != 1 or raw.size < 1 or raw.dtype.kind not in "iu":
+        raise ValueError("set_offsets must be a one-dimensional array of at least one integer")
+    g = raw.astype(np.int64)
+    if g[0] != 0 or g[-1] != int(n_obstacles) or np.any(np.diff(g) < 0):
+        raise ValueError("set_offsets must start at 0, not decrease and end at n_obstacles = %d (got %s)"
+                         % (n_obstacles, g.tolist()))
+    return np.ascontiguousarray(g, dtype=np.int32)
+
+
+def _check_operand(name, t, dtype, shape, like=None, optional=False):
+    """a device tensor as a plan step takes it, or ValueError: dtype, device (`like`'s), contiguous, the shape (None in it: any
+    extent)"""
+    import torch
+    if t is None:
+        if optional:
+            return
+        raise ValueError("%s is required" % name)
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or (like is not None and t.device != like.device):
+        raise ValueError("%s must be a tensor on the device%s" % (name, "" if like is None else " of samples"))
+    if t.dtype != dtype or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous %s tensor" % (name, dtype))
+    if t.dim() != len(shape) or any(want is not None and have != want for have, want in zip(t.shape, shape)):
+        raise ValueError("%s must be %s, not %s" % (name, "".join("[%s]" % ("." if w is None else w) for w in shape),
+                                                    list(t.shape)))
 
 
 class Context:
@@ -1049,6 +1089,74 @@ class Plan:
                                                                  _t_ptr(first_step), _t_ptr(status), float(z_scale),
                                                                  _t_ptr(partner), _t_ptr(grad_clearance), _t_ptr(grad_samples)),
                         "mrs_tg_plan_mutual_clearance_vjp")
+
+    def _set_offsets_dev(self, set_offsets, obstacles):
+        """set_offsets as mrs_tg_plan_obstacle_clearance takes them: a device int32 tensor is the caller's statement and passes
+        as it is; a host sequence or array is checked (check_set_offsets: ValueError) and uploaded to the obstacles' device -- a
+        blocking copy, so a caller in a loop keeps the tensor this returns"""
+        import torch
+        if isinstance(set_offsets, torch.Tensor) and set_offsets.is_cuda:
+            if set_offsets.dtype != torch.int32 or set_offsets.dim() != 1 or set_offsets.numel() < 1 or \
+                    not set_offsets.is_contiguous() or set_offsets.device != obstacles.device:
+                raise ValueError("set_offsets on the device must be a contiguous int32 tensor [n_sets + 1] beside the obstacles")
+            return set_offsets
+        if isinstance(set_offsets, torch.Tensor):
+            set_offsets = set_offsets.numpy()
+        g = torch.from_numpy(check_set_offsets(set_offsets, int(obstacles.shape[0]))).to(obstacles.device)
+        torch.cuda.current_stream(obstacles.device).synchronize()
+        return g
+
+    def _obstacle_operands(self, samples, n_samples, obstacles, set_offsets, path_set, status):
+        """the operand checks the two obstacle calls share -> (set_offsets on the device, capacity)"""
+        import torch
+        P = self.n_paths
+        _check_operand("samples", samples, torch.float64, (P, None, N_DIM))
+        _check_operand("n_samples", n_samples, torch.int32, (P,), samples)
+        _check_operand("obstacles", obstacles, torch.float64, (None, 4), samples)
+        _check_operand("path_set", path_set, torch.int32, (P,), samples, optional=True)
+        _check_operand("status", status, torch.int32, (P,), samples, optional=True)
+        return self._set_offsets_dev(set_offsets, obstacles), int(samples.shape[1])
+
+    def obstacle_clearance(self, samples, n_samples, obstacles, set_offsets, path_set=None, status=None, z_scale=1.0,
+                           clearance=None, nearest=None, min_clearance=None, argmin=None):
+        """mrs_tg_plan_obstacle_clearance: per row of samples [n_paths][capacity][4] (n_samples [n_paths] int32) the signed
+        distance to the nearest obstacle of the path's set -- obstacles [n_obstacles][4] = (x, y, z, radius), set_offsets
+        [n_sets + 1] (a device int32 tensor, or a host sequence, which is checked and uploaded), path_set [n_paths] int32 (None:
+        every path sees set 0), z_scale the weight of the vertical separation -- into clearance [n_paths][capacity] (+inf
+        without an obstacle; negative inside a sphere), nearest [n_paths][capacity] (int32, the obstacle's index in the whole
+        array, -1 where clearance is +inf), min_clearance [n_paths] and argmin [n_paths][2] (int32: row, obstacle) (device
+        tensors, written; None = not wanted, at least one given); asynchronous on the context's stream."""
+        import torch
+        g, cap = self._obstacle_operands(samples, n_samples, obstacles, set_offsets, path_set, status)
+        P = self.n_paths
+        _check_operand("clearance", clearance, torch.float64, (P, cap), samples, optional=True)
+        _check_operand("nearest", nearest, torch.int32, (P, cap), samples, optional=True)
+        _check_operand("min_clearance", min_clearance, torch.float64, (P,), samples, optional=True)
+        _check_operand("argmin", argmin, torch.int32, (P, 2), samples, optional=True)
+        self.ctx._check(self._L.mrs_tg_plan_obstacle_clearance(self._h, _t_ptr(samples), _t_ptr(n_samples), cap, _t_ptr(obstacles),
+                                                               int(obstacles.shape[0]), _t_ptr(g), int(g.numel()) - 1,
+                                                               _t_ptr(path_set), _t_ptr(status), float(z_scale),
+                                                               _t_ptr(clearance), _t_ptr(nearest), _t_ptr(min_clearance),
+                                                               _t_ptr(argmin)),
+                        "mrs_tg_plan_obstacle_clearance")
+
+    def obstacle_clearance_vjp(self, samples, n_samples, obstacles, set_offsets, nearest, grad_clearance, grad_samples,
+                               path_set=None, status=None, z_scale=1.0):
+        """mrs_tg_plan_obstacle_clearance_vjp: dL/dsamples [n_paths][capacity][4] (grad_samples, written, zeros included) from
+        dL/dclearance (grad_clearance [n_paths][capacity]) with the forward's nearest [n_paths][capacity] (int32) held fixed;
+        the other arguments are the forward's; asynchronous on the context's stream."""
+        import torch
+        g, cap = self._obstacle_operands(samples, n_samples, obstacles, set_offsets, path_set, status)
+        P = self.n_paths
+        _check_operand("nearest", nearest, torch.int32, (P, cap), samples)
+        _check_operand("grad_clearance", grad_clearance, torch.float64, (P, cap), samples)
+        _check_operand("grad_samples", grad_samples, torch.float64, (P, cap, N_DIM), samples)
+        self.ctx._check(self._L.mrs_tg_plan_obstacle_clearance_vjp(self._h, _t_ptr(samples), _t_ptr(n_samples), cap,
+                                                                   _t_ptr(obstacles), int(obstacles.shape[0]), _t_ptr(g),
+                                                                   int(g.numel()) - 1, _t_ptr(path_set), _t_ptr(status),
+                                                                   float(z_scale), _t_ptr(nearest), _t_ptr(grad_clearance),
+                                                                   _t_ptr(grad_samples)),
+                        "mrs_tg_plan_obstacle_clearance_vjp")
 
     def estimate_times(self, waypoints, limits, seg_times):
         """mrs_tg_plan_estimate_times: the Euclidean segment-time estimate of waypoints [sum V][4] under limits [n_paths][9] into

@@ -124,6 +124,21 @@ paths in one plan, kept 2 m apart:
     >>> clearance, partner = mutual_clearance(plan, samples, n, [0, 4], status=status)   # one group; all start at step 0
     >>> torch.relu(2.0 - clearance).sum().backward()                    # +inf where nobody is near in time: no mask; fv.grad, times.grad
     >>> closest = clearance.amin(dim=1)                                 # per UAV; partner says to whom
+
+obstacle_clearance (Plan.obstacle_clearance forward, Plan.obstacle_clearance_vjp backward: mrs_tg_plan_obstacle_clearance /
+mrs_tg_plan_obstacle_clearance_vjp) is the clearance loss of the first example against a real map: a
+point cloud or a list of spheres, hundreds to thousands of them, [n_obstacles][4] = (x, y, z, radius) with radius 0 for a point.
+For every row the stage gives the signed distance to the nearest obstacle (negative inside a sphere) and that obstacle's index
+-- one launch, no [N][Q][M] temporary, ties to the lowest index.  Paths may see different parts of the map (set_offsets,
+path_set); the nearest obstacle is held fixed in the backward pass, and the map itself gets no gradient.  Keeping 1 m away
+from everything, checked on a grid finer than the tracker's:
+
+    >>> fv = fixed_values.clone().requires_grad_(); times = seg_times.clone().requires_grad_()
+    >>> coeffs, _, status = solve(plan, fixed_mask, fv, times)
+    >>> samples, n = sample(plan, coeffs, times, 0.05, 2048, status)    # (or evaluate(...) at times of the caller's choosing)
+    >>> clearance, nearest = obstacle_clearance(plan, samples, n, obstacles, status=status)   # one set: the whole map
+    >>> torch.relu(1.0 - clearance).sum().backward()                    # +inf behind a path's last row: no mask; fv.grad, times.grad
+    >>> worst = clearance.amin(dim=1)                                   # per path; nearest says which obstacle
 """
 import numpy as np
 import torch
@@ -704,6 +719,66 @@ def mutual_clearance(plan, samples, n_samples, group_offsets, first_step=None, s
     gradient holds every partner fixed; coincident rows (clearance 0) contribute zero.  A path counts only on the steps where
     it has rows -- to let a UAV hover at its last row, repeat that row up to the horizon and raise n_samples."""
     return _MutualClearance.apply(plan, samples, n_samples, group_offsets, first_step, status, z_scale)
+
+
+class _ObstacleClearance(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, samples, n_samples, obstacles, set_offsets, path_set, status, z_scale):
+        s = samples.detach().to(torch.float64).contiguous()
+        n = n_samples.detach().to(torch.int32).contiguous()
+        if s.dim() != 3 or s.shape[0] != plan.n_paths or s.shape[2] != api.N_DIM:
+            raise ValueError("samples must be [n_paths][capacity][4]")
+        if n.dim() != 1 or n.shape[0] != plan.n_paths:
+            raise ValueError("n_samples must be [n_paths]")
+        ob = obstacles.detach().to(torch.float64).contiguous()
+        if ob.dim() != 2 or ob.shape[1] != 4:
+            raise ValueError("obstacles must be [n_obstacles][4]: x, y, z, radius")
+        ps = None if path_set is None else path_set.detach().to(torch.int32).contiguous()
+        if ps is not None and (ps.dim() != 1 or ps.shape[0] != plan.n_paths):
+            raise ValueError("path_set must be [n_paths]")
+        st = None if status is None else status.detach().to(torch.int32).contiguous()
+        g = plan._set_offsets_dev([0, int(ob.shape[0])] if set_offsets is None else set_offsets, ob)
+        # (a call without rows launches nothing: the neutral values are there beforehand)
+        clearance = torch.full(s.shape[:2], float("inf"), dtype=torch.float64, device=s.device)
+        nearest = torch.full(s.shape[:2], -1, dtype=torch.int32, device=s.device)
+        plan.ctx.use_torch_stream()
+        plan.obstacle_clearance(s, n, ob, g, path_set=ps, status=st, z_scale=float(z_scale), clearance=clearance, nearest=nearest)
+        ctx.plan, ctx.path_set, ctx.status, ctx.z_scale = plan, ps, st, float(z_scale)
+        ctx.save_for_backward(s, n, ob, g, nearest)
+        ctx.mark_non_differentiable(nearest)
+        ctx.set_materialize_grads(False)
+        return clearance, nearest
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_clearance, _grad_nearest):
+        s, n, ob, g, nearest = ctx.saved_tensors
+        if grad_clearance is None or not ctx.needs_input_grad[1]:
+            return None, None, None, None, None, None, None, None
+        gs = torch.zeros_like(s)
+        plan = ctx.plan
+        plan.ctx.use_torch_stream()   # (the autograd engine runs this on its own thread, on the forward's stream)
+        plan.obstacle_clearance_vjp(s, n, ob, g, nearest, grad_clearance.to(torch.float64).contiguous(), gs,
+                                    path_set=ctx.path_set, status=ctx.status, z_scale=ctx.z_scale)
+        return None, gs, None, None, None, None, None, None
+
+
+def obstacle_clearance(plan, samples, n_samples, obstacles, set_offsets=None, path_set=None, status=None, z_scale=1.0):
+    """(clearance [n_paths][capacity], nearest [n_paths][capacity] int32) of Plan.obstacle_clearance: for every live row of
+    samples [n_paths][capacity][4] the signed distance sqrt(dx^2 + dy^2 + (z_scale dz)^2) - radius to the nearest obstacle of
+    the path's set (negative inside a sphere), and that obstacle's index in the whole array.  obstacles [n_obstacles][4] =
+    (x, y, z, radius), a radius of 0 a point of a cloud; the sets are contiguous runs of obstacles: set_offsets [n_sets + 1], a
+    device int32 tensor or a host sequence (checked: starts at 0, does not decrease, ends at n_obstacles), None: one set that
+    holds every obstacle; path_set [n_paths] int32 names every path's set (None: set 0; an entry outside [0, n_sets): no
+    obstacle); n_samples [n_paths] int32 as the sampler returned it.  Differentiable in samples ONLY (float64 device tensor; x,
+    y, z are read, column 3 gets a zero gradient): the obstacles are a static map, and asking for their gradient raises
+    instead of returning None.  Rows of a path that sees no obstacle, rows from n on and the rows of a path with status <= 0
+    (status [n_paths], optional) hold clearance +inf and nearest -1 and get a zero gradient: relu(R - clearance) needs no
+    mask.  The gradient holds every nearest obstacle fixed; a row on an obstacle's centre contributes zero."""
+    if isinstance(obstacles, torch.Tensor) and obstacles.requires_grad:
+        raise ValueError("obstacle_clearance has no gradient with respect to the obstacles (a static map): pass "
+                         "obstacles.detach()")
+    return _ObstacleClearance.apply(plan, samples, n_samples, obstacles, set_offsets, path_set, status, z_scale)
 
 
 def _f64(t):

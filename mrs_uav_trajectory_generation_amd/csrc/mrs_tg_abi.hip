@@ -53,7 +53,7 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 37;  // kernel_id 0 .. 36 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 39;  // kernel_id 0 .. 38 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
   long long ev_count[kTimedKernels] = {};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
@@ -197,7 +197,7 @@ int mrs_tg_capabilities(void) {
          MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE | MRS_TG_CAP_DEVIATION |
          MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE | MRS_TG_CAP_BACA | MRS_TG_CAP_FALLBACK_SAMPLE |
          MRS_TG_CAP_PATH_EDIT | MRS_TG_CAP_TRAVEL_HEADING | MRS_TG_CAP_INITIAL_CONDITION | MRS_TG_CAP_REQUEST |
-         MRS_TG_CAP_MUTUAL_CLEARANCE;
+         MRS_TG_CAP_MUTUAL_CLEARANCE | MRS_TG_CAP_OBSTACLE_CLEARANCE;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1651,6 +1651,72 @@ int mrs_tg_plan_mutual_clearance_vjp(mrs_tg_plan* plan, const double* samples, c
   HIP_TRY(ctx, mrs_tg::launch_mutual_clearance_vjp(plan->view.n_paths, samples, n_samples, sample_capacity, group_offsets, n_groups,
                                                    first_step, status, z_scale, partner, grad_clearance, grad_samples_out,
                                                    ctx->stream));
+  return MRS_TG_OK;
+}
+
+// ---- clearance from static obstacles as a plan step (mrs_tg_obstacle.hip) --------------------------------------------------------
+
+// what the two obstacle calls check before any launch
+static int obstacle_clearance_arguments(mrs_tg_ctx* ctx, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                        const double* obstacles, int32_t n_obstacles, const int32_t* set_offsets, int32_t n_sets,
+                                        const int32_t* path_set, const int32_t* status, double z_scale) {
+  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
+  if (n_obstacles < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_obstacles %d is negative", n_obstacles);
+  if (n_sets < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_sets %d is negative", n_sets);
+  if (!n_samples || !set_offsets || (sample_capacity > 0 && !samples))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev and set_offsets_dev are required");
+  if (n_obstacles > 0 && !obstacles) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "obstacles_dev is NULL with %d obstacles", n_obstacles);
+  if (!(std::isfinite(z_scale) && z_scale > 0.0)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "z_scale must be finite and positive");
+  if ((((uintptr_t)samples | (uintptr_t)obstacles) & 15u) != 0)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev or obstacles_dev is not 16-byte aligned");
+  if ((((uintptr_t)n_samples | (uintptr_t)set_offsets | (uintptr_t)path_set | (uintptr_t)status) & 3u) != 0)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "an int32 array is not 4-byte aligned");
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_obstacle_clearance(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                   const double* obstacles, int32_t n_obstacles, const int32_t* set_offsets, int32_t n_sets,
+                                   const int32_t* path_set, const int32_t* status, double z_scale, double* clearance_out,
+                                   int32_t* nearest_out, double* min_clearance_out, int32_t* argmin_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (const int rc = obstacle_clearance_arguments(ctx, samples, n_samples, sample_capacity, obstacles, n_obstacles, set_offsets,
+                                                  n_sets, path_set, status, z_scale);
+      rc != MRS_TG_OK)
+    return rc;
+  if (!clearance_out && !nearest_out && !min_clearance_out && !argmin_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "every output of mrs_tg_plan_obstacle_clearance is NULL");
+  if ((((uintptr_t)clearance_out | (uintptr_t)min_clearance_out) & 7u) != 0 ||
+      (((uintptr_t)nearest_out | (uintptr_t)argmin_out) & 3u) != 0)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "an output array is not aligned to its element");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 37);
+  HIP_TRY(ctx, mrs_tg::launch_obstacle_clearance(plan->view.n_paths, samples, n_samples, sample_capacity, obstacles, n_obstacles,
+                                                 set_offsets, n_sets, path_set, status, z_scale, clearance_out, nearest_out,
+                                                 min_clearance_out, argmin_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_obstacle_clearance_vjp(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                       const double* obstacles, int32_t n_obstacles, const int32_t* set_offsets, int32_t n_sets,
+                                       const int32_t* path_set, const int32_t* status, double z_scale, const int32_t* nearest,
+                                       const double* grad_clearance, double* grad_samples_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  if (const int rc = obstacle_clearance_arguments(ctx, samples, n_samples, sample_capacity, obstacles, n_obstacles, set_offsets,
+                                                  n_sets, path_set, status, z_scale);
+      rc != MRS_TG_OK)
+    return rc;
+  if (!nearest || !grad_clearance || !grad_samples_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "nearest_dev, grad_clearance_dev and grad_samples_out_dev are required");
+  if (((uintptr_t)grad_samples_out & 15u) != 0 || ((uintptr_t)grad_clearance & 7u) != 0 || ((uintptr_t)nearest & 3u) != 0)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
+                "grad_samples_out_dev is not 16-byte aligned, or grad_clearance_dev or nearest_dev not to its element");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 38);
+  HIP_TRY(ctx, mrs_tg::launch_obstacle_clearance_vjp(plan->view.n_paths, samples, n_samples, sample_capacity, obstacles,
+                                                     n_obstacles, set_offsets, n_sets, path_set, status, z_scale, nearest,
+                                                     grad_clearance, grad_samples_out, ctx->stream));
   return MRS_TG_OK;
 }
 

@@ -354,6 +354,21 @@ hipError_t launch_mutual_clearance_vjp(int n_paths, const double* samples, const
                                        const int32_t* group_offsets, int n_groups, const int32_t* first_step,
                                        const int32_t* status, double z_scale, const int32_t* partner, const double* grad_clearance,
                                        double* grad_samples, hipStream_t stream);
+// mrs_tg_plan_obstacle_clearance / mrs_tg_plan_obstacle_clearance_vjp (mrs_tg_obstacle.hip, mrs_tg_obstacle.hpp): per row of samples
+// [n_paths][capacity][4] the signed distance to the nearest obstacle of the path's set -- obstacles [n_obstacles][4] = (x, y, z,
+// radius), partitioned into sets by set_offsets [n_sets + 1], path_set [n_paths] or null: every path sees set 0; z_scale weighs
+// the vertical separation -- and that obstacle's index in the whole array, per path the minimum over its rows and where it is
+// (every output may be null); and its backward pass, dL/dsamples from dL/dclearance with the nearest obstacles held fixed.
+// status null or per path (<= 0: no rows).  One workgroup per path; reads only, no workspace, no dynamic LDS; each timed as the
+// kernel family of the pending ProfileScope
+hipError_t launch_obstacle_clearance(int n_paths, const double* samples, const int32_t* n_samples, int capacity,
+                                     const double* obstacles, int n_obstacles, const int32_t* set_offsets, int n_sets,
+                                     const int32_t* path_set, const int32_t* status, double z_scale, double* clearance,
+                                     int32_t* nearest, double* min_clearance, int32_t* argmin, hipStream_t stream);
+hipError_t launch_obstacle_clearance_vjp(int n_paths, const double* samples, const int32_t* n_samples, int capacity,
+                                         const double* obstacles, int n_obstacles, const int32_t* set_offsets, int n_sets,
+                                         const int32_t* path_set, const int32_t* status, double z_scale, const int32_t* nearest,
+                                         const double* grad_clearance, double* grad_samples, hipStream_t stream);
 // What the rows kernel can do around its solve for the same path, in the same launch:
 //   before: the feasibility scaling of the segment times (scaleSegmentTimesWithViolation's T_i <- s_i T_i from the
 //           per-segment maxima, written back to seg_times) -- the last stage before the final solve of the Mellinger pipeline;
