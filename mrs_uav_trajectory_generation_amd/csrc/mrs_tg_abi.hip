@@ -421,8 +421,7 @@ int mrs_tg_plan_create(mrs_tg_ctx* ctx, int32_t n_paths, const int32_t* so, mrs_
   plan->view.seg_offsets = plan->d_seg_offsets.get();
   plan->view.order = plan->view.seg_offsets + off_order;  // (views into the one block)
   plan->view.slot_start = plan->view.seg_offsets + off_slot;
-  const int rc = mrs_tg::nonlinear_plan_build(plan->nl, plan->seg_offsets_host, plan->order_host);
-  if (rc != 0) return cleanup(fail(ctx, MRS_TG_ERR_HIP, "nonlinear plan setup failed"));
+  plan->nl.host = mrs_tg::nonlinear_host_plan(plan->seg_offsets_host, plan->order_host);
   *plan_out = plan;
   return MRS_TG_OK;
 }

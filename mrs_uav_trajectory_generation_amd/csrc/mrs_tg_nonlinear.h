@@ -3,9 +3,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <vector>
 
 #include "mrs_tg_launch.h"
+#include "mrs_tg_nonlinear_route.hpp"
 #include "mrs_tg_pool.h"
 
 namespace mrs_tg {
@@ -37,9 +37,6 @@ struct NonlinearParams {
   bool reference_status = false;   // MRS_TG_FLAG_REFERENCE_STATUS: no runaway test, the outer loop's own code is the path's status
 };
 
-// Paths are sorted by segment count (longest first), so every lane-group class is a contiguous range
-// of positions q.  A path with S segments uses a group of G = min(64, pow2ceil(S + 1)) lanes: lane k of
-// the group evaluates the cost at the k-th perturbed time vector (k = 0: unperturbed).
 struct DfoParams {
   int derivative;
   int mode;            // 0 squared time, 1 Richter time, 3 / 4 the same with the free constraints as variables
@@ -51,28 +48,9 @@ struct DfoParams {
   long long time_budget_ticks = 0;  // as NonlinearParams
 };
 
-struct NonlinearBin {
-  int group;      // lanes per path: 4, 8, 16, 32 or 64
-  int q_begin;    // first position of the bin
-  int q_count;    // number of paths in the bin
-  int max_S;      // largest segment count in the bin
-  int min_S;      // smallest
-};
-
 // (its device blocks go back to the pool with the plan: mrs_tg_plan_destroy synchronises, then deletes)
 struct NonlinearPlan {
-  std::vector<NonlinearBin> bins;
-  std::vector<NonlinearBin> bins1;   // the one-lane-per-vector groups of a plan whose own choice is the dimension split (regroup_possible)
-  bool regroup_possible = false;     // a call may take the lane-group kernels instead of the split kernel (launch_nonlinear)
-  // the plain-path outer loop's bins when EVERY path of four or more segments gets the lanes of the shared half sweeps
-  // (G = pow2ceil(S + 4) instead of pow2ceil(S + 1): 5-7, 13-15 and 29-30 segments move to the next group width); chosen
-  // by launch_nonlinear while the launch is about as large as the device holds at once (see there)
-  std::vector<NonlinearBin> wide_bins;
-  int wide_blocks = 0;             // workgroups of a launch over wide_bins
-  // objective orders below snap (free slots at the end vertices): every path of four or more segments in a group of at least
-  // S + 4 lanes, for the shared half sweeps with free ends (optimize_lean_shared_ends_kernel); empty when a path is too long
-  std::vector<NonlinearBin> ends_bins;
-  int dim_split = 1;               // lanes per time vector in the outer loop: 1 (compact) or 4 (one per dimension)
+  NonlinearHostPlan host;            // the lane-group bins and the dimension split (nonlinear_host_plan, mrs_tg_nonlinear_route.hpp)
   DeviceBlock<double> d_ws;          // factor store of the per-lane linear solve
   DeviceBlock<int32_t> d_opt_status; // stopping reason of the outer loop per path
   DeviceBlock<double> d_maxima;      // [n_segments][9] per-segment maxima
@@ -104,8 +82,6 @@ hipError_t nonlinear_prepare_general(NonlinearPlan& nl, const BatchView& b, cons
 
 // whether optimize_careful_kernel (MRS_TG_FLAG_CAREFUL_COST) is in this build (-DMRS_TG_WITH_CAREFUL=1)
 bool careful_rerun_built();
-
-int nonlinear_plan_build(NonlinearPlan& nl, const std::vector<int32_t>& seg_offsets, const std::vector<int32_t>& order);
 
 // general: paths with a position-free vertex may occur (MRS_TG_FLAG_GENERAL_PATTERNS); they take the 5 x 5-block route
 // (optimize_general_kernel / solve_general_kernel) behind the fast kernels, the others are untouched by it.

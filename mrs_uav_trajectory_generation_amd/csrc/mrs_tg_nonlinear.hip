@@ -56,9 +56,7 @@ namespace mrs_tg {
 #ifndef MRS_TG_MAXIMA_WAVES
 #define MRS_TG_MAXIMA_WAVES 4
 #endif
-#ifndef MRS_TG_LEAN_WAVES
-#define MRS_TG_LEAN_WAVES 2
-#endif
+// (MRS_TG_LEAN_WAVES, the lean kernels' wavefronts per SIMD: mrs_tg_nonlinear_route.hpp, which counts residency by it)
 // The careful re-run (MRS_TG_FLAG_CAREFUL_COST: a second outer-loop kernel with the primal cost for the paths whose by-product
 // cost failed the guard) moved 65536 x 10 from 99.9435 % to 99.9481 % agreement with the oracle at 2-3x the outer loop's time
 // (DESIGN.md section 5): a compile-time option, ON in the shipped library since ABI 4 (build.py: MRS_TG_WITH_CAREFUL=0 in the
@@ -73,7 +71,8 @@ namespace mrs_tg {
 // (twisted factorisation: the two half sweeps meet at the middle vertex, whose block receives a Schur update from each
 // side); the chain per tick is S/2 steps + one join, and the two wavefronts of a path hide each other's latencies.
 // Only for "plain" paths (start, interior..., end segment kinds); anything else keeps the one-sided sweep.
-constexpr int kPairState = 16;  // Sm[10], y[4], qf, red handed from the backward to the forward wavefront, per lane
+// (kPairState doubles per lane are handed from the backward to the forward wavefront: mrs_tg_nonlinear_route.hpp, as every LDS
+// footprint below -- kTickState, group_lds_doubles, gradient_lds_doubles, kLeanPub, kLeanMoving, lean_eval_doubles, lean_group_doubles)
 
 // special: bit i set = segment i takes the masked step, bit 31 = the first segment is a moving start (wave-uniform,
 // worked out once per kernel).  The plain start | interior ... | end path is its own instantiation: even a never-taken
@@ -186,22 +185,6 @@ __device__ __forceinline__ double group_dot(const double* a, const double* b, in
   double s = 0.0;
   for (int i = g; i < S; i += G) s += a[i] * b[i];
   return group_sum(s, G);
-}
-
-// The optimiser's scalar state (f, alpha | neval, npairs, head, ret) is the same in every lane of a group; it is parked
-// in LDS while the objective is evaluated, so that it does not occupy registers there (the kernel sits on its 256-VGPR
-// cap and the compiler spilled exactly these to scratch memory, a global-memory round trip per reload).
-constexpr int kTickState = 5;  // doubles: f, alpha, then six ints (neval, npairs, head, ret | guard tripped, spare)
-// per-group LDS block (doubles): x, g, xn, gn, dir [5*Sb], s[M][Sb], y[M][Sb], rho[M + 1], tick state, staged vertices
-// [(Sb+1)*kVtxLds], moving-start extras [kStartExtra], staged segment records [Sb*kSegLds]
-// extras: the moving-start area (only the one-dimension-per-lane kernels use it; in the four-dimensions-per-lane mapping
-// of large batches many groups share a workgroup and 96 doubles each cost a workgroup per CU)
-__host__ __device__ constexpr int group_lds_doubles(int Sb, bool extras) {
-  return (5 + 2 * kLbfgsM) * Sb + (kLbfgsM + 1) + kTickState + (Sb + 1) * kVtxLds + (extras ? kStartExtra : 0) + Sb * kSegLds;
-}
-// cost_gradient_kernel: x, g [2*Sb], staged vertices
-__host__ __device__ constexpr int gradient_lds_doubles(int Sb, bool extras) {
-  return 2 * Sb + (Sb + 1) * kVtxLds + (extras ? kStartExtra : 0) + Sb * kSegLds;
 }
 
 // Two-sided objective evaluation (forward wavefront's side): forward half sweep, barrier, join with the backward
@@ -371,13 +354,6 @@ __device__ __forceinline__ double evaluate_general(const uint8_t* __restrict__ m
 // keeps the kernel at <= 256 VGPRs, i.e. TWO wavefronts per SIMD where optimize_compact_kernel (436 VGPRs) has one.  The
 // kernels are bound by the dependent chain of a step, not by issue: the second wavefront runs in
 // the first one's idle issue slots.  Lane k of a group of G sweeps time vector k (k, k + G, ... when S + 1 > G).
-constexpr int kLeanPub = 3 * 28;  // evaluate_lean_shared's hand-over area: three half-sweep states of 28 doubles
-// behind it: the start vertex's constrained derivative values of a path that starts from a MOVING state (a replanning request
-// in flight: velocity / acceleration / jerk of the first vertex constrained to non-zero values) -- [0] non-zero = there are
-// such values, [2 + c * 4 + q] = derivative c + 1 of dimension q (zero where the slot is free)
-constexpr int kLeanMoving = 18;
-__host__ __device__ constexpr int lean_eval_doubles(int Sb) { return 4 * Sb + 4 * (Sb + 1) + kLeanPub + kLeanMoving; }  // dp, staging area, hand-over, moving start
-
 // The 45 table constants live in 90 VGPRs per lane, one table per sweep direction.  As compile-time operands -- SGPR pairs the
 // scalar unit sets up -- and ONE table for both sweep directions (an A / B build of round 5, profiles/round5_lean_table_ab.txt):
 // bit-identical results; measured in round 5 (same box, scripts/lean_ab.py): optimize_lean_shared_kernel 256 VGPRs + 80 B of
@@ -847,11 +823,6 @@ __device__ __forceinline__ double evaluate_lean_shared(const double* tabs, const
 }
 
 #undef LEAN_TAB
-// per-group LDS of the plain-path kernels and their staging
-__host__ __device__ constexpr int lean_group_doubles(int Sb) {
-  return (5 + 2 * kLbfgsM) * Sb + (kLbfgsM + 1) + kTickState + lean_eval_doubles(Sb);
-}
-
 // positions -> dp of every segment; returns whether the path is one the evaluation takes (group-uniform)
 // end_masks: the two end vertices may leave slots free (rest-to-rest paths under an objective order below snap: jerk and /
 // or snap stay free there); their free masks are left at ev[4 Sb] and ev[4 Sb + 1] for evaluate_lean<true>
@@ -935,12 +906,7 @@ __device__ __forceinline__ double start_time(const NonlinearParams& prm, const d
 // the outer-loop kernel: optimiser ticks (one objective evaluation each).  On exit seg_times holds the
 // last evaluated point and opt_status the stopping reason (-2: start rejected, as NLopt would).
 
-// All bins of a plan run in ONE launch: blocks [block_begin, block_begin + n_blocks) of the grid belong to a
-// bin (paths sorted longest first, so the long paths are dispatched first and the short ones fill the tail).
-struct BinTable {
-  int n;
-  int group[5], q_begin[5], q_count[5], max_S[5], block_begin[5];
-};
+// (all bins of a plan run in ONE launch, by its BinTable: mrs_tg_nonlinear_route.hpp)
 
 // The variants of the outer loop, one per kernel: what optimize_body<V> compiles in.  A variant states what it changes.
 namespace variant {
@@ -1926,97 +1892,10 @@ __global__ __launch_bounds__(64) void cost_gradient_kernel(BatchView b, int d, i
 // ---------------------------------------------------------------------------------------------
 // host side
 
-// split the four dimensions over lanes while the batch is too small to fill the machine otherwise
-static int dim_split_for(int n_paths, int max_S) {
-  if (const int forced = knob::dim_split_max_paths(); forced != knob::kUnset) return n_paths <= forced ? 4 : 1;  // tuning knob
-  // One lane per dimension pays while a path's (S + 1) x 4 lanes fit ONE wavefront: from 16 segments on the split kernel
-  // walks a path in several passes and the lean kernel's lane groups are 2-3x faster at every batch size (whole pipeline,
-  // scripts/measure_configs.py uniform<P>x<S>, profiles/round5_dim_split_crossover.txt: 256 x 16 0.378 vs 0.168 ms,
-  // 2048 x 30 1.290 vs 0.429 ms, 1024 ragged 3..30 0.681 vs 0.240 ms).
-  if (max_S > 15) return 1;
-  // measured cross-over against the lean kernel of large batches (scripts/ps_step.py with MRS_TG_DIM_SPLIT_MAX_PATHS=0):
-  // outer-loop kernel 2048 paths 122 vs 143 us, 3072 paths 160 vs 150 us (10 segments); 13 segments: 1024 paths 0.152 vs
-  // 0.168 ms, 2048 paths 0.220 vs 0.192 ms (whole pipeline)
-  return n_paths <= (max_S > 12 ? 1536 : 2560) ? 4 : 1;
-}
-
-static int group_for(int S, int ds) {
-  int G = 4;
-  while (G < (S + 1) * ds && G < 64) G <<= 1;
-  return G;
-}
-
-// lanes per path when the long paths get the S + 4 lanes of the shared half sweeps: 13-15 and 29-30 segments move to the next
-// group width.  (5-7 segments stay in groups of 8 and their one-sided sweeps: six steps against four do not pay for half
-// the paths per wavefront -- 8192 x 6: 0.190 ms narrow, 0.197 ms wide; 65536 x 6: 0.861 vs 1.015 ms.)  These bins decide
-// WHETHER a launch is small enough for wide groups (wide_blocks) and are what MRS_TG_LEAN_WIDE_ALL=0 launches; by default
-// such a launch uses the bins of group_for_ends below (every path of two or more segments in S + 4 lanes: launch_nonlinear)
-static int group_for_wide(int S) {
-  int G = group_for(S, 1);
-  if (S >= 13 && G < S + 4 && G < 64) G <<= 1;
-  return G;
-}
-
-constexpr int kLeanTwoPassMaxS = 121;  // evaluate_lean_shared: 3 publishers + 61 other virtual lanes per pass, two passes
-// lanes per path when EVERY path of kEndsMinSegments or more segments gets its S + 4 lanes (0: no group is wide enough).
-// Two segments are enough for the shared half sweeps (one step per half); handing the 2- and 3-segment paths of a ragged
-// batch to the sweeping kernel BEHIND the launch instead cost 8192 ragged paths 0.67 instead of 0.58 ms (d = 2).
-// MRS_TG_ENDS_MIN_SEGMENTS: tuning / test knob, read when the library is loaded
+// The route of a call -- the plan's bins, every size rule and every launch's grid and LDS -- is mrs_tg_nonlinear_route.hpp's; what
+// follows allocates, maps the route's enums to kernels and enqueues.
+// MRS_TG_ENDS_MIN_SEGMENTS is read when the library is loaded (group_for_ends and the kernels' ends_min_segments get this value)
 static const int kEndsMinSegments = knob::ends_min_segments();
-static int group_for_ends(int S) {
-  if (S < kEndsMinSegments) return group_for(S, 1);
-  if (S + 4 > 64) return S <= kLeanTwoPassMaxS ? 64 : 0;  // a wavefront per path, two passes of the shared evaluation
-  int G = 8;
-  while (G < S + 4) G <<= 1;
-  return G;
-}
-
-template <class GroupFor>
-static void build_bins(std::vector<NonlinearBin>& bins, const std::vector<int32_t>& so, const std::vector<int32_t>& order,
-                       GroupFor group_of) {
-  bins.clear();
-  const int P = (int)order.size();
-  int q = 0;
-  while (q < P) {
-    const int p = order[q];
-    const int S = so[p + 1] - so[p];
-    NonlinearBin bin;
-    bin.group = group_of(S);
-    bin.q_begin = q;
-    bin.max_S = S;  // sorted longest first: the first path of a bin is its longest
-    int e = q;
-    while (e < P && group_of(so[order[e] + 1] - so[order[e]]) == bin.group) ++e;
-    bin.q_count = e - q;
-    bin.min_S = so[order[e - 1] + 1] - so[order[e - 1]];  // ... and the last one its shortest
-    bins.push_back(bin);
-    q = e;
-  }
-}
-
-int nonlinear_plan_build(NonlinearPlan& nl, const std::vector<int32_t>& so, const std::vector<int32_t>& order) {
-  const int P = (int)order.size();
-  nl.dim_split = dim_split_for(P, P > 0 ? so[order[0] + 1] - so[order[0]] : 0);  // (sorted longest first)
-  const int ds = nl.dim_split;
-  const int max_S = P > 0 ? so[order[0] + 1] - so[order[0]] : 0;
-  build_bins(nl.bins, so, order, [ds](int S) { return group_for(S, ds); });
-  // The lane-group layouts as well where a CALL may prefer them to the plan's dimension split (launch_nonlinear: 13-15
-  // segments under an objective order below snap or with constrained slots / moving starts, whose paths the split kernel
-  // hands to its general step): the plan is built before the options are known
-  nl.regroup_possible = ds == 4 && max_S >= 13 && max_S <= 15;
-  const bool groups = ds == 1 || nl.regroup_possible;
-  nl.bins1.clear();
-  if (nl.regroup_possible) build_bins(nl.bins1, so, order, [](int S) { return group_for(S, 1); });
-  nl.wide_bins.clear();
-  nl.wide_blocks = 0;
-  if (groups) {
-    build_bins(nl.wide_bins, so, order, [](int S) { return group_for_wide(S); });
-    for (const NonlinearBin& bin : nl.wide_bins) nl.wide_blocks += (int)cdiv(bin.q_count, 64 / bin.group);
-  }
-  nl.ends_bins.clear();
-  if (groups && P > 0 && group_for_ends(max_S) != 0)
-    build_bins(nl.ends_bins, so, order, [](int S) { return group_for_ends(S); });
-  return 0;
-}
 
 constexpr int kCarefulCap = 1024;  // paths per call that can be re-run with primal costs; further ones keep the fast result
 
@@ -2032,15 +1911,6 @@ hipError_t nonlinear_ensure_buffers(NonlinearPlan& nl, const BatchView& b) {
   return nl.d_careful.ensure_filled(4 + kCarefulCap, [](int32_t* p) { return hipMemset(p, 0, sizeof(int32_t) * 4); });
 }
 
-// Lean sweeps for plain paths (optimize_lean_kernel): two wavefronts per SIMD where the general sweeping kernel has one.
-// Objective orders below snap leave slots free at the end vertices of a rest-to-rest path: optimize_lean_masked_kernel takes
-// those (masked step at the two ends of the sweep), at one wavefront per SIMD -- 256 + 74 registers; forced to two it spills
-// 96 and loses to the general kernel (8192 x 10 random-walk paths at d = 2: 429 vs 365 us; at one wavefront 332 us).
-static bool lean_applies(int dim_split) {
-  if (const int forced = knob::lean_forced(); forced >= 0) return forced != 0;
-  return dim_split == 1;
-}
-
 // Buffers of the pipelines' route for paths with a position-free vertex, and the list / flags of this call's batch
 // (general_list_kernel).  `outer_loop`: also the factor store of optimize_general_kernel's lanes and the copy of the start
 // times; returns the number of paths one launch of that kernel takes in *cap.
@@ -2051,9 +1921,8 @@ hipError_t nonlinear_prepare_general(NonlinearPlan& nl, const BatchView& b, cons
   if ((e = nl.d_general.ensure(4 + 2 * P)) != hipSuccess) return e;
   if ((e = nl.d_general_solve_ws.ensure(general_workspace_doubles(b))) != hipSuccess) return e;
   if (outer_loop) {
-    // as many paths per launch as a 2 GB factor store holds (64 lanes x S vertices x kGenWs doubles each)
-    const size_t per_path = (size_t)64 * (size_t)b.max_segments * kGenWs;
-    const size_t n = std::min<size_t>(P, std::max<size_t>((size_t)16, ((size_t)1 << 28) / per_path));
+    const size_t per_path = (size_t)64 * (size_t)b.max_segments * kGenWs;  // 64 lanes x S vertices x kGenWs doubles each
+    const size_t n = factor_store_paths(per_path, P);
     if ((e = nl.d_general_ws.ensure(per_path * n)) != hipSuccess) return e;
     if ((e = nl.d_general_t0.ensure((size_t)b.n_segments)) != hipSuccess) return e;
     if (!dry_run() && (e = hipMemcpyAsync(nl.d_general_t0.get(), seg_times, sizeof(double) * (size_t)b.n_segments,
@@ -2066,202 +1935,20 @@ hipError_t nonlinear_prepare_general(NonlinearPlan& nl, const BatchView& b, cons
   return hipGetLastError();
 }
 
-// ---- the route of a call: WHICH kernels launch_nonlinear enqueues, with which bins, grid and LDS -- decided here, from the plan,
-// the batch, the call's options and hints, the knobs (mrs_tg_knobs.hpp) and the device's compute units; nothing is allocated or
-// launched, and no HIP call is made
-using LeanKernel = Kernel<BatchView, NonlinearParams, BinTable, const uint8_t*, const double*, double*, int32_t*, int32_t*>;
-using SweepKernel = Kernel<BatchView, NonlinearParams, BinTable, const uint8_t*, const double*, double*, int32_t*>;
-
-struct OuterLaunch {
-  BinTable bins{};
-  int blocks = 0;
-  unsigned threads = 64;
-  size_t lds_bytes = 0;
-};
-
-// what follows the outer loop: a reading of the closing solves' routes (NonlinearRoute::first_solve, final_solve)
-enum class Closing {
-  kRowsPipeline,  // solve -> maxima -> scaling -> solve (-> sampling) in one launch of the rows kernel
-  kQuadTail,      // solve, maxima, then the scaling on the quad kernel's final solve (the caller's sampler follows)
-  kRowsTail,      // solve, maxima, then scaling (and sampling) on the rows kernel's final solve
-  kSeparate,      // solve, maxima, scaling, runaway test and final solve as launches of their own
-};
-
-struct NonlinearRoute {
-  bool estimate_in_kernel = false;  // the outer-loop kernels compute the start point themselves (else: a launch in front of them)
-  int dim_split = 1;                // of THIS call: 1 where it goes back from the plan's dimension split to lane groups
-  // 1a. the lean kernel takes every plain path and flags the others for the sweeping kernel behind it
-  bool lean = false;
-  LeanKernel lean_kernel{};
-  OuterLaunch lean_launch;
-  bool queued = false;              // the launch holds what is resident; lane groups claim further paths from the plan's queue
-  // 1b. the sweeping kernel: alone, or behind the lean kernel for the paths that one flagged
-  bool wave = false;                // one wavefront per path (mrs_tg_wave.hip) instead of the kernel below
-  bool sweep_fits = true;           // false: more than five bins or more LDS than a workgroup can have -- the call fails there
-  SweepKernel sweep_kernel{};
-  OuterLaunch sweep_launch;
-  bool careful = false;             // 1c. the careful re-run follows
-  bool general = false;             // 1d. the outer loop of the paths with a position-free vertex follows (and their solves below)
-  bool certified_maxima = true;     // segment_maxima_scaling_kernel, else every entry searched (segment_maxima9_kernel)
-  // the closing solves, routed as every fixed-times solve is (route_solve): the trajectory of the last evaluated point (not
-  // launched where the final solve takes the maxima into its own launch), and the solve at the scaled times
-  SolveRoute first_solve, final_solve;
-  Closing closing() const {
-    return final_solve.maxima_in_launch           ? Closing::kRowsPipeline
-           : !final_solve.scales                  ? Closing::kSeparate
-           : uses_factor_store(final_solve)       ? Closing::kQuadTail
-                                                  : Closing::kRowsTail;
-  }
-  bool tail_samples() const { return final_solve.sampling; }  // the sampling rides on the closing launch
-};
-
-// the kernel's table of `bins`; returns the largest lds_of(bin) and leaves the workgroup count in *blocks
-template <class LdsOf>
-static size_t fill_bin_table(BinTable& bt, const std::vector<NonlinearBin>& bins, LdsOf lds_of, int* blocks) {
-  bt.n = (int)bins.size();
-  size_t lds = 0;
-  *blocks = 0;
-  for (int i = 0; i < bt.n; ++i) {
-    const NonlinearBin& bin = bins[i];
-    bt.group[i] = bin.group;
-    bt.q_begin[i] = bin.q_begin;
-    bt.q_count[i] = bin.q_count;
-    bt.max_S[i] = bin.max_S;
-    bt.block_begin[i] = *blocks;
-    *blocks += (int)cdiv(bin.q_count, 64 / bin.group);
-    lds = std::max(lds, lds_of(bin));
-  }
-  return lds;
+// the route's enums as kernels, each mapped once; the names are what the kernel trace notes
+using LeanKernelFn = Kernel<BatchView, NonlinearParams, BinTable, const uint8_t*, const double*, double*, int32_t*, int32_t*>;
+using SweepKernelFn = Kernel<BatchView, NonlinearParams, BinTable, const uint8_t*, const double*, double*, int32_t*>;
+static LeanKernelFn lean_kernel_of(LeanKernel k) {
+  return k == LeanKernel::kLeanSharedEndsLong ? MRS_TG_KERNEL(optimize_lean_shared_ends_long_kernel)
+         : k == LeanKernel::kLeanSharedEnds   ? MRS_TG_KERNEL(optimize_lean_shared_ends_kernel)
+         : k == LeanKernel::kLeanMasked       ? MRS_TG_KERNEL(optimize_lean_masked_kernel)
+         : k == LeanKernel::kLeanShared       ? MRS_TG_KERNEL(optimize_lean_shared_kernel)
+                                              : MRS_TG_KERNEL(optimize_lean_kernel);
 }
-
-// hints: the call's (RouteHints, launch_nonlinear's argument); compute_units: of the current device (device_compute_units);
-// closing: the request of the closing solves as solve_request fills it (objective order, hints, factor store, waypoints and the
-// compute units the solve routes by); estimate: the search starts from the estimate; samples_wanted: the caller asked for samples
-static NonlinearRoute route_nonlinear(const NonlinearPlan& nl, const BatchView& b, const RouteHints& hints, int compute_units,
-                                      const SolveRequest& closing, bool estimate, bool general, bool careful, bool samples_wanted) {
-  const int derivative = closing.derivative;
-  const bool constrained_slots = hints.constrained_slots, moving_starts = hints.moving_starts;
-  NonlinearRoute r;
-  r.general = general;
-  r.careful = careful;
-  // the start point is the estimate: computed by the outer-loop kernels themselves (start_time), by a launch of its own in
-  // front of the kernels that read their start from a copy
-  // (every outer-loop kernel but the one for position-free paths and the careful re-run, which start from a copy of the times)
-  r.estimate_in_kernel = estimate && !general && !careful;
-  // The split of the four dimensions over lanes is the PLAN's choice (batch size and longest path); this CALL goes back to
-  // lane groups where the split kernel would hand its paths to the general step anyway and the groups are 10-25 % faster:
-  // 13-15 segments (<= 1536 paths) under an objective order below snap, or when the caller says that vertices hold
-  // constrained slots (stop_at waypoints: MRS_TG_FLAG_CONSTRAINED_SLOTS) or mrs_tg_solve_batch has seen a moving start in
-  // its host copy of the values.  MRS_TG_REGROUP=0 switches it off.
-  const bool regroup = knob::regroup() && nl.regroup_possible && (derivative < 4 || constrained_slots || moving_starts);
-  r.dim_split = regroup ? 1 : nl.dim_split;
-  const std::vector<NonlinearBin>& plan_bins = regroup ? nl.bins1 : nl.bins;
-  r.lean = lean_applies(r.dim_split) && (int)plan_bins.size() <= 5;
-  auto plain_lds = [](const NonlinearBin& bin) {
-    return ((size_t)(64 / bin.group) * lean_group_doubles(bin.max_S) + 2 * kPsTable) * sizeof(double);
-  };
-  auto all_fit = [&](const std::vector<NonlinearBin>& bins) {
-    for (const NonlinearBin& bin : bins)
-      if (plain_lds(bin) > 160 * 1024) return false;
-    return true;
-  };
-  // Which lane groups.  The shared half sweeps halve the steps of an evaluation but need S + 4 lanes, the next group width
-  // for 13-15 and 29-30 segments: half the paths per wavefront for (S/2 + 1)/S of the steps -- more instructions per path,
-  // so a launch of many residency rounds (a saturated device: the kernel is bound by its instruction count) keeps the
-  // narrow groups and their one-sided sweeps.  A launch of a few residency rounds lasts about as long as its slowest
-  // wavefronts -- ten evaluations of the longest paths -- and there the wide groups win: whole pipeline, wide vs narrow,
-  // 8192 ragged 0.57 vs 0.65 ms, 8192 x 14 0.395 vs 0.425, 16384 x 14 0.644 vs 0.674, 32768 x 30 3.33 vs 3.51,
-  // 32768 ragged 1.87 vs 1.89; past that narrow: 65536 x 14 2.03 vs 1.97 ms (profiles/round5_wide_groups_ab.txt).
-  // (MRS_TG_LEAN_WIDE=0 / 1 forces.)
-  // (per device: a process may drive devices of different sizes or partitions, and the first call's figure is not theirs)
-  const int resident_waves = compute_units * 4 * MRS_TG_LEAN_WAVES;
-  const int lean_shared = knob::lean_shared();
-  const int wide_forced = knob::lean_wide_forced();
-  const bool lean_masked = derivative < 4;  // rest-to-rest paths end on vertices with free slots
-  const bool wide = !nl.wide_bins.empty() && (int)nl.wide_bins.size() <= 5 && !lean_masked && lean_shared != 0 &&
-                    (wide_forced >= 0 ? wide_forced == 1 : nl.wide_blocks <= 8 * resident_waves) && all_fit(nl.wide_bins);
-  // objective orders below snap: the shared half sweeps with free end slots, every path in a group of S + 4 lanes at least
-  // (MRS_TG_LEAN_SHARED=0: the one-sided masked sweeps of optimize_lean_masked_kernel, as until round 5)
-  // (a min-snap launch whose caller says that interior vertices may hold constrained slots -- stop_at waypoints -- as well:
-  // MRS_TG_FLAG_CONSTRAINED_SLOTS)
-  const bool ends_shared = (lean_masked || constrained_slots) && lean_shared != 0 && !nl.ends_bins.empty() &&
-                           (int)nl.ends_bins.size() <= 5 && all_fit(nl.ends_bins);
-  // min-snap launches of a few residency rounds: EVERY path of two or more segments in a group of S + 4 lanes (the bins of the
-  // free-end kernel), so that the kernel with only the shared half sweeps runs -- the one that takes moving starts; 5-7
-  // segments then pay 3-4 % for their wider groups when they start at rest (MRS_TG_LEAN_WIDE_ALL=0: only 13-15 and 29-30
-  // segments move up and a ragged batch runs the mixed kernel, whose one-sided sweeps leave moving starts to the sweeping kernel)
-  const bool wide_shared_all = wide && knob::lean_wide_all() && !nl.ends_bins.empty() && (int)nl.ends_bins.size() <= 5;
-  const std::vector<NonlinearBin>& lean_bins = (ends_shared || wide_shared_all) ? nl.ends_bins : wide ? nl.wide_bins : plan_bins;
-  r.lean = r.lean && all_fit(lean_bins);
-  if (r.lean) {
-    OuterLaunch& L = r.lean_launch;
-    L.lds_bytes = fill_bin_table(L.bins, lean_bins, plain_lds, &L.blocks);
-    // A uniform batch of more wavefronts than the device holds at once (two per SIMD): launch what is resident and let a
-    // lane group whose path has stopped claim the next one (optimize_body, `queued`), instead of eight rounds of wavefronts
-    // that each last as long as the slowest of their four paths.  65536 x 10: 780 -> us.
-    // (what the FIRST device to run a lean launch holds, for the whole process -- a process that drives devices of different
-    // sizes queues as it always has; changing that is for another day.  MRS_TG_LEAN_RESIDENT_BLOCKS: tuning knob; 0 = no queue)
-    static const int resident_blocks =
-        knob::lean_resident_blocks() != knob::kUnset ? knob::lean_resident_blocks() : compute_units * 4 * MRS_TG_LEAN_WAVES;
-    if (L.bins.n == 1 && resident_blocks > 0 && L.blocks > resident_blocks) {
-      L.blocks = resident_blocks;
-      r.queued = true;
-    }
-    // shared half sweeps (evaluate_lean_shared) where every path of every bin has its S + 4 lanes
-    // (with a bin of paths shorter than four segments beside them the kernel that has both evaluations compiled in runs, the
-    // short paths in wavefronts of their own next to the others: handing them to the compact kernel BEHIND the launch cost
-    // 66 us on 8192 ragged paths, profiles/round5_wide_groups_ab.txt)
-    bool lean_shared_only = lean_shared != 0 && !lean_masked;
-    bool long_paths = false;  // a bin whose paths have more half sweeps than a wavefront has lanes: the two-pass instantiations
-    for (const NonlinearBin& bin : lean_bins) {  // (a bin of one-segment paths: the kernel leaves them to the sweeping kernel behind it)
-      if (bin.max_S >= 2 && (bin.min_S < 2 || (bin.max_S + 4 > bin.group && !(bin.group == 64 && bin.max_S <= kLeanTwoPassMaxS))))
-        lean_shared_only = false;
-      if (bin.max_S + 4 > bin.group && bin.group == 64) long_paths = true;
-    }
-    const bool ends_long = long_paths && (ends_shared || lean_shared_only);
-    r.lean_kernel = ends_long          ? MRS_TG_KERNEL(optimize_lean_shared_ends_long_kernel)
-                    : ends_shared      ? MRS_TG_KERNEL(optimize_lean_shared_ends_kernel)
-                    : lean_masked      ? MRS_TG_KERNEL(optimize_lean_masked_kernel)
-                    : lean_shared_only ? MRS_TG_KERNEL(optimize_lean_shared_kernel)
-                                       : MRS_TG_KERNEL(optimize_lean_kernel);
-  }
-  // one wavefront per path, both directions of the two-sided evaluation in it (mrs_tg_wave.hip)
-  r.wave = !r.lean && wave_kernel_applies(b, r.dim_split);
-  if (!r.wave) {
-    OuterLaunch& L = r.sweep_launch;
-    r.sweep_fits = (int)plan_bins.size() <= 5;
-    if (r.sweep_fits) {
-      const bool split = r.dim_split == 4;
-      L.lds_bytes = fill_bin_table(L.bins, plan_bins, [split](const NonlinearBin& bin) {
-        return ((size_t)(64 / bin.group) * group_lds_doubles(bin.max_S, split) + kBlockConsts) * sizeof(double);
-      }, &L.blocks);
-      bool all_single = true;
-      for (const NonlinearBin& bin : plan_bins)
-        if (bin.group != 64) all_single = false;
-      // one path per block and one dimension per lane: a partner wavefront runs the other half of every sweep
-      L.threads = (split && all_single) ? 128u : 64u;
-      if (L.threads == 128u) L.lds_bytes += (64 * kPairState + 2) * sizeof(double);  // hand-over area + flags
-      r.sweep_fits = L.lds_bytes <= 160 * 1024;
-      // objective order below snap: the end vertices of rest-to-rest paths keep free slots, so the large-batch kernel is
-      // launched with the masked step compiled in (the min-snap instantiation stays free of it)
-      r.sweep_kernel = split            ? MRS_TG_KERNEL(optimize_split_kernel)
-                       : derivative < 4 ? MRS_TG_KERNEL(optimize_compact_kernel<true>)
-                                        : MRS_TG_KERNEL(optimize_compact_kernel<false>);
-    }
-  }
-  r.certified_maxima = knob::maxima_bounds();  // MRS_TG_MAXIMA_BOUNDS=0: every entry searched
-  // 2-4 in one launch for the small batches whose wavefronts hold one path (solve_rows_pipeline_kernel, mrs_tg_rows.hip); else
-  // 3b + 4 in one launch where the quad kernel (saturated device; the caller's sampler follows) or the rows kernel applies:
-  // its staging pass scales the times of its own path, the rows kernel's tail samples.  Paths with a position-free vertex:
-  // every stage a launch of its own, the final solve without the waypoints
-  r.first_solve = route_solve(b, closing);
-  SolveRequest final_request = closing;
-  final_request.stage = SolveStage::kClosing;
-  final_request.maxima_in_launch = final_request.scale_from_maxima = !general;
-  final_request.sampling = samples_wanted && !general;
-  final_request.waypoints = closing.waypoints && !general;
-  r.final_solve = route_solve(b, final_request);
-  return r;
+static SweepKernelFn sweep_kernel_of(SweepKernel k) {  // (kWave has a launcher of its own, launch_optimize_wave)
+  return k == SweepKernel::kSplit            ? MRS_TG_KERNEL(optimize_split_kernel)
+         : k == SweepKernel::kCompactMasked ? MRS_TG_KERNEL(optimize_compact_kernel<true>)
+                                            : MRS_TG_KERNEL(optimize_compact_kernel<false>);
 }
 
 hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const RouteHints& hints, const NonlinearParams& prm_in,
@@ -2280,8 +1967,13 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const RouteHi
   op.ws = nl.d_ws.get();
   op.coeffs = coeffs;
   op.pos_wp = prm_in.pos_wp;
+  // workgroups of a queued lean launch: what the FIRST device to get here holds, for the whole process -- a process that drives
+  // devices of different sizes queues as it always has; changing that is for another day.  MRS_TG_LEAN_RESIDENT_BLOCKS: tuning
+  // knob; 0 = no queue
+  static const int resident_blocks = knob::lean_resident_blocks() != knob::kUnset ? knob::lean_resident_blocks()
+                                                                                 : device_compute_units() * 4 * MRS_TG_LEAN_WAVES;
   const NonlinearRoute route =
-      route_nonlinear(nl, b, hints, device_compute_units(), solve_request(prm_in.derivative, true, hints, op),
+      route_nonlinear(nl.host, b, hints, device_compute_units(), resident_blocks, solve_request(prm_in.derivative, true, hints, op),
                       prm_in.estimate_wp != nullptr, general, careful, sampling_dt > 0.0 && n_samples != nullptr);
   if (prm_in.estimate_wp && !route.estimate_in_kernel &&
       (e = launch_estimate_times(b, prm_in.estimate_wp, prm_in.estimate_limits, seg_times, stream)) != hipSuccess)
@@ -2305,10 +1997,8 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const RouteHi
   }
   int careful_cap = 0;
   if (careful) {
-    // as many paths per call as a 2 GB factor store holds (64 lanes x S vertices x 30 doubles each), at most kCarefulCap
-    const size_t per_path = (size_t)64 * (size_t)b.max_segments * ws_per_vertex<1>();
-    careful_cap = (int)std::min<size_t>((size_t)kCarefulCap, std::max<size_t>((size_t)16, ((size_t)1 << 28) / per_path));
-    careful_cap = std::min(careful_cap, b.n_paths);
+    const size_t per_path = (size_t)64 * (size_t)b.max_segments * ws_per_vertex<1>();  // 64 lanes x S vertices x 30 doubles each
+    careful_cap = (int)factor_store_paths(per_path, (size_t)std::min(kCarefulCap, b.n_paths));
     if ((e = nl.d_careful_ws.ensure(per_path * (size_t)careful_cap)) != hipSuccess) return e;
     prm.careful_count = nl.d_careful.get();
     prm.careful_list = nl.d_careful.get() + 4;
@@ -2333,8 +2023,9 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const RouteHi
       if ((e = hipGetLastError()) != hipSuccess) return e;
       prm.queue_next = nl.d_queue.get();
     }
-    if (L.lds_bytes > 64 * 1024 && (e = set_max_dynamic_lds(route.lean_kernel, L.lds_bytes)) != hipSuccess) return e;
-    MRS_TG_LAUNCH_EXT(route.lean_kernel, dim3(L.blocks), dim3(64), L.lds_bytes, stream, kt.start, nullptr, 0, b, prm, L.bins, mask,
+    const LeanKernelFn lean_kernel = lean_kernel_of(route.lean_kernel);
+    if (L.lds_bytes > kLdsDefaultLimit && (e = set_max_dynamic_lds(lean_kernel, L.lds_bytes)) != hipSuccess) return e;
+    MRS_TG_LAUNCH_EXT(lean_kernel, dim3(L.blocks), dim3(64), L.lds_bytes, stream, kt.start, nullptr, 0, b, prm, L.bins, mask,
                       vals, seg_times, nl.d_opt_status.get(), nl.d_fallback.get());
     if ((e = hipGetLastError()) != hipSuccess) return e;
     prm.only_flagged = nl.d_fallback.get();
@@ -2343,20 +2034,21 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const RouteHi
   // 1b. the sweeping kernel
   {
     const hipEvent_t ev_start = route.lean ? nullptr : kt.start, ev_stop = (careful || general) ? nullptr : kt.stop;
-    if (route.wave) {
+    if (route.wave()) {
       e = launch_optimize_wave(b, prm, mask, vals, seg_times, nl.d_opt_status.get(), stream, ev_start, ev_stop);
       if (e != hipSuccess) return e;
     } else {
       const OuterLaunch& L = route.sweep_launch;
       if (!route.sweep_fits) return hipErrorInvalidValue;
-      if (L.lds_bytes > 64 * 1024 && (e = set_max_dynamic_lds(route.sweep_kernel, L.lds_bytes)) != hipSuccess) return e;
-      MRS_TG_LAUNCH_EXT(route.sweep_kernel, dim3(L.blocks), dim3(L.threads), L.lds_bytes, stream, ev_start, ev_stop, 0, b, prm, L.bins,
+      const SweepKernelFn sweep_kernel = sweep_kernel_of(route.sweep_kernel);
+      if (L.lds_bytes > kLdsDefaultLimit && (e = set_max_dynamic_lds(sweep_kernel, L.lds_bytes)) != hipSuccess) return e;
+      MRS_TG_LAUNCH_EXT(sweep_kernel, dim3(L.blocks), dim3(L.threads), L.lds_bytes, stream, ev_start, ev_stop, 0, b, prm, L.bins,
                         mask, vals, seg_times, nl.d_opt_status.get());
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
 #if MRS_TG_WITH_CAREFUL
     if (careful) {
-      const size_t clds = ((size_t)group_lds_doubles(b.max_segments, true) + kBlockConsts) * sizeof(double);
+      const size_t clds = listed_lds_bytes(b.max_segments);
       if ((e = prepare_dynamic_lds(MRS_TG_KERNEL(optimize_careful_kernel), clds)) != hipSuccess) return e;
       MRS_TG_LAUNCH_EXT(optimize_careful_kernel, dim3(careful_cap), dim3(64), clds, stream, nullptr, general ? nullptr : kt.stop,
                         0, b, prm, mask, vals, seg_times, nl.d_opt_status.get(), nl.d_careful_ws.get());
@@ -2370,7 +2062,7 @@ hipError_t launch_nonlinear(NonlinearPlan& nl, const BatchView& b, const RouteHi
     // the paths none of the kernels above knows (what they wrote for them is overwritten here): the same search with the
     // 5 x 5-block evaluation, from the start times kept aside, `general_cap` listed paths per launch
     if (general) {
-      const size_t glds = ((size_t)group_lds_doubles(b.max_segments, true) + kBlockConsts) * sizeof(double);
+      const size_t glds = listed_lds_bytes(b.max_segments);
       if ((e = prepare_dynamic_lds(MRS_TG_KERNEL(optimize_general_kernel), glds)) != hipSuccess) return e;
       NonlinearParams gp = prm;
       gp.only_flagged = nullptr;
@@ -2454,12 +2146,12 @@ hipError_t launch_cost_gradient(NonlinearPlan& nl, const BatchView& b, int d, co
                                 const double* seg_times, double* cost, double* grad, hipStream_t stream) {
   hipError_t e;
   const int32_t* only = nullptr;
-  for (const NonlinearBin& bin : nl.bins) {
-    const int per_block = 64 / bin.group;
-    const size_t lds_bytes = ((size_t)per_block * gradient_lds_doubles(bin.max_S, nl.dim_split == 4) + kBlockConsts) * sizeof(double);
-    if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-    const dim3 grid(cdiv(bin.q_count, per_block));
-    const auto gradient = nl.dim_split == 4 ? MRS_TG_KERNEL(cost_gradient_kernel<4>) : MRS_TG_KERNEL(cost_gradient_kernel<1>);
+  const bool split = nl.host.dim_split == 4;
+  for (const NonlinearBin& bin : nl.host.bins) {
+    const size_t lds_bytes = gradient_lds_bytes(bin, split);
+    if (lds_bytes > kLdsPerWorkgroup) return hipErrorInvalidValue;
+    const dim3 grid(bin_blocks(bin));
+    const auto gradient = split ? MRS_TG_KERNEL(cost_gradient_kernel<4>) : MRS_TG_KERNEL(cost_gradient_kernel<1>);
     MRS_TG_LAUNCH(gradient, grid, dim3(64), lds_bytes, stream, b, d, bin.group, bin.q_begin, bin.q_count, bin.max_S, mask, vals,
                   seg_times, cost, grad, only);
     if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -10,10 +10,12 @@
 
 #include "mrs_tg_device.hpp"
 #include "mrs_tg_nl_common.hpp"
+#include "mrs_tg_nonlinear_route.hpp"
 
 namespace mrs_tg {
 
-constexpr int kLbfgsM = 5;
+// (the LDS footprints -- kLbfgsM, kVtxLds, kSegLds, kStartExtra, kBlockConsts, kPsTable: mrs_tg_nonlinear_route.hpp, which sizes the
+// launches by them)
 constexpr double kGradStep = 0.1;  // increment_time, nonlinear_impl.h:281
 
 // ---------------------------------------------------------------------------------------------
@@ -32,7 +34,6 @@ __device__ __forceinline__ double perturbed_time(const double* xs, int i, int k,
 // of them on every lane: they are staged once per kernel in LDS (kVtxLds doubles per vertex: the 5 x 4 constrained
 // values, 0 where free, then the free mask).  Read from global memory inside the sweep, each segment step exposed
 // one L2 round trip on the only wavefront of its SIMD.
-constexpr int kVtxLds = 22;
 
 __device__ __forceinline__ void stage_vertices(const uint8_t* __restrict__ mask, const double* __restrict__ vals, int v0,
                                                int S, double* vtx, int g, int G) {
@@ -96,7 +97,6 @@ __device__ __forceinline__ double guarded_cost(double J, double qf, bool base) {
 // ~230 instructions per interior step for one dimension per lane, ~360 for four.  A first segment that starts from a
 // moving state has its own variant of the start step (kSegStartState below); any other mask / value pattern
 // (partially constrained stop vertices, a moving start straight into a stop) takes the general step.
-constexpr int kSegLds = 38;
 enum { kSegGeneral = 0, kSegStart = 1, kSegInterior = 2, kSegEnd = 3, kSegStartState = 4, kSegMasked = 5, kSegMaskedStartState = 6 };
 // kSegMasked: every constrained derivative value is zero (so the position brackets are the whole right-hand side) but
 // the free masks of the two vertices are not one of the three patterns above: the end vertices of a rest-to-rest path
@@ -114,8 +114,7 @@ enum { kSegGeneral = 0, kSegStart = 1, kSegInterior = 2, kSegEnd = 3, kSegStartS
 // unknown): the masked step, plus the terms above for vertex 1 and f^T H f, plus the start vertex's own right-hand side
 // -- row r gets sum_c HBAR[1+r][c] f_c T^(r+1+c+1-2d) -- whose coefficients are 16 more doubles per dimension.  Only
 // optimize_wave_kernel has a step for it; every other evaluation takes the general step.
-constexpr int kStartExtraDim = 16 + 8 + 16;
-constexpr int kStartExtra = kD * kStartExtraDim;
+// (kStartExtra = kD * kStartExtraDim, kStartExtraDim = 16 + 8 + 16)
 
 __device__ __forceinline__ void stage_segments(const double* vtx, int S, int d, double* seg, int g, int G, bool extras) {
   const double (*hb)[kN] = c_hbar[d];
@@ -210,8 +209,7 @@ __device__ __forceinline__ void segment_powers(double T, int d, double (&p2)[9])
 
 // The 36 HBAR_d constants of the three 4 x 4 blocks (start-start packed | start-end | end-end packed) are staged in
 // LDS as well: addressed through the constant bank with a run-time d they were scalar loads inside the sweep, whose
-// latency stalled every step and whose SGPR footprint forced spills.
-constexpr int kBlockConsts = 36;
+// latency stalled every step and whose SGPR footprint forced spills (kBlockConsts).
 
 __device__ __forceinline__ void stage_block_constants(int d, double* hc, int tid, int nthreads) {
   const double (*hb)[kN] = c_hbar[d];
@@ -451,7 +449,7 @@ struct FastStep {
 // (These tables and stage_ps below were built for the prefix / suffix evaluation of the Mellinger gradient -- an experiment
 // that was verified, measured slower than the sweeping kernels and removed from the source in round 3; DESIGN.md section 13
 // keeps its description and numbers.  The lean sweeps use the tables and the staging pass.)
-constexpr int kPsTable = 45;  // near block [10] | coupling [16] | far block [10] | near bracket consts [4] | far [4] | qf const
+// kPsTable doubles each: near block [10] | coupling [16] | far block [10] | near bracket consts [4] | far [4] | qf const
 
 // [0]: the table of a left-to-right lane, [1]: of a right-to-left lane (near / far swapped, coupling transposed), so that
 // FastStep's REV = false forms compute either direction

@@ -595,10 +595,6 @@ __global__ __launch_bounds__(64, MRS_TG_WAVE_WAVES) void optimize_wave_kernel(Ba
   if (lane == 0) opt_status[pr.p] = bad ? -2 : ret;
 }
 
-bool wave_kernel_applies(const BatchView& b, int dim_split) {
-  return knob::wave_kernel() && dim_split == 4 && b.n_paths > 0 && b.max_segments <= kWaveMaxS;
-}
-
 hipError_t launch_optimize_wave(const BatchView& b, const NonlinearParams& prm, const uint8_t* mask, const double* vals,
                                 double* seg_times, int32_t* opt_status, hipStream_t stream, hipEvent_t ev_start,
                                 hipEvent_t ev_stop) {

@@ -87,7 +87,7 @@ int main(int argc, char** argv) {
   // outer loop (mode 2): one optimiser tick = one objective evaluation (S + 1 forward sweeps) + bookkeeping
   {
     NonlinearPlan nl;
-    nonlinear_plan_build(nl, so, order);
+    nl.host = nonlinear_host_plan(so, order);
     NonlinearParams prm{d, 10, 0.05, -1.0, 0.1, -1.0};
     std::vector<double> lim((size_t)P * 9);
     const double l9[9] = {2, 2, 1, 2, 2, 2, 20, 20, 20};

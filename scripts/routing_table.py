@@ -32,7 +32,7 @@ SHAPES = [("1 x 3 (configs[0])", lambda: uniform(1, 3)), ("1 x 10 (one request)"
           ("8192 x 10 (a shard of configs[3])", lambda: uniform(8192, 10)), ("8192 ragged 3..30 (configs[4])", lambda: ragged(8192)),
           ("65536 x 10 (configs[3])", lambda: uniform(65536, 10)), ("300 x 80", lambda: uniform(300, 80)),
           ("4 x 200", lambda: uniform(4, 200))]
-# one batch on each side of every size the routers compare against (mrs_tg_nonlinear.hip: route_nonlinear, dim_split_for;
+# one batch on each side of every size the routers compare against (mrs_tg_nonlinear_route.hpp: route_nonlinear, dim_split_for;
 # mrs_tg_solve_route.hpp: quad_kernel_applies, rows_pipeline_applies, the rows kernel's paths per wavefront in route_solve)
 BOUNDS = [(2560, 10), (2561, 10), (1536, 14), (1537, 14),   # dimension split
           (6143, 10), (6144, 10),                            # MRS_TG_QUAD_MIN_PATHS
