@@ -226,9 +226,12 @@ enum {
   MRS_TG_CAP_MUTUAL_CLEARANCE = 65536,  /* mrs_tg_plan_mutual_clearance and mrs_tg_plan_mutual_clearance_vjp are exported: how close
                                          the paths of one group (a swarm) come to each other at common steps, the nearest
                                          neighbour's index, and the backward pass */
-  MRS_TG_CAP_OBSTACLE_CLEARANCE = 131072 /* mrs_tg_plan_obstacle_clearance and mrs_tg_plan_obstacle_clearance_vjp are exported: the
+  MRS_TG_CAP_OBSTACLE_CLEARANCE = 131072, /* mrs_tg_plan_obstacle_clearance and mrs_tg_plan_obstacle_clearance_vjp are exported: the
                                          signed distance of every row to the nearest sphere or point of the path's obstacle set,
                                          that obstacle's index, and the backward pass */
+  MRS_TG_CAP_FIELD_CLEARANCE = 262144   /* mrs_tg_plan_field_clearance and mrs_tg_plan_field_clearance_vjp are exported: the
+                                         trilinear interpolant of a voxel grid of signed distances at every row, its cell, the
+                                         field's gradient, and the backward pass */
 };
 
 /* mrs_tg_plan_request_limits' flags_dev: what the request asks of its limits */
@@ -1195,7 +1198,8 @@ int mrs_tg_plan_mutual_clearance_vjp(mrs_tg_plan* plan, const double* samples_de
  * changes.  No atomics, no workspace; every output element that belongs to the plan is written exactly once; the same bits on
  * every call and for a path wherever it sits in the batch and wherever its set sits in the array.  Set bounds are clamped into
  * [0, n_obstacles] with end >= begin, so no read leaves the obstacle array whatever set_offsets_dev and path_set_dev hold.  Out
- * of scope: a gradient with respect to the obstacles (a static map); a spatial index over them; a small batch against a large
+ * of scope: a gradient with respect to the obstacles (a static map); a spatial index over them is
+ * mrs_tg_plan_field_clearance's voxel grid, built once from this step; a small batch against a large
  * map uses one workgroup per path and so a part of the device.
  * MRS_TG_ERR_INVALID_ARG, before any launch: plan, n_samples_dev or set_offsets_dev NULL, samples_dev NULL with a positive
  * capacity, obstacles_dev NULL with n_obstacles > 0, a negative n_obstacles, n_sets or sample_capacity, a z_scale that is not
@@ -1224,6 +1228,79 @@ int mrs_tg_plan_obstacle_clearance_vjp(mrs_tg_plan* plan, const double* samples_
                                        const int32_t* status_dev, double z_scale, const int32_t* nearest_dev,
                                        const double* grad_clearance_dev, double* grad_samples_out_dev);
 
+/* Clearance from a voxel distance field as a plan step (MRS_TG_CAP_FIELD_CLEARANCE; field_clearance_kernel,
+ * csrc/mrs_tg_field.hpp): how close every row a sampler left comes to a static map given as a grid of
+ * signed distances (an ESDF), looked up by trilinear interpolation -- eight voxel reads per row whatever the size of the map,
+ * where mrs_tg_plan_obstacle_clearance walks its list of obstacles per row.  The plan contributes its path count and its
+ * context; segments play no part and every array is in the caller's path order.  fields_dev is [n_fields][nz][ny][nx] doubles,
+ * x fastest: n_fields grids of ONE geometry (host struct) stacked in one array.  The value with indices (i, j, k) sits at
+ * origin + (i hx, j hy, k hz): the grid is node-centred, and a caller with cell-centred voxels passes the centre of voxel 0 as
+ * the origin; a 2-D map is passed as two equal layers.  path_field_dev [n_paths] (int32) names the grid each path sees; NULL =
+ * every path sees grid 0; an entry outside [0, n_fields) = the path sees none.  samples_dev [n_paths][sample_capacity][4] and
+ * n_samples_dev [n_paths] are what a solve or a sampler left; a path has n = min(n_samples, sample_capacity) live rows (a count
+ * of sample_capacity + 1 is sample_capacity rows), none with status_dev (may be NULL) <= 0.  For a live row (x, y, z, .) of a path
+ * that sees grid f, in this order and with no fused multiply-add:
+ *   ux = (x - ox) / hx, uy, uz alike                         a true division
+ *   inside  <=>  0 <= u && u <= n - 1 on every axis          tested in double: a NaN fails, a huge u is never made an integer
+ *   i = (int)ux, lowered to nx - 2 when above it;  tx = ux - (double)i     (the upper face belongs to the last cell, tx = 1)
+ *   lerp(a, b, t) = a + t (b - a);  fIJK the voxel at (i + I, j + J, k + K)
+ *   c00 = lerp(f000, f100, tx), c10 = lerp(f010, f110, tx), c01 = lerp(f001, f101, tx), c11 = lerp(f011, f111, tx)
+ *   c0 = lerp(c00, c10, ty), c1 = lerp(c01, c11, ty), clearance = lerp(c0, c1, tz)
+ *   gx = lerp(lerp(f100 - f000, f110 - f010, ty), lerp(f101 - f001, f111 - f011, ty), tz) / hx
+ *   gy = lerp(lerp(f010 - f000, f110 - f100, tx), lerp(f011 - f001, f111 - f101, tx), tz) / hy
+ *   gz = lerp(lerp(f001 - f000, f101 - f100, tx), lerp(f011 - f010, f111 - f110, tx), ty) / hz
+ *   cell = ((f nz + k) ny + j) nx + i                        the low corner's index in the WHOLE fields array
+ * Voxel values are ordinary data: an infinite or NaN voxel gives what the arithmetic makes of it; a NaN clearance is written
+ * as it is and never becomes a minimum.  Outputs, each may be NULL, not all:
+ *   clearance_out_dev [n_paths][sample_capacity]       the interpolant; outside_value (any double: +inf for "unknown is free",
+ *                                                      a negative value for "unknown is occupied") for a live row that is not
+ *                                                      inside; +inf in the rows from n on, on dead paths and on paths that see
+ *                                                      no grid (relu(R - c) needs no mask)
+ *   cell_out_dev [n_paths][sample_capacity] int32      the cell; -1 wherever the row is not a live row inside its path's grid
+ *   gradient_out_dev [n_paths][sample_capacity][4]     (gx, gy, gz, 0): the field's gradient at the row; zeros wherever cell = -1
+ *   min_clearance_out_dev [n_paths]                    the minimum over the path's rows, +inf without any
+ *   argmin_out_dev [n_paths][2] int32                  {row, cell} of the first row whose clearance is strictly below every row in
+ *                                                      front of it, starting from +inf; {-1, -1} without any.  An outside_value
+ *                                                      row takes part like any other and reports cell = -1
+ * One workgroup per path, one lane per row; the per-path minimum is combined in the order "smaller value, then lower row",
+ * which no split changes.  No atomics, no workspace; every output element that belongs to the plan is written exactly once;
+ * the same bits on every call and for a path wherever it sits in the batch.  Out of scope: float32 fields; a gradient with
+ * respect to the field; interpolation smoother than trilinear; a device kernel that builds the field from an occupancy grid
+ * (from a list of obstacles the field IS mrs_tg_plan_obstacle_clearance's output over the nodes: DESIGN.md section 11k);
+ * splitting one path over several workgroups.
+ * MRS_TG_ERR_INVALID_ARG, before any launch: plan, n_samples_dev or geometry NULL, fields_dev NULL with n_fields > 0,
+ * samples_dev NULL with a positive capacity, a negative sample_capacity or n_fields, a dim below 2, a spacing that is not
+ * finite and positive, an origin that is not finite, n_fields nz ny nx above 2^31 - 1 (a cell is an int32), no output given,
+ * samples_dev or gradient_out_dev not 16-byte aligned or another array not aligned to its element.  n_paths == 0 or
+ * sample_capacity == 0: success, nothing is launched or written.  n_fields == 0: the kernel runs and writes +inf / -1 (and
+ * zeros) everywhere.  Device pointers except geometry, asynchronous on the context's stream. */
+typedef struct mrs_tg_field_geometry {
+  double origin[3];  /* x, y, z of node (0, 0, 0) */
+  double spacing[3]; /* hx, hy, hz: finite, positive */
+  int32_t dims[3];   /* nx, ny, nz: each >= 2 */
+  int32_t n_fields;  /* >= 0: grids of this geometry stacked in one array */
+} mrs_tg_field_geometry;
+int mrs_tg_plan_field_clearance(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev,
+                                int32_t sample_capacity, const double* fields_dev, const mrs_tg_field_geometry* geometry,
+                                const int32_t* path_field_dev, const int32_t* status_dev, double outside_value,
+                                double* clearance_out_dev, int32_t* cell_out_dev, double* gradient_out_dev,
+                                double* min_clearance_out_dev, int32_t* argmin_out_dev);
+/* Backward pass of mrs_tg_plan_field_clearance (field_clearance_vjp_kernel), the cells held fixed: given
+ * grad_clearance_dev [n_paths][sample_capacity] = dL/dclearance and cell_dev, the forward's cell_out_dev (an input), writes
+ * grad_samples_out_dev [n_paths][sample_capacity][4] = dL/dsamples = (g gx, g gy, g gz, 0): rows from n on zero, dead paths
+ * zero.  gx, gy, gz are recomputed from the row and the recorded cell as in the forward, with t = u - (double)i NOT clamped
+ * again: for the same inputs g * gradient_out_dev and this output are the same bits.  Exactly 0 come from: g == 0 (so the +inf
+ * rows never make a NaN), cell = -1, a cell that decodes to a grid other than the path's own, a cell that decodes to i, j, k
+ * outside [0, n - 2] -- none of which dereferences a voxel.  There is no gradient with respect to the field, and none through
+ * the choice of the cell.  One lane per output row: deterministic, no atomics, no workspace, every element written exactly
+ * once, the same bits on every call and wherever the path sits in the batch.  The argument checks are the forward's, with
+ * cell_dev, grad_clearance_dev and grad_samples_out_dev (16-byte aligned) required; grad_samples_out_dev may not overlap an
+ * input (MRS_TG_ERR_INVALID_ARG). */
+int mrs_tg_plan_field_clearance_vjp(mrs_tg_plan* plan, const double* samples_dev, const int32_t* n_samples_dev,
+                                    int32_t sample_capacity, const double* fields_dev, const mrs_tg_field_geometry* geometry,
+                                    const int32_t* path_field_dev, const int32_t* status_dev, const int32_t* cell_dev,
+                                    const double* grad_clearance_dev, double* grad_samples_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
@@ -1246,7 +1323,8 @@ int mrs_tg_plan_obstacle_clearance_vjp(mrs_tg_plan* plan, const double* samples_
  * (mrs_tg_plan_request_vertices), 32 their backward pass (mrs_tg_plan_request_vertices_vjp), 33 the request's limits
  * (mrs_tg_plan_request_limits), 34 their backward pass (mrs_tg_plan_request_limits_vjp), 35 the mutual clearance
  * (mrs_tg_plan_mutual_clearance), 36 its backward pass (mrs_tg_plan_mutual_clearance_vjp), 37 the clearance from obstacles
- * (mrs_tg_plan_obstacle_clearance), 38 its backward pass (mrs_tg_plan_obstacle_clearance_vjp): thirty-nine ids, 0 .. 38.
+ * (mrs_tg_plan_obstacle_clearance), 38 its backward pass (mrs_tg_plan_obstacle_clearance_vjp), 39 the clearance from a
+ * distance field (mrs_tg_plan_field_clearance), 40 its backward pass (mrs_tg_plan_field_clearance_vjp): forty-one ids, 0 .. 40.
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

@@ -57,6 +57,7 @@ KERNEL_SPLICE_PREDICTION_VJP, KERNEL_INITIAL_CONDITION_VJP, KERNEL_PREPEND_INITI
 KERNEL_REQUEST_VERTICES, KERNEL_REQUEST_VERTICES_VJP, KERNEL_REQUEST_LIMITS, KERNEL_REQUEST_LIMITS_VJP = 31, 32, 33, 34
 KERNEL_MUTUAL_CLEARANCE, KERNEL_MUTUAL_CLEARANCE_VJP = 35, 36
 KERNEL_OBSTACLE_CLEARANCE, KERNEL_OBSTACLE_CLEARANCE_VJP = 37, 38
+KERNEL_FIELD_CLEARANCE, KERNEL_FIELD_CLEARANCE_VJP = 39, 40
 
 
 class MrsTgError(RuntimeError):
@@ -99,6 +100,10 @@ class Prediction(C.Structure):
                 ("acceleration", C.c_void_p), ("jerk", C.c_void_p)]
 
 
+class _FieldGeometryStruct(C.Structure):   # mrs_tg_field_geometry (FieldGeometry fills it)
+    _fields_ = [("origin", C.c_double * 3), ("spacing", C.c_double * 3), ("dims", C.c_int32 * 3), ("n_fields", C.c_int32)]
+
+
 EXPORTED_SYMBOLS = [
     "mrs_tg_create", "mrs_tg_destroy", "mrs_tg_last_error", "mrs_tg_abi_version", "mrs_tg_capabilities", "mrs_tg_default_options",
     "mrs_tg_kernel_trace_reset", "mrs_tg_kernel_trace", "mrs_tg_plan_explain",
@@ -129,6 +134,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_plan_request_limits_vjp",
     "mrs_tg_plan_mutual_clearance", "mrs_tg_plan_mutual_clearance_vjp",
     "mrs_tg_plan_obstacle_clearance", "mrs_tg_plan_obstacle_clearance_vjp",
+    "mrs_tg_plan_field_clearance", "mrs_tg_plan_field_clearance_vjp",
 ]
 
 _lib = None
@@ -292,6 +298,11 @@ def load_library():
     L.mrs_tg_plan_obstacle_clearance.argtypes = [vp, dp, ip, C.c_int32, dp, C.c_int32, ip, C.c_int32, ip, ip, C.c_double, dp, ip, dp, ip]
     L.mrs_tg_plan_obstacle_clearance_vjp.restype = C.c_int
     L.mrs_tg_plan_obstacle_clearance_vjp.argtypes = [vp, dp, ip, C.c_int32, dp, C.c_int32, ip, C.c_int32, ip, ip, C.c_double, ip, dp, dp]
+    gp = C.POINTER(_FieldGeometryStruct)
+    L.mrs_tg_plan_field_clearance.restype = C.c_int
+    L.mrs_tg_plan_field_clearance.argtypes = [vp, dp, ip, C.c_int32, dp, gp, ip, ip, C.c_double, dp, ip, dp, dp, ip]
+    L.mrs_tg_plan_field_clearance_vjp.restype = C.c_int
+    L.mrs_tg_plan_field_clearance_vjp.argtypes = [vp, dp, ip, C.c_int32, dp, gp, ip, ip, ip, dp, dp]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -357,6 +368,7 @@ IC_FLAG_TRACKER, IC_FLAG_UAV, IC_FLAG_DONT_PREPEND = 1, 2, 4
 CAP_REQUEST = 32768   # MRS_TG_CAP_REQUEST: Plan.request_vertices, Plan.request_limits (findTrajectory's vertices and limits as plan steps) and their two backward passes
 CAP_MUTUAL_CLEARANCE = 65536   # MRS_TG_CAP_MUTUAL_CLEARANCE: Plan.mutual_clearance (the nearest other path of a row's group at the same step), Plan.mutual_clearance_vjp
 CAP_OBSTACLE_CLEARANCE = 131072   # MRS_TG_CAP_OBSTACLE_CLEARANCE: Plan.obstacle_clearance (the nearest sphere or point of the path's obstacle set, signed), Plan.obstacle_clearance_vjp
+CAP_FIELD_CLEARANCE = 262144   # MRS_TG_CAP_FIELD_CLEARANCE: Plan.field_clearance (the trilinear interpolant of a voxel grid of signed distances, its cell and gradient), Plan.field_clearance_vjp
 # Plan.request_limits' flags input (MRS_TG_REQ_*) and its branch word (MRS_TG_LIM_*)
 REQ_OVERRIDE, REQ_RELAX_HEADING = 1, 2
 LIM_OVERRIDDEN, LIM_OVERRIDE_REFUSED, LIM_RELAXED, LIM_V_DESCENDING, LIM_A_DESCENDING, LIM_J_DESCENDING, LIM_FALLBACK = 1, 2, 4, 8, 16, 32, 64
@@ -560,6 +572,53 @@ def check_set_offsets(set_offsets, n_obstacles):
         raise ValueError("set_offsets must start at 0, not decrease and end at n_obstacles = %d (got %s)"
                          % (n_obstacles, g.tolist()))
     return np.ascontiguousarray(g, dtype=np.int32)
+
+
+class FieldGeometry:
+    """mrs_tg_field_geometry: the geometry the grids of one fields array [n_fields][nz][ny][nx] share -- origin (x, y, z of
+    node (0, 0, 0)), spacing (hx, hy, hz), dims (nx, ny, nz), n_fields.  Node-centred: a caller with cell-centred voxels
+    passes the centre of voxel 0 as the origin."""
+
+    def __init__(self, origin, spacing, dims, n_fields=1):
+        self.origin = tuple(float(x) for x in origin)
+        self.spacing = tuple(float(x) for x in spacing)
+        self.dims = tuple(int(x) for x in dims)
+        self.n_fields = int(n_fields)
+        if len(self.origin) != 3 or len(self.spacing) != 3 or len(self.dims) != 3:
+            raise ValueError("origin, spacing and dims have three entries each: x, y, z")
+
+    def fields_shape(self):
+        return (self.n_fields, self.dims[2], self.dims[1], self.dims[0])
+
+    def as_struct(self):
+        g = _FieldGeometryStruct()
+        g.origin[:], g.spacing[:], g.dims[:], g.n_fields = self.origin, self.spacing, self.dims, self.n_fields
+        return g
+
+    def __repr__(self):
+        return "FieldGeometry(origin=%r, spacing=%r, dims=%r, n_fields=%d)" % (self.origin, self.spacing, self.dims, self.n_fields)
+
+
+def check_field_geometry(fields_shape, geometry):
+    """The geometry of Plan.field_clearance against the shape of its fields tensor, or ValueError: dims each >= 2, spacing
+    finite and positive, origin finite, n_fields >= 0, n_fields nz ny nx at most 2^31 - 1 (a cell is an int32), and the shape
+    [n_fields][nz][ny][nx].  No device is needed.  Returns the geometry."""
+    if not isinstance(geometry, FieldGeometry):
+        raise ValueError("geometry must be an api.FieldGeometry")
+    if any(n < 2 for n in geometry.dims):
+        raise ValueError("every dim of a field must be at least 2 (a 2-D map is two equal layers), not %r" % (geometry.dims,))
+    if not all(np.isfinite(h) and h > 0.0 for h in geometry.spacing):
+        raise ValueError("spacing must be finite and positive, not %r" % (geometry.spacing,))
+    if not all(np.isfinite(o) for o in geometry.origin):
+        raise ValueError("origin must be finite, not %r" % (geometry.origin,))
+    if geometry.n_fields < 0:
+        raise ValueError("n_fields %d is negative" % geometry.n_fields)
+    nx, ny, nz = geometry.dims
+    if geometry.n_fields * nz * ny * nx > 2 ** 31 - 1:
+        raise ValueError("n_fields nz ny nx = %d exceeds 2^31 - 1: a cell is an int32" % (geometry.n_fields * nz * ny * nx))
+    if tuple(int(x) for x in fields_shape) != geometry.fields_shape():
+        raise ValueError("fields must be [n_fields][nz][ny][nx] = %s, not %s" % (list(geometry.fields_shape()), list(fields_shape)))
+    return geometry
 
 
 def _check_operand(name, t, dtype, shape, like=None, optional=False):
@@ -1157,6 +1216,57 @@ class Plan:
                                                                    float(z_scale), _t_ptr(nearest), _t_ptr(grad_clearance),
                                                                    _t_ptr(grad_samples)),
                         "mrs_tg_plan_obstacle_clearance_vjp")
+
+    def _field_operands(self, samples, n_samples, fields, geometry, path_field, status):
+        """the operand checks the two field calls share -> (the C geometry, capacity)"""
+        import torch
+        P = self.n_paths
+        _check_operand("samples", samples, torch.float64, (P, None, N_DIM))
+        _check_operand("n_samples", n_samples, torch.int32, (P,), samples)
+        _check_operand("fields", fields, torch.float64, (None, None, None, None), samples)
+        check_field_geometry(fields.shape, geometry)
+        _check_operand("path_field", path_field, torch.int32, (P,), samples, optional=True)
+        _check_operand("status", status, torch.int32, (P,), samples, optional=True)
+        return geometry.as_struct(), int(samples.shape[1])
+
+    def field_clearance(self, samples, n_samples, fields, geometry, path_field=None, status=None, outside_value=float("inf"),
+                        clearance=None, cell=None, gradient=None, min_clearance=None, argmin=None):
+        """mrs_tg_plan_field_clearance: per row of samples [n_paths][capacity][4] (n_samples [n_paths] int32) the trilinear
+        interpolant of the voxel grid of signed distances the path sees -- fields [n_fields][nz][ny][nx] float64 with geometry
+        (an api.FieldGeometry, checked: ValueError), path_field [n_paths] int32 (None: every path sees grid 0), outside_value
+        for a live row outside the grid -- into clearance [n_paths][capacity] (+inf behind a path's rows and without a grid),
+        cell [n_paths][capacity] (int32, the low corner's index in the whole fields array, -1 where there is none), gradient
+        [n_paths][capacity][4] (the field's gradient, column 3 zero), min_clearance [n_paths] and argmin [n_paths][2] (int32:
+        row, cell) (device tensors, written; None = not wanted, at least one given); asynchronous on the context's stream."""
+        import torch
+        g, cap = self._field_operands(samples, n_samples, fields, geometry, path_field, status)
+        P = self.n_paths
+        _check_operand("clearance", clearance, torch.float64, (P, cap), samples, optional=True)
+        _check_operand("cell", cell, torch.int32, (P, cap), samples, optional=True)
+        _check_operand("gradient", gradient, torch.float64, (P, cap, N_DIM), samples, optional=True)
+        _check_operand("min_clearance", min_clearance, torch.float64, (P,), samples, optional=True)
+        _check_operand("argmin", argmin, torch.int32, (P, 2), samples, optional=True)
+        self.ctx._check(self._L.mrs_tg_plan_field_clearance(self._h, _t_ptr(samples), _t_ptr(n_samples), cap, _t_ptr(fields),
+                                                            C.byref(g), _t_ptr(path_field), _t_ptr(status), float(outside_value),
+                                                            _t_ptr(clearance), _t_ptr(cell), _t_ptr(gradient),
+                                                            _t_ptr(min_clearance), _t_ptr(argmin)),
+                        "mrs_tg_plan_field_clearance")
+
+    def field_clearance_vjp(self, samples, n_samples, fields, geometry, cell, grad_clearance, grad_samples, path_field=None,
+                            status=None):
+        """mrs_tg_plan_field_clearance_vjp: dL/dsamples [n_paths][capacity][4] (grad_samples, written, zeros included) from
+        dL/dclearance (grad_clearance [n_paths][capacity]) with the forward's cell [n_paths][capacity] (int32) held fixed; the
+        other arguments are the forward's; asynchronous on the context's stream."""
+        import torch
+        g, cap = self._field_operands(samples, n_samples, fields, geometry, path_field, status)
+        P = self.n_paths
+        _check_operand("cell", cell, torch.int32, (P, cap), samples)
+        _check_operand("grad_clearance", grad_clearance, torch.float64, (P, cap), samples)
+        _check_operand("grad_samples", grad_samples, torch.float64, (P, cap, N_DIM), samples)
+        self.ctx._check(self._L.mrs_tg_plan_field_clearance_vjp(self._h, _t_ptr(samples), _t_ptr(n_samples), cap, _t_ptr(fields),
+                                                                C.byref(g), _t_ptr(path_field), _t_ptr(status), _t_ptr(cell),
+                                                                _t_ptr(grad_clearance), _t_ptr(grad_samples)),
+                        "mrs_tg_plan_field_clearance_vjp")
 
     def estimate_times(self, waypoints, limits, seg_times):
         """mrs_tg_plan_estimate_times: the Euclidean segment-time estimate of waypoints [sum V][4] under limits [n_paths][9] into

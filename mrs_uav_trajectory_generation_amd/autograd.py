@@ -139,6 +139,17 @@ from everything, checked on a grid finer than the tracker's:
     >>> clearance, nearest = obstacle_clearance(plan, samples, n, obstacles, status=status)   # one set: the whole map
     >>> torch.relu(1.0 - clearance).sum().backward()                    # +inf behind a path's last row: no mask; fv.grad, times.grad
     >>> worst = clearance.amin(dim=1)                                   # per path; nearest says which obstacle
+
+field_clearance (Plan.field_clearance forward, Plan.field_clearance_vjp backward: mrs_tg_plan_field_clearance /
+mrs_tg_plan_field_clearance_vjp) is the same loss against a map given as a voxel grid of signed
+distances (an ESDF), looked up by trilinear interpolation: eight voxel reads per row whatever the size of the map, where
+obstacle_clearance pays for every obstacle on every iteration.  Where only a list of obstacles exists the grid is built once
+(Plan.obstacle_clearance over the nodes of the grid).  The cell is held fixed in the backward pass, the
+field itself gets no gradient, and the caller says what space outside the grid means (outside_value):
+
+    >>> geometry = api.FieldGeometry(origin=(-20.0, -20.0, 0.0), spacing=(0.2, 0.2, 0.2), dims=(200, 200, 50))
+    >>> clearance, cell, least, where = field_clearance(plan, samples, n, fields, geometry, status=status)   # fields [1][50][200][200]
+    >>> torch.relu(1.0 - clearance).sum().backward()                    # or torch.relu(1.0 - least).sum(): the worst row of every path
 """
 import numpy as np
 import torch
@@ -779,6 +790,76 @@ def obstacle_clearance(plan, samples, n_samples, obstacles, set_offsets=None, pa
         raise ValueError("obstacle_clearance has no gradient with respect to the obstacles (a static map): pass "
                          "obstacles.detach()")
     return _ObstacleClearance.apply(plan, samples, n_samples, obstacles, set_offsets, path_set, status, z_scale)
+
+
+class _FieldClearance(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, samples, n_samples, fields, geometry, path_field, status, outside_value):
+        s = samples.detach().to(torch.float64).contiguous()
+        n = n_samples.detach().to(torch.int32).contiguous()
+        if s.dim() != 3 or s.shape[0] != plan.n_paths or s.shape[2] != api.N_DIM:
+            raise ValueError("samples must be [n_paths][capacity][4]")
+        if n.dim() != 1 or n.shape[0] != plan.n_paths:
+            raise ValueError("n_samples must be [n_paths]")
+        fl = fields.detach().to(torch.float64).contiguous()
+        if fl.dim() != 4:
+            raise ValueError("fields must be [n_fields][nz][ny][nx]")
+        pf = None if path_field is None else path_field.detach().to(torch.int32).contiguous()
+        if pf is not None and (pf.dim() != 1 or pf.shape[0] != plan.n_paths):
+            raise ValueError("path_field must be [n_paths]")
+        st = None if status is None else status.detach().to(torch.int32).contiguous()
+        # (a call without rows launches nothing: the neutral values are there beforehand)
+        P = plan.n_paths
+        clearance = torch.full(s.shape[:2], float("inf"), dtype=torch.float64, device=s.device)
+        cell = torch.full(s.shape[:2], -1, dtype=torch.int32, device=s.device)
+        least = torch.full((P,), float("inf"), dtype=torch.float64, device=s.device)
+        argmin = torch.full((P, 2), -1, dtype=torch.int32, device=s.device)
+        plan.ctx.use_torch_stream()
+        plan.field_clearance(s, n, fl, geometry, path_field=pf, status=st, outside_value=float(outside_value),
+                             clearance=clearance, cell=cell, min_clearance=least, argmin=argmin)
+        ctx.plan, ctx.geometry, ctx.path_field, ctx.status = plan, geometry, pf, st
+        ctx.save_for_backward(s, n, fl, cell, argmin)
+        ctx.mark_non_differentiable(cell, argmin)
+        ctx.set_materialize_grads(False)
+        return clearance, cell, least, argmin
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_clearance, _grad_cell, grad_least, _grad_argmin):
+        s, n, fl, cell, argmin = ctx.saved_tensors
+        if (grad_clearance is None and grad_least is None) or not ctx.needs_input_grad[1]:
+            return None, None, None, None, None, None, None, None
+        up = torch.zeros(s.shape[:2], dtype=torch.float64, device=s.device) if grad_clearance is None \
+            else grad_clearance.to(torch.float64).contiguous().clone()
+        if grad_least is not None and s.shape[1] > 0:
+            # the minimum is the clearance of its argmin row: its upstream goes there (nowhere for a path without a minimum)
+            row = argmin[:, 0].to(torch.int64)
+            has = row >= 0
+            up[has.nonzero(as_tuple=True)[0], row[has]] += grad_least.to(torch.float64)[has]
+        gs = torch.zeros_like(s)
+        plan = ctx.plan
+        plan.ctx.use_torch_stream()   # (the autograd engine runs this on its own thread, on the forward's stream)
+        plan.field_clearance_vjp(s, n, fl, ctx.geometry, cell, up, gs, path_field=ctx.path_field, status=ctx.status)
+        return None, gs, None, None, None, None, None, None
+
+
+def field_clearance(plan, samples, n_samples, fields, geometry, path_field=None, status=None, outside_value=float("inf")):
+    """(clearance [n_paths][capacity], cell [n_paths][capacity] int32, min_clearance [n_paths], argmin [n_paths][2] int32) of
+    Plan.field_clearance: for every live row of samples [n_paths][capacity][4] the trilinear interpolant of the voxel grid of
+    signed distances its path sees, the index of the cell's low corner in the whole fields array, per path the least
+    clearance and {row, cell} of the first row that has it.  fields [n_fields][nz][ny][nx] float64 on the device, x fastest,
+    node-centred, with geometry an api.FieldGeometry (origin, spacing, dims, n_fields; checked); path_field [n_paths] int32
+    names every path's grid (None: grid 0; an entry outside [0, n_fields): none); n_samples [n_paths] int32 as the sampler
+    returned it; outside_value is what a live row outside the grid gets (+inf: unknown space is free; a negative value: it is
+    occupied), with cell -1.  Differentiable in samples ONLY (float64 device tensor; x, y, z are read, column 3 gets a zero
+    gradient), through clearance and through min_clearance, whose gradient goes to its argmin row: the field is a static
+    map, and asking for its gradient raises instead of returning None.  Rows outside the grid, rows of a path without a grid,
+    rows from n on and the rows of a path with status <= 0 (status [n_paths], optional) have cell -1 and get a zero gradient;
+    the last three hold clearance +inf, so relu(R - clearance) needs no mask.  The gradient holds every cell fixed: it is the
+    gradient of the trilinear interpolant inside the cell the forward chose, which jumps across cell faces."""
+    if isinstance(fields, torch.Tensor) and fields.requires_grad:
+        raise ValueError("field_clearance has no gradient with respect to the field (a static map): pass fields.detach()")
+    return _FieldClearance.apply(plan, samples, n_samples, fields, geometry, path_field, status, outside_value)
 
 
 def _f64(t):

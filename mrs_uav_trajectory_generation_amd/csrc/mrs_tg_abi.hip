@@ -24,6 +24,7 @@
 
 #include "../../include/mrs_tg.h"
 #include "mrs_tg_fallback.hpp"
+#include "mrs_tg_field.hpp"
 #include "mrs_tg_pathedit.hpp"
 #include "mrs_tg_launch.h"
 #include "mrs_tg_nonlinear.h"
@@ -53,7 +54,7 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 39;  // kernel_id 0 .. 38 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 41;  // kernel_id 0 .. 40 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
   long long ev_count[kTimedKernels] = {};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
@@ -197,7 +198,7 @@ int mrs_tg_capabilities(void) {
          MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE | MRS_TG_CAP_DEVIATION |
          MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE | MRS_TG_CAP_BACA | MRS_TG_CAP_FALLBACK_SAMPLE |
          MRS_TG_CAP_PATH_EDIT | MRS_TG_CAP_TRAVEL_HEADING | MRS_TG_CAP_INITIAL_CONDITION | MRS_TG_CAP_REQUEST |
-         MRS_TG_CAP_MUTUAL_CLEARANCE | MRS_TG_CAP_OBSTACLE_CLEARANCE;
+         MRS_TG_CAP_MUTUAL_CLEARANCE | MRS_TG_CAP_OBSTACLE_CLEARANCE | MRS_TG_CAP_FIELD_CLEARANCE;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1716,6 +1717,98 @@ int mrs_tg_plan_obstacle_clearance_vjp(mrs_tg_plan* plan, const double* samples,
   HIP_TRY(ctx, mrs_tg::launch_obstacle_clearance_vjp(plan->view.n_paths, samples, n_samples, sample_capacity, obstacles,
                                                      n_obstacles, set_offsets, n_sets, path_set, status, z_scale, nearest,
                                                      grad_clearance, grad_samples_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+// ---- clearance from a voxel distance field as a plan step (mrs_tg_field.hip) ---------------------------------------------------------
+
+// what the two field calls check before any launch; fills the kernels' geometry
+static int field_clearance_arguments(mrs_tg_ctx* ctx, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                     const double* fields, const mrs_tg_field_geometry* geometry, const int32_t* path_field,
+                                     const int32_t* status, mrs_tg::fldq::Geometry* out) {
+  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
+  if (!n_samples || !geometry || (sample_capacity > 0 && !samples))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev and geometry are required");
+  if (geometry->n_fields < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_fields %d is negative", geometry->n_fields);
+  if (geometry->n_fields > 0 && !fields) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "fields_dev is NULL with %d fields", geometry->n_fields);
+  long long voxels = geometry->n_fields;
+  for (int a = 0; a < 3; ++a) {
+    if (geometry->dims[a] < 2) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "dims[%d] = %d is below 2", a, geometry->dims[a]);
+    if (!(std::isfinite(geometry->spacing[a]) && geometry->spacing[a] > 0.0))
+      return fail(ctx, MRS_TG_ERR_INVALID_ARG, "spacing[%d] must be finite and positive", a);
+    if (!std::isfinite(geometry->origin[a])) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "origin[%d] is not finite", a);
+    // (every factor is below 2^31 and the running product is held to 2^31 - 1: no overflow of the 64-bit product)
+    voxels *= geometry->dims[a];
+    if (voxels > 2147483647LL)
+      return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_fields nz ny nx exceeds 2^31 - 1: a cell is an int32");
+  }
+  if ((((uintptr_t)samples) & 15u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev is not 16-byte aligned");
+  if ((((uintptr_t)fields) & 7u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "fields_dev is not 8-byte aligned");
+  if ((((uintptr_t)n_samples | (uintptr_t)path_field | (uintptr_t)status) & 3u) != 0)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "an int32 array is not 4-byte aligned");
+  for (int a = 0; a < 3; ++a) out->o[a] = geometry->origin[a], out->h[a] = geometry->spacing[a], out->n[a] = geometry->dims[a];
+  out->n_fields = geometry->n_fields;
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_field_clearance(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                const double* fields, const mrs_tg_field_geometry* geometry, const int32_t* path_field,
+                                const int32_t* status, double outside_value, double* clearance_out, int32_t* cell_out,
+                                double* gradient_out, double* min_clearance_out, int32_t* argmin_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  mrs_tg::fldq::Geometry G;
+  if (const int rc = field_clearance_arguments(ctx, samples, n_samples, sample_capacity, fields, geometry, path_field, status, &G);
+      rc != MRS_TG_OK)
+    return rc;
+  if (!clearance_out && !cell_out && !gradient_out && !min_clearance_out && !argmin_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "every output of mrs_tg_plan_field_clearance is NULL");
+  if (((uintptr_t)gradient_out & 15u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "gradient_out_dev is not 16-byte aligned");
+  if ((((uintptr_t)clearance_out | (uintptr_t)min_clearance_out) & 7u) != 0 ||
+      (((uintptr_t)cell_out | (uintptr_t)argmin_out) & 3u) != 0)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "an output array is not aligned to its element");
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 39);
+  HIP_TRY(ctx, mrs_tg::launch_field_clearance(plan->view.n_paths, samples, n_samples, sample_capacity, fields, G, path_field, status,
+                                              outside_value, clearance_out, cell_out, gradient_out, min_clearance_out, argmin_out,
+                                              ctx->stream));
+  return MRS_TG_OK;
+}
+
+int mrs_tg_plan_field_clearance_vjp(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                    const double* fields, const mrs_tg_field_geometry* geometry, const int32_t* path_field,
+                                    const int32_t* status, const int32_t* cell, const double* grad_clearance,
+                                    double* grad_samples_out) {
+  if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
+  mrs_tg_ctx* ctx = plan->ctx;
+  mrs_tg::fldq::Geometry G;
+  if (const int rc = field_clearance_arguments(ctx, samples, n_samples, sample_capacity, fields, geometry, path_field, status, &G);
+      rc != MRS_TG_OK)
+    return rc;
+  if (!cell || !grad_clearance || !grad_samples_out)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "cell_dev, grad_clearance_dev and grad_samples_out_dev are required");
+  if (((uintptr_t)grad_samples_out & 15u) != 0 || ((uintptr_t)grad_clearance & 7u) != 0 || ((uintptr_t)cell & 3u) != 0)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
+                "grad_samples_out_dev is not 16-byte aligned, or grad_clearance_dev or cell_dev not to its element");
+  // the output may not overlap an input: the byte ranges the kernel touches
+  const size_t P = (size_t)plan->view.n_paths, rows = P * (size_t)sample_capacity;
+  const size_t voxels = (size_t)G.n_fields * (size_t)G.n[2] * (size_t)G.n[1] * (size_t)G.n[0];
+  const uintptr_t out_lo = (uintptr_t)grad_samples_out, out_hi = out_lo + rows * 4 * sizeof(double);
+  const struct {
+    const void* at;
+    size_t bytes;
+    const char* name;
+  } inputs[] = {{samples, rows * 4 * sizeof(double), "samples_dev"},       {n_samples, P * sizeof(int32_t), "n_samples_dev"},
+                {fields, voxels * sizeof(double), "fields_dev"},            {path_field, P * sizeof(int32_t), "path_field_dev"},
+                {status, P * sizeof(int32_t), "status_dev"},                {cell, rows * sizeof(int32_t), "cell_dev"},
+                {grad_clearance, rows * sizeof(double), "grad_clearance_dev"}};
+  for (const auto& in : inputs)
+    if (in.at && in.bytes && (uintptr_t)in.at < out_hi && out_lo < (uintptr_t)in.at + in.bytes)
+      return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_samples_out_dev overlaps %s", in.name);
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 40);
+  HIP_TRY(ctx, mrs_tg::launch_field_clearance_vjp(plan->view.n_paths, samples, n_samples, sample_capacity, fields, G, path_field,
+                                                  status, cell, grad_clearance, grad_samples_out, ctx->stream));
   return MRS_TG_OK;
 }
 

@@ -20,6 +20,9 @@ namespace mrs_tg {
 namespace pathq {
 struct ThinOptions;  // mrs_tg_pathedit.hpp
 }
+namespace fldq {
+struct Geometry;  // mrs_tg_field.hpp
+}
 
 // Per-dispatch timing (mrs_tg_set_profiling): the next launch of the kernel family a ProfileScope names carries these
 // events on the launch itself (hipExtLaunchKernelGGL), so their difference is the dispatch's own start-to-end time.
@@ -369,6 +372,21 @@ hipError_t launch_obstacle_clearance_vjp(int n_paths, const double* samples, con
                                          const double* obstacles, int n_obstacles, const int32_t* set_offsets, int n_sets,
                                          const int32_t* path_set, const int32_t* status, double z_scale, const int32_t* nearest,
                                          const double* grad_clearance, double* grad_samples, hipStream_t stream);
+// mrs_tg_plan_field_clearance / mrs_tg_plan_field_clearance_vjp (mrs_tg_field.hip, mrs_tg_field.hpp): per row of samples
+// [n_paths][capacity][4] the trilinear interpolant of the voxel grid of signed distances the path sees -- fields
+// [n_fields][nz][ny][nx] of one geometry, path_field [n_paths] or null: every path sees grid 0; outside_value for a live row
+// outside the grid -- the low corner's index in the whole array, the field's gradient [n_paths][capacity][4], per path the
+// minimum over its rows and where it is (every output may be null); and its backward pass, dL/dsamples from dL/dclearance with
+// the cells held fixed.  status null or per path (<= 0: no rows).  One workgroup per path; reads only, no workspace, no dynamic
+// LDS; each timed as the kernel family of the pending ProfileScope
+hipError_t launch_field_clearance(int n_paths, const double* samples, const int32_t* n_samples, int capacity, const double* fields,
+                                  const fldq::Geometry& geometry, const int32_t* path_field, const int32_t* status,
+                                  double outside_value, double* clearance, int32_t* cell, double* gradient, double* min_clearance,
+                                  int32_t* argmin, hipStream_t stream);
+hipError_t launch_field_clearance_vjp(int n_paths, const double* samples, const int32_t* n_samples, int capacity,
+                                      const double* fields, const fldq::Geometry& geometry, const int32_t* path_field,
+                                      const int32_t* status, const int32_t* cell, const double* grad_clearance,
+                                      double* grad_samples, hipStream_t stream);
 // What the rows kernel can do around its solve for the same path, in the same launch:
 //   before: the feasibility scaling of the segment times (scaleSegmentTimesWithViolation's T_i <- s_i T_i from the
 //           per-segment maxima, written back to seg_times) -- the last stage before the final solve of the Mellinger pipeline;

@@ -21,8 +21,8 @@
 // arrays leaves the obstacle array.
 //
 // Out of scope.  No gradient with respect to the obstacles: they are a static map.  No gradient flows through the choice of
-// the obstacle.  A spatial index (grid, tree) over the obstacles.  (The kernel spares the square root of obstacles that cannot
-// win, by cannot_win below, which holds the argument why that changes no bit; the plain loop nearest_obstacle is the definition
+// the obstacle.  A spatial index over the obstacles: for a static map that is mrs_tg_field.hpp's voxel grid.  (The kernel
+// spares the square root of obstacles that cannot win, by cannot_win below, which holds the argument why that changes no bit; the plain loop nearest_obstacle is the definition
 // and what the harness runs.)
 #pragma once
 
