@@ -15,7 +15,18 @@ and for every fixed slot (0 on free slots).  Cases:
   * a 30-segment path: directional derivatives along three random directions in (times, fixed values) only;
   * an ill-conditioned path: one segment 50 times shorter than its neighbours.
 
-Run from the repo root:  python3 tests/golden/gen_vjp_cases.py   (a few minutes: the 30-segment case dominates)
+With --edges the second list goes to tests/golden/vjp_edge_cases.json instead (vjp_cases.json is not touched): the lengths,
+derivatives and patterns at which the lane routine's sweeps degenerate, every one with the full per-slot gradients:
+
+  * one and two segments (S = 1: the forward sweep's last-vertex branch, the backward sweep's first step and the first vertex's
+    epilogue are the whole path);
+  * d = 1 and d = 0 (vertices built for d = 2, so that the end vertices fix position, velocity and acceleration);
+  * a position-only end vertex on one segment, a position-only start vertex;
+  * every slot fixed (no free slot: lambda = 0, the gradient is the direct term alone);
+  * a fixed slot between free ones in a vertex block; two adjacent position-free vertices; two adjacent stop_at vertices.
+
+Run from the repo root:  python3 tests/golden/gen_vjp_cases.py           (a few minutes: the 30-segment case dominates)
+                         python3 tests/golden/gen_vjp_cases.py --edges   (seconds)
 """
 import json
 import os
@@ -33,6 +44,7 @@ mp.mp.dps = 60
 N, D, B = 10, 4, 5
 STEP = mp.mpf("1e-20")
 OUT = os.path.join(ROOT, "tests", "golden", "vjp_cases.json")
+OUT_EDGES = os.path.join(ROOT, "tests", "golden", "vjp_edge_cases.json")
 
 
 def kkt_solver(mask, times, d):
@@ -184,11 +196,46 @@ def cases():
     return out
 
 
+def edge_cases():
+    out = []
+    # (name, segments, d the vertices are built for, d of the solve, seed)
+    for name, S, d_build, d, seed in (("s1_d4", 1, 4, 4, 800), ("s1_d2", 1, 2, 2, 801), ("s2_d4", 2, 4, 4, 802),
+                                      ("s2_d3", 2, 3, 3, 803), ("d1_s3", 3, 2, 1, 804), ("d0_s3", 3, 2, 0, 805),
+                                      ("d0_s1", 1, 2, 0, 806)):
+        m, v, t = path(S, seed, d_build)
+        out.append(record(name, m, v, t, d, seed))
+    m, v, t = path(1, 810, 4)
+    m[-1, 1:] = 0      # one segment whose end vertex constrains its position only
+    v[-1, 1:, :] = 0.0
+    out.append(record("s1_free_end", m, v, t, 4, 810))
+    m, v, t = path(3, 811, 4)
+    m[0, 1:] = 0       # the start vertex constrains its position only
+    v[0, 1:, :] = 0.0
+    out.append(record("s3_free_start", m, v, t, 4, 811))
+    m, v, t = path(3, 812, 4)
+    rng = np.random.default_rng(812)
+    for k in range(1, B):   # every slot fixed, the interior derivatives at dyadic values that shrink with the order
+        v[1:-1, k, :] = rng.integers(-16, 17, size=(2, D)) / (16.0 * 4.0 ** k)
+    m[:, :] = 1
+    out.append(record("s3_all_fixed", m, v, t, 4, 812))
+    m, v, t = path(4, 813, 4)
+    m[1, 2] = 1        # vertex 1 fixes its acceleration (at 0) while its velocity stays free: a fixed slot between free ones
+    out.append(record("s4_fixed_acc_free_vel", m, v, t, 4, 813))
+    m, v, t = path(4, 814, 4)
+    m[1:3, 0] = 0      # vertices 1 and 2 both leave their position free
+    v[1:3, 0, :] = 0.0
+    out.append(record("s4_two_position_free", m, v, t, 4, 814))
+    m, v, t = path(4, 815, 4, stop_at=[False, True, True, False, False])
+    out.append(record("s4_two_stop_at", m, v, t, 4, 815))
+    return out
+
+
 def main():
-    cs = cases()
-    with open(OUT, "w") as f:
-        json.dump(dict(generator="tests/golden/gen_vjp_cases.py", mp_dps=60, cases=cs), f)
-    print("wrote", len(cs), "cases to", OUT)
+    edges = "--edges" in sys.argv[1:]
+    cs, out = (edge_cases(), OUT_EDGES) if edges else (cases(), OUT)
+    with open(out, "w") as f:
+        json.dump(dict(generator="tests/golden/gen_vjp_cases.py" + (" --edges" if edges else ""), mp_dps=60, cases=cs), f)
+    print("wrote", len(cs), "cases to", out)
 
 
 if __name__ == "__main__":

@@ -4,6 +4,9 @@ compiled with g++ by tests/host/vjp_harness.cpp, against
   * the 60-digit central differences of tests/golden/vjp_cases.json (gen_vjp_cases.py): every well-conditioned case to 1e-10
     of the path's largest gradient entry, the ill-conditioned one (a segment 50 times shorter than its neighbours) to the bound
     this harness measures (DESIGN.md section 4c), the 30-segment path along its three directions;
+  * those of tests/golden/vjp_edge_cases.json (gen_vjp_cases.py --edges) to the same 1e-10: one and two segments, d = 0 and 1,
+    position-only end and start vertices, no free slot at all, a fixed slot between free ones, adjacent position-free and
+    adjacent stop_at vertices;
   * a dense float64 torch-autograd restatement (tests/vjp_util.py) on 200 random paths;
   * itself under -fsanitize=address,undefined (host code only).
 
@@ -53,10 +56,35 @@ def test_fixtures_hold_the_required_cases():
     assert np.array(free_end["fixed_mask"])[-1].tolist() == [1, 0, 0, 0, 0]
     assert np.array(next(c for c in cases if c["name"] == "position_free_vertex")["fixed_mask"])[2, 0] == 0
     assert len(next(c for c in cases if c["name"] == "seg30_directional")["seg_times"]) == 30
+    # the edge file (gen_vjp_cases.py --edges): the lengths and derivatives the file above leaves out, and its patterns
+    edges = {c["name"]: c for c in vu.load_edge_cases()}
+    assert not set(edges) & names
+    key = {(c["derivative_to_optimize"], len(c["seg_times"])) for c in edges.values()}
+    assert {(4, 1), (2, 1), (4, 2), (3, 2), (1, 3), (0, 3), (0, 1)} <= key
+    assert {d for d, _ in key} == {0, 1, 2, 3, 4} and {S for _, S in key} == {1, 2, 3, 4}
+    for c in edges.values():
+        m = np.array(c["fixed_mask"])
+        assert "directions" not in c and m.shape == (len(c["seg_times"]) + 1, 5), c["name"]
+        g = np.array(c["grad_coeffs"])
+        assert np.array_equal(g * 64, np.round(g * 64)) and c["grad_cost"] * 8 == round(c["grad_cost"] * 8)   # dyadic
+        assert np.all(np.array(c["grad_fixed_values"])[m == 0] == 0.0), c["name"]
+        assert np.any(np.array(c["grad_seg_times"]) != 0.0), c["name"]
+
+    def mask(name):
+        return np.array(edges[name]["fixed_mask"])
+    assert len(edges["s1_free_end"]["seg_times"]) == 1 and mask("s1_free_end")[-1].tolist() == [1, 0, 0, 0, 0]
+    assert len(edges["s3_free_start"]["seg_times"]) == 3 and mask("s3_free_start")[0].tolist() == [1, 0, 0, 0, 0]
+    assert len(edges["s3_all_fixed"]["seg_times"]) == 3 and np.all(mask("s3_all_fixed") == 1)
+    assert np.any(np.array(edges["s3_all_fixed"]["grad_fixed_values"])[1:-1, 1:] != 0.0)
+    assert mask("s4_fixed_acc_free_vel")[1].tolist() == [1, 0, 1, 0, 0]
+    assert mask("s4_two_position_free")[1:3, 0].tolist() == [0, 0]
+    assert mask("s4_two_stop_at")[1:3].tolist() == [[1, 1, 1, 1, 0]] * 2
+    for name in ("d1_s3", "d0_s3", "d0_s1"):   # built for d = 2: the end vertices fix position, velocity and acceleration
+        assert mask(name)[0].tolist() == mask(name)[-1].tolist() == [1, 1, 1, 0, 0], name
 
 
 def test_lane_routine_matches_every_fixture(harness):
-    cases = vu.load_cases()
+    cases = vu.load_cases() + vu.load_edge_cases()
     errs = _fixture_errors(vu.run_harness(harness, [vu.case_problem(c) for c in cases]), cases)
     print("VJP HOST FIXTURES: %s" % {k: "%.1e" % v for k, v in errs.items()})
     for name, e in errs.items():
@@ -64,7 +92,7 @@ def test_lane_routine_matches_every_fixture(harness):
 
 
 def test_null_upstream_coefficients_count_as_zero(harness):
-    cases = [c for c in vu.load_cases() if "directions" not in c]
+    cases = [c for c in vu.load_cases() + vu.load_edge_cases() if "directions" not in c]
     nul = [dict(vu.case_problem(c), G=None) for c in cases]
     zero = [dict(vu.case_problem(c), G=np.zeros_like(np.array(c["grad_coeffs"]))) for c in cases]
     for (a_v, a_t), (b_v, b_t) in zip(vu.run_harness(harness, nul), vu.run_harness(harness, zero)):
@@ -111,8 +139,8 @@ def test_lane_routine_matches_a_dense_torch_restatement_on_200_random_paths(harn
 
 def test_harness_under_address_and_undefined_behaviour_sanitizers(tmp_path, harness):
     san = vu.build_harness(tmp_path, sanitize=True)
-    cases = vu.load_cases()
-    probs = [vu.case_problem(c) for c in cases] + [dict(vu.case_problem(cases[0]), G=None)]
+    cases = vu.load_cases() + vu.load_edge_cases()
+    probs = [vu.case_problem(c) for c in cases] + [dict(vu.case_problem(c), G=None) for c in (cases[0], cases[-1])]
     env = dict(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     got = vu.run_harness(san, probs, env=env)
     ref = vu.run_harness(harness, probs)

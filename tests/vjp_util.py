@@ -12,6 +12,7 @@ import numpy as np
 from tests import host_harness as hh
 
 load_cases = functools.partial(hh.load_cases, "vjp_cases.json")
+load_edge_cases = functools.partial(hh.load_cases, "vjp_edge_cases.json")   # (gen_vjp_cases.py --edges)
 build_harness = functools.partial(hh.build, "vjp_harness.cpp")   # (tmp_path, sanitize=False)
 N, D, B = 10, 4, 5
 
