@@ -229,9 +229,11 @@ enum {
   MRS_TG_CAP_OBSTACLE_CLEARANCE = 131072, /* mrs_tg_plan_obstacle_clearance and mrs_tg_plan_obstacle_clearance_vjp are exported: the
                                          signed distance of every row to the nearest sphere or point of the path's obstacle set,
                                          that obstacle's index, and the backward pass */
-  MRS_TG_CAP_FIELD_CLEARANCE = 262144   /* mrs_tg_plan_field_clearance and mrs_tg_plan_field_clearance_vjp are exported: the
+  MRS_TG_CAP_FIELD_CLEARANCE = 262144,  /* mrs_tg_plan_field_clearance and mrs_tg_plan_field_clearance_vjp are exported: the
                                          trilinear interpolant of a voxel grid of signed distances at every row, its cell, the
                                          field's gradient, and the backward pass */
+  MRS_TG_CAP_FIELD_FROM_OCCUPANCY = 524288 /* mrs_tg_field_from_occupancy is exported: that grid of (signed) distances built on
+                                         the device from an occupancy grid by an exact Euclidean distance transform */
 };
 
 /* mrs_tg_plan_request_limits' flags_dev: what the request asks of its limits */
@@ -1265,9 +1267,9 @@ int mrs_tg_plan_obstacle_clearance_vjp(mrs_tg_plan* plan, const double* samples_
  * One workgroup per path, one lane per row; the per-path minimum is combined in the order "smaller value, then lower row",
  * which no split changes.  No atomics, no workspace; every output element that belongs to the plan is written exactly once;
  * the same bits on every call and for a path wherever it sits in the batch.  Out of scope: float32 fields; a gradient with
- * respect to the field; interpolation smoother than trilinear; a device kernel that builds the field from an occupancy grid
- * (from a list of obstacles the field IS mrs_tg_plan_obstacle_clearance's output over the nodes: DESIGN.md section 11k);
- * splitting one path over several workgroups.
+ * respect to the field; interpolation smoother than trilinear; splitting one path over several workgroups.  (The field itself:
+ * from an occupancy grid mrs_tg_field_from_occupancy builds it on the device; from a list of obstacles it IS
+ * mrs_tg_plan_obstacle_clearance's output over the nodes)
  * MRS_TG_ERR_INVALID_ARG, before any launch: plan, n_samples_dev or geometry NULL, fields_dev NULL with n_fields > 0,
  * samples_dev NULL with a positive capacity, a negative sample_capacity or n_fields, a dim below 2, a spacing that is not
  * finite and positive, an origin that is not finite, n_fields nz ny nx above 2^31 - 1 (a cell is an int32), no output given,
@@ -1301,6 +1303,39 @@ int mrs_tg_plan_field_clearance_vjp(mrs_tg_plan* plan, const double* samples_dev
                                     const int32_t* path_field_dev, const int32_t* status_dev, const int32_t* cell_dev,
                                     const double* grad_clearance_dev, double* grad_samples_out_dev);
 
+/* The distance field from an occupancy grid (MRS_TG_CAP_FIELD_FROM_OCCUPANCY; edt_x_kernel, edt_y_kernel, edt_z_kernel,
+ * csrc/mrs_tg_edt.hpp): an exact Euclidean distance transform on the device, from what a mapping stack
+ * publishes to what mrs_tg_plan_field_clearance reads, in the same layout and geometry.  Keyed on the context, not on a plan: a
+ * map has no paths.  occupancy_dev is [n_fields][nz][ny][nx] uint8, x fastest, node-centred, grids of ONE geometry stacked; a
+ * voxel is OCCUPIED when its byte is non-zero (what "unknown" means is the caller's business).  fields_out_dev is
+ * [n_fields][nz][ny][nx] doubles.  With the weights
+ *   wx = hx hx,  wy = hy hy,  wz = (z_scale hz) (z_scale hz)                      computed once on the host
+ * the squared distance between two nodes of one grid with integer offsets di, dj, dk is
+ *   q = (wx (double)(di di) + wy (double)(dj dj)) + wz (double)(dk dk)           in this order, nothing fused
+ * D_occ(v) is the minimum of q over the occupied nodes of v's own grid, +inf where there is none; D_free(v) the same over the
+ * free nodes; grids never see each other.  With rt(D) = min(sqrt(D), max_distance), sqrt correctly rounded:
+ *   flags = 0                  a free node gets rt(D_occ), an occupied node 0.0
+ *   MRS_TG_FIELD_SIGNED        a free node gets rt(D_occ), an occupied node -rt(D_free)
+ * The result is this definition in every bit, whatever the algorithm (three separable passes with an outward scan per node:
+ * csrc/mrs_tg_edt.hpp holds the argument).  z_scale is the weight on the vertical separation of the clearance steps.
+ * max_distance is positive and may be +inf.  THE TRAP: with +inf an all-free or all-occupied grid yields +-inf voxels, and
+ * lerp(inf, inf, t) is NaN in mrs_tg_plan_field_clearance; a caller who looks such a field up passes a finite cap (which also
+ * bounds the scan, and so the cost, on a sparse map).  The origin plays no part in the values and is checked like the rest.
+ * A dim may not exceed MRS_TG_FIELD_MAX_DIM (a line of the y and z passes is staged in LDS).  The passes run in place in
+ * fields_out_dev: no workspace, signed or not.  No atomics; occupancy_dev is only read; every output element is written; the same input gives the same bits on every call.
+ * Out of scope: the index of the nearest occupied voxel; incremental updates of a changed region; float32 fields; sub-voxel
+ * surfaces; a gradient of anything (occupancy is discrete).
+ * MRS_TG_ERR_INVALID_ARG, with the context's last error set and nothing launched: ctx or geometry NULL; occupancy_dev or
+ * fields_out_dev NULL with voxels to process; a negative n_fields, a dim below 2 or above MRS_TG_FIELD_MAX_DIM, a spacing that
+ * is not finite and positive, an origin that is not finite, n_fields nz ny nx above 2^31 - 1; a z_scale that is not finite and
+ * positive; a max_distance that is NaN or <= 0; unknown flag bits; fields_out_dev not 8-byte aligned or overlapping
+ * occupancy_dev.  n_fields == 0: success, nothing is launched or written.  Device pointers except geometry, asynchronous on
+ * the context's stream. */
+#define MRS_TG_FIELD_SIGNED 1
+#define MRS_TG_FIELD_MAX_DIM 1024
+int mrs_tg_field_from_occupancy(mrs_tg_ctx* ctx, const uint8_t* occupancy_dev, const mrs_tg_field_geometry* geometry,
+                                double z_scale, double max_distance, int32_t flags, double* fields_out_dev);
+
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for
  * it) -- requires mrs_tg_set_profiling(ctx, 1).  kernel_id: 0 block assembly, 1 linear solve, 2 nonlinear outer loop,
@@ -1324,7 +1359,9 @@ int mrs_tg_plan_field_clearance_vjp(mrs_tg_plan* plan, const double* samples_dev
  * (mrs_tg_plan_request_limits), 34 their backward pass (mrs_tg_plan_request_limits_vjp), 35 the mutual clearance
  * (mrs_tg_plan_mutual_clearance), 36 its backward pass (mrs_tg_plan_mutual_clearance_vjp), 37 the clearance from obstacles
  * (mrs_tg_plan_obstacle_clearance), 38 its backward pass (mrs_tg_plan_obstacle_clearance_vjp), 39 the clearance from a
- * distance field (mrs_tg_plan_field_clearance), 40 its backward pass (mrs_tg_plan_field_clearance_vjp): forty-one ids, 0 .. 40.
+ * distance field (mrs_tg_plan_field_clearance), 40 its backward pass (mrs_tg_plan_field_clearance_vjp), 41 the
+ * distance field from an occupancy grid (mrs_tg_field_from_occupancy, timed from its first launch to its last): forty-two ids,
+ * 0 .. 41.
  * Blocks until that launch has finished. */
 int mrs_tg_set_profiling(mrs_tg_ctx* ctx, int enabled); /* switching it on starts a new series */
 int mrs_tg_last_kernel_ms(mrs_tg_ctx* ctx, int kernel_id, float* ms_out);

@@ -58,6 +58,7 @@ KERNEL_REQUEST_VERTICES, KERNEL_REQUEST_VERTICES_VJP, KERNEL_REQUEST_LIMITS, KER
 KERNEL_MUTUAL_CLEARANCE, KERNEL_MUTUAL_CLEARANCE_VJP = 35, 36
 KERNEL_OBSTACLE_CLEARANCE, KERNEL_OBSTACLE_CLEARANCE_VJP = 37, 38
 KERNEL_FIELD_CLEARANCE, KERNEL_FIELD_CLEARANCE_VJP = 39, 40
+KERNEL_FIELD_FROM_OCCUPANCY = 41   # edt_x_kernel's start to edt_z_kernel's end
 
 
 class MrsTgError(RuntimeError):
@@ -135,6 +136,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_plan_mutual_clearance", "mrs_tg_plan_mutual_clearance_vjp",
     "mrs_tg_plan_obstacle_clearance", "mrs_tg_plan_obstacle_clearance_vjp",
     "mrs_tg_plan_field_clearance", "mrs_tg_plan_field_clearance_vjp",
+    "mrs_tg_field_from_occupancy",
 ]
 
 _lib = None
@@ -303,6 +305,8 @@ def load_library():
     L.mrs_tg_plan_field_clearance.argtypes = [vp, dp, ip, C.c_int32, dp, gp, ip, ip, C.c_double, dp, ip, dp, dp, ip]
     L.mrs_tg_plan_field_clearance_vjp.restype = C.c_int
     L.mrs_tg_plan_field_clearance_vjp.argtypes = [vp, dp, ip, C.c_int32, dp, gp, ip, ip, ip, dp, dp]
+    L.mrs_tg_field_from_occupancy.restype = C.c_int
+    L.mrs_tg_field_from_occupancy.argtypes = [vp, vp, gp, C.c_double, C.c_double, C.c_int32, dp]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -369,6 +373,8 @@ CAP_REQUEST = 32768   # MRS_TG_CAP_REQUEST: Plan.request_vertices, Plan.request_
 CAP_MUTUAL_CLEARANCE = 65536   # MRS_TG_CAP_MUTUAL_CLEARANCE: Plan.mutual_clearance (the nearest other path of a row's group at the same step), Plan.mutual_clearance_vjp
 CAP_OBSTACLE_CLEARANCE = 131072   # MRS_TG_CAP_OBSTACLE_CLEARANCE: Plan.obstacle_clearance (the nearest sphere or point of the path's obstacle set, signed), Plan.obstacle_clearance_vjp
 CAP_FIELD_CLEARANCE = 262144   # MRS_TG_CAP_FIELD_CLEARANCE: Plan.field_clearance (the trilinear interpolant of a voxel grid of signed distances, its cell and gradient), Plan.field_clearance_vjp
+CAP_FIELD_FROM_OCCUPANCY = 524288   # MRS_TG_CAP_FIELD_FROM_OCCUPANCY: Context.field_from_occupancy (that grid built on the device from an occupancy grid, an exact Euclidean distance transform)
+FIELD_SIGNED, FIELD_MAX_DIM = 1, 1024   # MRS_TG_FIELD_SIGNED (mrs_tg_field_from_occupancy's flag), MRS_TG_FIELD_MAX_DIM (its largest dim)
 # Plan.request_limits' flags input (MRS_TG_REQ_*) and its branch word (MRS_TG_LIM_*)
 REQ_OVERRIDE, REQ_RELAX_HEADING = 1, 2
 LIM_OVERRIDDEN, LIM_OVERRIDE_REFUSED, LIM_RELAXED, LIM_V_DESCENDING, LIM_A_DESCENDING, LIM_J_DESCENDING, LIM_FALLBACK = 1, 2, 4, 8, 16, 32, 64
@@ -638,6 +644,29 @@ def _check_operand(name, t, dtype, shape, like=None, optional=False):
                                                     list(t.shape)))
 
 
+def check_occupancy_operands(occupancy, geometry, z_scale, max_distance, out=None, device=None):
+    """What Context.field_from_occupancy checks before anything reaches the library, or ValueError; no device is needed to be
+    refused.  The geometry as check_field_geometry checks it against occupancy's shape [n_fields][nz][ny][nx], every dim at
+    most FIELD_MAX_DIM, z_scale finite and positive, max_distance positive (inf: no cap; nan refused); occupancy a contiguous
+    uint8 tensor on the device (`device`: the context's ordinal, None = any), out None or a contiguous float64 tensor of the
+    same shape on the same device."""
+    import torch
+    if not isinstance(occupancy, torch.Tensor):
+        raise ValueError("occupancy must be a tensor")
+    check_field_geometry(occupancy.shape, geometry)
+    if any(n > FIELD_MAX_DIM for n in geometry.dims):
+        raise ValueError("every dim of an occupancy grid is at most %d, not %r" % (FIELD_MAX_DIM, geometry.dims))
+    if not (np.isfinite(z_scale) and z_scale > 0.0):
+        raise ValueError("z_scale must be finite and positive, not %r" % (z_scale,))
+    if not max_distance > 0.0:
+        raise ValueError("max_distance must be positive (inf: no cap), not %r" % (max_distance,))
+    shape = geometry.fields_shape()
+    _check_operand("occupancy", occupancy, torch.uint8, shape)
+    _check_operand("out", out, torch.float64, shape, occupancy, optional=True)
+    if device is not None and occupancy.device.index != device:
+        raise ValueError("occupancy must be on the context's device %d, not %s" % (device, occupancy.device))
+
+
 class Context:
     """One HIP device + stream (mrs_tg_ctx)."""
 
@@ -688,6 +717,27 @@ class Context:
         if n < 0:
             self._check(n, "kernel_ms_history")
         return [buf[i] for i in range(n)]
+
+    def field_from_occupancy(self, occupancy, geometry, z_scale=1.0, max_distance=float("inf"), signed=True, out=None):
+        """mrs_tg_field_from_occupancy: the voxel grid of distances Plan.field_clearance reads, built on the device from an
+        occupancy grid by an exact Euclidean distance transform.  occupancy [n_fields][nz][ny][nx] uint8 on the context's
+        device (non-zero: occupied) with geometry (an api.FieldGeometry, every dim at most FIELD_MAX_DIM; checked: ValueError)
+        -> the float64 tensor of the same shape (out, or a new one): at a free node the distance to the nearest occupied node of
+        its own grid, sqrt((hx^2 di^2 + hy^2 dj^2) + (z_scale hz)^2 dk^2) minimised over the nodes, capped at max_distance; at
+        an occupied node minus the capped distance to the nearest free node (signed) or 0 (signed=False).  The definition's
+        bits, whatever the grid.  THE TRAP of max_distance = inf: an all-free or all-occupied grid
+        yields +-inf voxels and Plan.field_clearance's lerp(inf, inf, t) is NaN -- pass a finite cap to a field that is looked
+        up (it also bounds the cost on a sparse map).  There is no autograd entry: occupancy is discrete, nothing here has a
+        gradient.  Asynchronous on the context's stream; occupancy is never written."""
+        import torch
+        check_occupancy_operands(occupancy, geometry, z_scale, max_distance, out, self.device)
+        if out is None:
+            out = torch.empty(geometry.fields_shape(), dtype=torch.float64, device=occupancy.device)
+        g = geometry.as_struct()
+        self._check(self._L.mrs_tg_field_from_occupancy(self._h, _t_ptr(occupancy), C.byref(g), float(z_scale), float(max_distance),
+                                                        FIELD_SIGNED if signed else 0, _t_ptr(out)),
+                    "mrs_tg_field_from_occupancy")
+        return out
 
     def solve_batch(self, batch: Batch, seg_times=None, out=None, **opts):
         """Host arrays in, host arrays out (mrs_tg_solve_batch).  seg_times None => estimate_times.

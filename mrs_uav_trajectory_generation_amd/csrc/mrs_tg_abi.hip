@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/mrs_tg.h"
+#include "mrs_tg_edt.hpp"
 #include "mrs_tg_fallback.hpp"
 #include "mrs_tg_field.hpp"
 #include "mrs_tg_pathedit.hpp"
@@ -54,7 +55,7 @@ struct mrs_tg_ctx {
   // per-dispatch timing: a ring of event pairs per kernel family, one pair per timed launch (kTimerRing launches can be
   // queued before the oldest is overwritten)
   static constexpr int kTimerRing = 512;
-  static constexpr int kTimedKernels = 41;  // kernel_id 0 .. 40 (mrs_tg_last_kernel_ms)
+  static constexpr int kTimedKernels = 42;  // kernel_id 0 .. 41 (mrs_tg_last_kernel_ms)
   std::vector<hipEvent_t> ev_start[kTimedKernels], ev_stop[kTimedKernels];
   long long ev_count[kTimedKernels] = {};   // timed launches since profiling was switched on
   hipDeviceProp_t prop;
@@ -198,7 +199,8 @@ int mrs_tg_capabilities(void) {
          MRS_TG_CAP_GRADIENT | MRS_TG_CAP_MAXIMA_GRADIENT | MRS_TG_CAP_SAMPLE_GRADIENT | MRS_TG_CAP_EVALUATE | MRS_TG_CAP_DEVIATION |
          MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE | MRS_TG_CAP_BACA | MRS_TG_CAP_FALLBACK_SAMPLE |
          MRS_TG_CAP_PATH_EDIT | MRS_TG_CAP_TRAVEL_HEADING | MRS_TG_CAP_INITIAL_CONDITION | MRS_TG_CAP_REQUEST |
-         MRS_TG_CAP_MUTUAL_CLEARANCE | MRS_TG_CAP_OBSTACLE_CLEARANCE | MRS_TG_CAP_FIELD_CLEARANCE;
+         MRS_TG_CAP_MUTUAL_CLEARANCE | MRS_TG_CAP_OBSTACLE_CLEARANCE | MRS_TG_CAP_FIELD_CLEARANCE |
+         MRS_TG_CAP_FIELD_FROM_OCCUPANCY;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1722,15 +1724,9 @@ int mrs_tg_plan_obstacle_clearance_vjp(mrs_tg_plan* plan, const double* samples,
 
 // ---- clearance from a voxel distance field as a plan step (mrs_tg_field.hip) ---------------------------------------------------------
 
-// what the two field calls check before any launch; fills the kernels' geometry
-static int field_clearance_arguments(mrs_tg_ctx* ctx, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
-                                     const double* fields, const mrs_tg_field_geometry* geometry, const int32_t* path_field,
-                                     const int32_t* status, mrs_tg::fldq::Geometry* out) {
-  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
-  if (!n_samples || !geometry || (sample_capacity > 0 && !samples))
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev and geometry are required");
+// what every call that takes a mrs_tg_field_geometry (not NULL) refuses in it; the number of voxels of the whole array
+static int field_geometry_voxels(mrs_tg_ctx* ctx, const mrs_tg_field_geometry* geometry, long long* voxels_out) {
   if (geometry->n_fields < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_fields %d is negative", geometry->n_fields);
-  if (geometry->n_fields > 0 && !fields) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "fields_dev is NULL with %d fields", geometry->n_fields);
   long long voxels = geometry->n_fields;
   for (int a = 0; a < 3; ++a) {
     if (geometry->dims[a] < 2) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "dims[%d] = %d is below 2", a, geometry->dims[a]);
@@ -1742,6 +1738,20 @@ static int field_clearance_arguments(mrs_tg_ctx* ctx, const double* samples, con
     if (voxels > 2147483647LL)
       return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_fields nz ny nx exceeds 2^31 - 1: a cell is an int32");
   }
+  *voxels_out = voxels;
+  return MRS_TG_OK;
+}
+
+// what the two field calls check before any launch; fills the kernels' geometry
+static int field_clearance_arguments(mrs_tg_ctx* ctx, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
+                                     const double* fields, const mrs_tg_field_geometry* geometry, const int32_t* path_field,
+                                     const int32_t* status, mrs_tg::fldq::Geometry* out) {
+  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
+  if (!n_samples || !geometry || (sample_capacity > 0 && !samples))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev and geometry are required");
+  long long voxels = 0;
+  if (const int rc = field_geometry_voxels(ctx, geometry, &voxels); rc != MRS_TG_OK) return rc;
+  if (geometry->n_fields > 0 && !fields) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "fields_dev is NULL with %d fields", geometry->n_fields);
   if ((((uintptr_t)samples) & 15u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev is not 16-byte aligned");
   if ((((uintptr_t)fields) & 7u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "fields_dev is not 8-byte aligned");
   if ((((uintptr_t)n_samples | (uintptr_t)path_field | (uintptr_t)status) & 3u) != 0)
@@ -1809,6 +1819,40 @@ int mrs_tg_plan_field_clearance_vjp(mrs_tg_plan* plan, const double* samples, co
   ProfileScope ps(ctx, 40);
   HIP_TRY(ctx, mrs_tg::launch_field_clearance_vjp(plan->view.n_paths, samples, n_samples, sample_capacity, fields, G, path_field,
                                                   status, cell, grad_clearance, grad_samples_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+// ---- the distance field from an occupancy grid (mrs_tg_edt.hip) -----------------------------------------------------------------------
+
+int mrs_tg_field_from_occupancy(mrs_tg_ctx* ctx, const uint8_t* occupancy, const mrs_tg_field_geometry* geometry, double z_scale,
+                                double max_distance, int32_t flags, double* fields_out) {
+  static_assert(MRS_TG_FIELD_SIGNED == mrs_tg::edtq::kSigned && MRS_TG_FIELD_MAX_DIM == mrs_tg::edtq::kMaxDim, "the header's");
+  if (!ctx) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "ctx is NULL");
+  if (!geometry) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "geometry is NULL");
+  long long voxels = 0;
+  if (const int rc = field_geometry_voxels(ctx, geometry, &voxels); rc != MRS_TG_OK) return rc;
+  for (int a = 0; a < 3; ++a)
+    if (geometry->dims[a] > MRS_TG_FIELD_MAX_DIM)
+      return fail(ctx, MRS_TG_ERR_INVALID_ARG, "dims[%d] = %d exceeds MRS_TG_FIELD_MAX_DIM = %d (a line is staged in LDS)", a,
+                  geometry->dims[a], MRS_TG_FIELD_MAX_DIM);
+  if (!(std::isfinite(z_scale) && z_scale > 0.0)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "z_scale must be finite and positive");
+  if (!(max_distance > 0.0)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "max_distance must be positive (+inf: no cap)");
+  if ((flags & ~MRS_TG_FIELD_SIGNED) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "unknown flag bits 0x%x", (unsigned)flags);
+  if (voxels > 0 && (!occupancy || !fields_out))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "occupancy_dev and fields_out_dev are required with %lld voxels", voxels);
+  if (((uintptr_t)fields_out & 7u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "fields_out_dev is not 8-byte aligned");
+  const uintptr_t out_lo = (uintptr_t)fields_out, out_hi = out_lo + (size_t)voxels * sizeof(double);
+  if (voxels > 0 && (uintptr_t)occupancy < out_hi && out_lo < (uintptr_t)occupancy + (size_t)voxels)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "fields_out_dev overlaps occupancy_dev");
+  if (voxels == 0) return MRS_TG_OK;
+  const bool is_signed = (flags & MRS_TG_FIELD_SIGNED) != 0;
+  const double h[3] = {geometry->spacing[0], geometry->spacing[1], geometry->spacing[2]};
+  const int dims[3] = {geometry->dims[0], geometry->dims[1], geometry->dims[2]};
+  const mrs_tg::edtq::Weights W = mrs_tg::edtq::weights(h, z_scale);
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 41);
+  HIP_TRY(ctx, mrs_tg::launch_field_from_occupancy(occupancy, dims, geometry->n_fields, W, mrs_tg::edtq::saturation(max_distance),
+                                                   max_distance, is_signed, fields_out, ctx->stream));
   return MRS_TG_OK;
 }
 

@@ -32,9 +32,9 @@
 // (cell_of_path) -- none of which dereferences a voxel.  A cell that passes has all eight corners inside the path's own grid.
 //
 // Out of scope.  float32 fields.  A gradient with respect to the field (a static map).  No gradient flows through the choice
-// of the cell.  Interpolation smoother than trilinear (the gradient jumps across cell faces).  A device kernel that builds the
-// field from an occupancy grid: the recipe from a list of obstacles covers static maps.  Splitting one
-// path over several workgroups.
+// of the cell.  Interpolation smoother than trilinear (the gradient jumps across cell faces).  Splitting one path over several
+// workgroups.  (Building the field is not this file's business: mrs_tg_edt.hpp does it from an occupancy grid, the recipe of
+// DESIGN.md section 11k from a list of obstacles.)
 #pragma once
 
 #include "mrs_tg_clearance.hpp"

@@ -23,6 +23,9 @@ struct ThinOptions;  // mrs_tg_pathedit.hpp
 namespace fldq {
 struct Geometry;  // mrs_tg_field.hpp
 }
+namespace edtq {
+struct Weights;  // mrs_tg_edt.hpp
+}
 
 // Per-dispatch timing (mrs_tg_set_profiling): the next launch of the kernel family a ProfileScope names carries these
 // events on the launch itself (hipExtLaunchKernelGGL), so their difference is the dispatch's own start-to-end time.
@@ -387,6 +390,14 @@ hipError_t launch_field_clearance_vjp(int n_paths, const double* samples, const 
                                       const double* fields, const fldq::Geometry& geometry, const int32_t* path_field,
                                       const int32_t* status, const int32_t* cell, const double* grad_clearance,
                                       double* grad_samples, hipStream_t stream);
+// mrs_tg_field_from_occupancy (mrs_tg_edt.hip, mrs_tg_edt.hpp): occupancy [n_fields][nz][ny][nx] bytes (non-zero: occupied) ->
+// fields [n_fields][nz][ny][nx] doubles, the exact Euclidean distance to the nearest occupied node with the weights W, capped at
+// max_distance (limit: edtq::saturation(max_distance)); is_signed: minus the distance to the nearest free node at the occupied
+// ones.  dims = nx, ny, nz, each in [2, edtq::kMaxDim].  Three launches (edt_x_kernel, edt_y_kernel, edt_z_kernel), none for
+// n_fields == 0; in place in fields, no workspace, no atomics; timed from the first launch's start to the last one's end as the
+// kernel family of the pending ProfileScope
+hipError_t launch_field_from_occupancy(const uint8_t* occupancy, const int (&dims)[3], int n_fields, const edtq::Weights& W,
+                                       double limit, double max_distance, bool is_signed, double* fields, hipStream_t stream);
 // What the rows kernel can do around its solve for the same path, in the same launch:
 //   before: the feasibility scaling of the segment times (scaleSegmentTimesWithViolation's T_i <- s_i T_i from the
 //           per-segment maxima, written back to seg_times) -- the last stage before the final solve of the Mellinger pipeline;
