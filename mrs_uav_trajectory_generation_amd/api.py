@@ -549,35 +549,30 @@ def _t_ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _check_offsets(offsets, name, end, end_name):
+    """host offsets as a contiguous int32 array, or ValueError: they start at 0, do not decrease and end at `end`"""
+    try:
+        raw = np.asarray(offsets)
+    except Exception as e:
+        raise ValueError("%s is not an array of integers: %s" % (name, e))
+    if raw.ndim != 1 or raw.size < 1 or raw.dtype.kind not in "iu":
+        raise ValueError("%s must be a one-dimensional array of at least one integer" % name)
+    g = raw.astype(np.int64)
+    if g[0] != 0 or g[-1] != int(end) or np.any(np.diff(g) < 0):
+        raise ValueError("%s must start at 0, not decrease and end at %s = %d (got %s)" % (name, end_name, end, g.tolist()))
+    return np.ascontiguousarray(g, dtype=np.int32)
+
+
 def check_group_offsets(group_offsets, n_paths):
     """Host group offsets of Plan.mutual_clearance as a contiguous int32 array [n_groups + 1], or ValueError: they start at 0,
     do not decrease and end at n_paths (a group may be empty).  No device is needed."""
-    try:
-        raw = np.asarray(group_offsets)
-    except Exception as e:
-        raise ValueError("group_offsets is not an array of integers: %s" % e)
-    if raw.ndim != 1 or raw.size < 1 or raw.dtype.kind not in "iu":
-        raise ValueError("group_offsets must be a one-dimensional array of at least one integer")
-    g = raw.astype(np.int64)
-    if g[0] != 0 or g[-1] != int(n_paths) or np.any(np.diff(g) < 0):
-        raise ValueError("group_offsets must start at 0, not decrease and end at n_paths = %d (got %s)" % (n_paths, g.tolist()))
-    return np.ascontiguousarray(g, dtype=np.int32)
+    return _check_offsets(group_offsets, "group_offsets", n_paths, "n_paths")
 
 
 def check_set_offsets(set_offsets, n_obstacles):
     """Host set offsets of Plan.obstacle_clearance as a contiguous int32 array [n_sets + 1], or ValueError: they start at 0, do
     not decrease and end at n_obstacles (a set may be empty).  No device is needed."""
-    try:
-        raw = np.asarray(set_offsets)
-    except Exception as e:
-        raise ValueError("set_offsets is not an array of integers: %s" % e)
-    if raw.ndim != 1 or raw.size < 1 or raw.dtype.kind not in "iu":
-        raise ValueError("set_offsets must be a one-dimensional array of at least one integer")
-    g = raw.astype(np.int64)
-    if g[0] != 0 or g[-1] != int(n_obstacles) or np.any(np.diff(g) < 0):
-        raise ValueError("set_offsets must start at 0, not decrease and end at n_obstacles = %d (got %s)"
-                         % (n_obstacles, g.tolist()))
-    return np.ascontiguousarray(g, dtype=np.int32)
+    return _check_offsets(set_offsets, "set_offsets", n_obstacles, "n_obstacles")
 
 
 class FieldGeometry:
@@ -1156,21 +1151,26 @@ class Plan:
                                                                _t_ptr(grad_deviation), _t_ptr(grad_samples),
                                                                _t_ptr(grad_waypoints)), "mrs_tg_plan_path_deviation_vjp")
 
-    def _group_offsets_dev(self, group_offsets, like):
-        """group_offsets as mrs_tg_plan_mutual_clearance takes them: a device int32 tensor is the caller's statement and passes
-        as it is; a host sequence or array is checked (check_group_offsets: ValueError) and uploaded to `like`'s device -- a
+    @staticmethod
+    def _offsets_dev(offsets, name, count_name, end, end_name, beside):
+        """Offsets as a clearance step takes them: a device int32 tensor on `beside`'s device is the caller's statement and
+        passes as it is; a host sequence or array is checked (_check_offsets: ValueError) and uploaded to that device -- a
         blocking copy, so a caller in a loop keeps the tensor this returns"""
         import torch
-        if isinstance(group_offsets, torch.Tensor) and group_offsets.is_cuda:
-            if group_offsets.dtype != torch.int32 or group_offsets.dim() != 1 or group_offsets.numel() < 1 or \
-                    not group_offsets.is_contiguous():
-                raise ValueError("group_offsets on the device must be a contiguous int32 tensor [n_groups + 1]")
-            return group_offsets
-        if isinstance(group_offsets, torch.Tensor):
-            group_offsets = group_offsets.numpy()
-        g = torch.from_numpy(check_group_offsets(group_offsets, self.n_paths)).to(like.device)
-        torch.cuda.current_stream(like.device).synchronize()
+        if isinstance(offsets, torch.Tensor) and offsets.is_cuda:
+            if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 1 or not offsets.is_contiguous() or \
+                    offsets.device != beside.device:
+                raise ValueError("%s on the device must be a contiguous int32 tensor [%s + 1] on the device of its operands"
+                                 % (name, count_name))
+            return offsets
+        if isinstance(offsets, torch.Tensor):
+            offsets = offsets.numpy()
+        g = torch.from_numpy(_check_offsets(offsets, name, end, end_name)).to(beside.device)
+        torch.cuda.current_stream(beside.device).synchronize()
         return g
+
+    def _group_offsets_dev(self, group_offsets, like):
+        return self._offsets_dev(group_offsets, "group_offsets", "n_groups", self.n_paths, "n_paths", like)
 
     def mutual_clearance(self, samples, n_samples, group_offsets, first_step=None, status=None, z_scale=1.0, clearance=None,
                          partner=None, min_clearance=None, argmin=None):
@@ -1200,20 +1200,7 @@ class Plan:
                         "mrs_tg_plan_mutual_clearance_vjp")
 
     def _set_offsets_dev(self, set_offsets, obstacles):
-        """set_offsets as mrs_tg_plan_obstacle_clearance takes them: a device int32 tensor is the caller's statement and passes
-        as it is; a host sequence or array is checked (check_set_offsets: ValueError) and uploaded to the obstacles' device -- a
-        blocking copy, so a caller in a loop keeps the tensor this returns"""
-        import torch
-        if isinstance(set_offsets, torch.Tensor) and set_offsets.is_cuda:
-            if set_offsets.dtype != torch.int32 or set_offsets.dim() != 1 or set_offsets.numel() < 1 or \
-                    not set_offsets.is_contiguous() or set_offsets.device != obstacles.device:
-                raise ValueError("set_offsets on the device must be a contiguous int32 tensor [n_sets + 1] beside the obstacles")
-            return set_offsets
-        if isinstance(set_offsets, torch.Tensor):
-            set_offsets = set_offsets.numpy()
-        g = torch.from_numpy(check_set_offsets(set_offsets, int(obstacles.shape[0]))).to(obstacles.device)
-        torch.cuda.current_stream(obstacles.device).synchronize()
-        return g
+        return self._offsets_dev(set_offsets, "set_offsets", "n_sets", int(obstacles.shape[0]), "n_obstacles", obstacles)
 
     def _obstacle_operands(self, samples, n_samples, obstacles, set_offsets, path_set, status):
         """the operand checks the two obstacle calls share -> (set_offsets on the device, capacity)"""

@@ -341,14 +341,36 @@ def evaluate(plan, coeffs, seg_times, query_times, n_orders=5, status=None):
     return _Evaluate.apply(plan, coeffs, seg_times, query_times, int(n_orders), status)
 
 
+def _f64(t):
+    return t.detach().to(torch.float64).contiguous()
+
+
+def _i32(t):
+    return t.detach().to(torch.int32).contiguous()
+
+
+def _rows(plan, samples):
+    """samples detached as a contiguous float64 tensor [n_paths][capacity][4], or ValueError"""
+    s = _f64(samples)
+    if s.dim() != 3 or s.shape[0] != plan.n_paths or s.shape[2] != api.N_DIM:
+        raise ValueError("samples must be [n_paths][capacity][4]")
+    return s
+
+
+def _rows_and_counts(plan, samples, n_samples):
+    """... and n_samples as a contiguous int32 tensor [n_paths]"""
+    s, n = _rows(plan, samples), _i32(n_samples)
+    if n.dim() != 1 or n.shape[0] != plan.n_paths:
+        raise ValueError("n_samples must be [n_paths]")
+    return s, n
+
+
 class _PathDeviation(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, samples, n_samples, waypoints, first_segment, status):
-        s = samples.detach().to(torch.float64).contiguous()
         w = waypoints.detach().to(torch.float64).contiguous()
         n = n_samples.detach().to(torch.int32).contiguous()
-        if s.dim() != 3 or s.shape[0] != plan.n_paths or s.shape[2] != api.N_DIM:
-            raise ValueError("samples must be [n_paths][capacity][4]")
+        s = _rows(plan, samples)
         if w.dim() != 2 or w.shape[0] != plan.n_segments + plan.n_paths or w.shape[1] != api.N_DIM:
             raise ValueError("waypoints must be [sum V][4]")
         st = None if status is None else status.detach().to(torch.int32).contiguous()
@@ -393,11 +415,9 @@ def path_deviation(plan, samples, n_samples, waypoints, first_segment=True, stat
 class _WaypointPassage(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, samples, n_samples, waypoints, wp_offsets, status):
-        s = samples.detach().to(torch.float64).contiguous()
         w = waypoints.detach().to(torch.float64).contiguous()
         n = n_samples.detach().to(torch.int32).contiguous()
-        if s.dim() != 3 or s.shape[0] != plan.n_paths or s.shape[2] != api.N_DIM:
-            raise ValueError("samples must be [n_paths][capacity][4]")
+        s = _rows(plan, samples)
         if w.dim() != 2 or w.shape[1] != api.N_DIM:
             raise ValueError("waypoints must be [sum W][4]")
         off = None
@@ -637,12 +657,7 @@ def fallback_trajectory(plan, waypoints, limits, sampling_dt, sample_capacity, s
 class _TravelHeading(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, samples, n_samples, status, min_step):
-        s = samples.detach().to(torch.float64).contiguous()
-        n = n_samples.detach().to(torch.int32).contiguous()
-        if s.dim() != 3 or s.shape[0] != plan.n_paths or s.shape[2] != api.N_DIM:
-            raise ValueError("samples must be [n_paths][capacity][4]")
-        if n.dim() != 1 or n.shape[0] != plan.n_paths:
-            raise ValueError("n_samples must be [n_paths]")
+        s, n = _rows_and_counts(plan, samples, n_samples)
         st = None if status is None else status.detach().to(torch.int32).contiguous()
         # (the kernel writes the rows a live path has; the rows behind them and the rows of a path with status <= 0 stay zero)
         out = torch.zeros_like(s)
@@ -682,12 +697,7 @@ def travel_heading(plan, samples, n_samples, status=None, min_step=0.05):
 class _MutualClearance(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, samples, n_samples, group_offsets, first_step, status, z_scale):
-        s = samples.detach().to(torch.float64).contiguous()
-        n = n_samples.detach().to(torch.int32).contiguous()
-        if s.dim() != 3 or s.shape[0] != plan.n_paths or s.shape[2] != api.N_DIM:
-            raise ValueError("samples must be [n_paths][capacity][4]")
-        if n.dim() != 1 or n.shape[0] != plan.n_paths:
-            raise ValueError("n_samples must be [n_paths]")
+        s, n = _rows_and_counts(plan, samples, n_samples)
         fs = None if first_step is None else first_step.detach().to(torch.int32).contiguous()
         if fs is not None and (fs.dim() != 1 or fs.shape[0] != plan.n_paths):
             raise ValueError("first_step must be [n_paths]")
@@ -735,12 +745,7 @@ def mutual_clearance(plan, samples, n_samples, group_offsets, first_step=None, s
 class _ObstacleClearance(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, samples, n_samples, obstacles, set_offsets, path_set, status, z_scale):
-        s = samples.detach().to(torch.float64).contiguous()
-        n = n_samples.detach().to(torch.int32).contiguous()
-        if s.dim() != 3 or s.shape[0] != plan.n_paths or s.shape[2] != api.N_DIM:
-            raise ValueError("samples must be [n_paths][capacity][4]")
-        if n.dim() != 1 or n.shape[0] != plan.n_paths:
-            raise ValueError("n_samples must be [n_paths]")
+        s, n = _rows_and_counts(plan, samples, n_samples)
         ob = obstacles.detach().to(torch.float64).contiguous()
         if ob.dim() != 2 or ob.shape[1] != 4:
             raise ValueError("obstacles must be [n_obstacles][4]: x, y, z, radius")
@@ -795,12 +800,7 @@ def obstacle_clearance(plan, samples, n_samples, obstacles, set_offsets=None, pa
 class _FieldClearance(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, samples, n_samples, fields, geometry, path_field, status, outside_value):
-        s = samples.detach().to(torch.float64).contiguous()
-        n = n_samples.detach().to(torch.int32).contiguous()
-        if s.dim() != 3 or s.shape[0] != plan.n_paths or s.shape[2] != api.N_DIM:
-            raise ValueError("samples must be [n_paths][capacity][4]")
-        if n.dim() != 1 or n.shape[0] != plan.n_paths:
-            raise ValueError("n_samples must be [n_paths]")
+        s, n = _rows_and_counts(plan, samples, n_samples)
         fl = fields.detach().to(torch.float64).contiguous()
         if fl.dim() != 4:
             raise ValueError("fields must be [n_fields][nz][ny][nx]")
@@ -860,14 +860,6 @@ def field_clearance(plan, samples, n_samples, fields, geometry, path_field=None,
     if isinstance(fields, torch.Tensor) and fields.requires_grad:
         raise ValueError("field_clearance has no gradient with respect to the field (a static map): pass fields.detach()")
     return _FieldClearance.apply(plan, samples, n_samples, fields, geometry, path_field, status, outside_value)
-
-
-def _f64(t):
-    return t.detach().to(torch.float64).contiguous()
-
-
-def _i32(t):
-    return t.detach().to(torch.int32).contiguous()
 
 
 class _InitialCondition(torch.autograd.Function):

@@ -1079,14 +1079,21 @@ int mrs_tg_plan_evaluate_vjp(mrs_tg_plan* plan, const double* coeffs, const doub
                                                           status, grad_coeffs, grad_times, grad_query_times, ctx->stream));
 }
 
+// the sample rows of a plan step: a capacity, the counts, the rows where there are any
+static int sample_rows_present(mrs_tg_ctx* ctx, const double* samples, const int32_t* n_samples, int32_t capacity) {
+  if (capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", capacity);
+  if (!n_samples) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_samples_dev is NULL");
+  if (capacity > 0 && !samples) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev is NULL with rows");
+  return MRS_TG_OK;
+}
+
 int mrs_tg_plan_path_deviation(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
                                const double* waypoints, int32_t first_segment, const int32_t* status, double* deviation,
                                int32_t* cursor, double* max_deviation, int32_t* argmax, double* segment_max) {
   if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
   mrs_tg_ctx* ctx = plan->ctx;
-  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
-  if (!n_samples || !waypoints || (sample_capacity > 0 && !samples))
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev and waypoints_dev are required");
+  if (const int rc = sample_rows_present(ctx, samples, n_samples, sample_capacity); rc != MRS_TG_OK) return rc;
+  if (!waypoints) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "waypoints_dev is NULL");
   if (!deviation && !cursor && !max_deviation && !argmax && !segment_max)
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "every output of mrs_tg_plan_path_deviation is NULL");
   HIP_TRY(ctx, use_device(ctx->device));
@@ -1102,9 +1109,9 @@ int mrs_tg_plan_path_deviation_vjp(mrs_tg_plan* plan, const double* samples, con
                                    double* grad_samples, double* grad_waypoints) {
   if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
   mrs_tg_ctx* ctx = plan->ctx;
-  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
-  if (!n_samples || !waypoints || (sample_capacity > 0 && (!samples || !grad_deviation)))
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev, waypoints_dev and grad_deviation_dev are required");
+  if (const int rc = sample_rows_present(ctx, samples, n_samples, sample_capacity); rc != MRS_TG_OK) return rc;
+  if (!waypoints || (sample_capacity > 0 && !grad_deviation))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "waypoints_dev and grad_deviation_dev are required");
   if (!grad_samples && !grad_waypoints)
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_samples_out and grad_waypoints_out are both NULL");
   HIP_TRY(ctx, use_device(ctx->device));
@@ -1146,9 +1153,8 @@ int mrs_tg_plan_waypoint_passage(mrs_tg_plan* plan, const double* samples, const
                                  int32_t* count, double* miss, double* fraction) {
   if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
   mrs_tg_ctx* ctx = plan->ctx;
-  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
-  if (!n_samples || !waypoints || (sample_capacity > 0 && !samples))
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev and waypoints_dev are required");
+  if (const int rc = sample_rows_present(ctx, samples, n_samples, sample_capacity); rc != MRS_TG_OK) return rc;
+  if (!waypoints) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "waypoints_dev is NULL");
   if (!index && !count && !miss && !fraction)
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "every output of mrs_tg_plan_waypoint_passage is NULL");
   HIP_TRY(ctx, use_device(ctx->device));
@@ -1164,9 +1170,8 @@ int mrs_tg_plan_waypoint_passage_vjp(mrs_tg_plan* plan, const double* samples, c
                                      double* grad_waypoints) {
   if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
   mrs_tg_ctx* ctx = plan->ctx;
-  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
-  if (!n_samples || !waypoints || (sample_capacity > 0 && !samples))
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev and waypoints_dev are required");
+  if (const int rc = sample_rows_present(ctx, samples, n_samples, sample_capacity); rc != MRS_TG_OK) return rc;
+  if (!waypoints) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "waypoints_dev is NULL");
   if (!grad_samples && !grad_waypoints)
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_samples_out and grad_waypoints_out are both NULL");
   HIP_TRY(ctx, use_device(ctx->device));
@@ -1335,21 +1340,12 @@ int mrs_tg_plan_path_edit_vjp(mrs_tg_plan* plan, const int32_t* vertex_offsets, 
   return MRS_TG_OK;
 }
 
-// what the two heading calls check before any launch
-static int travel_heading_arguments(mrs_tg_ctx* ctx, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
-                                    double min_step) {
-  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
-  if (!n_samples || (sample_capacity > 0 && !samples))
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev and n_samples_dev are required");
-  if (!std::isfinite(min_step)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "min_step must be finite");
-  return MRS_TG_OK;
-}
-
 int mrs_tg_plan_travel_heading(mrs_tg_plan* plan, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
                                const int32_t* status, double min_step, double* samples_out, int32_t* source_out) {
   if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
   mrs_tg_ctx* ctx = plan->ctx;
-  if (const int rc = travel_heading_arguments(ctx, samples, n_samples, sample_capacity, min_step); rc != MRS_TG_OK) return rc;
+  if (const int rc = sample_rows_present(ctx, samples, n_samples, sample_capacity); rc != MRS_TG_OK) return rc;
+  if (!std::isfinite(min_step)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "min_step must be finite");
   if (sample_capacity > 0 && !samples_out) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_out_dev is required");
   HIP_TRY(ctx, use_device(ctx->device));
   ProfileScope ps(ctx, 23);
@@ -1362,7 +1358,8 @@ int mrs_tg_plan_travel_heading_vjp(mrs_tg_plan* plan, const double* samples, con
                                    const int32_t* status, double min_step, const double* grad_out, double* grad_samples) {
   if (!plan) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "plan is NULL");
   mrs_tg_ctx* ctx = plan->ctx;
-  if (const int rc = travel_heading_arguments(ctx, samples, n_samples, sample_capacity, min_step); rc != MRS_TG_OK) return rc;
+  if (const int rc = sample_rows_present(ctx, samples, n_samples, sample_capacity); rc != MRS_TG_OK) return rc;
+  if (!std::isfinite(min_step)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "min_step must be finite");
   if (sample_capacity > 0 && (!grad_out || !grad_samples))
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_out_dev and grad_samples_out_dev are required");
   HIP_TRY(ctx, use_device(ctx->device));
@@ -1593,19 +1590,34 @@ int mrs_tg_plan_request_limits_vjp(mrs_tg_plan* plan, const int32_t* branch, int
   return MRS_TG_OK;
 }
 
-// ---- mutual clearance within groups of paths as a plan step (mrs_tg_clearance.hip) ----------------------------------------------
+// ---- the clearance steps: mutual (mrs_tg_clearance.hip), from obstacles (mrs_tg_obstacle.hip), from a field (mrs_tg_field.hip) ----
 
-// what the two clearance calls check before any launch
+// ... and their alignment, which the clearance steps ask for (the older steps never did, and do not start now)
+static int sample_rows_arguments(mrs_tg_ctx* ctx, const double* samples, const int32_t* n_samples, int32_t capacity) {
+  if (const int rc = sample_rows_present(ctx, samples, n_samples, capacity); rc != MRS_TG_OK) return rc;
+  if (((uintptr_t)samples & 15u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev is not 16-byte aligned");
+  if (((uintptr_t)n_samples & 3u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_samples_dev is not 4-byte aligned");
+  return MRS_TG_OK;
+}
+
+// the backward passes' operands: the forward's tag array (named in the messages), the upstream and the output
+static int backward_operands(mrs_tg_ctx* ctx, bool required, const int32_t* tag, const char* tag_name, const double* grad_clearance,
+                             const double* grad_samples_out) {
+  if (required && (!tag || !grad_clearance || !grad_samples_out))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "%s, grad_clearance_dev and grad_samples_out_dev are required", tag_name);
+  if (((uintptr_t)grad_samples_out & 15u) == 0 && ((uintptr_t)grad_clearance & 7u) == 0 && ((uintptr_t)tag & 3u) == 0) return MRS_TG_OK;
+  return fail(ctx, MRS_TG_ERR_INVALID_ARG, "grad_samples_out_dev (16 bytes), grad_clearance_dev or %s is not aligned", tag_name);
+}
+
+// what the two mutual clearance calls check before any launch
 static int mutual_clearance_arguments(mrs_tg_ctx* ctx, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
                                       const int32_t* group_offsets, int32_t n_groups, const int32_t* first_step,
                                       const int32_t* status, double z_scale) {
-  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
+  if (const int rc = sample_rows_arguments(ctx, samples, n_samples, sample_capacity); rc != MRS_TG_OK) return rc;
   if (n_groups < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_groups %d is negative", n_groups);
-  if (!n_samples || !group_offsets || (sample_capacity > 0 && !samples))
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev and group_offsets_dev are required");
+  if (!group_offsets) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "group_offsets_dev is NULL");
   if (!(std::isfinite(z_scale) && z_scale > 0.0)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "z_scale must be finite and positive");
-  if (((uintptr_t)samples & 15u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev is not 16-byte aligned");
-  if ((((uintptr_t)n_samples | (uintptr_t)group_offsets | (uintptr_t)first_step | (uintptr_t)status) & 3u) != 0)
+  if ((((uintptr_t)group_offsets | (uintptr_t)first_step | (uintptr_t)status) & 3u) != 0)
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "an int32 array is not 4-byte aligned");
   return MRS_TG_OK;
 }
@@ -1620,6 +1632,7 @@ int mrs_tg_plan_mutual_clearance(mrs_tg_plan* plan, const double* samples, const
                                                 status, z_scale);
       rc != MRS_TG_OK)
     return rc;
+  // (at capacity 0 this step alone takes a forward without outputs and a backward without operands; the other two refuse both)
   if (sample_capacity > 0 && !clearance_out && !partner_out && !min_clearance_out && !argmin_out)
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "every output of mrs_tg_plan_mutual_clearance is NULL");
   if ((((uintptr_t)clearance_out | (uintptr_t)min_clearance_out) & 7u) != 0 ||
@@ -1643,11 +1656,9 @@ int mrs_tg_plan_mutual_clearance_vjp(mrs_tg_plan* plan, const double* samples, c
                                                 status, z_scale);
       rc != MRS_TG_OK)
     return rc;
-  if (sample_capacity > 0 && (!partner || !grad_clearance || !grad_samples_out))
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "partner_dev, grad_clearance_dev and grad_samples_out_dev are required");
-  if (((uintptr_t)grad_samples_out & 15u) != 0 || ((uintptr_t)grad_clearance & 7u) != 0 || ((uintptr_t)partner & 3u) != 0)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
-                "grad_samples_out_dev is not 16-byte aligned, or grad_clearance_dev or partner_dev not to its element");
+  if (const int rc = backward_operands(ctx, sample_capacity > 0, partner, "partner_dev", grad_clearance, grad_samples_out);
+      rc != MRS_TG_OK)
+    return rc;
   HIP_TRY(ctx, use_device(ctx->device));
   ProfileScope ps(ctx, 36);
   HIP_TRY(ctx, mrs_tg::launch_mutual_clearance_vjp(plan->view.n_paths, samples, n_samples, sample_capacity, group_offsets, n_groups,
@@ -1656,22 +1667,18 @@ int mrs_tg_plan_mutual_clearance_vjp(mrs_tg_plan* plan, const double* samples, c
   return MRS_TG_OK;
 }
 
-// ---- clearance from static obstacles as a plan step (mrs_tg_obstacle.hip) --------------------------------------------------------
-
 // what the two obstacle calls check before any launch
 static int obstacle_clearance_arguments(mrs_tg_ctx* ctx, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
                                         const double* obstacles, int32_t n_obstacles, const int32_t* set_offsets, int32_t n_sets,
                                         const int32_t* path_set, const int32_t* status, double z_scale) {
-  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
+  if (const int rc = sample_rows_arguments(ctx, samples, n_samples, sample_capacity); rc != MRS_TG_OK) return rc;
   if (n_obstacles < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_obstacles %d is negative", n_obstacles);
   if (n_sets < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_sets %d is negative", n_sets);
-  if (!n_samples || !set_offsets || (sample_capacity > 0 && !samples))
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev and set_offsets_dev are required");
+  if (!set_offsets) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "set_offsets_dev is NULL");
   if (n_obstacles > 0 && !obstacles) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "obstacles_dev is NULL with %d obstacles", n_obstacles);
   if (!(std::isfinite(z_scale) && z_scale > 0.0)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "z_scale must be finite and positive");
-  if ((((uintptr_t)samples | (uintptr_t)obstacles) & 15u) != 0)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev or obstacles_dev is not 16-byte aligned");
-  if ((((uintptr_t)n_samples | (uintptr_t)set_offsets | (uintptr_t)path_set | (uintptr_t)status) & 3u) != 0)
+  if (((uintptr_t)obstacles & 15u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "obstacles_dev is not 16-byte aligned");
+  if ((((uintptr_t)set_offsets | (uintptr_t)path_set | (uintptr_t)status) & 3u) != 0)
     return fail(ctx, MRS_TG_ERR_INVALID_ARG, "an int32 array is not 4-byte aligned");
   return MRS_TG_OK;
 }
@@ -1709,11 +1716,8 @@ int mrs_tg_plan_obstacle_clearance_vjp(mrs_tg_plan* plan, const double* samples,
                                                   n_sets, path_set, status, z_scale);
       rc != MRS_TG_OK)
     return rc;
-  if (!nearest || !grad_clearance || !grad_samples_out)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "nearest_dev, grad_clearance_dev and grad_samples_out_dev are required");
-  if (((uintptr_t)grad_samples_out & 15u) != 0 || ((uintptr_t)grad_clearance & 7u) != 0 || ((uintptr_t)nearest & 3u) != 0)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
-                "grad_samples_out_dev is not 16-byte aligned, or grad_clearance_dev or nearest_dev not to its element");
+  if (const int rc = backward_operands(ctx, true, nearest, "nearest_dev", grad_clearance, grad_samples_out); rc != MRS_TG_OK)
+    return rc;
   HIP_TRY(ctx, use_device(ctx->device));
   ProfileScope ps(ctx, 38);
   HIP_TRY(ctx, mrs_tg::launch_obstacle_clearance_vjp(plan->view.n_paths, samples, n_samples, sample_capacity, obstacles,
@@ -1721,8 +1725,6 @@ int mrs_tg_plan_obstacle_clearance_vjp(mrs_tg_plan* plan, const double* samples,
                                                      grad_clearance, grad_samples_out, ctx->stream));
   return MRS_TG_OK;
 }
-
-// ---- clearance from a voxel distance field as a plan step (mrs_tg_field.hip) ---------------------------------------------------------
 
 // what every call that takes a mrs_tg_field_geometry (not NULL) refuses in it; the number of voxels of the whole array
 static int field_geometry_voxels(mrs_tg_ctx* ctx, const mrs_tg_field_geometry* geometry, long long* voxels_out) {
@@ -1746,18 +1748,16 @@ static int field_geometry_voxels(mrs_tg_ctx* ctx, const mrs_tg_field_geometry* g
 static int field_clearance_arguments(mrs_tg_ctx* ctx, const double* samples, const int32_t* n_samples, int32_t sample_capacity,
                                      const double* fields, const mrs_tg_field_geometry* geometry, const int32_t* path_field,
                                      const int32_t* status, mrs_tg::fldq::Geometry* out) {
-  if (sample_capacity < 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "sample_capacity %d is negative", sample_capacity);
-  if (!n_samples || !geometry || (sample_capacity > 0 && !samples))
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev, n_samples_dev and geometry are required");
+  if (const int rc = sample_rows_arguments(ctx, samples, n_samples, sample_capacity); rc != MRS_TG_OK) return rc;
+  if (!geometry) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "geometry is NULL");
   long long voxels = 0;
   if (const int rc = field_geometry_voxels(ctx, geometry, &voxels); rc != MRS_TG_OK) return rc;
   if (geometry->n_fields > 0 && !fields) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "fields_dev is NULL with %d fields", geometry->n_fields);
-  if ((((uintptr_t)samples) & 15u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "samples_dev is not 16-byte aligned");
   if ((((uintptr_t)fields) & 7u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "fields_dev is not 8-byte aligned");
-  if ((((uintptr_t)n_samples | (uintptr_t)path_field | (uintptr_t)status) & 3u) != 0)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "an int32 array is not 4-byte aligned");
   for (int a = 0; a < 3; ++a) out->o[a] = geometry->origin[a], out->h[a] = geometry->spacing[a], out->n[a] = geometry->dims[a];
   out->n_fields = geometry->n_fields;
+  if ((((uintptr_t)path_field | (uintptr_t)status) & 3u) != 0)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "an int32 array is not 4-byte aligned");
   return MRS_TG_OK;
 }
 
@@ -1795,11 +1795,7 @@ int mrs_tg_plan_field_clearance_vjp(mrs_tg_plan* plan, const double* samples, co
   if (const int rc = field_clearance_arguments(ctx, samples, n_samples, sample_capacity, fields, geometry, path_field, status, &G);
       rc != MRS_TG_OK)
     return rc;
-  if (!cell || !grad_clearance || !grad_samples_out)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "cell_dev, grad_clearance_dev and grad_samples_out_dev are required");
-  if (((uintptr_t)grad_samples_out & 15u) != 0 || ((uintptr_t)grad_clearance & 7u) != 0 || ((uintptr_t)cell & 3u) != 0)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG,
-                "grad_samples_out_dev is not 16-byte aligned, or grad_clearance_dev or cell_dev not to its element");
+  if (const int rc = backward_operands(ctx, true, cell, "cell_dev", grad_clearance, grad_samples_out); rc != MRS_TG_OK) return rc;
   // the output may not overlap an input: the byte ranges the kernel touches
   const size_t P = (size_t)plan->view.n_paths, rows = P * (size_t)sample_capacity;
   const size_t voxels = (size_t)G.n_fields * (size_t)G.n[2] * (size_t)G.n[1] * (size_t)G.n[0];

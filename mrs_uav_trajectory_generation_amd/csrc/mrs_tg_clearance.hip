@@ -4,9 +4,8 @@
 //   mutual_clearance_kernel      the loop over the group's other paths is the outer loop of a chunk: a neighbour's rows at the
 //                                chunk's steps are consecutive, one 16 + 8 byte load per lane, taken kClrUnroll neighbours at a
 //                                time so that independent loads are in flight; the distances are then taken in increasing path
-//                                index.  Every lane keeps the first smallest of its rows; the path's minimum is combined in the
-//                                order "smaller value, then lower row" by shuffles and, across the wavefronts, through four LDS
-//                                slots -- an order-free combination (clrq::better), so the split changes no bit.
+//                                index.  Every lane keeps the first smallest of its rows; write_path_minimum
+//                                (mrs_tg_pathwave.hpp) combines them into the path's minimum.
 //   mutual_clearance_vjp_kernel  a gather: the lane of row (j, r) takes its own term against its own partner, then walks the
 //                                group in increasing path index and reads the partner entry of each path's row at the same step
 //                                (consecutive int32 across the lanes); the neighbour's row and upstream are loaded only where
@@ -58,8 +57,6 @@ __global__ __launch_bounds__(kClrThreads) void mutual_clearance_kernel(int n_pat
                                                                        int32_t* __restrict__ partner,
                                                                        double* __restrict__ min_clearance,
                                                                        int32_t* __restrict__ argmin) {
-  __shared__ double s_c[kClrWaves];
-  __shared__ int s_row[kClrWaves], s_partner[kClrWaves];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int p = blockIdx.x;
   const PathSpan me = path_span(status, n_samples, first_step, p, capacity);
@@ -103,21 +100,7 @@ __global__ __launch_bounds__(kClrThreads) void mutual_clearance_kernel(int n_pat
     }
     if (m.c < best.c) best.c = m.c, best.index = r, best_partner = m.index;  // (a lane's rows come in increasing order)
   }
-  if (!min_clearance && !argmin) return;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double oc = __shfl_xor(best.c, o);
-    const int orow = __shfl_xor(best.index, o), opartner = __shfl_xor(best_partner, o);
-    if (clrq::better(oc, orow, best.c, best.index)) best.c = oc, best.index = orow, best_partner = opartner;
-  }
-  if (lane == 0) s_c[wave] = best.c, s_row[wave] = best.index, s_partner[wave] = best_partner;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kClrWaves; ++w)
-      if (clrq::better(s_c[w], s_row[w], best.c, best.index)) best.c = s_c[w], best.index = s_row[w], best_partner = s_partner[w];
-    if (min_clearance) min_clearance[p] = best.c;
-    if (argmin) argmin[2 * (size_t)p] = best.index, argmin[2 * (size_t)p + 1] = best_partner;
-  }
+  write_path_minimum<kClrWaves>(best, best_partner, lane, wave, p, min_clearance, argmin);
 }
 
 __global__ __launch_bounds__(kClrThreads) void mutual_clearance_vjp_kernel(int n_paths, const double* __restrict__ samples,

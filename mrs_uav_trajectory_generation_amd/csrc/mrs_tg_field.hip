@@ -9,9 +9,9 @@
 //                               and only then interpolates (fldq::interpolate, and fldq::gradient where the caller wants the
 //                               field's gradient).  A lane whose row is not inside or behind the path's last row loads the
 //                               first cell of the path's grid instead and drops it, so that no branch keeps the loads apart;
-//                               a path without a grid loads nothing.  Every lane keeps the first smallest of its rows; the path's minimum
-//                               is combined in the order "smaller value, then lower row" by shuffles and, across the wavefronts,
-//                               through four LDS slots (clrq::better: an order-free combination, so the split changes no bit).
+//                               a path without a grid loads nothing.  Every lane keeps the first smallest of its rows;
+//                               the path's minimum is combined as write_path_minimum (mrs_tg_pathwave.hpp) does it, by this
+//                               kernel's own copy of those lines (DESIGN.md section 4a has the reason).
 //   field_clearance_vjp_kernel  one lane per output row: the row, its recorded cell and its upstream; the eight corners are
 //                               loaded only where the cell is a low corner of the path's own grid (fldq::row_gradient).
 // Reads only; no atomics, no workspace, no dynamic LDS; every output element written once.  A cell the forward forms lies in
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kFldThreads) void field_clearance_kernel(const doub
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (one value per wavefront: the chunk loop is uniform)
   const int p = blockIdx.x;
   const int n = live_samples(path_live(status, p), n_samples, p, capacity);
-  const int f = fldq::grid_of_path(path_field, p, G.n_fields);
+  const int f =fldq::grid_of_path(path_field, p, G.n_fields);
   const size_t row0 = (size_t)p * (size_t)capacity;
   const double* __restrict__ rows = samples + row0 * 4;
   const int first_cell = f >= 0 ? fldq::encode_cell(G, f, 0, 0, 0) : 0;
@@ -104,6 +104,7 @@ __global__ __launch_bounds__(kFldThreads) void field_clearance_kernel(const doub
       if (c[j] < best.c) best.c = c[j], best.index = r[j], best_cell = cell[j];  // (a lane's rows come in increasing order)
     }
   }
+  // write_path_minimum (mrs_tg_pathwave.hpp), written out: through the function this kernel's time left the parent's spread
   if (!min_clearance && !argmin) return;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {

@@ -11,9 +11,8 @@
 //                                  are formed first; the square roots are taken only where obsq::cannot_win does not rule all of
 //                                  them out for the row -- a wavefront none of whose rows any of them can win on branches round
 //                                  the roots, and the header holds the argument why no output bit depends on it.  Every lane
-//                                  keeps the first smallest of its rows; the path's minimum is combined in the order "smaller
-//                                  value, then lower row" by shuffles and, across the wavefronts, through four LDS slots -- an
-//                                  order-free combination (clrq::better), so the split changes no bit.
+//                                  keeps the first smallest of its rows; write_path_minimum (mrs_tg_pathwave.hpp) combines them
+//                                  into the path's minimum.
 //   obstacle_clearance_vjp_kernel  one lane per output row: the row, its nearest entry and its upstream, one obstacle loaded where
 //                                  the entry names one of the path's own set (obsq::row_gradient).
 // Reads only; no atomics, no workspace, no dynamic LDS; every output element written once.  The set's bounds come clamped from
@@ -59,8 +58,6 @@ __global__ __launch_bounds__(kObsThreads) void obstacle_clearance_kernel(const d
                                                                          int32_t* __restrict__ nearest,
                                                                          double* __restrict__ min_clearance,
                                                                          int32_t* __restrict__ argmin) {
-  __shared__ double s_c[kObsWaves];
-  __shared__ int s_row[kObsWaves], s_nearest[kObsWaves];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (one value per wavefront: the chunk loop is uniform)
   const int p = blockIdx.x;
@@ -123,21 +120,7 @@ __global__ __launch_bounds__(kObsThreads) void obstacle_clearance_kernel(const d
       if (m[j].c < best.c) best.c = m[j].c, best.index = r[j], best_nearest = m[j].index;  // (a lane's rows come in increasing order)
     }
   }
-  if (!min_clearance && !argmin) return;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double oc = __shfl_xor(best.c, o);
-    const int orow = __shfl_xor(best.index, o), onearest = __shfl_xor(best_nearest, o);
-    if (obsq::better(oc, orow, best.c, best.index)) best.c = oc, best.index = orow, best_nearest = onearest;
-  }
-  if (lane == 0) s_c[wave] = best.c, s_row[wave] = best.index, s_nearest[wave] = best_nearest;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kObsWaves; ++w)
-      if (obsq::better(s_c[w], s_row[w], best.c, best.index)) best.c = s_c[w], best.index = s_row[w], best_nearest = s_nearest[w];
-    if (min_clearance) min_clearance[p] = best.c;
-    if (argmin) argmin[2 * (size_t)p] = best.index, argmin[2 * (size_t)p + 1] = best_nearest;
-  }
+  write_path_minimum<kObsWaves>(best, best_nearest, lane, wave, p, min_clearance, argmin);
 }
 
 __global__ __launch_bounds__(kObsThreads) void obstacle_clearance_vjp_kernel(const double* __restrict__ samples,

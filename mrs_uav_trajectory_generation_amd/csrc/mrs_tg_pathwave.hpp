@@ -1,7 +1,10 @@
 // mrs_tg_pathwave.hpp -- what the kernels that give ONE WAVEFRONT ONE PATH share around their own loops (mrs_tg_sample_vjp.hip,
 // mrs_tg_evaluate.hip, mrs_tg_deviation.hip, mrs_tg_passage.hip, mrs_tg_heading.hip, mrs_tg_pathedit.hip, mrs_tg_initial.hip).  Device only; only what they spell the same way AND compile
 // to the same code through a function: the chunk loops and the loops that stage a path into LDS stay written out.
+// The kernels that give ONE WORKGROUP ONE PATH (mrs_tg_clearance.hip, mrs_tg_obstacle.hip, mrs_tg_field.hip) take the row helpers
+// from here too, and the end they share: write_path_minimum.
 #pragma once
+#include "mrs_tg_clearance.hpp"
 #include "mrs_tg_device.hpp"
 
 namespace mrs_tg {
@@ -62,6 +65,34 @@ __device__ __forceinline__ void store_xyz0(double* __restrict__ row, const doubl
   lo.x = v[0], lo.y = v[1], hi.x = v[2], hi.y = 0.0;
   out[0] = lo;
   out[1] = hi;
+}
+
+// The minimum of a path whose rows ONE WORKGROUP of kWaves wavefronts shares: every lane brings the first smallest of its rows as
+// best = (c, row) and tag -- what the step records beside the row: partner, obstacle, cell.  Combined in clrq::better's order
+// "smaller value, then lower row" by shuffles and, across the wavefronts, through kWaves LDS slots; the order is free of how the
+// rows were dealt, so the split changes no bit.  Thread 0 writes min_clearance[p] and argmin[2p], argmin[2p + 1]; nothing where
+// the caller wants neither.  Every thread of the workgroup calls it (one barrier).  `best` whole and by value: the spelling
+// whose code is nearest the kernels' own copies (profiles/clearance_family_isa_identity.txt).
+template <int kWaves>
+__device__ __forceinline__ void write_path_minimum(clrq::Nearest best, int tag, int lane, int wave, int p,
+                                                   double* __restrict__ min_clearance, int32_t* __restrict__ argmin) {
+  __shared__ double s_c[kWaves];
+  __shared__ int s_row[kWaves], s_tag[kWaves];
+  if (!min_clearance && !argmin) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double oc = __shfl_xor(best.c, o);
+    const int orow = __shfl_xor(best.index, o), otag = __shfl_xor(tag, o);
+    if (clrq::better(oc, orow, best.c, best.index)) best.c = oc, best.index = orow, tag = otag;
+  }
+  if (lane == 0) s_c[wave] = best.c, s_row[wave] = best.index, s_tag[wave] = tag;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kWaves; ++w)
+      if (clrq::better(s_c[w], s_row[w], best.c, best.index)) best.c = s_c[w], best.index = s_row[w], tag = s_tag[w];
+    if (min_clearance) min_clearance[p] = best.c;
+    if (argmin) argmin[2 * (size_t)p] = best.index, argmin[2 * (size_t)p + 1] = tag;
+  }
 }
 
 // dL/dT_i = -(s_{i+1} + (s_{i+2} + ...)) of a path from its time sums s_i = s_sum[i * stride] in LDS (sampvjp::time_gradients'

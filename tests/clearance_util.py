@@ -173,10 +173,6 @@ def rotated_case(c):
     return case([c["paths"][q] for q in order], c["groups"][1:] + c["groups"][:1], c["z_scale"]), np.array(order)
 
 
-def live_rows(n_samples, status, capacity):
-    return 0 if status <= 0 else max(min(int(n_samples), int(capacity)), 0)
-
-
 # ---- the restatements ------------------------------------------------------------------------------------------------------------
 
 def mutual_clearance_numpy(arr, second=False):
@@ -321,10 +317,6 @@ def build_harness(tmp_path, sanitize=False):
     return hh.build("clearance_harness.cpp", tmp_path, sanitize=sanitize)
 
 
-def _ints(a):
-    return " ".join(str(int(x)) for x in np.asarray(a).reshape(-1))
-
-
 def run_harness(exe, arr, partner=None):
     """the harness on batch_arrays' dict (any offsets, well-formed or not; partner: the array the backward pass is driven by
     instead of the forward's) -> dict(clearance [P][cap], partner [P][cap], min_clearance [P], argmin [P][2], grad [P][cap][4])"""
@@ -349,15 +341,8 @@ def run_harness(exe, arr, partner=None):
     return out
 
 
-def same_bits(a, b):
-    """bit for bit, a NaN equal to any NaN"""
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    if a.shape != b.shape:
-        return False
-    return bool(np.all((a.view(np.int64) == b.view(np.int64)) | (np.isnan(a) & np.isnan(b))))
+same_bits, live_rows, _ints = hh.same_bits, hh.live_rows, hh.ints
 
 
 def grads_agree(got, want, scale):
-    """|got - want| <= GRAD_RTOL * scale entry by entry (no NaN on either side)"""
-    got, want = np.asarray(got), np.asarray(want)
-    return bool(np.all(np.isfinite(got)) and np.all(np.abs(got - want) <= GRAD_RTOL * scale))
+    return hh.grads_agree(got, want, scale, GRAD_RTOL)

@@ -453,8 +453,7 @@ def build_harness(tmp_path, sanitize=False):
     return hh.build("field_harness.cpp", tmp_path, sanitize=sanitize)
 
 
-def _ints(a):
-    return " ".join(str(int(x)) for x in np.asarray(a).reshape(-1))
+_ints = ou._ints
 
 
 def run_harness(exe, arr, cell=None):

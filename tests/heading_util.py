@@ -186,11 +186,6 @@ def batch_arrays(batch, seed=0):
     return samples, n, status, upstream
 
 
-def live_rows(n_samples, status, capacity):
-    """the rows the stage sees of a path"""
-    return 0 if status <= 0 else max(min(int(n_samples), int(capacity)), 0)
-
-
 # ---- the CPU harness -----------------------------------------------------------------------------------------------------------
 
 def build_harness(tmp_path, sanitize=False):
@@ -218,12 +213,7 @@ def run_harness(exe, batch, min_step=MIN_STEP, seed=0):
     return out
 
 
-def same_bits(a, b):
-    """bit for bit, a NaN equal to any NaN (two libms need not agree on a NaN's payload)"""
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    if a.shape != b.shape:
-        return False
-    return bool(np.all((a.view(np.int64) == b.view(np.int64)) | (np.isnan(a) & np.isnan(b))))
+same_bits, live_rows = hh.same_bits, hh.live_rows   # (a NaN equal to any NaN: two libms need not agree on a NaN's payload)
 
 
 def grads_agree(got, want, scale):

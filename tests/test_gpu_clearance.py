@@ -329,3 +329,40 @@ def test_chain_solve_sample_mutual_clearance_hinge_loss(gpu_ctx):
         assert nf > 0 and nt > 0 and np.all(np.isfinite(gfk[vs])) and np.all(np.isfinite(gtk[ss]))
         worst.append((ef - rho * nf, et - rho * nt))
     assert all(f <= 0.0 and t <= 0.0 for f, t in worst), worst
+
+
+TIE_ROWS = (5, 37, 70, 200, 260)      # at capacity 264: lanes 5 and 37 of wavefront 0, wavefronts 1 and 3, wavefront 0's second chunk
+
+
+def _tie_case(keep):
+    """Subject (path 0) and neighbour (path 2) fly 261 rows side by side up the z axis, a dead path of NaN rows between them in
+    the same group; the gap along x is the row's clearance itself: 1 on the rows of `keep`, 2 on the other rows of TIE_ROWS,
+    2 .. 3.5 in quarters elsewhere -- every coordinate and every distance exactly representable.  Path 3 is a group of its own:
+    no neighbour, every row +inf."""
+    m = 261
+    gap = 2.0 + 0.25 * (np.arange(m) % 7)
+    gap[list(TIE_ROWS)] = 2.0
+    gap[list(keep)] = 1.0
+    subject = np.zeros((m, 4))
+    subject[:, 2] = 0.25 * np.arange(m)
+    neighbour = subject.copy()
+    neighbour[:, 0] = gap
+    lone = subject.copy()
+    lone[:, 1] = 64.0
+    dead = dict(cu.path(np.full((m, 4), np.nan)), status=0)
+    return cu.case([cu.path(subject), dead, cu.path(neighbour), cu.path(lone)], groups=[3, 1])
+
+
+@pytest.mark.parametrize("first", range(len(TIE_ROWS)))
+def test_rows_that_tie_for_the_path_minimum_give_the_lowest_row(gpu_ctx, harness, first):
+    """the same double on several rows of one path -- in one wavefront, across wavefronts, in a lane's second chunk: the lowest
+    tied row is the argmin, as in the harness"""
+    keep = TIE_ROWS[first:]
+    arr = cu.batch_arrays(_tie_case(keep))
+    assert arr["samples"].shape[1] == 264
+    got, want = _run(gpu_ctx, arr), cu.run_harness(harness, arr)
+    tied = np.flatnonzero(want["clearance"][0] == want["min_clearance"][0])
+    assert tied.tolist() == list(keep) and want["min_clearance"][0] == 1.0 and np.all(want["clearance"][0, :261] >= 1.0)
+    _same(got, want, "tie kept on rows %s" % (keep,))
+    assert cu.same_bits(got["min_clearance"], [1.0, np.inf, 1.0, np.inf])
+    assert got["argmin"].tolist() == [[keep[0], 2], [-1, -1], [keep[0], 0], [-1, -1]]

@@ -515,3 +515,40 @@ def test_chain_solve_sample_field_clearance_hinge_loss(gpu_ctx):
         assert nf > 0 and nt > 0 and np.all(np.isfinite(gfk[vs])) and np.all(np.isfinite(gtk[ss]))
         worst.append((ef - rho * nf, et - rho * nt))
     assert all(f <= 0.0 and t <= 0.0 for f, t in worst), worst
+
+
+TIE_ROWS = (5, 37, 70, 200, 260)      # at capacity 264: lanes 5 and 37 of wavefront 0, wavefronts 1 and 3, lane 4's second row
+
+
+def _tie_case(keep):
+    """A (4, 3, 2) grid of unit spacing at the origin whose field depends on x alone: 1, 1, 3, 3 on the four node planes, so it
+    is the constant 1 on the cells with i = 0, the constant 3 on those with i = 2 and 1 + 2 t between.  A path of 261 rows:
+    the rows of `keep` in the cells (0, 0, 0) and (0, 1, 0) in turn, the other rows of TIE_ROWS where the field is 3, the rest
+    at 1.25 .. 3 -- every operation of the lookup exact.  Path 1 is dead (NaN rows); path 2 names no grid: every row +inf."""
+    m = 261
+    fields = np.zeros((1, 2, 3, 4))
+    fields[...] = np.array([1.0, 1.0, 3.0, 3.0])
+    rows = np.zeros((m, 4))
+    rows[:, 0] = 1.125 + 0.125 * (np.arange(m) % 8)
+    rows[:, 1] = 0.25 + 0.0625 * (np.arange(m) % 24)
+    rows[:, 2] = 0.5
+    for k, r in enumerate(TIE_ROWS):
+        rows[r, :3] = [0.5, 0.5 + (k % 2), 0.25] if r in keep else [2.5, 0.5, 0.25]
+    dead = dict(fu.path(np.full((m, 4), np.nan)), status=0)
+    return fu.case([fu.path(rows), dead, fu.path(rows)], fields, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), path_field=[0, 0, -1])
+
+
+@pytest.mark.parametrize("first", range(len(TIE_ROWS)))
+def test_rows_that_tie_for_the_path_minimum_give_the_lowest_row(gpu_ctx, harness, first):
+    """the same double on several rows of one path -- in one wavefront, across wavefronts, in a lane's second row: the lowest
+    tied row is the argmin, as in the harness"""
+    keep = TIE_ROWS[first:]
+    arr = fu.batch_arrays(_tie_case(keep))
+    assert arr["samples"].shape[1] == 264
+    got, want = _run(gpu_ctx, arr), fu.run_harness(harness, arr)
+    tied = np.flatnonzero(want["clearance"][0] == want["min_clearance"][0])
+    assert tied.tolist() == list(keep) and want["min_clearance"][0] == 1.0 and np.all(want["clearance"][0, :261] >= 1.0)
+    _same(got, want, "tie kept on rows %s" % (keep,))
+    assert fu.same_bits(got["min_clearance"], [1.0, np.inf, np.inf])
+    cell = 4 * (TIE_ROWS.index(keep[0]) % 2)                # (0, j, 0) of grid 0 in a row of nx = 4
+    assert got["argmin"].tolist() == [[keep[0], cell], [-1, -1], [-1, -1]]

@@ -408,3 +408,38 @@ def test_chain_solve_sample_obstacle_clearance_hinge_loss(gpu_ctx):
         assert nf > 0 and nt > 0 and np.all(np.isfinite(gfk[vs])) and np.all(np.isfinite(gtk[ss]))
         worst.append((ef - rho * nf, et - rho * nt))
     assert all(f <= 0.0 and t <= 0.0 for f, t in worst), worst
+
+
+TIE_ROWS = (5, 37, 70, 200, 260)      # at capacity 264: lanes 5 and 37 of wavefront 0, wavefronts 1 and 3, lane 4's second row
+
+
+def _tie_case(keep):
+    """One point obstacle at (1, 2, 3) and a path of 261 rows around it: the rows of `keep` on the sphere of radius 4 about it
+    (on five different half-axes), the other rows of TIE_ROWS at 8, the rest at 8 .. 9.5 in quarters along x -- every coordinate
+    and every distance exactly representable.  Path 1 is dead (NaN rows, the same set); path 2 sees the empty set: every row
+    +inf."""
+    m = 261
+    centre = np.array([1.0, 2.0, 3.0])
+    rows = np.zeros((m, 4))
+    rows[:, :3] = centre
+    rows[:, 0] += 8.0 + 0.25 * (np.arange(m) % 7)
+    axes = ([4.0, 0.0, 0.0], [-4.0, 0.0, 0.0], [0.0, 4.0, 0.0], [0.0, -4.0, 0.0], [0.0, 0.0, 4.0])
+    for r, axis in zip(TIE_ROWS, axes):
+        rows[r, :3] = centre + (np.array(axis) if r in keep else [8.0, 0.0, 0.0])
+    dead = dict(ou.path(np.full((m, 4), np.nan)), status=0)
+    return ou.case([ou.path(rows), dead, ou.path(rows)], [list(centre) + [0.0]], sets=[1, 0], path_set=[0, 0, 1])
+
+
+@pytest.mark.parametrize("first", range(len(TIE_ROWS)))
+def test_rows_that_tie_for_the_path_minimum_give_the_lowest_row(gpu_ctx, harness, first):
+    """the same double on several rows of one path -- in one wavefront, across wavefronts, in a lane's second row: the lowest
+    tied row is the argmin, as in the harness"""
+    keep = TIE_ROWS[first:]
+    arr = ou.batch_arrays(_tie_case(keep))
+    assert arr["samples"].shape[1] == 264
+    got, want = _run(gpu_ctx, arr), ou.run_harness(harness, arr)
+    tied = np.flatnonzero(want["clearance"][0] == want["min_clearance"][0])
+    assert tied.tolist() == list(keep) and want["min_clearance"][0] == 4.0 and np.all(want["clearance"][0, :261] >= 4.0)
+    _same(got, want, "tie kept on rows %s" % (keep,))
+    assert ou.same_bits(got["min_clearance"], [4.0, np.inf, np.inf])
+    assert got["argmin"].tolist() == [[keep[0], 0], [-1, -1], [-1, -1]]
