@@ -232,8 +232,10 @@ enum {
   MRS_TG_CAP_FIELD_CLEARANCE = 262144,  /* mrs_tg_plan_field_clearance and mrs_tg_plan_field_clearance_vjp are exported: the
                                          trilinear interpolant of a voxel grid of signed distances at every row, its cell, the
                                          field's gradient, and the backward pass */
-  MRS_TG_CAP_FIELD_FROM_OCCUPANCY = 524288 /* mrs_tg_field_from_occupancy is exported: that grid of (signed) distances built on
+  MRS_TG_CAP_FIELD_FROM_OCCUPANCY = 524288, /* mrs_tg_field_from_occupancy is exported: that grid of (signed) distances built on
                                          the device from an occupancy grid by an exact Euclidean distance transform */
+  MRS_TG_CAP_FIELD_UPDATE_REGION = 1048576 /* mrs_tg_field_update_query and mrs_tg_field_update_region are exported: that grid
+                                         brought up to date after the occupancy changed inside a box, in the full rebuild's bits */
 };
 
 /* mrs_tg_plan_request_limits' flags_dev: what the request asks of its limits */
@@ -1323,8 +1325,8 @@ int mrs_tg_plan_field_clearance_vjp(mrs_tg_plan* plan, const double* samples_dev
  * bounds the scan, and so the cost, on a sparse map).  The origin plays no part in the values and is checked like the rest.
  * A dim may not exceed MRS_TG_FIELD_MAX_DIM (a line of the y and z passes is staged in LDS).  The passes run in place in
  * fields_out_dev: no workspace, signed or not.  No atomics; occupancy_dev is only read; every output element is written; the same input gives the same bits on every call.
- * Out of scope: the index of the nearest occupied voxel; incremental updates of a changed region; float32 fields; sub-voxel
- * surfaces; a gradient of anything (occupancy is discrete).
+ * Out of scope: the index of the nearest occupied voxel; float32 fields; sub-voxel surfaces; a gradient of anything (occupancy
+ * is discrete).  (A map that changes inside a box: mrs_tg_field_update_region, below.)
  * MRS_TG_ERR_INVALID_ARG, with the context's last error set and nothing launched: ctx or geometry NULL; occupancy_dev or
  * fields_out_dev NULL with voxels to process; a negative n_fields, a dim below 2 or above MRS_TG_FIELD_MAX_DIM, a spacing that
  * is not finite and positive, an origin that is not finite, n_fields nz ny nx above 2^31 - 1; a z_scale that is not finite and
@@ -1335,6 +1337,45 @@ int mrs_tg_plan_field_clearance_vjp(mrs_tg_plan* plan, const double* samples_dev
 #define MRS_TG_FIELD_MAX_DIM 1024
 int mrs_tg_field_from_occupancy(mrs_tg_ctx* ctx, const uint8_t* occupancy_dev, const mrs_tg_field_geometry* geometry,
                                 double z_scale, double max_distance, int32_t flags, double* fields_out_dev);
+
+/* The distance field brought up to date after the occupancy changed inside a box (MRS_TG_CAP_FIELD_UPDATE_REGION;
+ * edt_region_x_kernel, edt_region_y_kernel, edt_region_z_kernel, csrc/mrs_tg_edt_region.hpp): what a
+ * mapping stack that rewrites a small box of voxels per scan calls instead of a full rebuild.  occupancy_dev is the NEW
+ * occupancy of the whole stack, in mrs_tg_field_from_occupancy's layout; fields_inout_dev holds the field of the OLD occupancy,
+ * built with the SAME z_scale, max_distance and flags; region names one grid of the stack and the box lo .. hi (x, y, z node
+ * indices, inclusive) that holds every voxel of that grid whose byte may differ between the two (a voxel outside it that
+ * differs makes the result undefined near it; the other grids must be unchanged or are the caller's to update).  After the call
+ * fields_inout_dev holds, in every bit, what mrs_tg_field_from_occupancy gives for the new occupancy.
+ * With T = nextafter(max_distance max_distance, +inf) the REACH of axis a is the largest d >= 0 with w_a (double)(d d) < T, held
+ * to dims[a] - 1 (and equal to it with max_distance = +inf).  The CORE is the box grown by the reach on either side of every
+ * axis, clipped to the grid: the only nodes whose value can differ, and the only elements of fields_inout_dev that are written,
+ * each exactly once.  The WINDOW is the core grown by the reach once more, clipped: the only occupancy that is read.  The three
+ * passes of the full transform run on the window through workspace_dev, which holds [window nz][window ny][core nx] doubles
+ * (workspace_bytes of mrs_tg_field_update_query, 8-byte aligned, the caller's: the call stays asynchronous and allocates
+ * nothing).  When the window is the whole grid on every axis (whole_grid; always so with max_distance = +inf) the full
+ * transform runs on that one grid instead, in place: no workspace is needed (workspace_bytes = 0, workspace_dev may be NULL),
+ * and the core is reported as -- and is -- the whole grid.  Both routes are timed as kernel id 41, from first launch to last.
+ * No atomics; occupancy_dev is only read; the same input gives the same bits on every call.
+ * mrs_tg_field_update_query is host only: it needs no context, touches no device and fills *out from the geometry, z_scale,
+ * max_distance and region alone (the error text goes to the global last error, mrs_tg_last_error(NULL)).
+ * MRS_TG_ERR_INVALID_ARG, with the last error set and nothing launched: everything mrs_tg_field_from_occupancy refuses (with
+ * fields_inout_dev in the place of fields_out_dev); n_fields == 0 (there is no grid to update); region or out NULL; field
+ * outside [0, n_fields); lo > hi or an index outside the grid on any axis; when a workspace is needed, workspace_dev NULL, not
+ * 8-byte aligned, workspace_bytes below the query's, or the workspace overlapping occupancy_dev or fields_inout_dev.  Device
+ * pointers except geometry and region, asynchronous on the context's stream. */
+typedef struct mrs_tg_field_region {
+  int32_t field;        /* grid of the stack */
+  int32_t lo[3], hi[3]; /* x, y, z node indices, inclusive */
+} mrs_tg_field_region;
+typedef struct mrs_tg_field_update_info {
+  int32_t reach[3], core_lo[3], core_hi[3], window_lo[3], window_hi[3], whole_grid;
+  int64_t workspace_bytes;
+} mrs_tg_field_update_info;
+int mrs_tg_field_update_query(const mrs_tg_field_geometry* geometry, double z_scale, double max_distance,
+                              const mrs_tg_field_region* region, mrs_tg_field_update_info* out);
+int mrs_tg_field_update_region(mrs_tg_ctx* ctx, const uint8_t* occupancy_dev, const mrs_tg_field_geometry* geometry,
+                               double z_scale, double max_distance, int32_t flags, const mrs_tg_field_region* region,
+                               void* workspace_dev, int64_t workspace_bytes, double* fields_inout_dev);
 
 /* Duration in milliseconds of the most recent launch of a kernel, from the start and end time stamps of that very dispatch
  * (the events are attached to the kernel launch itself, hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports for

@@ -105,6 +105,15 @@ class _FieldGeometryStruct(C.Structure):   # mrs_tg_field_geometry (FieldGeometr
     _fields_ = [("origin", C.c_double * 3), ("spacing", C.c_double * 3), ("dims", C.c_int32 * 3), ("n_fields", C.c_int32)]
 
 
+class FieldRegion(C.Structure):   # mrs_tg_field_region: a grid of the stack and a box of its nodes, x y z, inclusive
+    _fields_ = [("field", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
+
+
+class FieldUpdateInfo(C.Structure):   # mrs_tg_field_update_info (field_update_query returns it as a dict)
+    _fields_ = [("reach", C.c_int32 * 3), ("core_lo", C.c_int32 * 3), ("core_hi", C.c_int32 * 3), ("window_lo", C.c_int32 * 3),
+                ("window_hi", C.c_int32 * 3), ("whole_grid", C.c_int32), ("workspace_bytes", C.c_int64)]
+
+
 EXPORTED_SYMBOLS = [
     "mrs_tg_create", "mrs_tg_destroy", "mrs_tg_last_error", "mrs_tg_abi_version", "mrs_tg_capabilities", "mrs_tg_default_options",
     "mrs_tg_kernel_trace_reset", "mrs_tg_kernel_trace", "mrs_tg_plan_explain",
@@ -136,7 +145,7 @@ EXPORTED_SYMBOLS = [
     "mrs_tg_plan_mutual_clearance", "mrs_tg_plan_mutual_clearance_vjp",
     "mrs_tg_plan_obstacle_clearance", "mrs_tg_plan_obstacle_clearance_vjp",
     "mrs_tg_plan_field_clearance", "mrs_tg_plan_field_clearance_vjp",
-    "mrs_tg_field_from_occupancy",
+    "mrs_tg_field_from_occupancy", "mrs_tg_field_update_query", "mrs_tg_field_update_region",
 ]
 
 _lib = None
@@ -307,6 +316,11 @@ def load_library():
     L.mrs_tg_plan_field_clearance_vjp.argtypes = [vp, dp, ip, C.c_int32, dp, gp, ip, ip, ip, dp, dp]
     L.mrs_tg_field_from_occupancy.restype = C.c_int
     L.mrs_tg_field_from_occupancy.argtypes = [vp, vp, gp, C.c_double, C.c_double, C.c_int32, dp]
+    rp = C.POINTER(FieldRegion)
+    L.mrs_tg_field_update_query.restype = C.c_int
+    L.mrs_tg_field_update_query.argtypes = [gp, C.c_double, C.c_double, rp, C.POINTER(FieldUpdateInfo)]
+    L.mrs_tg_field_update_region.restype = C.c_int
+    L.mrs_tg_field_update_region.argtypes = [vp, vp, gp, C.c_double, C.c_double, C.c_int32, rp, vp, C.c_int64, dp]
     L.mrs_tg_set_profiling.restype = C.c_int
     L.mrs_tg_set_profiling.argtypes = [vp, C.c_int]
     L.mrs_tg_last_kernel_ms.restype = C.c_int
@@ -374,7 +388,8 @@ CAP_MUTUAL_CLEARANCE = 65536   # MRS_TG_CAP_MUTUAL_CLEARANCE: Plan.mutual_cleara
 CAP_OBSTACLE_CLEARANCE = 131072   # MRS_TG_CAP_OBSTACLE_CLEARANCE: Plan.obstacle_clearance (the nearest sphere or point of the path's obstacle set, signed), Plan.obstacle_clearance_vjp
 CAP_FIELD_CLEARANCE = 262144   # MRS_TG_CAP_FIELD_CLEARANCE: Plan.field_clearance (the trilinear interpolant of a voxel grid of signed distances, its cell and gradient), Plan.field_clearance_vjp
 CAP_FIELD_FROM_OCCUPANCY = 524288   # MRS_TG_CAP_FIELD_FROM_OCCUPANCY: Context.field_from_occupancy (that grid built on the device from an occupancy grid, an exact Euclidean distance transform)
-FIELD_SIGNED, FIELD_MAX_DIM = 1, 1024   # MRS_TG_FIELD_SIGNED (mrs_tg_field_from_occupancy's flag), MRS_TG_FIELD_MAX_DIM (its largest dim)
+CAP_FIELD_UPDATE_REGION = 1048576   # MRS_TG_CAP_FIELD_UPDATE_REGION: field_update_query, Context.field_update_region (that grid brought up to date after the occupancy changed inside a box)
+FIELD_SIGNED, FIELD_MAX_DIM = 1, 1024  # MRS_TG_FIELD_SIGNED (mrs_tg_field_from_occupancy's flag), MRS_TG_FIELD_MAX_DIM (its largest dim)
 # Plan.request_limits' flags input (MRS_TG_REQ_*) and its branch word (MRS_TG_LIM_*)
 REQ_OVERRIDE, REQ_RELAX_HEADING = 1, 2
 LIM_OVERRIDDEN, LIM_OVERRIDE_REFUSED, LIM_RELAXED, LIM_V_DESCENDING, LIM_A_DESCENDING, LIM_J_DESCENDING, LIM_FALLBACK = 1, 2, 4, 8, 16, 32, 64
@@ -662,6 +677,78 @@ def check_occupancy_operands(occupancy, geometry, z_scale, max_distance, out=Non
         raise ValueError("occupancy must be on the context's device %d, not %s" % (device, occupancy.device))
 
 
+def _check_region(geometry, lo, hi, field):
+    """the box lo .. hi (x, y, z node indices, inclusive) of grid `field` of a checked geometry as a FieldRegion, or ValueError"""
+    if geometry.n_fields == 0:
+        raise ValueError("n_fields is 0: there is no grid to update")
+    try:
+        lo, hi, field = tuple(int(x) for x in lo), tuple(int(x) for x in hi), int(field)
+    except (TypeError, ValueError):
+        raise ValueError("lo and hi are three node indices each (x, y, z) and field is an integer")
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("lo and hi have three entries each: x, y, z")
+    if not 0 <= field < geometry.n_fields:
+        raise ValueError("field %d is outside [0, %d)" % (field, geometry.n_fields))
+    for a in range(3):
+        if not 0 <= lo[a] <= hi[a] < geometry.dims[a]:
+            raise ValueError("axis %d of the box: [%d, %d] is empty or not inside [0, %d]" % (a, lo[a], hi[a], geometry.dims[a] - 1))
+    r = FieldRegion()
+    r.field, r.lo[:], r.hi[:] = field, lo, hi
+    return r
+
+
+def field_update_query(geometry, lo, hi, field=0, z_scale=1.0, max_distance=float("inf")):
+    """mrs_tg_field_update_query: what Context.field_update_region does for a change of the occupancy inside the box lo .. hi (x,
+    y, z node indices, inclusive) of grid `field`, as a dict: reach [3] (how many nodes a voxel is felt along each axis under the
+    cap max_distance), core_lo / core_hi (the nodes that are recomputed and written: the box grown by the reach, clipped),
+    window_lo / window_hi (the occupancy that is read: the core grown by the reach, clipped), whole_grid (the window is the whole
+    grid -- always with max_distance = inf: the full transform runs on that grid, the core is the whole grid) and
+    workspace_bytes (0 with whole_grid).  Host only: no context, no device.  ValueError for a geometry, scalar or box the library
+    would refuse."""
+    if not isinstance(geometry, FieldGeometry):
+        raise ValueError("geometry must be an api.FieldGeometry")
+    check_field_geometry(geometry.fields_shape(), geometry)
+    if any(n > FIELD_MAX_DIM for n in geometry.dims):
+        raise ValueError("every dim of an occupancy grid is at most %d, not %r" % (FIELD_MAX_DIM, geometry.dims))
+    if not (np.isfinite(z_scale) and z_scale > 0.0):
+        raise ValueError("z_scale must be finite and positive, not %r" % (z_scale,))
+    if not max_distance > 0.0:
+        raise ValueError("max_distance must be positive (inf: no cap), not %r" % (max_distance,))
+    region = _check_region(geometry, lo, hi, field)
+    L = load_library()
+    g, info = geometry.as_struct(), FieldUpdateInfo()
+    rc = L.mrs_tg_field_update_query(C.byref(g), float(z_scale), float(max_distance), C.byref(region), C.byref(info))
+    if rc != 0:
+        raise MrsTgError("mrs_tg_field_update_query failed (%d): %s" % (rc, L.mrs_tg_last_error(None).decode()))
+    out = {k: list(getattr(info, k)) for k in ("reach", "core_lo", "core_hi", "window_lo", "window_hi")}
+    out["whole_grid"], out["workspace_bytes"] = int(info.whole_grid), int(info.workspace_bytes)
+    return out
+
+
+def check_region_operands(occupancy, fields, geometry, lo, hi, field=0, z_scale=1.0, max_distance=float("inf"), workspace=None,
+                          device=None):
+    """What Context.field_update_region checks before anything reaches the library, or ValueError; no device is needed to be
+    refused.  Everything check_occupancy_operands checks, with fields (required) in the place of out; the box as
+    field_update_query takes it; workspace None or a contiguous float64 tensor on occupancy's device that holds at least the
+    query's workspace_bytes and shares no memory with occupancy or fields.  Returns (the FieldRegion, the query's dict)."""
+    import torch
+    if fields is None:
+        raise ValueError("fields is required: the field of the old occupancy, updated in place")
+    check_occupancy_operands(occupancy, geometry, z_scale, max_distance, None, device)
+    _check_operand("fields", fields, torch.float64, geometry.fields_shape(), occupancy)
+    region = _check_region(geometry, lo, hi, field)
+    info = field_update_query(geometry, lo, hi, field, z_scale, max_distance)
+    if workspace is not None:
+        _check_operand("workspace", workspace, torch.float64, (None,), occupancy)
+        if workspace.numel() * 8 < info["workspace_bytes"]:
+            raise ValueError("workspace holds %d bytes, the update needs %d" % (workspace.numel() * 8, info["workspace_bytes"]))
+        for name, t in (("occupancy", occupancy), ("fields", fields)):
+            a, b = workspace.data_ptr(), t.data_ptr()
+            if a < b + t.numel() * t.element_size() and b < a + workspace.numel() * 8:
+                raise ValueError("workspace overlaps %s" % name)
+    return region, info
+
+
 class Context:
     """One HIP device + stream (mrs_tg_ctx)."""
 
@@ -733,6 +820,28 @@ class Context:
                                                         FIELD_SIGNED if signed else 0, _t_ptr(out)),
                     "mrs_tg_field_from_occupancy")
         return out
+
+    def field_update_region(self, occupancy, fields, geometry, lo, hi, field=0, z_scale=1.0, max_distance=float("inf"), signed=True,
+                            workspace=None):
+        """mrs_tg_field_update_region: the field of field_from_occupancy brought up to date after the occupancy changed inside
+        a box.  occupancy is the NEW occupancy of the whole stack; fields holds the field of the OLD one, built with the same
+        z_scale, max_distance and signed; lo .. hi (x, y, z node indices, inclusive) holds every voxel of grid `field` whose
+        byte may differ.  Updates fields IN PLACE and returns it: afterwards it is field_from_occupancy(occupancy, ...) in every
+        bit, and only the nodes of the core (field_update_query) were written.  workspace: a float64 tensor of at least the
+        query's workspace_bytes, or None -- then one is allocated here (a caller in a loop passes its own).  With
+        max_distance = inf, or a box whose window is the whole grid, the full transform runs on that grid (DESIGN.md section
+        11m).  No autograd entry.  Asynchronous on the context's stream; occupancy is never written."""
+        import torch
+        region, info = check_region_operands(occupancy, fields, geometry, lo, hi, field, z_scale, max_distance, workspace, self.device)
+        if workspace is None and info["workspace_bytes"] > 0:
+            workspace = torch.empty((info["workspace_bytes"] // 8,), dtype=torch.float64, device=occupancy.device)
+        g = geometry.as_struct()
+        self._check(self._L.mrs_tg_field_update_region(self._h, _t_ptr(occupancy), C.byref(g), float(z_scale), float(max_distance),
+                                                       FIELD_SIGNED if signed else 0, C.byref(region),
+                                                       None if workspace is None else _t_ptr(workspace),
+                                                       0 if workspace is None else workspace.numel() * 8, _t_ptr(fields)),
+                    "mrs_tg_field_update_region")
+        return fields
 
     def solve_batch(self, batch: Batch, seg_times=None, out=None, **opts):
         """Host arrays in, host arrays out (mrs_tg_solve_batch).  seg_times None => estimate_times.

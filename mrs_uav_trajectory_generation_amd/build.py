@@ -16,7 +16,8 @@ LIB = os.path.join(HERE, "libmrs_tg.so")
 SOURCES = ["mrs_tg_kernels.hip", "mrs_tg_tile.hip", "mrs_tg_rows.hip", "mrs_tg_quad.hip", "mrs_tg_general.hip", "mrs_tg_nonlinear.hip", "mrs_tg_wave.hip", "mrs_tg_dfo.hip", "mrs_tg_abi.hip", "mrs_tg_multi.hip", "mrs_tg_policy.hip", "mrs_tg_policy_dev.hip",
            "mrs_tg_pool.hip", "mrs_tg_refine.hip", "mrs_tg_vjp.hip", "mrs_tg_maxima_vjp.hip", "mrs_tg_sample_vjp.hip", "mrs_tg_evaluate.hip", "mrs_tg_deviation.hip",
            "mrs_tg_estimate_vjp.hip", "mrs_tg_passage.hip", "mrs_tg_baca.hip", "mrs_tg_fallback.hip", "mrs_tg_pathedit.hip", "mrs_tg_heading.hip",
-           "mrs_tg_initial.hip", "mrs_tg_request.hip", "mrs_tg_clearance.hip", "mrs_tg_obstacle.hip", "mrs_tg_field.hip", "mrs_tg_edt.hip"]
+           "mrs_tg_initial.hip", "mrs_tg_request.hip", "mrs_tg_clearance.hip", "mrs_tg_obstacle.hip", "mrs_tg_field.hip", "mrs_tg_edt.hip",
+           "mrs_tg_edt_region.hip"]
 # every header under csrc/ (a header that is split or added is picked up without editing this file) + the public ABI
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + \
     [os.path.join("..", "..", "include", h) for h in ("mrs_tg.h", "mrs_tg_initial_condition.hpp")]

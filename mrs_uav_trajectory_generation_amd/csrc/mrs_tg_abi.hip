@@ -24,6 +24,7 @@
 
 #include "../../include/mrs_tg.h"
 #include "mrs_tg_edt.hpp"
+#include "mrs_tg_edt_region.hpp"
 #include "mrs_tg_fallback.hpp"
 #include "mrs_tg_field.hpp"
 #include "mrs_tg_pathedit.hpp"
@@ -200,7 +201,7 @@ int mrs_tg_capabilities(void) {
          MRS_TG_CAP_ESTIMATE_GRADIENT | MRS_TG_CAP_WAYPOINT_PASSAGE | MRS_TG_CAP_BACA | MRS_TG_CAP_FALLBACK_SAMPLE |
          MRS_TG_CAP_PATH_EDIT | MRS_TG_CAP_TRAVEL_HEADING | MRS_TG_CAP_INITIAL_CONDITION | MRS_TG_CAP_REQUEST |
          MRS_TG_CAP_MUTUAL_CLEARANCE | MRS_TG_CAP_OBSTACLE_CLEARANCE | MRS_TG_CAP_FIELD_CLEARANCE |
-         MRS_TG_CAP_FIELD_FROM_OCCUPANCY;
+         MRS_TG_CAP_FIELD_FROM_OCCUPANCY | MRS_TG_CAP_FIELD_UPDATE_REGION;
 }
 
 // prepareInitialCondition (:506-614) + the first-waypoint rule (:650-655): mrs_tg_initial_condition.hpp, host arithmetic
@@ -1820,26 +1821,41 @@ int mrs_tg_plan_field_clearance_vjp(mrs_tg_plan* plan, const double* samples, co
 
 // ---- the distance field from an occupancy grid (mrs_tg_edt.hip) -----------------------------------------------------------------------
 
-int mrs_tg_field_from_occupancy(mrs_tg_ctx* ctx, const uint8_t* occupancy, const mrs_tg_field_geometry* geometry, double z_scale,
-                                double max_distance, int32_t flags, double* fields_out) {
+// what mrs_tg_field_from_occupancy and mrs_tg_field_update_region refuse in the geometry and the scalars (geometry not NULL);
+// ctx may be NULL (mrs_tg_field_update_query).  The number of voxels of the whole stack
+static int occupancy_scalars(mrs_tg_ctx* ctx, const mrs_tg_field_geometry* geometry, double z_scale, double max_distance,
+                             long long* voxels_out) {
   static_assert(MRS_TG_FIELD_SIGNED == mrs_tg::edtq::kSigned && MRS_TG_FIELD_MAX_DIM == mrs_tg::edtq::kMaxDim, "the header's");
-  if (!ctx) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "ctx is NULL");
-  if (!geometry) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "geometry is NULL");
-  long long voxels = 0;
-  if (const int rc = field_geometry_voxels(ctx, geometry, &voxels); rc != MRS_TG_OK) return rc;
+  if (const int rc = field_geometry_voxels(ctx, geometry, voxels_out); rc != MRS_TG_OK) return rc;
   for (int a = 0; a < 3; ++a)
     if (geometry->dims[a] > MRS_TG_FIELD_MAX_DIM)
       return fail(ctx, MRS_TG_ERR_INVALID_ARG, "dims[%d] = %d exceeds MRS_TG_FIELD_MAX_DIM = %d (a line is staged in LDS)", a,
                   geometry->dims[a], MRS_TG_FIELD_MAX_DIM);
   if (!(std::isfinite(z_scale) && z_scale > 0.0)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "z_scale must be finite and positive");
   if (!(max_distance > 0.0)) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "max_distance must be positive (+inf: no cap)");
+  return MRS_TG_OK;
+}
+
+// ... and in the flags and the two arrays of the stack; `fields_name` is the header's name of the array of doubles
+static int occupancy_arrays(mrs_tg_ctx* ctx, long long voxels, int32_t flags, const uint8_t* occupancy, const double* fields,
+                            const char* fields_name) {
   if ((flags & ~MRS_TG_FIELD_SIGNED) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "unknown flag bits 0x%x", (unsigned)flags);
-  if (voxels > 0 && (!occupancy || !fields_out))
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "occupancy_dev and fields_out_dev are required with %lld voxels", voxels);
-  if (((uintptr_t)fields_out & 7u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "fields_out_dev is not 8-byte aligned");
-  const uintptr_t out_lo = (uintptr_t)fields_out, out_hi = out_lo + (size_t)voxels * sizeof(double);
+  if (voxels > 0 && (!occupancy || !fields))
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "occupancy_dev and %s are required with %lld voxels", fields_name, voxels);
+  if (((uintptr_t)fields & 7u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "%s is not 8-byte aligned", fields_name);
+  const uintptr_t out_lo = (uintptr_t)fields, out_hi = out_lo + (size_t)voxels * sizeof(double);
   if (voxels > 0 && (uintptr_t)occupancy < out_hi && out_lo < (uintptr_t)occupancy + (size_t)voxels)
-    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "fields_out_dev overlaps occupancy_dev");
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "%s overlaps occupancy_dev", fields_name);
+  return MRS_TG_OK;
+}
+
+int mrs_tg_field_from_occupancy(mrs_tg_ctx* ctx, const uint8_t* occupancy, const mrs_tg_field_geometry* geometry, double z_scale,
+                                double max_distance, int32_t flags, double* fields_out) {
+  if (!ctx) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "ctx is NULL");
+  if (!geometry) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "geometry is NULL");
+  long long voxels = 0;
+  if (const int rc = occupancy_scalars(ctx, geometry, z_scale, max_distance, &voxels); rc != MRS_TG_OK) return rc;
+  if (const int rc = occupancy_arrays(ctx, voxels, flags, occupancy, fields_out, "fields_out_dev"); rc != MRS_TG_OK) return rc;
   if (voxels == 0) return MRS_TG_OK;
   const bool is_signed = (flags & MRS_TG_FIELD_SIGNED) != 0;
   const double h[3] = {geometry->spacing[0], geometry->spacing[1], geometry->spacing[2]};
@@ -1849,6 +1865,79 @@ int mrs_tg_field_from_occupancy(mrs_tg_ctx* ctx, const uint8_t* occupancy, const
   ProfileScope ps(ctx, 41);
   HIP_TRY(ctx, mrs_tg::launch_field_from_occupancy(occupancy, dims, geometry->n_fields, W, mrs_tg::edtq::saturation(max_distance),
                                                    max_distance, is_signed, fields_out, ctx->stream));
+  return MRS_TG_OK;
+}
+
+// ---- the distance field brought up to date after a change inside a box (mrs_tg_edt_region.hip) ------------------------------------------
+
+// the plan of a region of a checked geometry (occupancy_scalars), or what is wrong with the region
+static int field_region_plan(mrs_tg_ctx* ctx, const mrs_tg_field_geometry* geometry, double z_scale, double max_distance,
+                             const mrs_tg_field_region* region, mrs_tg::edtq::RegionPlan* plan_out) {
+  if (geometry->n_fields == 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "n_fields is 0: there is no grid to update");
+  if (!region) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "region is NULL");
+  if (region->field < 0 || region->field >= geometry->n_fields)
+    return fail(ctx, MRS_TG_ERR_INVALID_ARG, "region.field = %d is outside [0, %d)", region->field, geometry->n_fields);
+  for (int a = 0; a < 3; ++a)
+    if (region->lo[a] < 0 || region->hi[a] >= geometry->dims[a] || region->lo[a] > region->hi[a])
+      return fail(ctx, MRS_TG_ERR_INVALID_ARG, "region axis %d: [%d, %d] is empty or not inside [0, %d]", a, region->lo[a],
+                  region->hi[a], geometry->dims[a] - 1);
+  const double h[3] = {geometry->spacing[0], geometry->spacing[1], geometry->spacing[2]};
+  const int dims[3] = {geometry->dims[0], geometry->dims[1], geometry->dims[2]};
+  const int lo[3] = {region->lo[0], region->lo[1], region->lo[2]}, hi[3] = {region->hi[0], region->hi[1], region->hi[2]};
+  *plan_out = mrs_tg::edtq::plan_region(dims, mrs_tg::edtq::weights(h, z_scale), mrs_tg::edtq::saturation(max_distance), lo, hi);
+  return MRS_TG_OK;
+}
+
+int mrs_tg_field_update_query(const mrs_tg_field_geometry* geometry, double z_scale, double max_distance,
+                              const mrs_tg_field_region* region, mrs_tg_field_update_info* out) {
+  if (!geometry) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "geometry is NULL");
+  if (!out) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "out is NULL");
+  long long voxels = 0;
+  if (const int rc = occupancy_scalars(nullptr, geometry, z_scale, max_distance, &voxels); rc != MRS_TG_OK) return rc;
+  mrs_tg::edtq::RegionPlan P;
+  if (const int rc = field_region_plan(nullptr, geometry, z_scale, max_distance, region, &P); rc != MRS_TG_OK) return rc;
+  for (int a = 0; a < 3; ++a) {
+    out->reach[a] = P.reach[a];
+    out->core_lo[a] = P.core_lo[a], out->core_hi[a] = P.core_hi[a];
+    out->window_lo[a] = P.window_lo[a], out->window_hi[a] = P.window_hi[a];
+  }
+  out->whole_grid = P.whole_grid;
+  out->workspace_bytes = (int64_t)P.workspace_doubles * (int64_t)sizeof(double);
+  return MRS_TG_OK;
+}
+
+int mrs_tg_field_update_region(mrs_tg_ctx* ctx, const uint8_t* occupancy, const mrs_tg_field_geometry* geometry, double z_scale,
+                               double max_distance, int32_t flags, const mrs_tg_field_region* region, void* workspace,
+                               int64_t workspace_bytes, double* fields_inout) {
+  if (!ctx) return fail(nullptr, MRS_TG_ERR_INVALID_ARG, "ctx is NULL");
+  if (!geometry) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "geometry is NULL");
+  long long voxels = 0;
+  if (const int rc = occupancy_scalars(ctx, geometry, z_scale, max_distance, &voxels); rc != MRS_TG_OK) return rc;
+  mrs_tg::edtq::RegionPlan P;
+  if (const int rc = field_region_plan(ctx, geometry, z_scale, max_distance, region, &P); rc != MRS_TG_OK) return rc;
+  if (const int rc = occupancy_arrays(ctx, voxels, flags, occupancy, fields_inout, "fields_inout_dev"); rc != MRS_TG_OK) return rc;
+  if (!P.whole_grid) {
+    const int64_t need = (int64_t)P.workspace_doubles * (int64_t)sizeof(double);
+    if (!workspace) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "workspace_dev is NULL and %lld bytes are needed", (long long)need);
+    if (((uintptr_t)workspace & 7u) != 0) return fail(ctx, MRS_TG_ERR_INVALID_ARG, "workspace_dev is not 8-byte aligned");
+    if (workspace_bytes < need)
+      return fail(ctx, MRS_TG_ERR_INVALID_ARG, "workspace_bytes = %lld is below the %lld bytes mrs_tg_field_update_query reports",
+                  (long long)workspace_bytes, (long long)need);
+    // (the bytes the kernels touch: `need` of them, whatever the caller's buffer holds beyond)
+    const uintptr_t ws_lo = (uintptr_t)workspace, ws_hi = ws_lo + (size_t)need;
+    if ((uintptr_t)occupancy < ws_hi && ws_lo < (uintptr_t)occupancy + (size_t)voxels)
+      return fail(ctx, MRS_TG_ERR_INVALID_ARG, "workspace_dev overlaps occupancy_dev");
+    if ((uintptr_t)fields_inout < ws_hi && ws_lo < (uintptr_t)fields_inout + (size_t)voxels * sizeof(double))
+      return fail(ctx, MRS_TG_ERR_INVALID_ARG, "workspace_dev overlaps fields_inout_dev");
+  }
+  const bool is_signed = (flags & MRS_TG_FIELD_SIGNED) != 0;
+  const double h[3] = {geometry->spacing[0], geometry->spacing[1], geometry->spacing[2]};
+  const int dims[3] = {geometry->dims[0], geometry->dims[1], geometry->dims[2]};
+  HIP_TRY(ctx, use_device(ctx->device));
+  ProfileScope ps(ctx, 41);
+  HIP_TRY(ctx, mrs_tg::launch_field_update_region(occupancy, dims, region->field, P, mrs_tg::edtq::weights(h, z_scale),
+                                                  mrs_tg::edtq::saturation(max_distance), max_distance, is_signed,
+                                                  (double*)workspace, fields_inout, ctx->stream));
   return MRS_TG_OK;
 }
 

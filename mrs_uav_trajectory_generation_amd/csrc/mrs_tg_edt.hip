@@ -24,12 +24,8 @@
 // index is formed only from i < nx, l < n and a line or tile index below its count, so every address lies in [0, voxels).
 #include <hip/hip_runtime.h>
 
-#include "mrs_tg_edt.hpp"
+#include "mrs_tg_edt_dev.hpp"
 #include "mrs_tg_launch.h"
-
-#ifndef MRS_TG_EDT_THREADS
-#define MRS_TG_EDT_THREADS 512  // of a workgroup of the y and z passes (an experiment build may say 256 or 1024)
-#endif
 
 namespace mrs_tg {
 
@@ -37,8 +33,6 @@ namespace {
 
 constexpr int kEdtXWaves = 4;                  // lines a workgroup of the x pass takes at a time
 constexpr int kEdtXThreads = 64 * kEdtXWaves;
-constexpr int kEdtThreads = MRS_TG_EDT_THREADS;
-constexpr long long kEdtBlocks = 1 << 20;      // workgroups of a launch at the most
 
 }  // namespace
 
@@ -46,29 +40,9 @@ struct EdtGrid {
   int nx, ny, nz, n_fields;
 };
 
-// the staged tile of one workgroup: n rows of tx columns at base + l stride + c, c < width
-struct Tile {
-  size_t base, stride;
-  int n, tx_log2, width;
-};
+// (Tile, stage_tile, scan_tile, tile_node: mrs_tg_edt_dev.hpp, shared with the update of a changed box)
 
 namespace {
-
-__device__ inline void stage_tile(const double* D, const Tile& T, double* __restrict__ s_tile) {
-  const int total = T.n << T.tx_log2, mask = (1 << T.tx_log2) - 1;
-  for (int e = threadIdx.x; e < total; e += kEdtThreads) {
-    const int l = e >> T.tx_log2, c = e & mask;
-    if (c < T.width) s_tile[e] = D[T.base + (size_t)l * T.stride + (size_t)c];
-  }
-}
-
-// the scan of node (l, c) of the staged tile as a node of the class `occupied`: a node of its own class shows its partial
-// distance, a node of the other class is a source at 0 (edtq::seen_by)
-__device__ inline double scan_tile(const double* __restrict__ s_tile, const Tile& T, int l, int c, bool occupied, double w,
-                                   double limit) {
-  const int shift = T.tx_log2;
-  return edtq::scan_line([&](int p) { return edtq::seen_by(s_tile[(p << shift) + c], occupied); }, T.n, l, w, limit);
-}
 
 // One pass along y (Last = false) or z (Last = true) over the tiles of this workgroup, in place.  An occupied node of an
 // unsigned field keeps its -0.0 through the y pass and becomes 0.0 in the last.
@@ -96,14 +70,7 @@ __device__ inline void axis_pass(double* fields, const EdtGrid& G, int tx_log2, 
       const int l = e >> tx_log2, c = e & (tx - 1);
       if (c < T.width) {
         const size_t at = T.base + (size_t)l * T.stride + (size_t)c;
-        const bool occupied = edtq::packed_occupied(s_tile[e]);
-        if (occupied && !is_signed) {
-          if (Last) fields[at] = 0.0;
-        } else {
-          const double d = scan_tile(s_tile, T, l, c, occupied, w, limit);
-          fields[at] = !Last ? edtq::packed(d, occupied)
-                             : (occupied ? edtq::occupied_value(d, max_distance) : edtq::free_value(d, max_distance));
-        }
+        tile_node<Last>(&fields[at], s_tile, T, l, c, e, w, limit, max_distance, is_signed);
       }
     }
     __syncthreads();  // (the tile is read until here)
@@ -167,18 +134,6 @@ __global__ __launch_bounds__(kEdtThreads) void edt_z_kernel(double* __restrict__
   axis_pass<true>(fields, G, tx_log2, tiles_x, tiles, wz, limit, max_distance, is_signed != 0, s_tile);
 }
 
-namespace {
-
-int log2_of(int power_of_two) {
-  int s = 0;
-  while ((1 << s) < power_of_two) ++s;
-  return s;
-}
-
-unsigned blocks_for(long long items) { return (unsigned)(items < kEdtBlocks ? items : kEdtBlocks); }
-
-}  // namespace
-
 hipError_t launch_field_from_occupancy(const uint8_t* occupancy, const int (&dims)[3], int n_fields, const edtq::Weights& W,
                                        double limit, double max_distance, bool is_signed, double* fields, hipStream_t stream) {
   const KernelTimer kt = take_kernel_timer();  // the family: edt_x_kernel's start to edt_z_kernel's end
@@ -186,7 +141,7 @@ hipError_t launch_field_from_occupancy(const uint8_t* occupancy, const int (&dim
   const EdtGrid G{dims[0], dims[1], dims[2], n_fields};
   const int sign = is_signed ? 1 : 0;
   const long long lines = (long long)n_fields * G.nz * G.ny;
-  MRS_TG_LAUNCH_EXT(edt_x_kernel, dim3(blocks_for((lines + kEdtXWaves - 1) / kEdtXWaves)), dim3(kEdtXThreads), 0, stream, kt.start,
+  MRS_TG_LAUNCH_EXT(edt_x_kernel, dim3(edt_blocks_for((lines + kEdtXWaves - 1) / kEdtXWaves)), dim3(kEdtXThreads), 0, stream, kt.start,
                     nullptr, 0, occupancy, G.nx, lines, W.w[0], sign, fields);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   {
@@ -194,16 +149,16 @@ hipError_t launch_field_from_occupancy(const uint8_t* occupancy, const int (&dim
     const long long tiles = (long long)n_fields * G.nz * tiles_x;
     const size_t lds = (size_t)G.ny * (size_t)tx * sizeof(double);
     if (hipError_t e = prepare_dynamic_lds(MRS_TG_KERNEL(edt_y_kernel), lds); e != hipSuccess) return e;
-    MRS_TG_LAUNCH_EXT(edt_y_kernel, dim3(blocks_for(tiles)), dim3(kEdtThreads), lds, stream, nullptr, nullptr, 0, fields, G,
-                      log2_of(tx), tiles_x, tiles, W.w[1], limit, sign);
+    MRS_TG_LAUNCH_EXT(edt_y_kernel, dim3(edt_blocks_for(tiles)), dim3(kEdtThreads), lds, stream, nullptr, nullptr, 0, fields, G,
+                      edt_log2_of(tx), tiles_x, tiles, W.w[1], limit, sign);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   }
   const int tx = edtq::tile_width(G.nz, G.nx), tiles_x = (G.nx + tx - 1) / tx;
   const long long tiles = (long long)n_fields * G.ny * tiles_x;
   const size_t lds = (size_t)G.nz * (size_t)tx * sizeof(double);
   if (hipError_t e = prepare_dynamic_lds(MRS_TG_KERNEL(edt_z_kernel), lds); e != hipSuccess) return e;
-  MRS_TG_LAUNCH_EXT(edt_z_kernel, dim3(blocks_for(tiles)), dim3(kEdtThreads), lds, stream, nullptr, kt.stop, 0, fields, G,
-                    log2_of(tx), tiles_x, tiles, W.w[2], limit, max_distance, sign);
+  MRS_TG_LAUNCH_EXT(edt_z_kernel, dim3(edt_blocks_for(tiles)), dim3(kEdtThreads), lds, stream, nullptr, kt.stop, 0, fields, G,
+                    edt_log2_of(tx), tiles_x, tiles, W.w[2], limit, max_distance, sign);
   return hipGetLastError();
 }
 

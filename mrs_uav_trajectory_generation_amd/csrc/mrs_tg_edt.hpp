@@ -55,8 +55,9 @@
 // A staged line limits a dim: kMaxDim per axis (the ABI refuses larger dims before any launch).
 //
 // Out of scope.  The INDEX of the nearest occupied voxel: a tie rule on the rounded total is not separable (two different
-// partial sums can round to the same total).  Incremental updates of a changed region.  float32 fields.  Sub-voxel surfaces
-// (half-voxel offsets: the distance is between nodes).  A gradient of anything: occupancy is discrete.
+// partial sums can round to the same total).  float32 fields.  Sub-voxel surfaces (half-voxel offsets: the distance is between
+// nodes).  A gradient of anything: occupancy is discrete.  (A map that changes inside a box: mrs_tg_edt_region.hpp brings the
+// field up to date on these routines.)
 #pragma once
 
 #include "mrs_tg_hd.hpp"

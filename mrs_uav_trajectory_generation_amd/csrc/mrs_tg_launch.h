@@ -24,7 +24,8 @@ namespace fldq {
 struct Geometry;  // mrs_tg_field.hpp
 }
 namespace edtq {
-struct Weights;  // mrs_tg_edt.hpp
+struct Weights;     // mrs_tg_edt.hpp
+struct RegionPlan;  // mrs_tg_edt_region.hpp
 }
 
 // Per-dispatch timing (mrs_tg_set_profiling): the next launch of the kernel family a ProfileScope names carries these
@@ -398,6 +399,14 @@ hipError_t launch_field_clearance_vjp(int n_paths, const double* samples, const 
 // kernel family of the pending ProfileScope
 hipError_t launch_field_from_occupancy(const uint8_t* occupancy, const int (&dims)[3], int n_fields, const edtq::Weights& W,
                                        double limit, double max_distance, bool is_signed, double* fields, hipStream_t stream);
+// mrs_tg_field_update_region (mrs_tg_edt_region.hip, mrs_tg_edt_region.hpp): fields holds the field of an earlier occupancy that
+// differs from `occupancy` inside the box `plan` was made for (edtq::plan_region) on grid `field` of the stack alone; brings the
+// core of the plan up to date, in the full rebuild's bits, and writes no other element.  Three launches (edt_region_x_kernel,
+// edt_region_y_kernel, edt_region_z_kernel) through workspace (plan.workspace_doubles doubles, overlapping nothing), or, with
+// plan.whole_grid, launch_field_from_occupancy on that one grid without a workspace; timed like it, under the same ProfileScope
+hipError_t launch_field_update_region(const uint8_t* occupancy, const int (&dims)[3], int field, const edtq::RegionPlan& plan,
+                                      const edtq::Weights& W, double limit, double max_distance, bool is_signed, double* workspace,
+                                      double* fields, hipStream_t stream);
 // What the rows kernel can do around its solve for the same path, in the same launch:
 //   before: the feasibility scaling of the segment times (scaleSegmentTimesWithViolation's T_i <- s_i T_i from the
 //           per-segment maxima, written back to seg_times) -- the last stage before the final solve of the Mellinger pipeline;
